@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s (ray·bounces = closest-hit segments per second) of the per-pixel sample loop on MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W [--workload cfg3|cfg2|cfg5]
+  python bench.py --gpus 1 --steps K --warmup W [--workload cfg3|cfg2|cfg5] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one full frame of the workload (every pixel, every sample, all bounces).  Default workload = cfg3 of
@@ -156,10 +156,15 @@ def main():
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (invalidates the headline number)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-src-sha", action="store_true", help="print the source hash profiles/*_traffic.json are keyed by, and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the frame the last step computed to DIR/radiance.npy")
     args = ap.parse_args()
     if args.kernel_src_sha:
         print(kernel_src_sha())
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and os.environ.get("ZR_BENCH_SHARD_OF"):
+        ap.error("--dump-outputs needs the whole frame: ZR_BENCH_SHARD_OF renders one rank's tiles only")
 
     if args.gpus > 1 and "RANK" not in os.environ:   # started plainly, like the N = 1 case: be our own launcher
         self_launch(args.gpus)
@@ -206,6 +211,8 @@ def main():
     stats = sc.stats()
 
     H, W = cam.image_height, cam.image_width
+    if args.dump_outputs and H * W * 3 * 8 > 64 * 10**6:
+        raise SystemExit(f"--dump-outputs: the {W}x{H} float64 frame is over the 64 MB the dump may hold")
     acc = torch.zeros((H, W, 3), dtype=torch.float64, device=dev)
     region = multi.tile_region(capi, rank, world)
     if os.environ.get("ZR_BENCH_SHARD_OF"):  # development aid: time one rank's share of an N-way sharded frame on one GPU
@@ -254,6 +261,13 @@ def main():
     path = int(getattr(ctr, "path", 2 if variant == 2 else 0))   # which kernels rendered the frame (zr_counters::path)
     kernel_name = {0: "render_pixels", 2: "stream_extend", 3: "fused_render"}.get(path, "render_pixels")
 
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        # the frame a caller of the timed path receives: the per-pixel mean radiance, (H, W, 3) float64, whole (cfg3's 1920x1080 is 49.8 MB).
+        # Every input is fixed by the workload (compiled scene, camera, seed), so two builds can be compared output for output
+        frame = acc.cpu().numpy()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "radiance.npy"), frame)
     if rank == 0:
         ms_step = dt / args.steps * 1e3
         value = segments * args.steps / dt * 1e-6

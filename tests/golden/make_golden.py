@@ -219,10 +219,10 @@ def make_refdemo(tmp):
     unchanged against the drop-in) dumps every array of the zr_scene_desc it flattens to (decoded texels included), oracle/_ref/zenith_ref (the same scene
     code against the reference's own headers) renders the full frame at 8 spp and two tiles at the scene's 16 spp.  tests/test_refdemo_gpu.py commits the
     arrays through the C ABI and compares."""
-    from refdemo_assets import asset_dir
+    from refdemo_assets import REF as REF_TREE, asset_dir
     dropin = os.path.join(ROOT, "oracle", "_ref", "refscene_dropin")
     os.makedirs(os.path.join(tmp, "refdemo_cwd"))
-    cwd = asset_dir(os.path.join(tmp, "refdemo_cwd"))
+    cwd = asset_dir(os.path.join(tmp, "refdemo_cwd"), ref=REF_TREE)
     pre = os.path.join(tmp, "refdemo_d")
     p = subprocess.run([dropin, "dump", pre], cwd=cwd, capture_output=True, text=True, check=True)
     meta = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -311,6 +311,8 @@ def main():
             np.savez_compressed(os.path.join(HERE, name + ".npz"), meta=np.array(json.dumps(metas)), **arrays)
             print(name, [m["preset"] for m in metas])
         if not want or "refdemo" in want:
+            from refdemo_assets import store
+            store()   # tests/golden/refdemo_assets.npz: the images tests/test_refdemo.py gives the scene code
             make_refdemo(tmp)
         if not want or "kat" in want or "kat0" in want:
             make_kat(tmp)

@@ -597,6 +597,28 @@ def test_bench_line_contract(built):
         assert cb["cores"] <= 16 and len(cb["runs"]) == 3 and sorted(cb["runs"])[1] == cb["value"] and "reference_on_all_cores" in cb
 
 
+def test_bench_dumps_the_frame_of_its_last_step(ctx, tmp_path):
+    """bench.py --dump-outputs DIR writes the frame the timed path computed (DIR/radiance.npy: the (H, W, 3) float64 mean radiance); it is
+    the frame a caller of the C ABI gets for the same workload.  --steps sets the number of timed steps: K steps launch K times the render
+    kernels of one step."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    launches = {}
+    for steps in (1, 2):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg1", "--steps", str(steps), "--warmup", "0", "--no-cpu-baseline",
+                            "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps
+        launches[steps] = d["roofline"]["launches_timed"]
+    assert launches[1] >= 1 and launches[2] == 2 * launches[1], launches
+    assert sorted(os.listdir(tmp_path / "out")) == ["radiance.npy"]
+    frame = np.load(tmp_path / "out" / "radiance.npy")
+    assert frame.dtype == np.float64 and frame.shape == (225, 400, 3) and np.isfinite(frame).all() and frame.sum() > 0
+    ds = demo_scene("cfg1")
+    _check(frame, gpu_scene(ctx, "cfg1").render(ds.camera, ds.env, ds.seed), "bench.py --dump-outputs frame")
+
+
 @pytest.mark.parametrize("workload", ["cfg2", "cfg3", "cfg5", "demo"])
 def test_bench_line_names_its_bound_from_counters(built, workload):
     """for every workload the bench can name, `roofline.bound` comes from a counter pass of the CURRENT kernel source

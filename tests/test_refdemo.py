@@ -1,12 +1,13 @@
 """The reference's OWN demo scene code — load_materials(), sceneAssetsLoader and build_geometry() of
-/root/reference/scene_management.hpp:28-236 — compiled twice from its own text (oracle/Makefile): against the reference headers
+the reference's scene_management.hpp:28-236 — compiled twice from its own text (oracle/Makefile): against the reference headers
 (oracle/_ref/zenith_ref, scene "refdemo") and, UNCHANGED, against the drop-in headers (oracle/_ref/refscene_dropin, through the
 forwarding headers include/zenith/compat/ and the optional stb decode of image_texture).  The drop-in side flattens the world and
 renders it with the CPU restatement; the tiles must equal the genuine reference's bit for bit.
 
-Runs only where /root/reference exists (the build container): the scene reads the reference's assets/ tree at run time, which
-never travels.  assets/models/teapot.obj is one of the blobs missing from the checkout — the reference itself would dereference a
-null mesh without it — so a generated OBJ stands in for it (synthetic input of the same shape).  The mesh sits under
+The scene reads assets/ relative to its working directory at run time: tests/golden/refdemo_assets.py writes its images out of the committed
+fixture tests/golden/refdemo_assets.npz and generates its models (the teapot, a blob missing from the reference's checkout, as a small synthetic
+body; the five models that are loaded but never placed as strips with the reference files' triangle counts, which keeps the scene's RNG stream).
+Runs wherever build() has made the two oracle/_ref binaries (they are compiled from the reference's text, and travel with the tree).  The mesh sits under
 rotate_y, whose bounding box the reference builds with the inverse rotation (rotate_y.hpp:26-27): pixels
 that see it are not reproducible even between two reference builds, so the compared tiles look elsewhere."""
 import json
@@ -19,7 +20,6 @@ import pytest
 
 from conftest import ROOT
 
-REF = "/root/reference"
 BIN_REF = os.path.join(ROOT, "oracle", "_ref", "zenith_ref")
 BIN_DROPIN = os.path.join(ROOT, "oracle", "_ref", "refscene_dropin")
 
@@ -28,8 +28,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from refdemo_assets import asset_dir as _asset_dir   # (shared with tests/golden/make_golden.py, which makes the fixtures of tests/test_refdemo_gpu.py)
 
 
-@pytest.mark.skipif(not (os.path.isdir(REF) and os.path.exists(BIN_REF) and os.path.exists(BIN_DROPIN)),
-                    reason="needs /root/reference and the oracle/_ref binaries (build container only)")
+@pytest.mark.skipif(not (os.path.exists(BIN_REF) and os.path.exists(BIN_DROPIN)),
+                    reason="needs the oracle/_ref binaries (build() makes them where the reference's text is available)")
 def test_reference_scene_code_compiles_and_renders_unchanged(built, tmp_path):
     cwd = _asset_dir(str(tmp_path))
     st = json.loads(subprocess.run([BIN_DROPIN, "stats"], cwd=cwd, capture_output=True, text=True, check=True).stdout.strip().splitlines()[-1])
