@@ -1217,6 +1217,8 @@ struct post_processor {
         p.debug_red = debug.red; p.debug_green = debug.green; p.debug_blue = debug.blue; p.debug_luminance = debug.luminance; p.debug_bvh = debug.bvh;
         return p;
     }
+    // post-denoise sharpening (color_processing.hpp:207-227), on the device of the last render (zr_sharpen_frame); defined below
+    void apply_sharpening(std::vector<color>& buffer, int width, int height, double amount) const;
 };
 
 namespace zenith {
@@ -1365,6 +1367,15 @@ inline bool device_scatter(const material& self, const ray& r_in, const hit_reco
 }
 }  // namespace zenith
 
+inline void post_processor::apply_sharpening(std::vector<color>& buffer, int width, int height, double amount) const {
+    if (amount <= 0.0) return;   // color_processing.hpp:208-210
+    if (width < 1 || height < 1 || buffer.size() != (size_t)width * height) { std::cerr << "[zenith] apply_sharpening: buffer size mismatch\n"; return; }
+    zenith::context_lease lease(zenith::object_device().load());
+    zr_ctx* ctx = lease;
+    double* p = reinterpret_cast<double*>(buffer.data());
+    if (!ctx || zr_sharpen_frame(ctx, p, width, height, amount, p) != ZR_OK) std::cerr << "[zenith] apply_sharpening failed: " << zr_last_error() << "\n";
+}
+
 // ---- camera.hpp: public configuration + render() ------------------------------------------------------
 class camera {
 public:
@@ -1383,6 +1394,7 @@ public:
     std::vector<color> render_accumulator;
     std::vector<color> albedo_buffer, normal_buffer, z_depth_buffer;  // first-hit passes (camera.hpp:81-83), filled when their flag is set
     std::vector<color> reflection_buffer, refraction_buffer;          // second-path split (camera.hpp:84-85, 490-517), filled when either flag is set
+    std::vector<color> denoise_buffer;   // camera.hpp:80: the denoised copy of render_accumulator, filled when use_denoiser is set (not OIDN)
     std::atomic<int> lines_rendered{0};
     uint64_t seed = 0x5EED0000ull;  // extension: the reference cannot be seeded (common.hpp:30-31)
     int device = 0;                 // extension: HIP device ordinal
@@ -1390,6 +1402,7 @@ public:
 
     void reset_accumulator() {  // camera.hpp:209-233
         render_accumulator.assign((size_t)image_width * image_height, color(0, 0, 0));
+        denoise_buffer.assign(render_accumulator.size(), color(0, 0, 0));
         albedo_buffer.assign(render_accumulator.size(), color(0, 0, 0));
         normal_buffer.assign(render_accumulator.size(), color(0, 0, 0));
         z_depth_buffer.assign(render_accumulator.size(), color(0, 0, 0));
@@ -1448,6 +1461,7 @@ public:
         for (const auto& w : fs.warnings) std::cerr << "[zenith] " << w << "\n";
         zenith::object_device() = device;
         int rc;
+        std::vector<color> guide_albedo, guide_normal;   // the denoiser's guides when the public AOV buffers are off
         {
         zenith::context_lease lease(device);   // one context of the process-wide pool, exclusively, for this frame
         zr_ctx* ctx = lease;
@@ -1466,14 +1480,19 @@ public:
                            reinterpret_cast<volatile const uint8_t*>(&render_flag), reinterpret_cast<volatile int*>(&lines_rendered));
             zr_get_counters(ctx, &last_counters);
             ph("zr_render");
-            if (rc == ZR_OK && (use_albedo_buffer || use_normal_buffer || use_z_depth_buffer)) {
+            if (rc == ZR_OK && (use_albedo_buffer || use_normal_buffer || use_z_depth_buffer || use_denoiser)) {
                 const size_t npx = (size_t)image_width * image_height;
                 if (use_albedo_buffer) albedo_buffer.assign(npx, color(0, 0, 0));
                 if (use_normal_buffer) normal_buffer.assign(npx, color(0, 0, 0));
                 if (use_z_depth_buffer) z_depth_buffer.assign(npx, color(0, 0, 0));
+                // the denoiser's guides: the public buffers when their flags are set, private scratch otherwise (the reference would
+                // hand OIDN zero guides then)
+                if (use_denoiser && !use_albedo_buffer) guide_albedo.assign(npx, color(0, 0, 0));
+                if (use_denoiser && !use_normal_buffer) guide_normal.assign(npx, color(0, 0, 0));
+                double* pa = use_albedo_buffer ? reinterpret_cast<double*>(albedo_buffer.data()) : use_denoiser ? reinterpret_cast<double*>(guide_albedo.data()) : nullptr;
+                double* pn = use_normal_buffer ? reinterpret_cast<double*>(normal_buffer.data()) : use_denoiser ? reinterpret_cast<double*>(guide_normal.data()) : nullptr;
                 zr_aov_params ap{post.z_depth_max_dist};
-                rc = zr_render_aov(ctx, sc, &zc, seed, nullptr, &ap, use_albedo_buffer ? reinterpret_cast<double*>(albedo_buffer.data()) : nullptr,
-                                   use_normal_buffer ? reinterpret_cast<double*>(normal_buffer.data()) : nullptr,
+                rc = zr_render_aov(ctx, sc, &zc, seed, nullptr, &ap, pa, pn,
                                    use_z_depth_buffer ? reinterpret_cast<double*>(z_depth_buffer.data()) : nullptr);
             }
             if (rc == ZR_OK && (use_reflection || use_refraction)) {
@@ -1494,5 +1513,34 @@ public:
             post.last_stats = stats;
             post.exposure = static_cast<float>(post.apply_auto_exposure(stats));
         }
+        if (rc == ZR_OK && use_denoiser) {   // camera.hpp:268-291; the a-trous filter of zr_denoise stands in for OIDN
+            const std::vector<color>& ga = use_albedo_buffer ? albedo_buffer : guide_albedo;
+            const std::vector<color>& gn = use_normal_buffer ? normal_buffer : guide_normal;
+            denoise_buffer = render_accumulator;
+            bool ok = denoise(denoise_buffer, ga, gn);
+            if (ok && use_reflection) {
+                ok = denoise(reflection_buffer, ga, gn);
+                if (ok && post.use_sharpening) post.apply_sharpening(reflection_buffer, image_width, image_height, post.sharpen_amount);
+            }
+            if (ok && use_refraction) {
+                ok = denoise(refraction_buffer, ga, gn);
+                if (ok && post.use_sharpening) post.apply_sharpening(refraction_buffer, image_width, image_height, post.sharpen_amount);
+            }
+        }
+    }
+
+private:
+    // apply_denoising (camera.hpp:581-699) in place, with zr_denoise's default parameters; false (and a message) on failure
+    bool denoise(std::vector<color>& buffer, const std::vector<color>& albedo, const std::vector<color>& normal) const {
+        zenith::context_lease lease(device);
+        zr_ctx* ctx = lease;
+        const zr_denoise_params dp{ZR_DENOISE_DEFAULT_ITERATIONS, ZR_DENOISE_DEFAULT_DEMODULATE, ZR_DENOISE_DEFAULT_SIGMA_COLOR, ZR_DENOISE_DEFAULT_SIGMA_NORMAL,
+                                   ZR_DENOISE_DEFAULT_SIGMA_ALBEDO, 0.0f};
+        double* p = reinterpret_cast<double*>(buffer.data());
+        const int rc = ctx ? zr_denoise(ctx, &dp, p, reinterpret_cast<const double*>(albedo.data()), reinterpret_cast<const double*>(normal.data()),
+                                        nullptr, image_width, image_height, p)
+                           : ZR_E_DEVICE;
+        if (rc != ZR_OK) std::cerr << "[zenith] denoise failed: " << zr_last_error() << "\n";
+        return rc == ZR_OK;
     }
 };

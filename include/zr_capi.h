@@ -336,6 +336,41 @@ typedef struct zr_image_stats {
 } zr_image_stats;
 int zr_analyze_frame(zr_ctx*, const double* frame_rgb, size_t n_pixels, zr_image_stats* out);
 
+/* ---- denoising: step 4 of camera::render (camera.hpp:268-291) -------------------------------------------------------
+ * zr_denoise fills the role of the reference's apply_denoising (camera.hpp:581-699), but it is NOT Intel OIDN and does not
+ * reproduce OIDN's output (OIDN is a trained network whose weights the reference does not ship).  It is an edge-avoiding
+ * a-trous wavelet filter (Dammertz et al., HPG 2010) in FP32, guided by the first-hit albedo and normal frames of
+ * zr_render_aov and, optionally, its z-depth frame.  Per pixel every input is cleaned (NaN / Inf -> 0; the reference
+ * cleans only the guides), the normal is decoded from the [0,1] camera-space encoding (n = normalize(2e - 1), "no
+ * information" when |2e - 1| < 1e-6) and, with demodulate_albedo, the colour is divided by the albedo (channels <= 1e-3
+ * count as 1).  `iterations` levels of the 5 x 5 B3-spline kernel at steps 1, 2, 4, ... then weight each tap by
+ *   exp(-|t(d_p) - t(d_q)|^2 / (sigma_color^2 4^-level))   t(x) = x / (1 + luminance(x)): tone-compressed colour distance
+ *   max(0, n_p . n_q)^sigma_normal                          1 when either normal carries no information
+ *   exp(-|a_p - a_q|^2 / sigma_albedo^2)
+ *   exp(-|z_p - z_q| / sigma_depth)                          only with a depth frame and sigma_depth > 0
+ * taps outside the frame are skipped; the result is multiplied back by the albedo and widened to double.  Deterministic
+ * (a fixed tap order, no atomics).  The exact arithmetic is restated in NumPy by tests/denoise_model.py; DESIGN §9.
+ * All frames are W*H*3 doubles in host memory, row-major like out_rgb; zdepth may be NULL, out may equal color.
+ * The defaults below are what camera::render uses with use_denoiser. */
+typedef struct zr_denoise_params {
+    int32_t iterations;                 /* levels, 0..8; 0 = demodulate / remodulate only (identity up to FP32 rounding) */
+    int32_t demodulate_albedo;          /* filter c / albedo instead of c */
+    float sigma_color, sigma_normal, sigma_albedo, sigma_depth;   /* > 0; sigma_depth <= 0: depth guide off */
+} zr_denoise_params;
+/* defaults: chosen on 8-spp renders of cfg5 and mix0 against 1024 spp.  Demodulation is off: the 8-spp albedo
+ * pass is itself noisy on textures, and dividing by it cost more than it saved on the textured scene. */
+#define ZR_DENOISE_DEFAULT_ITERATIONS 5
+#define ZR_DENOISE_DEFAULT_DEMODULATE 0
+#define ZR_DENOISE_DEFAULT_SIGMA_COLOR 1.5f
+#define ZR_DENOISE_DEFAULT_SIGMA_NORMAL 64.0f
+#define ZR_DENOISE_DEFAULT_SIGMA_ALBEDO 0.25f
+int zr_denoise(zr_ctx*, const zr_denoise_params*, const double* color, const double* albedo, const double* normal,
+               const double* zdepth, int width, int height, double* out);
+/* post_processor::apply_sharpening (color_processing.hpp:207-227) on its own: interior pixels become
+ * c (1 - amount) + (5 c - the four neighbours) amount, border pixels are copied.  Double in, double out, byte-exact with
+ * the reference; amount <= 0 copies.  Host memory, W*H*3 doubles; out may equal in. */
+int zr_sharpen_frame(zr_ctx*, const double* in, int width, int height, double amount, double* out);
+
 /* Known answers for whole paths: walks the primary sample (px, py, sample) of each request on the device and records
  * every segment, ZR_PATH_RECORD doubles each: ray origin, direction | hit flag, t, material id | scattered flag,
  * attenuation rgb | emission rgb | main-stream RNG draws consumed so far.  requests = n * 3 ints; out = n * max_segments *

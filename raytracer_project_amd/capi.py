@@ -89,6 +89,22 @@ class PostParams(C.Structure):
         return p
 
 
+class DenoiseParams(C.Structure):
+    """zr_denoise_params: the a-trous denoiser behind camera::use_denoiser (not OIDN; include/zr_capi.h)"""
+    _fields_ = [("iterations", C.c_int32), ("demodulate_albedo", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """ZR_DENOISE_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses); depth guide off"""
+        p = cls(5, 0, 1.5, 64.0, 0.25, 0.0)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"DenoiseParams has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class ImageStats(C.Structure):
     _fields_ = [("average_luminance", C.c_float), ("max_luminance", C.c_float), ("histogram", C.c_int32 * 256)]
 
@@ -157,7 +173,7 @@ CAPI_SYMBOLS = [
     "zr_abi_version", "zr_last_error", "zr_create", "zr_destroy", "zr_scene_create", "zr_scene_destroy",
     "zr_scene_set_spheres", "zr_scene_set_triangles", "zr_scene_set_cubes", "zr_scene_set_media",
     "zr_scene_set_xform_ops", "zr_scene_set_objects", "zr_scene_set_groups", "zr_scene_set_materials", "zr_scene_set_textures",
-    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device", "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_get_counters",
+    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device", "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame", "zr_get_counters",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
 
@@ -197,6 +213,8 @@ def load():
     lib.zr_render_aov.argtypes = [vp, vp, C.POINTER(Camera), u64, C.POINTER(Region), C.POINTER(AovParams), vp, vp, vp]
     lib.zr_post_process.argtypes = [vp, C.POINTER(PostParams), vp, i32, i32, i32, i32, vp]
     lib.zr_analyze_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(ImageStats)]
+    lib.zr_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, i32, i32, vp]
+    lib.zr_sharpen_frame.argtypes = [vp, vp, i32, i32, C.c_double, vp]
     lib.zr_trace_paths.argtypes = [vp, vp, C.POINTER(Camera), u64, vp, i32, i32, vp]
     lib.zr_render_passes.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), vp, vp, vp]
     lib.zr_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -289,6 +307,22 @@ class DemoScene:
             raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
         return out, rc
 
+    def render_dropin_denoise(self, width=0, height=0, spp=0, device=0, passes=False, sharpening=False):
+        """camera::render with use_denoiser (and optionally use_reflection / use_refraction, post.use_sharpening) through
+        include/zenith/zenith.hpp: dict of render_accumulator, denoise_buffer, reflection_buffer, refraction_buffer,
+        albedo_buffer, normal_buffer as (H, W, 3) float64"""
+        w = width or self.camera.image_width
+        h = height or self.camera.image_height
+        names = ("render_accumulator", "denoise_buffer", "reflection_buffer", "refraction_buffer", "albedo_buffer", "normal_buffer")
+        outs = {k: np.zeros((h, w, 3), dtype=np.float64) for k in names}
+        lib = load_scenes()
+        lib.zrs_render_dropin_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+        flags = (1 if passes else 0) | (2 if sharpening else 0)
+        rc = lib.zrs_render_dropin_denoise(self._h, width, height, spp, device, flags, *[outs[k].ctypes.data for k in names])
+        if rc != 0:
+            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        return outs
+
     def dropin_virtuals(self, rays8, seed, pixel=0x7ACE):
         """bvh_node(world).hit + rec.mat->emitted / scatter through the drop-in classes (one device launch per call):
         (recs[n,16], scat[n,14]) in the layout of `zenith_ref kat <scene> hits`"""
@@ -356,6 +390,34 @@ class Context:
         st = ImageStats()
         _check(self.lib.zr_analyze_frame(self._c, frame.ctypes.data, frame.size // 3, C.byref(st)))
         return st
+
+    def denoise(self, params, color, albedo, normal, zdepth=None, out=None):
+        """zr_denoise (the a-trous filter of camera::use_denoiser): (H, W, 3) float64 frames -> (H, W, 3) float64.
+        `out` may be `color` itself (in place)."""
+        color = np.ascontiguousarray(color, dtype=np.float64)
+        h, w = color.shape[:2]
+        guides = [np.ascontiguousarray(g, dtype=np.float64) for g in (albedo, normal)]
+        if zdepth is not None:
+            zdepth = np.ascontiguousarray(zdepth, dtype=np.float64)
+        for g in guides + ([zdepth] if zdepth is not None else []):
+            if g.shape != color.shape:
+                raise ValueError(f"guide shape {g.shape} differs from the colour frame's {color.shape}")
+        if out is None:
+            out = np.zeros_like(color)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == color.shape
+        _check(self.lib.zr_denoise(self._c, C.byref(params), color.ctypes.data, guides[0].ctypes.data, guides[1].ctypes.data,
+                                   zdepth.ctypes.data if zdepth is not None else None, w, h, out.ctypes.data))
+        return out
+
+    def sharpen(self, frame, amount, out=None):
+        """post_processor::apply_sharpening on the device: (H, W, 3) float64 -> (H, W, 3) float64"""
+        frame = np.ascontiguousarray(frame, dtype=np.float64)
+        h, w = frame.shape[:2]
+        if out is None:
+            out = np.zeros_like(frame)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == frame.shape
+        _check(self.lib.zr_sharpen_frame(self._c, frame.ctypes.data, w, h, C.c_double(amount), out.ctypes.data))
+        return out
 
     def kat_camera_rays(self, camera, seed, requests):
         """camera::initialize + get_ray: (n, 7) = origin, direction, draws"""

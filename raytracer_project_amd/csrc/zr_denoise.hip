@@ -1,0 +1,146 @@
+// zr_denoise.hip — the denoiser behind camera::use_denoiser (camera.hpp:268-291): an edge-avoiding a-trous wavelet filter
+// (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) guided by the first-hit albedo and normal passes and, optionally, the z-depth pass.
+// The reference runs Intel OIDN there (apply_denoising, camera.hpp:581-699); its network weights are not part of the reference and
+// this is NOT a reproduction of it.  The contract of this file is its own NumPy restatement (tests/denoise_model.py), DESIGN §9.
+//
+//   pack     per pixel, FP32: clean (NaN / Inf -> 0, every input), n = normalize(2e - 1) (0 = no information when |2e - 1| < 1e-6),
+//            a' = a where a > 1e-3 else 1 (per channel, demodulation on; else a' = 1), d = c / a'
+//   atrous   one launch per level i = 0..L-1, step s = 2^i, taps (kx, ky) in {-2..2}^2 at (kx s, ky s), ky outer / kx inner,
+//            taps outside the frame skipped; w = h(kx) h(ky) w_c w_n w_a w_z with
+//              w_c = exp(-|t(d_p) - t(d_q)|^2 / (sigma_c^2 4^-i)),  t(x) = x / (1 + max(lum(x), 0)),  lum = Rec.709
+//              w_n = max(0, n_p . n_q)^sigma_n  (1 when either normal is 0)
+//              w_a = exp(-|a_p - a_q|^2 / sigma_a^2)
+//              w_z = exp(-|z_p - z_q| / sigma_z)  (1 without a depth frame or with sigma_z <= 0)
+//            d'_p = sum w d_q / sum w  (the centre tap's weight is h(0)^2 w_n(p, p) > 0)
+//   unpack   c_out = d' a', widened to double
+//
+// As evaluated (the same formula up to FP32 rounding; the taps are ALU-bound): whoever writes a colour also writes
+// r = 1 / (1 + max(lum, 0)) into its .w, so t(x) = x r; the three exponentials are one, w_c w_a w_z = exp(-(|dt|^2 ic + |da|^2 ia
+// + |dz| iz)) with the reciprocals ic, ia, iz taken once on the host; w_n = exp2(sigma_n log2(max(0, n_p . n_q))).  Then
+// w = (h(kx) h(ky)) (w_c w_a w_z) w_n.
+//
+// Buffers: colour ping-pong float4 (xyz = d, w = r), guide0 float4 (xyz = cleaned albedo, w = depth), guide1 float4 (xyz = n,
+// w = 1 when n carries information).  A plain gather: the 25 taps of a 16 x 16 block come from L2 / MALL.  Compiled with
+// -ffp-contract=off, so that the NumPy model follows the arithmetic operation for operation; only expf / exp2f / log2f differ
+// from NumPy's (an ulp or two).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/zr_capi.h"
+
+namespace zr {
+
+namespace {
+
+struct DenoiseLevel {
+    float inv_c;      // 1 / (sigma_c^2 4^-i)
+    float inv_a;      // 1 / sigma_a^2
+    float inv_z;      // 1 / sigma_z with the depth guide on, else 0
+    float sigma_n;
+    int step;         // 2^i
+};
+
+__device__ __forceinline__ float clean(double v) {   // clean_val (camera.hpp:596-600) after the reference's cast to float
+    const float f = (float)v;
+    return isfinite(f) ? f : 0.0f;
+}
+
+__device__ __forceinline__ float lum709(float x, float y, float z) { return 0.2126f * x + 0.7152f * y + 0.0722f * z; }
+// a colour with the reciprocal of its tone-compression divisor in .w
+__device__ __forceinline__ float4 with_tone(float x, float y, float z) { return make_float4(x, y, z, 1.0f / (1.0f + fmaxf(lum709(x, y, z), 0.0f))); }
+
+__global__ __launch_bounds__(256) void denoise_pack(const double* __restrict__ color, const double* __restrict__ albedo,
+                                                    const double* __restrict__ normal, const double* __restrict__ zdepth, int W, int H,
+                                                    int demodulate, float4* __restrict__ col, float4* __restrict__ g0, float4* __restrict__ g1) {
+    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
+    if (i >= W || j >= H) return;
+    const size_t p = (size_t)j * W + i;
+    const float ax = clean(albedo[3 * p]), ay = clean(albedo[3 * p + 1]), az = clean(albedo[3 * p + 2]);
+    const float z = zdepth ? clean(zdepth[3 * p]) : 0.0f;
+    float mx = 2.0f * clean(normal[3 * p]) - 1.0f, my = 2.0f * clean(normal[3 * p + 1]) - 1.0f, mz = 2.0f * clean(normal[3 * p + 2]) - 1.0f;
+    const float len = sqrtf(mx * mx + my * my + mz * mz);
+    float valid = 1.0f;
+    if (len < 1e-6f) { mx = my = mz = 0.0f; valid = 0.0f; }
+    else { mx = mx / len; my = my / len; mz = mz / len; }
+    float dx = clean(color[3 * p]), dy = clean(color[3 * p + 1]), dz = clean(color[3 * p + 2]);
+    if (demodulate) {
+        dx = dx / (ax > 1e-3f ? ax : 1.0f); dy = dy / (ay > 1e-3f ? ay : 1.0f); dz = dz / (az > 1e-3f ? az : 1.0f);
+    }
+    col[p] = with_tone(dx, dy, dz);
+    g0[p] = make_float4(ax, ay, az, z);
+    g1[p] = make_float4(mx, my, mz, valid);
+}
+
+__global__ __launch_bounds__(256) void denoise_atrous(const float4* __restrict__ in, const float4* __restrict__ g0, const float4* __restrict__ g1,
+                                                      int W, int H, DenoiseLevel lv, float4* __restrict__ out) {
+    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
+    if (i >= W || j >= H) return;
+    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const size_t p = (size_t)j * W + i;
+    const float4 cp = in[p], ap = g0[p], np = g1[p];
+    const float tpx = cp.x * cp.w, tpy = cp.y * cp.w, tpz = cp.z * cp.w;
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f;
+#pragma unroll
+    for (int ky = -2; ky <= 2; ky++) {
+        const int qj = j + ky * lv.step;
+        if (qj < 0 || qj >= H) continue;
+#pragma unroll
+        for (int kx = -2; kx <= 2; kx++) {
+            const int qi = i + kx * lv.step;
+            if (qi < 0 || qi >= W) continue;
+            const size_t q = (size_t)qj * W + qi;
+            const float4 cq = in[q], aq = g0[q], nq = g1[q];
+            const float ex = tpx - cq.x * cq.w, ey = tpy - cq.y * cq.w, ez = tpz - cq.z * cq.w;
+            const float bx = ap.x - aq.x, by = ap.y - aq.y, bz = ap.z - aq.z;
+            const float arg = (ex * ex + ey * ey + ez * ez) * lv.inv_c + (bx * bx + by * by + bz * bz) * lv.inv_a + fabsf(ap.w - aq.w) * lv.inv_z;
+            float wn = 1.0f;
+            if (np.w != 0.0f && nq.w != 0.0f) wn = exp2f(lv.sigma_n * log2f(fmaxf(0.0f, np.x * nq.x + np.y * nq.y + np.z * nq.z)));
+            const float w = h[kx + 2] * h[ky + 2] * expf(-arg) * wn;
+            sx = sx + w * cq.x; sy = sy + w * cq.y; sz = sz + w * cq.z;
+            sw = sw + w;
+        }
+    }
+    out[p] = with_tone(sx / sw, sy / sw, sz / sw);
+}
+
+__global__ __launch_bounds__(256) void denoise_unpack(const float4* __restrict__ col, const float4* __restrict__ g0, int W, int H, int demodulate,
+                                                      double* __restrict__ out) {
+    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
+    if (i >= W || j >= H) return;
+    const size_t p = (size_t)j * W + i;
+    float4 d = col[p];
+    if (demodulate) {
+        const float4 a = g0[p];
+        d.x = d.x * (a.x > 1e-3f ? a.x : 1.0f); d.y = d.y * (a.y > 1e-3f ? a.y : 1.0f); d.z = d.z * (a.z > 1e-3f ? a.z : 1.0f);
+    }
+    out[3 * p] = (double)d.x; out[3 * p + 1] = (double)d.y; out[3 * p + 2] = (double)d.z;
+}
+
+}  // namespace
+
+// d_color / d_albedo / d_normal / d_zdepth (may be null): W*H*3 doubles on the device; d_col0 / d_col1 / d_g0 / d_g1: W*H float4
+// scratch; d_out: W*H*3 doubles (may be d_color).  The caller has validated the parameters (zr_denoise).
+hipError_t launch_denoise(const double* d_color, const double* d_albedo, const double* d_normal, const double* d_zdepth, int W, int H,
+                          const zr_denoise_params& dp, float4* d_col0, float4* d_col1, float4* d_g0, float4* d_g1, double* d_out,
+                          hipStream_t stream) {
+    const dim3 block(16, 16), grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
+    const int demod = dp.demodulate_albedo ? 1 : 0;
+    hipLaunchKernelGGL(denoise_pack, grid, block, 0, stream, d_color, d_albedo, d_normal, d_zdepth, W, H, demod, d_col0, d_g0, d_g1);
+    float4* cur = d_col0;
+    float4* nxt = d_col1;
+    for (int it = 0; it < dp.iterations; it++) {
+        DenoiseLevel lv;
+        lv.inv_c = 1.0f / (dp.sigma_color * dp.sigma_color * ldexpf(1.0f, -2 * it));
+        lv.inv_a = 1.0f / (dp.sigma_albedo * dp.sigma_albedo);
+        lv.inv_z = d_zdepth && dp.sigma_depth > 0.0f ? 1.0f / dp.sigma_depth : 0.0f;
+        lv.sigma_n = dp.sigma_normal;
+        lv.step = 1 << it;
+        hipLaunchKernelGGL(denoise_atrous, grid, block, 0, stream, (const float4*)cur, (const float4*)d_g0, (const float4*)d_g1, W, H, lv, nxt);
+        float4* t = cur; cur = nxt; nxt = t;
+    }
+    hipLaunchKernelGGL(denoise_unpack, grid, block, 0, stream, (const float4*)cur, (const float4*)d_g0, W, H, demod, d_out);
+    return hipGetLastError();
+}
+
+}  // namespace zr

@@ -76,6 +76,10 @@ hipError_t launch_passes(const DScene& sc, const DCamera& cam, const DEnv& env, 
 hipError_t launch_post(const double* d_frame, int W, int H, const zr_post_params& pp, int is_data_pass, int apply_gamma, double ev, double* d_tmp0,
                        double* d_tmp1, double* d_tmp2, uint8_t* d_out, hipStream_t stream);
 hipError_t launch_analyze(const double* d_frame, size_t n, double* d_part_log, float* d_part_max, int* d_hist, hipStream_t stream);
+hipError_t launch_sharpen(const double* d_in, double* d_out, int W, int H, double amount, hipStream_t stream);
+hipError_t launch_denoise(const double* d_color, const double* d_albedo, const double* d_normal, const double* d_zdepth, int W, int H,
+                          const zr_denoise_params& dp, float4* d_col0, float4* d_col1, float4* d_g0, float4* d_g1, double* d_out,
+                          hipStream_t stream);
 #define ZR_PATH_REC 17
 hipError_t launch_path_records(const DScene& sc, const DCamera& cam, uint64_t seed, const int32_t* req, int n_req, int max_seg, double* out,
                                hipStream_t stream);

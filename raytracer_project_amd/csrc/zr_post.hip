@@ -249,6 +249,11 @@ hipError_t launch_post(const double* d_frame, int W, int H, const zr_post_params
     return hipGetLastError();
 }
 
+hipError_t launch_sharpen(const double* d_in, double* d_out, int W, int H, double amount, hipStream_t stream) {
+    hipLaunchKernelGGL(post_sharpen, dim3(grid_for((size_t)W * H)), dim3(256), 0, stream, d_in, d_out, W, H, amount);
+    return hipGetLastError();
+}
+
 hipError_t launch_analyze(const double* d_frame, size_t n, double* d_part_log, float* d_part_max, int* d_hist, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(d_hist, 0, 256 * sizeof(int), stream);
     if (e != hipSuccess) return e;

@@ -562,6 +562,49 @@ int zr_post_process(zr_ctx* c, const zr_post_params* pp, const double* frame, in
     return ZR_OK;
 }
 
+int zr_denoise(zr_ctx* c, const zr_denoise_params* dp, const double* color, const double* albedo, const double* normal, const double* zdepth,
+               int W, int H, double* out) {
+    if (!c || !dp || !color || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
+    if (W < 1 || H < 1 || (size_t)W * H > (1ull << 31)) return fail(ZR_E_INVALID, "frame size %d x %d not supported", W, H);
+    if (dp->iterations < 0 || dp->iterations > 8) return fail(ZR_E_INVALID, "denoise iterations %d outside 0..8", dp->iterations);
+    if (!(dp->sigma_color > 0.0f) || !(dp->sigma_normal > 0.0f) || !(dp->sigma_albedo > 0.0f) || dp->sigma_depth < 0.0f || std::isnan(dp->sigma_depth))
+        return fail(ZR_E_INVALID, "denoise sigmas must be positive (sigma_depth: >= 0, 0 = no depth guide)");
+    HIP_OK(hipSetDevice(c->device));
+    const size_t n = (size_t)W * H;
+    DevBuf<double> d_c, d_a, d_n, d_z; DevBuf<float4> col0, col1, g0, g1;
+    int rc;
+    if ((rc = d_c.alloc(n * 3)) || (rc = d_a.alloc(n * 3)) || (rc = d_n.alloc(n * 3)) || (zdepth && (rc = d_z.alloc(n * 3)))) return rc;
+    if ((rc = col0.alloc(n)) || (rc = col1.alloc(n)) || (rc = g0.alloc(n)) || (rc = g1.alloc(n))) return rc;
+    HIP_OK(hipMemcpyAsync(d_c.p, color, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d_a.p, albedo, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d_n.p, normal, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (zdepth) HIP_OK(hipMemcpyAsync(d_z.p, zdepth, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // the colour frame has been packed before the unpack kernel overwrites it
+    HIP_OK(zr::launch_denoise(d_c.p, d_a.p, d_n.p, zdepth ? d_z.p : nullptr, W, H, *dp, col0.p, col1.p, g0.p, g1.p, d_c.p, c->stream));
+    HIP_OK(hipMemcpyAsync(out, d_c.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return ZR_OK;
+}
+
+int zr_sharpen_frame(zr_ctx* c, const double* in, int W, int H, double amount, double* out) {
+    if (!c || !in || !out) return fail(ZR_E_INVALID, "null argument");
+    if (W < 1 || H < 1 || (size_t)W * H > (1ull << 31)) return fail(ZR_E_INVALID, "frame size %d x %d not supported", W, H);
+    const size_t n = (size_t)W * H;
+    if (!(amount > 0.0)) {   // color_processing.hpp:208-210: nothing to do
+        if (out != in) std::memmove(out, in, n * 3 * sizeof(double));
+        return ZR_OK;
+    }
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<double> d_in, d_out;
+    int rc;
+    if ((rc = d_in.alloc(n * 3)) || (rc = d_out.alloc(n * 3))) return rc;
+    HIP_OK(hipMemcpyAsync(d_in.p, in, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(zr::launch_sharpen(d_in.p, d_out.p, W, H, amount, c->stream));
+    HIP_OK(hipMemcpyAsync(out, d_out.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return ZR_OK;
+}
+
 int zr_analyze_frame(zr_ctx* c, const double* frame, size_t n, zr_image_stats* out) {
     if (!c || !frame || !out) return fail(ZR_E_INVALID, "null argument");
     if (n == 0 || n > (1ull << 31)) return fail(ZR_E_INVALID, "pixel count not supported");

@@ -126,6 +126,41 @@ int zrs_dropin_frame_to_rgb8(void* p, int spp, int device, unsigned char* rgb8, 
     return 0;
 }
 
+// camera::render with use_denoiser set (camera.hpp:268-291) through the drop-in API.  flags: 1 = use_reflection and use_refraction,
+// 2 = post.use_sharpening (sharpen_amount 0.2).  The public albedo / normal buffers stay off, so the denoiser's guides are the drop-in's
+// private ones.  Outputs (W*H*3 doubles each, any may be null): render_accumulator, denoise_buffer, reflection_buffer,
+// refraction_buffer, albedo_buffer, normal_buffer.  spp/width/height <= 0 keep the scene's values.  Returns 0, or -1 if the
+// render did not finish.
+int zrs_render_dropin_denoise(void* p, int width, int height, int spp, int device, int flags, double* acc, double* den, double* refl, double* refr,
+                              double* alb, double* nrm) {
+    handle* h = (handle*)p;
+    camera cam;
+    const zr_camera& c = h->s.cam;
+    cam.image_width = width > 0 ? width : c.image_width;
+    cam.image_height = height > 0 ? height : c.image_height;
+    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
+    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
+    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
+    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
+    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
+    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
+    cam.seed = h->s.seed; cam.device = device;
+    cam.use_denoiser = true;
+    cam.use_reflection = cam.use_refraction = (flags & 1) != 0;
+    cam.reset_accumulator();
+    post_processor post;
+    post.use_sharpening = (flags & 2) != 0;
+    std::atomic<bool> flag{true};
+    auto bvh_world = make_shared<bvh_node>(h->s.world);
+    cam.render(*bvh_world, h->s.env, post, flag);
+    if (cam.lines_rendered.load() != cam.image_height) return -1;
+    const std::pair<const std::vector<color>*, double*> outs[] = {{&cam.render_accumulator, acc}, {&cam.denoise_buffer, den}, {&cam.reflection_buffer, refl},
+                                                                  {&cam.refraction_buffer, refr}, {&cam.albedo_buffer, alb}, {&cam.normal_buffer, nrm}};
+    for (const auto& o : outs)
+        if (o.second) std::memcpy(o.second, o.first->data(), o.first->size() * sizeof(color));
+    return 0;
+}
+
 // The reference's per-ray virtual API through the drop-in classes: for n rays (o, d, tmin, tmax) calls
 // bvh_node(world).hit(r, interval(tmin, tmax), rec), then rec.mat->emitted(...) and rec.mat->scatter(r, rec, att, scattered)
 // with random_double() positioned on the stream (seed, pixel, k) — the layout of `zenith_ref kat <scene> hits`:
@@ -191,6 +226,7 @@ extern "C" size_t zrs_sizeof(int which) {
         case 11: return sizeof(zr_post_params);
         case 12: return sizeof(zr_image_stats);
         case 13: return sizeof(zr_aov_params);
+        case 14: return sizeof(zr_denoise_params);
         default: return 0;
     }
 }
