@@ -54,6 +54,14 @@ constexpr double infinity = std::numeric_limits<double>::infinity();
 constexpr double pi = 3.14159265358979323846;
 const double ray_epsilon = 0.0001;
 inline double degrees_to_radians(double d) { return d * pi / 180.0; }
+
+// common.hpp:120-124: the BVH debug view (bvh.hpp:46-110).  camera::render with bvh_debug_mode set renders the wireframe / volume view of the
+// device's own trees through zr_render_bvh_debug (include/zr_capi.h); the drop-in objects' own hit() does not read these.
+namespace global_settings {
+inline bool bvh_debug_mode = false;
+inline float bvh_thickness = 0.01f;
+inline int debug_bvh_level = -1;
+}  // namespace global_settings
 inline double radians_to_degrees(double r) { return r * 180.0 / pi; }
 
 namespace zenith {
@@ -1476,6 +1484,14 @@ public:
             zc.image_width = image_width; zc.image_height = image_height; zc.samples_per_pixel = samples_per_pixel; zc.max_depth = max_depth;
             zc.vfov = vfov; zc.defocus_angle = defocus_angle; zc.focus_dist = focus_dist;
             for (int k = 0; k < 3; k++) { zc.lookfrom[k] = lookfrom[k]; zc.lookat[k] = lookat[k]; zc.vup[k] = vup[k]; }
+            if (global_settings::bvh_debug_mode) {
+                // the debug view fills render_accumulator only: the AOV, split-pass and denoise buffers stay as reset_accumulator left them
+                // (the reference would feed them the debug frame's records)
+                const zr_bvh_debug_params dp{global_settings::debug_bvh_level, global_settings::bvh_thickness};
+                rc = zr_render_bvh_debug(ctx, sc, &zc, &zenv, seed, nullptr, &dp, reinterpret_cast<double*>(render_accumulator.data()),
+                                         reinterpret_cast<volatile const uint8_t*>(&render_flag), reinterpret_cast<volatile int*>(&lines_rendered));
+                ph("zr_render_bvh_debug");
+            } else {
             rc = zr_render(ctx, sc, &zc, &zenv, seed, nullptr, 0, reinterpret_cast<double*>(render_accumulator.data()),
                            reinterpret_cast<volatile const uint8_t*>(&render_flag), reinterpret_cast<volatile int*>(&lines_rendered));
             zr_get_counters(ctx, &last_counters);
@@ -1504,6 +1520,7 @@ public:
                 rc = zr_render_passes(ctx, sc, &zc, &zenv, seed, nullptr, nullptr, reinterpret_cast<double*>(reflection_buffer.data()),
                                       reinterpret_cast<double*>(refraction_buffer.data()));
             }
+            }
         }
         if (rc != ZR_OK && rc != ZR_E_CANCELLED) std::cerr << "[zenith] render failed: " << zr_last_error() << "\n";
         if (sc) zr_scene_destroy(sc);
@@ -1513,7 +1530,7 @@ public:
             post.last_stats = stats;
             post.exposure = static_cast<float>(post.apply_auto_exposure(stats));
         }
-        if (rc == ZR_OK && use_denoiser) {   // camera.hpp:268-291; the a-trous filter of zr_denoise stands in for OIDN
+        if (rc == ZR_OK && use_denoiser && !global_settings::bvh_debug_mode) {   // camera.hpp:268-291; the a-trous filter of zr_denoise stands in for OIDN
             const std::vector<color>& ga = use_albedo_buffer ? albedo_buffer : guide_albedo;
             const std::vector<color>& gn = use_normal_buffer ? normal_buffer : guide_normal;
             denoise_buffer = render_accumulator;

@@ -371,6 +371,69 @@ int zr_denoise(zr_ctx*, const zr_denoise_params*, const double* color, const dou
  * the reference; amount <= 0 copies.  Host memory, W*H*3 doubles; out may equal in. */
 int zr_sharpen_frame(zr_ctx*, const double* in, int width, int height, double amount, double* out);
 
+/* ---- BVH debug view: global_settings::bvh_debug_mode (bvh.hpp:46-110, aabb.hpp:44-84, camera.hpp:455-461, 928-953, 989-1004) ----
+ * The reference's wireframe rule applied to the device's own trees: the nodes are the binary sibling-pair records; depth 0
+ * is a tree's root box (the union of its first record's two child boxes), the children of a box at depth d sit at depth d + 1, a leaf is
+ * a child box that holds a primitive range, "left" is child slot 0, boxes are the stored FP32 planes widened to double.  The tree of a
+ * placed run of triangles (ZR_PRIM_GROUP) restarts at depth 0 and is walked in the placement's space.  Per node: the box is entered with
+ * aabb::hit's arithmetic on the interval narrowed by the best hit so far; a node of the current level (depth == level, or a leaf for
+ * level -1) whose entry point r.at(t_in + 0.0001f) or exit point r.at(t_out - 0.0001f) lies within
+ * float(thickness * (0.05f + t_in * 0.1f)) of the planes of at least two axes is an EDGE hit at t_in (entry on the edge) or t_out and
+ * emits (0.4, g, 1 - g) * 4, g = min(depth * 0.15f, 1); otherwise the walk goes on, left child first, and a hit below a current-level
+ * node is re-coloured (0.4, g, 1 - g) * 0.1f (VOLUME; the outermost tree's such node wins).  The frame (zr_render_bvh_debug) is the
+ * mean over spp of: the background on a primary miss; the debug colour on an edge / volume hit; emitted + attenuation * c on a surface
+ * hit whose material scatters, where c is the secondary ray's debug colour, its surface's emission if longer than 0.1 or (0.01, 0.01,
+ * 0.01), and 0 on a miss or with max_depth < 2.  Primary rays, RNG streams and scattering are zr_render's. */
+typedef struct zr_bvh_debug_params {
+    int32_t level;    /* global_settings::debug_bvh_level: -1 = leaves, 0 = the root, ...; below -1 is refused */
+    float thickness;  /* global_settings::bvh_thickness: > 0 and finite */
+} zr_bvh_debug_params;
+#define ZR_BVH_DEBUG_DEFAULT_LEVEL -1
+#define ZR_BVH_DEBUG_DEFAULT_THICKNESS 0.01f
+/* box ids: the child box in slot s of pair record r is 2 r + s; the root box of the tree whose first record is R is ZR_BVH_ROOT_BOX | R.
+ * A tree is named by R (0 = the world's tree). */
+#define ZR_BVH_ROOT_BOX 0x80000000u
+#define ZR_BVH_NO_BOX 0xFFFFFFFFu
+enum { ZR_BVH_MISS = 0, ZR_BVH_EDGE = 1, ZR_BVH_VOLUME = 2, ZR_BVH_SURFACE = 3 };
+/* the debug view's answer for one ray */
+typedef struct zr_bvh_debug_hit {
+    zr_hit hit;          /* SURFACE: the record zr_trace gives for that hit; EDGE / VOLUME: t, p = r.at(t), normal (0, 0, 1) (the volume's t is that of
+                            the hit beneath it); mat = 0xFFFFFFFF unless SURFACE */
+    double color[3];     /* what the hit emits: the edge / volume colour, or the surface material's emitted(u, v, p) */
+    uint32_t cls;        /* ZR_BVH_MISS / EDGE / VOLUME / SURFACE */
+    int32_t depth;       /* the deciding box's depth (EDGE: the edge's node, VOLUME: the current-level ancestor, SURFACE: the leaf); -1 on a miss */
+    uint32_t tree;       /* ... its tree (first pair record of the tree) */
+    uint32_t box;        /* ... its box id */
+} zr_bvh_debug_hit;
+/* camera::render with global_settings::bvh_debug_mode set: fills out_rgb like zr_render (host memory, W*H*3 doubles, region, keep_going polled
+ * and rows_done advanced between kernel batches).  ZR_E_INVALID for a level below -1 or a thickness that is not a positive finite number. */
+int zr_render_bvh_debug(zr_ctx*, const zr_scene*, const zr_camera*, const zr_env*, uint64_t seed, const zr_region* region,
+                        const zr_bvh_debug_params*, double* out_rgb, volatile const uint8_t* keep_going, volatile int* rows_done);
+/* known-answer entry: bvh_node::hit in debug mode on the interval (tmin, inf) for n rays (6 doubles each); the medium draw of ray k is keyed
+ * by zr_stream_key(seed, pixel, k) and `bounce`, as in zr_trace */
+int zr_trace_bvh_debug(zr_ctx*, const zr_scene*, const zr_bvh_debug_params*, const double* rays6, size_t n, double tmin, uint64_t seed,
+                       uint64_t pixel, uint32_t bounce, zr_bvh_debug_hit* out);
+/* every box of the committed trees, as the debug view walks them */
+typedef struct zr_tree_box {
+    float lo[3], hi[3];   /* the stored FP32 planes (a root: the union of its record's non-empty children) */
+    uint32_t id;          /* box id (above) */
+    uint32_t tree;        /* first pair record of its tree (0 = the world's) */
+    uint32_t parent;      /* parent's box id, ZR_BVH_NO_BOX for a root */
+    int32_t depth;
+    uint32_t slot;        /* child slot in the parent's record (0 = left); 0 for a root */
+    uint32_t leaf;        /* 1: holds a primitive range */
+    uint32_t kind;        /* leaf: the range's kind: ZR_PRIM_SPHERE / TRIANGLE / CUBE / MEDIUM, 4 wrapped object, 5 cube under translate /
+                             rotate_y / scale, 6 placed run of triangles (ZR_PRIM_GROUP) */
+    uint32_t count;       /* leaf: primitives in the range (1 .. 4) */
+    uint32_t first;       /* leaf: first primitive in the kind's leaf order; inner: the pair record holding its children */
+    uint32_t subtree;     /* leaf of kind 6: the placed run's tree (its first pair record); else ZR_BVH_NO_BOX */
+    uint32_t src[4];      /* leaf: the primitives' indices in the caller's arrays — spheres, triangles, cubes (kinds 2 and 5), media — and, for
+                             kinds 4 and 6, the world-list entry (zr_scene_set_objects, or the implicit list's position) */
+} zr_tree_box;
+/* copies min(cap, n) boxes, world tree first, each tree in pre-order (a box, its left subtree, its right subtree); returns n (or a negative
+ * ZR_E_*).  out may be NULL with cap = 0 to ask for n. */
+int zr_scene_tree_boxes(const zr_scene*, zr_tree_box* out, size_t cap);
+
 /* Known answers for whole paths: walks the primary sample (px, py, sample) of each request on the device and records
  * every segment, ZR_PATH_RECORD doubles each: ray origin, direction | hit flag, t, material id | scattered flag,
  * attenuation rgb | emission rgb | main-stream RNG draws consumed so far.  requests = n * 3 ints; out = n * max_segments *

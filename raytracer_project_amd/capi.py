@@ -105,6 +105,25 @@ class DenoiseParams(C.Structure):
         return p
 
 
+class BvhDebugParams(C.Structure):
+    """zr_bvh_debug_params: global_settings::debug_bvh_level / bvh_thickness of the BVH debug view (include/zr_capi.h, DESIGN §10)"""
+    _fields_ = [("level", C.c_int32), ("thickness", C.c_float)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """ZR_BVH_DEBUG_DEFAULT_LEVEL / _THICKNESS (the reference's global_settings defaults: leaves, 0.01)"""
+        p = cls(-1, 0.01)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"BvhDebugParams has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+BVH_MISS, BVH_EDGE, BVH_VOLUME, BVH_SURFACE = 0, 1, 2, 3
+BVH_ROOT_BOX, BVH_NO_BOX = 0x80000000, 0xFFFFFFFF
+
+
 class ImageStats(C.Structure):
     _fields_ = [("average_luminance", C.c_float), ("max_luminance", C.c_float), ("histogram", C.c_int32 * 256)]
 
@@ -152,6 +171,11 @@ SCATTER_DTYPE = np.dtype([("attenuation", "<f8", 3), ("origin", "<f8", 3), ("dir
 assert SCATTER_DTYPE.itemsize == C.sizeof(ScatterOut)
 
 
+BVH_DEBUG_HIT_DTYPE = np.dtype([("hit", HIT_DTYPE), ("color", "<f8", 3), ("cls", "<u4"), ("depth", "<i4"), ("tree", "<u4"), ("box", "<u4")])
+TREE_BOX_DTYPE = np.dtype([("lo", "<f4", 3), ("hi", "<f4", 3), ("id", "<u4"), ("tree", "<u4"), ("parent", "<u4"), ("depth", "<i4"), ("slot", "<u4"),
+                           ("leaf", "<u4"), ("kind", "<u4"), ("count", "<u4"), ("first", "<u4"), ("subtree", "<u4"), ("src", "<u4", 4)])
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("spheres", C.c_void_p), ("sphere_mat", C.c_void_p), ("n_spheres", C.c_uint64),
                 ("tri_v", C.c_void_p), ("tri_n", C.c_void_p), ("tri_mat", C.c_void_p), ("n_tris", C.c_uint64),
@@ -173,7 +197,8 @@ CAPI_SYMBOLS = [
     "zr_abi_version", "zr_last_error", "zr_create", "zr_destroy", "zr_scene_create", "zr_scene_destroy",
     "zr_scene_set_spheres", "zr_scene_set_triangles", "zr_scene_set_cubes", "zr_scene_set_media",
     "zr_scene_set_xform_ops", "zr_scene_set_objects", "zr_scene_set_groups", "zr_scene_set_materials", "zr_scene_set_textures",
-    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device", "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame", "zr_get_counters",
+    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device", "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
+    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
 
@@ -215,6 +240,9 @@ def load():
     lib.zr_analyze_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(ImageStats)]
     lib.zr_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, i32, i32, vp]
     lib.zr_sharpen_frame.argtypes = [vp, vp, i32, i32, C.c_double, vp]
+    lib.zr_render_bvh_debug.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), C.POINTER(BvhDebugParams), vp, vp, vp]
+    lib.zr_trace_bvh_debug.argtypes = [vp, vp, C.POINTER(BvhDebugParams), vp, C.c_size_t, C.c_double, u64, u64, C.c_uint32, vp]
+    lib.zr_scene_tree_boxes.argtypes = [vp, vp, C.c_size_t]
     lib.zr_trace_paths.argtypes = [vp, vp, C.POINTER(Camera), u64, vp, i32, i32, vp]
     lib.zr_render_passes.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), vp, vp, vp]
     lib.zr_get_counters.argtypes = [vp, C.POINTER(Counters)]
@@ -322,6 +350,18 @@ class DemoScene:
         if rc != 0:
             raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
         return outs
+
+    def render_dropin_bvh_debug(self, level, thickness, width=0, height=0, spp=0, device=0):
+        """camera::render with global_settings::bvh_debug_mode set through include/zenith/zenith.hpp: (render_accumulator,
+        albedo_buffer) as (H, W, 3) float64 (the debug view leaves the AOV buffers as reset_accumulator made them)"""
+        w = width or self.camera.image_width
+        h = height or self.camera.image_height
+        out = np.zeros((h, w, 3), dtype=np.float64); aux = np.full((h, w, 3), -1.0)
+        lib = load_scenes()
+        lib.zrs_render_dropin_bvh_debug.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        if lib.zrs_render_dropin_bvh_debug(self._h, width, height, spp, device, level, thickness, out.ctypes.data, aux.ctypes.data) != 0:
+            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        return out, aux
 
     def dropin_virtuals(self, rays8, seed, pixel=0x7ACE):
         """bvh_node(world).hit + rec.mat->emitted / scatter through the drop-in classes (one device launch per call):
@@ -494,6 +534,40 @@ class Scene:
         _check(self.lib.zr_render_passes(self.ctx._c, self._s, C.byref(camera), C.byref(env), C.c_uint64(seed), rp,
                                          outs[0].ctypes.data, outs[1].ctypes.data, outs[2].ctypes.data))
         return outs
+
+    def render_bvh_debug(self, camera, env, seed, params=None, region=None, out=None, keep_going=None, rows_done=None):
+        """the BVH debug view (global_settings::bvh_debug_mode): (H, W, 3) float64.  keep_going: a ctypes.c_uint8 polled between
+        kernel batches (0 cancels: ZR_E_CANCELLED is raised); rows_done: a ctypes.c_int advanced like camera::lines_rendered"""
+        h, w = camera.image_height, camera.image_width
+        if out is None:
+            out = np.zeros((h, w, 3), dtype=np.float64)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (h, w, 3)
+        params = params if params is not None else BvhDebugParams.defaults()
+        rp = C.byref(region) if region is not None else None
+        _check(self.lib.zr_render_bvh_debug(self.ctx._c, self._s, C.byref(camera), C.byref(env), C.c_uint64(seed), rp, C.byref(params),
+                                            out.ctypes.data, C.byref(keep_going) if keep_going is not None else None,
+                                            C.byref(rows_done) if rows_done is not None else None))
+        return out
+
+    def trace_bvh_debug(self, rays, params=None, tmin=0.001, seed=1, pixel=0x7ACE, bounce=0):
+        """bvh_node::hit in debug mode for (n, 6) rays -> array of BVH_DEBUG_HIT_DTYPE"""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out = np.zeros(len(rays), dtype=BVH_DEBUG_HIT_DTYPE)
+        params = params if params is not None else BvhDebugParams.defaults()
+        _check(self.lib.zr_trace_bvh_debug(self.ctx._c, self._s, C.byref(params), rays.ctypes.data, len(rays), tmin, C.c_uint64(seed),
+                                           C.c_uint64(pixel), bounce, out.ctypes.data))
+        return out
+
+    def tree_boxes(self):
+        """every box of the committed trees (zr_scene_tree_boxes) -> array of TREE_BOX_DTYPE"""
+        n = self.lib.zr_scene_tree_boxes(self._s, None, 0)
+        if n < 0:
+            _check(n)
+        out = np.zeros(n, dtype=TREE_BOX_DTYPE)
+        m = self.lib.zr_scene_tree_boxes(self._s, out.ctypes.data if n else None, n)
+        if m < 0:
+            _check(m)
+        return out
 
     def render_device(self, camera, env, seed, d_ptr, stream=0, region=None, count=False):
         rp = C.byref(region) if region is not None else None

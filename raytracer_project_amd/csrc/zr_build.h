@@ -43,6 +43,7 @@ struct BuildPrimOut {
     double* pcubes = nullptr; uint32_t* pcube_mat = nullptr;
     DInstance* insts = nullptr; uint32_t* inst_group = nullptr;
     uint32_t base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t* src[8] = {};   // per leaf kind (may be null): each leaf primitive's index in the caller's arrays, as Flattener::note_src
 };
 
 // a built tree: device records with indices local to the tree (relocate() moves them into the scene's arrays)

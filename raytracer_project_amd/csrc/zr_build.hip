@@ -700,6 +700,7 @@ __global__ __launch_bounds__(256) void k_emit(BuildSceneIn in, const zr_object* 
     zr_object o; uint32_t bk = 0;
     if (objs) { o = objs[oi]; bk = code[oi] >> 4; }
     else { o.type = ZR_PRIM_TRIANGLE; o.index = first_triangle + oi; o.chain_first = 0; o.chain_count = 0; }
+    if (out.src[kind]) out.src[kind][di] = (kind == ZR_KIND_WRAPPED || kind == ZR_KIND_INSTANCE) ? oi : o.index;
     if (kind == ZR_PRIM_MEDIUM || kind == ZR_KIND_WRAPPED) {   // compound: the host finishes these few (inner primitives behind the leaf ranges)
         const uint32_t at = atomicAdd(n_compound, 1u);
         compound[2 * at] = oi; compound[2 * at + 1] = (uint32_t)di;

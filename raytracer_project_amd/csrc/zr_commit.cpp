@@ -228,7 +228,17 @@ int commit_device(zr_scene* s, const std::vector<zr_object>& objs, bool commit_s
         const double top_env = env_double("ZR_BVH_TOP", -1);
         bp.top_clusters = top_env >= 0 ? (int)top_env : (int)std::min<size_t>(65536, std::max<size_t>(4096, (size_t)n / 64));
     }
+    // leaf primitive -> caller index (zr_scene_tree_boxes), written by the emit kernel
+    DevBuf<uint32_t> d_src[8];
+    {
+        const size_t sz[8] = {n_sph, n_tri, n_cube, n_media, n_wrapped, n_pcube, n_insts, 0};
+        for (int k = 0; k < 7; k++) {
+            if ((rc = d_src[k].alloc(sz[k]))) return rc;
+            HIP_OK(hipMemsetAsync(d_src[k].p, 0xFF, std::max<size_t>(sz[k], 1) * 4, st));
+        }
+    }
     zr::BuildPrimOut out;
+    for (int k = 0; k < 7; k++) out.src[k] = d_src[k].p;
     out.spheres = s->d_spheres.p; out.sphere_mat = s->d_sphere_mat.p; out.tri_v = s->d_tri_v.p; out.tri_s = s->d_tri_s.p;
     out.cubes = s->d_cubes.p; out.cube_mat = s->d_cube_mat.p; out.pcubes = s->d_pcubes.p; out.pcube_mat = s->d_pcube_mat.p;
     out.insts = s->d_insts.p; out.inst_group = d_inst_group.p;
@@ -352,6 +362,10 @@ int commit_device(zr_scene* s, const std::vector<zr_object>& objs, bool commit_s
         HIP_OK(hipStreamSynchronize(st));   // (the staging arrays die with this block)
     }
     HIP_OK(hipStreamSynchronize(st));
+    for (int k = 0; k < 8; k++) {
+        s->leaf_src[k].assign(d_src[k].n, 0xFFFFFFFFu);
+        if (d_src[k].n) HIP_OK(hipMemcpy(s->leaf_src[k].data(), d_src[k].p, d_src[k].n * 4, hipMemcpyDeviceToHost));
+    }
     phase("node arrays + compound");
     cs.root = world.root; cs.quant_ok = world.quant_ok;
     for (const zr::BuiltTree& r : runs) cs.quant_ok = cs.quant_ok && r.quant_ok;
@@ -607,6 +621,7 @@ int zr_scene_commit(zr_scene* s) {
     fl.baked = &baked;
     fl.runs = runs.empty() ? nullptr : &runs;
     fl.open_ratio = env_double("ZR_BVH_OPEN_RATIO", 1.25);
+    fl.want_src = true;
     // the primitive arrays (a quarter of a gigabyte for a million triangles) go to the device while the host still plans and
     // numbers the 4-wide nodes: a thread of its own, joined before the node arrays follow
     int up_rc = ZR_OK;
@@ -646,6 +661,7 @@ int zr_scene_commit(zr_scene* s) {
         fl.after_primitives(); if (uploader.joinable()) uploader.join();
     }
     if (up_rc != ZR_OK) return fail(up_rc, "%s", up_err.c_str());
+    for (int k = 0; k < 8; k++) s->leaf_src[k] = std::move(fl.src[k]);
     CommitSummary cs;
     cs.root = fl.root; cs.quant_ok = fl.quant_ok; cs.n_pairs = fl.pairs.size(); cs.n_quads = fl.quads.size();
     cs.n_sph = fl.sphere_mat.size(); cs.n_tri = fl.tri_s.size() / 20; cs.n_cube = fl.cube_mat.size(); cs.n_pcube = fl.pcube_mat.size();
@@ -673,6 +689,72 @@ int zr_scene_stats(const zr_scene* s, uint64_t out[4]) {
     if (!s || !s->committed) return fail(ZR_E_STATE, "scene not committed");
     std::memcpy(out, s->stats, sizeof s->stats);
     return ZR_OK;
+}
+
+int zr_scene_tree_boxes(const zr_scene* s, zr_tree_box* out, size_t cap) {
+    if (!s) return fail(ZR_E_INVALID, "null scene");
+    if (!s->committed) return fail(ZR_E_STATE, "scene not committed");
+    if (cap && !out) return fail(ZR_E_INVALID, "null output array");
+    HIP_OK(hipSetDevice(s->device));
+    const size_t n_pairs = s->d_nodes.n;
+    std::vector<zr::NodePair> pairs(n_pairs);
+    std::vector<zr::DInstance> insts(s->d_insts.n);
+    if (n_pairs) HIP_OK(hipMemcpy(pairs.data(), s->d_nodes.p, n_pairs * sizeof(zr::NodePair), hipMemcpyDeviceToHost));
+    if (!insts.empty()) HIP_OK(hipMemcpy(insts.data(), s->d_insts.p, insts.size() * sizeof(zr::DInstance), hipMemcpyDeviceToHost));
+    auto empty = [](uint32_t meta) { return meta != 0 && (meta & 0xFFFFu) == 0; };
+    std::vector<zr_tree_box> boxes;
+    // one tree from its first record R, in pre-order (the order the debug walk meets its boxes)
+    auto walk = [&](uint32_t R) -> int {
+        if (R >= n_pairs) return fail(ZR_E_DEVICE, "tree root %u outside the %zu pair records (internal error)", R, n_pairs);
+        const zr::NodePair& rp = pairs[R];
+        const bool e0 = empty(rp.meta[0]), e1 = empty(rp.meta[1]);
+        if (e0 && e1) return ZR_OK;
+        zr_tree_box root{};
+        for (int a = 0; a < 3; a++) {
+            root.lo[a] = e0 ? rp.lo[1][a] : (e1 ? rp.lo[0][a] : std::fmin(rp.lo[0][a], rp.lo[1][a]));
+            root.hi[a] = e0 ? rp.hi[1][a] : (e1 ? rp.hi[0][a] : std::fmax(rp.hi[0][a], rp.hi[1][a]));
+        }
+        root.id = ZR_BVH_ROOT_BOX | R; root.tree = R; root.parent = ZR_BVH_NO_BOX; root.depth = 0; root.first = R; root.subtree = ZR_BVH_NO_BOX;
+        boxes.push_back(root);
+        struct E { uint32_t id; int depth; uint32_t parent; };   // a child box: id = 2 * record + slot
+        std::vector<E> st;
+        auto push_children = [&](uint32_t rec, int depth, uint32_t parent) {   // right first: the left subtree is emitted first
+            for (int s2 = 1; s2 >= 0; s2--) if (!empty(pairs[rec].meta[s2])) st.push_back({2 * rec + (uint32_t)s2, depth, parent});
+        };
+        push_children(R, 1, root.id);
+        while (!st.empty()) {
+            const E e = st.back(); st.pop_back();
+            if (e.depth > ZR_STACK_DEPTH + 2) return fail(ZR_E_DEVICE, "tree %u deeper than the traversal stack (internal error)", R);
+            const uint32_t rec = e.id >> 1, s2 = e.id & 1u;
+            const zr::NodePair& np = pairs[rec];
+            zr_tree_box b{};
+            for (int a = 0; a < 3; a++) { b.lo[a] = np.lo[s2][a]; b.hi[a] = np.hi[s2][a]; }
+            b.id = e.id; b.tree = R; b.parent = e.parent; b.depth = e.depth; b.slot = s2; b.subtree = ZR_BVH_NO_BOX; b.first = np.child[s2];
+            for (int k = 0; k < 4; k++) b.src[k] = ZR_BVH_NO_BOX;
+            if (np.meta[s2] != 0) {
+                b.leaf = 1; b.kind = (np.meta[s2] >> 16) - 1; b.count = np.meta[s2] & 0xFFFFu;
+                const std::vector<uint32_t>& src = s->leaf_src[b.kind & 7];
+                for (uint32_t k = 0; k < b.count && k < 4; k++) if ((size_t)b.first + k < src.size()) b.src[k] = src[b.first + k];
+                if (b.kind == ZR_KIND_INSTANCE && b.first < insts.size()) b.subtree = insts[b.first].root;
+            }
+            boxes.push_back(b);
+            if (np.meta[s2] == 0) {
+                if (b.first >= n_pairs) return fail(ZR_E_DEVICE, "child record %u outside the %zu pair records (internal error)", b.first, n_pairs);
+                push_children(b.first, e.depth + 1, b.id);
+            }
+        }
+        return ZR_OK;
+    };
+    int rc = walk(0);
+    if (rc) return rc;
+    std::vector<uint32_t> roots;
+    for (const zr::DInstance& in : insts) roots.push_back(in.root);
+    std::sort(roots.begin(), roots.end());
+    roots.erase(std::unique(roots.begin(), roots.end()), roots.end());
+    for (uint32_t R : roots) if ((rc = walk(R))) return rc;
+    const size_t n = std::min(cap, boxes.size());
+    if (n) std::memcpy(out, boxes.data(), n * sizeof(zr_tree_box));
+    return (int)std::min<size_t>(boxes.size(), 0x7FFFFFFF);
 }
 
 uint32_t zr_scene_traversal_stack(const zr_scene* s) { return s && s->committed ? s->stack_demand : 0u; }

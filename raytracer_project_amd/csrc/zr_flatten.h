@@ -195,6 +195,8 @@ struct Flattener {
     size_t n_sph = 0, n_tri = 0, n_cube = 0, n_pcube = 0, n_media = 0, n_wrapped = 0;   // filled sizes (the arrays are sized exactly)
     std::function<void()> after_primitives;   // called by run() once spheres / triangles / cubes / media / wrapped are complete
     const std::vector<uint8_t>* baked = nullptr;   // per object: 0 as is, 1 baked triangle, 2 material-only chain, 3 baked sphere, 4 placed cube
+    bool want_src = false;                         // fill src: per leaf kind, each leaf primitive's index in the caller's arrays (zr_scene::leaf_src)
+    std::vector<uint32_t> src[8];
     size_t n_baked = 0;
     int threads = 1;
 
@@ -351,6 +353,10 @@ struct Flattener {
         std::memcpy(&pcubes[di * ZR_PCUBE_STRIDE], rec, sizeof rec);
         pcube_mat[di] = mat;
     }
+    // where leaf primitive `di` of kind `kind` came from: the world-list entry for wrapped objects and placed runs, else the primitive's own index
+    void note_src(uint32_t kind, size_t di, uint32_t oi) {
+        if (want_src) src[kind & 7][di] = (kind == ZR_KIND_WRAPPED || kind == ZR_KIND_INSTANCE) ? oi : objs[oi].index;
+    }
     // object `oi` as a leaf primitive of a plain kind (sphere / triangle / cube / placed cube) at index di of that kind's array
     void put_leaf_object(uint32_t oi, size_t di) {
         const zr_object& o = objs[oi];
@@ -391,7 +397,10 @@ struct Flattener {
             const zr::BuildNode& n = rb.nodes[id];
             if (!n.count) continue;
             first_of[id] = (uint32_t)n_tri;
-            for (uint32_t k = 0; k < n.count; k++) { put_triangle(n_tri, grp.first_triangle + rb.order[n.first + k]); n_tri++; }
+            for (uint32_t k = 0; k < n.count; k++) {
+                if (want_src) src[ZR_PRIM_TRIANGLE][n_tri] = grp.first_triangle + rb.order[n.first + k];
+                put_triangle(n_tri, grp.first_triangle + rb.order[n.first + k]); n_tri++;
+            }
         }
         auto leaf_tris = [&](const zr::BuildNode& n) { return first_of[(size_t)(&n - &rb.nodes[0])]; };
         if (rb.nodes[0].count) {
@@ -751,12 +760,19 @@ struct Flattener {
         cubes.allocate((n_cube + x_cube) * 6); cube_mat.allocate(n_cube + x_cube);
         pcubes.allocate(n_pcube * ZR_PCUBE_STRIDE); pcube_mat.allocate(n_pcube);
         media.allocate(n_media + x_media); wrapped.allocate(n_wrapped);
+        if (want_src) {
+            const size_t sz[8] = {n_sph + x_sph, n_tri + x_tri, n_cube + x_cube, n_media + x_media, n_wrapped, n_pcube, cnt[ZR_KIND_INSTANCE], 0};
+            for (int k = 0; k < 8; k++) src[k].assign(sz[k], 0xFFFFFFFFu);
+        }
         // 3. leaf primitives of the plain kinds: all threads
         parallel_for(leaves.size(), 2048, [&](size_t a, size_t b) {
             for (size_t i = a; i < b; i++) {
                 const zr::BuildNode& n = br.nodes[leaves[i]];
                 if (n.kind == ZR_PRIM_MEDIUM || n.kind == ZR_KIND_WRAPPED) continue;
-                for (uint32_t k = 0; k < n.count; k++) put_leaf_object(br.order[n.first + k], (size_t)leaf_first[leaves[i]] + k);
+                for (uint32_t k = 0; k < n.count; k++) {
+                    put_leaf_object(br.order[n.first + k], (size_t)leaf_first[leaves[i]] + k);
+                    note_src(n.kind, (size_t)leaf_first[leaves[i]] + k, br.order[n.first + k]);
+                }
             }
         });
         if (runs) for (size_t g = 0; g < runs->size(); g++) emit_run((uint32_t)g, run_root[g]);   // serial: runs are shared, hence few
@@ -768,6 +784,7 @@ struct Flattener {
             for (uint32_t k = 0; k < n.count; k++) {
                 const zr_object& o = objs[br.order[n.first + k]];
                 const size_t di = (size_t)leaf_first[lf] + k;
+                note_src(n.kind, di, br.order[n.first + k]);
                 if (n.kind == ZR_PRIM_MEDIUM) put_medium(di, o.index);
                 else {
                     zr::DWrapped w{};

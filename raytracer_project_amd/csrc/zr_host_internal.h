@@ -208,6 +208,8 @@ struct zr_scene {
     bool fused_ok = false;
     uint64_t stats[4] = {0, 0, 0, 0};
     const char* builder = "";   // which builder made the committed tree (zr_scene_builder)
+    std::vector<uint32_t> leaf_src[8];   // per leaf kind, in that kind's array order: a leaf primitive's index in the caller's arrays (zr_scene_tree_boxes);
+                                         // 0xFFFFFFFF for the primitives inside media and wrapper chains
 };
 
 struct CommitSummary {   // what the shared end of a commit needs to know about the tree either builder produced

@@ -80,6 +80,10 @@ hipError_t launch_sharpen(const double* d_in, double* d_out, int W, int H, doubl
 hipError_t launch_denoise(const double* d_color, const double* d_albedo, const double* d_normal, const double* d_zdepth, int W, int H,
                           const zr_denoise_params& dp, float4* d_col0, float4* d_col1, float4* d_g0, float4* d_g1, double* d_out,
                           hipStream_t stream);
+hipError_t launch_bvh_debug(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, int level, float thickness, double* out,
+                            hipStream_t stream);
+hipError_t launch_trace_bvh_debug(const DScene& sc, const double* rays, size_t n, double tmin, uint64_t seed, uint64_t pixel, uint32_t bounce, int level,
+                                  float thickness, zr_bvh_debug_hit* out, hipStream_t stream);
 #define ZR_PATH_REC 17
 hipError_t launch_path_records(const DScene& sc, const DCamera& cam, uint64_t seed, const int32_t* req, int n_req, int max_seg, double* out,
                                hipStream_t stream);

@@ -627,6 +627,92 @@ int zr_analyze_frame(zr_ctx* c, const double* frame, size_t n, zr_image_stats* o
     return ZR_OK;
 }
 
+namespace {
+int check_debug_params(const zr_bvh_debug_params* dp) {
+    if (!dp) return fail(ZR_E_INVALID, "null argument");
+    if (dp->level < -1) return fail(ZR_E_INVALID, "BVH debug level %d below -1", dp->level);
+    if (!(dp->thickness > 0.0f) || !std::isfinite(dp->thickness)) return fail(ZR_E_INVALID, "BVH debug thickness must be a positive finite number");
+    return ZR_OK;
+}
+}  // namespace
+
+int zr_render_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region,
+                        const zr_bvh_debug_params* dp, double* out_rgb, volatile const uint8_t* keep_going, volatile int* rows_done) {
+    if (!c || !s || !cam || !env || !out_rgb) return fail(ZR_E_INVALID, "null argument");
+    int rc = check_debug_params(dp);
+    if (rc) return rc;
+    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_render_bvh_debug");
+    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
+    HIP_OK(hipSetDevice(c->device));
+    Plan plan;
+    if ((rc = make_plan(*cam, region, plan))) return rc;
+    zr::DCamera dc; make_camera(*cam, dc);
+    zr::DEnv de; make_env(*env, de);
+    if (de.mode > ZR_ENV_SOLID_COLOR) return fail(ZR_E_INVALID, "unknown environment mode %u", de.mode);
+    if (de.mode == ZR_ENV_HDR_MAP && de.hdr_tex != ZR_NO_TEXTURE && de.hdr_tex >= s->textures.size()) return fail(ZR_E_INVALID, "environment texture id out of range");
+    const size_t npx = (size_t)plan.W * plan.H;
+    if ((rc = c->d_out.alloc(npx * 3))) return rc;
+    HIP_OK(hipMemsetAsync(c->d_out.p, 0, npx * 3 * sizeof(double), c->stream));
+    if (rows_done) *rows_done = 0;
+    std::vector<int32_t> tiles = plan.tiles;
+    if ((rc = c->d_tiles.upload(tiles))) return rc;
+    // one launch per frame unless the caller polls (cancellation, progress): then batches of tiles with the poll between them, as zr_render's
+    // pixel-group path does
+    const bool interactive = keep_going || rows_done;
+    const size_t batch = (size_t)std::max(1, (int)env_double("ZR_BATCH_TILES", interactive ? 256 : (double)(1 << 30)));
+    const size_t n_batches = (tiles.size() + batch - 1) / batch;
+    int rrc = ZR_OK;
+    for (size_t b = 0; b < n_batches; b++) {
+        if (keep_going && *keep_going == 0) { rrc = ZR_E_CANCELLED; fail(rrc, "render cancelled after %zu of %zu batches", b, n_batches); break; }
+        zr::WorkDesc wd;
+        wd.tiles = c->d_tiles.p + b * batch;
+        wd.n_tiles = (int32_t)std::min(batch, tiles.size() - b * batch);
+        wd.tile_size = plan.ts; wd.tiles_x = plan.tiles_x;
+        wd.x0 = plan.x0; wd.y0 = plan.y0; wd.x1 = plan.x1; wd.y1 = plan.y1;
+        wd.lanes_per_pixel = 1;
+        HIP_OK(zr::launch_bvh_debug(s->ds, dc, de, seed, wd, dp->level, dp->thickness, c->d_out.p, c->stream));
+        if (interactive) {
+            HIP_OK(hipStreamSynchronize(c->stream));
+            if (rows_done) {
+                const int last_tile = tiles[std::min(tiles.size(), (b + 1) * batch) - 1];
+                const int rows = std::min(plan.H, (last_tile / plan.tiles_x + 1) * plan.ts);
+                if (rows > *rows_done) *rows_done = b + 1 == n_batches ? plan.H : rows;
+            }
+        }
+    }
+    std::string cancel_msg = zr_host::last_error();
+    HIP_OK(hipStreamSynchronize(c->stream));
+    // the region's pixels of the device frame -> the caller's buffer (other pixels are not touched)
+    std::vector<double> frame(npx * 3);
+    HIP_OK(hipMemcpy(frame.data(), c->d_out.p, frame.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int32_t t : plan.tiles) {
+        int tx = (t % plan.tiles_x) * plan.ts, ty = (t / plan.tiles_x) * plan.ts;
+        int xa = std::max(tx, plan.x0), xb = std::min(tx + plan.ts, plan.x1), ya = std::max(ty, plan.y0), yb = std::min(ty + plan.ts, plan.y1);
+        for (int y = ya; y < yb; y++)
+            if (xb > xa) std::memcpy(out_rgb + ((size_t)y * plan.W + xa) * 3, frame.data() + ((size_t)y * plan.W + xa) * 3, (size_t)(xb - xa) * 3 * sizeof(double));
+    }
+    if (rrc == ZR_E_CANCELLED) return fail(rrc, "%s", cancel_msg.c_str());
+    if (rows_done) *rows_done = plan.H;
+    return ZR_OK;
+}
+
+int zr_trace_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_bvh_debug_params* dp, const double* rays6, size_t n, double tmin, uint64_t seed,
+                       uint64_t pixel, uint32_t bounce, zr_bvh_debug_hit* out) {
+    if (!c || !s || (n && (!rays6 || !out))) return fail(ZR_E_INVALID, "null argument");
+    int rc = check_debug_params(dp);
+    if (rc) return rc;
+    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_trace_bvh_debug");
+    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
+    if (n == 0) return ZR_OK;
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<double> d_rays; DevBuf<zr_bvh_debug_hit> d_out;
+    if ((rc = d_rays.upload(std::vector<double>(rays6, rays6 + n * 6))) || (rc = d_out.alloc(n))) return rc;
+    HIP_OK(zr::launch_trace_bvh_debug(s->ds, d_rays.p, n, tmin, seed, pixel, bounce, dp->level, dp->thickness, d_out.p, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    HIP_OK(hipMemcpy(out, d_out.p, n * sizeof(zr_bvh_debug_hit), hipMemcpyDeviceToHost));
+    return ZR_OK;
+}
+
 int zr_trace_paths(zr_ctx* c, const zr_scene* s, const zr_camera* cam, uint64_t seed, const int32_t* requests, int n, int max_segments, double* out) {
     if (!c || !s || !cam || (n > 0 && (!requests || !out))) return fail(ZR_E_INVALID, "null argument");
     if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_trace_paths");

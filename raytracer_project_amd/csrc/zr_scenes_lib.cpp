@@ -81,6 +81,38 @@ int zrs_render_dropin(void* p, int width, int height, int spp, int device, doubl
     return 0;
 }
 
+// camera::render with global_settings::bvh_debug_mode set (debug_bvh_level = level, bvh_thickness = thickness) through the drop-in API; the
+// settings are restored afterwards.  `aux`, when not null, receives albedo_buffer (which the debug view leaves as reset_accumulator made it).
+// Returns 0, or -1 if the render did not finish.
+int zrs_render_dropin_bvh_debug(void* p, int width, int height, int spp, int device, int level, float thickness, double* out, double* aux) {
+    handle* h = (handle*)p;
+    camera cam;
+    const zr_camera& c = h->s.cam;
+    cam.image_width = width > 0 ? width : c.image_width;
+    cam.image_height = height > 0 ? height : c.image_height;
+    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
+    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
+    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
+    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
+    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
+    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
+    cam.seed = h->s.seed; cam.device = device;
+    cam.use_albedo_buffer = aux != nullptr;
+    cam.reset_accumulator();
+    post_processor post;
+    post.debug.bvh = true;   // main.cpp:1039-1044
+    const bool m0 = global_settings::bvh_debug_mode; const float t0 = global_settings::bvh_thickness; const int l0 = global_settings::debug_bvh_level;
+    global_settings::bvh_debug_mode = true; global_settings::bvh_thickness = thickness; global_settings::debug_bvh_level = level;
+    std::atomic<bool> flag{true};
+    auto bvh_world = make_shared<bvh_node>(h->s.world);
+    cam.render(*bvh_world, h->s.env, post, flag);
+    global_settings::bvh_debug_mode = m0; global_settings::bvh_thickness = t0; global_settings::debug_bvh_level = l0;
+    if (cam.lines_rendered.load() != cam.image_height) return -1;
+    std::memcpy(out, cam.render_accumulator.data(), cam.render_accumulator.size() * sizeof(color));
+    if (aux) std::memcpy(aux, cam.albedo_buffer.data(), cam.albedo_buffer.size() * sizeof(color));
+    return 0;
+}
+
 // The reference starts a fresh thread for every render (main.cpp:1520-1531): `n` renders of the scene, each on a thread of its own,
 // one after the other.  Returns the number of device contexts the process has created so far (the drop-in keeps them in a
 // process-wide pool: successive threads share one), or -1 if a render failed; `out` receives the last frame.
@@ -227,6 +259,9 @@ extern "C" size_t zrs_sizeof(int which) {
         case 12: return sizeof(zr_image_stats);
         case 13: return sizeof(zr_aov_params);
         case 14: return sizeof(zr_denoise_params);
+        case 15: return sizeof(zr_bvh_debug_params);
+        case 16: return sizeof(zr_bvh_debug_hit);
+        case 17: return sizeof(zr_tree_box);
         default: return 0;
     }
 }
