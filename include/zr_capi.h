@@ -257,6 +257,10 @@ int zr_scene_commit(zr_scene*);
 /* sizes of the committed scene: out[0]=bvh nodes (child-pair records), [1]=max depth, [2]=objects,
  * [3]=device bytes */
 int zr_scene_stats(const zr_scene*, uint64_t out[4]);
+/* which kernel builds the committed scene renders through: out[0] = the EXTEND build (0 bare triangles / spheres, 1 + cubes and
+ * unwrapped media, 2 + wrapped objects and media, 3 + placed runs of triangles; ZR_EXTEND_LEVEL may only raise it), [1] = 1 for
+ * SHADE's lean build, [2] = 1 when the world may take the fused small-scene kernel (zr_counters::path 3), [3] = leaf objects */
+int zr_scene_kernels(const zr_scene*, uint32_t out[4]);
 /* traversal-stack bound of the committed scene: the exact worst-case number of entries one ray's stack can hold while
  * walking the 4-wide tree (the recursion depth of bvh_node::hit, bvh.hpp:46-54, has no bound in the reference; here the
  * per-wave spill slabs are sized from this number, so no scene can overrun them); 0 = not committed */

@@ -197,7 +197,7 @@ CAPI_SYMBOLS = [
     "zr_abi_version", "zr_last_error", "zr_create", "zr_destroy", "zr_scene_create", "zr_scene_destroy",
     "zr_scene_set_spheres", "zr_scene_set_triangles", "zr_scene_set_cubes", "zr_scene_set_media",
     "zr_scene_set_xform_ops", "zr_scene_set_objects", "zr_scene_set_groups", "zr_scene_set_materials", "zr_scene_set_textures",
-    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device", "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
+    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_kernels", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device", "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
@@ -231,6 +231,7 @@ def load():
     lib.zr_scene_set_textures.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     lib.zr_scene_commit.argtypes = [vp]
     lib.zr_scene_stats.argtypes = [vp, C.POINTER(u64 * 4)]
+    lib.zr_scene_kernels.argtypes = [vp, C.POINTER(C.c_uint32 * 4)]
     lib.zr_scene_traversal_stack.argtypes = [vp]; lib.zr_scene_traversal_stack.restype = C.c_uint32
     lib.zr_scene_builder.argtypes = [vp]; lib.zr_scene_builder.restype = C.c_char_p
     lib.zr_render.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), i32, vp, vp, vp]
@@ -495,6 +496,12 @@ class Scene:
         _check(self.lib.zr_scene_stats(self._s, C.byref(out)))
         return {"bvh_pairs": out[0], "bvh_depth": out[1], "objects": out[2], "device_bytes": out[3],
                 "traversal_stack": int(self.lib.zr_scene_traversal_stack(self._s)), "builder": self.lib.zr_scene_builder(self._s).decode()}
+
+    def kernels(self):
+        """the kernel builds the committed scene renders through (zr_scene_kernels)"""
+        out = (C.c_uint32 * 4)()
+        _check(self.lib.zr_scene_kernels(self._s, C.byref(out)))
+        return {"extend_level": out[0], "shade_lean": out[1], "fused_ok": out[2], "leaf_objects": out[3]}
 
     def render(self, camera, env, seed, region=None, count=False, out=None):
         h, w = camera.image_height, camera.image_width

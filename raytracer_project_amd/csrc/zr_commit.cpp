@@ -691,6 +691,13 @@ int zr_scene_stats(const zr_scene* s, uint64_t out[4]) {
     return ZR_OK;
 }
 
+int zr_scene_kernels(const zr_scene* s, uint32_t out[4]) {
+    if (!s || !out) return fail(ZR_E_INVALID, "null argument");
+    if (!s->committed) return fail(ZR_E_STATE, "scene not committed");
+    out[0] = (uint32_t)s->leaf_level; out[1] = s->ds.shade_lean; out[2] = s->fused_ok ? 1u : 0u; out[3] = (uint32_t)s->leaf_objects;
+    return ZR_OK;
+}
+
 int zr_scene_tree_boxes(const zr_scene* s, zr_tree_box* out, size_t cap) {
     if (!s) return fail(ZR_E_INVALID, "null scene");
     if (!s->committed) return fail(ZR_E_STATE, "scene not committed");

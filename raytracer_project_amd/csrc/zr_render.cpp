@@ -513,6 +513,7 @@ int zr_render_passes(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const z
         if ((rc = render_stream(c, s, dc, de, seed, plan, 0, d_b.p, c->stream, nullptr, 1))) return rc;
         HIP_OK(hipMemcpy(ha, c->d_ctr.p, sizeof ha, hipMemcpyDeviceToHost));
         if ((rc = render_stream(c, s, dc, de, seed, plan, 0, d_r.p, c->stream, nullptr, 2, d_f.p))) return rc;
+        c->last_path = 2;
         HIP_OK(hipMemcpy(hb, c->d_ctr.p, sizeof hb, hipMemcpyDeviceToHost));
         // counted by SHADE in both passes (EXTEND runs uninstrumented): samples, segments, hits, draws
         unsigned long long h[16] = {0};
@@ -521,7 +522,7 @@ int zr_render_passes(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const z
         HIP_OK(hipMemcpy(c->d_ctr.p, h, sizeof h, hipMemcpyHostToDevice));
         c->last_counted = true;
     } else {
-        c->render_id++; c->last_counted = true; c->last_rounds = 0;
+        c->render_id++; c->last_counted = true; c->last_rounds = 0; c->last_path = 0;
         HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, 48 * sizeof(unsigned long long), c->stream));
         HIP_OK(zr::launch_passes(s->ds, dc, de, seed, wd, d_b.p, d_r.p, d_f.p, c->d_ctr.p, c->stream));
     }

@@ -463,13 +463,16 @@ def test_unit_order_does_not_change_the_image(built, monkeypatch):
 @pytest.mark.parametrize("var,values", [("ZR_STREAM_POOLS", ("1", "2", "3")), ("ZR_EXTEND_LEVEL", ("-1", "2"))])
 def test_pipeline_shape_does_not_change_the_image(var, values, built, monkeypatch):
     """Sub-pools on separate HIP streams (the default for a rank's share of a sharded frame) and the build of the traversal
-    kernel chosen for a scene (lean / cubes-and-media / everything) are scheduling and code-size choices: same bits, same counters."""
+    kernel chosen for a scene (lean / cubes-and-media / everything) are scheduling and code-size choices: same bits, same counters.
+    Every frame is the streaming pipeline's (ZR_FUSED=0: cfg5 would otherwise take the fused kernel); cfg5 compares EXTEND's level-1
+    build with its level-2 build."""
     from raytracer_project_amd import capi
+    monkeypatch.setenv("ZR_FUSED", "0")
     for name in ("mix0", "cfg5" if var == "ZR_EXTEND_LEVEL" else "mix1"):
         ds = demo_scene(name)
         cam = ds.camera.copy()
         cam.samples_per_pixel = min(cam.samples_per_pixel, 48)
-        frames, ctrs = [], []
+        frames, ctrs, levels = [], [], []
         for v in values:
             monkeypatch.setenv(var, v)
             monkeypatch.setenv("ZR_STREAM_SLOTS", "262144")   # a pool small enough to be split
@@ -478,10 +481,14 @@ def test_pipeline_shape_does_not_change_the_image(var, values, built, monkeypatc
                 sc = capi.Scene(c, ds.desc)
                 frames.append(sc.render(cam, ds.env, ds.seed, None, count=True))
                 k = c.counters()
+                assert k.path == 2, (name, var, v, k.path)
                 ctrs.append((k.segments, k.rng_draws, k.primary_samples, k.hits))
+                levels.append(sc.kernels()["extend_level"])
                 sc.close()
             finally:
                 c.close()
+        if name == "cfg5":
+            assert levels == [1, 2], levels
         for f, k in zip(frames[1:], ctrs[1:]):
             assert np.array_equal(frames[0], f) and ctrs[0] == k, (name, var)
 
@@ -643,11 +650,13 @@ def test_bench_line_names_its_bound_from_counters(built, workload):
 
 def test_lean_shade_build_renders_the_general_builds_image(ctx, monkeypatch):
     """SHADE's lean build (zr_device.h lean_rec / lean_shade: worlds of bare triangles and spheres over solid-colour lambertian / metal / dielectric / light
-    materials, chosen at commit) leaves code out, not arithmetic: the frame equals the general build's — bit for bit on cfg3 (lambertian) and the instanced-free
-    sphere scene cfg2 at reduced size except where a dielectric's Schlick weight is involved (x^5 by three multiplications instead of pow: within 1e-12),
-    and the two sub-pools the lean pair runs on change nothing either."""
+    materials, chosen at commit) leaves code out, not arithmetic: the frame equals the general build's bit for bit, on cfg3 (lambertian) and on the sphere
+    scene cfg2 at reduced size, and the two sub-pools the lean pair runs on change nothing either.  The one arithmetic difference, a dielectric's Schlick
+    weight as x^5 by three multiplications instead of pow (within 2 ulp), only meets a comparison with a random number: a different last bit would flip a
+    scatter decision (~1e-16 per dielectric hit), not move a value by 1e-12, so there is no tolerance to allow.  Both builds render through the pipeline
+    (test_render_paths.py checks the general build's cfg2 tiles against the reference fixtures)."""
     from raytracer_project_amd import capi
-    for name, args, spp, exact in (("cfg3", (200, 20, 256, 128), 16, True), ("cfg2", (), 4, False)):
+    for name, args, spp in (("cfg3", (200, 20, 256, 128), 16), ("cfg2", (), 4)):
         ds = demo_scene(name, args)
         cam = ds.camera.copy(); cam.samples_per_pixel = spp
         reg = capi.Region(0, 0, 640, 360, 0, 0, 0, 0) if name == "cfg2" else None
@@ -656,12 +665,11 @@ def test_lean_shade_build_renders_the_general_builds_image(ctx, monkeypatch):
             monkeypatch.setenv("ZR_SHADE_LEAN", lean)
             sc = capi.Scene(ctx, ds.desc)
             frames[lean] = sc.render(cam, ds.env, ds.seed, reg)
+            assert (ctx.counters().path, sc.kernels()["shade_lean"]) == (2, int(lean)), (name, lean)
             sc.close()
         monkeypatch.delenv("ZR_SHADE_LEAN")
-        if exact:
-            assert np.array_equal(frames["1"], frames["0"]), name
-        else:
-            assert rel_err(frames["1"], frames["0"], 1e-6).max() < 1e-9, name
+        d = frames["1"] != frames["0"]
+        assert not d.any(), (name, int(d.sum()), rel_err(frames["1"], frames["0"], 1e-6).max())
         assert float(frames["1"].sum()) > 0
 
 
