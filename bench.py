@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s (ray·bounces = closest-hit segments per second) of the per-pixel sample loop on MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W [--workload cfg3|cfg2|cfg5] [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W [--workload cfg3|cfg2|cfg5] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one full frame of the workload (every pixel, every sample, all bounces).  Default workload = cfg3 of
@@ -15,6 +15,12 @@ its N ranks itself (fresh child processes through torch.distributed.run, before 
 
 The timed region starts with the scene (BVH, vertices, normals, HDRI) resident in HBM and contains: zeroing the
 accumulator, the render kernel(s), the RCCL exchange.  One JSON line is printed by rank 0.
+
+A plain run does what the headline needs: it builds and commits the scene once, renders one counting step (the segment
+count the headline divides by comes from it; the roofline is priced on the same counts and on the timed launches),
+warms up, times the steps, writes the frame with --dump-outputs and prints the line.  --full adds what takes runs of
+its own: a second commit, whose time is the restart cost (`config.bvh_build_upload_s`, null without --full), and the
+CPU baseline (`cpu_baseline`: the reference and the CPU restatement on host cores, about 65 s on cfg3).
 """
 import argparse
 import glob
@@ -154,7 +160,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (invalidates the headline number)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the restart commit and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--kernel-src-sha", action="store_true", help="print the source hash profiles/*_traffic.json are keyed by, and exit")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the frame the last step computed to DIR/radiance.npy")
     args = ap.parse_args()
@@ -202,12 +209,14 @@ def main():
     t0 = time.perf_counter()
     sc = capi.Scene(ctx, ds.desc)           # BVH build + upload: reported, not timed
     t_commit_first = time.perf_counter() - t0
-    # the reference rebuilds its BVH on every render restart (main.cpp:1492-1500): what a restart costs is a commit in a process that
-    # has committed before (the first one also loads the code objects and warms the allocator); both are reported
-    sc.close()
-    t0 = time.perf_counter()
-    sc = capi.Scene(ctx, ds.desc)
-    t_commit = time.perf_counter() - t0
+    t_commit = None
+    if args.full:
+        # the reference rebuilds its BVH on every render restart (main.cpp:1492-1500): what a restart costs is a commit in a process that
+        # has committed before (the first one also loads the code objects and warms the allocator); both are reported
+        sc.close()
+        t0 = time.perf_counter()
+        sc = capi.Scene(ctx, ds.desc)
+        t_commit = time.perf_counter() - t0
     stats = sc.stats()
 
     H, W = cam.image_height, cam.image_width
@@ -354,7 +363,8 @@ def main():
                        "parallelism": f"pixel-tiles x{world}" if world > 1 else "single GPU",
                        "bvh_pairs": stats["bvh_pairs"], "bvh_depth": stats["bvh_depth"], "objects": stats["objects"],
                        "traversal_stack": stats.get("traversal_stack"),
-                       "scene_build_s": round(t_scene, 3), "bvh_build_upload_s": round(t_commit, 3), "bvh_build_upload_first_s": round(t_commit_first, 3),
+                       "scene_build_s": round(t_scene, 3), "bvh_build_upload_s": round(t_commit, 3) if t_commit is not None else None,
+                       "bvh_build_upload_first_s": round(t_commit_first, 3),
                        "bvh_builder": stats.get("builder"), "render_path": {0: "pixel-group megakernel", 2: "streaming pipeline", 3: "fused small-scene kernel"}.get(path),
                        "frame_checksum": checksum},
             # `achieved` / `frac`: SURVEY 8(d)'s ALGORITHMIC bytes (a work rate: the no-reuse BVH2-style model) per launch / launch
@@ -385,7 +395,7 @@ def main():
                                    "its 12 doubles — a placed cube's record is 128 B — so the figure is conservative); the 76 B per hit of shading data belong to SHADE "
                                    "and are NOT in this kernel's figure")},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.workload)
             except Exception as e:  # the baseline is reported, never required

@@ -569,11 +569,11 @@ def test_composite_prefab_shares_its_triangles(built, monkeypatch):
 
 
 def test_bench_line_contract(built):
-    """bench.py on the reference's own CPU-sized case: one JSON line with the driver's keys, the roofline object (incl. the
+    """bench.py --full on the reference's own CPU-sized case: one JSON line with the driver's keys, the roofline object (incl. the
     random-record rate the traversal kernel runs against) and a CPU baseline whose port reproduces the reference's counts."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg1", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg1", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -602,6 +602,30 @@ def test_bench_line_contract(built):
     if cb["kind"] == "reference":   # the reference's best thread count (at most 16), median of three runs; the all-cores figure beside it
         assert cb["port"]["value"] > 0 and cb["port_matches_reference"] is True
         assert cb["cores"] <= 16 and len(cb["runs"]) == 3 and sorted(cb["runs"])[1] == cb["value"] and "reference_on_all_cores" in cb
+
+
+def test_plain_bench_line_leaves_out_what_full_adds(built):
+    """A plain bench.py run does only what its headline needs: the same line without the CPU baseline and without the restart commit
+    (`bvh_build_upload_s` is null), both of which --full adds.  It renders what the --full run renders: same path, segments and frame."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg1", "--steps", "1", "--warmup", "0"] + extra,
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    assert "cpu_baseline" not in plain and "cpu_baseline" not in full
+    assert plain["config"]["bvh_build_upload_s"] is None and plain["config"]["bvh_build_upload_first_s"] >= 0
+    assert full["config"]["bvh_build_upload_s"] >= 0 and full["config"]["bvh_build_upload_first_s"] >= 0
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup"):
+        assert plain[key] == full[key], key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and set(plain["roofline"]) == set(full["roofline"])
+    for key in ("render_path", "segments_per_step", "primary_per_step", "frame_checksum"):
+        assert plain["config"][key] == full["config"][key], key
 
 
 def test_bench_dumps_the_frame_of_its_last_step(ctx, tmp_path):
