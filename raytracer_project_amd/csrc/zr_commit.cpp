@@ -126,6 +126,31 @@ int finish_commit(zr_scene* s, const CommitSummary& cs, size_t n_objs) {
 // behind the leaf ranges) and sizes the final arrays.  ZR_E_STATE from here means "this input is for the host builder" (a tree
 // deeper than the traversal stack, coordinates beyond 1e18): the caller falls back.
 constexpr int ZR_FALLBACK_HOST = 1;
+
+// The build knobs the two builders share, read by whichever of them runs: a frame must not depend on which builder made the tree, so
+// neither has defaults of its own.
+struct BuildKnobs {
+    bool bake;                  // ZR_BAKE_TRIANGLES (classify_object)
+    double ct, ck[8];           // SAH cost of a traversal step and of testing one object of kind k
+    int max_leaf, leaf_cap[8];  // objects per leaf; per kind, 0 = max_leaf
+    double open_ratio;          // 4-wide collapse (Flattener::open_ratio, BuildParams::open_ratio)
+};
+static BuildKnobs read_build_knobs() {
+    BuildKnobs kn;
+    kn.bake = env_double("ZR_BAKE_TRIANGLES", 1) != 0;
+    kn.ct = env_double("ZR_BVH_COST_TRAVERSE", 1.0);
+    const double ck[8] = {env_double("ZR_BVH_COST_SPHERE", 1.0), env_double("ZR_BVH_COST_TRI", 1.5), env_double("ZR_BVH_COST_CUBE", 1.0),
+                          env_double("ZR_BVH_COST_MEDIUM", 3.0), env_double("ZR_BVH_COST_WRAPPED", 3.0), env_double("ZR_BVH_COST_PCUBE", 1.5),
+                          env_double("ZR_BVH_COST_GROUP", 16.0), 1};
+    kn.max_leaf = (int)env_double("ZR_BVH_MAX_LEAF", 4);
+    // cubes, media and wrapped objects are few, large and dear to test: one per leaf, so that a ray only tests those whose own box it enters
+    const int big = (int)env_double("ZR_BVH_MAX_LEAF_BIG", 1);
+    const int leaf_cap[8] = {0, 0, big, big, big, big, 1, 0};   // a placement is always a leaf of its own (EXTEND enters it as a whole)
+    for (int k = 0; k < 8; k++) { kn.ck[k] = ck[k]; kn.leaf_cap[k] = leaf_cap[k]; }
+    kn.open_ratio = env_double("ZR_BVH_OPEN_RATIO", 1.25);
+    return kn;
+}
+
 int commit_device(zr_scene* s, const std::vector<zr_object>& objs, bool commit_stats, CommitSummary& cs) {
     auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_phase = now_s();
@@ -141,7 +166,7 @@ int commit_device(zr_scene* s, const std::vector<zr_object>& objs, bool commit_s
     }
     // 1. classification + array sizes
     std::vector<uint8_t> code(n);
-    const bool bake = env_double("ZR_BAKE_TRIANGLES", 1) != 0;
+    const BuildKnobs kn = read_build_knobs();
     uint32_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     {
         unsigned hw = std::thread::hardware_concurrency();
@@ -149,7 +174,7 @@ int commit_device(zr_scene* s, const std::vector<zr_object>& objs, bool commit_s
         std::vector<std::array<uint32_t, 8>> part((size_t)T, std::array<uint32_t, 8>{});
         auto work = [&](int t, size_t k0, size_t k1) {
             std::array<uint32_t, 8> c{};
-            for (size_t k = k0; k < k1; k++) { uint32_t kind; uint8_t bk; classify_object(*s, objs[k], bake, kind, bk); code[k] = (uint8_t)(kind | (bk << 4)); c[kind & 7]++; }
+            for (size_t k = k0; k < k1; k++) { uint32_t kind; uint8_t bk; classify_object(*s, objs[k], kn.bake, kind, bk); code[k] = (uint8_t)(kind | (bk << 4)); c[kind & 7]++; }
             part[(size_t)t] = c;
         };
         std::vector<std::thread> th;
@@ -209,16 +234,10 @@ int commit_device(zr_scene* s, const std::vector<zr_object>& objs, bool commit_s
     in.spheres = r_sph.p; in.sphere_mat = r_sph_mat.p; in.tri_v = r_tri_v.p; in.tri_n = r_tri_n.p; in.tri_mat = r_tri_mat.p;
     in.cubes = r_cubes.p; in.cube_mat = r_cube_mat.p; in.media = r_media.p; in.ops = s->d_ops.p;
     zr::BuildParams bp;
-    bp.ct = (float)env_double("ZR_BVH_COST_TRAVERSE", 1.0);
-    const double ck[8] = {env_double("ZR_BVH_COST_SPHERE", 1.0), env_double("ZR_BVH_COST_TRI", 1.5), env_double("ZR_BVH_COST_CUBE", 1.0),
-                          env_double("ZR_BVH_COST_MEDIUM", 3.0), env_double("ZR_BVH_COST_WRAPPED", 3.0), env_double("ZR_BVH_COST_PCUBE", 1.5),
-                          env_double("ZR_BVH_COST_GROUP", 16.0), 1};
-    for (int k = 0; k < 8; k++) bp.ck[k] = (float)ck[k];
-    bp.max_leaf = (int)env_double("ZR_BVH_MAX_LEAF", 4);
-    const int big = (int)env_double("ZR_BVH_MAX_LEAF_BIG", 1);
-    const int leaf_cap[8] = {0, 0, big, big, big, big, 1, 0};
-    for (int k = 0; k < 8; k++) bp.leaf_cap[k] = leaf_cap[k];
-    bp.open_ratio = (float)env_double("ZR_BVH_OPEN_RATIO", 1.25);
+    bp.ct = (float)kn.ct;
+    for (int k = 0; k < 8; k++) { bp.ck[k] = (float)kn.ck[k]; bp.leaf_cap[k] = kn.leaf_cap[k]; }
+    bp.max_leaf = kn.max_leaf;
+    bp.open_ratio = (float)kn.open_ratio;
     bp.radius = (int)env_double("ZR_BVH_PLOC_RADIUS", 16);
     // PLOC stops at n / 64 clusters (4096 ... 65536) and the host's SAH builder arranges those: the larger the SAH-built top, the closer
     // the walk comes to the host tree's, and the longer the host's pass takes (cfg3 EXTEND per frame against the host tree's: no top
@@ -581,7 +600,7 @@ int zr_scene_commit(zr_scene* s) {
     std::vector<zr::BuildBox> boxes(objs.size());
     std::vector<uint32_t> kinds(objs.size());
     std::vector<uint8_t> baked(objs.size(), 0);
-    const bool bake = env_double("ZR_BAKE_TRIANGLES", 1) != 0;
+    const BuildKnobs kn = read_build_knobs();
     std::atomic<size_t> bad_box{(size_t)-1};
     {
         unsigned hw = std::thread::hardware_concurrency();
@@ -591,7 +610,7 @@ int zr_scene_commit(zr_scene* s) {
             for (size_t k = k0; k < k1; k++) {
             const zr_object& o = objs[k];
             boxes[k] = boxer.chain(o.type, o.index, o.chain_first, o.chain_count);
-            classify_object(*s, o, bake, kinds[k], baked[k]);
+            classify_object(*s, o, kn.bake, kinds[k], baked[k]);
             for (int a = 0; a < 3; a++)
                 if (!std::isfinite(boxes[k].lo[a]) || !std::isfinite(boxes[k].hi[a])) { size_t want = (size_t)-1; bad_box.compare_exchange_strong(want, k); }
         }
@@ -603,15 +622,8 @@ int zr_scene_commit(zr_scene* s) {
     }
     if (bad_box.load() != (size_t)-1) return fail(ZR_E_INVALID, "object %zu has a non-finite bounding box", bad_box.load());
     zr::BuildResult br;
-    double ck[8] = {env_double("ZR_BVH_COST_SPHERE", 1.0), env_double("ZR_BVH_COST_TRI", 1.5), env_double("ZR_BVH_COST_CUBE", 1.0),
-                    env_double("ZR_BVH_COST_MEDIUM", 3.0), env_double("ZR_BVH_COST_WRAPPED", 3.0), env_double("ZR_BVH_COST_PCUBE", 1.5),
-                    env_double("ZR_BVH_COST_GROUP", 16.0), 1};
-    int max_leaf = (int)env_double("ZR_BVH_MAX_LEAF", 4);
-    // cubes, media and wrapped objects are few, large and dear to test: one per leaf, so that a ray only tests those whose own box it enters
-    const int big = (int)env_double("ZR_BVH_MAX_LEAF_BIG", 1);
-    const int leaf_cap[8] = {0, 0, big, big, big, big, 1, 0};   // a placement is always a leaf of its own (EXTEND enters it as a whole)
     phase("boxes");
-    zr::build_bvh(boxes, kinds, max_leaf, ZR_STACK_DEPTH - 2, env_double("ZR_BVH_COST_TRAVERSE", 1.0), ck, br, leaf_cap);
+    zr::build_bvh(boxes, kinds, kn.max_leaf, ZR_STACK_DEPTH - 2, kn.ct, kn.ck, br, kn.leaf_cap);
     phase("binned-SAH build");
     if (br.max_depth >= ZR_STACK_DEPTH - 1) return fail(ZR_E_INVALID, "BVH depth %d exceeds the traversal stack", br.max_depth);
 
@@ -620,7 +632,7 @@ int zr_scene_commit(zr_scene* s) {
     Flattener& fl = *flp;
     fl.baked = &baked;
     fl.runs = runs.empty() ? nullptr : &runs;
-    fl.open_ratio = env_double("ZR_BVH_OPEN_RATIO", 1.25);
+    fl.open_ratio = kn.open_ratio;
     fl.want_src = true;
     // the primitive arrays (a quarter of a gigabyte for a million triangles) go to the device while the host still plans and
     // numbers the 4-wide nodes: a thread of its own, joined before the node arrays follow
@@ -668,7 +680,7 @@ int zr_scene_commit(zr_scene* s) {
     cs.n_media = fl.media.size(); cs.n_wrapped = fl.wrapped.size(); cs.n_insts = fl.insts.size();
     cs.plain_media = true;   // media whose boundary is an unwrapped sphere or cube
     for (size_t k = 0; k < fl.media.size(); k++) if (fl.media[k].chain_count != 0) cs.plain_media = false;
-    cs.stack_demand = fl.stack_demand(); cs.quad_depth = fl.quad_depth; cs.max_depth = br.max_depth; cs.max_leaf = max_leaf; cs.kept_closed = fl.n_kept_closed;
+    cs.stack_demand = fl.stack_demand(); cs.quad_depth = fl.quad_depth; cs.max_depth = br.max_depth; cs.max_leaf = kn.max_leaf; cs.kept_closed = fl.n_kept_closed;
     for (int k = 0; k < 8; k++) cs.leaf_cnt[k] = fl.cnt[k];
     cs.builder = "host (binned SAH)";
     if ((rc = finish_commit(s, cs, objs.size()))) return rc;

@@ -61,8 +61,8 @@ struct Rng {
 };
 
 // vec3.hpp:184-191.  (Round 4 tried letting the lanes that have their vector draw the pending lanes' next candidates — the wave runs this loop until its slowest
-// lane accepts, ~7 iterations at 1.9 per lane — through LDS tables: bit-identical, and no faster on any workload: profiles/r4_experiments_ab.txt,
-// scripts/dev/ruv_help_experiment.patch.  What did pay is ONE call site for all material kinds: scatter().)
+// lane accepts, ~7 iterations at 1.9 per lane — through LDS tables: bit-identical, and no faster on any workload: profiles/r4_experiments_ab.txt
+// (the patch: scripts/dev/ruv_help_experiment.patch as of commit 2d31f5a).  What did pay is ONE call site for all material kinds: scatter().)
 __device__ inline V3 random_unit_vector(Rng& g) {
     for (;;) {
         double x = g.range(-1, 1);

@@ -149,15 +149,15 @@ __global__ __launch_bounds__(ZR_BLOCK) void render_pixels(DScene sc, DCamera cam
         o[0] = sum.x * scale; o[1] = sum.y * scale; o[2] = sum.z * scale;
     }
     if (COUNT && active) {
-        atomicAdd(&gctr[0], (unsigned long long)nsamp);
-        atomicAdd(&gctr[1], (unsigned long long)segments);
-        atomicAdd(&gctr[2], (unsigned long long)ctr.nodes);
-        atomicAdd(&gctr[3], (unsigned long long)ctr.sph);
-        atomicAdd(&gctr[4], (unsigned long long)ctr.tri);
-        atomicAdd(&gctr[5], (unsigned long long)ctr.cube);
-        atomicAdd(&gctr[6], (unsigned long long)ctr.med);
-        atomicAdd(&gctr[7], (unsigned long long)hits);
-        atomicAdd(&gctr[8], (unsigned long long)draws);
+        atomicAdd(&gctr[CTR_SAMPLES], (unsigned long long)nsamp);
+        atomicAdd(&gctr[CTR_SEGMENTS], (unsigned long long)segments);
+        atomicAdd(&gctr[CTR_NODES], (unsigned long long)ctr.nodes);
+        atomicAdd(&gctr[CTR_SPHERES], (unsigned long long)ctr.sph);
+        atomicAdd(&gctr[CTR_TRIANGLES], (unsigned long long)ctr.tri);
+        atomicAdd(&gctr[CTR_CUBES], (unsigned long long)ctr.cube);
+        atomicAdd(&gctr[CTR_MEDIA], (unsigned long long)ctr.med);
+        atomicAdd(&gctr[CTR_HITS], (unsigned long long)hits);
+        atomicAdd(&gctr[CTR_DRAWS], (unsigned long long)draws);
     }
 }
 
@@ -207,10 +207,10 @@ __global__ __launch_bounds__(ZR_BLOCK) void passes_pixels(DScene sc, DCamera cam
         if (out_refraction) { out_refraction[o] = sf.x * scale; out_refraction[o + 1] = sf.y * scale; out_refraction[o + 2] = sf.z * scale; }
     }
     if (active) {
-        atomicAdd(&gctr[0], (unsigned long long)nsamp);
-        atomicAdd(&gctr[1], (unsigned long long)segments);
-        atomicAdd(&gctr[7], (unsigned long long)hits);
-        atomicAdd(&gctr[8], (unsigned long long)draws);
+        atomicAdd(&gctr[CTR_SAMPLES], (unsigned long long)nsamp);
+        atomicAdd(&gctr[CTR_SEGMENTS], (unsigned long long)segments);
+        atomicAdd(&gctr[CTR_HITS], (unsigned long long)hits);
+        atomicAdd(&gctr[CTR_DRAWS], (unsigned long long)draws);
     }
 }
 

@@ -12,6 +12,20 @@ struct DScene;
 struct DCamera;
 struct DEnv;
 
+// The context's counter block (zr_ctx::d_ctr, `gctr` in the kernels): CTR_BLOCK 64-bit words, cleared before every render.  zr_get_counters hands the
+// first CTR_WORDS of them out as zr_counters; an instrumented render (count != 0) fills words 0-12.
+enum { CTR_SAMPLES = 0, CTR_SEGMENTS = 1, CTR_NODES = 2, CTR_SPHERES = 3, CTR_TRIANGLES = 4, CTR_CUBES = 5, CTR_MEDIA = 6, CTR_HITS = 7, CTR_DRAWS = 8,
+       CTR_NODE_EXECS = 9, CTR_NODE_LANES = 10, CTR_LEAF_EXECS = 11, CTR_LEAF_LANES = 12,   // EXTEND's iterations per phase and the lanes they ran with
+       CTR_SHADE_EXECS = 13, CTR_SHADE_LANES = 14,   // zr_counters::shade_execs / shade_lanes: no kernel of the product build writes them (zero); see below
+       CTR_WORDS = 16,                               // (word 15 is spare)
+       CTR_HIST = 16, CTR_HIST_WORDS = 24,           // ZR_WAVE_PROFILE build only: EXTEND's per-phase lane histograms, [phase][8 buckets of 8 lanes]
+       CTR_BLOCK = 48 };
+// A -DZR_WAVE_PROFILE build (scripts/wave_profile.sh) runs uninstrumented renders and REUSES words of the block for EXTEND's wave statistics, read back
+// through the zr_counters fields of the words' product meaning (ZR_RAW_COUNTERS=1, scripts/wave_profile.py): phase p = 0 NODE, 1 LEAF, 2 FETCH
+enum { CTR_PROF_EXECS = 1, CTR_PROF_LANES = 2,   // + 2 * p: iterations of phase p, lanes they ran with (words 1-6)
+       CTR_PROF_WAVE_TICKS = 13,                 // sum of wave lifetimes in 10 ns ticks (read as shade_execs)
+       CTR_PROF_WAVES = 14 };                    // waves launched (read as shade_lanes)
+
 // which pixels one launch covers: the tiles `tiles[0..n_tiles)` (row-major tile ids), clipped to the
 // rectangle [x0,x1) x [y0,y1)
 struct WorkDesc {
@@ -38,6 +52,7 @@ struct StreamProgress {
     virtual ~StreamProgress() = default;
 };
 #define ST_MAX_POOLS 8   /* sub-pools of the slot pool, one HIP stream each */
+enum { CTL_CAPPED = 2 };   // control block (zr_ctx::d_ctl; the rest of its layout: zr_stream.hip, CTL_*): EXTEND waves that hit their iteration cap
 uint32_t stream_overflow_levels(uint32_t stack_demand);
 size_t stream_overflow_bytes(int blocks, uint32_t levels);
 size_t stream_ctl_words();

@@ -4,6 +4,10 @@
 
 namespace {
 
+// tiles per launch of the paths that render tile lists (the pixel-group kernel, the BVH debug view): one launch per frame unless the caller polls
+// (cancellation, progress), which needs batch boundaries
+size_t batch_tiles(bool interactive) { return (size_t)std::max(1, (int)env_double("ZR_BATCH_TILES", interactive ? 256 : (double)(1 << 30))); }
+
 // camera::initialize, camera.hpp:358-399
 void make_camera(const zr_camera& c, zr::DCamera& d) {
     int W = c.image_width < 1 ? 1 : c.image_width, H = c.image_height < 1 ? 1 : c.image_height;
@@ -157,7 +161,7 @@ int render_stream(zr_ctx* c, const zr_scene* s, const zr::DCamera& dc, const zr:
     const uint32_t n_pix = (uint32_t)c->d_pixels.n;
     if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
     c->render_id++; c->last_stream = stream; c->last_counted = count != 0; c->last_rounds = 0;
-    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, 48 * sizeof(unsigned long long), stream));
+    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), stream));
     if (n_pix == 0) return ZR_OK;
     const uint32_t spp = (uint32_t)dc.spp;
     const uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
@@ -274,7 +278,7 @@ int enqueue_render(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_
     std::vector<int32_t> tiles = plan.tiles;
     int rc = c->d_tiles.upload(tiles);
     if (rc) return rc;
-    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, 48 * sizeof(unsigned long long), stream));
+    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), stream));
     // the streaming pipeline packs bounce counters into 8 bits, work units into 32 bits and leaf references into 24 + 4
     // bits; frames or scenes beyond that are rendered by the pixel-group megakernel below (slower, same results)
     uint64_t stream_units = 0;
@@ -290,7 +294,7 @@ int enqueue_render(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_
         // the pipeline's buffers (24 bytes per primary sample + the slot pool) do not fit beside what else lives on the device: the
         // pixel-group kernel below needs neither
         std::fprintf(stderr, "[zr] %s: rendering this frame with the pixel-group kernel (same results, slower)\n", zr_host::last_error());
-        HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, 48 * sizeof(unsigned long long), stream));
+        HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), stream));
     } else if (c->variant == 2 && !c->warned_fallback) {   // said once per context: the frame is rendered, by the slower kernel
         c->warned_fallback = true;
         std::fprintf(stderr, "[zr] frame outside the streaming pipeline's packing limits (max_depth %d > 250, %llu work units > 2^32, %d x %d px > 65535, "
@@ -300,7 +304,7 @@ int enqueue_render(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_
     c->last_path = 0;
     // one launch per frame unless the caller wants progress / cancellation, which need batch boundaries
     const bool interactive = keep_going || rows_done;
-    const int batch = std::max(1, (int)env_double("ZR_BATCH_TILES", interactive ? 256 : (double)(1 << 30)));
+    const int batch = (int)batch_tiles(interactive);
     size_t n_batches = (tiles.size() + batch - 1) / batch;
     if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
     c->render_id++; c->last_stream = stream; c->last_counted = count != 0;
@@ -509,21 +513,21 @@ int zr_render_passes(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const z
     if (streaming) {
         // two runs of the streaming pipeline: the beauty pass records where every sample's stream stopped, the replay pass traces
         // the camera ray again and runs the second path from there (stream_shade MODE 1 / 2)
-        unsigned long long ha[16], hb[16];
+        unsigned long long ha[zr::CTR_WORDS], hb[zr::CTR_WORDS];
         if ((rc = render_stream(c, s, dc, de, seed, plan, 0, d_b.p, c->stream, nullptr, 1))) return rc;
         HIP_OK(hipMemcpy(ha, c->d_ctr.p, sizeof ha, hipMemcpyDeviceToHost));
         if ((rc = render_stream(c, s, dc, de, seed, plan, 0, d_r.p, c->stream, nullptr, 2, d_f.p))) return rc;
         c->last_path = 2;
         HIP_OK(hipMemcpy(hb, c->d_ctr.p, sizeof hb, hipMemcpyDeviceToHost));
         // counted by SHADE in both passes (EXTEND runs uninstrumented): samples, segments, hits, draws
-        unsigned long long h[16] = {0};
-        h[0] = (unsigned long long)c->d_pixels.n * (unsigned long long)dc.spp;   // every sample of the region, once
-        h[1] = ha[1] + hb[1]; h[7] = ha[7] + hb[7]; h[8] = ha[8] + hb[8];
+        unsigned long long h[zr::CTR_WORDS] = {0};
+        h[zr::CTR_SAMPLES] = (unsigned long long)c->d_pixels.n * (unsigned long long)dc.spp;   // every sample of the region, once
+        for (int w : {zr::CTR_SEGMENTS, zr::CTR_HITS, zr::CTR_DRAWS}) h[w] = ha[w] + hb[w];
         HIP_OK(hipMemcpy(c->d_ctr.p, h, sizeof h, hipMemcpyHostToDevice));
         c->last_counted = true;
     } else {
         c->render_id++; c->last_counted = true; c->last_rounds = 0; c->last_path = 0;
-        HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, 48 * sizeof(unsigned long long), c->stream));
+        HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), c->stream));
         HIP_OK(zr::launch_passes(s->ds, dc, de, seed, wd, d_b.p, d_r.p, d_f.p, c->d_ctr.p, c->stream));
     }
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -660,7 +664,7 @@ int zr_render_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_camera* cam, cons
     // one launch per frame unless the caller polls (cancellation, progress): then batches of tiles with the poll between them, as zr_render's
     // pixel-group path does
     const bool interactive = keep_going || rows_done;
-    const size_t batch = (size_t)std::max(1, (int)env_double("ZR_BATCH_TILES", interactive ? 256 : (double)(1 << 30)));
+    const size_t batch = batch_tiles(interactive);
     const size_t n_batches = (tiles.size() + batch - 1) / batch;
     int rrc = ZR_OK;
     for (size_t b = 0; b < n_batches; b++) {
@@ -744,17 +748,18 @@ int zr_get_counters(zr_ctx* c, zr_counters* out) {
     std::memset(out, 0, sizeof *out);
     out->kernel_ms = c->last_render_ms;
     out->extend_ms = c->last_extend_ms; out->shade_ms = c->last_shade_ms; out->rounds = c->last_rounds; out->path = (uint64_t)c->last_path;
-    unsigned long long h[16];
+    unsigned long long h[zr::CTR_WORDS];
     HIP_OK(hipMemcpy(h, c->d_ctr.p, sizeof h, hipMemcpyDeviceToHost));
-    if (h[15] != 0) return fail(ZR_E_DEVICE, "render kernel hit its iteration cap on %llu task(s): results are incomplete", h[15]);
     if (c->last_counted || env_double("ZR_RAW_COUNTERS", 0) != 0) {
-        out->primary_samples = h[0]; out->segments = h[1]; out->nodes_tested = h[2]; out->spheres_tested = h[3];
-        out->triangles_tested = h[4]; out->cubes_tested = h[5]; out->media_tested = h[6]; out->hits = h[7]; out->rng_draws = h[8];
-        out->node_execs = h[9]; out->node_lanes = h[10]; out->leaf_execs = h[11]; out->leaf_lanes = h[12]; out->shade_execs = h[13]; out->shade_lanes = h[14];
+        out->primary_samples = h[zr::CTR_SAMPLES]; out->segments = h[zr::CTR_SEGMENTS]; out->nodes_tested = h[zr::CTR_NODES]; out->spheres_tested = h[zr::CTR_SPHERES];
+        out->triangles_tested = h[zr::CTR_TRIANGLES]; out->cubes_tested = h[zr::CTR_CUBES]; out->media_tested = h[zr::CTR_MEDIA]; out->hits = h[zr::CTR_HITS];
+        out->rng_draws = h[zr::CTR_DRAWS];
+        out->node_execs = h[zr::CTR_NODE_EXECS]; out->node_lanes = h[zr::CTR_NODE_LANES]; out->leaf_execs = h[zr::CTR_LEAF_EXECS]; out->leaf_lanes = h[zr::CTR_LEAF_LANES];
+        out->shade_execs = h[zr::CTR_SHADE_EXECS]; out->shade_lanes = h[zr::CTR_SHADE_LANES];   // filled by a ZR_WAVE_PROFILE build only (zr_launch.h)
     }
     if (std::getenv("ZR_LANE_HISTOGRAM")) {   // development aid (a -DZR_WAVE_PROFILE build fills them): EXTEND's iterations per phase by ready lanes, 8 buckets of 8 lanes
-        unsigned long long hh[24];
-        HIP_OK(hipMemcpy(hh, c->d_ctr.p + 16, sizeof hh, hipMemcpyDeviceToHost));
+        unsigned long long hh[zr::CTR_HIST_WORDS];
+        HIP_OK(hipMemcpy(hh, c->d_ctr.p + zr::CTR_HIST, sizeof hh, hipMemcpyDeviceToHost));
         const char* names[3] = {"NODE", "LEAF", "FETCH"};
         for (int ph = 0; ph < 3; ph++) {
             unsigned long long tot = 0;
@@ -800,12 +805,12 @@ int zr_trace(zr_ctx* c, const zr_scene* s, const double* rays6, size_t n, double
         DevBuf<unsigned char> pool;
         if ((rc = ensure_stack_slabs(c, s))) return rc;
         if ((rc = pool.alloc(zr::stream_pool_bytes((uint32_t)n) + 65536))) return rc;
-        HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, 48 * sizeof(unsigned long long), c->stream));
+        HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), c->stream));
         HIP_OK(zr::stream_trace(s->ds, d_rays.p, (uint32_t)n, seed, pixel, bounce, d_hits.p, pool.p, c->d_ctl.p, c->d_st_overflow.p, c->st_ovf_levels, c->st_blocks,
                                 c->d_ctr.p, s->leaf_level, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
         unsigned int capped = 0;
-        HIP_OK(hipMemcpy(&capped, c->d_ctl.p + 2, sizeof capped, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(&capped, c->d_ctl.p + zr::CTL_CAPPED, sizeof capped, hipMemcpyDeviceToHost));
         if (capped) return fail(ZR_E_DEVICE, "EXTEND hit its iteration cap on %u wave(s)", capped);
     } else {
         HIP_OK(zr::launch_trace(s->ds, d_rays.p, n, tmin, tmax, seed, pixel, bounce, d_hits.p, c->stream));

@@ -43,21 +43,7 @@ namespace zr {
 #ifndef ST_FETCH_MIN
 #define ST_FETCH_MIN 16  /* idle lanes that trigger a refill even when another phase has more ready lanes */
 #endif
-#ifndef ST_LEAF_ONE_KIND
-#define ST_LEAF_ALL 1   /* a LEAF iteration serves EVERY leaf kind that has waiting lanes, kind by kind under wave-uniform guards (round 3), instead of only
-                           the kind with most lanes: the few lanes at the other kind (cfg3: the ground sphere every ray meets) no longer sit out NODE
-                           iterations waiting for company.  cfg3 EXTEND 213.1 -> 204.6 ms per frame with the 1:1 bias below (2:3: 206.2; the old
-                           one-kind rule with its 1:2 bias: 213.1), cfg2 46.7 -> 46.2; image bit-identical (profiles/r3_experiments_ab.txt) */
-#endif
-#ifndef ST_BIAS_NODE
-#define ST_BIAS_NODE 1  /* NODE runs when ready NODE lanes x ST_BIAS_NODE >= ready LEAF lanes x ST_BIAS_LEAF (LEAF lanes = all kinds together with ST_LEAF_ALL) */
-#ifdef ST_LEAF_ALL
-#define ST_BIAS_LEAF 1
-#else
-#define ST_BIAS_LEAF 2  /* one kind per LEAF iteration: favouring LEAF 2:1 was 3 % faster on cfg3 than 1:1 (a tested leaf shrinks tbest and culls the stack) */
-#endif
-#endif
-#define ST_SHARDS 64     /* unit counters (ctl[16 + 32 * s]): a single contended word sustains only ~90 atomics/us */
+#define ST_SHARDS 64     /* sharded counters of the control block (CTL_* below): a single contended word sustains only ~90 atomics/us */
 #ifndef ST_LDS_STACK
 #define ST_LDS_STACK 12
 #endif
@@ -74,14 +60,22 @@ struct SEntry { uint32_t node; float tn; };
 enum { SF_RAY = 0, SF_HIT_T = 6, SF_HIT_KI = 7, SF_BETA = 8, SF_L = 11, SF_ATT0 = 14, SF_SUM = 17, SF_KEY = 20,
        SF_MA = 21 /* RNG draw index, bounce | b_inner << 8 | flags */, SF_MB = 22 /* work unit */, SF_N = 24 };
 
+// Control block of one (sub-)pool, 32-bit words: a header, then CTL_STRIDE words per shard s from CTL_SHARD0 on, so that the ST_SHARDS copies of
+// a counter lie on separate cache lines; word w of shard s is ctl[CTL_SHARD0 + CTL_STRIDE * s + w].  The host keeps ST_MAX_POOLS such blocks and one
+// more behind them for the work-unit counters, which the sub-pools share: that one has no header, shard s counts in uctl[CTL_STRIDE * s + CTL_SH_UNITS].
+// (CTL_CAPPED, the header word the host reads after a trace: zr_launch.h.)
+enum { CTL_COMPACT = 4,      // header: the drain's compaction counter (stream_compact); zero since the frame began
+       CTL_SHARD0 = 16, CTL_STRIDE = 32,
+       CTL_SH_UNITS = 0,     // work units the shard has handed out dynamically (in the unit-counter block only)
+       CTL_SH_CHUNK = 8,     // EXTEND's chunk cursor: chunks of ST_CHUNK slots reserved this round
+       CTL_SH_ACTIVE = 16 }; // slots left active by the last SHADE
+
 struct StreamBuf {
     double* pool;             // [P / 64][SF_N][64] 8-byte cells
     const uint32_t* pixels;   // [n_pix] px | py << 16
     double* samples;          // [n_pix][spp][3] radiance of every primary sample
-    unsigned int* ctl;        // [2] iteration-cap hits; per shard s: [16 + 32 s] unit counter, [16 + 32 s + 8] EXTEND chunk head,
-                              // [16 + 32 s + 16] active slots after the last SHADE (ST_SHARDS words on separate cache lines:
-                              // a single contended word sustains only ~90 atomics/us)
-    unsigned int* uctl;       // work-unit counters [32 s], shared by the two half pools
+    unsigned int* ctl;        // this pool's control block
+    unsigned int* uctl;       // the unit-counter block, shared by the sub-pools
     uint32_t P, spp, n_units, n_pix;
     uint32_t unit0;           // slot k of this pool starts on unit unit0 + k
     uint32_t unit_base;       // first dynamically assigned unit (= slots of both pools)
@@ -168,7 +162,7 @@ __global__ __launch_bounds__(256) void stream_init(StreamBuf B, DCamera cam, uin
     const SlotAt S = slot_at(B, blockIdx.x, threadIdx.x);
     if (u0 < (unsigned long long)B.n_units) begin_sample(B, cam, seed, S, (uint32_t)u0, c_samp);
     else { uint2 z; z.x = 0; z.y = 0; S.st2(SF_MA, z); }
-    if (COUNT && c_samp) atomicAdd(&gctr[0], (unsigned long long)c_samp);
+    if (COUNT && c_samp) atomicAdd(&gctr[CTR_SAMPLES], (unsigned long long)c_samp);
 }
 
 // ---- EXTEND: closest hit for every active slot ------------------------------------------------------------
@@ -244,7 +238,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
     bool work_left = true;
     uint32_t chunk_next = 0, chunk_end = 0;  // wave-uniform: the private range of ray indices being handed out
     uint32_t head_shard = wave_id % ST_SHARDS, shards_tried = 0;
-    if (wave_id == 0 && lane < ST_SHARDS) B.ctl[16 + 32 * lane + 16] = 0;  // SHADE of this round recounts the active slots
+    if (wave_id == 0 && lane < ST_SHARDS) B.ctl[CTL_SHARD0 + CTL_STRIDE * lane + CTL_SH_ACTIVE] = 0;  // SHADE of this round recounts the active slots
     uint32_t c_nodes = 0, c_sph = 0, c_tri = 0, c_cube = 0, c_med = 0, c_seg = 0, c_hits = 0;
     unsigned long long s_exec[2] = {0, 0}, s_lanes[2] = {0, 0};
 
@@ -334,11 +328,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
         const int n2s = __popcll(__ballot(st == X_LEAF && lkind == ZR_PRIM_SPHERE));
         const int n2g = LEVEL > 0 ? __popcll(__ballot(st == X_LEAF)) - n2t - n2s : 0;
         const int n0 = work_left ? __popcll(__ballot(st == X_IDLE)) : 0;
-#ifdef ST_LEAF_ALL
         const int n2 = n2t + n2s + n2g;
-#else
-        const int n2 = n2t > n2s ? (n2t > n2g ? n2t : n2g) : (n2s > n2g ? n2s : n2g);
-#endif
         if (n1 + n2 + n0 == 0) break;
 
         if (n0 >= ST_FETCH_MIN || (n0 > 0 && n0 >= n1 && n0 >= n2)) {
@@ -353,7 +343,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
             while (chunk_next >= chunk_end && work_left) {
                 // reserve the next chunk of this wave's shard; an exhausted shard sends the wave to the next one
                 uint32_t nb = 0;
-                if (lane == 0) nb = atomicAdd(&B.ctl[16 + 32 * head_shard + 8], 1u);
+                if (lane == 0) nb = atomicAdd(&B.ctl[CTL_SHARD0 + CTL_STRIDE * head_shard + CTL_SH_CHUNK], 1u);
                 nb = __builtin_amdgcn_readfirstlane(nb);
                 const unsigned long long first = ((unsigned long long)nb * ST_SHARDS + head_shard) * ST_CHUNK;
                 if (first < (unsigned long long)B.P) {
@@ -401,7 +391,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                     }
                 }
             }
-        } else if (n1 * ST_BIAS_NODE >= n2 * ST_BIAS_LEAF) {
+        } else if (n1 >= n2) {
             // ================= NODE: one 4-wide node per lane =================
             if (COUNT) { s_exec[0]++; s_lanes[0] += n1; }
 #ifdef ZR_WAVE_PROFILE
@@ -411,43 +401,12 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
             if (st == X_NODE) {
                 float tn0, tn1, tn2, tn3;
                 uint32_t r0, r1, r2, r3;
-#ifdef ST_DUMMY_VALU   /* measurement aid: ST_DUMMY_VALU extra vector instructions per node step (four independent chains) */
-                {
-                    float d0_ = idx_, d1_ = idy_, d2_ = idz_, d3_ = cnx;
-#pragma unroll
-                    for (int k_ = 0; k_ < ST_DUMMY_VALU / 4; k_++) {
-                        asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(d0_)); asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(d1_));
-                        asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(d2_)); asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(d3_));
-                    }
-                    asm volatile("" ::"v"(d0_), "v"(d1_), "v"(d2_), "v"(d3_));
-                }
-#endif
-#ifdef ST_NODE_MINMAX   /* A/B: the min / max form of round 2 */
-                const uint4* nq = reinterpret_cast<const uint4*>(sc.quads + cur);
-                const uint4 w0 = nq[0], w1 = nq[1], w2 = nq[2], ref = nq[3];
-                const bool px_ = idx_ > 0.0f, py_ = idy_ > 0.0f, pz_ = idz_ > 0.0f;
-                // t = fmaf(q, a, b): a = scale * id, b = the node origin's parametric distance (the lower planes' b moved
-                // by -2^-15 a, the upper planes' by +2^-15 a: towards "earlier" resp. "later" whatever the sign of id)
-                const float ax_ = __uint_as_float(w0.w) * idx_, ay_ = __uint_as_float(w1.x) * idy_, az_ = __uint_as_float(w1.y) * idz_;
-                const float blx = fmaf(ax_, -3.0517578e-5f, fmaf(__uint_as_float(w0.x), idx_, (px_ ? cnx : cfx))), bhx = fmaf(ax_, 3.0517578e-5f, fmaf(__uint_as_float(w0.x), idx_, (px_ ? cfx : cnx)));
-                const float bly = fmaf(ay_, -3.0517578e-5f, fmaf(__uint_as_float(w0.y), idy_, (py_ ? cny : cfy))), bhy = fmaf(ay_, 3.0517578e-5f, fmaf(__uint_as_float(w0.y), idy_, (py_ ? cfy : cny)));
-                const float blz = fmaf(az_, -3.0517578e-5f, fmaf(__uint_as_float(w0.z), idz_, (pz_ ? cnz : cfz))), bhz = fmaf(az_, 3.0517578e-5f, fmaf(__uint_as_float(w0.z), idz_, (pz_ ? cfz : cnz)));
-#define ZR_QBOX(C, RF_IN, TN, RF)                                                                                          \
-    ZR_SLAB(fmaf((float)((w1.z >> (8 * C)) & 0xFFu), ax_, blx), fmaf((float)((w2.y >> (8 * C)) & 0xFFu), ax_, bhx),         \
-            fmaf((float)((w1.w >> (8 * C)) & 0xFFu), ay_, bly), fmaf((float)((w2.z >> (8 * C)) & 0xFFu), ay_, bhy),         \
-            fmaf((float)((w2.x >> (8 * C)) & 0xFFu), az_, blz), fmaf((float)((w2.w >> (8 * C)) & 0xFFu), az_, bhz), RF_IN, TN, RF)
-                ZR_QBOX(0, ref.x, tn0, r0)
-                ZR_QBOX(1, ref.y, tn1, r1)
-                ZR_QBOX(2, ref.z, tn2, r2)
-                ZR_QBOX(3, ref.w, tn3, r3)
-#undef ZR_QBOX
-#else
                 const uint4* nq = reinterpret_cast<const uint4*>(sc.quads + cur);
                 const uint4 w0 = nq[0], w1 = nq[1], w2 = nq[2], ref = nq[3];
                 // t = fmaf(q, a, b): a = scale * id, b = the node origin's parametric distance (the entry planes' b moved by -2^-15 |a|,
                 // the exit planes' by +2^-15 |a|).  The sign of id says which of an axis' two planes the ray enters through — for all four
                 // children at once: the word of lower planes or the word of upper planes — so no per-child min / max is needed, and the
-                // children are evaluated two at a time (v_pk_fma_f32): the planes' values are those of the min / max form, bit for bit.
+                // children are evaluated two at a time (v_pk_fma_f32): the planes' values are those of a per-child min / max, bit for bit.
                 typedef float f2_ __attribute__((ext_vector_type(2)));
                 const float ax_ = __uint_as_float(w0.w) * idx_, ay_ = __uint_as_float(w1.x) * idy_, az_ = __uint_as_float(w1.y) * idz_;
                 const float bnx = fmaf(fabsf(ax_), -3.0517578e-5f, fmaf(__uint_as_float(w0.x), idx_, cnx)), bfx = fmaf(fabsf(ax_), 3.0517578e-5f, fmaf(__uint_as_float(w0.x), idx_, cfx));
@@ -481,26 +440,21 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                 ZR_QBOX(nx23.x, ny23.x, nz23.x, fx23.x, fy23.x, fz23.x, ref.z, tn2, r2)
                 ZR_QBOX(nx23.y, ny23.y, nz23.y, fx23.y, fy23.y, fz23.y, ref.w, tn3, r3)
 #undef ZR_QBOX
-#endif
                 ZR_DESCEND()
             }
         } else {
-            // ================= LEAF: one primitive per lane, the kind with most waiting lanes =================
+            // ================= LEAF: one primitive per lane, every kind that has waiting lanes =================
+            // kind by kind, each under a wave-uniform guard: the few lanes at a minority kind (cfg3: the ground sphere every ray meets) do not
+            // sit out NODE iterations waiting for company.  Against serving only the kind with most lanes, and with NODE and LEAF lanes
+            // weighed 1:1 above: cfg3 EXTEND 213.1 -> 204.6 ms per frame, image bit-identical (profiles/r3_experiments_ab.txt)
             if (COUNT) { s_exec[1]++; s_lanes[1] += n2; }
 #ifdef ZR_WAVE_PROFILE
             p_exec[1]++; p_lanes[1] += n2;
             if (lane == 0 && n2 > 0) p_hist[threadIdx.x >> 6][8 + ((n2 - 1) >> 3)]++;
 #endif
             const bool is_leaf = st == X_LEAF;
-#ifdef ST_LEAF_ALL
-            // experiment: every leaf kind that has waiting lanes is served in this iteration (kind by kind, each under a wave-uniform
-            // guard) instead of only the kind with most lanes
             const bool do_tri = n2t > 0;
             const bool do_sph = n2s > 0;
-#else
-            const bool do_tri = n2t == n2;
-            const bool do_sph = !do_tri && n2s == n2;
-#endif
             const uint32_t prim = (cur & 0xFFFFFFu) + pend_i;
             bool tested = false;
             if (do_tri) {
@@ -514,11 +468,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                     tested = true;
                 }
             }
-#ifdef ST_LEAF_ALL
             if (do_sph) {
-#else
-            else if (do_sph) {
-#endif
                 if (is_leaf && lkind == ZR_PRIM_SPHERE) {
                     double t;
                     if (COUNT) c_sph++;
@@ -526,11 +476,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                     tested = true;
                 }
             }
-#ifdef ST_LEAF_ALL
             if (LEVEL > 0 && is_leaf && lkind != ZR_PRIM_TRIANGLE && lkind != ZR_PRIM_SPHERE) {
-#else
-            else if (LEVEL > 0 && is_leaf && lkind != ZR_PRIM_TRIANGLE && lkind != ZR_PRIM_SPHERE) {
-#endif
                 double t;
                 if (COUNT && lkind < ZR_KIND_INSTANCE) {
                     uint32_t kk = lkind;
@@ -570,23 +516,23 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
             }
         }
     }
-    if (iter >= iter_cap && lane == 0) atomicAdd(&B.ctl[2], 1u);
+    if (iter >= iter_cap && lane == 0) atomicAdd(&B.ctl[CTL_CAPPED], 1u);
 #ifdef ZR_WAVE_PROFILE
     if (!COUNT && lane == 0) {  // development build: wave lifetime (10 ns ticks) and phase statistics into the raw counter words
-        atomicAdd(&gctr[13], wall_clock64() - t_begin); atomicAdd(&gctr[14], 1ull);
-        for (int k = 0; k < 3; k++) { atomicAdd(&gctr[1 + 2 * k], p_exec[k]); atomicAdd(&gctr[2 + 2 * k], p_lanes[k]); }
-        for (int k = 0; k < 24; k++) if (p_hist[threadIdx.x >> 6][k]) atomicAdd(&gctr[16 + k], (unsigned long long)p_hist[threadIdx.x >> 6][k]);   // (the context's counter block has 48 words)
+        atomicAdd(&gctr[CTR_PROF_WAVE_TICKS], wall_clock64() - t_begin); atomicAdd(&gctr[CTR_PROF_WAVES], 1ull);
+        for (int k = 0; k < 3; k++) { atomicAdd(&gctr[CTR_PROF_EXECS + 2 * k], p_exec[k]); atomicAdd(&gctr[CTR_PROF_LANES + 2 * k], p_lanes[k]); }
+        for (int k = 0; k < CTR_HIST_WORDS; k++) if (p_hist[threadIdx.x >> 6][k]) atomicAdd(&gctr[CTR_HIST + k], (unsigned long long)p_hist[threadIdx.x >> 6][k]);
     }
 #endif
     if (COUNT) {
-        atomicAdd(&gctr[1], (unsigned long long)c_seg);
-        atomicAdd(&gctr[2], (unsigned long long)c_nodes);
-        atomicAdd(&gctr[3], (unsigned long long)c_sph);
-        atomicAdd(&gctr[4], (unsigned long long)c_tri);
-        atomicAdd(&gctr[5], (unsigned long long)c_cube);
-        atomicAdd(&gctr[6], (unsigned long long)c_med);
-        atomicAdd(&gctr[7], (unsigned long long)c_hits);
-        if (lane == 0) for (int k = 0; k < 2; k++) { atomicAdd(&gctr[9 + 2 * k], s_exec[k]); atomicAdd(&gctr[10 + 2 * k], s_lanes[k]); }
+        atomicAdd(&gctr[CTR_SEGMENTS], (unsigned long long)c_seg);
+        atomicAdd(&gctr[CTR_NODES], (unsigned long long)c_nodes);
+        atomicAdd(&gctr[CTR_SPHERES], (unsigned long long)c_sph);
+        atomicAdd(&gctr[CTR_TRIANGLES], (unsigned long long)c_tri);
+        atomicAdd(&gctr[CTR_CUBES], (unsigned long long)c_cube);
+        atomicAdd(&gctr[CTR_MEDIA], (unsigned long long)c_med);
+        atomicAdd(&gctr[CTR_HITS], (unsigned long long)c_hits);
+        if (lane == 0) for (int k = 0; k < 2; k++) { atomicAdd(&gctr[CTR_NODE_EXECS + 2 * k], s_exec[k]); atomicAdd(&gctr[CTR_NODE_LANES + 2 * k], s_lanes[k]); }   // k = 1: CTR_LEAF_*
     }
 }
 
@@ -603,7 +549,7 @@ template <bool COUNT, int MODE, bool LEAN = false>
 __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) void stream_shade(DScene sc, DCamera cam, DEnv env, uint64_t seed, StreamBuf B,
                                                     unsigned long long* __restrict__ gctr) {
     const uint32_t slot0 = blockIdx.x * 256 + threadIdx.x;
-    if (slot0 < ST_SHARDS) B.ctl[16 + 32 * slot0 + 8] = 0;  // EXTEND of the next round starts from chunk 0 of every shard
+    if (slot0 < ST_SHARDS) B.ctl[CTL_SHARD0 + CTL_STRIDE * slot0 + CTL_SH_CHUNK] = 0;  // EXTEND of the next round starts from chunk 0 of every shard
     // the split passes count through LDS into a per-block record (a global atomic per thread costs ~1.5 ms per round and word)
     __shared__ unsigned long long s_cnt[4];
     if (MODE != 0 && threadIdx.x < 4) s_cnt[threadIdx.x] = 0;   // ordered before its use by the partition's barriers
@@ -627,21 +573,16 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
         uint2 m0; m0.x = 0; m0.y = 0;
         uint2 k0; k0.x = 0xFFFFFFFFu; k0.y = 0;
         if (slot0 < B.P) { const SlotAt S0 = slot_at(B, blockIdx.x, threadIdx.x); m0 = S0.ld2(SF_MA); k0 = S0.ld2(SF_HIT_KI); }
-#ifdef ZR_SHADE_NO_PARTITION
-        src = threadIdx.x; m = m0; ki = k0;
-#else
         uint32_t cls = 7;
         if (m0.y & F_ACTIVE) {
             if (k0.x == 0xFFFFFFFFu) cls = 6;
             else {
                 cls = 0;
-#ifndef ZR_SHADE_HITMISS_ONLY
                 if (sc.mat_kinds & (sc.mat_kinds - 1u)) {   // more than one material kind in the scene (wave-uniform)
                     const uint32_t mat = object_material(sc, k0.x, k0.y);
                     cls = mat < sc.n_mats ? sc.mats[mat].kind : 5u;
                     if (cls > 5u) cls = 5u;
                 }
-#endif
             }
         }
         const int w = threadIdx.x >> 6, wl = threadIdx.x & 63;
@@ -665,7 +606,6 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
         mk4 = x_mk[threadIdx.x];
         src = x_src[threadIdx.x];
         m.x = mk4.x; m.y = mk4.y; ki.x = mk4.z; ki.y = mk4.w;
-#endif
     }
     const SlotAt S = slot_at(B, blockIdx.x, src);
     bool active_after = false, want_unit = false;
@@ -674,20 +614,6 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
         if (m.y & F_ACTIVE) {   // (a thread beyond the pool got meta = 0 from the prologue)
             const uint32_t NONE = 0xFFFFFFFFu;
             const bool first = (m.y & F_FIRST) != 0;
-#ifdef ZR_SHADE_TOUCH
-            // experiment, off: first and last line of the record object_rec() will read, requested with the state rows (cfg3 +1.3 %:
-            // the record's own read costs less than the extra requests).  The loads
-            // are invisible to the compiler's wait counting, which is safe: memory returns in order, so every wait it inserts for
-            // a younger load covers them; the register they write stays reserved until the hit branch has waited for the ray.
-            uint32_t touch = 0;
-            if (ki.x == ZR_PRIM_TRIANGLE) {
-                const double* q = sc.tri_s + (size_t)ki.y * 20;
-                asm volatile("global_load_dword %0, %1, off\n\tglobal_load_dword %0, %1, off offset:156" : "=&v"(touch) : "v"(q) : "memory");
-            } else if (ki.x == ZR_PRIM_SPHERE) {
-                const double* q = sc.spheres + (size_t)ki.y * 4;
-                asm volatile("global_load_dword %0, %1, off" : "=&v"(touch) : "v"(q) : "memory");
-            }
-#endif
             // every row this segment reads, requested in one go (a row of a slot is always addressable; what a path does not
             // need is not requested: beta before the second hit, the unit id is 8 bytes)
             Ray ray; ray.o = S.ld3(SF_RAY); ray.d = S.ld3(SF_RAY + 3);
@@ -738,9 +664,6 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
                     sc_ok = lean_shade(sc, ray, rec, em, att, nr, g);
                 } else {
                     Rec rec;
-#ifdef ZR_SHADE_TOUCH
-                    asm volatile("" ::"v"(touch), "v"(ray.o.x), "v"(ray.d.z));   // the ray is here, so the touches (older) have returned
-#endif
                     object_rec(sc, ki.x, ki.y, ray, t, rec);
                     em = emitted(sc, rec);
                     if (MODE == 2 && first) {   // the stream continues where the beauty path of this sample stopped
@@ -829,7 +752,7 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
             const uint32_t shard = blockIdx.x % ST_SHARDS;
             const int wl = threadIdx.x & 63;
             uint32_t k0 = 0;
-            if (wl == (int)__builtin_ctzll(wm)) k0 = atomicAdd(&B.uctl[32 * shard], (unsigned int)__popcll(wm));
+            if (wl == (int)__builtin_ctzll(wm)) k0 = atomicAdd(&B.uctl[CTL_STRIDE * shard + CTL_SH_UNITS], (unsigned int)__popcll(wm));
             k0 = __shfl(k0, (int)__builtin_ctzll(wm), 64);
             if (want_unit) {
                 const unsigned long long k = (unsigned long long)k0 + (unsigned long long)__popcll(wm & ((1ull << wl) - 1ull));
@@ -842,10 +765,10 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
     // active-slot count for the host's round loop: sharded like the other counters — one contended word would cost
     // ~3 ms per 16 M-slot round (262 144 wave atomics at ~90 per microsecond)
     const unsigned long long am = __ballot(active_after);
-    if ((threadIdx.x & 63) == 0 && am != 0ull) atomicAdd(&B.ctl[16 + 32 * (blockIdx.x % ST_SHARDS) + 16], (unsigned int)__popcll(am));
+    if ((threadIdx.x & 63) == 0 && am != 0ull) atomicAdd(&B.ctl[CTL_SHARD0 + CTL_STRIDE * (blockIdx.x % ST_SHARDS) + CTL_SH_ACTIVE], (unsigned int)__popcll(am));
     if (COUNT && MODE == 0) {
-        if (c_samp) atomicAdd(&gctr[0], (unsigned long long)c_samp);
-        if (c_draws) atomicAdd(&gctr[8], c_draws);
+        if (c_samp) atomicAdd(&gctr[CTR_SAMPLES], (unsigned long long)c_samp);
+        if (c_draws) atomicAdd(&gctr[CTR_DRAWS], c_draws);
     }
     if (MODE != 0) {
         if (c_samp) atomicAdd(&s_cnt[0], (unsigned long long)c_samp);
@@ -876,7 +799,7 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
 #define ST_FUSED_WAVES 2
 #endif
 struct FusedBuf {
-    const uint32_t* pixels; double* samples; unsigned int* uctl;   // uctl[32 s]: chunk counter of shard s
+    const uint32_t* pixels; double* samples; unsigned int* uctl;   // uctl: the unit-counter block; here shard s counts chunks of ST_FUSED_CHUNK units
     uint32_t spp, n_units;
     uint32_t chunk_lo, chunk_hi;   // this launch hands out the chunks [chunk_lo, chunk_hi) of ST_FUSED_CHUNK units (a frame in one launch, or in
                                    // parts when the caller polls for cancellation / progress between them)
@@ -963,7 +886,7 @@ __global__ __launch_bounds__(256, ST_FUSED_WAVES) void fused_render(DScene sc, D
             uint32_t want = (uint32_t)__popcll(idle);
             while (chunk_next >= chunk_end && units_left) {
                 uint32_t nb = 0;
-                if (lane == 0) nb = atomicAdd(&B.uctl[32 * shard], 1u);
+                if (lane == 0) nb = atomicAdd(&B.uctl[CTL_STRIDE * shard + CTL_SH_UNITS], 1u);
                 nb = __builtin_amdgcn_readfirstlane(nb);
                 const unsigned long long c = (unsigned long long)B.chunk_lo + (unsigned long long)nb * ST_SHARDS + shard;   // chunk index
                 if (c < n_chunks) {
@@ -1043,9 +966,9 @@ __global__ __launch_bounds__(256, ST_FUSED_WAVES) void fused_render(DScene sc, D
         }
     }
     if (COUNT) {
-        atomicAdd(&gctr[0], (unsigned long long)c_samp); atomicAdd(&gctr[1], (unsigned long long)c_seg);
-        atomicAdd(&gctr[3], (unsigned long long)cn[0]); atomicAdd(&gctr[4], (unsigned long long)cn[1]); atomicAdd(&gctr[5], (unsigned long long)cn[2]); atomicAdd(&gctr[6], (unsigned long long)cn[3]);
-        atomicAdd(&gctr[7], (unsigned long long)c_hit); atomicAdd(&gctr[8], c_draws);
+        atomicAdd(&gctr[CTR_SAMPLES], (unsigned long long)c_samp); atomicAdd(&gctr[CTR_SEGMENTS], (unsigned long long)c_seg);
+        atomicAdd(&gctr[CTR_SPHERES], (unsigned long long)cn[0]); atomicAdd(&gctr[CTR_TRIANGLES], (unsigned long long)cn[1]); atomicAdd(&gctr[CTR_CUBES], (unsigned long long)cn[2]); atomicAdd(&gctr[CTR_MEDIA], (unsigned long long)cn[3]);
+        atomicAdd(&gctr[CTR_HITS], (unsigned long long)c_hit); atomicAdd(&gctr[CTR_DRAWS], c_draws);
     }
 }
 
@@ -1107,7 +1030,7 @@ __global__ __launch_bounds__(256) void stream_sum_counters(const unsigned long l
     for (size_t b = threadIdx.x; b < n_blocks; b += 256) for (int k = 0; k < 4; k++) a[k] += cpart[b * 4 + k];
     for (int k = 0; k < 4; k++) if (a[k]) atomicAdd(&s[k], a[k]);
     __syncthreads();
-    if (threadIdx.x == 0) { gctr[0] += s[0]; gctr[1] += s[1]; gctr[7] += s[2]; gctr[8] += s[3]; }
+    if (threadIdx.x == 0) { gctr[CTR_SAMPLES] += s[0]; gctr[CTR_SEGMENTS] += s[1]; gctr[CTR_HITS] += s[2]; gctr[CTR_DRAWS] += s[3]; }
 }
 
 // the split frames: the same order-fixed sum, every sample to the frame its class names
@@ -1172,7 +1095,7 @@ __global__ __launch_bounds__(256) void stream_hits_out(DScene sc, StreamBuf B, u
 }
 
 // ---- host-side launch helpers -----------------------------------------------------------------------------------
-size_t stream_ctl_words() { return 16 + 32 * ST_SHARDS; }
+size_t stream_ctl_words() { return CTL_SHARD0 + CTL_STRIDE * ST_SHARDS; }
 // spill slab of the EXTEND stack: `stack_demand` = worst-case entries of the committed tree (zr_scene_stats), ST_LDS_STACK of them live in LDS
 uint32_t stream_overflow_levels(uint32_t stack_demand) { return stack_demand > ST_LDS_STACK ? stack_demand - ST_LDS_STACK : 1u; }
 size_t stream_overflow_bytes(int blocks, uint32_t levels) { return (size_t)blocks * levels * 64 * sizeof(SEntry); }
@@ -1234,6 +1157,7 @@ hipError_t stream_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
     StreamBuf Q[ST_MAX_POOLS];
     void* ov[ST_MAX_POOLS];
     unsigned int* uctl = d_ctl + (size_t)ST_MAX_POOLS * W;
+    const unsigned int* h_units = h_active + (size_t)ST_MAX_POOLS * W;   // the host's copy of it
     {
         uint32_t first = 0;
         unsigned char* base = (unsigned char*)pool;
@@ -1312,14 +1236,14 @@ hipError_t stream_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
         if (e != hipSuccess) break;
         unsigned long long active = 0;
         for (int k = 0; k < K; k++) {
-            if (h_active[(size_t)k * W + 2] != 0) capped = true;   // (looked at here, for every sub-pool: the drain below folds them into one)
-            for (int sh = 0; sh < ST_SHARDS; sh++) active += h_active[(size_t)k * W + 16 + 32 * sh + 16];
+            if (h_active[(size_t)k * W + CTL_CAPPED] != 0) capped = true;   // (looked at here, for every sub-pool: the drain below folds them into one)
+            for (int sh = 0; sh < ST_SHARDS; sh++) active += h_active[(size_t)k * W + CTL_SHARD0 + CTL_STRIDE * sh + CTL_SH_ACTIVE];
         }
         if (progress && active != 0) {
             unsigned long long started = 0;   // the first P units are dealt at initialisation, the rest through the sharded counters
-            if (!unit_chunk) { started = P; for (int sh = 0; sh < ST_SHARDS; sh++) started += h_active[(size_t)ST_MAX_POOLS * W + 32 * sh]; }
+            if (!unit_chunk) { started = P; for (int sh = 0; sh < ST_SHARDS; sh++) started += h_units[CTL_STRIDE * sh + CTL_SH_UNITS]; }
             else for (int sh = 0; sh < ST_SHARDS; sh++) {   // affine: of a shard's sequence, the units that exist (a shard's last chunks may lie beyond the frame)
-                const unsigned long long k_sh = (unsigned long long)(P / ST_SHARDS) + h_active[(size_t)ST_MAX_POOLS * W + 32 * sh];
+                const unsigned long long k_sh = (unsigned long long)(P / ST_SHARDS) + h_units[CTL_STRIDE * sh + CTL_SH_UNITS];
                 const uint32_t pos = ((uint32_t)sh & 7u) * (ST_SHARDS / 8u) + ((uint32_t)sh >> 3);
                 const unsigned long long full = k_sh / unit_chunk, part = k_sh % unit_chunk;
                 for (unsigned long long q = 0; q <= full; q++) {
@@ -1341,11 +1265,11 @@ hipError_t stream_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
         if (!drained && drain_pool && active * 16ull <= (unsigned long long)P && active <= (unsigned long long)drain_slots) {
             bool units_left = false;   // shard sh has handed out every k below its counter: unit_base + k * shards + sh
             for (int sh = 0; sh < ST_SHARDS && !units_left; sh++)
-                if (st_unit_of(unit_chunk, P, (uint32_t)sh, (unsigned long long)(unit_chunk ? P / ST_SHARDS : 0u) + h_active[(size_t)ST_MAX_POOLS * W + 32 * sh]) < (unsigned long long)n_units) units_left = true;
+                if (st_unit_of(unit_chunk, P, (uint32_t)sh, (unsigned long long)(unit_chunk ? P / ST_SHARDS : 0u) + h_units[CTL_STRIDE * sh + CTL_SH_UNITS]) < (unsigned long long)n_units) units_left = true;
             if (!units_left) {   // see stream_compact
                 StreamBuf D = Q[0];
                 D.pool = (double*)drain_pool; D.P = (uint32_t)((active + 255ull) / 256ull * 256ull); D.unit0 = 0;
-                unsigned int* counter = d_ctl + 4;   // a control word of pool 0 nothing else uses; zero since the frame began
+                unsigned int* counter = d_ctl + CTL_COMPACT;   // (of pool 0)
                 for (int k = 0; k < K; k++) hipLaunchKernelGGL(stream_compact, dim3((Q[k].P + 255) / 256), dim3(256), 0, stream, Q[k], D, counter);
                 if (D.P > (uint32_t)active) hipLaunchKernelGGL(stream_compact_pad, dim3((D.P - (uint32_t)active + 255) / 256), dim3(256), 0, stream, D, (uint32_t)active);
                 if ((e = hipStreamSynchronize(stream)) != hipSuccess) break;

@@ -3,20 +3,23 @@
 # 1. rocprofv3 --kernel-trace --stats of `bench.py --steps 2 --warmup 1`  -> gpurun_out/<tag>_<workload>_kernel_stats.csv + the bench line
 # 2. FETCH_SIZE and WRITE_SIZE of the same command, each in its OWN --pmc pass (they do not fit one pass on gfx950; counters only with
 #    --kernel-trace)                                                      -> gpurun_out/<tag>_<workload>_traffic.json, keyed by the kernel
-#    source hash (bench.py --kernel-src-sha) so that bench.py only quotes it for the sources it was taken on
+#    source hash (bench.py --kernel-src-sha) so that bench.py only quotes it for the sources it was taken on; written only when every pass ran
 # Copy the summaries into profiles/ by hand.
 R=$GRAFT_REPO_ROOT
 TAG=${1:-r2}; WL=${2:-cfg3}
 OUT=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/prof_${TAG}_$WL $OUT/pmcF_${TAG}_$WL $OUT/pmcW_${TAG}_$WL $OUT/pmcL_${TAG}_$WL $OUT/pmcD_${TAG}_$WL
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_$WL -- python3 $R/bench.py --steps 2 --warmup 1 --workload $WL --no-cpu-baseline > $OUT/${TAG}_${WL}_bench_profiled.json 2> $OUT/prof_${TAG}_$WL.err || echo "stats pass failed"
-timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmcF_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcF_${TAG}_$WL.err || echo "FETCH_SIZE pass failed"
-timeout -k 10 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmcW_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcW_${TAG}_$WL.err || echo "WRITE_SIZE pass failed"
+# a pass that fails or times out ends the script: nothing further is started on the GPU, no JSON is written, and the pass's .err file and
+# output directory stay for reading
+stop() { echo "$1 failed (status $?): stopping here" >&2; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_$WL -- python3 $R/bench.py --steps 2 --warmup 1 --workload $WL --no-cpu-baseline > $OUT/${TAG}_${WL}_bench_profiled.json 2> $OUT/prof_${TAG}_$WL.err || stop "stats pass"
+timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmcF_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcF_${TAG}_$WL.err || stop "FETCH_SIZE pass"
+timeout -k 10 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmcW_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcW_${TAG}_$WL.err || stop "WRITE_SIZE pass"
 # 3. L2 (TCC) hits / misses and the FP64 vector instructions of the same command, one --pmc pass each -> the same JSON (bench.py: roofline.l2_hit_rate,
 #    roofline.fp64_valu_frac)
-timeout -k 10 400 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum --output-format csv -d $OUT/pmcL_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcL_${TAG}_$WL.err || echo "TCC pass failed"
-timeout -k 10 400 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmcD_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcD_${TAG}_$WL.err || echo "FP64 pass failed"
+timeout -k 10 400 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum --output-format csv -d $OUT/pmcL_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcL_${TAG}_$WL.err || stop "TCC pass"
+timeout -k 10 400 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmcD_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcD_${TAG}_$WL.err || stop "FP64 pass"
 SHA=$(python3 $R/bench.py --kernel-src-sha)
 python3 - "$OUT" "$TAG" "$WL" "$SHA" <<'PY'
 import csv, glob, json, os, sys, collections
