@@ -7,8 +7,8 @@ namespace {
 int finish_commit(zr_scene* s, const CommitSummary& cs, size_t n_objs) {
     int rc;
     if (std::getenv("ZR_QUANT_STATS")) std::fprintf(stderr, "[zr] 4-wide nodes: %zu quantised (64 B) + FP32 root; %zu children kept closed for the grid\n", cs.n_quads, cs.kept_closed);
-    s->quad_ok = cs.quant_ok && cs.n_quads < (1u << 31) && cs.max_leaf <= 16 && cs.n_sph < (1u << 24) && cs.n_tri < (1u << 24) && cs.n_cube < (1u << 24) &&
-                 cs.n_media < (1u << 24) && cs.n_wrapped < (1u << 24) && cs.n_pcube < (1u << 24) && cs.n_insts < (1u << 24);
+    s->quad_ok = cs.quant_ok && cs.n_quads < (1u << 31) && cs.max_leaf <= 16 && cs.n_sph < zr::ST_MAX_LEAF_PRIMS && cs.n_tri < zr::ST_MAX_LEAF_PRIMS && cs.n_cube < zr::ST_MAX_LEAF_PRIMS &&
+                 cs.n_media < zr::ST_MAX_LEAF_PRIMS && cs.n_wrapped < zr::ST_MAX_LEAF_PRIMS && cs.n_pcube < zr::ST_MAX_LEAF_PRIMS && cs.n_insts < zr::ST_MAX_LEAF_PRIMS;
     if ((rc = s->d_ops.upload(s->ops.data(), s->ops.size()))) return rc;
     {
         // zr_material::pad_ on the device copy: the material reads u/v/tangent (image texture anywhere in its

@@ -1,8 +1,8 @@
 // zr_host_internal.h — what the host-side translation units of libzr_hip.so share (round 4: zr_host.cpp was one 2 482-line file):
 //   zr_host.cpp    context life cycle, error string, small C-ABI entry points
 //   zr_commit.cpp  scene setters, validation, zr_scene_commit through the host builder or the device builder (zr_flatten.h: the flattener)
-//   zr_render.cpp  camera frame / sky constants, the render drivers (streaming pipeline, fused kernel, pixel-group kernel), AOV / split passes, post stack,
-//                  known-answer entry points
+//   zr_render.cpp  camera frame / sky constants, the frame job every render entry prepares (tile plan, validation) and its drivers (streaming pipeline, fused
+//                  kernel, pixel-group kernel), AOV / split passes, post stack, known-answer entry points
 // Plain C++ (host compiler, -ffp-contract=off so that the camera frame and the sky constants are computed with exactly the reference's operation order,
 // camera.hpp:358-399, 874-895,914); the kernels live in the .hip files.  There is deliberately no CPU rendering path in this library: without a HIP device
 // zr_create() fails and says so.

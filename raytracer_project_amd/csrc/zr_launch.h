@@ -58,12 +58,34 @@ size_t stream_overflow_bytes(int blocks, uint32_t levels);
 size_t stream_ctl_words();
 int stream_extend_blocks();
 size_t stream_pool_bytes(uint32_t P);
-hipError_t stream_render(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, void* pool, uint32_t P, uint32_t spp,
-                         uint32_t n_pix, const uint32_t* d_pixels, double* d_samples, unsigned int* d_ctl, void* d_overflow, uint32_t ovf_levels, int extend_blocks,
-                         double* out, unsigned long long* gctr, bool count, hipStream_t* streams, int n_pools, hipEvent_t ev, StreamTimer* timer,
-                         unsigned int* h_active, volatile const uint8_t* keep_going, int* rounds_out, int leaf_level, int mode = 0, void* d_kend = nullptr,
-                         void* d_cls = nullptr, double* out2 = nullptr, unsigned long long* d_cpart = nullptr, StreamProgress* progress = nullptr,
-                         void* drain_pool = nullptr, uint32_t drain_slots = 0, uint32_t unit_chunk = 0);
+// Packing limits of the pipeline.  A frame or scene beyond one of them is rendered by the pixel-group kernel (zr_render.cpp: fits_stream).
+constexpr int ST_MAX_BOUNCES = 250;               // the bounce counter is 8 bits of a slot's flag word (zr_stream.hip: SF_MA)
+constexpr uint64_t ST_MAX_UNITS = 0xFFFFFFFFull;   // work units (one per primary sample) are numbered in 32 bits (SF_MB)
+constexpr int ST_MAX_FRAME_SIDE = 65535;           // a pixel of the pixel list is x | y << 16
+constexpr uint32_t ST_MAX_LEAF_PRIMS = 1u << 24;   // a leaf reference is 24 bits of index + 4 of count (zr_scene::quad_ok, decided at the commit)
+// One run of the pipeline, grouped by what the arguments are for.  Pointers are device memory unless they say otherwise; the hooks may all be null.
+struct StreamFrame {     // what is rendered: one work unit per primary sample of the n_pix listed pixels (x | y << 16)
+    const DCamera* cam; const DEnv* env; uint64_t seed; uint32_t spp, n_pix; const uint32_t* pixels;
+    double* samples;     // per-sample radiance, 3 doubles per unit
+    double *out, *out2;  // the frame the samples are reduced into (null: none wanted) and, in mode 2, the refraction frame
+    bool count;          // the instrumented builds (zr_counters)
+};
+struct StreamPool {      // the frame's slot pool; the small pool the survivors of its drain are moved to (null: not used); chunk of the XCD-affine hand-out (0: striped)
+    void* slots; uint32_t P; void* drain; uint32_t drain_slots, unit_chunk;
+};
+struct StreamContext {   // what the context owns (zr_ctx): control block, EXTEND's spill slabs and persistent grid, counter block (CTR_*), streams, pinned copy of ctl
+    unsigned int* ctl; void* overflow; uint32_t ovf_levels; int extend_blocks; unsigned long long* gctr;
+    hipStream_t* streams; int n_pools;   // streams[0] is the caller's stream, the others are internal; n_pools: sub-pools wanted
+    hipEvent_t event; unsigned int* h_active;
+};
+struct StreamSplit { int mode; void* kend; void* cls; unsigned long long* cpart; };   // mode 0: the render; 1 / 2: the passes of the reflection / refraction split, with their buffers
+struct StreamHooks {     // the host's view into the loop
+    StreamTimer* timer; volatile const uint8_t* keep_going /* host memory, polled between rounds: 0 cancels */; StreamProgress* progress;
+    int* done_out;       // rounds run (stream_render) or parts launched (fused_render_frame); negative: cancelled after that many
+};
+struct StreamJob { StreamFrame frame; StreamPool pool; StreamContext ctx; StreamSplit split; StreamHooks hooks; };
+// leaf_level: the EXTEND build the scene needs (zr_scene::leaf_level)
+hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level);
 // The objects of a small world as the fused kernel wants them: IN THE KERNEL ARGUMENTS.  The kernarg segment is read with scalar
 // loads, so an object's record reaches every lane of a wave through SGPRs — no vector memory instruction, no VGPRs per lane for
 // data that is the same in all of them (reading the records through the scene's pointers, the compiler issued 255 vector loads
@@ -78,12 +100,11 @@ struct FusedObjs {
     double rec[ZR_FUSED_OBJECTS][16];   // (a placed cube's record is the longest: ZR_PCUBE_STRIDE)
 };
 int fused_blocks();
-hipError_t fused_render_frame(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, uint32_t spp, uint32_t n_pix, const uint32_t* d_pixels, double* d_samples,
-                              unsigned int* d_ctl, int blocks, double* out, unsigned long long* gctr, bool count, int level, hipStream_t stream, StreamTimer* timer,
-                              const FusedObjs& objs, volatile const uint8_t* keep_going = nullptr, StreamProgress* progress = nullptr, int* parts_done = nullptr);
-hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out,
-                        void* pool, unsigned int* d_ctl, void* d_overflow, uint32_t ovf_levels, int extend_blocks, unsigned long long* gctr, int leaf_level,
-                        hipStream_t stream);
+// uses of `ctx`: ctl, gctr, streams[0].  level: 1 = no wrapped objects and only plain media, 2 = everything but placements
+hipError_t fused_render_frame(const DScene& sc, const StreamFrame& frame, const StreamContext& ctx, int blocks, int level, const FusedObjs& objs, const StreamHooks& hooks);
+// closest hits of n rays in [0.001, inf) through the EXTEND kernel on ctx.streams[0]; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes
+hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, void* pool,
+                        const StreamContext& ctx, int leaf_level);
 hipError_t launch_aov(const DScene& sc, const DCamera& cam, uint64_t seed, const WorkDesc& wd, int aux, double zmax, const double* uvw9,
                       double* out_albedo, double* out_normal, double* out_zdepth, hipStream_t stream);
 hipError_t launch_passes(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, double* out_beauty,

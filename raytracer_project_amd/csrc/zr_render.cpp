@@ -1,5 +1,6 @@
-// zr_render.cpp — the render side of the C ABI (include/zr_capi.h): camera frame and sky constants, the round loop of the streaming pipeline, the fused
-// small-scene kernel, the pixel-group fallback, AOV and split passes, the post stack, counters and the known-answer entry points.
+// zr_render.cpp — the render side of the C ABI (include/zr_capi.h).  Every render entry point describes its frame once (FrameJob, filled and validated by prepare_frame;
+// the region arithmetic lives on Plan) and hands it to a driver: enqueue_render (the streaming pipeline where the frame fits it, else the pixel-group kernel), render_stream
+// (the pipeline's round loop or the fused small-scene kernel) or the AOV / split-pass / BVH-debug launches.  Also here: post stack, counters, known-answer entry points.
 #include "zr_host_internal.h"
 
 namespace {
@@ -64,10 +65,32 @@ void make_env(const zr_env& e, zr::DEnv& d) {
     st3(d.sun_add, (scol * e.sun_intensity) * vis);
 }
 
+struct TileRect { int xa, xb, ya, yb; };   // the pixels [xa, xb) x [ya, yb); xb <= xa or yb <= ya: none
+
+// which pixels a call renders: the frame, its tile grid, the region rectangle and the tiles of this part (zr_region)
 struct Plan {
-    int W, H, ts, tiles_x, tiles_y, x0, y0, x1, y1, lanes;
+    int W, H, ts, tiles_x, tiles_y, x0, y0, x1, y1;
     std::vector<int32_t> tiles;
+    size_t npx() const { return (size_t)W * H; }
+    bool whole() const { return tiles.size() == (size_t)tiles_x * tiles_y && x0 == 0 && y0 == 0 && x1 == W && y1 == H; }
+    // tile t's pixels that lie in the region
+    TileRect clip(int32_t t) const {
+        const int tx = (t % tiles_x) * ts, ty = (t / tiles_x) * ts;
+        return {std::max(tx, x0), std::min(tx + ts, x1), std::max(ty, y0), std::min(ty + ts, y1)};
+    }
+    // work units of the streaming pipeline: one per primary sample of the plan's pixels
+    uint64_t units(int spp) const {
+        uint64_t n = 0;
+        for (int32_t t : tiles) {
+            const TileRect r = clip(t);
+            if (r.xb > r.xa && r.yb > r.ya) n += (uint64_t)(r.xb - r.xa) * (r.yb - r.ya) * (uint64_t)spp;
+        }
+        return n;
+    }
 };
+
+// lanes of a wave that share a pixel in the tile-list kernels: the largest power of two <= n samples, at most 64
+int lanes_for(int n) { int lanes = 64; while (lanes > n) lanes >>= 1; return lanes; }
 
 int make_plan(const zr_camera& cam, const zr_region* region, Plan& p) {
     p.W = cam.image_width < 1 ? 1 : cam.image_width;
@@ -89,12 +112,101 @@ int make_plan(const zr_camera& cam, const zr_region* region, Plan& p) {
             const int part = skew > 0 ? (int)(((long long)tx + (long long)skew * ty) % mod) : t % mod;   // zr_region::tile_skew
             if (part == rem) p.tiles.push_back(t);
         }
-    int spp = cam.samples_per_pixel < 1 ? 1 : cam.samples_per_pixel;
-    p.lanes = 64; while (p.lanes > spp) p.lanes >>= 1;
     return ZR_OK;
 }
 
-int resolve_times(zr_ctx* c);
+// tiles [first, first + count) of the uploaded tile list, for one launch of a tile-list kernel
+zr::WorkDesc work_desc(const Plan& p, const int32_t* d_tiles, size_t first, size_t count, int lanes) {
+    zr::WorkDesc wd;
+    wd.tiles = d_tiles + first; wd.n_tiles = (int32_t)count; wd.tile_size = p.ts; wd.tiles_x = p.tiles_x;
+    wd.x0 = p.x0; wd.y0 = p.y0; wd.x1 = p.x1; wd.y1 = p.y1;
+    wd.lanes_per_pixel = lanes;
+    return wd;
+}
+
+// the plan's pixels of the device frame -> the caller's frame, through `scratch`; no other pixel of `out` is touched (null: an output the caller did not ask for)
+int copy_region(const Plan& p, const double* d_frame, double* out, std::vector<double>& scratch) {
+    if (!out) return ZR_OK;
+    scratch.resize(p.npx() * 3);
+    HIP_OK(hipMemcpy(scratch.data(), d_frame, scratch.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int32_t t : p.tiles) {
+        const TileRect r = p.clip(t);
+        for (int y = r.ya; y < r.yb; y++)
+            if (r.xb > r.xa) std::memcpy(out + ((size_t)y * p.W + r.xa) * 3, scratch.data() + ((size_t)y * p.W + r.xa) * 3, (size_t)(r.xb - r.xa) * 3 * sizeof(double));
+    }
+    return ZR_OK;
+}
+
+// a zeroed device frame for an output the caller asked for
+int zeroed_frame(DevBuf<double>& d, const double* out, const Plan& p, hipStream_t stream) {
+    if (!out) return ZR_OK;
+    int rc = d.alloc(p.npx() * 3);
+    if (rc) return rc;
+    HIP_OK(hipMemsetAsync(d.p, 0, p.npx() * 3 * sizeof(double), stream));
+    return ZR_OK;
+}
+
+// the scene half of an entry point's argument preamble (the null tests differ per entry and stay there)
+int scene_ready(const zr_ctx* c, const zr_scene* s, const char* entry, bool any_context = false) {
+    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede %s", entry);
+    if (!any_context && s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
+    return ZR_OK;
+}
+
+int check_env(const zr::DEnv& de, const zr_scene* s) {
+    if (de.mode > ZR_ENV_SOLID_COLOR) return fail(ZR_E_INVALID, "unknown environment mode %u", de.mode);
+    if (de.mode == ZR_ENV_HDR_MAP && de.hdr_tex != ZR_NO_TEXTURE && de.hdr_tex >= s->textures.size()) return fail(ZR_E_INVALID, "environment texture id out of range");
+    return ZR_OK;
+}
+
+// One frame job: what every render entry works out before it launches, and what its driver needs.  prepare_frame fills the first line, the entry the rest.
+struct FrameJob {
+    Plan plan; zr::DCamera dc; zr::DEnv de{}; uint64_t seed = 0; hipStream_t stream = nullptr;
+    bool count = false;                               // zr_counters wanted
+    double* d_out = nullptr; double* d_out2 = nullptr;   // device frames (d_out2: the refraction frame of the split's replay pass)
+    volatile const uint8_t* keep_going = nullptr; volatile int* rows_done = nullptr;
+    zr::StreamProgress* progress = nullptr;
+    bool interactive() const { return keep_going || rows_done; }   // the caller polls: the tile-list paths need batch boundaries
+};
+
+// the shared validation, in the order every entry has had it: region and tile parameters, then the environment (`env` is null for the AOV passes, which have none)
+int prepare_frame(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region, FrameJob& job) {
+    HIP_OK(hipSetDevice(c->device));
+    int rc = make_plan(*cam, region, job.plan);
+    if (rc) return rc;
+    make_camera(*cam, job.dc);
+    if (env) { make_env(*env, job.de); if ((rc = check_env(job.de, s))) return rc; }
+    job.seed = seed; job.stream = c->stream;
+    return ZR_OK;
+}
+
+// Does the frame fit the streaming pipeline's packing (zr_launch.h: ST_MAX_*)?  Otherwise the pixel-group kernels render it: slower, same results.
+// depth_factor: paths per sample (the split passes trace two and count both in the bounce byte); units: the caller's count of work units
+bool fits_stream(const zr_ctx* c, const zr_scene* s, const Plan& plan, const zr::DCamera& dc, int depth_factor, uint64_t units) {
+    return c->variant == 2 && s->quad_ok /* ST_MAX_LEAF_PRIMS */ && depth_factor * dc.max_depth <= zr::ST_MAX_BOUNCES && units <= zr::ST_MAX_UNITS &&
+           plan.W <= zr::ST_MAX_FRAME_SIDE && plan.H <= zr::ST_MAX_FRAME_SIDE;
+}
+
+int resolve_times(zr_ctx* c) {
+    if (c->pending.empty()) return ZR_OK;
+    bool fresh = false;
+    for (auto& p : c->pending) {
+        HIP_OK(hipEventSynchronize(p.b));
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, p.a, p.b));
+        if (p.kind == c->log_kind) c->log.push_back(ms);  // default: the dominant kernel's launches (render_* / stream_extend)
+        if (p.render_id == c->render_id) {
+            if (!fresh) { c->last_render_ms = 0; c->last_extend_ms = 0; c->last_shade_ms = 0; fresh = true; }
+            c->last_render_ms += ms;
+            if (p.kind == 1) c->last_extend_ms += ms;
+            if (p.kind == 2) c->last_shade_ms += ms;
+        }
+        c->pool.push_back(p.a); c->pool.push_back(p.b);
+    }
+    c->pending.clear();
+    if (c->log.size() > (1u << 20)) c->log.erase(c->log.begin(), c->log.begin() + (c->log.size() - (1u << 20)));
+    return ZR_OK;
+}
 
 // spill slabs of the EXTEND traversal stack, sized for the deepest tree this context has met (never below 36 levels, the
 // fixed size of round 1): one slab per resident wave and sub-pool
@@ -109,13 +221,14 @@ int ensure_stack_slabs(zr_ctx* c, const zr_scene* s) {
     return ZR_OK;
 }
 
+// records a pair of HIP events around a launch into zr_ctx::pending (resolve_times turns them into milliseconds); the one recycler of zr_ctx::pool
 struct HostTimer : zr::StreamTimer {
-    zr_ctx* c; hipEvent_t cur_a = nullptr; bool ok = true;
+    zr_ctx* c; hipEvent_t cur_a = nullptr; hipError_t err = hipSuccess;
     explicit HostTimer(zr_ctx* c) : c(c) {}
     hipEvent_t get() {
         if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }
         hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) { ok = false; return nullptr; }
+        if ((err = hipEventCreate(&e)) != hipSuccess) return nullptr;
         return e;
     }
     void begin(hipStream_t st, int) override { cur_a = get(); if (cur_a) (void)hipEventRecord(cur_a, st); }
@@ -129,75 +242,53 @@ struct HostTimer : zr::StreamTimer {
     }
 };
 
-// variant 2: streaming wavefront pipeline (zr_stream.hip).  Synchronises the stream internally (the round loop
-// needs the active-slot count), so zr_render_device returns with the frame complete.
-// mode 0: the render; 1 / 2: beauty pass and replay pass of the reflection / refraction split (zr_stream.hip, stream_shade)
-int render_stream(zr_ctx* c, const zr_scene* s, const zr::DCamera& dc, const zr::DEnv& de, uint64_t seed, const Plan& plan, int count,
-                  double* d_out, hipStream_t stream, volatile const uint8_t* keep_going, int mode = 0, double* d_out2 = nullptr,
-                  zr::StreamProgress* progress = nullptr) {
-    // pixel list (cached per plan)
+// ---- variant 2: the streaming wavefront pipeline (zr_stream.hip), in the steps of render_stream below -------------------------------------------------
+
+// the plan's pixels as the pipeline's pixel list, uploaded when the plan differs from the cached list's
+int upload_pixel_list(zr_ctx* c, const Plan& plan) {
+    // Work units are handed out in pixel-list order, and when they run out the frame DRAINS: the paths still alive need up to
+    // max_depth more rounds, each with fewer rays than the chip wants (10 rounds = 16 ms of a 415 ms cfg3 frame, 10 of the
+    // 60 ms of a rank's 1/8 share).  The drain is as long as the paths started last, so the list runs BOTTOM-UP: the top
+    // of a frame is where the sky is, and a sky sample ends in one round.  The image does not depend on the order (every
+    // sample is written once and reduced in a fixed order).
+    const double bottom_up = env_double("ZR_STREAM_BOTTOM_UP", 1);
     std::vector<int32_t> key = {plan.W, plan.H, plan.ts, plan.x0, plan.y0, plan.x1, plan.y1, (int32_t)plan.tiles.size(),
                                 plan.tiles.empty() ? -1 : plan.tiles.front(), plan.tiles.empty() ? -1 : plan.tiles.back(),
-                                (int32_t)env_double("ZR_STREAM_BOTTOM_UP", 1)};
-    if (plan.W > 65535 || plan.H > 65535) return fail(ZR_E_INVALID, "kernel variant 2 supports frames up to 65535 x 65535");
-    if (key != c->pix_key || !c->d_pixels.p) {
-        std::vector<uint32_t> pix;
-        pix.reserve((size_t)plan.tiles.size() * plan.ts * plan.ts);
-        for (int32_t t : plan.tiles) {
-            int tx = (t % plan.tiles_x) * plan.ts, ty = (t / plan.tiles_x) * plan.ts;
-            int xa = std::max(tx, plan.x0), xb = std::min(tx + plan.ts, plan.x1), ya = std::max(ty, plan.y0), yb = std::min(ty + plan.ts, plan.y1);
-            for (int y = ya; y < yb; y++) for (int x = xa; x < xb; x++) pix.push_back((uint32_t)x | ((uint32_t)y << 16));
-        }
-        // Work units are handed out in pixel-list order, and when they run out the frame DRAINS: the paths still alive need up to
-        // max_depth more rounds, each with fewer rays than the chip wants (10 rounds = 16 ms of a 415 ms cfg3 frame, 10 of the
-        // 60 ms of a rank's 1/8 share).  The drain is as long as the paths started last, so the list runs BOTTOM-UP: the top
-        // of a frame is where the sky is, and a sky sample ends in one round.  The image does not depend on the order (every
-        // sample is written once and reduced in a fixed order).
-        if (env_double("ZR_STREAM_BOTTOM_UP", 1) != 0) std::reverse(pix.begin(), pix.end());
-        int rc = c->d_pixels.upload(pix);
-        if (rc) return rc;
-        c->pix_key = key;
+                                (int32_t)bottom_up};
+    if (key == c->pix_key && c->d_pixels.p) return ZR_OK;
+    std::vector<uint32_t> pix;
+    pix.reserve((size_t)plan.tiles.size() * plan.ts * plan.ts);
+    for (int32_t t : plan.tiles) {
+        const TileRect r = plan.clip(t);
+        for (int y = r.ya; y < r.yb; y++) for (int x = r.xa; x < r.xb; x++) pix.push_back((uint32_t)x | ((uint32_t)y << 16));   // ST_MAX_FRAME_SIDE
     }
-    const uint32_t n_pix = (uint32_t)c->d_pixels.n;
-    if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
-    c->render_id++; c->last_stream = stream; c->last_counted = count != 0; c->last_rounds = 0;
-    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), stream));
-    if (n_pix == 0) return ZR_OK;
-    const uint32_t spp = (uint32_t)dc.spp;
-    const uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
-    if (units > 0xFFFFFFFFull) return fail(ZR_E_INVALID, "frame too large for kernel variant 2 (pixels x spp must fit 32 bits); shard it (zr_region) or set ZR_KERNEL=0");
-    // slot pool: large enough to fill the chip every round, small enough that the frame takes dozens of rounds (a
-    // rank that owns 1/8 of the tiles must not degenerate into one shrinking batch)
-    int rc;
-    // per-sample radiance first: without it this pipeline cannot run at all (the caller falls back to the pixel-group kernel)
-    const size_t samples_n = (size_t)units * 3;
-    if (c->d_partial.n < samples_n) {
-        HIP_OK(hipStreamSynchronize(stream));
-        if (c->d_partial.alloc(samples_n) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes)", samples_n * sizeof(double));
-    }
-    // A world of a handful of objects is rendered by the FUSED kernel (zr_stream.hip: fused_render): every object tested per
-    // segment, the path in registers, no tree, no slot pool.  Testing all objects costs time in proportion to their number, the
-    // pipeline about the same per segment whatever the scene: the switch-over is ZR_FUSED_MAX objects.  A caller that polls
-    // (cancellation, lines_rendered, live preview) gets the frame in sixteen launches with the poll between them; the split passes
-    // stay on the pipeline.
-    if (mode == 0 && s->fused_ok && s->leaf_level <= 2 && s->leaf_objects > 0 && (double)s->leaf_objects <= env_double("ZR_FUSED_MAX", ZR_FUSED_OBJECTS) &&
-        env_double("ZR_FUSED", 1) != 0) {
-        if (c->fused_blocks == 0) c->fused_blocks = zr::fused_blocks();
-        HostTimer ftimer(c);
-        int parts = 1;
-        if (keep_going || progress) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), stream));   // a cancelled frame / a preview reduces what exists
-        hipError_t fe = zr::fused_render_frame(s->ds, dc, de, seed, spp, n_pix, c->d_pixels.p, c->d_partial.p, c->d_ctl.p, c->fused_blocks, d_out, c->d_ctr.p, count != 0,
-                                               s->leaf_level <= 1 ? 1 : 2, stream, &ftimer, s->fused, keep_going, progress, &parts);
-        if (fe != hipSuccess) return fail(ZR_E_DEVICE, "fused small-scene kernel failed: %s", hipGetErrorString(fe));
-        c->last_rounds = (uint64_t)(parts < 0 ? -parts : parts); c->last_path = 3;
-        HIP_OK(hipStreamSynchronize(stream));
-        if (parts < 0) return fail(ZR_E_CANCELLED, "render cancelled after %d of 16 parts", -parts);
-        return ZR_OK;
-    }
-    c->last_path = 2;
-    if ((rc = ensure_stack_slabs(c, s))) return rc;
-    // slot pool: large enough to fill the chip every round, small enough that the frame takes dozens of rounds (a
-    // rank that owns 1/8 of the tiles must not degenerate into one shrinking batch)
+    if (bottom_up != 0) std::reverse(pix.begin(), pix.end());
+    int rc = c->d_pixels.upload(pix);
+    if (rc == ZR_OK) c->pix_key = key;
+    return rc;
+}
+
+// A world of a handful of objects is rendered by the FUSED kernel (zr_stream.hip: fused_render): every object tested per
+// segment, the path in registers, no tree, no slot pool.  Testing all objects costs time in proportion to their number, the
+// pipeline about the same per segment whatever the scene: the switch-over is ZR_FUSED_MAX objects.  A caller that polls
+// (cancellation, lines_rendered, live preview) gets the frame in sixteen launches with the poll between them; the split passes
+// stay on the pipeline.
+int render_fused(zr_ctx* c, const zr_scene* s, const zr::StreamJob& sj) {
+    if (c->fused_blocks == 0) c->fused_blocks = zr::fused_blocks();
+    HostTimer timer(c);
+    int parts = 1;
+    zr::StreamHooks hooks = sj.hooks; hooks.timer = &timer; hooks.done_out = &parts;
+    hipError_t fe = zr::fused_render_frame(s->ds, sj.frame, sj.ctx, c->fused_blocks, s->leaf_level <= 1 ? 1 : 2, s->fused, hooks);
+    if (fe != hipSuccess) return fail(ZR_E_DEVICE, "fused small-scene kernel failed: %s", hipGetErrorString(fe));
+    c->last_rounds = (uint64_t)(parts < 0 ? -parts : parts); c->last_path = 3;
+    HIP_OK(hipStreamSynchronize(sj.ctx.streams[0]));
+    if (parts < 0) return fail(ZR_E_CANCELLED, "render cancelled after %d of 16 parts", -parts);
+    return ZR_OK;
+}
+
+// The slot pool of a frame of `units` work units: large enough to fill the chip every round, small enough that the frame takes dozens of rounds (a
+// rank that owns 1/8 of the tiles must not degenerate into one shrinking batch).  Grows zr_ctx::d_pool when this frame needs more than it holds.
+int size_slot_pool(zr_ctx* c, uint64_t units, uint32_t spp, bool lean_pair, hipStream_t stream, zr::StreamPool& pool) {
     const bool affine = env_double("ZR_STREAM_AFFINE", 0) != 0;   // measured: -18 % L2 requests, -14 % misses, frame time +1 % (profiles/r3_affine_ab.txt): off
     uint32_t P = 0, unit_chunk = 0, drain_slots = 0;
     size_t drain_at = 0;
@@ -205,8 +296,7 @@ int render_stream(zr_ctx* c, const zr_scene* s, const zr::DCamera& dc, const zr:
         P = cap / 64 * 64;
         // slots = units / 8 where the lean kernels run as two sub-pools (cfg2: 93.2 ms at 8, 98.9 at 4, 115 at 2), units / 3 for one pool of the general builds, whose
         // launches are worth making larger (demo: 128.1 ms at 8, 126.0 at 4, 125.1 at 3: profiles/r4_experiments_ab.txt)
-        const bool lean_two_pools = s->leaf_level == 0 && s->ds.shade_lean != 0 && mode == 0;
-        uint64_t want = std::max<uint64_t>(units / (uint64_t)std::max(1.0, env_double("ZR_STREAM_UNITS_PER_SLOT", lean_two_pools ? 8 : 3)), 1u << 20);
+        uint64_t want = std::max<uint64_t>(units / (uint64_t)std::max(1.0, env_double("ZR_STREAM_UNITS_PER_SLOT", lean_pair ? 8 : 3)), 1u << 20);
         want = want / 64 * 64;
         if (want < P) P = (uint32_t)want;
         if (units < P) P = (uint32_t)((units + 63) / 64 * 64);
@@ -235,133 +325,145 @@ int render_stream(zr_ctx* c, const zr_scene* s, const zr::DCamera& dc, const zr:
         std::fprintf(stderr, "[zr] no device memory for a pool of %u path slots (%zu bytes): retrying with half\n", P, pool_need);
     }
     const bool use_drain = env_double("ZR_STREAM_DRAIN_POOL", 1) != 0;
-    if (keep_going || progress) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), stream));  // a cancelled frame / a preview reduces what exists
-    if (mode != 0) {
-        if (c->d_kend.n < units * 2) { if ((rc = c->d_kend.alloc(units * 2))) return rc; }
-        if (c->d_cls.n < units) { if ((rc = c->d_cls.alloc(units))) return rc; }
-        if (mode == 2) HIP_OK(hipMemsetAsync(c->d_cls.p, 0, units, stream));
-        const size_t cp = ((size_t)c->st_slots / 256 + ST_MAX_POOLS + 1) * 4;
-        if (c->d_cpart.n < cp) { if ((rc = c->d_cpart.alloc(cp))) return rc; }
+    pool = zr::StreamPool{c->d_pool.p, P, use_drain ? (void*)(c->d_pool.p + drain_at) : nullptr, drain_slots, unit_chunk};
+    return ZR_OK;
+}
+
+// the buffers of the reflection / refraction split (mode 1 / 2), grown as the frame needs
+int split_buffers(zr_ctx* c, uint64_t units, int mode, hipStream_t stream, zr::StreamSplit& split) {
+    int rc;
+    if (c->d_kend.n < units * 2) { if ((rc = c->d_kend.alloc(units * 2))) return rc; }
+    if (c->d_cls.n < units) { if ((rc = c->d_cls.alloc(units))) return rc; }
+    if (mode == 2) HIP_OK(hipMemsetAsync(c->d_cls.p, 0, units, stream));
+    const size_t cp = ((size_t)c->st_slots / 256 + ST_MAX_POOLS + 1) * 4;
+    if (c->d_cpart.n < cp) { if ((rc = c->d_cpart.alloc(cp))) return rc; }
+    split = zr::StreamSplit{mode, c->d_kend.p, c->d_cls.p, c->d_cpart.p};
+    return ZR_OK;
+}
+
+// Renders job.plan into job.d_out through the pipeline or, for a small world, the fused kernel.  The frame must fit the pipeline (fits_stream: both callers ask
+// first).  Synchronises the stream internally (the round loop needs the active-slot count), so zr_render_device returns with the frame complete.
+// mode 0: the render; 1 / 2: beauty pass and replay pass of the reflection / refraction split (zr_stream.hip, stream_shade)
+int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode = 0) {
+    int rc = upload_pixel_list(c, job.plan);
+    if (rc) return rc;
+    const uint32_t n_pix = (uint32_t)c->d_pixels.n, spp = (uint32_t)job.dc.spp;
+    if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
+    c->render_id++; c->last_stream = job.stream; c->last_counted = job.count; c->last_rounds = 0;
+    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
+    if (n_pix == 0) return ZR_OK;
+    const uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
+    // per-sample radiance first: without it this pipeline cannot run at all (the caller falls back to the pixel-group kernel)
+    const size_t samples_n = (size_t)units * 3;
+    if (c->d_partial.n < samples_n) {
+        HIP_OK(hipStreamSynchronize(job.stream));
+        if (c->d_partial.alloc(samples_n) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes)", samples_n * sizeof(double));
     }
-    HostTimer timer(c);
-    int rounds = 0;
     hipStream_t streams[ST_MAX_POOLS];
-    streams[0] = stream;
+    streams[0] = job.stream;
     for (int k = 1; k < ST_MAX_POOLS; k++) streams[k] = c->sub[k];
-    const bool sharded = (size_t)plan.tiles.size() < (size_t)plan.tiles_x * plan.tiles_y;
+    zr::StreamJob sj{};
+    sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, c->d_pixels.p, c->d_partial.p, job.d_out, job.d_out2, job.count};
+    sj.ctx = zr::StreamContext{c->d_ctl.p, nullptr, 0, c->st_blocks, c->d_ctr.p, streams, 1, c->st_event, c->h_active};
+    sj.hooks = zr::StreamHooks{nullptr, job.keep_going, job.progress, nullptr};
+    const bool polled = job.keep_going || job.progress;   // a cancelled frame / a preview reduces what exists: the samples start at zero
+    if (mode == 0 && s->fused_ok && s->leaf_level <= 2 && s->leaf_objects > 0 && (double)s->leaf_objects <= env_double("ZR_FUSED_MAX", ZR_FUSED_OBJECTS) &&
+        env_double("ZR_FUSED", 1) != 0) {
+        if (polled) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), job.stream));
+        return render_fused(c, s, sj);
+    }
+    c->last_path = 2;
+    if ((rc = ensure_stack_slabs(c, s))) return rc;
+    sj.ctx.overflow = c->d_st_overflow.p; sj.ctx.ovf_levels = c->st_ovf_levels;
     // Two sub-pools, a fraction of a round apart on two streams, let one pool's SHADE run beside the other's EXTEND.  Until round 3 that paid on a rank's share only
     // (the whole frame: 366.6 against 365.7 ms): SHADE needed 124 registers and found no room beside EXTEND's waves.  The lean builds of both kernels use 80
     // (zr_stream.hip), a SIMD holds three waves of each, and a whole cfg3 frame gains 3.5 % with 64 Mi slots, 5.4 % with 128 Mi (profiles/r4_experiments_ab.txt); the
     // general builds (demo: 128 + 117 registers) do not fit beside each other and lose 2 %: one pool for those
     const bool lean_pair = s->leaf_level == 0 && s->ds.shade_lean != 0 && mode == 0;
-    const int pools = c->st_pools > 0 ? c->st_pools : ((sharded || lean_pair) ? 2 : 1);
-    hipError_t e = zr::stream_render(s->ds, dc, de, seed, c->d_pool.p, P, spp, n_pix, c->d_pixels.p, c->d_partial.p, c->d_ctl.p,
-                                     c->d_st_overflow.p, c->st_ovf_levels, c->st_blocks, d_out, c->d_ctr.p, count != 0, streams, pools, c->st_event, &timer, c->h_active,
-                                     keep_going, &rounds, s->leaf_level, mode, mode ? (void*)c->d_kend.p : nullptr, mode ? (void*)c->d_cls.p : nullptr, d_out2, mode ? c->d_cpart.p : nullptr, progress,
-                                     use_drain ? (void*)((unsigned char*)c->d_pool.p + drain_at) : nullptr, drain_slots, unit_chunk);
+    if ((rc = size_slot_pool(c, units, spp, lean_pair, job.stream, sj.pool))) return rc;
+    if (polled) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), job.stream));
+    sj.split.mode = mode;
+    if (mode != 0 && (rc = split_buffers(c, units, mode, job.stream, sj.split))) return rc;
+    const bool sharded = job.plan.tiles.size() < (size_t)job.plan.tiles_x * job.plan.tiles_y;
+    sj.ctx.n_pools = c->st_pools > 0 ? c->st_pools : ((sharded || lean_pair) ? 2 : 1);
+    HostTimer timer(c);
+    int rounds = 0;
+    sj.hooks.timer = &timer; sj.hooks.done_out = &rounds;
+    hipError_t e = zr::stream_render(s->ds, sj, s->leaf_level);
     if (e != hipSuccess) return fail(ZR_E_DEVICE, "streaming pipeline failed: %s", hipGetErrorString(e));
     c->last_rounds = (uint64_t)(rounds < 0 ? -rounds : rounds);
-    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipStreamSynchronize(job.stream));
     if (rounds < 0) return fail(ZR_E_CANCELLED, "render cancelled after %d rounds", -rounds);
     return ZR_OK;
 }
 
-int enqueue_render(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const Plan& plan, int count,
-                   double* d_out, hipStream_t stream, volatile const uint8_t* keep_going, volatile int* rows_done, zr::StreamProgress* progress = nullptr) {
-    c->last_rounds = 0;
-    zr::DCamera dc; make_camera(*cam, dc);
-    zr::DEnv de; make_env(*env, de);
-    if (de.mode > ZR_ENV_SOLID_COLOR) return fail(ZR_E_INVALID, "unknown environment mode %u", de.mode);
-    if (de.mode == ZR_ENV_HDR_MAP && de.hdr_tex != ZR_NO_TEXTURE) {
-        if (de.hdr_tex >= s->textures.size()) return fail(ZR_E_INVALID, "environment texture id out of range");
-    }
-    std::vector<int32_t> tiles = plan.tiles;
-    int rc = c->d_tiles.upload(tiles);
-    if (rc) return rc;
-    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), stream));
-    // the streaming pipeline packs bounce counters into 8 bits, work units into 32 bits and leaf references into 24 + 4
-    // bits; frames or scenes beyond that are rendered by the pixel-group megakernel below (slower, same results)
-    uint64_t stream_units = 0;
-    for (int32_t t : plan.tiles) {
-        int tx = (t % plan.tiles_x) * plan.ts, ty = (t / plan.tiles_x) * plan.ts;
-        int xa = std::max(tx, plan.x0), xb = std::min(tx + plan.ts, plan.x1), ya = std::max(ty, plan.y0), yb = std::min(ty + plan.ts, plan.y1);
-        if (xb > xa && yb > ya) stream_units += (uint64_t)(xb - xa) * (yb - ya) * (uint64_t)dc.spp;
-    }
-    if (c->variant == 2 && dc.max_depth <= 250 && s->quad_ok && stream_units <= 0xFFFFFFFFull && plan.W <= 65535 && plan.H <= 65535) {
-        int r2 = render_stream(c, s, dc, de, seed, plan, count, d_out, stream, keep_going, 0, nullptr, progress);
-        if (rows_done && r2 == ZR_OK) *rows_done = plan.H;
-        if (r2 != ZR_E_NOMEM) return r2;
-        // the pipeline's buffers (24 bytes per primary sample + the slot pool) do not fit beside what else lives on the device: the
-        // pixel-group kernel below needs neither
-        std::fprintf(stderr, "[zr] %s: rendering this frame with the pixel-group kernel (same results, slower)\n", zr_host::last_error());
-        HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), stream));
-    } else if (c->variant == 2 && !c->warned_fallback) {   // said once per context: the frame is rendered, by the slower kernel
-        c->warned_fallback = true;
-        std::fprintf(stderr, "[zr] frame outside the streaming pipeline's packing limits (max_depth %d > 250, %llu work units > 2^32, %d x %d px > 65535, "
-                             "or a scene with more than 2^24 primitives of a kind): rendered by the pixel-group kernel — same results, about six times slower\n",
-                     dc.max_depth, (unsigned long long)stream_units, plan.W, plan.H);
-    }
-    c->last_path = 0;
-    // one launch per frame unless the caller wants progress / cancellation, which need batch boundaries
-    const bool interactive = keep_going || rows_done;
-    const int batch = (int)batch_tiles(interactive);
-    size_t n_batches = (tiles.size() + batch - 1) / batch;
-    if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
-    c->render_id++; c->last_stream = stream; c->last_counted = count != 0;
-    auto get_event = [&](hipEvent_t& e) -> int {
-        if (!c->pool.empty()) { e = c->pool.back(); c->pool.pop_back(); return ZR_OK; }
-        HIP_OK(hipEventCreate(&e));
-        return ZR_OK;
-    };
+// ---- the tile-list paths ------------------------------------------------------------------------------------------------------------------------------
+
+// The batch loop of the two interactive tile-list callers (the pixel-group path of enqueue_render, zr_render_bvh_debug): the uploaded tile list in batches of
+// batch_tiles(), `launch(first, count)` for each.  A caller that polls gets keep_going looked at before every batch and, after it, the stream synchronised
+// (progress / cancellation need the batch to have finished: camera.hpp:441,548-552) and `report_rows(last tile of the batch, is it the last batch)` run.
+template <class Launch, class ReportRows>
+int run_tile_batches(const FrameJob& job, Launch launch, ReportRows report_rows) {
+    const std::vector<int32_t>& tiles = job.plan.tiles;
+    const size_t batch = batch_tiles(job.interactive());
+    const size_t n_batches = (tiles.size() + batch - 1) / batch;
     for (size_t b = 0; b < n_batches; b++) {
-        if (keep_going && *keep_going == 0) {
-            HIP_OK(hipStreamSynchronize(stream));
+        if (job.keep_going && *job.keep_going == 0) {
+            HIP_OK(hipStreamSynchronize(job.stream));
             return fail(ZR_E_CANCELLED, "render cancelled after %zu of %zu batches", b, n_batches);
         }
-        zr::WorkDesc wd;
-        wd.tiles = c->d_tiles.p + b * batch;
-        wd.n_tiles = (int32_t)std::min<size_t>(batch, tiles.size() - b * batch);
-        wd.tile_size = plan.ts; wd.tiles_x = plan.tiles_x;
-        wd.x0 = plan.x0; wd.y0 = plan.y0; wd.x1 = plan.x1; wd.y1 = plan.y1;
-        wd.lanes_per_pixel = plan.lanes;
-        zr_ctx::Pending pe{}; pe.render_id = c->render_id; pe.kind = 1;
-        if ((rc = get_event(pe.a)) || (rc = get_event(pe.b))) return rc;
-        HIP_OK(hipEventRecord(pe.a, stream));
-        HIP_OK(zr::launch_render(s->ds, dc, de, seed, wd, d_out, c->d_ctr.p, count != 0, stream));
-        HIP_OK(hipEventRecord(pe.b, stream));
-        c->pending.push_back(pe);
-        if (keep_going || rows_done) {
-            // progress / cancellation need the batch to have finished (camera.hpp:441,548-552)
-            HIP_OK(hipStreamSynchronize(stream));
-            if (rows_done) {
-                int last_tile = tiles[std::min(tiles.size(), (b + 1) * (size_t)batch) - 1];
-                int rows = std::min(plan.H, (last_tile / plan.tiles_x) * plan.ts);
-                if (rows > *rows_done) *rows_done = rows;
-            }
+        const size_t end = std::min(tiles.size(), (b + 1) * batch);
+        int rc = launch(b * batch, end - b * batch);
+        if (rc) return rc;
+        if (job.interactive()) {
+            HIP_OK(hipStreamSynchronize(job.stream));
+            if (job.rows_done) report_rows(tiles[end - 1], b + 1 == n_batches);
         }
     }
     return ZR_OK;
 }
 
-int resolve_times(zr_ctx* c) {
-    if (c->pending.empty()) return ZR_OK;
-    bool fresh = false;
-    for (auto& p : c->pending) {
-        HIP_OK(hipEventSynchronize(p.b));
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, p.a, p.b));
-        if (p.kind == c->log_kind) c->log.push_back(ms);  // default: the dominant kernel's launches (render_* / stream_extend)
-        if (p.render_id == c->render_id) {
-            if (!fresh) { c->last_render_ms = 0; c->last_extend_ms = 0; c->last_shade_ms = 0; fresh = true; }
-            c->last_render_ms += ms;
-            if (p.kind == 1) c->last_extend_ms += ms;
-            if (p.kind == 2) c->last_shade_ms += ms;
-        }
-        c->pool.push_back(p.a); c->pool.push_back(p.b);
+// Renders the job through the streaming pipeline where the frame fits it and the device has the memory, else through the pixel-group kernel.  (Left alone, as they
+// change what a frame submits: the tile list is uploaded for every frame although only the pixel-group path reads it; the counter block is cleared here and in render_stream.)
+int enqueue_render(zr_ctx* c, const zr_scene* s, const FrameJob& job) {
+    const Plan& plan = job.plan;
+    c->last_rounds = 0;
+    int rc = c->d_tiles.upload(plan.tiles);
+    if (rc) return rc;
+    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
+    const uint64_t units = plan.units(job.dc.spp);
+    if (fits_stream(c, s, plan, job.dc, 1, units)) {
+        int r2 = render_stream(c, s, job);
+        if (job.rows_done && r2 == ZR_OK) *job.rows_done = plan.H;
+        if (r2 != ZR_E_NOMEM) return r2;
+        // the pipeline's buffers (24 bytes per primary sample + the slot pool) do not fit beside what else lives on the device: the
+        // pixel-group kernel below needs neither
+        std::fprintf(stderr, "[zr] %s: rendering this frame with the pixel-group kernel (same results, slower)\n", zr_host::last_error());
+        HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
+    } else if (c->variant == 2 && !c->warned_fallback) {   // said once per context: the frame is rendered, by the slower kernel
+        c->warned_fallback = true;
+        std::fprintf(stderr, "[zr] frame outside the streaming pipeline's packing limits (max_depth %d > %d, %llu work units > 2^32, %d x %d px > %d, "
+                             "or a scene with more than 2^24 primitives of a kind): rendered by the pixel-group kernel — same results, about six times slower\n",
+                     job.dc.max_depth, zr::ST_MAX_BOUNCES, (unsigned long long)units, plan.W, plan.H, zr::ST_MAX_FRAME_SIDE);
     }
-    c->pending.clear();
-    if (c->log.size() > (1u << 20)) c->log.erase(c->log.begin(), c->log.begin() + (c->log.size() - (1u << 20)));
-    return ZR_OK;
+    c->last_path = 0;
+    if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
+    c->render_id++; c->last_stream = job.stream; c->last_counted = job.count;
+    HostTimer timer(c);
+    // rows_done after a batch: the rows ABOVE the tile row of the batch's last tile.  (zr_render_bvh_debug counts that tile row in, which is what a batch has
+    // finished when it ends a tile row; the two rules differ by one tile row and are both kept as they were.)
+    return run_tile_batches(job,
+        [&](size_t first, size_t count) -> int {
+            timer.begin(job.stream, 1);
+            HIP_OK(zr::launch_render(s->ds, job.dc, job.de, job.seed, work_desc(plan, c->d_tiles.p, first, count, lanes_for(job.dc.spp)), job.d_out, c->d_ctr.p, job.count, job.stream));
+            timer.end(job.stream, 1);
+            if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
+            return ZR_OK;
+        },
+        [&](int last_tile, bool) {
+            const int rows = std::min(plan.H, (last_tile / plan.tiles_x) * plan.ts);
+            if (rows > *job.rows_done) *job.rows_done = rows;
+        });
 }
 
 }  // namespace
@@ -371,42 +473,32 @@ extern "C" {
 int zr_render_device(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region,
                      int collect_counters, void* d_out_rgb, void* hip_stream) {
     if (!c || !s || !cam || !env || !d_out_rgb) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_render");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
-    HIP_OK(hipSetDevice(c->device));
-    Plan plan;
-    int rc = make_plan(*cam, region, plan);
+    int rc = scene_ready(c, s, "zr_render");
     if (rc) return rc;
+    FrameJob job;
+    if ((rc = prepare_frame(c, s, cam, env, seed, region, job))) return rc;
     // default stream requested: use the legacy null stream so that callers' stream-ordered work (torch) sees it
-    hipStream_t st = (hipStream_t)hip_stream;
-    return enqueue_render(c, s, cam, env, seed, plan, collect_counters, (double*)d_out_rgb, st, nullptr, nullptr);
+    job.stream = (hipStream_t)hip_stream;
+    job.count = collect_counters != 0; job.d_out = (double*)d_out_rgb;
+    return enqueue_render(c, s, job);
 }
 
 int zr_render(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region,
               int collect_counters, double* out_rgb, volatile const uint8_t* keep_going, volatile int* rows_done) {
     if (!c || !s || !cam || !env || !out_rgb) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_render");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
-    HIP_OK(hipSetDevice(c->device));
-    Plan plan;
-    int rc = make_plan(*cam, region, plan);
+    int rc = scene_ready(c, s, "zr_render");
     if (rc) return rc;
-    const size_t npx = (size_t)plan.W * plan.H;
-    if ((rc = c->d_out.alloc(npx * 3))) return rc;
-    HIP_OK(hipMemsetAsync(c->d_out.p, 0, npx * 3 * sizeof(double), c->stream));
+    FrameJob job;
+    if ((rc = prepare_frame(c, s, cam, env, seed, region, job))) return rc;
+    const Plan& plan = job.plan;
+    if ((rc = c->d_out.alloc(plan.npx() * 3))) return rc;
+    HIP_OK(hipMemsetAsync(c->d_out.p, 0, plan.npx() * 3 * sizeof(double), c->stream));
     if (rows_done) *rows_done = 0;
     // a whole frame goes straight into the caller's buffer; a region through a staging copy (only its pixels may be touched)
-    const bool whole = (size_t)plan.tiles.size() == (size_t)plan.tiles_x * plan.tiles_y && plan.x0 == 0 && plan.y0 == 0 && plan.x1 == plan.W && plan.y1 == plan.H;
-    std::vector<double> frame(whole ? 0 : npx * 3);
-    auto copy_out = [&]() -> int {   // the region's pixels of the device frame -> the caller's buffer
-        if (whole) { HIP_OK(hipMemcpy(out_rgb, c->d_out.p, npx * 3 * sizeof(double), hipMemcpyDeviceToHost)); return ZR_OK; }
-        HIP_OK(hipMemcpy(frame.data(), c->d_out.p, frame.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int32_t t : plan.tiles) {
-            int tx = (t % plan.tiles_x) * plan.ts, ty = (t / plan.tiles_x) * plan.ts;
-            int xa = std::max(tx, plan.x0), xb = std::min(tx + plan.ts, plan.x1), ya = std::max(ty, plan.y0), yb = std::min(ty + plan.ts, plan.y1);
-            for (int y = ya; y < yb; y++)
-                if (xb > xa) std::memcpy(out_rgb + ((size_t)y * plan.W + xa) * 3, frame.data() + ((size_t)y * plan.W + xa) * 3, (size_t)(xb - xa) * 3 * sizeof(double));
-        }
+    std::vector<double> staging;
+    auto copy_out = [&]() -> int {
+        if (!plan.whole()) return copy_region(plan, c->d_out.p, out_rgb, staging);
+        HIP_OK(hipMemcpy(out_rgb, c->d_out.p, plan.npx() * 3 * sizeof(double), hipMemcpyDeviceToHost));
         return ZR_OK;
     };
     // Progress as the reference's callers see it: lines_rendered advances while the frame renders (camera.hpp:548-552) and the
@@ -424,7 +516,9 @@ int zr_render(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* 
         }
     } preview;
     preview.rows = rows_done; preview.H = plan.H; preview.copy = copy_out; preview.period = env_double("ZR_PREVIEW_PERIOD_S", 0.2); preview.last = Preview::now();
-    int rrc = enqueue_render(c, s, cam, env, seed, plan, collect_counters, c->d_out.p, c->stream, keep_going, rows_done, rows_done ? &preview : nullptr);
+    job.count = collect_counters != 0; job.d_out = c->d_out.p;
+    job.keep_going = keep_going; job.rows_done = rows_done; job.progress = rows_done ? &preview : nullptr;
+    int rrc = enqueue_render(c, s, job);
     if (rrc != ZR_OK && rrc != ZR_E_CANCELLED) return rrc;
     std::string cancel_msg = zr_host::last_error();
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -437,113 +531,72 @@ int zr_render(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* 
 int zr_render_aov(zr_ctx* c, const zr_scene* s, const zr_camera* cam, uint64_t seed, const zr_region* region, const zr_aov_params* ap,
                   double* out_albedo, double* out_normal, double* out_zdepth) {
     if (!c || !s || !cam || !ap) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_render_aov");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
-    if (!out_albedo && !out_normal && !out_zdepth) return ZR_OK;
-    HIP_OK(hipSetDevice(c->device));
-    Plan plan;
-    int rc = make_plan(*cam, region, plan);
+    int rc = scene_ready(c, s, "zr_render_aov");
     if (rc) return rc;
-    zr::DCamera dc; make_camera(*cam, dc);
+    if (!out_albedo && !out_normal && !out_zdepth) return ZR_OK;
+    FrameJob job;
+    if ((rc = prepare_frame(c, s, cam, nullptr, seed, region, job))) return rc;
     // camera basis u, v, w exactly as camera::initialize builds it (camera.hpp:380-382)
     H3 w = unit(h3(cam->lookfrom) - h3(cam->lookat));
     H3 u = unit(cross(h3(cam->vup), w));
     H3 v = cross(w, u);
     double uvw[9] = {u.x, u.y, u.z, v.x, v.y, v.z, w.x, w.y, w.z};
-    const int spp = dc.spp;
+    const int spp = job.dc.spp;
     const int aux_sample = std::min(std::max(spp / 8, 64), 1024);   // std::clamp(spp / 8, 64, 1024), camera.hpp:433
     const int aux = std::min(aux_sample, spp);                      // camera.hpp:535
-    const size_t npx = (size_t)plan.W * plan.H;
+    const Plan& plan = job.plan;
     DevBuf<double> d_a, d_n, d_z;
-    if (out_albedo) { if ((rc = d_a.alloc(npx * 3))) return rc; HIP_OK(hipMemsetAsync(d_a.p, 0, npx * 24, c->stream)); }
-    if (out_normal) { if ((rc = d_n.alloc(npx * 3))) return rc; HIP_OK(hipMemsetAsync(d_n.p, 0, npx * 24, c->stream)); }
-    if (out_zdepth) { if ((rc = d_z.alloc(npx * 3))) return rc; HIP_OK(hipMemsetAsync(d_z.p, 0, npx * 24, c->stream)); }
-    std::vector<int32_t> tiles = plan.tiles;
-    if ((rc = c->d_tiles.upload(tiles))) return rc;
-    zr::WorkDesc wd;
-    wd.tiles = c->d_tiles.p; wd.n_tiles = (int32_t)tiles.size(); wd.tile_size = plan.ts; wd.tiles_x = plan.tiles_x;
-    wd.x0 = plan.x0; wd.y0 = plan.y0; wd.x1 = plan.x1; wd.y1 = plan.y1;
-    wd.lanes_per_pixel = 64; while (wd.lanes_per_pixel > aux) wd.lanes_per_pixel >>= 1;
-    HIP_OK(zr::launch_aov(s->ds, dc, seed, wd, aux, ap->z_depth_max_dist, uvw, d_a.p, d_n.p, d_z.p, c->stream));
+    if ((rc = zeroed_frame(d_a, out_albedo, plan, c->stream)) || (rc = zeroed_frame(d_n, out_normal, plan, c->stream)) || (rc = zeroed_frame(d_z, out_zdepth, plan, c->stream))) return rc;
+    if ((rc = c->d_tiles.upload(plan.tiles))) return rc;
+    const zr::WorkDesc wd = work_desc(plan, c->d_tiles.p, 0, plan.tiles.size(), lanes_for(aux));
+    HIP_OK(zr::launch_aov(s->ds, job.dc, seed, wd, aux, ap->z_depth_max_dist, uvw, d_a.p, d_n.p, d_z.p, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
-    std::vector<double> frame(npx * 3);
-    auto copy_out = [&](DevBuf<double>& d, double* out) -> int {
-        if (!out) return ZR_OK;
-        HIP_OK(hipMemcpy(frame.data(), d.p, frame.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int32_t t : plan.tiles) {
-            int tx = (t % plan.tiles_x) * plan.ts, ty = (t / plan.tiles_x) * plan.ts;
-            int xa = std::max(tx, plan.x0), xb = std::min(tx + plan.ts, plan.x1), ya = std::max(ty, plan.y0), yb = std::min(ty + plan.ts, plan.y1);
-            for (int y = ya; y < yb; y++)
-                if (xb > xa) std::memcpy(out + ((size_t)y * plan.W + xa) * 3, frame.data() + ((size_t)y * plan.W + xa) * 3, (size_t)(xb - xa) * 3 * sizeof(double));
-        }
-        return ZR_OK;
-    };
-    if ((rc = copy_out(d_a, out_albedo)) || (rc = copy_out(d_n, out_normal)) || (rc = copy_out(d_z, out_zdepth))) return rc;
+    std::vector<double> staging;
+    if ((rc = copy_region(plan, d_a.p, out_albedo, staging)) || (rc = copy_region(plan, d_n.p, out_normal, staging)) || (rc = copy_region(plan, d_z.p, out_zdepth, staging))) return rc;
     return ZR_OK;
 }
 
 int zr_render_passes(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region,
                      double* out_beauty, double* out_reflection, double* out_refraction) {
     if (!c || !s || !cam || !env) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_render_passes");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
-    if (!out_beauty && !out_reflection && !out_refraction) return ZR_OK;
-    HIP_OK(hipSetDevice(c->device));
-    Plan plan;
-    int rc = make_plan(*cam, region, plan);
+    int rc = scene_ready(c, s, "zr_render_passes");
     if (rc) return rc;
-    zr::DCamera dc; make_camera(*cam, dc);
-    zr::DEnv de; make_env(*env, de);
-    if (de.mode > ZR_ENV_SOLID_COLOR) return fail(ZR_E_INVALID, "unknown environment mode %u", de.mode);
-    if (de.mode == ZR_ENV_HDR_MAP && de.hdr_tex != ZR_NO_TEXTURE && de.hdr_tex >= s->textures.size()) return fail(ZR_E_INVALID, "environment texture id out of range");
-    const size_t npx = (size_t)plan.W * plan.H;
+    if (!out_beauty && !out_reflection && !out_refraction) return ZR_OK;
+    FrameJob job;
+    if ((rc = prepare_frame(c, s, cam, env, seed, region, job))) return rc;
+    const Plan& plan = job.plan;
     DevBuf<double> d_b, d_r, d_f;
-    if (out_beauty) { if ((rc = d_b.alloc(npx * 3))) return rc; HIP_OK(hipMemsetAsync(d_b.p, 0, npx * 24, c->stream)); }
-    if (out_reflection) { if ((rc = d_r.alloc(npx * 3))) return rc; HIP_OK(hipMemsetAsync(d_r.p, 0, npx * 24, c->stream)); }
-    if (out_refraction) { if ((rc = d_f.alloc(npx * 3))) return rc; HIP_OK(hipMemsetAsync(d_f.p, 0, npx * 24, c->stream)); }
-    std::vector<int32_t> tiles = plan.tiles;
-    if ((rc = c->d_tiles.upload(tiles))) return rc;
-    zr::WorkDesc wd;
-    wd.tiles = c->d_tiles.p; wd.n_tiles = (int32_t)tiles.size(); wd.tile_size = plan.ts; wd.tiles_x = plan.tiles_x;
-    wd.x0 = plan.x0; wd.y0 = plan.y0; wd.x1 = plan.x1; wd.y1 = plan.y1;
-    wd.lanes_per_pixel = 64; while (wd.lanes_per_pixel > dc.spp) wd.lanes_per_pixel >>= 1;
-    const uint64_t stream_units = (uint64_t)plan.tiles.size() * plan.ts * plan.ts * (uint64_t)dc.spp;
-    const bool streaming = c->variant == 2 && s->quad_ok && 2 * dc.max_depth <= 250 && stream_units <= 0xFFFFFFFFull && plan.W <= 65535 &&
-                           plan.H <= 65535 && env_double("ZR_PASSES_STREAM", 1) != 0;
-    if (streaming) {
+    if ((rc = zeroed_frame(d_b, out_beauty, plan, c->stream)) || (rc = zeroed_frame(d_r, out_reflection, plan, c->stream)) || (rc = zeroed_frame(d_f, out_refraction, plan, c->stream))) return rc;
+    if ((rc = c->d_tiles.upload(plan.tiles))) return rc;
+    // Historical, kept: this entry counts whole tiles, not the clipped region as zr_render does (Plan::units).  The counts differ by less than a tile's width
+    // of pixels per edge, so they only pick different paths for a frame that close to 2^32 units — and both paths render the same frame.
+    const uint64_t tile_units = (uint64_t)plan.tiles.size() * plan.ts * plan.ts * (uint64_t)job.dc.spp;
+    if (fits_stream(c, s, plan, job.dc, 2, tile_units) && env_double("ZR_PASSES_STREAM", 1) != 0) {
         // two runs of the streaming pipeline: the beauty pass records where every sample's stream stopped, the replay pass traces
         // the camera ray again and runs the second path from there (stream_shade MODE 1 / 2)
         unsigned long long ha[zr::CTR_WORDS], hb[zr::CTR_WORDS];
-        if ((rc = render_stream(c, s, dc, de, seed, plan, 0, d_b.p, c->stream, nullptr, 1))) return rc;
+        job.d_out = d_b.p;
+        if ((rc = render_stream(c, s, job, 1))) return rc;
         HIP_OK(hipMemcpy(ha, c->d_ctr.p, sizeof ha, hipMemcpyDeviceToHost));
-        if ((rc = render_stream(c, s, dc, de, seed, plan, 0, d_r.p, c->stream, nullptr, 2, d_f.p))) return rc;
+        job.d_out = d_r.p; job.d_out2 = d_f.p;
+        if ((rc = render_stream(c, s, job, 2))) return rc;
         c->last_path = 2;
         HIP_OK(hipMemcpy(hb, c->d_ctr.p, sizeof hb, hipMemcpyDeviceToHost));
         // counted by SHADE in both passes (EXTEND runs uninstrumented): samples, segments, hits, draws
         unsigned long long h[zr::CTR_WORDS] = {0};
-        h[zr::CTR_SAMPLES] = (unsigned long long)c->d_pixels.n * (unsigned long long)dc.spp;   // every sample of the region, once
+        h[zr::CTR_SAMPLES] = (unsigned long long)c->d_pixels.n * (unsigned long long)job.dc.spp;   // every sample of the region, once
         for (int w : {zr::CTR_SEGMENTS, zr::CTR_HITS, zr::CTR_DRAWS}) h[w] = ha[w] + hb[w];
         HIP_OK(hipMemcpy(c->d_ctr.p, h, sizeof h, hipMemcpyHostToDevice));
         c->last_counted = true;
     } else {
         c->render_id++; c->last_counted = true; c->last_rounds = 0; c->last_path = 0;
         HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), c->stream));
-        HIP_OK(zr::launch_passes(s->ds, dc, de, seed, wd, d_b.p, d_r.p, d_f.p, c->d_ctr.p, c->stream));
+        const zr::WorkDesc wd = work_desc(plan, c->d_tiles.p, 0, plan.tiles.size(), lanes_for(job.dc.spp));
+        HIP_OK(zr::launch_passes(s->ds, job.dc, job.de, seed, wd, d_b.p, d_r.p, d_f.p, c->d_ctr.p, c->stream));
     }
     HIP_OK(hipStreamSynchronize(c->stream));
-    std::vector<double> frame(npx * 3);
-    auto copy_out = [&](DevBuf<double>& d, double* out) -> int {
-        if (!out) return ZR_OK;
-        HIP_OK(hipMemcpy(frame.data(), d.p, frame.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int32_t t : plan.tiles) {
-            int tx = (t % plan.tiles_x) * plan.ts, ty = (t / plan.tiles_x) * plan.ts;
-            int xa = std::max(tx, plan.x0), xb = std::min(tx + plan.ts, plan.x1), ya = std::max(ty, plan.y0), yb = std::min(ty + plan.ts, plan.y1);
-            for (int y = ya; y < yb; y++)
-                if (xb > xa) std::memcpy(out + ((size_t)y * plan.W + xa) * 3, frame.data() + ((size_t)y * plan.W + xa) * 3, (size_t)(xb - xa) * 3 * sizeof(double));
-        }
-        return ZR_OK;
-    };
-    if ((rc = copy_out(d_b, out_beauty)) || (rc = copy_out(d_r, out_reflection)) || (rc = copy_out(d_f, out_refraction))) return rc;
+    std::vector<double> staging;
+    if ((rc = copy_region(plan, d_b.p, out_beauty, staging)) || (rc = copy_region(plan, d_r.p, out_reflection, staging)) || (rc = copy_region(plan, d_f.p, out_refraction, staging))) return rc;
     return ZR_OK;
 }
 
@@ -645,57 +698,31 @@ int zr_render_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_camera* cam, cons
                         const zr_bvh_debug_params* dp, double* out_rgb, volatile const uint8_t* keep_going, volatile int* rows_done) {
     if (!c || !s || !cam || !env || !out_rgb) return fail(ZR_E_INVALID, "null argument");
     int rc = check_debug_params(dp);
-    if (rc) return rc;
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_render_bvh_debug");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
-    HIP_OK(hipSetDevice(c->device));
-    Plan plan;
-    if ((rc = make_plan(*cam, region, plan))) return rc;
-    zr::DCamera dc; make_camera(*cam, dc);
-    zr::DEnv de; make_env(*env, de);
-    if (de.mode > ZR_ENV_SOLID_COLOR) return fail(ZR_E_INVALID, "unknown environment mode %u", de.mode);
-    if (de.mode == ZR_ENV_HDR_MAP && de.hdr_tex != ZR_NO_TEXTURE && de.hdr_tex >= s->textures.size()) return fail(ZR_E_INVALID, "environment texture id out of range");
-    const size_t npx = (size_t)plan.W * plan.H;
-    if ((rc = c->d_out.alloc(npx * 3))) return rc;
-    HIP_OK(hipMemsetAsync(c->d_out.p, 0, npx * 3 * sizeof(double), c->stream));
+    if (rc || (rc = scene_ready(c, s, "zr_render_bvh_debug"))) return rc;
+    FrameJob job;
+    if ((rc = prepare_frame(c, s, cam, env, seed, region, job))) return rc;
+    const Plan& plan = job.plan;
+    if ((rc = c->d_out.alloc(plan.npx() * 3))) return rc;
+    HIP_OK(hipMemsetAsync(c->d_out.p, 0, plan.npx() * 3 * sizeof(double), c->stream));
     if (rows_done) *rows_done = 0;
-    std::vector<int32_t> tiles = plan.tiles;
-    if ((rc = c->d_tiles.upload(tiles))) return rc;
-    // one launch per frame unless the caller polls (cancellation, progress): then batches of tiles with the poll between them, as zr_render's
-    // pixel-group path does
-    const bool interactive = keep_going || rows_done;
-    const size_t batch = batch_tiles(interactive);
-    const size_t n_batches = (tiles.size() + batch - 1) / batch;
-    int rrc = ZR_OK;
-    for (size_t b = 0; b < n_batches; b++) {
-        if (keep_going && *keep_going == 0) { rrc = ZR_E_CANCELLED; fail(rrc, "render cancelled after %zu of %zu batches", b, n_batches); break; }
-        zr::WorkDesc wd;
-        wd.tiles = c->d_tiles.p + b * batch;
-        wd.n_tiles = (int32_t)std::min(batch, tiles.size() - b * batch);
-        wd.tile_size = plan.ts; wd.tiles_x = plan.tiles_x;
-        wd.x0 = plan.x0; wd.y0 = plan.y0; wd.x1 = plan.x1; wd.y1 = plan.y1;
-        wd.lanes_per_pixel = 1;
-        HIP_OK(zr::launch_bvh_debug(s->ds, dc, de, seed, wd, dp->level, dp->thickness, c->d_out.p, c->stream));
-        if (interactive) {
-            HIP_OK(hipStreamSynchronize(c->stream));
-            if (rows_done) {
-                const int last_tile = tiles[std::min(tiles.size(), (b + 1) * batch) - 1];
-                const int rows = std::min(plan.H, (last_tile / plan.tiles_x + 1) * plan.ts);
-                if (rows > *rows_done) *rows_done = b + 1 == n_batches ? plan.H : rows;
-            }
-        }
-    }
+    if ((rc = c->d_tiles.upload(plan.tiles))) return rc;
+    job.d_out = c->d_out.p; job.keep_going = keep_going; job.rows_done = rows_done;
+    // rows_done after a batch: the rows down to the lower edge of the tile row of the batch's last tile, the whole frame after the last batch.  (The pixel-group
+    // path of enqueue_render reports one tile row less, the rows above that tile row; both rules are kept as they were.)
+    int rrc = run_tile_batches(job,
+        [&](size_t first, size_t count) -> int {
+            HIP_OK(zr::launch_bvh_debug(s->ds, job.dc, job.de, seed, work_desc(plan, c->d_tiles.p, first, count, 1), dp->level, dp->thickness, c->d_out.p, c->stream));
+            return ZR_OK;
+        },
+        [&](int last_tile, bool last_batch) {
+            const int rows = std::min(plan.H, (last_tile / plan.tiles_x + 1) * plan.ts);
+            if (rows > *rows_done) *rows_done = last_batch ? plan.H : rows;
+        });
+    if (rrc != ZR_OK && rrc != ZR_E_CANCELLED) return rrc;
     std::string cancel_msg = zr_host::last_error();
     HIP_OK(hipStreamSynchronize(c->stream));
-    // the region's pixels of the device frame -> the caller's buffer (other pixels are not touched)
-    std::vector<double> frame(npx * 3);
-    HIP_OK(hipMemcpy(frame.data(), c->d_out.p, frame.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int32_t t : plan.tiles) {
-        int tx = (t % plan.tiles_x) * plan.ts, ty = (t / plan.tiles_x) * plan.ts;
-        int xa = std::max(tx, plan.x0), xb = std::min(tx + plan.ts, plan.x1), ya = std::max(ty, plan.y0), yb = std::min(ty + plan.ts, plan.y1);
-        for (int y = ya; y < yb; y++)
-            if (xb > xa) std::memcpy(out_rgb + ((size_t)y * plan.W + xa) * 3, frame.data() + ((size_t)y * plan.W + xa) * 3, (size_t)(xb - xa) * 3 * sizeof(double));
-    }
+    std::vector<double> staging;
+    if ((rc = copy_region(plan, c->d_out.p, out_rgb, staging))) return rc;
     if (rrc == ZR_E_CANCELLED) return fail(rrc, "%s", cancel_msg.c_str());
     if (rows_done) *rows_done = plan.H;
     return ZR_OK;
@@ -706,8 +733,7 @@ int zr_trace_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_bvh_debug_params* 
     if (!c || !s || (n && (!rays6 || !out))) return fail(ZR_E_INVALID, "null argument");
     int rc = check_debug_params(dp);
     if (rc) return rc;
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_trace_bvh_debug");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
+    if (int rc0 = scene_ready(c, s, "zr_trace_bvh_debug")) return rc0;
     if (n == 0) return ZR_OK;
     HIP_OK(hipSetDevice(c->device));
     DevBuf<double> d_rays; DevBuf<zr_bvh_debug_hit> d_out;
@@ -720,7 +746,7 @@ int zr_trace_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_bvh_debug_params* 
 
 int zr_trace_paths(zr_ctx* c, const zr_scene* s, const zr_camera* cam, uint64_t seed, const int32_t* requests, int n, int max_segments, double* out) {
     if (!c || !s || !cam || (n > 0 && (!requests || !out))) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_trace_paths");
+    if (int rc0 = scene_ready(c, s, "zr_trace_paths", true)) return rc0;   // a scene of any context is accepted here, unlike everywhere else: kept as it has always been
     if (n <= 0 || max_segments <= 0) return ZR_OK;
     static_assert(ZR_PATH_RECORD == ZR_PATH_REC, "record size");
     HIP_OK(hipSetDevice(c->device));
@@ -787,7 +813,7 @@ int zr_get_kernel_times(zr_ctx* c, float* ms, int cap) {
 int zr_trace(zr_ctx* c, const zr_scene* s, const double* rays6, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel,
              uint32_t bounce, zr_hit* out) {
     if (!c || !s || (n && (!rays6 || !out))) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_trace");
+    if (int rc0 = scene_ready(c, s, "zr_trace", true)) return rc0;   // a scene of any context is accepted here, unlike everywhere else: kept as it has always been
     HIP_OK(hipSetDevice(c->device));
     DevBuf<double> d_rays; DevBuf<zr_hit> d_hits;
     std::vector<double> r(rays6, rays6 + n * 6);
@@ -806,8 +832,8 @@ int zr_trace(zr_ctx* c, const zr_scene* s, const double* rays6, size_t n, double
         if ((rc = ensure_stack_slabs(c, s))) return rc;
         if ((rc = pool.alloc(zr::stream_pool_bytes((uint32_t)n) + 65536))) return rc;
         HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), c->stream));
-        HIP_OK(zr::stream_trace(s->ds, d_rays.p, (uint32_t)n, seed, pixel, bounce, d_hits.p, pool.p, c->d_ctl.p, c->d_st_overflow.p, c->st_ovf_levels, c->st_blocks,
-                                c->d_ctr.p, s->leaf_level, c->stream));
+        const zr::StreamContext ctx{c->d_ctl.p, c->d_st_overflow.p, c->st_ovf_levels, c->st_blocks, c->d_ctr.p, &c->stream, 1, c->st_event, c->h_active};
+        HIP_OK(zr::stream_trace(s->ds, d_rays.p, (uint32_t)n, seed, pixel, bounce, d_hits.p, pool.p, ctx, s->leaf_level));
         HIP_OK(hipStreamSynchronize(c->stream));
         unsigned int capped = 0;
         HIP_OK(hipMemcpy(&capped, c->d_ctl.p + zr::CTL_CAPPED, sizeof capped, hipMemcpyDeviceToHost));
@@ -823,8 +849,7 @@ int zr_trace(zr_ctx* c, const zr_scene* s, const double* rays6, size_t n, double
 int zr_kat_scatter(zr_ctx* c, const zr_scene* s, const double* rays6, const zr_hit* recs, const uint64_t* keys, const uint64_t* first_draw,
                    size_t n, zr_scatter_out* out) {
     if (!c || !s || (n && (!rays6 || !recs || !keys || !out))) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_kat_scatter");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
+    if (int rc0 = scene_ready(c, s, "zr_kat_scatter")) return rc0;
     if (n == 0) return ZR_OK;
     HIP_OK(hipSetDevice(c->device));
     DevBuf<double> d_rays; DevBuf<zr_hit> d_recs; DevBuf<uint64_t> d_keys, d_first; DevBuf<zr_scatter_out> d_out;
@@ -840,8 +865,7 @@ int zr_kat_scatter(zr_ctx* c, const zr_scene* s, const double* rays6, const zr_h
 
 int zr_kat_texture(zr_ctx* c, const zr_scene* s, uint32_t texture_id, const double* uvp5, size_t n, double* out_rgb) {
     if (!c || !s || (n && (!uvp5 || !out_rgb))) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_kat_texture");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
+    if (int rc0 = scene_ready(c, s, "zr_kat_texture")) return rc0;
     if (texture_id >= s->textures.size()) return fail(ZR_E_INVALID, "texture id %u out of range", texture_id);
     if (n == 0) return ZR_OK;
     HIP_OK(hipSetDevice(c->device));
@@ -856,11 +880,9 @@ int zr_kat_texture(zr_ctx* c, const zr_scene* s, uint32_t texture_id, const doub
 
 int zr_kat_background(zr_ctx* c, const zr_scene* s, const zr_env* env, const double* dirs3, size_t n, double* out_rgb) {
     if (!c || !s || !env || (n && (!dirs3 || !out_rgb))) return fail(ZR_E_INVALID, "null argument");
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_kat_background");
-    if (s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
+    if (int rc0 = scene_ready(c, s, "zr_kat_background")) return rc0;
     zr::DEnv de; make_env(*env, de);
-    if (de.mode > ZR_ENV_SOLID_COLOR) return fail(ZR_E_INVALID, "unknown environment mode %u", de.mode);
-    if (de.mode == ZR_ENV_HDR_MAP && de.hdr_tex != ZR_NO_TEXTURE && de.hdr_tex >= s->textures.size()) return fail(ZR_E_INVALID, "environment texture id out of range");
+    if (int rc0 = check_env(de, s)) return rc0;
     if (n == 0) return ZR_OK;
     HIP_OK(hipSetDevice(c->device));
     DevBuf<double> d_in, d_out;

@@ -1140,14 +1140,14 @@ static void launch_extend(const DScene& sc, const StreamBuf& B, void* overflow, 
 // pool's EXTEND overlaps another's SHADE.  Measured on cfg3: K = 2 gains 1-3 % on a whole frame and 6 % on a rank's
 // 1/8 shard, K >= 3 loses (the stages are throughput-bound, co-running launches only stretch each other).
 // streams[0] is the caller's stream, the others are internal.
-hipError_t stream_render(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, void* pool, uint32_t P, uint32_t spp,
-                         uint32_t n_pix, const uint32_t* d_pixels, double* d_samples, unsigned int* d_ctl, void* d_overflow, uint32_t ovf_levels, int extend_blocks,
-                         double* out, unsigned long long* gctr, bool count, hipStream_t* streams, int n_pools, hipEvent_t ev, StreamTimer* timer,
-                         unsigned int* h_active, volatile const uint8_t* keep_going, int* rounds_out, int generic, int mode, void* d_kend, void* d_cls,
-                         double* out2, unsigned long long* d_cpart, StreamProgress* progress, void* drain_pool, uint32_t drain_slots, uint32_t unit_chunk) {
-    const uint32_t n_units = n_pix * spp;
+hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level) {
+    const StreamFrame& F = job.frame; const StreamContext& X = job.ctx; const StreamHooks& H = job.hooks;
+    const DCamera& cam = *F.cam; const DEnv& env = *F.env;
+    const uint32_t P = job.pool.P, unit_chunk = job.pool.unit_chunk, n_pix = F.n_pix;
+    const int mode = job.split.mode;
+    const uint32_t n_units = n_pix * F.spp;
     const size_t W = stream_ctl_words();
-    int K = n_pools < 1 ? 1 : (n_pools > ST_MAX_POOLS ? ST_MAX_POOLS : n_pools);
+    int K = X.n_pools < 1 ? 1 : (X.n_pools > ST_MAX_POOLS ? ST_MAX_POOLS : X.n_pools);
     while (K > 1 && P / K < 64u * 1024u) K--;
     // affine hand-out (st_unit_of): a slot's shard is (slot / 256) % ST_SHARDS counted over ALL sub-pools, and the SHADE block that
     // serves it must agree (blockIdx % ST_SHARDS inside its sub-pool): pool and sub-pools are whole rounds of ST_SHARDS blocks
@@ -1156,90 +1156,84 @@ hipError_t stream_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
     while (K > 1 && P / K < pool_round) K--;
     StreamBuf Q[ST_MAX_POOLS];
     void* ov[ST_MAX_POOLS];
-    unsigned int* uctl = d_ctl + (size_t)ST_MAX_POOLS * W;
-    const unsigned int* h_units = h_active + (size_t)ST_MAX_POOLS * W;   // the host's copy of it
+    unsigned int* uctl = X.ctl + (size_t)ST_MAX_POOLS * W;
+    const unsigned int* h_units = X.h_active + (size_t)ST_MAX_POOLS * W;   // the host's copy of it
     {
         uint32_t first = 0;
-        unsigned char* base = (unsigned char*)pool;
+        unsigned char* base = (unsigned char*)job.pool.slots;
         for (int k = 0; k < K; k++) {
             uint32_t Pk = k == K - 1 ? P - first : (P / K + pool_round - 1) / pool_round * pool_round;
-            Q[k] = make_buf(base, Pk, spp, n_units, n_pix, d_pixels, d_samples, d_ctl + (size_t)k * W, uctl, first, P);
+            Q[k] = make_buf(base, Pk, F.spp, n_units, n_pix, F.pixels, F.samples, X.ctl + (size_t)k * W, uctl, first, P);
             Q[k].unit_chunk = unit_chunk; Q[k].shard_k0 = unit_chunk ? P / ST_SHARDS : 0u;
-            Q[k].kend = (uint2*)d_kend; Q[k].cls = (unsigned char*)d_cls;
-            Q[k].cpart = d_cpart ? d_cpart + ((size_t)first / 256 + (size_t)k) * 4 : nullptr;
-            ov[k] = (unsigned char*)d_overflow + (size_t)k * stream_overflow_bytes(extend_blocks, ovf_levels);
+            Q[k].kend = (uint2*)job.split.kend; Q[k].cls = (unsigned char*)job.split.cls;
+            Q[k].cpart = job.split.cpart ? job.split.cpart + ((size_t)first / 256 + (size_t)k) * 4 : nullptr;
+            ov[k] = (unsigned char*)X.overflow + (size_t)k * stream_overflow_bytes(X.extend_blocks, X.ovf_levels);
             base += stream_pool_bytes(Pk);
             first += Pk;
         }
     }
     hipError_t e;
-    hipStream_t stream = streams[0];
-    if ((e = hipMemsetAsync(d_ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
+    hipStream_t stream = X.streams[0];
+    if ((e = hipMemsetAsync(X.ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
     const size_t cpart_blocks = (size_t)P / 256 + ST_MAX_POOLS + 1;
-    if (d_cpart && (e = hipMemsetAsync(d_cpart, 0, cpart_blocks * 4 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
+    if (job.split.cpart && (e = hipMemsetAsync(job.split.cpart, 0, cpart_blocks * 4 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
     auto init = [&](const StreamBuf& B, hipStream_t st) {
-        if (timer) timer->begin(st, 0);
-        if (count) hipLaunchKernelGGL(stream_init<true>, dim3((B.P + 255) / 256), dim3(256), 0, st, B, cam, seed, gctr);
-        else hipLaunchKernelGGL(stream_init<false>, dim3((B.P + 255) / 256), dim3(256), 0, st, B, cam, seed, gctr);
-        if (timer) timer->end(st, 0);
+        if (H.timer) H.timer->begin(st, 0);
+        if (F.count) hipLaunchKernelGGL(stream_init<true>, dim3((B.P + 255) / 256), dim3(256), 0, st, B, cam, F.seed, X.gctr);
+        else hipLaunchKernelGGL(stream_init<false>, dim3((B.P + 255) / 256), dim3(256), 0, st, B, cam, F.seed, X.gctr);
+        if (H.timer) H.timer->end(st, 0);
     };
     auto extend = [&](const StreamBuf& B, void* o, hipStream_t st) {
-        const int eb = (int)((B.P + 63) / 64 < (uint32_t)extend_blocks ? (B.P + 63) / 64 : (uint32_t)extend_blocks);
-        if (timer) timer->begin(st, 1);
-        if (count) launch_extend<true>(sc, B, o, ovf_levels, eb, gctr, generic, st); else launch_extend<false>(sc, B, o, ovf_levels, eb, gctr, generic, st);
-        if (timer) timer->end(st, 1);
+        const int eb = (int)((B.P + 63) / 64 < (uint32_t)X.extend_blocks ? (B.P + 63) / 64 : (uint32_t)X.extend_blocks);
+        if (H.timer) H.timer->begin(st, 1);
+        if (F.count) launch_extend<true>(sc, B, o, X.ovf_levels, eb, X.gctr, leaf_level, st); else launch_extend<false>(sc, B, o, X.ovf_levels, eb, X.gctr, leaf_level, st);
+        if (H.timer) H.timer->end(st, 1);
     };
     // development aid: ZR_SHADE_LDS_PAD bytes of dynamic LDS per SHADE block lower the blocks a CU can hold (160 KB: 4 fit by registers; > 40 KB: 3, > 53 KB: 2)
     static const unsigned shade_pad = std::getenv("ZR_SHADE_LDS_PAD") ? (unsigned)std::atoi(std::getenv("ZR_SHADE_LDS_PAD")) : 0u;
     auto shade = [&](const StreamBuf& B, hipStream_t st) {
-        if (timer) timer->begin(st, 2);
+        if (H.timer) H.timer->begin(st, 2);
         const dim3 sg((B.P + 255) / 256), sb(256);
         if (sc.shade_lean && mode == 0) {   // the lean build: same arithmetic, fewer registers, 6 waves per SIMD instead of 4 (see lean_rec, zr_device.h)
-            if (count) hipLaunchKernelGGL((stream_shade<true, 0, true>), sg, sb, 0, st, sc, cam, env, seed, B, gctr);
-            else hipLaunchKernelGGL((stream_shade<false, 0, true>), sg, sb, shade_pad, st, sc, cam, env, seed, B, gctr);
-            if (timer) timer->end(st, 2);
-            return;
+            if (F.count) hipLaunchKernelGGL((stream_shade<true, 0, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+            else hipLaunchKernelGGL((stream_shade<false, 0, true>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
         }
-        if (shade_pad && mode == 0 && !count) {
-            hipLaunchKernelGGL((stream_shade<false, 0>), sg, sb, shade_pad, st, sc, cam, env, seed, B, gctr);
-            if (timer) timer->end(st, 2);
-            return;
-        }
-        if (mode == 1) hipLaunchKernelGGL((stream_shade<true, 1>), sg, sb, 0, st, sc, cam, env, seed, B, gctr);        // the split passes always count
-        else if (mode == 2) hipLaunchKernelGGL((stream_shade<true, 2>), sg, sb, 0, st, sc, cam, env, seed, B, gctr);
-        else if (count) hipLaunchKernelGGL((stream_shade<true, 0>), sg, sb, 0, st, sc, cam, env, seed, B, gctr);
-        else hipLaunchKernelGGL((stream_shade<false, 0>), sg, sb, 0, st, sc, cam, env, seed, B, gctr);
-        if (timer) timer->end(st, 2);
+        else if (shade_pad && mode == 0 && !F.count) hipLaunchKernelGGL((stream_shade<false, 0>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
+        else if (mode == 1) hipLaunchKernelGGL((stream_shade<true, 1>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);        // the split passes always count
+        else if (mode == 2) hipLaunchKernelGGL((stream_shade<true, 2>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+        else if (F.count) hipLaunchKernelGGL((stream_shade<true, 0>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+        else hipLaunchKernelGGL((stream_shade<false, 0>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+        if (H.timer) H.timer->end(st, 2);
     };
     // start-up: pool k is initialised after the control words are cleared and starts once pool k-1 has a round in flight
     init(Q[0], stream);
     for (int k = 1; k < K; k++) {
-        extend(Q[k - 1], ov[k - 1], streams[k - 1]);
-        if ((e = hipEventRecord(ev, streams[k - 1])) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(streams[k], ev, 0)) != hipSuccess) return e;
-        init(Q[k], streams[k]);
-        shade(Q[k - 1], streams[k - 1]);
+        extend(Q[k - 1], ov[k - 1], X.streams[k - 1]);
+        if ((e = hipEventRecord(X.event, X.streams[k - 1])) != hipSuccess) return e;
+        if ((e = hipStreamWaitEvent(X.streams[k], X.event, 0)) != hipSuccess) return e;
+        init(Q[k], X.streams[k]);
+        shade(Q[k - 1], X.streams[k - 1]);
     }
     int rounds = K > 1 ? 1 : 0;
-    int check_every = progress ? 2 : 8;
+    int check_every = H.progress ? 2 : 8;
     bool cancelled = false, drained = false, capped = false;
     for (;;) {
         for (int r = 0; r < check_every; r++) {
-            for (int k = K - 1; k >= 0; k--) { extend(Q[k], ov[k], streams[k]); shade(Q[k], streams[k]); }
+            for (int k = K - 1; k >= 0; k--) { extend(Q[k], ov[k], X.streams[k]); shade(Q[k], X.streams[k]); }
             rounds++;
         }
         for (int k = 0; k < K && e == hipSuccess; k++)
-            e = hipMemcpyAsync(h_active + (size_t)k * W, d_ctl + (size_t)k * W, W * sizeof(unsigned int), hipMemcpyDeviceToHost, streams[k]);
+            e = hipMemcpyAsync(X.h_active + (size_t)k * W, X.ctl + (size_t)k * W, W * sizeof(unsigned int), hipMemcpyDeviceToHost, X.streams[k]);
         if (e == hipSuccess)   // the work-unit counters: how many samples have been started
-            e = hipMemcpyAsync(h_active + (size_t)ST_MAX_POOLS * W, uctl, W * sizeof(unsigned int), hipMemcpyDeviceToHost, streams[0]);
-        for (int k = K - 1; k >= 0 && e == hipSuccess; k--) e = hipStreamSynchronize(streams[k]);
+            e = hipMemcpyAsync(X.h_active + (size_t)ST_MAX_POOLS * W, uctl, W * sizeof(unsigned int), hipMemcpyDeviceToHost, X.streams[0]);
+        for (int k = K - 1; k >= 0 && e == hipSuccess; k--) e = hipStreamSynchronize(X.streams[k]);
         if (e != hipSuccess) break;
         unsigned long long active = 0;
         for (int k = 0; k < K; k++) {
-            if (h_active[(size_t)k * W + CTL_CAPPED] != 0) capped = true;   // (looked at here, for every sub-pool: the drain below folds them into one)
-            for (int sh = 0; sh < ST_SHARDS; sh++) active += h_active[(size_t)k * W + CTL_SHARD0 + CTL_STRIDE * sh + CTL_SH_ACTIVE];
+            if (X.h_active[(size_t)k * W + CTL_CAPPED] != 0) capped = true;   // (looked at here, for every sub-pool: the drain below folds them into one)
+            for (int sh = 0; sh < ST_SHARDS; sh++) active += X.h_active[(size_t)k * W + CTL_SHARD0 + CTL_STRIDE * sh + CTL_SH_ACTIVE];
         }
-        if (progress && active != 0) {
+        if (H.progress && active != 0) {
             unsigned long long started = 0;   // the first P units are dealt at initialisation, the rest through the sharded counters
             if (!unit_chunk) { started = P; for (int sh = 0; sh < ST_SHARDS; sh++) started += h_units[CTL_STRIDE * sh + CTL_SH_UNITS]; }
             else for (int sh = 0; sh < ST_SHARDS; sh++) {   // affine: of a shard's sequence, the units that exist (a shard's last chunks may lie beyond the frame)
@@ -1254,22 +1248,22 @@ hipError_t stream_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
             if (started > n_units) started = n_units;
             const double frac = started > active ? (double)(started - active) / (double)n_units : 0.0;
             bool reduced = false;
-            if (mode == 0 && out && progress->wants_frame()) {   // samples[] is zero-initialised in this case (render_stream)
-                hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, Q[0], cam, out);
+            if (mode == 0 && F.out && H.progress->wants_frame()) {   // samples[] is zero-initialised in this case (render_stream)
+                hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, Q[0], cam, F.out);
                 if ((e = hipStreamSynchronize(stream)) != hipSuccess) break;
                 reduced = true;
             }
-            progress->report(frac, reduced);
+            H.progress->report(frac, reduced);
         }
         if (active == 0) break;
-        if (!drained && drain_pool && active * 16ull <= (unsigned long long)P && active <= (unsigned long long)drain_slots) {
+        if (!drained && job.pool.drain && active * 16ull <= (unsigned long long)P && active <= (unsigned long long)job.pool.drain_slots) {
             bool units_left = false;   // shard sh has handed out every k below its counter: unit_base + k * shards + sh
             for (int sh = 0; sh < ST_SHARDS && !units_left; sh++)
                 if (st_unit_of(unit_chunk, P, (uint32_t)sh, (unsigned long long)(unit_chunk ? P / ST_SHARDS : 0u) + h_units[CTL_STRIDE * sh + CTL_SH_UNITS]) < (unsigned long long)n_units) units_left = true;
             if (!units_left) {   // see stream_compact
                 StreamBuf D = Q[0];
-                D.pool = (double*)drain_pool; D.P = (uint32_t)((active + 255ull) / 256ull * 256ull); D.unit0 = 0;
-                unsigned int* counter = d_ctl + CTL_COMPACT;   // (of pool 0)
+                D.pool = (double*)job.pool.drain; D.P = (uint32_t)((active + 255ull) / 256ull * 256ull); D.unit0 = 0;
+                unsigned int* counter = X.ctl + CTL_COMPACT;   // (of pool 0)
                 for (int k = 0; k < K; k++) hipLaunchKernelGGL(stream_compact, dim3((Q[k].P + 255) / 256), dim3(256), 0, stream, Q[k], D, counter);
                 if (D.P > (uint32_t)active) hipLaunchKernelGGL(stream_compact_pad, dim3((D.P - (uint32_t)active + 255) / 256), dim3(256), 0, stream, D, (uint32_t)active);
                 if ((e = hipStreamSynchronize(stream)) != hipSuccess) break;
@@ -1277,19 +1271,19 @@ hipError_t stream_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
             }
         }
         check_every = active > P / 2 ? 8 : (active > P / 16 ? 4 : 2);
-        if (progress && check_every > 2) check_every = 2;   // an interactive caller: report (and poll keep_going) every other round
-        if (keep_going && *keep_going == 0) { cancelled = true; break; }
+        if (H.progress && check_every > 2) check_every = 2;   // an interactive caller: report (and poll keep_going) every other round
+        if (H.keep_going && *H.keep_going == 0) { cancelled = true; break; }
         if (rounds > (1 << 22)) { e = hipErrorLaunchFailure; break; }
     }
     if (e != hipSuccess) return e;
     if (capped) return hipErrorLaunchFailure;  // an EXTEND wave of some sub-pool hit its iteration cap: its rays were abandoned mid-walk
     const StreamBuf& A = Q[0];
-    if (timer) timer->begin(stream, 3);
-    if (d_cpart) hipLaunchKernelGGL(stream_sum_counters, dim3(1), dim3(256), 0, stream, d_cpart, cpart_blocks, gctr);
-    if (mode == 2) hipLaunchKernelGGL(stream_reduce_split, dim3((n_pix + 3) / 4), dim3(256), 0, stream, A, cam, out, out2);
-    else if (out) hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, A, cam, out);
-    if (timer) timer->end(stream, 3);
-    if (rounds_out) *rounds_out = cancelled ? -rounds : rounds;
+    if (H.timer) H.timer->begin(stream, 3);
+    if (job.split.cpart) hipLaunchKernelGGL(stream_sum_counters, dim3(1), dim3(256), 0, stream, job.split.cpart, cpart_blocks, X.gctr);
+    if (mode == 2) hipLaunchKernelGGL(stream_reduce_split, dim3((n_pix + 3) / 4), dim3(256), 0, stream, A, cam, F.out, F.out2);
+    else if (F.out) hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, A, cam, F.out);
+    if (H.timer) H.timer->end(stream, 3);
+    if (H.done_out) *H.done_out = cancelled ? -rounds : rounds;
     return hipGetLastError();
 }
 
@@ -1301,67 +1295,67 @@ int fused_blocks() {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_render<2, false>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
     return cus * per_cu;
 }
-hipError_t fused_render_frame(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, uint32_t spp, uint32_t n_pix, const uint32_t* d_pixels, double* d_samples,
-                              unsigned int* d_ctl, int blocks, double* out, unsigned long long* gctr, bool count, int level, hipStream_t stream, StreamTimer* timer,
-                              const FusedObjs& fo, volatile const uint8_t* keep_going, StreamProgress* progress, int* parts_done) {
-    const uint32_t n_units = n_pix * spp;
+hipError_t fused_render_frame(const DScene& sc, const StreamFrame& F, const StreamContext& X, int blocks, int level, const FusedObjs& fo, const StreamHooks& H) {
+    const DCamera& cam = *F.cam; const DEnv& env = *F.env;
+    hipStream_t stream = X.streams[0];
+    const uint32_t n_units = F.n_pix * F.spp;
     const size_t W = stream_ctl_words();
     hipError_t e;
-    FusedBuf B; B.pixels = d_pixels; B.samples = d_samples; B.uctl = d_ctl + (size_t)ST_MAX_POOLS * W; B.spp = spp; B.n_units = n_units;
+    FusedBuf B; B.pixels = F.pixels; B.samples = F.samples; B.uctl = X.ctl + (size_t)ST_MAX_POOLS * W; B.spp = F.spp; B.n_units = n_units;
     const unsigned long long n_chunks = ((unsigned long long)n_units + ST_FUSED_CHUNK - 1) / ST_FUSED_CHUNK;
     // one launch for the whole frame — or, for a caller that polls (render_flag, lines_rendered, the live preview of camera.hpp:548-552 /
     // main.cpp:1576), sixteen launches over consecutive parts of the unit range with the poll between them (samples[] was zeroed, so the
     // reduce of a partial frame is the mean of the samples finished so far, as in the pipeline)
-    const int parts = (keep_going || progress) && n_chunks >= 64 ? 16 : 1;
-    StreamBuf R = make_buf(nullptr, 0, spp, n_units, n_pix, d_pixels, d_samples, d_ctl, d_ctl, 0, 0);
+    const int parts = (H.keep_going || H.progress) && n_chunks >= 64 ? 16 : 1;
+    StreamBuf R = make_buf(nullptr, 0, F.spp, n_units, F.n_pix, F.pixels, F.samples, X.ctl, X.ctl, 0, 0);
     bool cancelled = false;
     int done = 0;
     for (int p = 0; p < parts && !cancelled; p++) {
         B.chunk_lo = (uint32_t)(n_chunks * (unsigned long long)p / (unsigned long long)parts);
         B.chunk_hi = (uint32_t)(n_chunks * (unsigned long long)(p + 1) / (unsigned long long)parts);
         if (B.chunk_hi == B.chunk_lo) continue;
-        if ((e = hipMemsetAsync(d_ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(X.ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
         const unsigned long long want_blocks = ((unsigned long long)(B.chunk_hi - B.chunk_lo) + 3) / 4;   // no more waves than chunks
         const dim3 grid((unsigned)(want_blocks < (unsigned long long)blocks ? (want_blocks ? want_blocks : 1) : blocks)), block(256);
-        if (timer) timer->begin(stream, 1);
-        if (level <= 1) { if (count) hipLaunchKernelGGL((fused_render<1, true>), grid, block, 0, stream, sc, cam, env, seed, B, gctr, fo); else hipLaunchKernelGGL((fused_render<1, false>), grid, block, 0, stream, sc, cam, env, seed, B, gctr, fo); }
-        else { if (count) hipLaunchKernelGGL((fused_render<2, true>), grid, block, 0, stream, sc, cam, env, seed, B, gctr, fo); else hipLaunchKernelGGL((fused_render<2, false>), grid, block, 0, stream, sc, cam, env, seed, B, gctr, fo); }
-        if (timer) timer->end(stream, 1);
+        if (H.timer) H.timer->begin(stream, 1);
+        if (level <= 1) { if (F.count) hipLaunchKernelGGL((fused_render<1, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<1, false>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
+        else { if (F.count) hipLaunchKernelGGL((fused_render<2, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<2, false>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
+        if (H.timer) H.timer->end(stream, 1);
         done = p + 1;
         if (parts > 1 && p + 1 < parts) {
             if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-            if (progress) {
+            if (H.progress) {
                 bool reduced = false;
-                if (out && progress->wants_frame()) {
-                    hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, R, cam, out);
+                if (F.out && H.progress->wants_frame()) {
+                    hipLaunchKernelGGL(stream_reduce, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, R, cam, F.out);
                     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
                     reduced = true;
                 }
-                progress->report((double)(p + 1) / parts, reduced);
+                H.progress->report((double)(p + 1) / parts, reduced);
             }
-            if (keep_going && *keep_going == 0) cancelled = true;
+            if (H.keep_going && *H.keep_going == 0) cancelled = true;
         }
     }
-    if (timer) timer->begin(stream, 3);
-    if (out) hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, R, cam, out);
-    if (timer) timer->end(stream, 3);
-    if (parts_done) *parts_done = cancelled ? -done : done;
+    if (H.timer) H.timer->begin(stream, 3);
+    if (F.out) hipLaunchKernelGGL(stream_reduce, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, R, cam, F.out);
+    if (H.timer) H.timer->end(stream, 3);
+    if (H.done_out) *H.done_out = cancelled ? -done : done;
     return hipGetLastError();
 }
 
 // closest hits of n rays in [0.001, inf) through the EXTEND kernel; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes
-hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out,
-                        void* pool, unsigned int* d_ctl, void* d_overflow, uint32_t ovf_levels, int extend_blocks, unsigned long long* gctr, int generic,
-                        hipStream_t stream) {
+hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, void* pool,
+                        const StreamContext& X, int leaf_level) {
+    hipStream_t stream = X.streams[0];
     if (n == 0) return hipSuccess;
     const uint32_t P = (n + 63u) / 64u * 64u;
     const size_t W = stream_ctl_words();
-    StreamBuf B = make_buf(pool, P, 1, n, n, nullptr, nullptr, d_ctl, d_ctl + (size_t)ST_MAX_POOLS * W, 0, P);
+    StreamBuf B = make_buf(pool, P, 1, n, n, nullptr, nullptr, X.ctl, X.ctl + (size_t)ST_MAX_POOLS * W, 0, P);
     hipError_t e;
-    if ((e = hipMemsetAsync(d_ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(X.ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(stream_load_rays, dim3((P + 255) / 256), dim3(256), 0, stream, B, d_rays, n, seed, pixel, bounce);
-    const int eb = (int)(P / 64 < (uint32_t)extend_blocks ? P / 64 : (uint32_t)extend_blocks);
-    launch_extend<false>(sc, B, d_overflow, ovf_levels, eb, gctr, generic, stream);
+    const int eb = (int)(P / 64 < (uint32_t)X.extend_blocks ? P / 64 : (uint32_t)X.extend_blocks);
+    launch_extend<false>(sc, B, X.overflow, X.ovf_levels, eb, X.gctr, leaf_level, stream);
     hipLaunchKernelGGL(stream_hits_out, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out);
     return hipGetLastError();
 }
