@@ -1406,6 +1406,11 @@ public:
     std::atomic<int> lines_rendered{0};
     uint64_t seed = 0x5EED0000ull;  // extension: the reference cannot be seeded (common.hpp:30-31)
     int device = 0;                 // extension: HIP device ordinal
+    // extension: > 0 renders the frame progressively, this many samples per pass (zr_render_accumulate).  After every pass render_accumulator holds the exact
+    // image of the samples done so far, current_samples_count says how many that is, and render_flag is looked at: a cancelled render leaves the
+    // current_samples_count-spp image.  The finished frame equals the one-shot frame bit for bit.  0: exactly the one-shot render.
+    int samples_per_pass = 0;
+    int passes_rendered = 0;        // extension: passes of the last progressive render that reached render_accumulator
     zr_counters last_counters{};
 
     void reset_accumulator() {  // camera.hpp:209-233
@@ -1492,6 +1497,24 @@ public:
                                          reinterpret_cast<volatile const uint8_t*>(&render_flag), reinterpret_cast<volatile int*>(&lines_rendered));
                 ph("zr_render_bvh_debug");
             } else {
+            if (samples_per_pass > 0) {
+                // progressive (the reference's "real-time sample accumulation"): passes of samples_per_pass samples into a device accumulator
+                const int spp = samples_per_pixel < 1 ? 1 : samples_per_pixel;
+                current_samples_count = 0; passes_rendered = 0;
+                zr_accum* acc = zr_accum_create(ctx, image_width, image_height, nullptr);
+                rc = acc ? ZR_OK : ZR_E_DEVICE;
+                while (rc == ZR_OK && current_samples_count < spp) {
+                    const int n = std::min(samples_per_pass, spp - current_samples_count);
+                    rc = zr_render_accumulate(ctx, sc, &zc, &zenv, seed, acc, n, 0, reinterpret_cast<volatile const uint8_t*>(&render_flag));
+                    if (rc != ZR_OK) break;   // (a cancelled pass is discarded whole: the image stays the one of the passes before it)
+                    rc = zr_accum_resolve(acc, reinterpret_cast<double*>(render_accumulator.data()));
+                    if (rc != ZR_OK) break;
+                    current_samples_count += n; passes_rendered++;
+                    lines_rendered = current_samples_count < spp ? (int)((long long)image_height * current_samples_count / spp) : image_height;
+                    if (current_samples_count < spp && !render_flag.load()) { rc = ZR_E_CANCELLED; break; }
+                }
+                if (acc) zr_accum_destroy(acc);
+            } else
             rc = zr_render(ctx, sc, &zc, &zenv, seed, nullptr, 0, reinterpret_cast<double*>(render_accumulator.data()),
                            reinterpret_cast<volatile const uint8_t*>(&render_flag), reinterpret_cast<volatile int*>(&lines_rendered));
             zr_get_counters(ctx, &last_counters);

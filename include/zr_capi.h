@@ -291,6 +291,37 @@ int zr_render(zr_ctx*, const zr_scene*, const zr_camera*, const zr_env*, uint64_
 int zr_render_device(zr_ctx*, const zr_scene*, const zr_camera*, const zr_env*, uint64_t seed,
                      const zr_region* region, int collect_counters,
                      void* d_out_rgb, void* hip_stream);
+
+/* ---- progressive accumulation: a frame rendered in batches of samples (camera::current_samples_count) --------------------
+ * A zr_accum is device memory that carries a frame from one batch of samples to the next: for every pixel of the plan of
+ * (width, height, region) — the region's pixels, not the frame's — 64 lane sums x 3 doubles (1536 bytes per pixel) and the
+ * sample range [first, first + done) they hold.  Sample s of a pixel always belongs to lane s % 64 and a lane adds its samples
+ * in increasing s: that is the order zr_render's reduce uses, so ANY split of [0, N) into consecutive batches resolves to the
+ * image zr_render gives at samples_per_pixel = N, bit for bit, and every prefix [0, k) is the k-spp image.  (A sum of batch
+ * means would differ in the last bits.)
+ *   zr_accum_create       NULL (zr_last_error says why) for a bad size or region; the partials start at zero, first = 0
+ *   zr_accum_reset        zeroes the partials; the next batch starts at first_sample >= 0; forgets the camera / seed / scene
+ *   zr_render_accumulate  renders the samples [first + done, first + done + n_samples) of every pixel of the accumulator's plan
+ *                         and adds them.  camera.samples_per_pixel is ignored.  Takes the route zr_render would (pipeline, fused
+ *                         kernel, pixel-group kernel); a batch must fit its route in one run (ZR_E_NOMEM otherwise: ask for fewer
+ *                         samples).  ZR_E_INVALID: n_samples < 1, a camera of another size, or — after the first batch since
+ *                         create / reset — a camera, seed or scene that differs from that batch's.  A cancelled batch
+ *                         (*keep_going == 0) is discarded whole: ZR_E_CANCELLED, accumulator unchanged.  zr_get_counters
+ *                         afterwards reports this batch.
+ *   zr_accum_resolve      out_rgb (host, W*H*3 doubles) / d_out_rgb (device, on `hip_stream`, complete on return) receive the mean
+ *                         of the `done` samples in the plan's pixels; other pixels are untouched.  ZR_E_STATE while done == 0.
+ *                         Leaves the partials alone: callable after every batch.
+ *   zr_accum_state        out = first, done, pixels, device bytes held */
+typedef struct zr_accum zr_accum;
+zr_accum* zr_accum_create(zr_ctx*, int width, int height, const zr_region* region);
+void zr_accum_destroy(zr_accum*);
+int zr_accum_reset(zr_accum*, int first_sample);
+int zr_render_accumulate(zr_ctx*, const zr_scene*, const zr_camera*, const zr_env*, uint64_t seed, zr_accum*, int n_samples,
+                         int collect_counters, volatile const uint8_t* keep_going);
+int zr_accum_resolve(zr_accum*, double* out_rgb);
+int zr_accum_resolve_device(zr_accum*, void* d_out_rgb, void* hip_stream);
+int zr_accum_state(const zr_accum*, int64_t out[4]);
+
 /* ---- first-hit AOV passes: the albedo / normal / z-depth part of render_rows (camera.hpp:433, 464-488, 521-541) ---- */
 /* For the first min(clamp(spp / 8, 64, 1024), spp) samples of every pixel the primary hit contributes
  *   albedo  += rec.mat->get_albedo(rec)                       (material.hpp:29-31,99-102,154-156,226-229,266-275)

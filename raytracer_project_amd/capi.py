@@ -197,7 +197,9 @@ CAPI_SYMBOLS = [
     "zr_abi_version", "zr_last_error", "zr_create", "zr_destroy", "zr_scene_create", "zr_scene_destroy",
     "zr_scene_set_spheres", "zr_scene_set_triangles", "zr_scene_set_cubes", "zr_scene_set_media",
     "zr_scene_set_xform_ops", "zr_scene_set_objects", "zr_scene_set_groups", "zr_scene_set_materials", "zr_scene_set_textures",
-    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_kernels", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device", "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
+    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_kernels", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device",
+    "zr_accum_create", "zr_accum_destroy", "zr_accum_reset", "zr_render_accumulate", "zr_accum_resolve", "zr_accum_resolve_device", "zr_accum_state",
+    "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
@@ -236,6 +238,13 @@ def load():
     lib.zr_scene_builder.argtypes = [vp]; lib.zr_scene_builder.restype = C.c_char_p
     lib.zr_render.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), i32, vp, vp, vp]
     lib.zr_render_device.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), i32, vp, vp]
+    lib.zr_accum_create.restype = vp; lib.zr_accum_create.argtypes = [vp, i32, i32, C.POINTER(Region)]
+    lib.zr_accum_destroy.argtypes = [vp]; lib.zr_accum_destroy.restype = None
+    lib.zr_accum_reset.argtypes = [vp, i32]
+    lib.zr_render_accumulate.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, vp, i32, i32, vp]
+    lib.zr_accum_resolve.argtypes = [vp, vp]
+    lib.zr_accum_resolve_device.argtypes = [vp, vp, vp]
+    lib.zr_accum_state.argtypes = [vp, C.POINTER(C.c_int64 * 4)]
     lib.zr_render_aov.argtypes = [vp, vp, C.POINTER(Camera), u64, C.POINTER(Region), C.POINTER(AovParams), vp, vp, vp]
     lib.zr_post_process.argtypes = [vp, C.POINTER(PostParams), vp, i32, i32, i32, i32, vp]
     lib.zr_analyze_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(ImageStats)]
@@ -322,6 +331,19 @@ class DemoScene:
         if rc != 0:
             raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
         return out, ctr
+
+    def render_dropin_progressive(self, samples_per_pass, width=0, height=0, spp=0, device=0):
+        """camera::render with camera::samples_per_pass set: (frame, current_samples_count afterwards, refreshes of render_accumulator).
+        current_samples_count is -7 going in, so a render that does not touch it (samples_per_pass = 0) reports -7."""
+        w = width or self.camera.image_width
+        h = height or self.camera.image_height
+        out = np.zeros((h, w, 3), dtype=np.float64)
+        info = (C.c_int * 2)()
+        lib = load_scenes()
+        lib.zrs_render_dropin_progressive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        if lib.zrs_render_dropin_progressive(self._h, width, height, spp, device, int(samples_per_pass), out.ctypes.data, info) != 0:
+            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        return out, int(info[0]), int(info[1])
 
     def render_dropin_threads(self, n, width=0, height=0, spp=0, device=0):
         """n drop-in renders, each on a fresh host thread, one after the other (the reference's render-restart pattern,
@@ -478,6 +500,53 @@ class Context:
         if n < 0:
             _check(n)
         return [buf[i] for i in range(min(n, cap))]
+
+
+class Accumulator:
+    """A frame rendered in batches of samples (zr_accum): device-resident lane sums for the pixels of `region` of a width x height frame.
+    Any split of [0, N) into consecutive batches resolves to Scene.render's frame at N samples per pixel, bit for bit."""
+
+    def __init__(self, ctx, width, height, region=None):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.width, self.height = int(width), int(height)
+        self._a = self.lib.zr_accum_create(ctx._c, self.width, self.height, C.byref(region) if region is not None else None)
+        if not self._a:
+            raise ZrError(self.lib.zr_last_error().decode())
+
+    def accumulate(self, scene, camera, env, seed, n_samples, count=False, keep_going=None):
+        """renders the next n_samples samples of every pixel and adds them (camera.samples_per_pixel is ignored); keep_going: a
+        ctypes.c_uint8 polled like zr_render's — a cancelled batch raises nothing, returns ZR_E_CANCELLED and leaves the accumulator as it was"""
+        kg = C.cast(C.byref(keep_going), C.c_void_p) if keep_going is not None else None
+        return _check(self.lib.zr_render_accumulate(self.ctx._c, scene._s, C.byref(camera), C.byref(env), C.c_uint64(seed), self._a, int(n_samples),
+                                                    1 if count else 0, kg), allow_cancel=True)
+
+    def resolve(self, out=None):
+        """the mean of the samples accumulated so far: (H, W, 3) float64; only the region's pixels of `out` are written"""
+        if out is None:
+            out = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.height, self.width, 3)
+        _check(self.lib.zr_accum_resolve(self._a, out.ctypes.data))
+        return out
+
+    def reset(self, first_sample=0):
+        _check(self.lib.zr_accum_reset(self._a, int(first_sample)))
+
+    def state(self):
+        out = (C.c_int64 * 4)()
+        _check(self.lib.zr_accum_state(self._a, C.byref(out)))
+        return {"first": out[0], "done": out[1], "pixels": out[2], "device_bytes": out[3]}
+
+    def close(self):
+        if self._a:
+            self.lib.zr_accum_destroy(self._a)
+            self._a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Scene:

@@ -161,6 +161,38 @@ __global__ __launch_bounds__(ZR_BLOCK) void render_pixels(DScene sc, DCamera cam
     }
 }
 
+// One batch of a progressive render on the pixel-group route (zr_render_accumulate): sample_radiance for the samples [sample0, sample0 + n) of the listed
+// pixels (x | y << 16), one thread per sample, written as per-sample radiance [n_pix][n][3] — what the streaming pipeline leaves in samples[], so that the
+// one accumulate kernel (zr_stream.hip: stream_accumulate) serves every route.  A sample's arithmetic is render_pixels' (same stream key, same walk).
+template <bool COUNT>
+__global__ __launch_bounds__(ZR_BLOCK) void render_pixel_samples(DScene sc, DCamera cam, DEnv env, uint64_t seed, const uint32_t* __restrict__ pixels, uint32_t n_pix,
+                                                                  uint32_t sample0, uint32_t n, double* __restrict__ samples, unsigned long long* __restrict__ gctr) {
+    __shared__ uint32_t lds_stack[ZR_STACK_DEPTH * ZR_BLOCK];
+    uint32_t* stack = lds_stack + threadIdx.x;
+    const unsigned long long k = (unsigned long long)blockIdx.x * ZR_BLOCK + threadIdx.x;
+    if (k >= (unsigned long long)n_pix * n) return;
+    const uint32_t i = (uint32_t)(k / n), sidx = (uint32_t)(k - (unsigned long long)i * n);
+    const uint32_t pk = pixels[i];
+    const int px = (int)(pk & 0xFFFFu), py = (int)(pk >> 16);
+    Counters ctr = {0, 0, 0, 0, 0};
+    uint32_t segments = 0, hits = 0;
+    Rng g; g.key = zr_stream_key(seed, (uint64_t)py * (uint64_t)cam.W + (uint64_t)px, (uint64_t)sample0 + sidx); g.k = 0; g.bounce = 0;
+    const V3 c = sample_radiance<COUNT>(sc, cam, env, px, py, g, stack, ZR_BLOCK, ctr, segments, hits);
+    double* o = samples + k * 3;
+    o[0] = c.x; o[1] = c.y; o[2] = c.z;
+    if (COUNT) {
+        atomicAdd(&gctr[CTR_SAMPLES], 1ull);
+        atomicAdd(&gctr[CTR_SEGMENTS], (unsigned long long)segments);
+        atomicAdd(&gctr[CTR_NODES], (unsigned long long)ctr.nodes);
+        atomicAdd(&gctr[CTR_SPHERES], (unsigned long long)ctr.sph);
+        atomicAdd(&gctr[CTR_TRIANGLES], (unsigned long long)ctr.tri);
+        atomicAdd(&gctr[CTR_CUBES], (unsigned long long)ctr.cube);
+        atomicAdd(&gctr[CTR_MEDIA], (unsigned long long)ctr.med);
+        atomicAdd(&gctr[CTR_HITS], (unsigned long long)hits);
+        atomicAdd(&gctr[CTR_DRAWS], (unsigned long long)g.k);
+    }
+}
+
 // beauty + reflection + refraction frames (use_reflection / use_refraction on): same pixel-group layout as render_pixels
 __global__ __launch_bounds__(ZR_BLOCK) void passes_pixels(DScene sc, DCamera cam, DEnv env, uint64_t seed, WorkDesc wd, double* __restrict__ out_beauty,
                                                            double* __restrict__ out_reflection, double* __restrict__ out_refraction,
@@ -405,6 +437,17 @@ hipError_t launch_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
     dim3 grid((unsigned)blocks), block(ZR_BLOCK);
     if (count) hipLaunchKernelGGL(render_pixels<true>, grid, block, 0, stream, sc, cam, env, seed, wd, out, gctr);
     else hipLaunchKernelGGL(render_pixels<false>, grid, block, 0, stream, sc, cam, env, seed, wd, out, gctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_render_samples(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const uint32_t* pixels, uint32_t n_pix, uint32_t sample0,
+                                 uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream) {
+    const unsigned long long blocks = ((unsigned long long)n_pix * n + ZR_BLOCK - 1) / ZR_BLOCK;
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    dim3 grid((unsigned)blocks), block(ZR_BLOCK);
+    if (count) hipLaunchKernelGGL(render_pixel_samples<true>, grid, block, 0, stream, sc, cam, env, seed, pixels, n_pix, sample0, n, samples, gctr);
+    else hipLaunchKernelGGL(render_pixel_samples<false>, grid, block, 0, stream, sc, cam, env, seed, pixels, n_pix, sample0, n, samples, gctr);
     return hipGetLastError();
 }
 

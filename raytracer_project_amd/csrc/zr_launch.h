@@ -69,6 +69,7 @@ struct StreamFrame {     // what is rendered: one work unit per primary sample o
     double* samples;     // per-sample radiance, 3 doubles per unit
     double *out, *out2;  // the frame the samples are reduced into (null: none wanted) and, in mode 2, the refraction frame
     bool count;          // the instrumented builds (zr_counters)
+    uint32_t sample0 = 0;   // the run renders samples [sample0, sample0 + spp) of every pixel (a batch of a progressive render; 0: the whole frame)
 };
 struct StreamPool {      // the frame's slot pool; the small pool the survivors of its drain are moved to (null: not used); chunk of the XCD-affine hand-out (0: striped)
     void* slots; uint32_t P; void* drain; uint32_t drain_slots, unit_chunk;
@@ -102,6 +103,16 @@ struct FusedObjs {
 int fused_blocks();
 // uses of `ctx`: ctl, gctr, streams[0].  level: 1 = no wrapped objects and only plain media, 2 = everything but placements
 hipError_t fused_render_frame(const DScene& sc, const StreamFrame& frame, const StreamContext& ctx, int blocks, int level, const FusedObjs& objs, const StreamHooks& hooks);
+// Progressive accumulation (zr_accum, zr_stream.hip): `partial` holds 64 lane sums x 3 channels per pixel ([pixel][channel][lane], 192 doubles).
+// launch_accumulate adds a batch of per-sample radiance ([n_pix][n][3], the samples sample0 ... sample0 + n - 1) to it: sample s goes to lane s % 64, in increasing s
+// (flip: the batch's pixel list ran in the reverse of the accumulator's order).  launch_accum_resolve writes the mean of the `done` samples held into
+// the listed pixels of `out` (frame width W); asc_lanes: 1 = stream_reduce's butterfly, L = lanes_for(done) the pixel-group kernel's.
+constexpr size_t ACCUM_DOUBLES_PER_PIXEL = 192;
+hipError_t launch_accumulate(const double* samples, uint32_t n_pix, uint32_t n, uint32_t sample0, bool flip, double* partial, hipStream_t stream);
+hipError_t launch_accum_resolve(const double* partial, const uint32_t* pixels, uint32_t n_pix, int W, int done, int asc_lanes, double* out, hipStream_t stream);
+// the pixel-group kernel's arithmetic for one batch: samples [sample0, sample0 + n) of the listed pixels, written as per-sample radiance ([n_pix][n][3]) for launch_accumulate
+hipError_t launch_render_samples(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const uint32_t* pixels, uint32_t n_pix, uint32_t sample0,
+                                 uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream);
 // closest hits of n rays in [0.001, inf) through the EXTEND kernel on ctx.streams[0]; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes
 hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, void* pool,
                         const StreamContext& ctx, int leaf_level);

@@ -163,6 +163,7 @@ int check_env(const zr::DEnv& de, const zr_scene* s) {
 struct FrameJob {
     Plan plan; zr::DCamera dc; zr::DEnv de{}; uint64_t seed = 0; hipStream_t stream = nullptr;
     bool count = false;                               // zr_counters wanted
+    uint32_t sample0 = 0;                             // a batch of a progressive render: dc.spp samples from this one on (render_stream; 0 = the whole frame)
     double* d_out = nullptr; double* d_out2 = nullptr;   // device frames (d_out2: the refraction frame of the split's replay pass)
     volatile const uint8_t* keep_going = nullptr; volatile int* rows_done = nullptr;
     zr::StreamProgress* progress = nullptr;
@@ -244,6 +245,17 @@ struct HostTimer : zr::StreamTimer {
 
 // ---- variant 2: the streaming wavefront pipeline (zr_stream.hip), in the steps of render_stream below -------------------------------------------------
 
+// the plan's pixels in tile order, x | y << 16 (ST_MAX_FRAME_SIDE)
+std::vector<uint32_t> plan_pixels(const Plan& plan) {
+    std::vector<uint32_t> pix;
+    pix.reserve((size_t)plan.tiles.size() * plan.ts * plan.ts);
+    for (int32_t t : plan.tiles) {
+        const TileRect r = plan.clip(t);
+        for (int y = r.ya; y < r.yb; y++) for (int x = r.xa; x < r.xb; x++) pix.push_back((uint32_t)x | ((uint32_t)y << 16));
+    }
+    return pix;
+}
+
 // the plan's pixels as the pipeline's pixel list, uploaded when the plan differs from the cached list's
 int upload_pixel_list(zr_ctx* c, const Plan& plan) {
     // Work units are handed out in pixel-list order, and when they run out the frame DRAINS: the paths still alive need up to
@@ -256,12 +268,7 @@ int upload_pixel_list(zr_ctx* c, const Plan& plan) {
                                 plan.tiles.empty() ? -1 : plan.tiles.front(), plan.tiles.empty() ? -1 : plan.tiles.back(),
                                 (int32_t)bottom_up};
     if (key == c->pix_key && c->d_pixels.p) return ZR_OK;
-    std::vector<uint32_t> pix;
-    pix.reserve((size_t)plan.tiles.size() * plan.ts * plan.ts);
-    for (int32_t t : plan.tiles) {
-        const TileRect r = plan.clip(t);
-        for (int y = r.ya; y < r.yb; y++) for (int x = r.xa; x < r.xb; x++) pix.push_back((uint32_t)x | ((uint32_t)y << 16));   // ST_MAX_FRAME_SIDE
-    }
+    std::vector<uint32_t> pix = plan_pixels(plan);
     if (bottom_up != 0) std::reverse(pix.begin(), pix.end());
     int rc = c->d_pixels.upload(pix);
     if (rc == ZR_OK) c->pix_key = key;
@@ -363,7 +370,7 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode = 
     streams[0] = job.stream;
     for (int k = 1; k < ST_MAX_POOLS; k++) streams[k] = c->sub[k];
     zr::StreamJob sj{};
-    sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, c->d_pixels.p, c->d_partial.p, job.d_out, job.d_out2, job.count};
+    sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, c->d_pixels.p, c->d_partial.p, job.d_out, job.d_out2, job.count, job.sample0};
     sj.ctx = zr::StreamContext{c->d_ctl.p, nullptr, 0, c->st_blocks, c->d_ctr.p, streams, 1, c->st_event, c->h_active};
     sj.hooks = zr::StreamHooks{nullptr, job.keep_going, job.progress, nullptr};
     const bool polled = job.keep_going || job.progress;   // a cancelled frame / a preview reduces what exists: the samples start at zero
@@ -394,6 +401,156 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode = 
     c->last_rounds = (uint64_t)(rounds < 0 ? -rounds : rounds);
     HIP_OK(hipStreamSynchronize(job.stream));
     if (rounds < 0) return fail(ZR_E_CANCELLED, "render cancelled after %d rounds", -rounds);
+    return ZR_OK;
+}
+
+// ---- progressive accumulation: a frame in batches of samples (zr_accum, include/zr_capi.h) ----------------------------------------------------------
+
+// What a zr_accum holds.  The lane sums live in d_partial ([pixel][channel][lane], zr_launch.h: ACCUM_DOUBLES_PER_PIXEL), pixel k being the k-th of the plan's
+// pixels in tile order (d_pixels) whichever way the pipeline's own list runs.
+struct AccumState {
+    zr_ctx* ctx = nullptr; int device = 0;
+    Plan plan;
+    DevBuf<double> d_partial; DevBuf<uint32_t> d_pixels; uint32_t n_pix = 0;
+    int first = 0, done = 0;
+    int route = 2;                 // zr_counters::path of the batches so far: which one-shot kernel's pairing the resolve follows
+    bool bound = false;            // a batch has been added since create / reset: later ones must bring the same camera, seed and scene
+    zr_camera cam{}; uint64_t seed = 0; const zr_scene* scene = nullptr;
+    size_t device_bytes() const { return (size_t)n_pix * (zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double) + sizeof(uint32_t)); }
+};
+
+int accum_init(AccumState& a, zr_ctx* c, const zr_camera& cam, const zr_region* region) {
+    int rc = make_plan(cam, region, a.plan);
+    if (rc) return rc;
+    if (a.plan.W > zr::ST_MAX_FRAME_SIDE || a.plan.H > zr::ST_MAX_FRAME_SIDE) return fail(ZR_E_INVALID, "an accumulator's frame may be at most %d pixels a side", zr::ST_MAX_FRAME_SIDE);
+    const std::vector<uint32_t> pix = plan_pixels(a.plan);
+    if (pix.size() > 0xFFFFFFFFull) return fail(ZR_E_INVALID, "too many pixels for one accumulator");
+    a.ctx = c; a.device = c->device; a.n_pix = (uint32_t)pix.size();
+    if ((rc = a.d_pixels.upload(pix))) return rc;
+    if (a.d_partial.alloc((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL) != ZR_OK)
+        return fail(ZR_E_NOMEM, "no device memory for the lane sums of %u pixels (%zu bytes)", a.n_pix, (size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double));
+    HIP_OK(hipMemset(a.d_partial.p, 0, std::max<size_t>((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double), 64)));
+    HIP_OK(hipDeviceSynchronize());   // the context's streams do not wait for the null stream
+    a.first = 0; a.done = 0; a.bound = false; a.route = 2;
+    return ZR_OK;
+}
+
+// One batch: the samples [sample0, sample0 + n) of every pixel of the accumulator by the route zr_render takes for this scene and camera, added to the lane sums.
+// job: plan, camera, environment, seed, stream, count and keep_going as prepare_frame and the caller left them (the plan is the accumulator's).  The batch is rendered
+// whole before the sums are touched: on any failure — ZR_E_CANCELLED, ZR_E_NOMEM (this many samples do not fit the route in one run) — they are as they were.
+int accumulate_batch(zr_ctx* c, const zr_scene* s, FrameJob& job, AccumState& a, int sample0, int n) {
+    job.dc.spp = n; job.sample0 = (uint32_t)sample0; job.d_out = nullptr; job.d_out2 = nullptr; job.progress = nullptr; job.rows_done = nullptr;
+    c->last_rounds = 0;
+    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
+    if (a.n_pix == 0) return ZR_OK;
+    if (job.keep_going && *job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled before it began");
+    const uint64_t units = (uint64_t)a.n_pix * (uint64_t)n;
+    HostTimer timer(c);
+    if (fits_stream(c, s, job.plan, job.dc, 1, 0)) {
+        if (units > zr::ST_MAX_UNITS) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu work units, the pipeline numbers 2^32 - 1 per run: ask for fewer samples", n, (unsigned long long)units);
+        int rc = render_stream(c, s, job);
+        if (rc) return rc;
+        timer.begin(job.stream, 3);
+        HIP_OK(zr::launch_accumulate(c->d_partial.p, a.n_pix, (uint32_t)n, (uint32_t)sample0, env_double("ZR_STREAM_BOTTOM_UP", 1) != 0, a.d_partial.p, job.stream));
+        timer.end(job.stream, 3);
+    } else {
+        // the pixel-group route: the batch's per-sample radiance, then the same accumulate kernel
+        if (units > (1ull << 37)) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu samples of radiance: ask for fewer", n, (unsigned long long)units);
+        if (c->d_partial.n < units * 3) {
+            HIP_OK(hipStreamSynchronize(job.stream));
+            if (c->d_partial.alloc(units * 3) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes): ask for fewer samples", (size_t)units * 3 * sizeof(double));
+        }
+        c->last_path = 0;
+        if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
+        c->render_id++; c->last_stream = job.stream; c->last_counted = job.count;
+        timer.begin(job.stream, 1);
+        HIP_OK(zr::launch_render_samples(s->ds, job.dc, job.de, job.seed, a.d_pixels.p, a.n_pix, (uint32_t)sample0, (uint32_t)n, c->d_partial.p, c->d_ctr.p, job.count, job.stream));
+        timer.end(job.stream, 1);
+        if (job.keep_going) {
+            HIP_OK(hipStreamSynchronize(job.stream));
+            if (*job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled");
+        }
+        timer.begin(job.stream, 3);
+        HIP_OK(zr::launch_accumulate(c->d_partial.p, a.n_pix, (uint32_t)n, (uint32_t)sample0, false, a.d_partial.p, job.stream));
+        timer.end(job.stream, 3);
+    }
+    if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
+    HIP_OK(hipStreamSynchronize(job.stream));
+    a.route = c->last_path;
+    return ZR_OK;
+}
+
+// the mean of the samples held, into the accumulator's pixels of the device frame d_out, with the pairing of the kernel that rendered them (zr_stream.hip: accum_resolve)
+int accum_resolve_into(const AccumState& a, double* d_out, hipStream_t stream) {
+    HIP_OK(zr::launch_accum_resolve(a.d_partial.p, a.d_pixels.p, a.n_pix, a.plan.W, a.done, a.route == 0 ? lanes_for(a.done) : 1, d_out, stream));
+    return ZR_OK;
+}
+
+// work units one run of the pipeline may have: the packing limit, or less (ZR_STREAM_BATCH_UNITS: a development switch that makes a small frame render in batches)
+uint64_t stream_unit_limit() { return (uint64_t)std::min((double)zr::ST_MAX_UNITS, std::max(1.0, env_double("ZR_STREAM_BATCH_UNITS", (double)zr::ST_MAX_UNITS))); }
+
+// A frame whose only misfit is its size — more work units than one run numbers, or no memory for 24 bytes of samples[] per unit — rendered through the pipeline in
+// batches of samples with an accumulator of its own.  Same image bit for bit (the lane sums do not know where the batches were cut), counters are the frame's totals.
+// Batches are equal, a multiple of 64 samples where possible, at most `n_max` samples; a batch that meets ZR_E_NOMEM is retried at half the size.  ZR_E_NOMEM from here:
+// not even small batches fit (or the lane sums themselves do not): the caller falls back to the pixel-group kernel.
+int render_batched(zr_ctx* c, const zr_scene* s, const FrameJob& frame, int n_max) {
+    const int spp = frame.dc.spp;
+    AccumState a;
+    a.plan = frame.plan;
+    {
+        const std::vector<uint32_t> pix = plan_pixels(a.plan);
+        a.ctx = c; a.device = c->device; a.n_pix = (uint32_t)pix.size();
+        int rc = a.d_pixels.upload(pix);
+        if (rc) return rc;
+        HIP_OK(hipStreamSynchronize(frame.stream));
+        if (a.d_partial.alloc((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL) != ZR_OK)
+            return fail(ZR_E_NOMEM, "no device memory for the lane sums of %u pixels (%zu bytes)", a.n_pix, (size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double));
+        HIP_OK(hipMemsetAsync(a.d_partial.p, 0, std::max<size_t>((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double), 64), frame.stream));
+    }
+    n_max = std::max(1, std::min(n_max, spp));
+    const int n_batches = (spp + n_max - 1) / n_max;
+    int n = (spp + n_batches - 1) / n_batches;
+    if (n >= 64) n = (n + 63) / 64 * 64 <= n_max ? (n + 63) / 64 * 64 : std::max(n_max / 64 * 64, 1);
+    FrameJob job = frame;
+    unsigned long long totals[zr::CTR_WORDS] = {0};
+    uint64_t rounds = 0;
+    const uint64_t id0 = c->render_id;
+    bool cancelled = false;
+    while (a.done < spp) {
+        const int nb = std::min(n, spp - a.done);
+        int rc = accumulate_batch(c, s, job, a, a.done, nb);
+        if (rc == ZR_E_NOMEM && nb > 1) {
+            n = nb / 2 >= 64 ? nb / 2 / 64 * 64 : nb / 2;
+            std::fprintf(stderr, "[zr] %s: retrying with batches of %d samples\n", zr_host::last_error(), n);
+            continue;
+        }
+        if (rc == ZR_E_CANCELLED) { cancelled = true; break; }
+        if (rc) return rc;
+        if (frame.count) {
+            unsigned long long h[zr::CTR_WORDS];
+            HIP_OK(hipMemcpy(h, c->d_ctr.p, sizeof h, hipMemcpyDeviceToHost));
+            for (int w = 0; w < zr::CTR_WORDS; w++) totals[w] += h[w];
+        }
+        rounds += c->last_rounds;
+        a.done += nb;
+        if (a.done < spp) {
+            const double f = (double)a.done / spp;
+            if (frame.rows_done) { const int r = std::min(frame.plan.H - 1, (int)(f * frame.plan.H)); if (r > *frame.rows_done) *frame.rows_done = r; }
+            if (frame.progress) {   // the preview between batches is the exact image of the samples done
+                const bool wants = frame.d_out && frame.progress->wants_frame();
+                if (wants) { if ((rc = accum_resolve_into(a, frame.d_out, frame.stream))) return rc; HIP_OK(hipStreamSynchronize(frame.stream)); }
+                frame.progress->report(f, wants);
+            }
+            if (frame.keep_going && *frame.keep_going == 0) { cancelled = true; break; }
+        }
+    }
+    // one render as far as zr_get_counters is concerned: the launches of every batch count towards its times
+    for (auto& p : c->pending) if (p.render_id > id0) p.render_id = c->render_id;
+    if (a.done > 0 && frame.d_out) { int rc = accum_resolve_into(a, frame.d_out, frame.stream); if (rc) return rc; }
+    if (frame.count) HIP_OK(hipMemcpyAsync(c->d_ctr.p, totals, sizeof totals, hipMemcpyHostToDevice, frame.stream));
+    HIP_OK(hipStreamSynchronize(frame.stream));
+    c->last_counted = frame.count; c->last_rounds = rounds;
+    if (cancelled) return fail(ZR_E_CANCELLED, "render cancelled after %d of %d samples per pixel", a.done, spp);
     return ZR_OK;
 }
 
@@ -431,20 +588,26 @@ int enqueue_render(zr_ctx* c, const zr_scene* s, const FrameJob& job) {
     int rc = c->d_tiles.upload(plan.tiles);
     if (rc) return rc;
     HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
-    const uint64_t units = plan.units(job.dc.spp);
-    if (fits_stream(c, s, plan, job.dc, 1, units)) {
-        int r2 = render_stream(c, s, job);
+    const uint64_t units = plan.units(job.dc.spp), unit_limit = stream_unit_limit();
+    if (fits_stream(c, s, plan, job.dc, 1, 0)) {   // everything but the frame's size fits the pipeline
+        const uint64_t n_pix = units / (uint64_t)job.dc.spp;
+        int r2 = ZR_E_NOMEM, n_max = job.dc.spp / 2;
+        if (units <= unit_limit || job.dc.spp == 1) r2 = render_stream(c, s, job);
+        else n_max = (int)std::min<uint64_t>(unit_limit / std::max<uint64_t>(n_pix, 1), (uint64_t)job.dc.spp);
+        // too many work units for one run, or no memory for one run's buffers (24 bytes per primary sample + the slot pool) beside what else lives on the
+        // device: the same frame in batches of samples (render_batched)
+        if (r2 == ZR_E_NOMEM && job.dc.spp > 1) r2 = render_batched(c, s, job, n_max);
         if (job.rows_done && r2 == ZR_OK) *job.rows_done = plan.H;
         if (r2 != ZR_E_NOMEM) return r2;
-        // the pipeline's buffers (24 bytes per primary sample + the slot pool) do not fit beside what else lives on the device: the
-        // pixel-group kernel below needs neither
+        // not even in batches: the pixel-group kernel below needs neither buffer
         std::fprintf(stderr, "[zr] %s: rendering this frame with the pixel-group kernel (same results, slower)\n", zr_host::last_error());
         HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
     } else if (c->variant == 2 && !c->warned_fallback) {   // said once per context: the frame is rendered, by the slower kernel
         c->warned_fallback = true;
-        std::fprintf(stderr, "[zr] frame outside the streaming pipeline's packing limits (max_depth %d > %d, %llu work units > 2^32, %d x %d px > %d, "
-                             "or a scene with more than 2^24 primitives of a kind): rendered by the pixel-group kernel — same results, about six times slower\n",
-                     job.dc.max_depth, zr::ST_MAX_BOUNCES, (unsigned long long)units, plan.W, plan.H, zr::ST_MAX_FRAME_SIDE);
+        std::fprintf(stderr, "[zr] frame outside the streaming pipeline's packing limits (max_depth %d > %d, %d x %d px > %d, or a scene with more than 2^24 "
+                             "primitives of a kind; a frame of more than 2^32 work units is no longer one of them, it renders in sample batches): rendered by the "
+                             "pixel-group kernel — same results, several times slower\n",
+                     job.dc.max_depth, zr::ST_MAX_BOUNCES, plan.W, plan.H, zr::ST_MAX_FRAME_SIDE);
     }
     c->last_path = 0;
     if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
@@ -468,7 +631,93 @@ int enqueue_render(zr_ctx* c, const zr_scene* s, const FrameJob& job) {
 
 }  // namespace
 
+struct zr_accum { AccumState st; };
+
 extern "C" {
+
+zr_accum* zr_accum_create(zr_ctx* c, int width, int height, const zr_region* region) {
+    if (!c) { fail(ZR_E_INVALID, "null argument"); return nullptr; }
+    if (width < 1 || height < 1) { fail(ZR_E_INVALID, "accumulator size %d x %d not supported", width, height); return nullptr; }
+    if (hipSetDevice(c->device) != hipSuccess) { fail(ZR_E_DEVICE, "hipSetDevice(%d) failed", c->device); return nullptr; }
+    zr_camera shape{}; shape.image_width = width; shape.image_height = height;
+    std::unique_ptr<zr_accum> a(new zr_accum);
+    if (accum_init(a->st, c, shape, region)) return nullptr;
+    return a.release();
+}
+
+void zr_accum_destroy(zr_accum* a) {
+    if (!a) return;
+    (void)hipSetDevice(a->st.device);
+    delete a;
+}
+
+int zr_accum_reset(zr_accum* a, int first_sample) {
+    if (!a) return fail(ZR_E_INVALID, "null argument");
+    if (first_sample < 0) return fail(ZR_E_INVALID, "first sample %d below zero", first_sample);
+    AccumState& st = a->st;
+    HIP_OK(hipSetDevice(st.device));
+    HIP_OK(hipMemset(st.d_partial.p, 0, std::max<size_t>((size_t)st.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double), 64)));
+    HIP_OK(hipDeviceSynchronize());   // the context's streams do not wait for the null stream
+    st.first = first_sample; st.done = 0; st.bound = false;
+    return ZR_OK;
+}
+
+int zr_render_accumulate(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, zr_accum* a, int n_samples,
+                         int collect_counters, volatile const uint8_t* keep_going) {
+    if (!c || !s || !cam || !env || !a) return fail(ZR_E_INVALID, "null argument");
+    AccumState& st = a->st;
+    if (st.ctx != c) return fail(ZR_E_INVALID, "accumulator belongs to another context");
+    if (n_samples < 1) return fail(ZR_E_INVALID, "a batch has at least one sample (%d asked for)", n_samples);
+    int rc = scene_ready(c, s, "zr_render_accumulate");
+    if (rc) return rc;
+    const int W = cam->image_width < 1 ? 1 : cam->image_width, H = cam->image_height < 1 ? 1 : cam->image_height;
+    if (W != st.plan.W || H != st.plan.H) return fail(ZR_E_INVALID, "camera of %d x %d px, accumulator of %d x %d", W, H, st.plan.W, st.plan.H);
+    zr_camera key = *cam; key.samples_per_pixel = 0;   // ignored here
+    if (st.bound && (std::memcmp(&key, &st.cam, sizeof key) != 0 || seed != st.seed || s != st.scene))
+        return fail(ZR_E_INVALID, "camera, seed or scene differ from the first batch's: zr_accum_reset starts a new frame");
+    if ((long long)st.first + st.done + n_samples > 0x7FFFFFFFll) return fail(ZR_E_INVALID, "sample range beyond 2^31");
+    FrameJob job;
+    HIP_OK(hipSetDevice(c->device));
+    job.plan = st.plan;
+    make_camera(*cam, job.dc);
+    make_env(*env, job.de);
+    if ((rc = check_env(job.de, s))) return rc;
+    job.seed = seed; job.stream = c->stream; job.count = collect_counters != 0; job.keep_going = keep_going;
+    if ((rc = accumulate_batch(c, s, job, st, st.first + st.done, n_samples))) return rc;
+    st.done += n_samples;
+    if (!st.bound) { st.bound = true; st.cam = key; st.seed = seed; st.scene = s; }
+    return ZR_OK;
+}
+
+int zr_accum_resolve_device(zr_accum* a, void* d_out_rgb, void* hip_stream) {
+    if (!a || !d_out_rgb) return fail(ZR_E_INVALID, "null argument");
+    if (a->st.done == 0) return fail(ZR_E_STATE, "zr_render_accumulate must precede zr_accum_resolve");
+    HIP_OK(hipSetDevice(a->st.device));
+    int rc = accum_resolve_into(a->st, (double*)d_out_rgb, (hipStream_t)hip_stream);
+    if (rc) return rc;
+    HIP_OK(hipStreamSynchronize((hipStream_t)hip_stream));
+    return ZR_OK;
+}
+
+int zr_accum_resolve(zr_accum* a, double* out_rgb) {
+    if (!a || !out_rgb) return fail(ZR_E_INVALID, "null argument");
+    AccumState& st = a->st;
+    if (st.done == 0) return fail(ZR_E_STATE, "zr_render_accumulate must precede zr_accum_resolve");
+    HIP_OK(hipSetDevice(st.device));
+    DevBuf<double> d_frame;   // only the plan's pixels of it are written, and only they are copied out
+    int rc = d_frame.alloc(st.plan.npx() * 3);
+    if (rc) return rc;
+    if ((rc = accum_resolve_into(st, d_frame.p, nullptr))) return rc;
+    HIP_OK(hipStreamSynchronize(nullptr));
+    std::vector<double> staging;
+    return copy_region(st.plan, d_frame.p, out_rgb, staging);
+}
+
+int zr_accum_state(const zr_accum* a, int64_t out[4]) {
+    if (!a || !out) return fail(ZR_E_INVALID, "null argument");
+    out[0] = a->st.first; out[1] = a->st.done; out[2] = (int64_t)a->st.n_pix; out[3] = (int64_t)a->st.device_bytes();
+    return ZR_OK;
+}
 
 int zr_render_device(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region,
                      int collect_counters, void* d_out_rgb, void* hip_stream) {

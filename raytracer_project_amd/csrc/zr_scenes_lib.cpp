@@ -81,6 +81,35 @@ int zrs_render_dropin(void* p, int width, int height, int spp, int device, doubl
     return 0;
 }
 
+// camera::render with camera::samples_per_pass set (the progressive render of include/zenith/zenith.hpp).  info[0] = current_samples_count after the render,
+// info[1] = the number of times render_accumulator was refreshed.  current_samples_count holds -7 when render() is called, so a render that leaves it alone
+// (samples_per_pass = 0) reports -7.  Returns 0, or -1 if the render did not finish.
+int zrs_render_dropin_progressive(void* p, int width, int height, int spp, int device, int samples_per_pass, double* out, int* info) {
+    handle* h = (handle*)p;
+    camera cam;
+    const zr_camera& c = h->s.cam;
+    cam.image_width = width > 0 ? width : c.image_width;
+    cam.image_height = height > 0 ? height : c.image_height;
+    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
+    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
+    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
+    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
+    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
+    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
+    cam.seed = h->s.seed; cam.device = device;
+    cam.reset_accumulator();
+    cam.samples_per_pass = samples_per_pass;
+    cam.current_samples_count = -7;
+    post_processor post;
+    std::atomic<bool> flag{true};
+    auto bvh_world = make_shared<bvh_node>(h->s.world);
+    cam.render(*bvh_world, h->s.env, post, flag);
+    if (info) { info[0] = cam.current_samples_count; info[1] = cam.passes_rendered; }
+    if (cam.lines_rendered.load() != cam.image_height) return -1;
+    std::memcpy(out, cam.render_accumulator.data(), cam.render_accumulator.size() * sizeof(color));
+    return 0;
+}
+
 // camera::render with global_settings::bvh_debug_mode set (debug_bvh_level = level, bvh_thickness = thickness) through the drop-in API; the
 // settings are restored afterwards.  `aux`, when not null, receives albedo_buffer (which the debug view leaves as reset_accumulator made it).
 // Returns 0, or -1 if the render did not finish.

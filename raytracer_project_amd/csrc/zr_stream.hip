@@ -81,6 +81,7 @@ struct StreamBuf {
     uint32_t unit_base;       // first dynamically assigned unit (= slots of both pools)
     uint32_t unit_chunk;      // 0: units are striped over the shards (unit_base + k * ST_SHARDS + shard); G > 0: XCD-affine hand-out, see st_unit_of
     uint32_t shard_k0;        // affine hand-out: index in its shard's sequence of the first unit a shard deals dynamically (= slots per shard)
+    uint32_t sample0;         // the run renders samples [sample0, sample0 + spp) of every pixel: unit u is sample sample0 + u % spp (0: a whole frame)
     uint2* kend;              // reflection / refraction split: per unit (draws, segments) the beauty path consumed
     unsigned char* cls;       // reflection / refraction split: per unit 1 = reflection, 2 = refraction, 0 = no contribution
     unsigned long long* cpart; // reflection / refraction split: per SHADE block (samples, segments, hits, draws), owned by that block
@@ -140,7 +141,7 @@ __host__ __device__ inline unsigned long long st_first_unit(uint32_t G, uint32_t
 
 // ---- begin a sample in a slot: camera ray + fresh path state --------------------------------------------
 __device__ inline void begin_sample(const StreamBuf& B, const DCamera& cam, uint64_t seed, const SlotAt& S, uint32_t unit, uint32_t& c_samp) {
-    const uint32_t pix_i = unit / B.spp, sample = unit - pix_i * B.spp;
+    const uint32_t pix_i = unit / B.spp, sample = unit - pix_i * B.spp + B.sample0;
     const uint32_t pk = B.pixels[pix_i];
     const int px = (int)(pk & 0xFFFFu), py = (int)(pk >> 16);
     Rng g; g.key = zr_stream_key(seed, (uint64_t)py * (uint64_t)cam.W + (uint64_t)px, (uint64_t)sample); g.k = 0; g.bounce = 0;
@@ -801,6 +802,7 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
 struct FusedBuf {
     const uint32_t* pixels; double* samples; unsigned int* uctl;   // uctl: the unit-counter block; here shard s counts chunks of ST_FUSED_CHUNK units
     uint32_t spp, n_units;
+    uint32_t sample0;              // as StreamBuf::sample0
     uint32_t chunk_lo, chunk_hi;   // this launch hands out the chunks [chunk_lo, chunk_hi) of ST_FUSED_CHUNK units (a frame in one launch, or in
                                    // parts when the caller polls for cancellation / progress between them)
 };
@@ -906,7 +908,7 @@ __global__ __launch_bounds__(256, ST_FUSED_WAVES) void fused_render(DScene sc, D
                 const uint32_t my = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
                 if (my < want) {
                     unit = base + my;
-                    const uint32_t pix_i = unit / B.spp, sample = unit - pix_i * B.spp;
+                    const uint32_t pix_i = unit / B.spp, sample = unit - pix_i * B.spp + B.sample0;
                     const uint32_t pk = B.pixels[pix_i];
                     const int px = (int)(pk & 0xFFFFu), py = (int)(pk >> 16);
                     g.key = zr_stream_key(seed, (uint64_t)py * (uint64_t)cam.W + (uint64_t)px, (uint64_t)sample); g.k = 0; g.bounce = 0;
@@ -1021,6 +1023,57 @@ __global__ __launch_bounds__(256) void stream_reduce(StreamBuf B, DCamera cam, d
     }
 }
 
+// ---- progressive accumulation (zr_accum) ----------------------------------------------------------------------------
+// The lane sums of stream_reduce, kept between runs: partial[pixel][channel][lane] (64 x 3 doubles = 1536 contiguous bytes per pixel, one coalesced
+// 512-byte row per channel).  Sample s of a pixel ALWAYS belongs to lane s % 64 and a lane adds its samples in increasing s, so after any split of
+// [0, N) into consecutive batches the 64 sums are exactly those stream_reduce forms in registers for spp = N (0.0 + x is x).  One wave per pixel,
+// no atomics, no LDS.  `samples` holds the batch as the pipeline wrote it ([n_pix][n][3], sample0 + sidx at index sidx); flip: that pixel list ran
+// in the reverse of the accumulator's order (ZR_STREAM_BOTTOM_UP).
+__global__ __launch_bounds__(256) void stream_accumulate(const double* __restrict__ samples, uint32_t n_pix, uint32_t n, uint32_t sample0, uint32_t flip,
+                                                          double* __restrict__ partial) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i >= n_pix) return;
+    const uint32_t first = (lane - sample0) & 63u;   // the batch's first sample of this lane: (sample0 + first) % 64 == lane
+    if (first >= n) return;
+    const double* pp = samples + (size_t)i * n * 3;
+    double* q = partial + (size_t)(flip ? n_pix - 1u - i : i) * 192 + lane;
+    double sx = q[0], sy = q[64], sz = q[128];
+    for (uint32_t sidx = first; sidx < n; sidx += 64) { sx += pp[(size_t)sidx * 3]; sy += pp[(size_t)sidx * 3 + 1]; sz += pp[(size_t)sidx * 3 + 2]; }
+    q[0] = sx; q[64] = sy; q[128] = sz;
+}
+
+// The stored lane sums -> the mean of the `done` samples they hold, into the accumulator's pixels of `out`.  The xor butterfly of the kernel that
+// rendered the batches: stream_reduce pairs lanes 32, 16, ... 1 apart (asc_lanes = 1); the pixel-group kernel sums over L = asc_lanes lanes
+// (lanes_for: sample s in lane s % L) and pairs them 1, 2, ... L/2 apart, which here is the steps 32 ... L first (lane l + lane l + L, the
+// two samples a pixel-group lane adds) and then 1 ... L/2.  Either way every lane ends with the sum of all 64; the order is what makes the frame
+// equal the one-shot frame of the same route bit for bit.
+__global__ __launch_bounds__(256) void accum_resolve(const double* __restrict__ partial, const uint32_t* __restrict__ pixels, uint32_t n_pix, int W, int done,
+                                                      int asc_lanes, double* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= n_pix) return;
+    const double* q = partial + (size_t)i * 192 + lane;
+    double sx = q[0], sy = q[64], sz = q[128];
+    for (int m = 32; m >= asc_lanes; m >>= 1) {
+        sx += __hiloint2double(__shfl_xor(__double2hiint(sx), m, 64), __shfl_xor(__double2loint(sx), m, 64));
+        sy += __hiloint2double(__shfl_xor(__double2hiint(sy), m, 64), __shfl_xor(__double2loint(sy), m, 64));
+        sz += __hiloint2double(__shfl_xor(__double2hiint(sz), m, 64), __shfl_xor(__double2loint(sz), m, 64));
+    }
+    for (int m = 1; m < asc_lanes; m <<= 1) {
+        sx += __hiloint2double(__shfl_xor(__double2hiint(sx), m, 64), __shfl_xor(__double2loint(sx), m, 64));
+        sy += __hiloint2double(__shfl_xor(__double2hiint(sy), m, 64), __shfl_xor(__double2loint(sy), m, 64));
+        sz += __hiloint2double(__shfl_xor(__double2hiint(sz), m, 64), __shfl_xor(__double2loint(sz), m, 64));
+    }
+    if (lane == 0) {
+        const uint32_t pk = pixels[i];
+        const int px = (int)(pk & 0xFFFFu), py = (int)(pk >> 16);
+        const double scale = 1.0 / done;  // camera.hpp:437,531 with the samples that exist
+        double* o = out + ((size_t)py * W + px) * 3;
+        o[0] = sx * scale; o[1] = sy * scale; o[2] = sz * scale;
+    }
+}
+
 // per-block counters of the split passes -> the context's counter words (samples, segments, hits, draws)
 __global__ __launch_bounds__(256) void stream_sum_counters(const unsigned long long* __restrict__ cpart, size_t n_blocks, unsigned long long* __restrict__ gctr) {
     __shared__ unsigned long long s[4];
@@ -1121,7 +1174,7 @@ static StreamBuf make_buf(void* pool, uint32_t P, uint32_t spp, uint32_t n_units
                           unsigned int* ctl, unsigned int* uctl, uint32_t unit0, uint32_t unit_base) {
     StreamBuf B;
     B.pool = (double*)pool; B.pixels = pixels; B.samples = samples; B.ctl = ctl; B.uctl = uctl;
-    B.P = P; B.spp = spp; B.n_units = n_units; B.n_pix = n_pix; B.unit0 = unit0; B.unit_base = unit_base; B.unit_chunk = 0; B.shard_k0 = 0;
+    B.P = P; B.spp = spp; B.n_units = n_units; B.n_pix = n_pix; B.unit0 = unit0; B.unit_base = unit_base; B.unit_chunk = 0; B.shard_k0 = 0; B.sample0 = 0;
     B.kend = nullptr; B.cls = nullptr; B.cpart = nullptr;
     return B;
 }
@@ -1164,7 +1217,7 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
         for (int k = 0; k < K; k++) {
             uint32_t Pk = k == K - 1 ? P - first : (P / K + pool_round - 1) / pool_round * pool_round;
             Q[k] = make_buf(base, Pk, F.spp, n_units, n_pix, F.pixels, F.samples, X.ctl + (size_t)k * W, uctl, first, P);
-            Q[k].unit_chunk = unit_chunk; Q[k].shard_k0 = unit_chunk ? P / ST_SHARDS : 0u;
+            Q[k].unit_chunk = unit_chunk; Q[k].shard_k0 = unit_chunk ? P / ST_SHARDS : 0u; Q[k].sample0 = F.sample0;
             Q[k].kend = (uint2*)job.split.kend; Q[k].cls = (unsigned char*)job.split.cls;
             Q[k].cpart = job.split.cpart ? job.split.cpart + ((size_t)first / 256 + (size_t)k) * 4 : nullptr;
             ov[k] = (unsigned char*)X.overflow + (size_t)k * stream_overflow_bytes(X.extend_blocks, X.ovf_levels);
@@ -1301,7 +1354,7 @@ hipError_t fused_render_frame(const DScene& sc, const StreamFrame& F, const Stre
     const uint32_t n_units = F.n_pix * F.spp;
     const size_t W = stream_ctl_words();
     hipError_t e;
-    FusedBuf B; B.pixels = F.pixels; B.samples = F.samples; B.uctl = X.ctl + (size_t)ST_MAX_POOLS * W; B.spp = F.spp; B.n_units = n_units;
+    FusedBuf B; B.pixels = F.pixels; B.samples = F.samples; B.uctl = X.ctl + (size_t)ST_MAX_POOLS * W; B.spp = F.spp; B.n_units = n_units; B.sample0 = F.sample0;
     const unsigned long long n_chunks = ((unsigned long long)n_units + ST_FUSED_CHUNK - 1) / ST_FUSED_CHUNK;
     // one launch for the whole frame — or, for a caller that polls (render_flag, lines_rendered, the live preview of camera.hpp:548-552 /
     // main.cpp:1576), sixteen launches over consecutive parts of the unit range with the poll between them (samples[] was zeroed, so the
@@ -1340,6 +1393,17 @@ hipError_t fused_render_frame(const DScene& sc, const StreamFrame& F, const Stre
     if (F.out) hipLaunchKernelGGL(stream_reduce, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, R, cam, F.out);
     if (H.timer) H.timer->end(stream, 3);
     if (H.done_out) *H.done_out = cancelled ? -done : done;
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate(const double* samples, uint32_t n_pix, uint32_t n, uint32_t sample0, bool flip, double* partial, hipStream_t stream) {
+    if (n_pix == 0 || n == 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_accumulate, dim3((n_pix + 3) / 4), dim3(256), 0, stream, samples, n_pix, n, sample0, flip ? 1u : 0u, partial);
+    return hipGetLastError();
+}
+hipError_t launch_accum_resolve(const double* partial, const uint32_t* pixels, uint32_t n_pix, int W, int done, int asc_lanes, double* out, hipStream_t stream) {
+    if (n_pix == 0) return hipSuccess;
+    hipLaunchKernelGGL(accum_resolve, dim3((n_pix + 3) / 4), dim3(256), 0, stream, partial, pixels, n_pix, W, done, asc_lanes, out);
     return hipGetLastError();
 }
 
