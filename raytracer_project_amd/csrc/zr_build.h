@@ -24,15 +24,15 @@ struct BuildSceneIn {
     const double* group_box = nullptr;   // per zr_group: lo[3], hi[3] of its triangles in their own space
 };
 
-struct BuildParams {
-    float ct = 1.0f;           // cost of a node visit
-    float ck[8] = {1, 1.5f, 1, 3, 3, 1.5f, 16, 1};   // cost of testing one primitive of each leaf kind
-    int max_leaf = 4;
-    int leaf_cap[8] = {0, 0, 1, 1, 1, 1, 1, 0};      // per kind; 0 = max_leaf
-    float open_ratio = 1.25f;  // 4-wide collapse: a child is not opened when the wider node's grid would inflate a box's area beyond this
-    int radius = 16;           // PLOC search radius (clusters on either side in Morton order)
-    int top_clusters = 16384;  // PLOC stops at this many clusters and the host's binned-SAH builder arranges them (0: PLOC to the root); worlds under 8 x this: PLOC alone.
-                               // zr_commit.cpp picks n / 64 within 4096 ... 65536
+struct BuildParams {   // no defaults here: zr_commit.cpp fills every field from the knobs both builders share (zr_flatten.h: read_build_knobs)
+    float ct;            // cost of a node visit
+    float ck[8];         // cost of testing one primitive of each leaf kind
+    int max_leaf;
+    int leaf_cap[8];     // per kind; 0 = max_leaf
+    float open_ratio;    // 4-wide collapse: a child is not opened when the wider node's grid would inflate a box's area beyond this
+    int radius;          // PLOC search radius (clusters on either side in Morton order)
+    int top_clusters;    // PLOC stops at this many clusters and the host's binned-SAH builder arranges them (0: PLOC to the root); worlds under 8 x this: PLOC alone.
+                         // zr_commit.cpp picks n / 64 within 4096 ... 65536
 };
 
 // where a tree's leaves put their primitive records: the scene's final arrays and the first index this tree may use per leaf kind

@@ -11,6 +11,9 @@
 #ifndef ZR_TRI_STRIDE
 #define ZR_TRI_STRIDE 9    /* doubles between two records of DScene::tri_v (9 are used) */
 #endif
+#define ZR_SPHERE_DOUBLES 4     /* doubles per record of DScene::spheres */
+#define ZR_CUBE_DOUBLES 6       /* ... of DScene::cubes */
+#define ZR_TRI_SHADE_DOUBLES 20 /* ... of DScene::tri_s, the triangle's shading record */
 #define ZR_STACK_DEPTH 48  /* builder guarantees tree depth <= ZR_STACK_DEPTH */
 #define ZR_MAX_CHAIN 8
 

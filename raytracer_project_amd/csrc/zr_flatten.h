@@ -1,14 +1,15 @@
-// zr_flatten.h — from the caller's world list to the arrays the kernels read (included by zr_commit.cpp only): bounding boxes the way the reference's
-// constructors compute them (Boxer), the classification of world entries (bare / baked / placed / wrapped), validation, and the Flattener, which turns the
-// builder's tree into sibling-pair records, 4-wide quantised nodes and the primitive arrays in leaf order.
+// zr_flatten.h — from the caller's world list to the arrays the kernels read: bounding boxes the way the reference's constructors compute them (Boxer), the
+// classification of world entries (bare / baked / placed / wrapped), validation, the commit plan both builders work from, the Flattener, which turns the
+// builder's tree into sibling-pair records, 4-wide quantised nodes and the primitive arrays in leaf order, and the host builder's CPU half.  No HIP in
+// here: zr_commit.cpp includes it for the library, tests/native/flatten_check.cpp compiles it with zr_bvh.cpp alone.
 #pragma once
-#include "zr_host_internal.h"
+#include "zr_scene_input.h"
 
 namespace {
 
 // ---- bounding boxes of world-list entries, following the reference's constructors --------------------
 struct Boxer {
-    const zr_scene& s;
+    const SceneInput& s;
     const std::vector<zr::BuildBox>* group_box = nullptr;   // per zr_group: the box of its triangles in their own space
     zr::BuildBox prim(uint32_t type, uint32_t idx) const {
         zr::BuildBox b;
@@ -75,7 +76,7 @@ inline float f_up(double x) {
 
 // what a world-list entry becomes in the tree: its leaf kind, and whether the host stores it "baked" (0 as is, 1 baked triangle,
 // 2 material-only chain, 3 baked sphere, 4 placed cube) — see Flattener::put_baked_triangle / put_baked_sphere / put_pcube
-inline void classify_object(const zr_scene& s, const zr_object& o, bool bake, uint32_t& kind, uint8_t& baked) {
+inline void classify_object(const SceneInput& s, const zr_object& o, bool bake, uint32_t& kind, uint8_t& baked) {
     kind = o.chain_count ? ZR_KIND_WRAPPED : o.type;
     baked = 0;
     if (o.type == ZR_PRIM_GROUP) { kind = ZR_KIND_INSTANCE; return; }   // placed as one object, whatever its chain
@@ -116,7 +117,7 @@ inline void classify_object(const zr_scene& s, const zr_object& o, bool bake, ui
     }
 }
 
-int validate(const zr_scene& s, const std::vector<zr_object>& objs) {
+inline int validate(const SceneInput& s, const std::vector<zr_object>& objs) {
     const size_t nm = s.materials.size(), nt = s.textures.size();
     auto mat_ok = [&](uint32_t m) { return m == 0xFFFFFFFFu || m < nm; };
     for (uint32_t m : s.sphere_mat) if (!mat_ok(m)) return fail(ZR_E_INVALID, "sphere material id %u out of range", m);
@@ -169,13 +170,110 @@ int validate(const zr_scene& s, const std::vector<zr_object>& objs) {
     return ZR_OK;
 }
 
+// ZR_COMMIT_STATS: one line on stderr per phase of a commit, "[zr] <who>: <phase, padded to `width`> <time> ms"
+struct PhaseTimer {
+    const char* who; int width;
+    double t0 = now();
+    bool on = std::getenv("ZR_COMMIT_STATS") != nullptr;
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    void operator()(const char* what) { if (on) { const double t = now(); std::fprintf(stderr, "[zr] %s: %-*s %.1f ms\n", who, width, what, (t - t0) * 1e3); t0 = t; } }
+};
+
+// [0, n) split evenly over up to 16 threads (one below 65 536 items): fn(begin, end), the first part on the caller
+template <class F>
+void parallel_split(size_t n, F&& fn) {
+    const int T = n < 65536 ? 1 : (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; t++) th.emplace_back([&fn, n, t, T]() { fn(n * t / T, n * (t + 1) / T); });
+    fn((size_t)0, n / T);
+    for (auto& x : th) x.join();
+}
+
+// The build knobs the two builders share: a frame must not depend on which builder made the tree, so neither has defaults of its own — these are the only ones.
+struct BuildKnobs {
+    bool bake;                  // ZR_BAKE_TRIANGLES (classify_object)
+    double ct, ck[8];           // SAH cost of a traversal step and of testing one object of kind k
+    int max_leaf, leaf_cap[8];  // objects per leaf; per kind, 0 = max_leaf
+    double open_ratio;          // 4-wide collapse (Flattener::open_ratio, BuildParams::open_ratio)
+};
+inline BuildKnobs read_build_knobs() {
+    BuildKnobs kn;
+    kn.bake = env_double("ZR_BAKE_TRIANGLES", 1) != 0;
+    kn.ct = env_double("ZR_BVH_COST_TRAVERSE", 1.0);
+    const double ck[8] = {env_double("ZR_BVH_COST_SPHERE", 1.0), env_double("ZR_BVH_COST_TRI", 1.5), env_double("ZR_BVH_COST_CUBE", 1.0),
+                          env_double("ZR_BVH_COST_MEDIUM", 3.0), env_double("ZR_BVH_COST_WRAPPED", 3.0), env_double("ZR_BVH_COST_PCUBE", 1.5),
+                          env_double("ZR_BVH_COST_GROUP", 16.0), 1};
+    kn.max_leaf = (int)env_double("ZR_BVH_MAX_LEAF", 4);
+    // cubes, media and wrapped objects are few, large and dear to test: one per leaf, so that a ray only tests those whose own box it enters
+    const int big = (int)env_double("ZR_BVH_MAX_LEAF_BIG", 1);
+    const int leaf_cap[8] = {0, 0, big, big, big, big, 1, 0};   // a placement is always a leaf of its own (EXTEND enters it as a whole)
+    for (int k = 0; k < 8; k++) { kn.ck[k] = ck[k]; kn.leaf_cap[k] = leaf_cap[k]; }
+    kn.open_ratio = env_double("ZR_BVH_OPEN_RATIO", 1.25);
+    return kn;
+}
+
+// the world list: the caller's, or every primitive that is not a medium's boundary, then the media
+inline std::vector<zr_object> world_list(const SceneInput& s) {
+    std::vector<zr_object> objs;
+    if (s.objects_set) { objs.assign(s.objects.begin(), s.objects.end()); return objs; }
+    std::vector<char> sb(s.sphere_mat.size(), 0), cb(s.cube_mat.size(), 0);
+    for (const zr_medium& m : s.media) {
+        if (m.boundary_type == ZR_PRIM_SPHERE && m.boundary_index < sb.size()) sb[m.boundary_index] = 1;
+        if (m.boundary_type == ZR_PRIM_CUBE && m.boundary_index < cb.size()) cb[m.boundary_index] = 1;
+    }
+    for (uint32_t k = 0; k < s.sphere_mat.size(); k++) if (!sb[k]) objs.push_back({ZR_PRIM_SPHERE, k, 0, 0});
+    for (uint32_t k = 0; k < s.tri_mat.size(); k++) objs.push_back({ZR_PRIM_TRIANGLE, k, 0, 0});
+    for (uint32_t k = 0; k < s.cube_mat.size(); k++) if (!cb[k]) objs.push_back({ZR_PRIM_CUBE, k, 0, 0});
+    for (uint32_t k = 0; k < s.media.size(); k++) objs.push_back({ZR_PRIM_MEDIUM, k, 0, 0});
+    return objs;
+}
+
+// What both builders work from, computed once per commit (after validate): the world list, the knobs, what every entry becomes, and from that the final
+// length of every primitive array.  Arrays of 8 are indexed by leaf kind (ZR_PRIM_* / ZR_KIND_*).
+struct CommitPlan {
+    std::vector<zr_object> objs;
+    BuildKnobs kn;
+    std::vector<uint8_t> code;   // per entry: leaf kind | baked << 4 (classify_object) — the form the device builder reads
+    uint32_t cnt[8] = {};        // leaf objects
+    size_t inner[8] = {};        // primitives inside media and wrapper chains: stored behind the leaf ranges (and, for triangles, behind the groups' runs)
+    size_t group_tris = 0;       // triangles of all groups: behind the leaf triangles
+    size_t size[8] = {};         // records of each kind's array
+    uint32_t kind(size_t k) const { return code[k] & 7u; }
+};
+inline std::shared_ptr<CommitPlan> make_plan(const SceneInput& s, std::vector<zr_object>&& objs) {
+    auto plan = std::make_shared<CommitPlan>();
+    CommitPlan& p = *plan;
+    p.objs = std::move(objs); p.kn = read_build_knobs(); p.code.resize(p.objs.size());
+    std::atomic<uint32_t> cnt[8] = {};
+    parallel_split(p.objs.size(), [&](size_t k0, size_t k1) {
+        uint32_t c[8] = {};
+        for (size_t k = k0; k < k1; k++) { uint32_t kind; uint8_t bk; classify_object(s, p.objs[k], p.kn.bake, kind, bk); p.code[k] = (uint8_t)(kind | (bk << 4)); c[kind & 7]++; }
+        for (int k = 0; k < 8; k++) cnt[k] += c[k];
+    });
+    for (int k = 0; k < 8; k++) p.cnt[k] = cnt[k];
+    auto count_inner = [&](uint32_t type, uint32_t idx, auto&& self) -> void {
+        p.inner[type]++;
+        if (type == ZR_PRIM_MEDIUM) self(s.media[idx].boundary_type, s.media[idx].boundary_index, self);
+    };
+    if (p.cnt[ZR_PRIM_MEDIUM] + p.cnt[ZR_KIND_WRAPPED])   // (a million-entry scan for nothing otherwise)
+        for (size_t k = 0; k < p.objs.size(); k++) {
+            const zr_object& o = p.objs[k];
+            if (p.kind(k) == ZR_PRIM_MEDIUM) count_inner(s.media[o.index].boundary_type, s.media[o.index].boundary_index, count_inner);
+            else if (p.kind(k) == ZR_KIND_WRAPPED) count_inner(o.type, o.index, count_inner);
+        }
+    for (const zr_group& g : s.groups) p.group_tris += g.triangle_count;
+    for (int k = 0; k < 8; k++) p.size[k] = p.cnt[k] + p.inner[k];
+    p.size[ZR_PRIM_TRIANGLE] += p.group_tris;
+    return plan;
+}
+
 // flattens the build tree into sibling-pair records and 4-wide nodes and, leaf by leaf, the primitive arrays in leaf order.
 // Built for commit latency like the builder (zr_bvh.cpp): one cheap serial walk fixes every index (pair numbers in pre-order,
 // each leaf's range in its kind's array), then the primitive records, the pair records and the 4-wide nodes (whose shape
 // depends on quantisation trials) are produced by all threads; nothing is appended under a lock.  The arrays are
 // zr::RawArray (no zero-fill).  The result is the same as a serial depth-first emit, whatever the number of threads.
 struct Flattener {
-    const zr_scene& s;
+    const SceneInput& s;
     const std::vector<zr_object>& objs;
     const zr::BuildResult& br;
     zr::RawArray<zr::NodePair> pairs;
@@ -192,12 +290,11 @@ struct Flattener {
     std::vector<uint32_t> run_root;                       // per group: pair index of its subtree's root
     std::vector<uint32_t> run_tri_base, run_qroot, run_demand;   // per group: first triangle (device index), its root among the 4-wide nodes, its worst-case stack entries
     bool root_in_array = false;                           // a group's own flattener: the root is a quantised node like any other (quads[0])
-    size_t n_sph = 0, n_tri = 0, n_cube = 0, n_pcube = 0, n_media = 0, n_wrapped = 0;   // filled sizes (the arrays are sized exactly)
+    size_t n_sph = 0, n_tri = 0, n_cube = 0, n_media = 0;   // filled sizes of the arrays that grow behind their leaf ranges (the arrays are sized exactly)
     std::function<void()> after_primitives;   // called by run() once spheres / triangles / cubes / media / wrapped are complete
-    const std::vector<uint8_t>* baked = nullptr;   // per object: 0 as is, 1 baked triangle, 2 material-only chain, 3 baked sphere, 4 placed cube
+    const CommitPlan* commit_plan = nullptr;       // the world's flattener: sizes, and per object code >> 4 = 0 as is, 1 baked triangle, 2 material-only chain, 3 baked sphere, 4 placed cube
     bool want_src = false;                         // fill src: per leaf kind, each leaf primitive's index in the caller's arrays (zr_scene::leaf_src)
     std::vector<uint32_t> src[8];
-    size_t n_baked = 0;
     int threads = 1;
 
     // Workers that live as long as run(): the level-synchronous passes below call parallel_for some forty times, and starting
@@ -264,20 +361,20 @@ struct Flattener {
     // (material_instance.hpp:12-28) — it is stored bare with the outermost instance's material
     void put_sphere(size_t di, uint32_t idx, uint32_t mat) {
         const double* q = &s.spheres[(size_t)idx * 4];
-        double* d = &spheres[di * 4];
+        double* d = &spheres[di * ZR_SPHERE_DOUBLES];
         d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = std::fmax(0, q[3]);  // sphere.hpp:9
         sphere_mat[di] = mat != kKeepMaterial ? mat : s.sphere_mat[idx];
     }
     void put_triangle_raw(size_t di, const double* v, const double* nn, uint32_t mat, bool force_front) {
         std::memcpy(&tri_v[di * ZR_TRI_STRIDE], v, 72);
-        double* t = &tri_s[di * 20];
+        double* t = &tri_s[di * ZR_TRI_SHADE_DOUBLES];
         std::memcpy(t, v, 72); std::memcpy(t + 9, nn, 72);
         uint64_t mbits = mat, fbits = force_front ? 1u : 0u;
         std::memcpy(t + 18, &mbits, 8); std::memcpy(t + 19, &fbits, 8);
     }
     void put_triangle(size_t di, uint32_t idx) { put_triangle_raw(di, &s.tri_v[(size_t)idx * 9], &s.tri_n[(size_t)idx * 9], s.tri_mat[idx], false); }
     void put_cube(size_t di, uint32_t idx, uint32_t mat) {
-        std::memcpy(&cubes[di * 6], &s.cubes[(size_t)idx * 12], 48);
+        std::memcpy(&cubes[di * ZR_CUBE_DOUBLES], &s.cubes[(size_t)idx * 12], ZR_CUBE_DOUBLES * sizeof(double));
         cube_mat[di] = mat != kKeepMaterial ? mat : s.cube_mat[idx];
     }
     // A triangle under a chain of translate / rotate_x,y,z / material_instance wrappers is stored in WORLD space as a bare
@@ -329,7 +426,7 @@ struct Flattener {
             else if (op.kind == ZR_OP_TRANSLATE) { c[0] += op.a[0]; c[1] += op.a[1]; c[2] += op.a[2]; force_front = true; }
             else if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
         }
-        double* d = &spheres[di * 4];
+        double* d = &spheres[di * ZR_SPHERE_DOUBLES];
         d[0] = c[0]; d[1] = c[1]; d[2] = c[2]; d[3] = r;
         sphere_mat[di] = force_front ? (mat | 0x80000000u) : mat;
     }
@@ -360,7 +457,7 @@ struct Flattener {
     // object `oi` as a leaf primitive of a plain kind (sphere / triangle / cube / placed cube) at index di of that kind's array
     void put_leaf_object(uint32_t oi, size_t di) {
         const zr_object& o = objs[oi];
-        const uint8_t bk = baked ? (*baked)[oi] : 0;
+        const uint8_t bk = commit_plan ? commit_plan->code[oi] >> 4 : 0;
         if (o.type == ZR_PRIM_GROUP) { zr::DInstance in{}; in.chain_first = o.chain_first; in.chain_count = o.chain_count; in.root = run_root[o.index]; insts[di] = in; inst_group[di] = o.index; }
         else if (bk == 1) put_baked_triangle(di, o);
         else if (bk == 3) put_baked_sphere(di, o);
@@ -439,6 +536,38 @@ struct Flattener {
         d.mat = m.mat; d.id = idx; d.neg_inv_density = m.neg_inv_density;
         d.bindex = append_inner(m.boundary_type, m.boundary_index);
         media[di] = d;
+    }
+    // The compound leaf objects — media, wrapped objects — with the primitives they contain, which go behind the leaf ranges: serial, in the order given.
+    // The order decides where the inner primitives land, so each builder keeps its own: the host's is the leaves' emit order, the device's media before
+    // wrapped objects, each in array order.
+    struct Compound { uint32_t kind, di, oi; };   // leaf kind, index in its kind's array, world-list entry
+    void finish_compounds(const std::vector<Compound>& todo) {
+        for (const Compound& c : todo) {
+            const zr_object& o = objs[c.oi];
+            note_src(c.kind, c.di, c.oi);
+            if (c.kind == ZR_PRIM_MEDIUM) { put_medium(c.di, o.index); continue; }
+            zr::DWrapped w{};
+            w.type = o.type; w.chain_first = o.chain_first; w.chain_count = o.chain_count;
+            w.index = append_inner(o.type, o.index);
+            wrapped[c.di] = w;
+        }
+    }
+    // the primitive arrays at the plan's sizes (untouched pages cost nothing), the fill counters at the ends of the leaf ranges
+    void allocate_arrays(const CommitPlan& p) {
+        const size_t* z = p.size;
+        spheres.allocate(z[ZR_PRIM_SPHERE] * ZR_SPHERE_DOUBLES); sphere_mat.allocate(z[ZR_PRIM_SPHERE]);
+        tri_v.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_STRIDE); tri_s.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES);
+        cubes.allocate(z[ZR_PRIM_CUBE] * ZR_CUBE_DOUBLES); cube_mat.allocate(z[ZR_PRIM_CUBE]);
+        pcubes.allocate(z[ZR_KIND_PCUBE] * ZR_PCUBE_STRIDE); pcube_mat.allocate(z[ZR_KIND_PCUBE]);
+        media.allocate(z[ZR_PRIM_MEDIUM]); wrapped.allocate(z[ZR_KIND_WRAPPED]);
+        n_sph = p.cnt[ZR_PRIM_SPHERE]; n_tri = p.cnt[ZR_PRIM_TRIANGLE]; n_cube = p.cnt[ZR_PRIM_CUBE]; n_media = p.cnt[ZR_PRIM_MEDIUM];
+    }
+    bool plain_media() const {   // every medium's boundary is an unwrapped sphere or cube
+        for (size_t k = 0; k < media.size(); k++) if (media[k].chain_count != 0) return false;
+        return true;
+    }
+    bool filled(const CommitPlan& p) const {   // every array ended exactly where the plan said it would
+        return n_sph == p.size[ZR_PRIM_SPHERE] && n_tri == p.size[ZR_PRIM_TRIANGLE] && n_cube == p.size[ZR_PRIM_CUBE] && n_media == p.size[ZR_PRIM_MEDIUM];
     }
 
     // ---- the serial walk: pair numbers in pre-order, leaf ranges per kind, in the order a depth-first emit would visit them ----
@@ -703,11 +832,8 @@ struct Flattener {
         return std::max(nk, nk ? nk - 1 + best : 0u);
     }
     uint32_t stack_demand() const { return demand_of(root.ref); }
-    void run() {
-        const bool stats = std::getenv("ZR_COMMIT_STATS") != nullptr;
-        auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        double t_ph = now_s();
-        auto ph = [&](const char* what) { if (stats) { const double t = now_s(); std::fprintf(stderr, "[zr] flatten: %-18s %.1f ms\n", what, (t - t_ph) * 1e3); t_ph = t; } };
+    int run() {   // the world's flattener (needs `commit_plan`)
+        PhaseTimer ph{"flatten", 18};
         {
             unsigned hw = std::thread::hardware_concurrency();
             if (const char* e = std::getenv("ZR_BVH_THREADS")) hw = (unsigned)std::max(1, std::atoi(e));
@@ -716,37 +842,22 @@ struct Flattener {
         if (threads > 1 && br.nodes.size() > 65536) pool.reset(new Pool(threads - 1));
         struct Unpool { std::unique_ptr<Pool>& p; ~Unpool() { p.reset(); } } unpool{pool};   // the workers end with run()
         leaf_first.allocate(br.nodes.size());   // fresh pages: zero
-        if (baked) for (uint8_t b : *baked) if (b) n_baked++;
         if (br.nodes.empty()) {
             pairs.allocate(1); empty_child(0, 0); empty_child(0, 1);
             for (int k = 0; k < 4; k++) root.ref[k] = ZR_REF_EMPTY;
-            return;
+            return ZR_OK;
         }
         // 1. indices
         pair_of.allocate(br.nodes.size());
         if (br.nodes[0].count) { leaf_first[0] = 0; cnt[br.nodes[0].kind & 7] = br.nodes[0].count; leaves.push_back(0); }   // the whole world fits one leaf
         else index_nodes();
         ph("index pass");
-        // 2. array sizes: the leaf ranges, then the primitives inside media and wrapper chains
-        size_t x_sph = 0, x_tri = 0, x_cube = 0, x_media = 0;
-        auto count_inner = [&](uint32_t type, uint32_t idx, auto&& self) -> void {
-            if (type == ZR_PRIM_SPHERE) x_sph++; else if (type == ZR_PRIM_TRIANGLE) x_tri++; else if (type == ZR_PRIM_CUBE) x_cube++;
-            else { x_media++; self(s.media[idx].boundary_type, s.media[idx].boundary_index, self); }
-        };
-        const bool any_compound = cnt[ZR_PRIM_MEDIUM] + cnt[ZR_KIND_WRAPPED] != 0;   // (a million-leaf scan for nothing otherwise)
-        if (any_compound) for (int32_t lf : leaves) {
-            const zr::BuildNode& n = br.nodes[lf];
-            if (n.kind != ZR_PRIM_MEDIUM && n.kind != ZR_KIND_WRAPPED) continue;
-            for (uint32_t k = 0; k < n.count; k++) {
-                const zr_object& o = objs[br.order[n.first + k]];
-                if (n.kind == ZR_PRIM_MEDIUM) count_inner(s.media[o.index].boundary_type, s.media[o.index].boundary_index, count_inner);
-                else count_inner(o.type, o.index, count_inner);
-            }
-        }
-        n_sph = cnt[ZR_PRIM_SPHERE]; n_tri = cnt[ZR_PRIM_TRIANGLE]; n_cube = cnt[ZR_PRIM_CUBE]; n_pcube = cnt[ZR_KIND_PCUBE];
-        n_media = cnt[ZR_PRIM_MEDIUM]; n_wrapped = cnt[ZR_KIND_WRAPPED];
+        // 2. the arrays at the plan's sizes; what the walk counted must be what the plan classified
+        for (int k = 0; k < 8; k++)
+            if (cnt[k] != commit_plan->cnt[k]) return fail(ZR_E_DEVICE, "flattener: %u leaf objects of kind %d, the plan has %u (internal error)", cnt[k], k, commit_plan->cnt[k]);
+        allocate_arrays(*commit_plan);
         size_t run_pair_total = 0;
-        if (runs) for (size_t g = 0; g < runs->size(); g++) { x_tri += s.groups[g].triangle_count; run_pair_total += run_pairs((*runs)[g]); }
+        if (runs) for (size_t g = 0; g < runs->size(); g++) run_pair_total += run_pairs((*runs)[g]);
         insts.allocate(cnt[ZR_KIND_INSTANCE]); inst_group.assign(cnt[ZR_KIND_INSTANCE], 0);
         const size_t main_pairs = std::max<size_t>(1, inner.size());
         pairs.allocate(main_pairs + run_pair_total);
@@ -755,15 +866,7 @@ struct Flattener {
             size_t at = main_pairs;
             for (size_t g = 0; g < runs->size(); g++) { run_root[g] = (uint32_t)at; at += run_pairs((*runs)[g]); }
         }
-        spheres.allocate((n_sph + x_sph) * 4); sphere_mat.allocate(n_sph + x_sph);
-        tri_v.allocate((n_tri + x_tri) * ZR_TRI_STRIDE); tri_s.allocate((n_tri + x_tri) * 20);
-        cubes.allocate((n_cube + x_cube) * 6); cube_mat.allocate(n_cube + x_cube);
-        pcubes.allocate(n_pcube * ZR_PCUBE_STRIDE); pcube_mat.allocate(n_pcube);
-        media.allocate(n_media + x_media); wrapped.allocate(n_wrapped);
-        if (want_src) {
-            const size_t sz[8] = {n_sph + x_sph, n_tri + x_tri, n_cube + x_cube, n_media + x_media, n_wrapped, n_pcube, cnt[ZR_KIND_INSTANCE], 0};
-            for (int k = 0; k < 8; k++) src[k].assign(sz[k], 0xFFFFFFFFu);
-        }
+        if (want_src) for (int k = 0; k < 8; k++) src[k].assign(commit_plan->size[k], 0xFFFFFFFFu);
         // 3. leaf primitives of the plain kinds: all threads
         parallel_for(leaves.size(), 2048, [&](size_t a, size_t b) {
             for (size_t i = a; i < b; i++) {
@@ -777,23 +880,14 @@ struct Flattener {
         });
         if (runs) for (size_t g = 0; g < runs->size(); g++) emit_run((uint32_t)g, run_root[g]);   // serial: runs are shared, hence few
         ph("primitive records");
-        // media and wrapped objects, with what they contain: serial, in emit order
-        if (any_compound) for (int32_t lf : leaves) {
+        std::vector<Compound> todo;   // media and wrapped objects, in emit order
+        if (cnt[ZR_PRIM_MEDIUM] + cnt[ZR_KIND_WRAPPED]) for (int32_t lf : leaves) {   // (a million-leaf scan for nothing otherwise)
             const zr::BuildNode& n = br.nodes[lf];
             if (n.kind != ZR_PRIM_MEDIUM && n.kind != ZR_KIND_WRAPPED) continue;
-            for (uint32_t k = 0; k < n.count; k++) {
-                const zr_object& o = objs[br.order[n.first + k]];
-                const size_t di = (size_t)leaf_first[lf] + k;
-                note_src(n.kind, di, br.order[n.first + k]);
-                if (n.kind == ZR_PRIM_MEDIUM) put_medium(di, o.index);
-                else {
-                    zr::DWrapped w{};
-                    w.type = o.type; w.chain_first = o.chain_first; w.chain_count = o.chain_count;
-                    w.index = append_inner(o.type, o.index);
-                    wrapped[di] = w;
-                }
-            }
+            for (uint32_t k = 0; k < n.count; k++) todo.push_back({n.kind, leaf_first[lf] + k, br.order[n.first + k]});
         }
+        finish_compounds(todo);
+        if (!filled(*commit_plan)) return fail(ZR_E_DEVICE, "flattener: the primitive arrays do not add up to the plan's sizes (internal error)");
         ph("media / wrapped");
         if (after_primitives) after_primitives();   // the primitive arrays are final: their upload can run beside the rest
         // 4. pair records: all threads
@@ -808,6 +902,7 @@ struct Flattener {
         number_quads(0);
         ph("4-wide numbering");
         if (runs) { emit_run_quads(); ph("groups' 4-wide nodes"); }
+        return ZR_OK;
     }
     // The 4-wide quantised nodes of every group, behind the world's own: planned and numbered by a flattener of the group's tree
     // (same collapse, same quantisation; its root is a stored node, not kernel arguments), then copied with the indices moved —
@@ -857,5 +952,58 @@ struct Flattener {
         empty_child(0, 1);
     }
 };
+
+// ---- the host builder's CPU half: the groups' trees, the world's boxes, the binned-SAH tree over them and the flattener, ready to run() ----
+struct HostBuild {   // lives on the heap (the flattener refers to its neighbours) and is freed, with everything in it, off the caller's clock
+    std::shared_ptr<const CommitPlan> plan;
+    std::vector<zr::BuildResult> runs;    // two-level BVH: every group of triangles gets a tree of its own, in its own space, once — however many objects place it
+    std::vector<zr::BuildBox> group_box, boxes;
+    std::vector<uint32_t> kinds;          // the plan's classification in the form zr::build_bvh reads
+    zr::BuildResult br;
+    std::unique_ptr<Flattener> fl;
+};
+inline int build_host_tree(const SceneInput& s, std::shared_ptr<const CommitPlan> plan, PhaseTimer& ph, HostBuild& hb) {
+    const std::vector<zr_object>& objs = plan->objs;
+    const BuildKnobs& kn = plan->kn;
+    hb.plan = plan; hb.runs.resize(s.groups.size()); hb.group_box.resize(s.groups.size());
+    Boxer tri_boxer{s};
+    const double ck_tri[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+    for (size_t g = 0; g < s.groups.size(); g++) {
+        const zr_group& grp = s.groups[g];
+        std::vector<zr::BuildBox> tb(grp.triangle_count);
+        std::vector<uint32_t> tk(grp.triangle_count, ZR_PRIM_TRIANGLE);
+        zr::BuildBox all; for (int a = 0; a < 3; a++) { all.lo[a] = kInf; all.hi[a] = -kInf; }
+        for (uint32_t k = 0; k < grp.triangle_count; k++) {
+            tb[k] = tri_boxer.prim(ZR_PRIM_TRIANGLE, grp.first_triangle + k);
+            for (int a = 0; a < 3; a++) { all.lo[a] = std::fmin(all.lo[a], tb[k].lo[a]); all.hi[a] = std::fmax(all.hi[a], tb[k].hi[a]); }
+        }
+        hb.group_box[g] = all;
+        zr::build_bvh(tb, tk, 4, ZR_STACK_DEPTH - 2, 1.0, ck_tri, hb.runs[g]);
+        if (hb.runs[g].max_depth >= ZR_STACK_DEPTH - 1) return fail(ZR_E_INVALID, "group %zu: BVH depth %d exceeds the traversal stack", g, hb.runs[g].max_depth);
+    }
+    Boxer boxer{s, &hb.group_box};
+    hb.boxes.resize(objs.size()); hb.kinds.resize(objs.size());
+    std::atomic<size_t> bad_box{(size_t)-1};
+    parallel_split(objs.size(), [&](size_t k0, size_t k1) {
+        for (size_t k = k0; k < k1; k++) {
+            const zr_object& o = objs[k];
+            hb.boxes[k] = boxer.chain(o.type, o.index, o.chain_first, o.chain_count);
+            hb.kinds[k] = plan->kind(k);
+            for (int a = 0; a < 3; a++)
+                if (!std::isfinite(hb.boxes[k].lo[a]) || !std::isfinite(hb.boxes[k].hi[a])) { size_t want = (size_t)-1; bad_box.compare_exchange_strong(want, k); }
+        }
+    });
+    if (bad_box.load() != (size_t)-1) return fail(ZR_E_INVALID, "object %zu has a non-finite bounding box", bad_box.load());
+    ph("boxes");
+    zr::build_bvh(hb.boxes, hb.kinds, kn.max_leaf, ZR_STACK_DEPTH - 2, kn.ct, kn.ck, hb.br, kn.leaf_cap);
+    ph("binned-SAH build");
+    if (hb.br.max_depth >= ZR_STACK_DEPTH - 1) return fail(ZR_E_INVALID, "BVH depth %d exceeds the traversal stack", hb.br.max_depth);
+    hb.fl.reset(new Flattener{s, objs, hb.br});
+    hb.fl->commit_plan = plan.get();
+    hb.fl->runs = hb.runs.empty() ? nullptr : &hb.runs;
+    hb.fl->open_ratio = kn.open_ratio;
+    hb.fl->want_src = true;
+    return ZR_OK;
+}
 
 }  // namespace

@@ -1,6 +1,8 @@
 // zr_host_internal.h — what the host-side translation units of libzr_hip.so share (round 4: zr_host.cpp was one 2 482-line file):
 //   zr_host.cpp    context life cycle, error string, small C-ABI entry points
-//   zr_commit.cpp  scene setters, validation, zr_scene_commit through the host builder or the device builder (zr_flatten.h: the flattener)
+//   zr_commit.cpp  scene setters, the commit plan, zr_scene_commit through the host builder or the device builder (zr_flatten.h: validation, the plan, the
+//                  flattener and the host builder's CPU half — no HIP, built on zr_scene_input.h: the world as given)
+//   zr_scene_query.cpp  what a committed scene answers: statistics, kernel builds, traversal stack, builder, zr_scene_tree_boxes
 //   zr_render.cpp  camera frame / sky constants, the frame job every render entry prepares (tile plan, validation) and its drivers (streaming pipeline, fused
 //                  kernel, pixel-group kernel), AOV / split passes, post stack, known-answer entry points
 // Plain C++ (host compiler, -ffp-contract=off so that the camera frame and the sky constants are computed with exactly the reference's operation order,
@@ -9,38 +11,9 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
-#include <algorithm>
-#include <array>
-#include <chrono>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <limits>
-#include <condition_variable>
-#include <memory>
-#include <mutex>
-#include <atomic>
-#include <string>
-#include <thread>
-#include <type_traits>
-#include <vector>
-
-#include "../../include/zr_capi.h"
 #include "zr_build.h"
-#include "zr_bvh.h"
-#include "zr_device_types.h"
+#include "zr_scene_input.h"
 #include "zr_launch.h"
-
-namespace zr_host {
-int fail(int code, const char* fmt, ...);          // sets the calling thread's zr_last_error() text, returns `code`
-const char* last_error();
-double env_double(const char* name, double dflt);  // a number from the environment (development switches), `dflt` when unset
-}
-using zr_host::fail;
-using zr_host::env_double;
 
 #define HIP_OK(expr)                                                                                         \
     do {                                                                                                     \
@@ -50,7 +23,6 @@ using zr_host::env_double;
 
 namespace zr_host {
 
-const double kInf = std::numeric_limits<double>::infinity();
 const double kPi = 3.14159265358979323846;
 
 struct H3 { double x, y, z; };
@@ -153,39 +125,12 @@ struct zr_ctx {
     void drain_trash() { std::lock_guard<std::mutex> lk(trash_m); if (trash.joinable()) trash.join(); }
 };
 
-// one input array of a scene: the library's own copy (zr_scene_set_*) or a view of the caller's memory (zr_scene_set_all_borrowed)
-template <class T>
-struct HostArray {
-    const T* p = nullptr; size_t n = 0;
-    std::vector<T> own;
-    void copy(const T* src, size_t count) { own.assign(src, src + count); p = own.data(); n = count; }
-    void borrow(const T* src, size_t count) { std::vector<T>().swap(own); p = src; n = count; }
-    void drop() { std::vector<T>().swap(own); p = nullptr; n = 0; }
-    const T& operator[](size_t i) const { return p[i]; }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-    const T* data() const { return p; }
-    const T* begin() const { return p; }
-    const T* end() const { return p + n; }
-};
-
-struct zr_scene {
+struct zr_scene : SceneInput {   // the world as given (host side), then what the commit made of it
     zr_ctx* ctx = nullptr;
     int device = 0;               // the context's device ordinal, kept here so that zr_scene_destroy needs no live context (a scene may outlive its context)
-    // host side of the world as given: copies, or borrowed views until the commit
-    HostArray<double> spheres, tri_v, tri_n, cubes;
-    HostArray<uint32_t> sphere_mat, tri_mat, cube_mat;
-    HostArray<zr_medium> media;
-    HostArray<zr_xform_op> ops;
-    HostArray<zr_object> objects;
-    bool objects_set = false;
-    std::vector<zr_group> groups;   // runs of triangles that ZR_PRIM_GROUP objects place (small: copied)
     bool borrowed = false;        // the geometry arrays are the caller's (released after the commit)
     bool released = false;        // ... and have been released: the scene cannot be committed again without new input
     unsigned reset_mask = 0;      // ... which geometry arrays have been given again since (SET_* bits, zr_commit.cpp: GEOMETRY_SET)
-    std::vector<zr_material> materials;
-    std::vector<zr_texture> textures;
-    HostArray<unsigned char> texels;
     // device
     bool committed = false;
     DevBuf<zr::NodePair> d_nodes;
@@ -212,12 +157,10 @@ struct zr_scene {
                                          // 0xFFFFFFFF for the primitives inside media and wrapper chains
 };
 
-struct CommitSummary {   // what the shared end of a commit needs to know about the tree either builder produced
+struct CommitSummary {   // what the shared end of a commit needs to know about the tree either builder produced (counts and array sizes: the CommitPlan's)
     zr::NodeF root{}; bool quant_ok = true;
-    size_t n_pairs = 0, n_quads = 0, n_sph = 0, n_tri = 0, n_cube = 0, n_pcube = 0, n_media = 0, n_wrapped = 0, n_insts = 0, kept_closed = 0;
-    bool plain_media = true;
-    uint32_t stack_demand = 0; int quad_depth = 0, max_depth = 0, max_leaf = 4;
-    uint32_t leaf_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // leaf objects per kind
+    size_t n_pairs = 0, n_quads = 0, kept_closed = 0;
+    bool plain_media = true;   // every medium's boundary is an unwrapped sphere or cube
+    uint32_t stack_demand = 0; int quad_depth = 0, max_depth = 0;
     const char* builder = "";
 };
-// the tables every scene has (ops, materials, textures), the DScene the kernels receive, the EXTEND build the world needs

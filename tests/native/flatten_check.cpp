@@ -1,0 +1,176 @@
+// Host-side check of the host commit's CPU half (raytracer_project_amd/csrc/zr_flatten.h over zr_bvh.cpp): world list, validation, commit plan, boxes,
+// binned-SAH tree, Flattener::run — no HIP.  Compiled and run by tests/test_flatten_native.py.
+//   flatten_check <world> <seed>     world: zero | one | five | mixed | big
+// Prints one JSON line: an FNV-1a hash of every output array (the same for every ZR_BVH_THREADS) and validity flags.
+#include "zr_flatten.h"
+
+namespace zr_host {
+static thread_local std::string g_err;
+int fail(int code, const char* fmt, ...) { char buf[1024]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap); g_err = buf; return code; }
+const char* last_error() { return g_err.c_str(); }
+double env_double(const char* name, double dflt) { const char* v = std::getenv(name); return v && *v ? std::atof(v) : dflt; }
+}
+
+static uint64_t rng_state = 1;
+static double u01() {   // splitmix64
+    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
+    return (double)(z >> 11) * (1.0 / 9007199254740992.0);
+}
+
+struct World {
+    std::vector<double> sph, tv, tn, cubes;
+    std::vector<uint32_t> sph_mat, tmat, cmat;
+    std::vector<zr_medium> media; std::vector<zr_xform_op> ops; std::vector<zr_object> objs; std::vector<zr_group> groups;
+    double at[3] = {0, 0, 0};   // where the next primitive goes
+    void place() { for (double& x : at) x = u01() * 200 - 100; }
+    uint32_t sphere() { for (double x : at) sph.push_back(x); sph.push_back(0.2 + u01()); sph_mat.push_back((uint32_t)(u01() * 4)); return (uint32_t)sph_mat.size() - 1; }
+    uint32_t triangle() {
+        for (int v = 0; v < 3; v++) for (int k = 0; k < 3; k++) { tv.push_back(at[k] + u01() * 2 - 1); tn.push_back(u01() * 2 - 1); }
+        tmat.push_back((uint32_t)(u01() * 4)); return (uint32_t)tmat.size() - 1;
+    }
+    uint32_t cube() {
+        double h[3]; for (double& x : h) x = 0.2 + u01();
+        for (double x : h) cubes.push_back(x);
+        for (double x : at) cubes.push_back(x);
+        for (int k = 0; k < 3; k++) cubes.push_back(at[k] - h[k]);
+        for (int k = 0; k < 3; k++) cubes.push_back(at[k] + h[k]);
+        cmat.push_back((uint32_t)(u01() * 4)); return (uint32_t)cmat.size() - 1;
+    }
+    static zr_xform_op op(uint32_t kind, double a0 = 0, double a1 = 0, double a2 = 0, uint32_t mat = 0) { zr_xform_op o{}; o.kind = kind; o.mat = mat; o.a[0] = a0; o.a[1] = a1; o.a[2] = a2; return o; }
+    static zr_xform_op translate() { return op(ZR_OP_TRANSLATE, u01() * 10 - 5, u01() * 10 - 5, u01() * 10 - 5); }
+    static zr_xform_op rotate(uint32_t kind) { const double a = u01() * 6.28; return op(kind, std::sin(a), std::cos(a)); }
+    static zr_xform_op material() { return op(ZR_OP_MATERIAL, 0, 0, 0, (uint32_t)(u01() * 4)); }
+    void add(uint32_t type, uint32_t index, std::initializer_list<zr_xform_op> chain = {}) {   // a world-list entry, outermost wrapper first
+        objs.push_back({type, index, (uint32_t)ops.size(), (uint32_t)chain.size()});
+        ops.insert(ops.end(), chain.begin(), chain.end());
+    }
+    uint32_t medium(uint32_t btype, uint32_t bindex, std::initializer_list<zr_xform_op> chain = {}) {
+        zr_medium m{}; m.boundary_type = btype; m.boundary_index = bindex; m.chain_first = (uint32_t)ops.size(); m.chain_count = (uint32_t)chain.size(); m.mat = 3; m.neg_inv_density = -1.0 / (0.1 + u01());
+        ops.insert(ops.end(), chain.begin(), chain.end());
+        media.push_back(m); return (uint32_t)media.size() - 1;
+    }
+    uint32_t group(uint32_t n) { at[0] = at[1] = at[2] = 0; const uint32_t first = (uint32_t)tmat.size(); for (uint32_t k = 0; k < n; k++) triangle(); groups.push_back({first, n}); return (uint32_t)groups.size() - 1; }
+    void mixed_entry(uint32_t i) {
+        place();
+        const double f = 0.5 + u01();
+        switch (i % 16) {
+            case 0: case 1: case 2: add(ZR_PRIM_SPHERE, sphere()); break;
+            case 3: case 4: case 5: add(ZR_PRIM_TRIANGLE, triangle()); break;
+            case 6: add(ZR_PRIM_CUBE, cube()); break;
+            case 7: add(ZR_PRIM_CUBE, cube(), {translate()}); break;                                                        // placed cubes ...
+            case 8: add(ZR_PRIM_CUBE, cube(), {material(), translate(), rotate(ZR_OP_ROTATE_Y)}); break;
+            case 9: add(ZR_PRIM_CUBE, cube(), {translate(), op(ZR_OP_SCALE, f, 1.5, 0.7)}); break;
+            case 10: add(ZR_PRIM_CUBE, cube(), {translate(), rotate(ZR_OP_ROTATE_Y), op(ZR_OP_SCALE, f, f, 2)}); break;
+            case 11: add(ZR_PRIM_SPHERE, sphere(), {translate(), material(), op(ZR_OP_SCALE, f, f, f)}); break;           // baked sphere
+            case 12: add(ZR_PRIM_SPHERE, sphere(), {rotate(ZR_OP_ROTATE_X)}); break;                                        // wrapped
+            case 13: add(ZR_PRIM_TRIANGLE, triangle(), {op(ZR_OP_SCALE, f, 1, 1)}); break;                                  // wrapped
+            case 14: add(ZR_PRIM_TRIANGLE, triangle(), {translate(), rotate(ZR_OP_ROTATE_Z), material()}); break;          // baked triangle
+            default:
+                switch ((i / 16) % 6) {
+                    case 0: add(ZR_PRIM_MEDIUM, medium(ZR_PRIM_SPHERE, sphere())); break;                                  // plain medium
+                    case 1: add(ZR_PRIM_MEDIUM, medium(ZR_PRIM_CUBE, cube(), {translate(), rotate(ZR_OP_ROTATE_Y)})); break;   // its boundary carries a chain
+                    case 2: add(ZR_PRIM_MEDIUM, medium(ZR_PRIM_CUBE, cube()), {translate()}); break;                       // a medium inside a wrapper chain
+                    case 3: add(ZR_PRIM_SPHERE, sphere(), {material(), material()}); break;                                // material-only chains
+                    case 4: add(ZR_PRIM_CUBE, cube(), {material()}); break;
+                    default: add(ZR_PRIM_CUBE, cube(), {rotate(ZR_OP_ROTATE_Z), translate()}); break;                      // a cube that is not a placed one: wrapped
+                }
+        }
+    }
+};
+
+static unsigned long long fnv(const void* p, size_t bytes) {
+    unsigned long long x = 1469598103934665603ull;
+    for (size_t i = 0; i < bytes; i++) { x ^= ((const unsigned char*)p)[i]; x *= 1099511628211ull; }
+    return x;
+}
+
+int main(int argc, char** argv) {
+    const std::string world = argc > 1 ? argv[1] : "mixed";
+    rng_state = argc > 2 ? (uint64_t)std::atoll(argv[2]) : 1;
+    World w;
+    bool explicit_list = true;
+    if (world == "zero") explicit_list = false;
+    else if (world == "one") { w.place(); w.add(ZR_PRIM_SPHERE, w.sphere()); }
+    else if (world == "five") {   // one of each ZR_PRIM_* type
+        const uint32_t g = w.group(3);
+        w.place(); w.add(ZR_PRIM_SPHERE, w.sphere()); w.place(); w.add(ZR_PRIM_TRIANGLE, w.triangle()); w.place(); w.add(ZR_PRIM_CUBE, w.cube());
+        w.place(); w.add(ZR_PRIM_MEDIUM, w.medium(ZR_PRIM_SPHERE, w.sphere())); w.add(ZR_PRIM_GROUP, g, {World::translate()});
+    } else if (world == "mixed") {   // ~3000 entries: every classification, groups of 13, 200 and (a single leaf) 3 triangles placed five times each
+        const uint32_t g[3] = {w.group(13), w.group(200), w.group(3)};
+        for (uint32_t i = 0; i < 2985; i++) w.mixed_entry(i);
+        for (int k = 0; k < 15; k++) w.add(ZR_PRIM_GROUP, g[k % 3], {World::translate(), World::rotate(ZR_OP_ROTATE_Y), World::material()});
+    } else if (world == "big") {   // 140 000 bare triangles and spheres through the implicit world list: beyond the 65 536 where the thread split and the worker pool start
+        explicit_list = false;
+        for (uint32_t i = 0; i < 140000; i++) { w.place(); if (i % 3) w.triangle(); else w.sphere(); }
+    } else { std::fprintf(stderr, "unknown world %s\n", world.c_str()); return 2; }
+
+    SceneInput in;
+    in.spheres.copy(w.sph.data(), w.sph.size()); in.sphere_mat.copy(w.sph_mat.data(), w.sph_mat.size());
+    in.tri_v.copy(w.tv.data(), w.tv.size()); in.tri_n.copy(w.tn.data(), w.tn.size()); in.tri_mat.copy(w.tmat.data(), w.tmat.size());
+    in.cubes.copy(w.cubes.data(), w.cubes.size()); in.cube_mat.copy(w.cmat.data(), w.cmat.size());
+    in.media.copy(w.media.data(), w.media.size()); in.ops.copy(w.ops.data(), w.ops.size());
+    in.objects.copy(w.objs.data(), w.objs.size()); in.objects_set = explicit_list && !w.objs.empty();
+    in.groups = w.groups;
+    zr_texture tex{}; tex.kind = ZR_TEX_SOLID; in.textures.push_back(tex);
+    for (int k = 0; k < 4; k++) { zr_material m{}; m.kind = k == 3 ? ZR_MAT_ISOTROPIC : ZR_MAT_LAMBERTIAN; m.bump_tex = ZR_NO_TEXTURE; in.materials.push_back(m); }
+
+    std::vector<zr_object> objs = world_list(in);
+    if (validate(in, objs)) { std::fprintf(stderr, "validate: %s\n", zr_host::last_error()); return 2; }
+    std::shared_ptr<const CommitPlan> plan = make_plan(in, std::move(objs));
+    PhaseTimer ph{"commit", 22};
+    HostBuild hb;
+    if (build_host_tree(in, plan, ph, hb) || hb.fl->run()) { std::fprintf(stderr, "host build: %s\n", zr_host::last_error()); return 2; }
+    const Flattener& fl = *hb.fl;
+    const size_t* z = plan->size;
+    const size_t n = plan->objs.size();
+
+    // every world-list entry exactly once in the leaf range of its kind's src, the groups' triangles once each behind the leaf triangles, 0xFFFFFFFF behind those
+    bool once = true, inner_unset = true;
+    {
+        std::vector<uint32_t> want[8], got[8];
+        for (size_t k = 0; k < n; k++) { const uint32_t kind = plan->kind(k); want[kind].push_back(kind == ZR_KIND_WRAPPED || kind == ZR_KIND_INSTANCE ? (uint32_t)k : plan->objs[k].index); }
+        for (const zr_group& g : in.groups) for (uint32_t k = 0; k < g.triangle_count; k++) want[ZR_PRIM_TRIANGLE].push_back(g.first_triangle + k);
+        for (int k = 0; k < 8; k++) {
+            const size_t leaf_end = std::min(fl.src[k].size(), z[k] - plan->inner[k]);
+            got[k].assign(fl.src[k].begin(), fl.src[k].begin() + leaf_end);
+            for (size_t i = leaf_end; i < fl.src[k].size(); i++) if (fl.src[k][i] != 0xFFFFFFFFu) inner_unset = false;
+            std::sort(want[k].begin(), want[k].end()); std::sort(got[k].begin(), got[k].end());
+            if (want[k] != got[k]) once = false;
+        }
+    }
+    bool sizes = fl.spheres.size() == z[ZR_PRIM_SPHERE] * ZR_SPHERE_DOUBLES && fl.sphere_mat.size() == z[ZR_PRIM_SPHERE] && fl.tri_v.size() == z[ZR_PRIM_TRIANGLE] * ZR_TRI_STRIDE &&
+                 fl.tri_s.size() == z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES && fl.cubes.size() == z[ZR_PRIM_CUBE] * ZR_CUBE_DOUBLES && fl.cube_mat.size() == z[ZR_PRIM_CUBE] &&
+                 fl.pcubes.size() == z[ZR_KIND_PCUBE] * ZR_PCUBE_STRIDE && fl.pcube_mat.size() == z[ZR_KIND_PCUBE] && fl.media.size() == z[ZR_PRIM_MEDIUM] &&
+                 fl.wrapped.size() == z[ZR_KIND_WRAPPED] && fl.insts.size() == z[ZR_KIND_INSTANCE] && (n == 0 || fl.filled(*plan));
+    for (int k = 0; k < 8; k++) if (n && fl.src[k].size() != z[k]) sizes = false;
+    bool compound = true;
+    for (const zr::DWrapped& x : fl.wrapped) if (x.type > ZR_PRIM_MEDIUM || x.index >= z[x.type]) compound = false;
+    for (const zr::DMedium& m : fl.media) if (m.btype > ZR_PRIM_CUBE || m.bindex >= z[m.btype]) compound = false;
+    bool refs = true;
+    auto leaf_ok = [&](uint32_t kind, size_t first, size_t count) { return kind < 7 && count > 0 && first + count <= z[kind]; };
+    auto quad_refs = [&](const uint32_t ref[4]) {
+        for (int k = 0; k < 4; k++) {
+            if (ref[k] == ZR_REF_EMPTY) continue;
+            if (ref[k] & ZR_REF_LEAF) { if (!leaf_ok((ref[k] >> 28) & 7u, ref[k] & 0xFFFFFFu, ((ref[k] >> 24) & 15u) + 1u)) refs = false; }
+            else if (ref[k] >= fl.quads.size()) refs = false;
+        }
+    };
+    quad_refs(fl.root.ref);
+    for (const zr::NodeQ& q : fl.quads) quad_refs(q.ref);
+    for (const zr::NodePair& p : fl.pairs) for (int c = 0; c < 2; c++) {
+        if (p.meta[c] == 0) { if (p.child[c] >= fl.pairs.size()) refs = false; }
+        else if ((p.meta[c] & 0xFFFFu) && !leaf_ok((p.meta[c] >> 16) - 1, p.child[c], p.meta[c] & 0xFFFFu)) refs = false;
+    }
+    const bool valid = once && inner_unset && sizes && compound && refs;
+
+    auto h = [](const auto& a) { return a.size() ? fnv(a.data(), a.size() * sizeof(a[0])) : fnv(nullptr, 0); };
+    std::printf("{\"world\": \"%s\", \"n\": %zu, \"valid\": %s, \"once\": %s, \"inner_unset\": %s, \"sizes\": %s, \"compound\": %s, \"refs\": %s, ", world.c_str(), n, valid ? "true" : "false",
+                once ? "true" : "false", inner_unset ? "true" : "false", sizes ? "true" : "false", compound ? "true" : "false", refs ? "true" : "false");
+    std::printf("\"pairs\": \"%016llx\", \"quads\": \"%016llx\", \"root\": \"%016llx\", \"spheres\": \"%016llx\", \"sphere_mat\": \"%016llx\", \"tri_v\": \"%016llx\", \"tri_s\": \"%016llx\", ",
+                h(fl.pairs), h(fl.quads), fnv(&fl.root, sizeof fl.root), h(fl.spheres), h(fl.sphere_mat), h(fl.tri_v), h(fl.tri_s));
+    std::printf("\"cubes\": \"%016llx\", \"cube_mat\": \"%016llx\", \"pcubes\": \"%016llx\", \"pcube_mat\": \"%016llx\", \"media\": \"%016llx\", \"wrapped\": \"%016llx\", \"insts\": \"%016llx\", \"src\": [",
+                h(fl.cubes), h(fl.cube_mat), h(fl.pcubes), h(fl.pcube_mat), h(fl.media), h(fl.wrapped), h(fl.insts));
+    for (int k = 0; k < 7; k++) std::printf("\"%016llx\"%s", h(fl.src[k]), k < 6 ? ", " : "]}\n");
+    return valid ? 0 : 1;
+}

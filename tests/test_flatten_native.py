@@ -1,0 +1,40 @@
+"""The host commit's CPU half (raytracer_project_amd/csrc/zr_flatten.h: world list, validation, commit plan, boxes, then zr_bvh.cpp's tree and
+Flattener::run) on its own: a small C++ checker (tests/native/flatten_check.cpp) is compiled against the headers and zr_bvh.cpp with g++ — no HIP
+library — and run on synthetic worlds.  What must hold is that the arrays are VALID (every world-list entry exactly once in the leaf range of its
+kind, the primitives inside media and wrapper chains behind those ranges, every array filled to the plan's size, every reference inside its array)
+and DETERMINISTIC: the same bytes for every number of threads."""
+import json
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "raytracer_project_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("flatten") / "flatten_check")
+    subprocess.run(["g++", "-std=c++20", "-O2", "-pthread", "-ffp-contract=off", "-I", CSRC, "-o", out, os.path.join(ROOT, "tests", "native", "flatten_check.cpp"),
+                    os.path.join(CSRC, "zr_bvh.cpp")], check=True)
+    return out
+
+
+def run(checker, world, threads):
+    p = subprocess.run([checker, world, "11"], env=dict(os.environ, ZR_BVH_THREADS=str(threads)), capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+# zero / one (the whole world is one leaf) / five (one of each ZR_PRIM_* type) / mixed (3000 entries of every classification, media, wrapped objects,
+# three groups placed five times each) / big (140 000 bare triangles and spheres: past the 65 536 where the thread split and the worker pool start)
+@pytest.mark.parametrize("world,n", [("zero", 0), ("one", 1), ("five", 5), ("mixed", 3000), ("big", 140000)])
+def test_arrays_are_valid_and_independent_of_thread_count(checker, world, n):
+    ref = run(checker, world, 1)
+    assert ref["n"] == n
+    assert ref["valid"] and ref["once"] and ref["inner_unset"] and ref["sizes"] and ref["compound"] and ref["refs"], ref
+    for threads in (2, 8):
+        got = run(checker, world, threads)
+        assert got == ref, (threads, got, ref)

@@ -1362,3 +1362,32 @@ def test_rows_done_after_a_batch(which, built, monkeypatch):
         sc.close()
     finally:
         c.close()
+
+
+@pytest.mark.parametrize("name", ["mix0", "mix1", "inst0", "inst2"])
+def test_builders_agree_on_what_does_not_depend_on_the_tree(name, ctx):
+    """Both builders commit the same world (each with ZR_BUILD_CHECK=1): the same objects, the same kernel builds, the same leaf primitives — per leaf
+    kind, the caller's indices the leaves of the world's tree name, each once and as many as the world list has entries — and the same material behind 2000
+    fixed camera rays."""
+    ds = demo_scene(name)
+    host, dev = gpu_scene(ctx, name, (), "host"), gpu_scene(ctx, name, (), "device")
+    assert host.stats()["objects"] == dev.stats()["objects"]
+    assert host.kernels() == dev.kernels()
+
+    def leaf_src(sc):
+        b = sc.tree_boxes()
+        leaves = b[(b["leaf"] == 1) & (b["tree"] == 0)]   # the world's tree (a placed run's own tree lists its triangles once per group, not per entry)
+        assert (leaves["count"] <= 4).all()
+        return {int(k): np.sort(np.concatenate([l["src"][:l["count"]] for l in leaves[leaves["kind"] == k]])) for k in np.unique(leaves["kind"])}
+    hs, dv = leaf_src(host), leaf_src(dev)
+    assert hs.keys() == dv.keys()
+    for k in hs:
+        assert np.array_equal(hs[k], dv[k]), (name, k)
+        if k in (4, 6):   # wrapped objects and placed runs are named by their world-list entry: each exactly once
+            assert len(np.unique(hs[k])) == len(hs[k]), (name, k)
+    assert sum(len(v) for v in hs.values()) == host.stats()["objects"]
+    cam = ds.camera.copy()
+    rng = np.random.default_rng(2000)
+    px = np.stack([rng.integers(0, cam.image_width, 2000), rng.integers(0, cam.image_height, 2000), np.zeros(2000, np.int64)], axis=1).astype(np.int32)
+    rays = np.ascontiguousarray(ctx.kat_camera_rays(cam, ds.seed, px)[:, :6])
+    assert np.array_equal(host.trace(rays)["mat"], dev.trace(rays)["mat"])
