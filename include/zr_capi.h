@@ -187,13 +187,16 @@ typedef struct zr_counters {
     uint64_t hits;           /* segments that found a surface / medium event */
     uint64_t rng_draws;      /* main-stream draws */
     /* wave-scheduler statistics of the EXTEND kernel (counting build): executions of the NODE / LEAF phase and the lanes that were
-     * ready at each execution (lanes / (64 * execs) = SIMT utilisation of the phase); shade_* are unused by the pipeline */
+     * ready at each execution (lanes / (64 * execs) = SIMT utilisation of the phase); shade_execs is unused by the pipeline; shade_lanes:
+     * the slots the lean SHADE kernel shaded, i.e. the segments EXTEND traced for it (= segments - escaped); zero on every other build */
     uint64_t node_execs, node_lanes, leaf_execs, leaf_lanes, shade_execs, shade_lanes;
     uint64_t rounds;         /* kernel variant 2: EXTEND/SHADE rounds of the last render */
     double extend_ms, shade_ms; /* kernel variant 2: device time of the EXTEND / SHADE launches of the last render */
     double kernel_ms;        /* device time of the render kernels of the last call (hipEvents) */
     uint64_t path;           /* which kernels rendered the last frame: 0 pixel-group megakernel (fallback), 2 streaming pipeline
                                 (EXTEND / SHADE rounds), 3 fused small-scene kernel (worlds of at most ZR_FUSED_MAX objects) — ABI 3 */
+    uint64_t escaped;        /* kernel variant 2: of `segments`, those the lean SHADE kernel finished itself because the scattered ray provably
+                                leaves the world (never reached EXTEND); 0 with ZR_SHADE_ESCAPE=0 and on every other path */
 } zr_counters;
 
 /* hit record returned by zr_trace (debug / known-answer entry): hit_record, hittable.hpp:9-26 */

@@ -350,6 +350,8 @@ int finish_commit(zr_scene* s, const CommitPlan& plan, const CommitSummary& cs) 
             if (m.kind != ZR_MAT_DIELECTRIC && (m.tex >= s->textures.size() || s->textures[m.tex].kind != ZR_TEX_SOLID)) lean = false;
         }
         d.shade_lean = lean ? 1u : 0u;
+        // ... and its escape stage (zr_stream.hip, stream_shade): on wherever the lean pair runs; ZR_SHADE_ESCAPE=0 switches it off for A/B runs
+        d.shade_escape = lean && env_double("ZR_SHADE_ESCAPE", 1) != 0 ? 1u : 0u;
     }
     s->stack_demand = cs.stack_demand;
     if (std::getenv("ZR_QUANT_STATS")) std::fprintf(stderr, "[zr] 4-wide tree: depth %d, worst-case traversal stack %u entries\n", cs.quad_depth, s->stack_demand);

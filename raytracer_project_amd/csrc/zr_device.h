@@ -168,6 +168,84 @@ __device__ __forceinline__ bool sphere_t(const double* s, const Ray& r, double t
     return true;
 }
 
+// ---- EXTEND's conservative FP32 slab test (derivation and error bound: zr_stream.hip, above stream_extend) --------------------
+// Macros over the names of the code they are expanded in: `ray`, the slab constants idx_ idy_ idz_ / cnx cny cnz / cfx cfy cfz, tbest_f, INFf,
+// COUNT and c_nodes.  stream_extend and ray_escapes (below) share this one definition, so both take the same decision about a box.
+// one child from the parametric distances of its six planes (absolute slack already inside): entry distance or +inf
+#define ZR_SLAB(X0, X1, Y0, Y1, Z0, Z1, RF_IN, TN, RF)                                                      \
+    {                                                                                                       \
+        const float x0 = (X0), x1 = (X1), y0 = (Y0), y1 = (Y1), z0 = (Z0), z1 = (Z1);                       \
+        float n_ = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), 0.000999f));            \
+        float f_ = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), tbest_f));              \
+        n_ = fmaf(fabsf(n_), -9.5367432e-7f, n_);                                                           \
+        f_ = fmaf(fabsf(f_), 9.5367432e-7f, f_);                                                            \
+        const bool empty_ = (RF_IN) == ZR_REF_EMPTY;                                                        \
+        const bool hit_ = (n_ <= f_) && !empty_;                                                            \
+        if (COUNT && !empty_) c_nodes++;                                                                    \
+        TN = hit_ ? n_ : INFf;                                                                              \
+        RF = (RF_IN);                                                                                       \
+    }
+// the slab constants of `ray`
+#define ZR_RAY_CONSTANTS()                                                                                  \
+    {                                                                                                       \
+        const float NANf = __builtin_nanf("");                                                              \
+        idx_ = 1.0f / (float)ray.d.x; idy_ = 1.0f / (float)ray.d.y; idz_ = 1.0f / (float)ray.d.z;            \
+        float ocx = (float)(-ray.o.x * (double)idx_), ocy = (float)(-ray.o.y * (double)idy_), ocz = (float)(-ray.o.z * (double)idz_); \
+        /* 2^100 / 2^120: far inside the float range, so that no product with a plane or a scale overflows */ \
+        if (!(fabsf(idx_) < 1.2676506e30f) || !(fabsf(ocx) < 1.3292280e36f)) { idx_ = 0.0f; ocx = NANf; }    \
+        if (!(fabsf(idy_) < 1.2676506e30f) || !(fabsf(ocy) < 1.3292280e36f)) { idy_ = 0.0f; ocy = NANf; }    \
+        if (!(fabsf(idz_) < 1.2676506e30f) || !(fabsf(ocz) < 1.3292280e36f)) { idz_ = 0.0f; ocz = NANf; }    \
+        /* the ENTRY plane of an axis (the lower one when id > 0) gets the smaller constant, the exit plane the larger one */ \
+        const float sx = fabsf(ocx) * 2.3841858e-7f, sy = fabsf(ocy) * 2.3841858e-7f, sz = fabsf(ocz) * 2.3841858e-7f; \
+        cnx = ocx - sx; cfx = ocx + sx; cny = ocy - sy; cfy = ocy + sy; cnz = ocz - sz; cfz = ocz + sz;      \
+    }
+// the root's FP32 planes (once per ray): lower / upper plane with the constant of the role it plays for this ray
+#define ZR_FBOX(N, C, TN, RF)                                                                               \
+    ZR_SLAB(fmaf((N).lox[C], idx_, idx_ > 0.0f ? cnx : cfx), fmaf((N).hix[C], idx_, idx_ > 0.0f ? cfx : cnx),  \
+            fmaf((N).loy[C], idy_, idy_ > 0.0f ? cny : cfy), fmaf((N).hiy[C], idy_, idy_ > 0.0f ? cfy : cny),  \
+            fmaf((N).loz[C], idz_, idz_ > 0.0f ? cnz : cfz), fmaf((N).hiz[C], idz_, idz_ > 0.0f ? cfz : cnz), (N).ref[C], TN, RF)
+
+// ---- a ray that provably leaves the world (SHADE's escape stage, zr_stream.hip) ----------------------------------------------
+// sphere_miss_certain: true only if sphere_t(s, r, 0.001, tmax, .) is false for every tmax.  With sphere_t's quantities a = |d|^2, h = d.oc,
+// l2 = |oc|^2, c = l2 - r^2 and the margin m = (0.001^2 / 4) a:
+//   h < 0 and c >= 0:  both roots (h -+ sqrt(h^2 - a c)) / a are <= 0;
+//   h < 0 and -m <= c < 0:  the larger root is below sqrt(-c / a) <= 0.0005 (a ray that starts just inside the surface, going outwards);
+//   l2 2^-44 < m:  c's rounding noise (~2^-50 l2, however the multiply-adds of this site and of sphere_t are contracted) stays far below
+//   the margin, so the two sites cannot disagree about which side of 0.001 the root lies on.
+// A NaN makes a comparison false: no cull.  No hit is decided here — only misses; EXTEND stays the one place that finds a hit.
+__host__ __device__ __forceinline__ bool sphere_miss_certain(const double* s, const Ray& r) {
+    const double ox = s[0] - r.o.x, oy = s[1] - r.o.y, oz = s[2] - r.o.z;
+    const double a = r.d.x * r.d.x + r.d.y * r.d.y + r.d.z * r.d.z;
+    const double h = r.d.x * ox + r.d.y * oy + r.d.z * oz;
+    const double l2 = ox * ox + oy * oy + oz * oz;
+    const double c = l2 - s[3] * s[3];
+    const double m = 2.5e-7 * a;
+    return h < 0 && c >= -m && l2 * 5.684341886080802e-14 /* 2^-44 */ < m;
+}
+// ray_escapes: true only if EXTEND would report "no hit" for `ray`: every child of the root is empty, or missed under EXTEND's own slab test
+// (same macros, same constants, tbest = +inf; a NaN slab is dropped, i.e. the box counts as hit), or a leaf of exactly one sphere that
+// sphere_miss_certain rules out.  Any other child whose box is hit keeps the ray for EXTEND.  nodes: the non-empty root boxes tested.
+__host__ __device__ __forceinline__ bool ray_escapes(const Ray& ray, const NodeF& root, const double* spheres, uint32_t& nodes) {
+    const bool COUNT = true;
+    const float INFf = __builtin_huge_valf(), tbest_f = INFf;
+    float idx_, idy_, idz_, cnx, cny, cnz, cfx, cfy, cfz;
+    uint32_t c_nodes = 0;
+    ZR_RAY_CONSTANTS()
+    float tn0, tn1, tn2, tn3;
+    uint32_t r0, r1, r2, r3;
+    ZR_FBOX(root, 0, tn0, r0)
+    ZR_FBOX(root, 1, tn1, r1)
+    ZR_FBOX(root, 2, tn2, r2)
+    ZR_FBOX(root, 3, tn3, r3)
+    nodes = c_nodes;
+    // a child whose box is hit (ZR_SLAB gives an empty one +inf): missed only as a one-sphere leaf — kind ZR_PRIM_SPHERE, count - 1 = 0
+#define ZR_CHILD_MISSED(TN, RF) \
+    (!((TN) < INFf) || ((((RF) & 0xFF000000u) == (ZR_REF_LEAF | ((uint32_t)ZR_PRIM_SPHERE << 28))) && sphere_miss_certain(spheres + (size_t)((RF) & 0xFFFFFFu) * 4, ray)))
+    const bool esc = ZR_CHILD_MISSED(tn0, r0) && ZR_CHILD_MISSED(tn1, r1) && ZR_CHILD_MISSED(tn2, r2) && ZR_CHILD_MISSED(tn3, r3);
+#undef ZR_CHILD_MISSED
+    return esc;
+}
+
 // triangle.hpp:17-57, distance only.  Same decisions as the reference — degenerate (|N| < 1e-8), parallel
 // (|N̂·d| < 1e-8), contains(t) inclusive, the three edge tests N·((v_{k+1}-v_k) x (p-v_k)) >= 0 — evaluated in the
 // algebraically identical scaled-barycentric form, which needs no square root and a single division, and only

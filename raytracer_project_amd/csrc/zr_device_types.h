@@ -89,6 +89,8 @@ struct DScene {
     uint32_t shade_lean; // 1: SHADE may run its lean build (bare triangles / spheres, lambertian / metal / dielectric / light over solid colours, no bump maps)
     uint32_t leaf_cnt[8]; // leaf objects per kind (the first leaf_cnt[k] records of kind k's array): the fused small-scene kernel tests them all
     NodeF root;          // variant 2: the root of the 4-wide tree
+    uint32_t shade_escape; // 1: lean SHADE finishes a scattered ray that provably leaves the world in the round that made it (zr_device.h: ray_escapes).
+                           // Behind `root`, in the struct's tail padding: no other member moves
 };
 
 struct DCamera {

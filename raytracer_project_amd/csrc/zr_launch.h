@@ -13,11 +13,13 @@ struct DCamera;
 struct DEnv;
 
 // The context's counter block (zr_ctx::d_ctr, `gctr` in the kernels): CTR_BLOCK 64-bit words, cleared before every render.  zr_get_counters hands the
-// first CTR_WORDS of them out as zr_counters; an instrumented render (count != 0) fills words 0-12.
+// first CTR_WORDS of them out as zr_counters; an instrumented render (count != 0) fills words 0-12, 14 (lean SHADE) and 15.
 enum { CTR_SAMPLES = 0, CTR_SEGMENTS = 1, CTR_NODES = 2, CTR_SPHERES = 3, CTR_TRIANGLES = 4, CTR_CUBES = 5, CTR_MEDIA = 6, CTR_HITS = 7, CTR_DRAWS = 8,
        CTR_NODE_EXECS = 9, CTR_NODE_LANES = 10, CTR_LEAF_EXECS = 11, CTR_LEAF_LANES = 12,   // EXTEND's iterations per phase and the lanes they ran with
-       CTR_SHADE_EXECS = 13, CTR_SHADE_LANES = 14,   // zr_counters::shade_execs / shade_lanes: no kernel of the product build writes them (zero); see below
-       CTR_WORDS = 16,                               // (word 15 is spare)
+       CTR_SHADE_EXECS = 13, CTR_SHADE_LANES = 14,   // zr_counters::shade_execs / shade_lanes.  shade_execs: no kernel of the product build writes it (zero).  shade_lanes:
+                                                     // the counting lean SHADE adds the slots it shaded, i.e. the segments EXTEND handed it; other builds leave it zero; see below
+       CTR_ESCAPED = 15,                             // segments lean SHADE finished itself (ray_escapes); they are part of CTR_SEGMENTS
+       CTR_WORDS = 16,
        CTR_HIST = 16, CTR_HIST_WORDS = 24,           // ZR_WAVE_PROFILE build only: EXTEND's per-phase lane histograms, [phase][8 buckets of 8 lanes]
        CTR_BLOCK = 48 };
 // A -DZR_WAVE_PROFILE build (scripts/wave_profile.sh) runs uninstrumented renders and REUSES words of the block for EXTEND's wave statistics, read back

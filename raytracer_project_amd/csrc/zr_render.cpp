@@ -1028,9 +1028,9 @@ int zr_get_counters(zr_ctx* c, zr_counters* out) {
     if (c->last_counted || env_double("ZR_RAW_COUNTERS", 0) != 0) {
         out->primary_samples = h[zr::CTR_SAMPLES]; out->segments = h[zr::CTR_SEGMENTS]; out->nodes_tested = h[zr::CTR_NODES]; out->spheres_tested = h[zr::CTR_SPHERES];
         out->triangles_tested = h[zr::CTR_TRIANGLES]; out->cubes_tested = h[zr::CTR_CUBES]; out->media_tested = h[zr::CTR_MEDIA]; out->hits = h[zr::CTR_HITS];
-        out->rng_draws = h[zr::CTR_DRAWS];
+        out->rng_draws = h[zr::CTR_DRAWS]; out->escaped = h[zr::CTR_ESCAPED];
         out->node_execs = h[zr::CTR_NODE_EXECS]; out->node_lanes = h[zr::CTR_NODE_LANES]; out->leaf_execs = h[zr::CTR_LEAF_EXECS]; out->leaf_lanes = h[zr::CTR_LEAF_LANES];
-        out->shade_execs = h[zr::CTR_SHADE_EXECS]; out->shade_lanes = h[zr::CTR_SHADE_LANES];   // filled by a ZR_WAVE_PROFILE build only (zr_launch.h)
+        out->shade_execs = h[zr::CTR_SHADE_EXECS]; out->shade_lanes = h[zr::CTR_SHADE_LANES];   // shade_lanes: the counting lean SHADE's slots; otherwise a ZR_WAVE_PROFILE build's (zr_launch.h)
     }
     if (std::getenv("ZR_LANE_HISTOGRAM")) {   // development aid (a -DZR_WAVE_PROFILE build fills them): EXTEND's iterations per phase by ready lanes, 8 buckets of 8 lanes
         unsigned long long hh[zr::CTR_HIST_WORDS];

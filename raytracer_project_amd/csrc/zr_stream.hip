@@ -269,39 +269,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
         if (e_.tn <= tbest_f) { cur = e_.node; pend_i = 0; st = (e_.node & X_LEAF_BIT) ? X_LEAF : X_NODE; break; } \
     }
 
-// one child from the parametric distances of its six planes (absolute slack already inside): entry distance or +inf
-#define ZR_SLAB(X0, X1, Y0, Y1, Z0, Z1, RF_IN, TN, RF)                                                      \
-    {                                                                                                       \
-        const float x0 = (X0), x1 = (X1), y0 = (Y0), y1 = (Y1), z0 = (Z0), z1 = (Z1);                       \
-        float n_ = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), 0.000999f));            \
-        float f_ = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), tbest_f));              \
-        n_ = fmaf(fabsf(n_), -9.5367432e-7f, n_);                                                           \
-        f_ = fmaf(fabsf(f_), 9.5367432e-7f, f_);                                                            \
-        const bool empty_ = (RF_IN) == ZR_REF_EMPTY;                                                        \
-        const bool hit_ = (n_ <= f_) && !empty_;                                                            \
-        if (COUNT && !empty_) c_nodes++;                                                                    \
-        TN = hit_ ? n_ : INFf;                                                                              \
-        RF = (RF_IN);                                                                                       \
-    }
-// the slab constants of `ray` (see the header comment of this kernel)
-#define ZR_RAY_CONSTANTS()                                                                                  \
-    {                                                                                                       \
-        const float NANf = __builtin_nanf("");                                                              \
-        idx_ = 1.0f / (float)ray.d.x; idy_ = 1.0f / (float)ray.d.y; idz_ = 1.0f / (float)ray.d.z;            \
-        float ocx = (float)(-ray.o.x * (double)idx_), ocy = (float)(-ray.o.y * (double)idy_), ocz = (float)(-ray.o.z * (double)idz_); \
-        /* 2^100 / 2^120: far inside the float range, so that no product with a plane or a scale overflows */ \
-        if (!(fabsf(idx_) < 1.2676506e30f) || !(fabsf(ocx) < 1.3292280e36f)) { idx_ = 0.0f; ocx = NANf; }    \
-        if (!(fabsf(idy_) < 1.2676506e30f) || !(fabsf(ocy) < 1.3292280e36f)) { idy_ = 0.0f; ocy = NANf; }    \
-        if (!(fabsf(idz_) < 1.2676506e30f) || !(fabsf(ocz) < 1.3292280e36f)) { idz_ = 0.0f; ocz = NANf; }    \
-        /* the ENTRY plane of an axis (the lower one when id > 0) gets the smaller constant, the exit plane the larger one */ \
-        const float sx = fabsf(ocx) * 2.3841858e-7f, sy = fabsf(ocy) * 2.3841858e-7f, sz = fabsf(ocz) * 2.3841858e-7f; \
-        cnx = ocx - sx; cfx = ocx + sx; cny = ocy - sy; cfy = ocy + sy; cnz = ocz - sz; cfz = ocz + sz;      \
-    }
-// the root's FP32 planes (once per ray): lower / upper plane with the constant of the role it plays for this ray
-#define ZR_FBOX(N, C, TN, RF)                                                                               \
-    ZR_SLAB(fmaf((N).lox[C], idx_, idx_ > 0.0f ? cnx : cfx), fmaf((N).hix[C], idx_, idx_ > 0.0f ? cfx : cnx),  \
-            fmaf((N).loy[C], idy_, idy_ > 0.0f ? cny : cfy), fmaf((N).hiy[C], idy_, idy_ > 0.0f ? cfy : cny),  \
-            fmaf((N).loz[C], idz_, idz_ > 0.0f ? cnz : cfz), fmaf((N).hiz[C], idz_, idz_ > 0.0f ? cfz : cnz), (N).ref[C], TN, RF)
+// (ZR_SLAB, ZR_RAY_CONSTANTS, ZR_FBOX — the slab test itself: zr_device.h, shared with SHADE's escape stage)
 // the four children by entry distance (5-comparator network): push far -> near, continue with the nearest
 #define ZR_DESCEND()                                                                                        \
     {                                                                                                       \
@@ -610,11 +578,12 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
     }
     const SlotAt S = slot_at(B, blockIdx.x, src);
     bool active_after = false, want_unit = false;
-    uint32_t c_samp = 0, c_seg2 = 0, c_hit2 = 0; unsigned long long c_draws = 0;
+    uint32_t c_samp = 0, c_seg2 = 0, c_hit2 = 0, c_esc = 0, c_esc_nodes = 0, c_seen = 0; unsigned long long c_draws = 0;
     {
         if (m.y & F_ACTIVE) {   // (a thread beyond the pool got meta = 0 from the prologue)
             const uint32_t NONE = 0xFFFFFFFFu;
             const bool first = (m.y & F_FIRST) != 0;
+            if (COUNT && LEAN && MODE == 0) c_seen++;   // a segment EXTEND traced: CTR_SEGMENTS - CTR_ESCAPED, counted from this side
             // every row this segment reads, requested in one go (a row of a slot is always addressable; what a path does not
             // need is not requested: beta before the second hit, the unit id is 8 bytes)
             Ray ray; ray.o = S.ld3(SF_RAY); ray.d = S.ld3(SF_RAY + 3);
@@ -629,7 +598,9 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
             if (!first && ki.x == NONE) att0_now = S.ld3(SF_ATT0);   // a miss ends the path: its sample is att0 * (L + beta * background)
             int b_inner = (int)((m.y >> 8) & 0xFFu);
             const int depth_inner = cam.max_depth - 1;
-            auto load_L = [&]() { return (m.y & F_LZERO) ? mk(0, 0, 0) : S.ld3(SF_L); };
+            V3 L_now = mk(0, 0, 0);
+            bool have_L_now = false;    // L_now holds L (an escaped path whose L is in registers); otherwise L is what the slot says
+            auto load_L = [&]() { return have_L_now ? L_now : ((m.y & F_LZERO) ? mk(0, 0, 0) : S.ld3(SF_L)); };
             auto load_beta = [&]() { return beta_now; };
             uint32_t keep_lzero = m.y & F_LZERO;
             // the split passes count segments and hits here (SHADE sees every segment exactly once), so that their EXTEND can be
@@ -641,21 +612,36 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
             V3 add_now = mk(0, 0, 0);   // emission of a primary hit: added to the slot sum immediately
             bool has_add = false;
             bool no_output = false;     // MODE 2: the sample contributes nothing to the split frames
-            if (ki.x == NONE) {
-                if (MODE == 2 && first) { ended = true; no_output = true; }   // the primary ray saw the background only (camera.hpp:518-526)
-                else {
-                    V3 bg = background(sc, env, ray.d);
-                    if (MODE == 2) {
-                        V3 scol = load_L() + load_beta() * bg;
-                        const double luma = 0.2126 * len(scol);                  // camera.hpp:499-503
-                        if (luma > 2.0) scol = scol * (2.0 / luma);
-                        contrib = att0_now * scol;
-                    } else {
-                        contrib = first ? bg : att0_now * (load_L() + load_beta() * bg);  // camera.hpp:520 / 941,1000
-                    }
-                    ended = true;
-                }
-            } else {
+            // Two stages.  HIT: emission, scatter, depth and roulette; the path ends here or goes on with the ray `nr`.  MISS: the environment seen along
+            // `ray` ends the path.  A slot whose ray found nothing enters MISS directly.  In the lean render a path that goes on enters it in the SAME
+            // round when its new ray provably leaves the world (ray_escapes, zr_device.h: only certain misses, by EXTEND's own box arithmetic): the
+            // ray and the state rows are not stored, MISS gets from registers exactly the values the slot would have handed it one round later —
+            // att0, beta, L, the draw count, the primary hit's emission — and the slot starts its next sample a round earlier.  No hit is ever
+            // resolved here, and a regenerated camera ray always goes to EXTEND.
+            bool miss_first = first;    // MISS: `ray` is the camera ray (its sample is the background itself)
+            bool escaped = false;
+// MISS as a macro, not a lambda: through a lambda the general builds came out with other registers and, in two of them, with spills
+#define ZR_MISS_STAGE()                                                                                                                    \
+            {                                                                                                                              \
+                if (MODE == 2 && first) { ended = true; no_output = true; }   /* the primary ray saw the background only (camera.hpp:518-526) */ \
+                else {                                                                                                                     \
+                    V3 bg = background(sc, env, ray.d);                                                                                    \
+                    if (MODE == 2) {                                                                                                       \
+                        V3 scol = load_L() + load_beta() * bg;                                                                             \
+                        const double luma = 0.2126 * len(scol);                  /* camera.hpp:499-503 */                                  \
+                        if (luma > 2.0) scol = scol * (2.0 / luma);                                                                        \
+                        contrib = att0_now * scol;                                                                                         \
+                    } else {                                                                                                               \
+                        contrib = miss_first ? bg : att0_now * (load_L() + load_beta() * bg);  /* camera.hpp:520 / 941,1000 */             \
+                    }                                                                                                                      \
+                    ended = true;                                                                                                          \
+                }                                                                                                                          \
+            }
+            // every build compiles exactly one of the two calls: the builds without the escape stage keep the miss ahead of the hit, as their code has
+            // always been laid out (their registers and instructions are what they were); the lean render runs it behind the hit stage
+            constexpr bool ESC = LEAN && MODE == 0;
+            if (!ESC && ki.x == NONE) ZR_MISS_STAGE()
+            else if (ki.x != NONE) {
                 const double t = t_hit;
                 V3 em, att; Ray nr; bool sc_ok;
                 uint32_t cls_now = 0;
@@ -679,11 +665,15 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
                     }
                 }
                 const bool has_em = em.x != 0.0 || em.y != 0.0 || em.z != 0.0;
+                // decided before any state is stored; it takes effect only if the path does go on (depth, roulette)
+                uint32_t esc_nodes = 0;
+                const bool esc = ESC && sc_ok && sc.shade_escape && ray_escapes(nr, sc.root, sc.spheres, esc_nodes);
                 if (first) {  // ray_color_from_hit, camera.hpp:989-1004
                     if (MODE != 2 && has_em) { add_now = em; has_add = true; }
                     if (!sc_ok || depth_inner <= 0) { ended = true; if (MODE == 2) no_output = true; }
                     else {
-                        S.st3(SF_ATT0, att);   // L = 0, beta = 1: implicit (F_LZERO | F_BONE below)
+                        if (esc) { att0_now = att; have_L_now = true; }   // MISS gets att0 = att, L = 0 (L_now), beta = 1 (beta_now)
+                        else S.st3(SF_ATT0, att);   // L = 0, beta = 1: implicit (F_LZERO | F_BONE below)
                         if (MODE == 2) { uint2 mb = mb_now; mb.y = cls_now; S.st2(SF_MB, mb); }
                         b_inner = 0;
                     }
@@ -709,12 +699,20 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
                         if (!have_L) L = load_L();
                         if (MODE == 2) { const double luma = 0.2126 * len(L); if (luma > 2.0) L = L * (2.0 / luma); }
                         contrib = S.ld3(SF_ATT0) * L; ended = true;
+                    } else if (esc) {   // MISS gets what the slot would have carried: att0 as stored, the new beta, the new L if there is one
+                        att0_now = S.ld3(SF_ATT0); beta_now = beta;
+                        if (have_L) { L_now = L; have_L_now = true; }
                     } else {
                         if (have_L) { S.st3(SF_L, L); keep_lzero = 0; }
                         S.st3(SF_BETA, beta);
                     }
                 }
-                if (!ended) {
+                if (!ended && esc) {
+                    // the path continues and its ray leaves the world: nothing is published, MISS ends the path along the new ray
+                    escaped = true; miss_first = false;
+                    ray = nr;
+                    if (COUNT) { c_esc++; c_esc_nodes += esc_nodes; }
+                } else if (!ended) {
                     // the path continues: publish the scattered ray (a primary hit's emission waits in SF_SUM)
                     S.st3(SF_RAY, nr.o); S.st3(SF_RAY + 3, nr.d);
                     if (has_add) S.st3(SF_SUM, add_now);
@@ -725,6 +723,8 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
                     active_after = true;
                 }
             }
+            if (ESC && (ki.x == NONE || escaped)) ZR_MISS_STAGE()
+#undef ZR_MISS_STAGE
             if (ended) {
                 // radiance of this sample = L0 + att0 * L (camera.hpp:1000), written exactly once
                 V3 rad = contrib;
@@ -770,6 +770,11 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
     if (COUNT && MODE == 0) {
         if (c_samp) atomicAdd(&gctr[CTR_SAMPLES], (unsigned long long)c_samp);
         if (c_draws) atomicAdd(&gctr[CTR_DRAWS], c_draws);
+        if (c_seen) atomicAdd(&gctr[CTR_SHADE_LANES], (unsigned long long)c_seen);
+        if (c_esc) {   // a segment finished here is a segment all the same, and its root boxes were tested (EXTEND would have counted both)
+            atomicAdd(&gctr[CTR_SEGMENTS], (unsigned long long)c_esc); atomicAdd(&gctr[CTR_ESCAPED], (unsigned long long)c_esc);
+            atomicAdd(&gctr[CTR_NODES], (unsigned long long)c_esc_nodes);
+        }
     }
     if (MODE != 0) {
         if (c_samp) atomicAdd(&s_cnt[0], (unsigned long long)c_samp);
