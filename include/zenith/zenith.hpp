@@ -1411,6 +1411,16 @@ public:
     // current_samples_count-spp image.  The finished frame equals the one-shot frame bit for bit.  0: exactly the one-shot render.
     int samples_per_pass = 0;
     int passes_rendered = 0;        // extension: passes of the last progressive render that reached render_accumulator
+    // extension: > 0 renders adaptively (zr_render_adaptive): every pixel gets adaptive_min_samples, then adaptive_step more per pass while its noise estimate (the
+    // relative standard error of the pixel mean) is above adaptive_threshold, up to samples_per_pixel rounded down to a multiple of 64 (below 64 the flag is ignored
+    // with a warning).  Afterwards render_accumulator is the resolved frame — a pixel that stopped at k samples is that pixel of the k-spp frame, bit for bit —
+    // sample_counts holds the per-pixel counts and current_samples_count the largest.  render_flag is looked at between passes.  Takes precedence over
+    // samples_per_pass.  0: exactly the render without it.
+    double adaptive_threshold = 0;
+    int adaptive_min_samples = 64, adaptive_step = 64;
+    double adaptive_dark_floor = 0.01;
+    std::vector<int> sample_counts;   // extension: samples per pixel of the last adaptive render (row-major like render_accumulator); empty otherwise
+    zr_adaptive_stats last_adaptive{};
     zr_counters last_counters{};
 
     void reset_accumulator() {  // camera.hpp:209-233
@@ -1489,6 +1499,7 @@ public:
             zc.image_width = image_width; zc.image_height = image_height; zc.samples_per_pixel = samples_per_pixel; zc.max_depth = max_depth;
             zc.vfov = vfov; zc.defocus_angle = defocus_angle; zc.focus_dist = focus_dist;
             for (int k = 0; k < 3; k++) { zc.lookfrom[k] = lookfrom[k]; zc.lookat[k] = lookat[k]; zc.vup[k] = vup[k]; }
+            sample_counts.clear();
             if (global_settings::bvh_debug_mode) {
                 // the debug view fills render_accumulator only: the AOV, split-pass and denoise buffers stay as reset_accumulator left them
                 // (the reference would feed them the debug frame's records)
@@ -1497,7 +1508,34 @@ public:
                                          reinterpret_cast<volatile const uint8_t*>(&render_flag), reinterpret_cast<volatile int*>(&lines_rendered));
                 ph("zr_render_bvh_debug");
             } else {
-            if (samples_per_pass > 0) {
+            bool adaptive = adaptive_threshold > 0;
+            if (adaptive && samples_per_pixel < 64) { std::cerr << "[zenith] adaptive_threshold ignored: samples_per_pixel is below 64\n"; adaptive = false; }
+            if (adaptive) {
+                static_assert(sizeof(int) == sizeof(int32_t), "sample_counts layout");
+                zr_adaptive_params ap{};
+                ap.max_samples = samples_per_pixel / 64 * 64;
+                ap.min_samples = std::min(adaptive_min_samples, ap.max_samples); ap.step_samples = adaptive_step;
+                ap.threshold = adaptive_threshold; ap.dark_floor = adaptive_dark_floor;
+                current_samples_count = 0; passes_rendered = 0;
+                zr_accum* acc = zr_accum_create(ctx, image_width, image_height, nullptr);
+                rc = acc ? ZR_OK : ZR_E_DEVICE;
+                if (rc == ZR_OK) {
+                    // a cancelled run leaves the image of the passes that completed; a refused one (bad counts) leaves nothing
+                    const int arc = zr_render_adaptive(ctx, sc, &zc, &zenv, seed, acc, &ap, 0, reinterpret_cast<volatile const uint8_t*>(&render_flag), &last_adaptive);
+                    rc = arc;
+                    if ((arc == ZR_OK || arc == ZR_E_CANCELLED) && last_adaptive.passes > 0) {
+                        sample_counts.assign((size_t)image_width * image_height, 0);
+                        int64_t st4[4] = {0, 0, 0, 0};
+                        int qrc = zr_accum_resolve(acc, reinterpret_cast<double*>(render_accumulator.data()));
+                        if (qrc == ZR_OK) qrc = zr_accum_sample_counts(acc, reinterpret_cast<int32_t*>(sample_counts.data()));
+                        if (qrc == ZR_OK) qrc = zr_accum_state(acc, st4);
+                        if (qrc != ZR_OK) rc = qrc;
+                        else { current_samples_count = (int)st4[1]; passes_rendered = (int)last_adaptive.passes; }
+                    }
+                    if (rc == ZR_OK) lines_rendered = image_height;
+                }
+                if (acc) zr_accum_destroy(acc);
+            } else if (samples_per_pass > 0) {
                 // progressive (the reference's "real-time sample accumulation"): passes of samples_per_pass samples into a device accumulator
                 const int spp = samples_per_pixel < 1 ? 1 : samples_per_pixel;
                 current_samples_count = 0; passes_rendered = 0;

@@ -325,6 +325,55 @@ int zr_accum_resolve(zr_accum*, double* out_rgb);
 int zr_accum_resolve_device(zr_accum*, void* d_out_rgb, void* hip_stream);
 int zr_accum_state(const zr_accum*, int64_t out[4]);
 
+/* ---- adaptive sampling: further samples only for the pixels that are still noisy -----------------------------
+ * With k = 64 m samples in a pixel every lane holds exactly m of them, so the 64 lane sums S_l are 64 equally weighted,
+ * independent estimates of the pixel.  Their spread gives the noise estimate (FP64, in this order, no contraction):
+ *   v_l = S_l.r + S_l.g + S_l.b;  T = sum v_l (xor butterfly 32, 16, ... 1);  mu = T * (1.0 / 64);  d_l = v_l - mu;
+ *   Q = sum d_l * d_l (same butterfly);  se = sqrt(Q * (1.0 / 63) * (1.0 / 64)) * (1.0 / m);  I = mu * (1.0 / m);
+ *   err = se / (I + dark_floor)          0 exactly when Q == 0 (all lanes equal), +inf when T is not finite
+ * i.e. the standard error of the mean of the channel sum, relative to the channel sum.  tests/adaptive_model.py restates it.
+ *   zr_render_adaptive   pass 0 brings every pixel of the accumulator's plan to min_samples (the accumulator is fresh, or holds
+ *                        uniform batches with done a multiple of 64 and <= min_samples: ZR_E_STATE otherwise); every later pass
+ *                        gives step_samples more to the pixels still active.  After each pass a pixel stays active iff
+ *                        err > threshold and its count + step_samples <= max_samples; a pixel that stopped never restarts, so
+ *                        the active pixels share one count, counts lie in {min + j * step} and A PIXEL THAT STOPPED AT k SAMPLES IS
+ *                        THAT PIXEL OF THE k-spp zr_render FRAME, BIT FOR BIT (first = 0).  The loop ends when no pixel is active.
+ *                        Passes take zr_render_accumulate's route and must fit it in one run (ZR_E_NOMEM: lower step_samples;
+ *                        the accumulator is as the last complete pass left it).  *keep_going is looked at between passes and
+ *                        inside them; a cancelled or failed pass is discarded whole (ZR_E_CANCELLED or its error code).
+ *                        The parameters are checked before anything else, device or other arguments: ZR_E_INVALID for a count
+ *                        that is not a positive multiple of 64, max_samples < min_samples, a threshold or floor that is negative or
+ *                        not finite; then for the camera, seed or scene mismatches zr_render_accumulate refuses.  Once a pass
+ *                        has completed the accumulator is NON-UNIFORM: zr_render_accumulate and zr_render_adaptive return
+ *                        ZR_E_STATE until zr_accum_reset; resolve (1.0 / the pixel's own count) and the queries below keep
+ *                        working; zr_accum_state's `done` is the largest per-pixel count.  `out` (may be NULL) receives the
+ *                        statistics of the passes that completed, on every return (zeros when the call was refused); zr_get_counters afterwards holds the totals over all passes.
+ *   zr_accum_error       the estimate of the current sums with this dark_floor, W*H doubles; ZR_E_STATE on a uniform accumulator
+ *                        whose done is not a multiple of 64
+ *   zr_accum_sample_counts  the per-pixel sample counts, W*H int32
+ *   zr_accum_lane_sums   a known-answer entry like zr_trace: the raw sums, [pixel][channel][lane] with the pixels in plan (tile)
+ *                        order, 192 doubles each; returns their number (out may be NULL with cap_doubles = 0 to ask for it) or a
+ *                        negative ZR_E_* (ZR_E_STATE, the size query included, while nothing has been rendered; then ZR_E_INVALID:
+ *                        cap_doubles too small)
+ * The three queries write only the plan's pixels of W*H arrays and return ZR_E_STATE while nothing has been rendered. */
+typedef struct zr_adaptive_params {
+    int32_t min_samples, max_samples, step_samples;   /* positive multiples of 64, min <= max */
+    int32_t pad_;
+    double threshold;                                  /* a pixel goes on while err > threshold; 0: every pixel with any spread */
+    double dark_floor;                                 /* 0.01 keeps near-black pixels from demanding samples for invisible noise */
+} zr_adaptive_params;
+typedef struct zr_adaptive_stats {
+    uint64_t passes;                 /* passes completed (pass 0 included) */
+    uint64_t samples;                /* primary samples rendered */
+    uint64_t stopped_by_threshold;   /* pixels that stopped with err <= threshold */
+    uint64_t stopped_at_max;         /* pixels still above the threshold when max_samples stopped them */
+} zr_adaptive_stats;
+int zr_render_adaptive(zr_ctx*, const zr_scene*, const zr_camera*, const zr_env*, uint64_t seed, zr_accum*, const zr_adaptive_params*,
+                       int collect_counters, volatile const uint8_t* keep_going, zr_adaptive_stats* out);
+int zr_accum_error(zr_accum*, double dark_floor, double* out);
+int zr_accum_sample_counts(zr_accum*, int32_t* out);
+int64_t zr_accum_lane_sums(zr_accum*, double* out, size_t cap_doubles);
+
 /* ---- first-hit AOV passes: the albedo / normal / z-depth part of render_rows (camera.hpp:433, 464-488, 521-541) ---- */
 /* For the first min(clamp(spp / 8, 64, 1024), spp) samples of every pixel the primary hit contributes
  *   albedo  += rec.mat->get_albedo(rec)                       (material.hpp:29-31,99-102,154-156,226-229,266-275)

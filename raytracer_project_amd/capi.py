@@ -147,6 +147,28 @@ class Counters(C.Structure):
                 + 48 * self.cubes_tested + 76 * self.hits)
 
 
+class AdaptiveParams(C.Structure):
+    """zr_adaptive_params: the three counts are positive multiples of 64; a pixel goes on while err > threshold"""
+    _fields_ = [("min_samples", C.c_int32), ("max_samples", C.c_int32), ("step_samples", C.c_int32), ("pad_", C.c_int32),
+                ("threshold", C.c_double), ("dark_floor", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        p = cls(64, 512, 64, 0, 0.02, 0.01)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+
+class AdaptiveStats(C.Structure):
+    _fields_ = [("passes", C.c_uint64), ("samples", C.c_uint64), ("stopped_by_threshold", C.c_uint64), ("stopped_at_max", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class AovParams(C.Structure):
     _fields_ = [("z_depth_max_dist", C.c_double)]
 
@@ -200,6 +222,7 @@ CAPI_SYMBOLS = [
     "zr_scene_set_xform_ops", "zr_scene_set_objects", "zr_scene_set_groups", "zr_scene_set_materials", "zr_scene_set_textures",
     "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_kernels", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device",
     "zr_accum_create", "zr_accum_destroy", "zr_accum_reset", "zr_render_accumulate", "zr_accum_resolve", "zr_accum_resolve_device", "zr_accum_state",
+    "zr_render_adaptive", "zr_accum_error", "zr_accum_sample_counts", "zr_accum_lane_sums",
     "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
@@ -246,6 +269,10 @@ def load():
     lib.zr_accum_resolve.argtypes = [vp, vp]
     lib.zr_accum_resolve_device.argtypes = [vp, vp, vp]
     lib.zr_accum_state.argtypes = [vp, C.POINTER(C.c_int64 * 4)]
+    lib.zr_render_adaptive.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, vp, C.POINTER(AdaptiveParams), i32, vp, C.POINTER(AdaptiveStats)]
+    lib.zr_accum_error.argtypes = [vp, C.c_double, vp]
+    lib.zr_accum_sample_counts.argtypes = [vp, vp]
+    lib.zr_accum_lane_sums.restype = C.c_int64; lib.zr_accum_lane_sums.argtypes = [vp, vp, C.c_size_t]
     lib.zr_render_aov.argtypes = [vp, vp, C.POINTER(Camera), u64, C.POINTER(Region), C.POINTER(AovParams), vp, vp, vp]
     lib.zr_post_process.argtypes = [vp, C.POINTER(PostParams), vp, i32, i32, i32, i32, vp]
     lib.zr_analyze_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(ImageStats)]
@@ -345,6 +372,21 @@ class DemoScene:
         if lib.zrs_render_dropin_progressive(self._h, width, height, spp, device, int(samples_per_pass), out.ctypes.data, info) != 0:
             raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
         return out, int(info[0]), int(info[1])
+
+    def render_dropin_adaptive(self, threshold, min_samples=0, step=0, width=0, height=0, spp=0, device=0):
+        """camera::render with camera::adaptive_threshold set (min_samples / step 0: the camera's defaults of 64): (frame, camera::sample_counts as
+        (H, W) int32 — all -1 when the render was not adaptive —, current_samples_count afterwards (-7 going in), passes)"""
+        w = width or self.camera.image_width
+        h = height or self.camera.image_height
+        out = np.zeros((h, w, 3), dtype=np.float64)
+        counts = np.full((h, w), -1, dtype=np.int32)
+        info = (C.c_int * 2)()
+        lib = load_scenes()
+        lib.zrs_render_dropin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        if lib.zrs_render_dropin_adaptive(self._h, width, height, spp, device, float(threshold), int(min_samples), int(step), out.ctypes.data, counts.ctypes.data,
+                                          info) != 0:
+            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        return out, counts, int(info[0]), int(info[1])
 
     def render_dropin_threads(self, n, width=0, height=0, spp=0, device=0):
         """n drop-in renders, each on a fresh host thread, one after the other (the reference's render-restart pattern,
@@ -532,6 +574,43 @@ class Accumulator:
 
     def reset(self, first_sample=0):
         _check(self.lib.zr_accum_reset(self._a, int(first_sample)))
+
+    def render_adaptive(self, scene, camera, env, seed, params, count=False, keep_going=None):
+        """zr_render_adaptive: every pixel to params.min_samples, then params.step_samples more per pass for the pixels whose noise estimate is
+        above params.threshold, up to params.max_samples.  Returns (rc, AdaptiveStats); a cancelled run raises nothing and returns
+        ZR_E_CANCELLED with the statistics of the passes that completed."""
+        kg = C.cast(C.byref(keep_going), C.c_void_p) if keep_going is not None else None
+        stats = AdaptiveStats()
+        rc = _check(self.lib.zr_render_adaptive(self.ctx._c, scene._s, C.byref(camera), C.byref(env), C.c_uint64(seed), self._a, C.byref(params),
+                                                1 if count else 0, kg, C.byref(stats)), allow_cancel=True)
+        return rc, stats
+
+    def error(self, dark_floor=0.01, out=None):
+        """the noise estimate of the sums held (relative standard error of the pixel mean): (H, W) float64; only the region's pixels are written"""
+        if out is None:
+            out = np.zeros((self.height, self.width), dtype=np.float64)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.height, self.width)
+        _check(self.lib.zr_accum_error(self._a, C.c_double(dark_floor), out.ctypes.data))
+        return out
+
+    def sample_counts(self, out=None):
+        """samples per pixel: (H, W) int32; only the region's pixels are written"""
+        if out is None:
+            out = np.zeros((self.height, self.width), dtype=np.int32)
+        assert out.dtype == np.int32 and out.flags.c_contiguous and out.shape == (self.height, self.width)
+        _check(self.lib.zr_accum_sample_counts(self._a, out.ctypes.data))
+        return out
+
+    def lane_sums(self):
+        """the raw lane sums, (pixels, 3, 64) float64 with the pixels in plan (tile) order"""
+        n = int(self.lib.zr_accum_lane_sums(self._a, None, 0))
+        if n < 0:
+            _check(n)
+        out = np.zeros((n // 192, 3, 64), dtype=np.float64)
+        got = int(self.lib.zr_accum_lane_sums(self._a, out.ctypes.data, out.size))
+        if got < 0:
+            _check(got)
+        return out
 
     def state(self):
         out = (C.c_int64 * 4)()

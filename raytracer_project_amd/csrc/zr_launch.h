@@ -115,6 +115,18 @@ hipError_t launch_accum_resolve(const double* partial, const uint32_t* pixels, u
 // the pixel-group kernel's arithmetic for one batch: samples [sample0, sample0 + n) of the listed pixels, written as per-sample radiance ([n_pix][n][3]) for launch_accumulate
 hipError_t launch_render_samples(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const uint32_t* pixels, uint32_t n_pix, uint32_t sample0,
                                  uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream);
+// Adaptive sampling (zr_render_adaptive, zr_adaptive.hip).  launch_adaptive_accumulate: one pass's samples ([n_list][n][3]) of the active list onto the lane sums of
+// the slots slot[i], then the noise estimate of the updated sums: count[slot] = new_count, flag[i] = 1 goes on / 2 noisy at max_samples / 0 converged.
+// launch_adaptive_compact: the positions with flag 1, in order, into pixels_out / slot_out; totals (device) = {active, at max}; block_active / block_at_max: scratch of
+// ceil(n_list / 256) words each.  launch_accum_error: the estimate of every slot (count: per slot, or null for uniform_count).  launch_accum_resolve_counts:
+// launch_accum_resolve with 1.0 / count[pixel].
+hipError_t launch_adaptive_accumulate(const double* samples, const uint32_t* slot, uint32_t n_list, uint32_t n, uint32_t sample0, double* partial, int32_t* count,
+                                      uint32_t* flag, int new_count, int max_samples, double threshold, double dark_floor, hipStream_t stream);
+hipError_t launch_adaptive_compact(const uint32_t* flag, uint32_t n_list, const uint32_t* pixels_in, const uint32_t* slot_in, uint32_t* pixels_out,
+                                   uint32_t* slot_out, uint32_t* block_active, uint32_t* block_at_max, uint32_t* totals, hipStream_t stream);
+hipError_t launch_accum_error(const double* partial, const int32_t* count, int uniform_count, uint32_t n_pix, double dark_floor, double* err, hipStream_t stream);
+hipError_t launch_accum_resolve_counts(const double* partial, const uint32_t* pixels, const int32_t* count, uint32_t n_pix, int W, int asc_lanes, double* out,
+                                       hipStream_t stream);
 // closest hits of n rays in [0.001, inf) through the EXTEND kernel on ctx.streams[0]; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes
 hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, void* pool,
                         const StreamContext& ctx, int leaf_level);

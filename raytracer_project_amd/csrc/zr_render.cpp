@@ -167,6 +167,7 @@ struct FrameJob {
     double* d_out = nullptr; double* d_out2 = nullptr;   // device frames (d_out2: the refraction frame of the split's replay pass)
     volatile const uint8_t* keep_going = nullptr; volatile int* rows_done = nullptr;
     zr::StreamProgress* progress = nullptr;
+    const uint32_t* d_list = nullptr; uint32_t n_list = 0;   // a device pixel list of the caller's (an adaptive pass: the active pixels) instead of the plan's cached one
     bool interactive() const { return keep_going || rows_done; }   // the caller polls: the tile-list paths need batch boundaries
 };
 
@@ -352,9 +353,11 @@ int split_buffers(zr_ctx* c, uint64_t units, int mode, hipStream_t stream, zr::S
 // first).  Synchronises the stream internally (the round loop needs the active-slot count), so zr_render_device returns with the frame complete.
 // mode 0: the render; 1 / 2: beauty pass and replay pass of the reflection / refraction split (zr_stream.hip, stream_shade)
 int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode = 0) {
-    int rc = upload_pixel_list(c, job.plan);
-    if (rc) return rc;
-    const uint32_t n_pix = (uint32_t)c->d_pixels.n, spp = (uint32_t)job.dc.spp;
+    int rc = ZR_OK;
+    // the caller's own list leaves the cached one (zr_ctx::d_pixels, pix_key) alone: a later render of the plan gets the plan's list
+    if (!job.d_list && (rc = upload_pixel_list(c, job.plan))) return rc;
+    const uint32_t* const pixels = job.d_list ? job.d_list : c->d_pixels.p;
+    const uint32_t n_pix = job.d_list ? job.n_list : (uint32_t)c->d_pixels.n, spp = (uint32_t)job.dc.spp;
     if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
     c->render_id++; c->last_stream = job.stream; c->last_counted = job.count; c->last_rounds = 0;
     HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
@@ -370,7 +373,7 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode = 
     streams[0] = job.stream;
     for (int k = 1; k < ST_MAX_POOLS; k++) streams[k] = c->sub[k];
     zr::StreamJob sj{};
-    sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, c->d_pixels.p, c->d_partial.p, job.d_out, job.d_out2, job.count, job.sample0};
+    sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, pixels, c->d_partial.p, job.d_out, job.d_out2, job.count, job.sample0};
     sj.ctx = zr::StreamContext{c->d_ctl.p, nullptr, 0, c->st_blocks, c->d_ctr.p, streams, 1, c->st_event, c->h_active};
     sj.hooks = zr::StreamHooks{nullptr, job.keep_going, job.progress, nullptr};
     const bool polled = job.keep_going || job.progress;   // a cancelled frame / a preview reduces what exists: the samples start at zero
@@ -416,7 +419,14 @@ struct AccumState {
     int route = 2;                 // zr_counters::path of the batches so far: which one-shot kernel's pairing the resolve follows
     bool bound = false;            // a batch has been added since create / reset: later ones must bring the same camera, seed and scene
     zr_camera cam{}; uint64_t seed = 0; const zr_scene* scene = nullptr;
-    size_t device_bytes() const { return (size_t)n_pix * (zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double) + sizeof(uint32_t)); }
+    // adaptive sampling (zr_render_adaptive), allocated by its first run: the sample count per pixel, the active list and its slot index
+    // (two of each: a pass compacts one into the other), the flags per list position and the compaction's block counts and totals
+    bool adaptive = false;         // an adaptive pass has completed since create / reset: the counts are per pixel (d_count) and `done` is the largest
+    DevBuf<int32_t> d_count; DevBuf<uint32_t> d_list[2], d_slot[2], d_flag, d_block_active, d_block_at_max, d_totals;
+    size_t device_bytes() const {
+        return (size_t)n_pix * (zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double) + sizeof(uint32_t)) + d_count.n * sizeof(int32_t) +
+               (d_list[0].n + d_list[1].n + d_slot[0].n + d_slot[1].n + d_flag.n + d_block_active.n + d_block_at_max.n + d_totals.n) * sizeof(uint32_t);
+    }
 };
 
 int accum_init(AccumState& a, zr_ctx* c, const zr_camera& cam, const zr_region* region) {
@@ -431,49 +441,57 @@ int accum_init(AccumState& a, zr_ctx* c, const zr_camera& cam, const zr_region* 
         return fail(ZR_E_NOMEM, "no device memory for the lane sums of %u pixels (%zu bytes)", a.n_pix, (size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double));
     HIP_OK(hipMemset(a.d_partial.p, 0, std::max<size_t>((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double), 64)));
     HIP_OK(hipDeviceSynchronize());   // the context's streams do not wait for the null stream
-    a.first = 0; a.done = 0; a.bound = false; a.route = 2;
+    a.first = 0; a.done = 0; a.bound = false; a.route = 2; a.adaptive = false;
+    return ZR_OK;
+}
+
+// The samples [sample0, sample0 + n) of n_pix listed pixels as per-sample radiance in zr_ctx::d_partial ([pixel][n][3]), by the route zr_render takes for this scene and
+// camera.  job: plan, camera, environment, seed, stream, count and keep_going as prepare_frame and the caller left them.  `pixels` is what the pixel-group route
+// renders; the pipeline renders job.d_list when that is set (the same list) and otherwise the plan's cached list, *flipped then saying that it ran in the reverse of
+// the plan's order (ZR_STREAM_BOTTOM_UP).  Nothing but d_partial and the counters is written: the caller adds the samples to its sums, or drops them.
+int render_batch_samples(zr_ctx* c, const zr_scene* s, FrameJob& job, const uint32_t* pixels, uint32_t n_pix, int sample0, int n, HostTimer& timer, bool* flipped) {
+    job.dc.spp = n; job.sample0 = (uint32_t)sample0; job.d_out = nullptr; job.d_out2 = nullptr; job.progress = nullptr; job.rows_done = nullptr;
+    *flipped = false;
+    if (job.keep_going && *job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled before it began");
+    const uint64_t units = (uint64_t)n_pix * (uint64_t)n;
+    if (fits_stream(c, s, job.plan, job.dc, 1, 0)) {
+        if (units > zr::ST_MAX_UNITS) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu work units, the pipeline numbers 2^32 - 1 per run: ask for fewer samples", n, (unsigned long long)units);
+        *flipped = !job.d_list && env_double("ZR_STREAM_BOTTOM_UP", 1) != 0;
+        return render_stream(c, s, job);
+    }
+    // the pixel-group route: the batch's per-sample radiance
+    if (units > (1ull << 37)) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu samples of radiance: ask for fewer", n, (unsigned long long)units);
+    if (c->d_partial.n < units * 3) {
+        HIP_OK(hipStreamSynchronize(job.stream));
+        if (c->d_partial.alloc(units * 3) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes): ask for fewer samples", (size_t)units * 3 * sizeof(double));
+    }
+    c->last_path = 0;
+    if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
+    c->render_id++; c->last_stream = job.stream; c->last_counted = job.count;
+    timer.begin(job.stream, 1);
+    HIP_OK(zr::launch_render_samples(s->ds, job.dc, job.de, job.seed, pixels, n_pix, (uint32_t)sample0, (uint32_t)n, c->d_partial.p, c->d_ctr.p, job.count, job.stream));
+    timer.end(job.stream, 1);
+    if (job.keep_going) {
+        HIP_OK(hipStreamSynchronize(job.stream));
+        if (*job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled");
+    }
     return ZR_OK;
 }
 
 // One batch: the samples [sample0, sample0 + n) of every pixel of the accumulator by the route zr_render takes for this scene and camera, added to the lane sums.
-// job: plan, camera, environment, seed, stream, count and keep_going as prepare_frame and the caller left them (the plan is the accumulator's).  The batch is rendered
-// whole before the sums are touched: on any failure — ZR_E_CANCELLED, ZR_E_NOMEM (this many samples do not fit the route in one run) — they are as they were.
+// The batch is rendered whole before the sums are touched: on any failure — ZR_E_CANCELLED, ZR_E_NOMEM (this many samples do not fit the route in one run) — they
+// are as they were.
 int accumulate_batch(zr_ctx* c, const zr_scene* s, FrameJob& job, AccumState& a, int sample0, int n) {
-    job.dc.spp = n; job.sample0 = (uint32_t)sample0; job.d_out = nullptr; job.d_out2 = nullptr; job.progress = nullptr; job.rows_done = nullptr;
     c->last_rounds = 0;
     HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
     if (a.n_pix == 0) return ZR_OK;
-    if (job.keep_going && *job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled before it began");
-    const uint64_t units = (uint64_t)a.n_pix * (uint64_t)n;
     HostTimer timer(c);
-    if (fits_stream(c, s, job.plan, job.dc, 1, 0)) {
-        if (units > zr::ST_MAX_UNITS) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu work units, the pipeline numbers 2^32 - 1 per run: ask for fewer samples", n, (unsigned long long)units);
-        int rc = render_stream(c, s, job);
-        if (rc) return rc;
-        timer.begin(job.stream, 3);
-        HIP_OK(zr::launch_accumulate(c->d_partial.p, a.n_pix, (uint32_t)n, (uint32_t)sample0, env_double("ZR_STREAM_BOTTOM_UP", 1) != 0, a.d_partial.p, job.stream));
-        timer.end(job.stream, 3);
-    } else {
-        // the pixel-group route: the batch's per-sample radiance, then the same accumulate kernel
-        if (units > (1ull << 37)) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu samples of radiance: ask for fewer", n, (unsigned long long)units);
-        if (c->d_partial.n < units * 3) {
-            HIP_OK(hipStreamSynchronize(job.stream));
-            if (c->d_partial.alloc(units * 3) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes): ask for fewer samples", (size_t)units * 3 * sizeof(double));
-        }
-        c->last_path = 0;
-        if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
-        c->render_id++; c->last_stream = job.stream; c->last_counted = job.count;
-        timer.begin(job.stream, 1);
-        HIP_OK(zr::launch_render_samples(s->ds, job.dc, job.de, job.seed, a.d_pixels.p, a.n_pix, (uint32_t)sample0, (uint32_t)n, c->d_partial.p, c->d_ctr.p, job.count, job.stream));
-        timer.end(job.stream, 1);
-        if (job.keep_going) {
-            HIP_OK(hipStreamSynchronize(job.stream));
-            if (*job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled");
-        }
-        timer.begin(job.stream, 3);
-        HIP_OK(zr::launch_accumulate(c->d_partial.p, a.n_pix, (uint32_t)n, (uint32_t)sample0, false, a.d_partial.p, job.stream));
-        timer.end(job.stream, 3);
-    }
+    bool flipped = false;
+    int rc = render_batch_samples(c, s, job, a.d_pixels.p, a.n_pix, sample0, n, timer, &flipped);
+    if (rc) return rc;
+    timer.begin(job.stream, 3);
+    HIP_OK(zr::launch_accumulate(c->d_partial.p, a.n_pix, (uint32_t)n, (uint32_t)sample0, flipped, a.d_partial.p, job.stream));
+    timer.end(job.stream, 3);
     if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
     HIP_OK(hipStreamSynchronize(job.stream));
     a.route = c->last_path;
@@ -482,7 +500,9 @@ int accumulate_batch(zr_ctx* c, const zr_scene* s, FrameJob& job, AccumState& a,
 
 // the mean of the samples held, into the accumulator's pixels of the device frame d_out, with the pairing of the kernel that rendered them (zr_stream.hip: accum_resolve)
 int accum_resolve_into(const AccumState& a, double* d_out, hipStream_t stream) {
-    HIP_OK(zr::launch_accum_resolve(a.d_partial.p, a.d_pixels.p, a.n_pix, a.plan.W, a.done, a.route == 0 ? lanes_for(a.done) : 1, d_out, stream));
+    // per-pixel counts are all at least 64, where lanes_for gives 64
+    if (a.adaptive) HIP_OK(zr::launch_accum_resolve_counts(a.d_partial.p, a.d_pixels.p, a.d_count.p, a.n_pix, a.plan.W, a.route == 0 ? 64 : 1, d_out, stream));
+    else HIP_OK(zr::launch_accum_resolve(a.d_partial.p, a.d_pixels.p, a.n_pix, a.plan.W, a.done, a.route == 0 ? lanes_for(a.done) : 1, d_out, stream));
     return ZR_OK;
 }
 
@@ -629,6 +649,18 @@ int enqueue_render(zr_ctx* c, const zr_scene* s, const FrameJob& job) {
         });
 }
 
+// what the queries of an accumulator's contents share (zr_accum_error, zr_accum_sample_counts, zr_accum_lane_sums): something has been rendered
+int query_ready(const AccumState& st, const char* entry) {
+    if (st.done == 0) return fail(ZR_E_STATE, "zr_render_accumulate or zr_render_adaptive must precede %s", entry);
+    return ZR_OK;
+}
+// per-slot values -> the plan's pixels of a W*H array
+template <class T>
+void scatter_to_frame(const Plan& plan, const std::vector<T>& per_slot, T* out) {
+    const std::vector<uint32_t> pix = plan_pixels(plan);
+    for (size_t k = 0; k < pix.size(); k++) out[(size_t)(pix[k] >> 16) * plan.W + (pix[k] & 0xFFFFu)] = per_slot[k];
+}
+
 }  // namespace
 
 struct zr_accum { AccumState st; };
@@ -658,7 +690,7 @@ int zr_accum_reset(zr_accum* a, int first_sample) {
     HIP_OK(hipSetDevice(st.device));
     HIP_OK(hipMemset(st.d_partial.p, 0, std::max<size_t>((size_t)st.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double), 64)));
     HIP_OK(hipDeviceSynchronize());   // the context's streams do not wait for the null stream
-    st.first = first_sample; st.done = 0; st.bound = false;
+    st.first = first_sample; st.done = 0; st.bound = false; st.adaptive = false;
     return ZR_OK;
 }
 
@@ -676,6 +708,7 @@ int zr_render_accumulate(zr_ctx* c, const zr_scene* s, const zr_camera* cam, con
     if (st.bound && (std::memcmp(&key, &st.cam, sizeof key) != 0 || seed != st.seed || s != st.scene))
         return fail(ZR_E_INVALID, "camera, seed or scene differ from the first batch's: zr_accum_reset starts a new frame");
     if ((long long)st.first + st.done + n_samples > 0x7FFFFFFFll) return fail(ZR_E_INVALID, "sample range beyond 2^31");
+    if (st.adaptive) return fail(ZR_E_STATE, "the accumulator holds an adaptive run's per-pixel counts: zr_accum_reset starts a new frame");
     FrameJob job;
     HIP_OK(hipSetDevice(c->device));
     job.plan = st.plan;
@@ -717,6 +750,163 @@ int zr_accum_state(const zr_accum* a, int64_t out[4]) {
     if (!a || !out) return fail(ZR_E_INVALID, "null argument");
     out[0] = a->st.first; out[1] = a->st.done; out[2] = (int64_t)a->st.n_pix; out[3] = (int64_t)a->st.device_bytes();
     return ZR_OK;
+}
+
+// ---- adaptive sampling ----------------------------------------------------------------------------------------------------------------------
+
+int zr_render_adaptive(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, zr_accum* a, const zr_adaptive_params* p,
+                       int collect_counters, volatile const uint8_t* keep_going, zr_adaptive_stats* out) {
+    if (out) std::memset(out, 0, sizeof *out);   // whatever happens below, `out` holds the statistics of the passes that completed
+    if (!p) return fail(ZR_E_INVALID, "null argument");
+    // the parameters first: they need no device and no other argument
+    const int counts[3] = {p->min_samples, p->max_samples, p->step_samples};
+    const char* names[3] = {"min_samples", "max_samples", "step_samples"};
+    for (int k = 0; k < 3; k++)
+        if (counts[k] < 64 || counts[k] % 64 != 0) return fail(ZR_E_INVALID, "%s = %d is not a positive multiple of 64", names[k], counts[k]);
+    if (p->max_samples < p->min_samples) return fail(ZR_E_INVALID, "max_samples %d below min_samples %d", p->max_samples, p->min_samples);
+    if (!(p->threshold >= 0) || !std::isfinite(p->threshold)) return fail(ZR_E_INVALID, "threshold %g is negative or not finite", p->threshold);
+    if (!(p->dark_floor >= 0) || !std::isfinite(p->dark_floor)) return fail(ZR_E_INVALID, "dark_floor %g is negative or not finite", p->dark_floor);
+    if (!c || !s || !cam || !env || !a) return fail(ZR_E_INVALID, "null argument");
+    AccumState& st = a->st;
+    if (st.ctx != c) return fail(ZR_E_INVALID, "accumulator belongs to another context");
+    int rc = scene_ready(c, s, "zr_render_adaptive");
+    if (rc) return rc;
+    const int W = cam->image_width < 1 ? 1 : cam->image_width, H = cam->image_height < 1 ? 1 : cam->image_height;
+    if (W != st.plan.W || H != st.plan.H) return fail(ZR_E_INVALID, "camera of %d x %d px, accumulator of %d x %d", W, H, st.plan.W, st.plan.H);
+    zr_camera key = *cam; key.samples_per_pixel = 0;   // ignored here
+    if (st.bound && (std::memcmp(&key, &st.cam, sizeof key) != 0 || seed != st.seed || s != st.scene))
+        return fail(ZR_E_INVALID, "camera, seed or scene differ from the first batch's: zr_accum_reset starts a new frame");
+    if ((long long)st.first + p->max_samples > 0x7FFFFFFFll) return fail(ZR_E_INVALID, "sample range beyond 2^31");
+    if (st.adaptive) return fail(ZR_E_STATE, "the accumulator holds an adaptive run's per-pixel counts: zr_accum_reset starts a new frame");
+    if (st.done % 64 != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, not a multiple of 64: the noise estimate is not defined", st.done);
+    if (st.done > p->min_samples) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, more than min_samples = %d", st.done, p->min_samples);
+    FrameJob job;
+    HIP_OK(hipSetDevice(c->device));
+    job.plan = st.plan;
+    make_camera(*cam, job.dc);
+    make_env(*env, job.de);
+    if ((rc = check_env(job.de, s))) return rc;
+    job.seed = seed; job.stream = c->stream; job.count = collect_counters != 0; job.keep_going = keep_going;
+    c->last_rounds = 0;
+    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
+    if (st.n_pix == 0) return ZR_OK;
+    // the run's buffers, and the first list: every pixel, in the order the pipeline's own list has (upload_pixel_list: bottom-up shortens the drain)
+    const size_t n_blocks = ((size_t)st.n_pix + 255) / 256;
+    if ((rc = st.d_count.alloc(st.n_pix)) || (rc = st.d_flag.alloc(st.n_pix)) || (rc = st.d_block_active.alloc(n_blocks)) ||
+        (rc = st.d_block_at_max.alloc(n_blocks)) || (rc = st.d_totals.alloc(2)))
+        return rc;
+    for (int k = 0; k < 2; k++) if ((rc = st.d_list[k].alloc(st.n_pix)) || (rc = st.d_slot[k].alloc(st.n_pix))) return rc;
+    {
+        std::vector<uint32_t> pix = plan_pixels(st.plan), slot(pix.size());
+        for (size_t k = 0; k < slot.size(); k++) slot[k] = (uint32_t)k;
+        if (env_double("ZR_STREAM_BOTTOM_UP", 1) != 0) { std::reverse(pix.begin(), pix.end()); std::reverse(slot.begin(), slot.end()); }
+        HIP_OK(hipMemcpy(st.d_list[0].p, pix.data(), pix.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(st.d_slot[0].p, slot.data(), slot.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_OK(hipDeviceSynchronize());   // the context's streams do not wait for the null stream
+    }
+    // counts lie in {min + j * step}: the last of them at or below max_samples is where a pixel that is still noisy stops
+    const int last_count = p->min_samples + (p->max_samples - p->min_samples) / p->step_samples * p->step_samples;
+    zr_adaptive_stats stats{};
+    unsigned long long totals[zr::CTR_WORDS] = {0};
+    uint64_t rounds = 0;
+    const uint64_t id0 = c->render_id;
+    uint32_t n_active = st.n_pix;
+    int cur = 0, count_now = st.done, stop = ZR_OK;
+    std::string stop_msg;
+    while (n_active > 0) {
+        const int target = stats.passes == 0 ? p->min_samples : count_now + p->step_samples;
+        const int n = target - count_now;
+        if (keep_going && *keep_going == 0) { stop = ZR_E_CANCELLED; stop_msg = "adaptive render cancelled after " + std::to_string(stats.passes) + " passes"; break; }
+        HostTimer timer(c);
+        if (n > 0) {   // (0: the accumulator came with min_samples already; pass 0 is then the estimate alone)
+            job.d_list = st.d_list[cur].p; job.n_list = n_active;
+            HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
+            bool flipped = false;
+            rc = render_batch_samples(c, s, job, st.d_list[cur].p, n_active, st.first + count_now, n, timer, &flipped);
+            if (rc) {   // the pass is discarded whole; the accumulator is as the pass before left it
+                stop = rc; stop_msg = zr_host::last_error();
+                if (rc == ZR_E_NOMEM) stop_msg += " (adaptive pass " + std::to_string(stats.passes) + ": lower step_samples" + (stats.passes == 0 ? " / min_samples)" : ")");
+                break;
+            }
+        }
+        timer.begin(job.stream, 3);
+        HIP_OK(zr::launch_adaptive_accumulate(c->d_partial.p, st.d_slot[cur].p, n_active, (uint32_t)n, (uint32_t)(st.first + count_now), st.d_partial.p, st.d_count.p,
+                                              st.d_flag.p, target, last_count, p->threshold, p->dark_floor, job.stream));
+        HIP_OK(zr::launch_adaptive_compact(st.d_flag.p, n_active, st.d_list[cur].p, st.d_slot[cur].p, st.d_list[cur ^ 1].p, st.d_slot[cur ^ 1].p, st.d_block_active.p,
+                                           st.d_block_at_max.p, st.d_totals.p, job.stream));
+        timer.end(job.stream, 3);
+        if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
+        uint32_t h_totals[2] = {0, 0};   // the read-back of a pass: how many pixels go on, how many max_samples stopped (a counting run also reads the counter block)
+        HIP_OK(hipMemcpyAsync(h_totals, st.d_totals.p, sizeof h_totals, hipMemcpyDeviceToHost, job.stream));
+        HIP_OK(hipStreamSynchronize(job.stream));
+        if (n > 0) {
+            st.route = c->last_path;
+            if (job.count) {
+                unsigned long long h[zr::CTR_WORDS];
+                HIP_OK(hipMemcpy(h, c->d_ctr.p, sizeof h, hipMemcpyDeviceToHost));
+                for (int w = 0; w < zr::CTR_WORDS; w++) totals[w] += h[w];
+            }
+            rounds += c->last_rounds;
+        }
+        st.adaptive = true; st.done = target; count_now = target;
+        if (!st.bound) { st.bound = true; st.cam = key; st.seed = seed; st.scene = s; }
+        stats.passes++; stats.samples += (uint64_t)n_active * (uint64_t)n; stats.stopped_at_max += h_totals[1];
+        stats.stopped_by_threshold += n_active - h_totals[0] - h_totals[1];
+        n_active = h_totals[0]; cur ^= 1;
+        if (out) *out = stats;
+    }
+    // one render as far as zr_get_counters is concerned: the totals over all passes, the launches of every pass in its times
+    for (auto& pe : c->pending) if (pe.render_id > id0) pe.render_id = c->render_id;
+    if (job.count) HIP_OK(hipMemcpyAsync(c->d_ctr.p, totals, sizeof totals, hipMemcpyHostToDevice, job.stream));
+    HIP_OK(hipStreamSynchronize(job.stream));
+    c->last_counted = job.count; c->last_rounds = rounds;
+    if (stop != ZR_OK) return fail(stop, "%s", stop_msg.c_str());
+    return ZR_OK;
+}
+
+int zr_accum_error(zr_accum* a, double dark_floor, double* out) {
+    if (!a || !out) return fail(ZR_E_INVALID, "null argument");
+    if (!(dark_floor >= 0) || !std::isfinite(dark_floor)) return fail(ZR_E_INVALID, "dark_floor %g is negative or not finite", dark_floor);
+    AccumState& st = a->st;
+    int rc = query_ready(st, "zr_accum_error");
+    if (rc) return rc;
+    if (!st.adaptive && st.done % 64 != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, not a multiple of 64: the noise estimate is not defined", st.done);
+    HIP_OK(hipSetDevice(st.device));
+    DevBuf<double> d_err;
+    if ((rc = d_err.alloc(st.n_pix))) return rc;
+    HIP_OK(zr::launch_accum_error(st.d_partial.p, st.adaptive ? st.d_count.p : nullptr, st.done, st.n_pix, dark_floor, d_err.p, nullptr));
+    HIP_OK(hipStreamSynchronize(nullptr));
+    std::vector<double> h(st.n_pix);
+    if (st.n_pix) HIP_OK(hipMemcpy(h.data(), d_err.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    scatter_to_frame(st.plan, h, out);
+    return ZR_OK;
+}
+
+int zr_accum_sample_counts(zr_accum* a, int32_t* out) {
+    if (!a || !out) return fail(ZR_E_INVALID, "null argument");
+    AccumState& st = a->st;
+    int rc = query_ready(st, "zr_accum_sample_counts");
+    if (rc) return rc;
+    std::vector<int32_t> h(st.n_pix, (int32_t)st.done);
+    if (st.adaptive && st.n_pix) {
+        HIP_OK(hipSetDevice(st.device));
+        HIP_OK(hipMemcpy(h.data(), st.d_count.p, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    scatter_to_frame(st.plan, h, out);
+    return ZR_OK;
+}
+
+int64_t zr_accum_lane_sums(zr_accum* a, double* out, size_t cap_doubles) {
+    if (!a || (!out && cap_doubles != 0)) return fail(ZR_E_INVALID, "null argument");
+    AccumState& st = a->st;
+    int rc = query_ready(st, "zr_accum_lane_sums");
+    if (rc) return rc;
+    const size_t n = (size_t)st.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL;
+    if (!out) return (int64_t)n;
+    if (cap_doubles < n) return fail(ZR_E_INVALID, "room for %zu doubles, the lane sums are %zu", cap_doubles, n);
+    HIP_OK(hipSetDevice(st.device));
+    if (n) HIP_OK(hipMemcpy(out, st.d_partial.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    return (int64_t)n;
 }
 
 int zr_render_device(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region,

@@ -110,6 +110,37 @@ int zrs_render_dropin_progressive(void* p, int width, int height, int spp, int d
     return 0;
 }
 
+// camera::render with camera::adaptive_threshold set (min_samples and step <= 0 keep the camera's defaults).  counts = W*H ints (camera::sample_counts; left alone when
+// the render was not adaptive), info[0] = current_samples_count after the render (-7 going in), info[1] = passes.  Returns 0, or -1 if the render did not finish.
+int zrs_render_dropin_adaptive(void* p, int width, int height, int spp, int device, double threshold, int min_samples, int step, double* out, int* counts, int* info) {
+    handle* h = (handle*)p;
+    camera cam;
+    const zr_camera& c = h->s.cam;
+    cam.image_width = width > 0 ? width : c.image_width;
+    cam.image_height = height > 0 ? height : c.image_height;
+    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
+    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
+    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
+    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
+    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
+    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
+    cam.seed = h->s.seed; cam.device = device;
+    cam.reset_accumulator();
+    cam.adaptive_threshold = threshold;
+    if (min_samples > 0) cam.adaptive_min_samples = min_samples;
+    if (step > 0) cam.adaptive_step = step;
+    cam.current_samples_count = -7;
+    post_processor post;
+    std::atomic<bool> flag{true};
+    auto bvh_world = make_shared<bvh_node>(h->s.world);
+    cam.render(*bvh_world, h->s.env, post, flag);
+    if (info) { info[0] = cam.current_samples_count; info[1] = cam.passes_rendered; }
+    if (cam.lines_rendered.load() != cam.image_height) return -1;
+    std::memcpy(out, cam.render_accumulator.data(), cam.render_accumulator.size() * sizeof(color));
+    if (counts && !cam.sample_counts.empty()) std::memcpy(counts, cam.sample_counts.data(), cam.sample_counts.size() * sizeof(int));
+    return 0;
+}
+
 // camera::render with global_settings::bvh_debug_mode set (debug_bvh_level = level, bvh_thickness = thickness) through the drop-in API; the
 // settings are restored afterwards.  `aux`, when not null, receives albedo_buffer (which the debug view leaves as reset_accumulator made it).
 // Returns 0, or -1 if the render did not finish.
