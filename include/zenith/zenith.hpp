@@ -1420,6 +1420,14 @@ public:
     int adaptive_min_samples = 64, adaptive_step = 64;
     double adaptive_dark_floor = 0.01;
     std::vector<int> sample_counts;   // extension: samples per pixel of the last adaptive render (row-major like render_accumulator); empty otherwise
+    // extension: with use_denoiser, denoise_buffer comes from the variance-guided filter (zr_denoise_guided with its default parameters) when the
+    // frame came through an accumulator whose counts are multiples of 64 — adaptive_threshold > 0, or samples_per_pass > 0 with samples_per_pixel a multiple
+    // of 64.  variance_buffer then holds the variance of every pixel's mean per channel (zr_accum_variance).  Without such a frame (a one-shot render, another
+    // count) a warning is printed and the plain filter runs.  The reflection / refraction frames have no variance and keep the plain filter.  false: exactly
+    // the render without it.
+    bool denoise_variance_guided = false;
+    std::vector<color> variance_buffer;   // extension: filled by a render with use_denoiser and denoise_variance_guided that had a variance; empty otherwise
+    bool denoise_used_variance = false;   // extension: the last render's denoise_buffer came from the guided filter
     zr_adaptive_stats last_adaptive{};
     zr_counters last_counters{};
 
@@ -1500,6 +1508,15 @@ public:
             zc.vfov = vfov; zc.defocus_angle = defocus_angle; zc.focus_dist = focus_dist;
             for (int k = 0; k < 3; k++) { zc.lookfrom[k] = lookfrom[k]; zc.lookat[k] = lookat[k]; zc.vup[k] = vup[k]; }
             sample_counts.clear();
+            variance_buffer.clear(); denoise_used_variance = false;
+            const bool want_variance = use_denoiser && denoise_variance_guided;
+            // the variance of the accumulator's pixel means, fetched before the accumulator is destroyed
+            auto fetch_variance = [&](zr_accum* acc) {
+                variance_buffer.assign((size_t)image_width * image_height, color(0, 0, 0));
+                const int vrc = zr_accum_variance(acc, reinterpret_cast<double*>(variance_buffer.data()));
+                if (vrc != ZR_OK) variance_buffer.clear();
+                return vrc;
+            };
             if (global_settings::bvh_debug_mode) {
                 // the debug view fills render_accumulator only: the AOV, split-pass and denoise buffers stay as reset_accumulator left them
                 // (the reference would feed them the debug frame's records)
@@ -1529,6 +1546,7 @@ public:
                         int qrc = zr_accum_resolve(acc, reinterpret_cast<double*>(render_accumulator.data()));
                         if (qrc == ZR_OK) qrc = zr_accum_sample_counts(acc, reinterpret_cast<int32_t*>(sample_counts.data()));
                         if (qrc == ZR_OK) qrc = zr_accum_state(acc, st4);
+                        if (qrc == ZR_OK && arc == ZR_OK && want_variance) qrc = fetch_variance(acc);
                         if (qrc != ZR_OK) rc = qrc;
                         else { current_samples_count = (int)st4[1]; passes_rendered = (int)last_adaptive.passes; }
                     }
@@ -1551,6 +1569,7 @@ public:
                     lines_rendered = current_samples_count < spp ? (int)((long long)image_height * current_samples_count / spp) : image_height;
                     if (current_samples_count < spp && !render_flag.load()) { rc = ZR_E_CANCELLED; break; }
                 }
+                if (rc == ZR_OK && acc && want_variance && spp % 64 == 0) rc = fetch_variance(acc);
                 if (acc) zr_accum_destroy(acc);
             } else
             rc = zr_render(ctx, sc, &zc, &zenv, seed, nullptr, 0, reinterpret_cast<double*>(render_accumulator.data()),
@@ -1595,7 +1614,15 @@ public:
             const std::vector<color>& ga = use_albedo_buffer ? albedo_buffer : guide_albedo;
             const std::vector<color>& gn = use_normal_buffer ? normal_buffer : guide_normal;
             denoise_buffer = render_accumulator;
-            bool ok = denoise(denoise_buffer, ga, gn);
+            bool ok;
+            if (denoise_variance_guided && variance_buffer.size() == render_accumulator.size()) {
+                ok = denoise_guided(denoise_buffer, variance_buffer, ga, gn);
+                denoise_used_variance = ok;
+            } else {
+                if (denoise_variance_guided)
+                    std::cerr << "[zenith] denoise_variance_guided ignored: no variance (it needs adaptive_threshold, or samples_per_pass with a multiple of 64 samples)\n";
+                ok = denoise(denoise_buffer, ga, gn);
+            }
             if (ok && use_reflection) {
                 ok = denoise(reflection_buffer, ga, gn);
                 if (ok && post.use_sharpening) post.apply_sharpening(reflection_buffer, image_width, image_height, post.sharpen_amount);
@@ -1617,6 +1644,19 @@ private:
         double* p = reinterpret_cast<double*>(buffer.data());
         const int rc = ctx ? zr_denoise(ctx, &dp, p, reinterpret_cast<const double*>(albedo.data()), reinterpret_cast<const double*>(normal.data()),
                                         nullptr, image_width, image_height, p)
+                           : ZR_E_DEVICE;
+        if (rc != ZR_OK) std::cerr << "[zenith] denoise failed: " << zr_last_error() << "\n";
+        return rc == ZR_OK;
+    }
+    // the variance-guided filter with zr_denoise_guided's default parameters: `buffer` in place, `variance` left as zr_accum_variance gave it
+    bool denoise_guided(std::vector<color>& buffer, const std::vector<color>& variance, const std::vector<color>& albedo, const std::vector<color>& normal) const {
+        zenith::context_lease lease(device);
+        zr_ctx* ctx = lease;
+        const zr_denoise_guided_params dp{ZR_DENOISE_GUIDED_DEFAULT_ITERATIONS, ZR_DENOISE_GUIDED_DEFAULT_DEMODULATE, ZR_DENOISE_GUIDED_DEFAULT_SIGMA_VARIANCE,
+                                          ZR_DENOISE_GUIDED_DEFAULT_SIGMA_NORMAL, ZR_DENOISE_GUIDED_DEFAULT_SIGMA_ALBEDO, 0.0f, ZR_DENOISE_GUIDED_DEFAULT_EPSILON};
+        double* p = reinterpret_cast<double*>(buffer.data());
+        const int rc = ctx ? zr_denoise_guided(ctx, &dp, p, reinterpret_cast<const double*>(variance.data()), reinterpret_cast<const double*>(albedo.data()),
+                                               reinterpret_cast<const double*>(normal.data()), nullptr, image_width, image_height, p, nullptr)
                            : ZR_E_DEVICE;
         if (rc != ZR_OK) std::cerr << "[zenith] denoise failed: " << zr_last_error() << "\n";
         return rc == ZR_OK;

@@ -453,6 +453,55 @@ typedef struct zr_denoise_params {
 #define ZR_DENOISE_DEFAULT_SIGMA_ALBEDO 0.25f
 int zr_denoise(zr_ctx*, const zr_denoise_params*, const double* color, const double* albedo, const double* normal,
                const double* zdepth, int width, int height, double* out);
+
+/* ---- variance-guided denoising: the filter above with the colour weight driven by each pixel's own noise ----
+ * zr_accum_variance   the variance of every pixel's mean per channel, W*H*3 doubles laid out like out_rgb; only the plan's pixels
+ *                     are written.  With k = 64 m samples in a pixel and lane sums S_l, per channel (FP64, in this order, no contraction):
+ *                       T = sum S_l (xor butterfly 32, 16, ... 1);  mu = T * (1.0 / 64);  d_l = S_l - mu;
+ *                       Q = sum d_l * d_l (same butterfly);  var = Q * (1.0 / 63) * (1.0 / 64) * (1.0 / m) * (1.0 / m)
+ *                     0 exactly when all lanes are equal, +inf when T is not finite.  zr_accum_error's state rules: ZR_E_INVALID for
+ *                     NULL, ZR_E_STATE while nothing has been rendered or on a uniform accumulator whose done is not a multiple
+ *                     of 64; a non-uniform accumulator (after zr_render_adaptive) uses each pixel's own count.
+ * zr_denoise_guided   the spatial stage of SVGF (Schied et al., HPG 2017, section 4.4) laid over zr_denoise: cleaning, normal decoding,
+ *                     demodulation, taps, w_n, w_a, w_z and t(x) are zr_denoise's.  The variance frame is cleaned like the colour
+ *                     (NaN / Inf -> 0), negative values count as 0, and with demodulate_albedo it is divided by albedo^2.  At every
+ *                     level, with r = 1 / (1 + max(luminance(d), 0)) and s_q = r_q^2 (V_q.r + V_q.g + V_q.b) — the expected squared length
+ *                     of the noise of t(d_q) — and s^_p the 3 x 3 Gaussian ([1 2 1] x [1 2 1] / 16, unit spacing at every level, taps off
+ *                     the frame skipped and the weights renormalised) of s around p, the colour term of a tap's weight is
+ *                       exp(-|t(d_p) - t(d_q)|^2 / (sigma_variance^2 s^_p + epsilon))
+ *                     in place of exp(-|..|^2 / (sigma_color^2 4^-level)): colour differences are measured in standard deviations of the
+ *                     pixel's own noise.  Colour and variance are filtered together, d'_p = sum w d_q / sum w and
+ *                     V'_p = sum w^2 V_q / (sum w)^2 per channel.  A pixel without variance (background, a converged flat wall) has the
+ *                     denominator epsilon: it keeps its value unless its neighbours agree with it.  `variance` may come from
+ *                     zr_accum_variance or from anywhere else.  All frames W*H*3 doubles in host memory; zdepth and out_variance
+ *                     may be NULL, out may equal color and out_variance may equal variance.  ZR_E_INVALID, before any device call:
+ *                     NULL, sizes as zr_denoise, iterations outside 0..8, a sigma or epsilon that is not positive and finite
+ *                     (sigma_depth: >= 0, 0 = no depth guide).  FP32, deterministic; tests/denoise_guided_model.py restates it.
+ * zr_accum_denoise    zr_denoise_guided(zr_accum_resolve(), zr_accum_variance(), ...) bit for bit, with colour and variance resolved
+ *                     on the device straight into the filter: only the guides go up and only the result comes down.  Whole-frame
+ *                     accumulators only (ZR_E_INVALID for one made with a rectangle or tile_mod > 1); then zr_accum_variance's state
+ *                     rules.  out_variance may be NULL. */
+typedef struct zr_denoise_guided_params {
+    int32_t iterations;                 /* levels, 0..8 */
+    int32_t demodulate_albedo;          /* filter c / albedo (and variance / albedo^2) */
+    float sigma_variance;               /* > 0: colour differences are measured in standard deviations of the pixel's own noise */
+    float sigma_normal, sigma_albedo, sigma_depth;   /* as zr_denoise */
+    float epsilon;                      /* > 0, finite: added to the variance term's denominator */
+} zr_denoise_guided_params;
+/* defaults: the setting of scripts/dev/denoise_guided_sweep.py with the best worse-of-two-scenes factor on 64-spp accumulators of
+ * cfg5 and mix0 against 4096 spp; what camera::render uses with denoise_variance_guided.  Demodulation is on here: the
+ * albedo pass of a 64-spp frame is clean enough to divide by, and it won on cfg5 at every sigma_variance. */
+#define ZR_DENOISE_GUIDED_DEFAULT_ITERATIONS 4
+#define ZR_DENOISE_GUIDED_DEFAULT_DEMODULATE 1
+#define ZR_DENOISE_GUIDED_DEFAULT_SIGMA_VARIANCE 3.0f
+#define ZR_DENOISE_GUIDED_DEFAULT_SIGMA_NORMAL 64.0f
+#define ZR_DENOISE_GUIDED_DEFAULT_SIGMA_ALBEDO 0.25f
+#define ZR_DENOISE_GUIDED_DEFAULT_EPSILON 1e-8f
+int zr_accum_variance(zr_accum*, double* out_var);
+int zr_denoise_guided(zr_ctx*, const zr_denoise_guided_params*, const double* color, const double* variance, const double* albedo,
+                      const double* normal, const double* zdepth, int width, int height, double* out, double* out_variance);
+int zr_accum_denoise(zr_accum*, const zr_denoise_guided_params*, const double* albedo, const double* normal, const double* zdepth,
+                     double* out, double* out_variance);
 /* post_processor::apply_sharpening (color_processing.hpp:207-227) on its own: interior pixels become
  * c (1 - amount) + (5 c - the four neighbours) amount, border pixels are copied.  Double in, double out, byte-exact with
  * the reference; amount <= 0 copies.  Host memory, W*H*3 doubles; out may equal in. */

@@ -105,6 +105,22 @@ class DenoiseParams(C.Structure):
         return p
 
 
+class DenoiseGuidedParams(C.Structure):
+    """zr_denoise_guided_params: the variance-guided form of the a-trous denoiser (include/zr_capi.h)"""
+    _fields_ = [("iterations", C.c_int32), ("demodulate_albedo", C.c_int32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float), ("epsilon", C.c_float)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """ZR_DENOISE_GUIDED_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with denoise_variance_guided); depth guide off"""
+        p = cls(4, 1, 3.0, 64.0, 0.25, 0.0, 1e-8)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"DenoiseGuidedParams has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class BvhDebugParams(C.Structure):
     """zr_bvh_debug_params: global_settings::debug_bvh_level / bvh_thickness of the BVH debug view (include/zr_capi.h, DESIGN §10)"""
     _fields_ = [("level", C.c_int32), ("thickness", C.c_float)]
@@ -224,6 +240,7 @@ CAPI_SYMBOLS = [
     "zr_accum_create", "zr_accum_destroy", "zr_accum_reset", "zr_render_accumulate", "zr_accum_resolve", "zr_accum_resolve_device", "zr_accum_state",
     "zr_render_adaptive", "zr_accum_error", "zr_accum_sample_counts", "zr_accum_lane_sums",
     "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
+    "zr_accum_variance", "zr_denoise_guided", "zr_accum_denoise",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
@@ -278,6 +295,9 @@ def load():
     lib.zr_analyze_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(ImageStats)]
     lib.zr_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, i32, i32, vp]
     lib.zr_sharpen_frame.argtypes = [vp, vp, i32, i32, C.c_double, vp]
+    lib.zr_accum_variance.argtypes = [vp, vp]
+    lib.zr_denoise_guided.argtypes = [vp, C.POINTER(DenoiseGuidedParams), vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.zr_accum_denoise.argtypes = [vp, C.POINTER(DenoiseGuidedParams), vp, vp, vp, vp, vp]
     lib.zr_render_bvh_debug.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), C.POINTER(BvhDebugParams), vp, vp, vp]
     lib.zr_trace_bvh_debug.argtypes = [vp, vp, C.POINTER(BvhDebugParams), vp, C.c_size_t, C.c_double, u64, u64, C.c_uint32, vp]
     lib.zr_scene_tree_boxes.argtypes = [vp, vp, C.c_size_t]
@@ -417,6 +437,24 @@ class DemoScene:
             raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
         return outs
 
+    def render_dropin_denoise_guided(self, threshold, samples_per_pass=0, guided=True, width=0, height=0, spp=0, device=0):
+        """camera::render with use_denoiser and (guided) denoise_variance_guided, adaptively when threshold > 0, progressively when
+        samples_per_pass > 0, else in one shot: dict of render_accumulator, denoise_buffer, variance_buffer ((H, W, 3) float64; all -1 when the
+        render left variance_buffer empty) and "guided" (whether the guided filter made denoise_buffer)"""
+        w = width or self.camera.image_width
+        h = height or self.camera.image_height
+        names = ("render_accumulator", "denoise_buffer", "variance_buffer")
+        outs = {k: np.zeros((h, w, 3), dtype=np.float64) for k in names}
+        info = (C.c_int * 2)()
+        lib = load_scenes()
+        lib.zrs_render_dropin_denoise_guided.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 4
+        rc = lib.zrs_render_dropin_denoise_guided(self._h, width, height, spp, device, float(threshold), int(samples_per_pass), 1 if guided else 0,
+                                                  *[outs[k].ctypes.data for k in names], info)
+        if rc != 0:
+            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        outs["guided"] = bool(info[0])
+        return outs
+
     def render_dropin_bvh_debug(self, level, thickness, width=0, height=0, spp=0, device=0):
         """camera::render with global_settings::bvh_debug_mode set through include/zenith/zenith.hpp: (render_accumulator,
         albedo_buffer) as (H, W, 3) float64 (the debug view leaves the AOV buffers as reset_accumulator made them)"""
@@ -515,6 +553,27 @@ class Context:
                                    zdepth.ctypes.data if zdepth is not None else None, w, h, out.ctypes.data))
         return out
 
+    def denoise_guided(self, params, color, variance, albedo, normal, zdepth=None, out=None, out_variance=None):
+        """zr_denoise_guided (the a-trous filter with variance-driven colour weights): (H, W, 3) float64 frames -> (frame, variance), both
+        (H, W, 3) float64.  `out` may be `color` itself and `out_variance` may be `variance` itself (in place)."""
+        color = np.ascontiguousarray(color, dtype=np.float64)
+        h, w = color.shape[:2]
+        frames = [np.ascontiguousarray(g, dtype=np.float64) for g in (variance, albedo, normal)]
+        if zdepth is not None:
+            zdepth = np.ascontiguousarray(zdepth, dtype=np.float64)
+        for g in frames + ([zdepth] if zdepth is not None else []):
+            if g.shape != color.shape:
+                raise ValueError(f"frame shape {g.shape} differs from the colour frame's {color.shape}")
+        if out is None:
+            out = np.zeros_like(color)
+        if out_variance is None:
+            out_variance = np.zeros_like(color)
+        for o in (out, out_variance):
+            assert o.dtype == np.float64 and o.flags.c_contiguous and o.shape == color.shape
+        _check(self.lib.zr_denoise_guided(self._c, C.byref(params), color.ctypes.data, frames[0].ctypes.data, frames[1].ctypes.data, frames[2].ctypes.data,
+                                          zdepth.ctypes.data if zdepth is not None else None, w, h, out.ctypes.data, out_variance.ctypes.data))
+        return out, out_variance
+
     def sharpen(self, frame, amount, out=None):
         """post_processor::apply_sharpening on the device: (H, W, 3) float64 -> (H, W, 3) float64"""
         frame = np.ascontiguousarray(frame, dtype=np.float64)
@@ -592,6 +651,29 @@ class Accumulator:
         assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.height, self.width)
         _check(self.lib.zr_accum_error(self._a, C.c_double(dark_floor), out.ctypes.data))
         return out
+
+    def variance(self, out=None):
+        """the variance of every pixel's mean per channel (zr_accum_variance): (H, W, 3) float64; only the region's pixels are written"""
+        if out is None:
+            out = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.height, self.width, 3)
+        _check(self.lib.zr_accum_variance(self._a, out.ctypes.data))
+        return out
+
+    def denoise(self, params, albedo, normal, zdepth=None):
+        """zr_accum_denoise: Context.denoise_guided(params, resolve(), variance(), ...) bit for bit, with colour and variance resolved on the device;
+        returns (frame, variance).  Whole-frame accumulators only."""
+        shape = (self.height, self.width, 3)
+        guides = [np.ascontiguousarray(g, dtype=np.float64) for g in (albedo, normal)]
+        if zdepth is not None:
+            zdepth = np.ascontiguousarray(zdepth, dtype=np.float64)
+        for g in guides + ([zdepth] if zdepth is not None else []):
+            if g.shape != shape:
+                raise ValueError(f"guide shape {g.shape} differs from the accumulator's frame {shape}")
+        out = np.zeros(shape, dtype=np.float64); out_variance = np.zeros(shape, dtype=np.float64)
+        _check(self.lib.zr_accum_denoise(self._a, C.byref(params), guides[0].ctypes.data, guides[1].ctypes.data,
+                                         zdepth.ctypes.data if zdepth is not None else None, out.ctypes.data, out_variance.ctypes.data))
+        return out, out_variance
 
     def sample_counts(self, out=None):
         """samples per pixel: (H, W) int32; only the region's pixels are written"""

@@ -1,5 +1,6 @@
 // zr_adaptive.hip — adaptive sampling over a zr_accum: the noise estimate of a pixel from its 64 lane sums, the pass kernel that adds a pass's
-// samples to the still-active pixels and decides which of them go on, the stable compaction of the active list, and the resolve with a sample count per pixel.
+// samples to the still-active pixels and decides which of them go on, the stable compaction of the active list, the resolve with a sample count per pixel, and
+// the per-channel variance of a pixel's mean that the variance-guided denoiser reads (tests/denoise_guided_model.py restates it).
 // Compiled without contraction (csrc/Makefile): tests/adaptive_model.py restates the estimate operation for operation, and the decisions of an adaptive run
 // are exactly `err > threshold` on those numbers.  No atomics: the next pass's pixel list depends on the flags alone, never on the order waves ran in.
 #include <hip/hip_runtime.h>
@@ -70,6 +71,34 @@ __global__ __launch_bounds__(256) void accum_error(const double* __restrict__ pa
     const double* q = partial + (size_t)i * 192 + lane;
     const double e = noise_estimate(q[0], q[64], q[128], count ? count[i] : uniform_count, dark_floor);
     if (lane == 0) err[i] = e;
+}
+
+// The variance of every slot's mean, per channel (zr_accum_variance), into the slot's pixel of a frame W wide: with `count` = 64 m samples the 64
+// lane sums of a channel are 64 equally weighted, independent estimates of m times the pixel, so
+//   T = sum S_l;  mu = T * (1.0 / 64);  d_l = S_l - mu;  Q = sum d_l * d_l;  var = Q * (1.0 / 63) * (1.0 / 64) * (1.0 / m) * (1.0 / m)
+// (both sums by wave_total).  All lanes equal: exactly 0.  A non-finite total: +inf.  count: per slot, or null for `uniform_count` everywhere.
+__global__ __launch_bounds__(256) void accum_variance(const double* __restrict__ partial, const uint32_t* __restrict__ pixels, const int32_t* __restrict__ count,
+                                                       int uniform_count, uint32_t n_pix, int W, double* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i >= n_pix) return;   // (a whole wave: the butterflies below see all 64 lanes)
+    const double* q = partial + (size_t)i * 192 + lane;
+    const double inv_m = 1.0 / (double)((count ? count[i] : uniform_count) / 64);
+    double var[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double S = q[64 * c];
+        const double T = wave_total(S);
+        const double mu = T * (1.0 / 64);
+        const double d = S - mu;
+        const double Q = wave_total(d * d);
+        var[c] = isfinite(T) ? Q * (1.0 / 63) * (1.0 / 64) * inv_m * inv_m : __longlong_as_double(0x7FF0000000000000ll);
+    }
+    if (lane == 0) {
+        const uint32_t pk = pixels[i];
+        double* o = out + ((size_t)(pk >> 16) * W + (pk & 0xFFFFu)) * 3;
+        o[0] = var[0]; o[1] = var[1]; o[2] = var[2];
+    }
 }
 
 // accum_resolve (zr_stream.hip) with 1.0 / count[pixel]: same butterflies, same asc_lanes rule
@@ -173,6 +202,13 @@ hipError_t launch_adaptive_compact(const uint32_t* flag, uint32_t n_list, const 
 hipError_t launch_accum_error(const double* partial, const int32_t* count, int uniform_count, uint32_t n_pix, double dark_floor, double* err, hipStream_t stream) {
     if (n_pix == 0) return hipSuccess;
     hipLaunchKernelGGL(accum_error, dim3((n_pix + 3) / 4), dim3(256), 0, stream, partial, count, uniform_count, n_pix, dark_floor, err);
+    return hipGetLastError();
+}
+
+hipError_t launch_accum_variance(const double* partial, const uint32_t* pixels, const int32_t* count, int uniform_count, uint32_t n_pix, int W, double* out,
+                                 hipStream_t stream) {
+    if (n_pix == 0) return hipSuccess;
+    hipLaunchKernelGGL(accum_variance, dim3((n_pix + 3) / 4), dim3(256), 0, stream, partial, pixels, count, uniform_count, n_pix, W, out);
     return hipGetLastError();
 }
 

@@ -23,6 +23,20 @@
 // w = 1 when n carries information).  A plain gather: the 25 taps of a 16 x 16 block come from L2 / MALL.  Compiled with
 // -ffp-contract=off, so that the NumPy model follows the arithmetic operation for operation; only expf / exp2f / log2f differ
 // from NumPy's (an ulp or two).
+//
+// The variance-guided form (zr_denoise_guided; tests/denoise_guided_model.py) is the spatial stage of SVGF (Schied et al.,
+// HPG 2017, §4.4) laid over the filter above.  It runs denoise_pack / denoise_unpack unchanged for colour and guides and adds
+//   guided_pack    V = max(clean(variance), 0) / (a' a')  per channel (a' = 1 without demodulation)
+//   guided_atrous  the level kernel with the colour term |t(d_p) - t(d_q)|^2 / (sigma_v^2 s^_p + eps) in place of |..|^2 / (sigma_c^2 4^-i):
+//                  s_q = r_q^2 (V_q.x + V_q.y + V_q.z) is the expected squared length of the noise of t(d_q), s^_p its 3 x 3 Gaussian
+//                  ([1 2 1] x [1 2 1] / 16, unit spacing at every level, taps off the frame skipped, renormalised by the weights used);
+//                  d'_p = sum w d_q / sum w and V'_p = sum w^2 V_q / (sum w)^2, colour and variance ping-pong together
+//   guided_unpack  out_variance = V' a' a', widened to double
+// As evaluated: whoever writes a variance writes s = (r r) ((V.x + V.y) + V.z) into its .w, r being the .w of the colour written beside it.
+// Per pixel: gs = sum g s_k, gw = sum g over the 3 x 3 taps inside the frame (ky outer, kx inner, g = g1(kx) g1(ky), g1 = 1/4, 1/2, 1/4),
+// ic = 1 / (sv2 (gs / gw) + eps) with sv2 = sigma_v sigma_v taken on the host — one reciprocal per pixel.  Per tap arg and w exactly as
+// above with ic for lv.inv_c; then sx += w d_q.x ..., w2 = w w, vx += w2 V_q.x ..., sw += w.  At the end d' = sx / sw ...,
+// ss = sw sw, V' = vx / ss ....  A buffer more per tap (float4 variance) and nine float4 per pixel on top of the plain level kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -140,6 +154,136 @@ hipError_t launch_denoise(const double* d_color, const double* d_albedo, const d
         float4* t = cur; cur = nxt; nxt = t;
     }
     hipLaunchKernelGGL(denoise_unpack, grid, block, 0, stream, (const float4*)cur, (const float4*)d_g0, W, H, demod, d_out);
+    return hipGetLastError();
+}
+
+// ---- the variance-guided form (the file header's second part) ---------------------------------------------------------
+
+namespace {
+
+struct GuidedLevel {
+    float sv2;        // sigma_v^2
+    float eps;
+    float inv_a;      // 1 / sigma_a^2
+    float inv_z;      // 1 / sigma_z with the depth guide on, else 0
+    float sigma_n;
+    int step;         // 2^i
+};
+
+// a variance with s = r^2 (V.x + V.y + V.z) in .w, r being the .w of the colour it belongs to
+__device__ __forceinline__ float4 with_spread(float vx, float vy, float vz, float r) { return make_float4(vx, vy, vz, (r * r) * ((vx + vy) + vz)); }
+
+// after denoise_pack: col holds the (demodulated) colour with r, g0 the cleaned albedo
+__global__ __launch_bounds__(256) void guided_pack(const double* __restrict__ variance, const float4* __restrict__ col, const float4* __restrict__ g0, int W,
+                                                   int H, int demodulate, float4* __restrict__ var) {
+    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
+    if (i >= W || j >= H) return;
+    const size_t p = (size_t)j * W + i;
+    float vx = fmaxf(clean(variance[3 * p]), 0.0f), vy = fmaxf(clean(variance[3 * p + 1]), 0.0f), vz = fmaxf(clean(variance[3 * p + 2]), 0.0f);
+    if (demodulate) {
+        const float4 a = g0[p];
+        const float ax = a.x > 1e-3f ? a.x : 1.0f, ay = a.y > 1e-3f ? a.y : 1.0f, az = a.z > 1e-3f ? a.z : 1.0f;
+        vx = vx / (ax * ax); vy = vy / (ay * ay); vz = vz / (az * az);
+    }
+    var[p] = with_spread(vx, vy, vz, col[p].w);
+}
+
+__global__ __launch_bounds__(256) void guided_atrous(const float4* __restrict__ in, const float4* __restrict__ vin, const float4* __restrict__ g0,
+                                                     const float4* __restrict__ g1, int W, int H, GuidedLevel lv, float4* __restrict__ out,
+                                                     float4* __restrict__ vout) {
+    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
+    if (i >= W || j >= H) return;
+    const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    const float g[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
+    const size_t p = (size_t)j * W + i;
+    // the pixel's own noise in tone-compressed space, smoothed over 3 x 3 at unit spacing
+    float gs = 0.0f, gw = 0.0f;
+#pragma unroll
+    for (int ky = -1; ky <= 1; ky++) {
+        const int qj = j + ky;
+        if (qj < 0 || qj >= H) continue;
+#pragma unroll
+        for (int kx = -1; kx <= 1; kx++) {
+            const int qi = i + kx;
+            if (qi < 0 || qi >= W) continue;
+            const float gk = g[kx + 1] * g[ky + 1];
+            gs = gs + gk * vin[(size_t)qj * W + qi].w;
+            gw = gw + gk;
+        }
+    }
+    const float inv_c = 1.0f / (lv.sv2 * (gs / gw) + lv.eps);
+    const float4 cp = in[p], ap = g0[p], np = g1[p];
+    const float tpx = cp.x * cp.w, tpy = cp.y * cp.w, tpz = cp.z * cp.w;
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f, vx = 0.0f, vy = 0.0f, vz = 0.0f;
+#pragma unroll
+    for (int ky = -2; ky <= 2; ky++) {
+        const int qj = j + ky * lv.step;
+        if (qj < 0 || qj >= H) continue;
+#pragma unroll
+        for (int kx = -2; kx <= 2; kx++) {
+            const int qi = i + kx * lv.step;
+            if (qi < 0 || qi >= W) continue;
+            const size_t q = (size_t)qj * W + qi;
+            const float4 cq = in[q], vq = vin[q], aq = g0[q], nq = g1[q];
+            const float ex = tpx - cq.x * cq.w, ey = tpy - cq.y * cq.w, ez = tpz - cq.z * cq.w;
+            const float bx = ap.x - aq.x, by = ap.y - aq.y, bz = ap.z - aq.z;
+            const float arg = (ex * ex + ey * ey + ez * ez) * inv_c + (bx * bx + by * by + bz * bz) * lv.inv_a + fabsf(ap.w - aq.w) * lv.inv_z;
+            float wn = 1.0f;
+            if (np.w != 0.0f && nq.w != 0.0f) wn = exp2f(lv.sigma_n * log2f(fmaxf(0.0f, np.x * nq.x + np.y * nq.y + np.z * nq.z)));
+            const float w = h[kx + 2] * h[ky + 2] * expf(-arg) * wn;
+            const float w2 = w * w;
+            sx = sx + w * cq.x; sy = sy + w * cq.y; sz = sz + w * cq.z;
+            vx = vx + w2 * vq.x; vy = vy + w2 * vq.y; vz = vz + w2 * vq.z;
+            sw = sw + w;
+        }
+    }
+    const float4 d = with_tone(sx / sw, sy / sw, sz / sw);
+    const float ss = sw * sw;
+    out[p] = d;
+    vout[p] = with_spread(vx / ss, vy / ss, vz / ss, d.w);
+}
+
+__global__ __launch_bounds__(256) void guided_unpack(const float4* __restrict__ var, const float4* __restrict__ g0, int W, int H, int demodulate,
+                                                     double* __restrict__ out) {
+    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
+    if (i >= W || j >= H) return;
+    const size_t p = (size_t)j * W + i;
+    float4 v = var[p];
+    if (demodulate) {
+        const float4 a = g0[p];
+        const float ax = a.x > 1e-3f ? a.x : 1.0f, ay = a.y > 1e-3f ? a.y : 1.0f, az = a.z > 1e-3f ? a.z : 1.0f;
+        v.x = v.x * (ax * ax); v.y = v.y * (ay * ay); v.z = v.z * (az * az);
+    }
+    out[3 * p] = (double)v.x; out[3 * p + 1] = (double)v.y; out[3 * p + 2] = (double)v.z;
+}
+
+}  // namespace
+
+// launch_denoise's buffers plus d_variance (W*H*3 doubles), the variance ping-pong d_var0 / d_var1 (W*H float4) and d_out_var (W*H*3
+// doubles, may be null, may be d_variance).  The caller has validated the parameters (zr_denoise_guided).
+hipError_t launch_denoise_guided(const double* d_color, const double* d_variance, const double* d_albedo, const double* d_normal, const double* d_zdepth, int W,
+                                 int H, const zr_denoise_guided_params& dp, float4* d_col0, float4* d_col1, float4* d_var0, float4* d_var1, float4* d_g0,
+                                 float4* d_g1, double* d_out, double* d_out_var, hipStream_t stream) {
+    const dim3 block(16, 16), grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
+    const int demod = dp.demodulate_albedo ? 1 : 0;
+    hipLaunchKernelGGL(denoise_pack, grid, block, 0, stream, d_color, d_albedo, d_normal, d_zdepth, W, H, demod, d_col0, d_g0, d_g1);
+    hipLaunchKernelGGL(guided_pack, grid, block, 0, stream, d_variance, (const float4*)d_col0, (const float4*)d_g0, W, H, demod, d_var0);
+    float4 *cur = d_col0, *nxt = d_col1, *vcur = d_var0, *vnxt = d_var1;
+    for (int it = 0; it < dp.iterations; it++) {
+        GuidedLevel lv;
+        lv.sv2 = dp.sigma_variance * dp.sigma_variance;
+        lv.eps = dp.epsilon;
+        lv.inv_a = 1.0f / (dp.sigma_albedo * dp.sigma_albedo);
+        lv.inv_z = d_zdepth && dp.sigma_depth > 0.0f ? 1.0f / dp.sigma_depth : 0.0f;
+        lv.sigma_n = dp.sigma_normal;
+        lv.step = 1 << it;
+        hipLaunchKernelGGL(guided_atrous, grid, block, 0, stream, (const float4*)cur, (const float4*)vcur, (const float4*)d_g0, (const float4*)d_g1, W, H, lv,
+                           nxt, vnxt);
+        float4* t = cur; cur = nxt; nxt = t;
+        t = vcur; vcur = vnxt; vnxt = t;
+    }
+    hipLaunchKernelGGL(denoise_unpack, grid, block, 0, stream, (const float4*)cur, (const float4*)d_g0, W, H, demod, d_out);
+    if (d_out_var) hipLaunchKernelGGL(guided_unpack, grid, block, 0, stream, (const float4*)vcur, (const float4*)d_g0, W, H, demod, d_out_var);
     return hipGetLastError();
 }
 

@@ -127,6 +127,9 @@ hipError_t launch_adaptive_compact(const uint32_t* flag, uint32_t n_list, const 
 hipError_t launch_accum_error(const double* partial, const int32_t* count, int uniform_count, uint32_t n_pix, double dark_floor, double* err, hipStream_t stream);
 hipError_t launch_accum_resolve_counts(const double* partial, const uint32_t* pixels, const int32_t* count, uint32_t n_pix, int W, int asc_lanes, double* out,
                                        hipStream_t stream);
+// the per-channel variance of every slot's mean into the listed pixels of `out` (frame width W, 3 doubles a pixel; count as launch_accum_error's)
+hipError_t launch_accum_variance(const double* partial, const uint32_t* pixels, const int32_t* count, int uniform_count, uint32_t n_pix, int W, double* out,
+                                 hipStream_t stream);
 // closest hits of n rays in [0.001, inf) through the EXTEND kernel on ctx.streams[0]; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes
 hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, void* pool,
                         const StreamContext& ctx, int leaf_level);
@@ -141,6 +144,11 @@ hipError_t launch_sharpen(const double* d_in, double* d_out, int W, int H, doubl
 hipError_t launch_denoise(const double* d_color, const double* d_albedo, const double* d_normal, const double* d_zdepth, int W, int H,
                           const zr_denoise_params& dp, float4* d_col0, float4* d_col1, float4* d_g0, float4* d_g1, double* d_out,
                           hipStream_t stream);
+// the variance-guided form (zr_denoise_guided): d_variance W*H*3 doubles; d_var0 / d_var1 W*H float4 scratch beside the colour's; d_out_var (may be null, may
+// be d_variance) receives the filtered variance
+hipError_t launch_denoise_guided(const double* d_color, const double* d_variance, const double* d_albedo, const double* d_normal, const double* d_zdepth, int W,
+                                 int H, const zr_denoise_guided_params& dp, float4* d_col0, float4* d_col1, float4* d_var0, float4* d_var1, float4* d_g0,
+                                 float4* d_g1, double* d_out, double* d_out_var, hipStream_t stream);
 hipError_t launch_bvh_debug(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, int level, float thickness, double* out,
                             hipStream_t stream);
 hipError_t launch_trace_bvh_debug(const DScene& sc, const double* rays, size_t n, double tmin, uint64_t seed, uint64_t pixel, uint32_t bounce, int level,

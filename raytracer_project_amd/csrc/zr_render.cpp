@@ -1083,6 +1083,105 @@ int zr_denoise(zr_ctx* c, const zr_denoise_params* dp, const double* color, cons
     return ZR_OK;
 }
 
+// ---- variance-guided denoising ------------------------------------------------------------------------------------------------------------
+
+}  // extern "C"
+
+namespace {
+
+// the checks of a zr_denoise_guided_params, which need no device
+int check_guided_params(const zr_denoise_guided_params* dp) {
+    if (dp->iterations < 0 || dp->iterations > 8) return fail(ZR_E_INVALID, "denoise iterations %d outside 0..8", dp->iterations);
+    auto positive = [](float v) { return v > 0.0f && std::isfinite(v); };
+    if (!positive(dp->sigma_variance) || !positive(dp->sigma_normal) || !positive(dp->sigma_albedo) || !(dp->sigma_depth >= 0.0f) || !std::isfinite(dp->sigma_depth))
+        return fail(ZR_E_INVALID, "denoise sigmas must be positive and finite (sigma_depth: >= 0, 0 = no depth guide)");
+    if (!positive(dp->epsilon)) return fail(ZR_E_INVALID, "denoise epsilon %g is not positive and finite", (double)dp->epsilon);
+    return ZR_OK;
+}
+
+// what the queries of the variance share (zr_accum_variance, zr_accum_denoise): zr_accum_error's state rules
+int variance_ready(const AccumState& st, const char* entry) {
+    int rc = query_ready(st, entry);
+    if (rc) return rc;
+    if (!st.adaptive && st.done % 64 != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, not a multiple of 64: the variance is not defined", st.done);
+    return ZR_OK;
+}
+
+int accum_variance_into(const AccumState& a, double* d_out, hipStream_t stream) {
+    HIP_OK(zr::launch_accum_variance(a.d_partial.p, a.d_pixels.p, a.adaptive ? a.d_count.p : nullptr, a.done, a.n_pix, a.plan.W, d_out, stream));
+    return ZR_OK;
+}
+
+// The guided filter on device frames of n = W * H pixels: d_c / d_v hold colour and variance and receive the results; the guides are uploaded from the host.
+int denoise_guided_device(zr_ctx* c, const zr_denoise_guided_params* dp, DevBuf<double>& d_c, DevBuf<double>& d_v, const double* albedo, const double* normal,
+                          const double* zdepth, int W, int H, double* out, double* out_variance) {
+    const size_t n = (size_t)W * H;
+    DevBuf<double> d_a, d_n, d_z; DevBuf<float4> col0, col1, var0, var1, g0, g1;
+    int rc;
+    if ((rc = d_a.alloc(n * 3)) || (rc = d_n.alloc(n * 3)) || (zdepth && (rc = d_z.alloc(n * 3)))) return rc;
+    if ((rc = col0.alloc(n)) || (rc = col1.alloc(n)) || (rc = var0.alloc(n)) || (rc = var1.alloc(n)) || (rc = g0.alloc(n)) || (rc = g1.alloc(n))) return rc;
+    HIP_OK(hipMemcpyAsync(d_a.p, albedo, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d_n.p, normal, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (zdepth) HIP_OK(hipMemcpyAsync(d_z.p, zdepth, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // colour and variance have been packed before the unpack kernels overwrite them
+    HIP_OK(zr::launch_denoise_guided(d_c.p, d_v.p, d_a.p, d_n.p, zdepth ? d_z.p : nullptr, W, H, *dp, col0.p, col1.p, var0.p, var1.p, g0.p, g1.p, d_c.p,
+                                     out_variance ? d_v.p : nullptr, c->stream));
+    HIP_OK(hipMemcpyAsync(out, d_c.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (out_variance) HIP_OK(hipMemcpyAsync(out_variance, d_v.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return ZR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zr_accum_variance(zr_accum* a, double* out_var) {
+    if (!a || !out_var) return fail(ZR_E_INVALID, "null argument");
+    AccumState& st = a->st;
+    int rc = variance_ready(st, "zr_accum_variance");
+    if (rc) return rc;
+    HIP_OK(hipSetDevice(st.device));
+    DevBuf<double> d_frame;   // only the plan's pixels of it are written, and only they are copied out
+    if ((rc = d_frame.alloc(st.plan.npx() * 3))) return rc;
+    if ((rc = accum_variance_into(st, d_frame.p, nullptr))) return rc;
+    HIP_OK(hipStreamSynchronize(nullptr));
+    std::vector<double> staging;
+    return copy_region(st.plan, d_frame.p, out_var, staging);
+}
+
+int zr_denoise_guided(zr_ctx* c, const zr_denoise_guided_params* dp, const double* color, const double* variance, const double* albedo, const double* normal,
+                      const double* zdepth, int W, int H, double* out, double* out_variance) {
+    if (!c || !dp || !color || !variance || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
+    if (W < 1 || H < 1 || (size_t)W * H > (1ull << 31)) return fail(ZR_E_INVALID, "frame size %d x %d not supported", W, H);
+    int rc = check_guided_params(dp);
+    if (rc) return rc;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t n = (size_t)W * H;
+    DevBuf<double> d_c, d_v;
+    if ((rc = d_c.alloc(n * 3)) || (rc = d_v.alloc(n * 3))) return rc;
+    HIP_OK(hipMemcpyAsync(d_c.p, color, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d_v.p, variance, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return denoise_guided_device(c, dp, d_c, d_v, albedo, normal, zdepth, W, H, out, out_variance);
+}
+
+int zr_accum_denoise(zr_accum* a, const zr_denoise_guided_params* dp, const double* albedo, const double* normal, const double* zdepth, double* out,
+                     double* out_variance) {
+    if (!a || !dp || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
+    int rc = check_guided_params(dp);
+    if (rc) return rc;
+    AccumState& st = a->st;
+    if (!st.plan.whole()) return fail(ZR_E_INVALID, "zr_accum_denoise filters whole frames: the accumulator was made with a region");
+    if ((rc = variance_ready(st, "zr_accum_denoise"))) return rc;
+    zr_ctx* c = st.ctx;
+    HIP_OK(hipSetDevice(st.device));
+    DevBuf<double> d_c, d_v;
+    if ((rc = d_c.alloc(st.plan.npx() * 3)) || (rc = d_v.alloc(st.plan.npx() * 3))) return rc;
+    // a whole-frame plan: the two kernels write every pixel of the two frames
+    if ((rc = accum_resolve_into(st, d_c.p, c->stream)) || (rc = accum_variance_into(st, d_v.p, c->stream))) return rc;
+    return denoise_guided_device(c, dp, d_c, d_v, albedo, normal, zdepth, st.plan.W, st.plan.H, out, out_variance);
+}
+
 int zr_sharpen_frame(zr_ctx* c, const double* in, int W, int H, double amount, double* out) {
     if (!c || !in || !out) return fail(ZR_E_INVALID, "null argument");
     if (W < 1 || H < 1 || (size_t)W * H > (1ull << 31)) return fail(ZR_E_INVALID, "frame size %d x %d not supported", W, H);

@@ -253,6 +253,45 @@ int zrs_render_dropin_denoise(void* p, int width, int height, int spp, int devic
     return 0;
 }
 
+// camera::render with use_denoiser and camera::denoise_variance_guided (`guided` != 0) through the drop-in API: adaptively when threshold > 0
+// (min = step = 64), progressively when samples_per_pass > 0, else in one shot.  Outputs (W*H*3 doubles each, any may be null): render_accumulator,
+// denoise_buffer, variance_buffer (all -1 when the render left it empty); info (may be null): denoise_used_variance, current_samples_count.  Returns 0,
+// or -1 if the render did not finish.
+int zrs_render_dropin_denoise_guided(void* p, int width, int height, int spp, int device, double threshold, int samples_per_pass, int guided, double* acc,
+                                     double* den, double* var, int* info) {
+    handle* h = (handle*)p;
+    camera cam;
+    const zr_camera& c = h->s.cam;
+    cam.image_width = width > 0 ? width : c.image_width;
+    cam.image_height = height > 0 ? height : c.image_height;
+    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
+    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
+    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
+    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
+    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
+    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
+    cam.seed = h->s.seed; cam.device = device;
+    cam.use_denoiser = true;
+    cam.denoise_variance_guided = guided != 0;
+    cam.adaptive_threshold = threshold;
+    cam.samples_per_pass = samples_per_pass;
+    cam.reset_accumulator();
+    post_processor post;
+    std::atomic<bool> flag{true};
+    auto bvh_world = make_shared<bvh_node>(h->s.world);
+    cam.render(*bvh_world, h->s.env, post, flag);
+    if (cam.lines_rendered.load() != cam.image_height) return -1;
+    const size_t n = cam.render_accumulator.size() * 3;
+    if (acc) std::memcpy(acc, cam.render_accumulator.data(), n * sizeof(double));
+    if (den) std::memcpy(den, cam.denoise_buffer.data(), n * sizeof(double));
+    if (var) {
+        if (cam.variance_buffer.size() * 3 == n) std::memcpy(var, cam.variance_buffer.data(), n * sizeof(double));
+        else std::fill(var, var + n, -1.0);
+    }
+    if (info) { info[0] = cam.denoise_used_variance ? 1 : 0; info[1] = cam.current_samples_count; }
+    return 0;
+}
+
 // The reference's per-ray virtual API through the drop-in classes: for n rays (o, d, tmin, tmax) calls
 // bvh_node(world).hit(r, interval(tmin, tmax), rec), then rec.mat->emitted(...) and rec.mat->scatter(r, rec, att, scattered)
 // with random_double() positioned on the stream (seed, pixel, k) — the layout of `zenith_ref kat <scene> hits`:
@@ -322,6 +361,7 @@ extern "C" size_t zrs_sizeof(int which) {
         case 15: return sizeof(zr_bvh_debug_params);
         case 16: return sizeof(zr_bvh_debug_hit);
         case 17: return sizeof(zr_tree_box);
+        case 18: return sizeof(zr_denoise_guided_params);
         default: return 0;
     }
 }
