@@ -580,6 +580,9 @@ int zr_trace_paths(zr_ctx*, const zr_scene*, const zr_camera*, uint64_t seed, co
 
 /* counters + device time of the last render on this context (synchronises the context's stream) */
 int zr_get_counters(zr_ctx*, zr_counters*);
+/* pixels the last render on this context finished in the sky pre-pass (every camera ray of the pixel provably sees only the environment, so the pixel never
+ * entered the streaming pipeline; ZR_SKY_PREPASS=0 switches the pre-pass off); 0 for a render that took any other path, the counting render among them */
+uint64_t zr_last_presolved_pixels(zr_ctx*);
 /* drains the log of render-kernel launch durations (ms, measured with HIP events on the launch stream) recorded
  * since the previous call: copies the newest min(cap, n) of them, oldest first, and returns n */
 int zr_get_kernel_times(zr_ctx*, float* ms, int cap);

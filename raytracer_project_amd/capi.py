@@ -241,7 +241,7 @@ CAPI_SYMBOLS = [
     "zr_render_adaptive", "zr_accum_error", "zr_accum_sample_counts", "zr_accum_lane_sums",
     "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
     "zr_accum_variance", "zr_denoise_guided", "zr_accum_denoise",
-    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters",
+    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
 
@@ -304,6 +304,8 @@ def load():
     lib.zr_trace_paths.argtypes = [vp, vp, C.POINTER(Camera), u64, vp, i32, i32, vp]
     lib.zr_render_passes.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), vp, vp, vp]
     lib.zr_get_counters.argtypes = [vp, C.POINTER(Counters)]
+    if hasattr(lib, "zr_last_presolved_pixels"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
+        lib.zr_last_presolved_pixels.argtypes = [vp]; lib.zr_last_presolved_pixels.restype = u64
     lib.zr_get_kernel_times.argtypes = [vp, C.POINTER(C.c_float), i32]
     lib.zr_trace.argtypes = [vp, vp, vp, C.c_size_t, C.c_double, C.c_double, u64, u64, C.c_uint32, vp]
     lib.zr_kat_scatter.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
@@ -595,6 +597,10 @@ class Context:
         c = Counters()
         _check(self.lib.zr_get_counters(self._c, C.byref(c)))
         return c
+
+    def presolved_pixels(self):
+        """pixels the last render finished in the sky pre-pass (zr_last_presolved_pixels); 0 for every other path"""
+        return int(self.lib.zr_last_presolved_pixels(self._c))
 
     def kernel_times_ms(self, cap=256):
         buf = (C.c_float * cap)()

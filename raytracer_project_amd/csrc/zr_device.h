@@ -246,6 +246,56 @@ __host__ __device__ __forceinline__ bool ray_escapes(const Ray& ray, const NodeF
     return esc;
 }
 
+// ---- a camera ray that provably sees only the environment (the sky pre-pass, zr_sky.hip) -------------------------------------
+// sphere_passed_certain: true only if sphere_t(s, r, 0.001, tmax, .) is false for every tmax because its discriminant is negative: the ray passes the
+// sphere by (over the horizon of a ground sphere: h > 0, so sphere_miss_certain has nothing to say).  Both sites start from the same oc = s - o (a plain
+// subtraction: nothing to contract), so take oc and d as given and write A = |d|^2, H = d.oc, L = |oc|^2, R = r^2, Q = L + R, D = H^2 - A (L - R) for the
+// exact values and u = 2^-53.  However the multiply-adds of a site are contracted (a contraction only removes roundings):
+//   a = A (1 + e), |e| <= 3u;   l2 = L (1 + e), |e| <= 3u     sums of three squares
+//   |h - H| <= 3u sum |d_k oc_k| <= 3u sqrt(A L)              Cauchy-Schwarz, which also gives H^2 <= A L <= A Q
+//   |c - (L - R)| <= 3u L + u R + u |c| <= 5u Q               c = l2 - r r, with |L - R| <= Q
+//   |h h - H^2| <= 2 |H| |h - H| + |h - H|^2 + u h^2 <= 8u A Q
+//   |a c - A (L - R)| <= |a - A| |c| + A |c - (L - R)| + u |a c| <= 10u A Q
+//   the last subtraction rounds once more: <= u (h^2 + |a c|) <= 2.1u A Q
+// so a site's disc lies within E = 20.1u A Q < 2^-48 A Q of D, and two sites differ by less than 2^-47 A Q.  The margin is 2^-36 a (l2 + r r), 2048 times
+// that (a (l2 + r r) is A Q to within 8u): if disc < -margin here then D < 0 by a wide margin and sphere_t's disc is negative too.  2^-36 costs nothing where
+// the predicate is meant to pay: a ray that clears the horizon of cfg3's ground sphere by a relative 1e-6 has D = -2e-6 A R, five orders of magnitude beyond it.
+// The guards keep every product in the normal range (no underflow error, no overflow); a NaN makes a comparison false: no cull.  An origin inside the sphere
+// has c < 0, hence disc > 0: never ruled out.  No hit is decided here — only misses.
+__host__ __device__ __forceinline__ bool sphere_passed_certain(const double* s, const Ray& r) {
+    const double ox = s[0] - r.o.x, oy = s[1] - r.o.y, oz = s[2] - r.o.z;
+    const double a = r.d.x * r.d.x + r.d.y * r.d.y + r.d.z * r.d.z;
+    const double h = r.d.x * ox + r.d.y * oy + r.d.z * oz;
+    const double l2 = ox * ox + oy * oy + oz * oz;
+    const double r2 = s[3] * s[3];
+    const double c = l2 - r2;
+    const double disc = h * h - a * c;
+    const double q = l2 + r2;
+    return a > 1e-100 && a < 1e100 && q > 1e-100 && q < 1e100 && disc < -1.4551915228366852e-11 /* 2^-36 */ * (a * q);
+}
+// camera_ray_escapes: ray_escapes for a camera ray (same macros, same constants, tbest = +inf; a NaN slab counts as a hit), with both sphere predicates: a
+// one-sphere leaf whose box is hit is missed if the sphere lies behind the ray or the ray passes it by.  Any other child whose box is hit keeps the ray for EXTEND.
+__host__ __device__ __forceinline__ bool camera_ray_escapes(const Ray& ray, const NodeF& root, const double* spheres) {
+    const bool COUNT = false;
+    const float INFf = __builtin_huge_valf(), tbest_f = INFf;
+    float idx_, idy_, idz_, cnx, cny, cnz, cfx, cfy, cfz;
+    uint32_t c_nodes = 0;
+    ZR_RAY_CONSTANTS()
+    float tn0, tn1, tn2, tn3;
+    uint32_t r0, r1, r2, r3;
+    ZR_FBOX(root, 0, tn0, r0)
+    ZR_FBOX(root, 1, tn1, r1)
+    ZR_FBOX(root, 2, tn2, r2)
+    ZR_FBOX(root, 3, tn3, r3)
+    (void)c_nodes;
+#define ZR_CHILD_MISSED(TN, RF) \
+    (!((TN) < INFf) || ((((RF) & 0xFF000000u) == (ZR_REF_LEAF | ((uint32_t)ZR_PRIM_SPHERE << 28))) && \
+                        (sphere_miss_certain(spheres + (size_t)((RF) & 0xFFFFFFu) * 4, ray) || sphere_passed_certain(spheres + (size_t)((RF) & 0xFFFFFFu) * 4, ray))))
+    const bool esc = ZR_CHILD_MISSED(tn0, r0) && ZR_CHILD_MISSED(tn1, r1) && ZR_CHILD_MISSED(tn2, r2) && ZR_CHILD_MISSED(tn3, r3);
+#undef ZR_CHILD_MISSED
+    return esc;
+}
+
 // triangle.hpp:17-57, distance only.  Same decisions as the reference — degenerate (|N| < 1e-8), parallel
 // (|N̂·d| < 1e-8), contains(t) inclusive, the three edge tests N·((v_{k+1}-v_k) x (p-v_k)) >= 0 — evaluated in the
 // algebraically identical scaled-barycentric form, which needs no square root and a single division, and only
@@ -1036,6 +1086,22 @@ __device__ inline Ray camera_ray(const DCamera& cam, int i, int j, Rng& g) {
     }
     Ray r; r.o = org; r.d = ps - org;
     return r;
+}
+
+// ---- a pixel's mean from its n samples, one wave per pixel (stream_reduce, zr_stream.hip; the sky pre-pass, zr_sky.hip) -------------------------------
+// Lane l sums sample(l), sample(l + 64), ... in that order, then a fixed xor butterfly (every lane ends with the total) and 1 / spp (camera.hpp:437,531): the
+// order depends on n only.  All 64 lanes of the wave must call it.
+template <class Sample>
+__device__ __forceinline__ V3 wave_pixel_mean(int lane, uint32_t n, int spp, Sample sample) {
+    double sx = 0, sy = 0, sz = 0;
+    for (uint32_t sidx = (uint32_t)lane; sidx < n; sidx += 64) { const V3 v = sample(sidx); sx += v.x; sy += v.y; sz += v.z; }
+    for (int m = 32; m >= 1; m >>= 1) {
+        sx += __hiloint2double(__shfl_xor(__double2hiint(sx), m, 64), __shfl_xor(__double2loint(sx), m, 64));
+        sy += __hiloint2double(__shfl_xor(__double2hiint(sy), m, 64), __shfl_xor(__double2loint(sy), m, 64));
+        sz += __hiloint2double(__shfl_xor(__double2hiint(sz), m, 64), __shfl_xor(__double2loint(sz), m, 64));
+    }
+    const double scale = 1.0 / spp;
+    return mk(sx * scale, sy * scale, sz * scale);
 }
 
 }  // namespace zr

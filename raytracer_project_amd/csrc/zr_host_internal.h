@@ -87,7 +87,10 @@ struct zr_ctx {
     DevBuf<unsigned char> d_pool;
     DevBuf<uint32_t> d_pixels;
     DevBuf<double> d_partial;
-    DevBuf<uint32_t> d_kend;               // reflection / refraction split: (draws, segments) of every unit's beauty path
+    // the sky pre-pass (zr_sky.hip): flag per list position, the compaction's block counts, the pixels the pipeline walks, their number; grown as frames need
+    DevBuf<uint32_t> d_sky_flag, d_sky_blocks, d_walk_pixels, d_n_walk;
+    uint64_t presolved = 0, presolved_render = 0;   // pixels the pre-pass resolved in render `presolved_render` (zr_last_presolved_pixels)
+    DevBuf<uint32_t> d_kend;              // reflection / refraction split: (draws, segments) of every unit's beauty path
     DevBuf<unsigned char> d_cls;           // ... and the class of its second path
     DevBuf<unsigned long long> d_cpart;    // ... and the per-block counters of the two passes
     DevBuf<unsigned int> d_ctl;

@@ -130,6 +130,11 @@ hipError_t launch_accum_resolve_counts(const double* partial, const uint32_t* pi
 // the per-channel variance of every slot's mean into the listed pixels of `out` (frame width W, 3 doubles a pixel; count as launch_accum_error's)
 hipError_t launch_accum_variance(const double* partial, const uint32_t* pixels, const int32_t* count, int uniform_count, uint32_t n_pix, int W, double* out,
                                  hipStream_t stream);
+// The sky pre-pass (zr_sky.hip): of the n_pix listed pixels, those whose every camera ray of the samples [sample0, sample0 + spp) provably sees only the
+// environment get their mean written to `out` (stream_reduce's value, bit for bit); the others go, in list order, to walk[0 .. *n_walk).  Device scratch:
+// flag and walk n_pix words, block_count ceil(n_pix / 256) words, n_walk one word.
+hipError_t launch_sky_prepass(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const uint32_t* pixels, uint32_t n_pix, uint32_t spp,
+                              uint32_t sample0, double* out, uint32_t* flag, uint32_t* block_count, uint32_t* walk, uint32_t* n_walk, hipStream_t stream);
 // closest hits of n rays in [0.001, inf) through the EXTEND kernel on ctx.streams[0]; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes
 hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, void* pool,
                         const StreamContext& ctx, int leaf_level);

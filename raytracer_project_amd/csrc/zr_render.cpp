@@ -349,6 +349,29 @@ int split_buffers(zr_ctx* c, uint64_t units, int mode, hipStream_t stream, zr::S
     return ZR_OK;
 }
 
+// The sky pre-pass of a pipeline frame (zr_sky.hip): the listed pixels whose every camera ray provably sees only the environment are written to job.d_out here, the
+// others are compacted, in list order, into zr_ctx::d_walk_pixels; *n_walk (host) says how many those are.  The cached list (d_pixels, pix_key) is left alone.
+// One 4-byte device-to-host copy and a stream synchronisation.
+int sky_prepass(zr_ctx* c, const zr_scene* s, const FrameJob& job, const uint32_t* pixels, uint32_t n_pix, uint32_t* n_walk) {
+    int rc;
+    const size_t n_blocks = ((size_t)n_pix + 255) / 256;
+    if (c->d_sky_flag.n < n_pix && (rc = c->d_sky_flag.alloc(n_pix))) return rc;
+    if (c->d_walk_pixels.n < n_pix && (rc = c->d_walk_pixels.alloc(n_pix))) return rc;
+    if (c->d_sky_blocks.n < n_blocks && (rc = c->d_sky_blocks.alloc(n_blocks))) return rc;
+    if (!c->d_n_walk.p && (rc = c->d_n_walk.alloc(1))) return rc;
+    HostTimer timer(c);
+    timer.begin(job.stream, 0);
+    HIP_OK(zr::launch_sky_prepass(s->ds, job.dc, job.de, job.seed, pixels, n_pix, (uint32_t)job.dc.spp, job.sample0, job.d_out, c->d_sky_flag.p, c->d_sky_blocks.p,
+                                  c->d_walk_pixels.p, c->d_n_walk.p, job.stream));
+    timer.end(job.stream, 0);
+    if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
+    HIP_OK(hipMemcpyAsync(c->h_active, c->d_n_walk.p, sizeof(uint32_t), hipMemcpyDeviceToHost, job.stream));   // (pinned; the round loop's copies come later)
+    HIP_OK(hipStreamSynchronize(job.stream));
+    *n_walk = c->h_active[0];
+    if (*n_walk > n_pix) return fail(ZR_E_DEVICE, "the sky pre-pass kept %u of %u pixels", *n_walk, n_pix);
+    return ZR_OK;
+}
+
 // Renders job.plan into job.d_out through the pipeline or, for a small world, the fused kernel.  The frame must fit the pipeline (fits_stream: both callers ask
 // first).  Synchronises the stream internally (the round loop needs the active-slot count), so zr_render_device returns with the frame complete.
 // mode 0: the render; 1 / 2: beauty pass and replay pass of the reflection / refraction split (zr_stream.hip, stream_shade)
@@ -356,15 +379,16 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode = 
     int rc = ZR_OK;
     // the caller's own list leaves the cached one (zr_ctx::d_pixels, pix_key) alone: a later render of the plan gets the plan's list
     if (!job.d_list && (rc = upload_pixel_list(c, job.plan))) return rc;
-    const uint32_t* const pixels = job.d_list ? job.d_list : c->d_pixels.p;
-    const uint32_t n_pix = job.d_list ? job.n_list : (uint32_t)c->d_pixels.n, spp = (uint32_t)job.dc.spp;
+    const uint32_t* pixels = job.d_list ? job.d_list : c->d_pixels.p;
+    uint32_t n_pix = job.d_list ? job.n_list : (uint32_t)c->d_pixels.n;
+    const uint32_t spp = (uint32_t)job.dc.spp;
     if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
     c->render_id++; c->last_stream = job.stream; c->last_counted = job.count; c->last_rounds = 0;
     HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
     if (n_pix == 0) return ZR_OK;
-    const uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
+    uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
     // per-sample radiance first: without it this pipeline cannot run at all (the caller falls back to the pixel-group kernel)
-    const size_t samples_n = (size_t)units * 3;
+    size_t samples_n = (size_t)units * 3;
     if (c->d_partial.n < samples_n) {
         HIP_OK(hipStreamSynchronize(job.stream));
         if (c->d_partial.alloc(samples_n) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes)", samples_n * sizeof(double));
@@ -372,13 +396,23 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode = 
     hipStream_t streams[ST_MAX_POOLS];
     streams[0] = job.stream;
     for (int k = 1; k < ST_MAX_POOLS; k++) streams[k] = c->sub[k];
+    const bool fused = mode == 0 && s->fused_ok && s->leaf_level <= 2 && s->leaf_objects > 0 && (double)s->leaf_objects <= env_double("ZR_FUSED_MAX", ZR_FUSED_OBJECTS) &&
+                       env_double("ZR_FUSED", 1) != 0;
+    // A frame that the pipeline reduces into d_out from the plan's own list first loses its sky pixels (sky_prepass): they never become work units.  Not the counting
+    // render (the instrument: every unit goes through the pipeline), not a batch of an accumulator (d_out == nullptr, its own list), not the split passes.
+    if (mode == 0 && !fused && job.d_out && !job.d_list && !job.count && s->ds.shade_escape && env_double("ZR_SKY_PREPASS", 1) != 0) {
+        uint32_t n_walk = n_pix;
+        if ((rc = sky_prepass(c, s, job, pixels, n_pix, &n_walk))) return rc;
+        c->presolved = n_pix - n_walk; c->presolved_render = c->render_id;
+        if (n_walk < n_pix) { pixels = c->d_walk_pixels.p; n_pix = n_walk; units = (uint64_t)n_pix * spp; samples_n = (size_t)units * 3; }
+        if (n_pix == 0) { c->last_path = 2; return ZR_OK; }   // (the stream is idle: sky_prepass synchronised it)
+    }
     zr::StreamJob sj{};
     sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, pixels, c->d_partial.p, job.d_out, job.d_out2, job.count, job.sample0};
     sj.ctx = zr::StreamContext{c->d_ctl.p, nullptr, 0, c->st_blocks, c->d_ctr.p, streams, 1, c->st_event, c->h_active};
     sj.hooks = zr::StreamHooks{nullptr, job.keep_going, job.progress, nullptr};
     const bool polled = job.keep_going || job.progress;   // a cancelled frame / a preview reduces what exists: the samples start at zero
-    if (mode == 0 && s->fused_ok && s->leaf_level <= 2 && s->leaf_objects > 0 && (double)s->leaf_objects <= env_double("ZR_FUSED_MAX", ZR_FUSED_OBJECTS) &&
-        env_double("ZR_FUSED", 1) != 0) {
+    if (fused) {
         if (polled) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), job.stream));
         return render_fused(c, s, sj);
     }
@@ -1334,6 +1368,10 @@ int zr_get_counters(zr_ctx* c, zr_counters* out) {
         }
     }
     return ZR_OK;
+}
+
+uint64_t zr_last_presolved_pixels(zr_ctx* c) {
+    return c && c->presolved_render == c->render_id ? c->presolved : 0;
 }
 
 int zr_get_kernel_times(zr_ctx* c, float* ms, int cap) {

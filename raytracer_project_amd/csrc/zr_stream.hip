@@ -1012,19 +1012,12 @@ __global__ __launch_bounds__(256) void stream_reduce(StreamBuf B, DCamera cam, d
     const int lane = threadIdx.x & 63;
     if (i >= B.n_pix) return;
     const double* pp = B.samples + (size_t)i * B.spp * 3;
-    double sx = 0, sy = 0, sz = 0;
-    for (uint32_t sidx = (uint32_t)lane; sidx < B.spp; sidx += 64) { sx += pp[sidx * 3]; sy += pp[sidx * 3 + 1]; sz += pp[sidx * 3 + 2]; }
-    for (int m = 32; m >= 1; m >>= 1) {
-        sx += __hiloint2double(__shfl_xor(__double2hiint(sx), m, 64), __shfl_xor(__double2loint(sx), m, 64));
-        sy += __hiloint2double(__shfl_xor(__double2hiint(sy), m, 64), __shfl_xor(__double2loint(sy), m, 64));
-        sz += __hiloint2double(__shfl_xor(__double2hiint(sz), m, 64), __shfl_xor(__double2loint(sz), m, 64));
-    }
+    const V3 mean = wave_pixel_mean(lane, B.spp, cam.spp, [&](uint32_t sidx) { return mk(pp[sidx * 3], pp[sidx * 3 + 1], pp[sidx * 3 + 2]); });
     if (lane == 0) {
         const uint32_t pk = B.pixels[i];
         const int px = (int)(pk & 0xFFFFu), py = (int)(pk >> 16);
-        const double scale = 1.0 / cam.spp;  // camera.hpp:437,531
         double* o = out + ((size_t)py * cam.W + px) * 3;
-        o[0] = sx * scale; o[1] = sy * scale; o[2] = sz * scale;
+        o[0] = mean.x; o[1] = mean.y; o[2] = mean.z;
     }
 }
 
