@@ -123,10 +123,14 @@ enum {
     ZR_TEX_IMAGE_F32 = 3  /* image_texture, float RGB (HDR) */
 };
 
+/* A texture tree has at most this many checkers above any leaf (solid or image) and no cycle: the device's texture::value walks
+ * ZR_MAX_CHECKER_DEPTH + 1 textures at most.  zr_scene_commit refuses a scene that holds a deeper tree (ZR_E_INVALID). */
+#define ZR_MAX_CHECKER_DEPTH 15
+
 typedef struct zr_texture {
     uint32_t kind;      /* ZR_TEX_* */
     uint32_t odd, even; /* checker: child texture ids */
-    uint32_t width, height; /* image; 0 x 0 = the reference's "missing image" cyan fallback */
+    uint32_t width, height; /* image, each at most INT_MAX; 0 x 0 = the reference's "missing image" cyan fallback */
     uint32_t pad_;
     uint64_t texel_offset;  /* byte offset of the first texel inside the texel blob */
     double inv_scale;       /* checker */

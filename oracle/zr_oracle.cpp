@@ -812,7 +812,18 @@ void to_hit(const Rec& rec, bool h, zr_hit& o) {
 
 extern "C" {
 
+// the checkers between texture `id` and its deepest leaf; -1 for a cycle or for more than ZR_MAX_CHECKER_DEPTH of them (include/zr_capi.h)
+static int checker_depth(const zr_scene_desc& d, uint32_t id, int above) {
+    if (id >= d.n_textures || d.textures[id].kind != ZR_TEX_CHECKER) return 0;
+    if (above >= ZR_MAX_CHECKER_DEPTH) return -1;
+    const int a = checker_depth(d, d.textures[id].odd, above + 1), b = checker_depth(d, d.textures[id].even, above + 1);
+    return a < 0 || b < 0 ? -1 : 1 + std::max(a, b);
+}
+
+// returns null for a scene the device refuses at commit: a texture tree deeper than ZR_MAX_CHECKER_DEPTH checkers, or one with a cycle
 void* zro_scene_create(const zr_scene_desc* d) {
+    for (uint64_t t = 0; t < d->n_textures; t++)
+        if (checker_depth(*d, (uint32_t)t, 0) < 0) return nullptr;
     Scene* s = new Scene();
     s->d = *d;
     s->prepare();

@@ -62,6 +62,8 @@ class OracleScene:
         self.lib = load()
         self._keep = desc
         self._s = self.lib.zro_scene_create(C.byref(desc))
+        if not self._s:
+            raise ValueError("the oracle refuses this scene: a texture tree with a cycle or more than 15 checkers above a leaf")
 
     def render(self, camera, env, seed, region=None, threads=None, per_sample=False):
         """Returns (frame[H,W,3], counters, samples[h,w,spp,3] | None, counts[h,w,spp,2] | None)."""

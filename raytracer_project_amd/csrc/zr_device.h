@@ -787,7 +787,7 @@ __device__ inline bool closest_hit(const DScene& sc, const Ray& r, double tmin, 
 
 // ---- textures (texture.hpp:50-78, 96-98, 118-126) -----------------------------------------------------
 __device__ inline V3 tex_value(const DScene& sc, uint32_t id, double u, double v, V3 p) {
-    for (int guard = 0; guard < 16; guard++) {
+    for (int guard = 0; guard <= ZR_MAX_CHECKER_DEPTH; guard++) {   // (validate, zr_flatten.h, lets no deeper tree and no cycle through)
         const zr_texture& t = sc.texs[id];
         if (t.kind == ZR_TEX_SOLID) return mk(t.color[0], t.color[1], t.color[2]);
         if (t.kind == ZR_TEX_CHECKER) {
@@ -1034,8 +1034,10 @@ __device__ inline V3 background(const DScene& sc, const DEnv& env, V3 rd) {
             // Only the TEXEL INDEX of (u, v) matters (nearest lookup, texture.hpp:60-66).  Get it from FP32
             // atan2f/acosf, and fall back to the FP64 functions only when the FP32 coordinate lies within
             // `guard` texels of a texel boundary (or near the poles, where acos is ill-conditioned): the FP32
-            // path's absolute error is below 4e-6 rad (2 ulp functions + input rounding), i.e. < 0.011 texel at
-            // 16384 texels, so inside the guarded interior both paths select the same texel.
+            // coordinate's error, measured on an MI355X with the device's own atan2f / acosf (scripts/dev/hdr_fp32_error.hip),
+            // is at most 0.0019 texel in u and 0.0046 texel in v at 16384 texels and shrinks with the texel count, under a
+            // quarter of the guard, so inside the guarded interior both paths select the same texel
+            // (tests/test_lookup_edges.py: every map size up to the limit, both sides of the guard, the seam and the poles).
             const float xf = (float)d.x, yf = (float)d.y, zf = (float)d.z;
             const float PIf = 3.14159265358979323846f;
             const float fi = (atan2f(zf, xf) + PIf) * (0.15915494309189535f * (float)t.width);

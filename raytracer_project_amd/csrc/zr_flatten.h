@@ -162,9 +162,45 @@ inline int validate(const SceneInput& s, const std::vector<zr_object>& objs) {
         if (t.kind > ZR_TEX_IMAGE_F32) return fail(ZR_E_INVALID, "unknown texture kind %u", t.kind);
         if (t.kind == ZR_TEX_CHECKER && (t.odd >= nt || t.even >= nt)) return fail(ZR_E_INVALID, "checker child texture out of range");
         if (t.kind >= ZR_TEX_IMAGE_U8 && t.width && t.height) {
-            size_t bytes = (size_t)t.width * t.height * 3 * (t.kind == ZR_TEX_IMAGE_F32 ? 4 : 1);
-            if (t.texel_offset + bytes > s.texels.size()) return fail(ZR_E_INVALID, "image texture texels out of range");
+            const unsigned id = (unsigned)(&t - s.textures.data());
+            // texture::value indexes texels with int arithmetic (texture.hpp:60-66)
+            if (t.width > (uint32_t)INT_MAX || t.height > (uint32_t)INT_MAX) return fail(ZR_E_INVALID, "image texture %u: %u x %u texels, each dimension is at most INT_MAX", id, t.width, t.height);
+            // offset + width * height * texel <= blob size, with no sum or product that can wrap: width * height * texel <= room
+            // <=> width <= (room / texel) / height in integer division
+            const uint64_t texel = t.kind == ZR_TEX_IMAGE_F32 ? 12 : 3, have = s.texels.size();
+            if (t.texel_offset > have || t.width > (have - t.texel_offset) / texel / t.height) return fail(ZR_E_INVALID, "image texture %u: texels out of range", id);
             if (t.kind == ZR_TEX_IMAGE_F32 && (t.texel_offset & 3)) return fail(ZR_E_INVALID, "float texels must be 4-byte aligned");
+        }
+    }
+    // Every texture tree is one the device can walk (zr_device.h tex_value): at most ZR_MAX_CHECKER_DEPTH checkers above any leaf, and no cycle.
+    // depth[t] = checkers on the longest way from t down to a leaf, by a depth-first walk on an explicit stack (a chain can be as long as the table).
+    {
+        enum : uint8_t { NEW = 0, OPEN = 1, DONE = 2 };
+        std::vector<uint8_t> state(nt, NEW);
+        std::vector<uint32_t> depth(nt, 0), stack;
+        for (uint32_t root = 0; root < nt; root++) {
+            if (state[root] != NEW) continue;
+            stack.push_back(root);
+            while (!stack.empty()) {
+                const uint32_t id = stack.back();
+                const zr_texture& t = s.textures[id];
+                if (t.kind != ZR_TEX_CHECKER) { state[id] = DONE; stack.pop_back(); continue; }
+                if (state[id] == NEW) {
+                    state[id] = OPEN;
+                    for (uint32_t c : {t.odd, t.even}) {
+                        if (state[c] == OPEN) return fail(ZR_E_INVALID, "checker texture %u is its own descendant (through texture %u)", c, id);
+                        if (state[c] == NEW) stack.push_back(c);
+                    }
+                    continue;
+                }
+                if (state[id] == OPEN) {   // both children are done
+                    depth[id] = 1 + std::max(depth[t.odd], depth[t.even]);
+                    if (depth[id] > ZR_MAX_CHECKER_DEPTH)
+                        return fail(ZR_E_INVALID, "texture %u: %u checkers above a leaf, at most %d can be walked", id, depth[id], ZR_MAX_CHECKER_DEPTH);
+                    state[id] = DONE;
+                }
+                stack.pop_back();
+            }
         }
     }
     return ZR_OK;

@@ -184,7 +184,9 @@ def test_default_paths_are_pinned(built):
 class World:
     """A hand-built world: owns the ctypes arrays its SceneDesc points into.  Cubes are origin-centred (cube.hpp:57-58) and placed by
     their wrapper chain; glass goes on spheres only and no two surfaces coincide (DESIGN §1's non-contracts).  No flat face of a checkered
-    object lies on a checker boundary (floor(p / scale) there turns on the last bit of p, which fused multiply-add changes)."""
+    object lies on a checker boundary (floor(p / scale) there turns on the last bit of p, which fused multiply-add changes).  An image or bump map on a
+    cube has equal first and last columns (_pattern(seam=True)): within cube.hpp's 1e-3 of an x face a hit on a z face is recorded as the x face's, with
+    u = (p.z + he.z) / (2 he.z) equal to 0 or 1 up to the last bit of p, and u wraps — to the first or the last column."""
 
     def __init__(self):
         from raytracer_project_amd import capi
@@ -193,6 +195,8 @@ class World:
         self.spheres, self.smat, self.tv, self.tn, self.tmat = [], [], [], [], []
         self.cubes, self.cmat, self.media, self.ops, self.objs, self.groups = [], [], [], [], [], []
         self.iso = None   # the media's isotropic material, made with the first medium (it would make a world non-lean)
+        self.blob = bytearray()   # the texels of the image textures
+        self.env = None   # (hdr texture, hdri_rotation, hdri_tilt, hdri_roll, intensity) of a world that brings its own environment
 
     def solid(self, c):
         self.texs.append(self.capi.Texture(0, 0, 0, 0, 0, 0, 0, 0.0, (C.c_double * 3)(*c)))
@@ -203,9 +207,32 @@ class World:
         self.texs.append(self.capi.Texture(1, ia, ib, 0, 0, 0, 0, 1.0 / scale, (C.c_double * 3)(0, 0, 0)))
         return len(self.texs) - 1
 
-    def material(self, kind, tex, param=0.0):
-        self.mats.append(self.capi.Material(kind, tex, 0xFFFFFFFF, 0, param, 1.0, (C.c_double * 3)(1, 1, 1)))
+    def image(self, w, h, kind, array):
+        """an image texture of w x h texels, kind "u8" (bytes) or "f32" (floats, at a 4-byte-aligned offset of the blob) from an (h, w, 3) array"""
+        a = np.ascontiguousarray(array, dtype=np.uint8 if kind == "u8" else np.float32)
+        assert a.shape == (h, w, 3)
+        if kind == "f32":
+            self.blob += bytes(-len(self.blob) % 4)
+        self.texs.append(self.capi.Texture(2 if kind == "u8" else 3, 0, 0, w, h, 0, len(self.blob), 0.0, (C.c_double * 3)(0, 0, 0)))
+        self.blob += a.tobytes()
+        return len(self.texs) - 1
+
+    def checker_of(self, scale, odd, even):
+        self.texs.append(self.capi.Texture(1, odd, even, 0, 0, 0, 0, 1.0 / scale, (C.c_double * 3)(0, 0, 0)))
+        return len(self.texs) - 1
+
+    def material(self, kind, tex, param=0.0, bump=None, strength=1.0):
+        self.mats.append(self.capi.Material(kind, tex, 0xFFFFFFFF if bump is None else bump, 0, param, strength, (C.c_double * 3)(1, 1, 1)))
         return len(self.mats) - 1
+
+    def environment(self, base):
+        """the environment this world is rendered under: its own HDR map, or `base`"""
+        if self.env is None:
+            return base
+        e = self.capi.Env()
+        e.mode, e.hdr_texture = 1, self.env[0]   # ZR_ENV_HDR_MAP
+        e.hdri_rotation, e.hdri_tilt, e.hdri_roll, e.intensity = self.env[1:]
+        return e
 
     def lambertian(self, c):
         return self.material(0, self.solid(c))
@@ -281,7 +308,11 @@ class World:
         d.objects = arr(capi.Object, self.objs); d.n_objects = len(self.objs)
         d.materials = arr(capi.Material, self.mats); d.n_materials = len(self.mats)
         d.textures = arr(capi.Texture, self.texs); d.n_textures = len(self.texs)
-        d.texels, d.texel_bytes = None, 0
+        d.texels, d.texel_bytes = None, len(self.blob)
+        if self.blob:
+            texels = (C.c_ubyte * len(self.blob)).from_buffer_copy(bytes(self.blob))
+            self._keep.append(texels)
+            d.texels = C.cast(texels, C.c_void_p)
         d.groups = arr(C.c_uint32, self.groups) if self.groups else None; d.n_groups = len(self.groups) // 2
         self._desc = d
         return d
@@ -431,6 +462,70 @@ def world_placement():
     return w
 
 
+def _pattern(w, h, seed, lo=0.05, hi=1.0, seam=False):
+    """(h, w, 3) texels in [lo, hi): a seeded pattern in which neighbouring texels differ visibly, so a lookup one texel off shows; seam: the last column
+    repeats the first (for cubes, see World)"""
+    a = np.random.default_rng(seed).uniform(lo, hi, (h, w, 3))
+    if seam:
+        a[:, -1] = a[:, 0]
+    return a
+
+
+def world_textured_surfaces():
+    """level 0: spheres with a U8 image, an F32 image and an image under a checker; a bumped lambertian, a bumped mirror and a bumped glass sphere; a light
+    with an image texture.  zr_material::pad_ must be set for every one of them, or the kernels read texel (0, 0) everywhere."""
+    w = World()
+    _ground(w)
+    u8 = w.image(37, 19, "u8", _pattern(37, 19, 1) * 255)
+    f32 = w.image(16, 9, "f32", _pattern(16, 9, 2))
+    under = w.checker_of(0.35, w.image(5, 7, "u8", _pattern(5, 7, 3) * 255), w.solid((0.9, 0.9, 0.2)))
+    bump_u8 = w.image(64, 32, "u8", _pattern(64, 32, 4, 0.0) * 255)
+    bump_f32 = w.image(1024, 3, "f32", _pattern(1024, 3, 5, -1.0))
+    w.sphere((-2.4, -0.6, 0.6), 0.9, w.material(0, u8))
+    w.sphere((-0.4, -0.7, -0.6), 0.8, w.material(1, f32, 0.2))
+    w.sphere((1.5, -0.7, -0.3), 0.8, w.material(0, under))
+    w.sphere((-1.2, -1.0, 2.6), 0.5, w.material(0, w.solid((0.7, 0.6, 0.5)), bump=bump_u8, strength=2.0))
+    w.sphere((0.3, -0.9, 2.2), 0.6, w.material(1, w.solid((0.9, 0.9, 0.9)), 0.0, bump=bump_f32, strength=0.5))     # bumped mirror
+    w.sphere((1.8, -1.0, 2.4), 0.5, w.material(2, w.solid((1, 1, 1)), 1.5, bump=bump_u8, strength=-1.0))            # bumped glass
+    w.sphere((0.0, 3.0, -2.0), 0.8, w.material(3, w.image(8, 4, "f32", _pattern(8, 4, 6, 0.2, 4.0))))               # a light brighter than 1 in places
+    return w
+
+
+def world_textured_boxes():
+    """level 1: a bare cube and a placed cube (translate + rotate_y), each with an image and a bump map"""
+    w = World()
+    _ground(w)
+    img = w.image(23, 11, "u8", _pattern(23, 11, 7, seam=True) * 255)
+    bump = w.image(33, 17, "f32", _pattern(33, 17, 8, -0.5, 0.5, seam=True))
+    w.cube((0.7, 0.7, 0.7), w.material(0, img, bump=bump, strength=1.5))
+    w.cube((0.5, 0.6, 0.4), w.material(1, w.image(12, 12, "f32", _pattern(12, 12, 9, seam=True)), 0.1, bump=w.image(9, 40, "u8", _pattern(9, 40, 10, 0.0, seam=True) * 255), strength=-0.8),
+           chain=[(T, (2.3, -0.9, 0.6)), (RY, _rot(25))])
+    _light(w, (0.0, 3.5, 0.0), 0.6)
+    return w
+
+
+def world_textured_wrapped():
+    """level 2: a sphere under rotate_x + scale with an image; solid-colour spheres whose material instance (alone, and behind translate + rotate_x) swaps in
+    an image-textured material; an image-textured cube under rotate_z"""
+    w = World()
+    _ground(w)
+    img = w.material(0, w.image(31, 13, "u8", _pattern(31, 13, 11) * 255))
+    w.sphere((0.0, 0.2, 0.0), 0.7, w.material(1, w.image(14, 6, "f32", _pattern(14, 6, 12)), 0.3), chain=[(T, (-2.2, -0.8, 0.8)), (RX, _rot(35)), (S, (1.2, 0.9, 1.1))])
+    w.sphere((0.2, -0.8, 2.4), 0.7, w.lambertian((0.5, 0.5, 0.5)), chain=[(M, (0, 0, 0), img)])
+    w.sphere((0.0, 0.1, 0.0), 0.6, w.lambertian((0.2, 0.2, 0.8)), chain=[(T, (0.2, -0.2, -0.9)), (RX, _rot(-50)), (M, (0, 0, 0), img)])
+    w.cube((0.5, 0.6, 0.5), w.material(0, w.image(10, 20, "u8", _pattern(10, 20, 13, seam=True) * 255)), chain=[(T, (2.2, -0.8, 0.4)), (RZ, _rot(20))])
+    _light(w)
+    return w
+
+
+def world_hdr_only():
+    """one small sphere under a 512 x 256 F32 environment map with rotation, tilt and roll: most of the frame is the map"""
+    w = World()
+    w.sphere((0.0, 0.2, 0.0), 1.1, w.lambertian((0.7, 0.6, 0.5)))
+    w.env = (w.image(512, 256, "f32", _pattern(512, 256, 14, 0.05, 1.5)), 0.7, -0.3, 1.9, 1.25)
+    return w
+
+
 # world: (builder, its default (path, EXTEND level, lean SHADE, fused_ok, leaf objects))
 WORLDS = {
     "surfaces": (world_surfaces, (3, 0, 0, 1, 9)),
@@ -444,6 +539,10 @@ WORLDS = {
     "seventeen": (lambda: _crowd(17), (2, 1, 0, 0, 17)),
     "scaled_placed_cube": (world_scaled_placed_cube, (2, 1, 0, 0, 12)),
     "placement": (world_placement, (2, 3, 0, 0, 9)),
+    "textured_surfaces": (world_textured_surfaces, (3, 0, 0, 1, 8)),
+    "textured_boxes": (world_textured_boxes, (3, 1, 0, 1, 4)),
+    "textured_wrapped": (world_textured_wrapped, (3, 2, 0, 1, 6)),
+    "hdr_only": (world_hdr_only, (3, 0, 1, 1, 1)),
 }
 
 
@@ -490,6 +589,7 @@ def test_small_world_matches_oracle_on_every_path(name, variant, env, path, buil
         monkeypatch.setenv(k, v)
     world = build()
     cam, env_ = _small_camera()
+    env_ = world.environment(env_)
     seed = 4242 + len(name)
     c = capi.Context(0)
     try:
@@ -534,3 +634,62 @@ def test_fused_kernel_frame_equals_the_pipelines(built, monkeypatch):
     d = frames[0] != frames[1]
     assert not d.any(), f"{int(d.sum())} channels differ, first at {tuple(np.argwhere(d)[0].tolist())}"
     assert ctrs[0] == ctrs[1]
+
+
+def test_hdr_only_frame_is_the_frame_without_the_sky_prepass(built, monkeypatch):
+    """the world that is mostly environment map, through the pipeline with the sky pre-pass and with ZR_SKY_PREPASS=0: bit-equal frames, and the pre-pass
+    did resolve pixels — so the map is read by the pre-pass as by the MISS stage"""
+    from raytracer_project_amd import capi
+    monkeypatch.setenv("ZR_FUSED", "0")
+    world = world_hdr_only()
+    cam, env_ = _small_camera()
+    env_ = world.environment(env_)
+    c = capi.Context(0)
+    try:
+        sc = capi.Scene(c, world.desc)
+        try:
+            on = sc.render(cam, env_, 4250, None)
+            presolved, path = c.presolved_pixels(), c.counters().path
+            monkeypatch.setenv("ZR_SKY_PREPASS", "0")
+            off = sc.render(cam, env_, 4250, None)
+            presolved_off = c.presolved_pixels()
+        finally:
+            sc.close()
+    finally:
+        c.close()
+    assert path == 2 and presolved > 0 and presolved_off == 0, (path, presolved, presolved_off)
+    d = on != off
+    assert not d.any(), f"{int(d.sum())} channels differ, first at {tuple(np.argwhere(d)[0].tolist())}"
+    assert float(on.sum()) > 0
+
+
+def test_textured_world_aov_and_passes_match_oracle(built):
+    """render_aov and render_passes of textured_surfaces against the oracle's: the albedo pass reads the image textures at the primary hits and clamps the
+    textured light's colour to 1 (material::get_albedo), the passes split a frame whose materials all read u and v"""
+    from oracle import zr_oracle_py as zo
+    from raytracer_project_amd import capi
+    world = world_textured_surfaces()
+    cam, env_ = _small_camera()
+    seed = 4242
+    reg = capi.Region(0, 0, cam.image_width, cam.image_height, 0, 0, 0, 0)
+    c = capi.Context(0)
+    try:
+        sc = capi.Scene(c, world.desc)
+        try:
+            aov = sc.render_aov(cam, seed, 25.0, reg)
+            passes = sc.render_passes(cam, env_, seed, reg)
+            ctr = c.counters()
+        finally:
+            sc.close()
+    finally:
+        c.close()
+    osc = zo.OracleScene(world.desc)
+    for got, want, what in zip(aov, osc.render_aov(cam, seed, reg, 25.0), ("albedo", "normal", "z-depth")):
+        _check(got, want, "textured_surfaces " + what)
+    want, octr = osc.render_passes(cam, env_, seed, reg)
+    for got, ref, what in zip(passes, want, ("beauty", "reflection", "refraction")):
+        _check(got, ref, "textured_surfaces " + what)
+        assert float(ref.sum()) > 0, what
+    assert (ctr.segments, ctr.rng_draws) == (octr.segments, octr.rng_draws)
+    albedo = aov[0]
+    assert (albedo <= 1.0).all() and ((albedo == 1.0).any(2) & (albedo < 1.0).any(2)).any(), "a pixel of the light with one channel clamped to 1 and another below it"
