@@ -1,5 +1,5 @@
 // zr_host.cpp — context life cycle and error reporting of the C ABI (include/zr_capi.h).  The scene side lives in zr_commit.cpp, the render side in
-// zr_render.cpp; zr_host_internal.h holds what they share.
+// zr_render.cpp, zr_accum.cpp and zr_image.cpp; zr_host_internal.h holds what they share.
 #include "zr_host_internal.h"
 
 namespace zr_host {

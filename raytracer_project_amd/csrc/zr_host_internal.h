@@ -4,7 +4,10 @@
 //                  flattener and the host builder's CPU half — no HIP, built on zr_scene_input.h: the world as given)
 //   zr_scene_query.cpp  what a committed scene answers: statistics, kernel builds, traversal stack, builder, zr_scene_tree_boxes
 //   zr_render.cpp  camera frame / sky constants, the frame job every render entry prepares (tile plan, validation) and its drivers (streaming pipeline, fused
-//                  kernel, pixel-group kernel), AOV / split passes, post stack, known-answer entry points
+//                  kernel, pixel-group kernel), AOV / split passes, BVH debug view, counters, known-answer entry points
+//   zr_accum.cpp   the accumulator (zr_accum): a frame in batches of samples, adaptive sampling, the queries of what it holds, render_batched
+//   zr_image.cpp   the image-space entry points, which need no scene: post stack, the two denoisers, sharpening, frame analysis
+//                  (these three share zr_frame.h: Plan, FrameJob, HostTimer and the drivers one of them calls in another)
 // Plain C++ (host compiler, -ffp-contract=off so that the camera frame and the sky constants are computed with exactly the reference's operation order,
 // camera.hpp:358-399, 874-895,914); the kernels live in the .hip files.  There is deliberately no CPU rendering path in this library: without a HIP device
 // zr_create() fails and says so.

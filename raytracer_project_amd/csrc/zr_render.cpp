@@ -1,9 +1,10 @@
 // zr_render.cpp — the render side of the C ABI (include/zr_capi.h).  Every render entry point describes its frame once (FrameJob, filled and validated by prepare_frame;
-// the region arithmetic lives on Plan) and hands it to a driver: enqueue_render (the streaming pipeline where the frame fits it, else the pixel-group kernel), render_stream
-// (the pipeline's round loop or the fused small-scene kernel) or the AOV / split-pass / BVH-debug launches.  Also here: post stack, counters, known-answer entry points.
-#include "zr_host_internal.h"
+// the region arithmetic lives on Plan: zr_frame.h) and hands it to a driver: enqueue_render (the streaming pipeline where the frame fits it, else the pixel-group kernel),
+// render_stream (the pipeline's round loop or the fused small-scene kernel) or the AOV / split-pass / BVH-debug launches.  Also here: counters, known-answer entry points.
+#include "zr_frame.h"
 
-namespace {
+namespace zr_host {
+namespace {   // this unit's own; what zr_accum.cpp and zr_image.cpp call too follows below
 
 // tiles per launch of the paths that render tile lists (the pixel-group kernel, the BVH debug view): one launch per frame unless the caller polls
 // (cancellation, progress), which needs batch boundaries
@@ -65,56 +66,6 @@ void make_env(const zr_env& e, zr::DEnv& d) {
     st3(d.sun_add, (scol * e.sun_intensity) * vis);
 }
 
-struct TileRect { int xa, xb, ya, yb; };   // the pixels [xa, xb) x [ya, yb); xb <= xa or yb <= ya: none
-
-// which pixels a call renders: the frame, its tile grid, the region rectangle and the tiles of this part (zr_region)
-struct Plan {
-    int W, H, ts, tiles_x, tiles_y, x0, y0, x1, y1;
-    std::vector<int32_t> tiles;
-    size_t npx() const { return (size_t)W * H; }
-    bool whole() const { return tiles.size() == (size_t)tiles_x * tiles_y && x0 == 0 && y0 == 0 && x1 == W && y1 == H; }
-    // tile t's pixels that lie in the region
-    TileRect clip(int32_t t) const {
-        const int tx = (t % tiles_x) * ts, ty = (t / tiles_x) * ts;
-        return {std::max(tx, x0), std::min(tx + ts, x1), std::max(ty, y0), std::min(ty + ts, y1)};
-    }
-    // work units of the streaming pipeline: one per primary sample of the plan's pixels
-    uint64_t units(int spp) const {
-        uint64_t n = 0;
-        for (int32_t t : tiles) {
-            const TileRect r = clip(t);
-            if (r.xb > r.xa && r.yb > r.ya) n += (uint64_t)(r.xb - r.xa) * (r.yb - r.ya) * (uint64_t)spp;
-        }
-        return n;
-    }
-};
-
-// lanes of a wave that share a pixel in the tile-list kernels: the largest power of two <= n samples, at most 64
-int lanes_for(int n) { int lanes = 64; while (lanes > n) lanes >>= 1; return lanes; }
-
-int make_plan(const zr_camera& cam, const zr_region* region, Plan& p) {
-    p.W = cam.image_width < 1 ? 1 : cam.image_width;
-    p.H = cam.image_height < 1 ? 1 : cam.image_height;
-    p.ts = 32; int mod = 1, rem = 0, skew = 0;
-    p.x0 = 0; p.y0 = 0; p.x1 = p.W; p.y1 = p.H;
-    if (region) {
-        if (region->tile_size > 0) p.ts = region->tile_size;
-        if (region->tile_mod > 1) { mod = region->tile_mod; rem = region->tile_rem; skew = region->tile_skew; }
-        if (region->w > 0 && region->h > 0) { p.x0 = region->x0; p.y0 = region->y0; p.x1 = region->x0 + region->w; p.y1 = region->y0 + region->h; }
-    }
-    if (p.x0 < 0 || p.y0 < 0 || p.x1 > p.W || p.y1 > p.H || rem < 0 || rem >= mod || skew < 0 || p.ts > 1024)
-        return fail(ZR_E_INVALID, "region outside the %dx%d frame or bad tile parameters", p.W, p.H);
-    p.tiles_x = (p.W + p.ts - 1) / p.ts; p.tiles_y = (p.H + p.ts - 1) / p.ts;
-    p.tiles.clear();
-    for (int ty = p.y0 / p.ts; ty <= (p.y1 - 1) / p.ts; ty++)
-        for (int tx = p.x0 / p.ts; tx <= (p.x1 - 1) / p.ts; tx++) {
-            int t = ty * p.tiles_x + tx;
-            const int part = skew > 0 ? (int)(((long long)tx + (long long)skew * ty) % mod) : t % mod;   // zr_region::tile_skew
-            if (part == rem) p.tiles.push_back(t);
-        }
-    return ZR_OK;
-}
-
 // tiles [first, first + count) of the uploaded tile list, for one launch of a tile-list kernel
 zr::WorkDesc work_desc(const Plan& p, const int32_t* d_tiles, size_t first, size_t count, int lanes) {
     zr::WorkDesc wd;
@@ -122,19 +73,6 @@ zr::WorkDesc work_desc(const Plan& p, const int32_t* d_tiles, size_t first, size
     wd.x0 = p.x0; wd.y0 = p.y0; wd.x1 = p.x1; wd.y1 = p.y1;
     wd.lanes_per_pixel = lanes;
     return wd;
-}
-
-// the plan's pixels of the device frame -> the caller's frame, through `scratch`; no other pixel of `out` is touched (null: an output the caller did not ask for)
-int copy_region(const Plan& p, const double* d_frame, double* out, std::vector<double>& scratch) {
-    if (!out) return ZR_OK;
-    scratch.resize(p.npx() * 3);
-    HIP_OK(hipMemcpy(scratch.data(), d_frame, scratch.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int32_t t : p.tiles) {
-        const TileRect r = p.clip(t);
-        for (int y = r.ya; y < r.yb; y++)
-            if (r.xb > r.xa) std::memcpy(out + ((size_t)y * p.W + r.xa) * 3, scratch.data() + ((size_t)y * p.W + r.xa) * 3, (size_t)(r.xb - r.xa) * 3 * sizeof(double));
-    }
-    return ZR_OK;
 }
 
 // a zeroed device frame for an output the caller asked for
@@ -146,67 +84,9 @@ int zeroed_frame(DevBuf<double>& d, const double* out, const Plan& p, hipStream_
     return ZR_OK;
 }
 
-// the scene half of an entry point's argument preamble (the null tests differ per entry and stay there)
-int scene_ready(const zr_ctx* c, const zr_scene* s, const char* entry, bool any_context = false) {
-    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede %s", entry);
-    if (!any_context && s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
-    return ZR_OK;
-}
-
 int check_env(const zr::DEnv& de, const zr_scene* s) {
     if (de.mode > ZR_ENV_SOLID_COLOR) return fail(ZR_E_INVALID, "unknown environment mode %u", de.mode);
     if (de.mode == ZR_ENV_HDR_MAP && de.hdr_tex != ZR_NO_TEXTURE && de.hdr_tex >= s->textures.size()) return fail(ZR_E_INVALID, "environment texture id out of range");
-    return ZR_OK;
-}
-
-// One frame job: what every render entry works out before it launches, and what its driver needs.  prepare_frame fills the first line, the entry the rest.
-struct FrameJob {
-    Plan plan; zr::DCamera dc; zr::DEnv de{}; uint64_t seed = 0; hipStream_t stream = nullptr;
-    bool count = false;                               // zr_counters wanted
-    uint32_t sample0 = 0;                             // a batch of a progressive render: dc.spp samples from this one on (render_stream; 0 = the whole frame)
-    double* d_out = nullptr; double* d_out2 = nullptr;   // device frames (d_out2: the refraction frame of the split's replay pass)
-    volatile const uint8_t* keep_going = nullptr; volatile int* rows_done = nullptr;
-    zr::StreamProgress* progress = nullptr;
-    const uint32_t* d_list = nullptr; uint32_t n_list = 0;   // a device pixel list of the caller's (an adaptive pass: the active pixels) instead of the plan's cached one
-    bool interactive() const { return keep_going || rows_done; }   // the caller polls: the tile-list paths need batch boundaries
-};
-
-// the shared validation, in the order every entry has had it: region and tile parameters, then the environment (`env` is null for the AOV passes, which have none)
-int prepare_frame(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region, FrameJob& job) {
-    HIP_OK(hipSetDevice(c->device));
-    int rc = make_plan(*cam, region, job.plan);
-    if (rc) return rc;
-    make_camera(*cam, job.dc);
-    if (env) { make_env(*env, job.de); if ((rc = check_env(job.de, s))) return rc; }
-    job.seed = seed; job.stream = c->stream;
-    return ZR_OK;
-}
-
-// Does the frame fit the streaming pipeline's packing (zr_launch.h: ST_MAX_*)?  Otherwise the pixel-group kernels render it: slower, same results.
-// depth_factor: paths per sample (the split passes trace two and count both in the bounce byte); units: the caller's count of work units
-bool fits_stream(const zr_ctx* c, const zr_scene* s, const Plan& plan, const zr::DCamera& dc, int depth_factor, uint64_t units) {
-    return c->variant == 2 && s->quad_ok /* ST_MAX_LEAF_PRIMS */ && depth_factor * dc.max_depth <= zr::ST_MAX_BOUNCES && units <= zr::ST_MAX_UNITS &&
-           plan.W <= zr::ST_MAX_FRAME_SIDE && plan.H <= zr::ST_MAX_FRAME_SIDE;
-}
-
-int resolve_times(zr_ctx* c) {
-    if (c->pending.empty()) return ZR_OK;
-    bool fresh = false;
-    for (auto& p : c->pending) {
-        HIP_OK(hipEventSynchronize(p.b));
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, p.a, p.b));
-        if (p.kind == c->log_kind) c->log.push_back(ms);  // default: the dominant kernel's launches (render_* / stream_extend)
-        if (p.render_id == c->render_id) {
-            if (!fresh) { c->last_render_ms = 0; c->last_extend_ms = 0; c->last_shade_ms = 0; fresh = true; }
-            c->last_render_ms += ms;
-            if (p.kind == 1) c->last_extend_ms += ms;
-            if (p.kind == 2) c->last_shade_ms += ms;
-        }
-        c->pool.push_back(p.a); c->pool.push_back(p.b);
-    }
-    c->pending.clear();
-    if (c->log.size() > (1u << 20)) c->log.erase(c->log.begin(), c->log.begin() + (c->log.size() - (1u << 20)));
     return ZR_OK;
 }
 
@@ -223,39 +103,7 @@ int ensure_stack_slabs(zr_ctx* c, const zr_scene* s) {
     return ZR_OK;
 }
 
-// records a pair of HIP events around a launch into zr_ctx::pending (resolve_times turns them into milliseconds); the one recycler of zr_ctx::pool
-struct HostTimer : zr::StreamTimer {
-    zr_ctx* c; hipEvent_t cur_a = nullptr; hipError_t err = hipSuccess;
-    explicit HostTimer(zr_ctx* c) : c(c) {}
-    hipEvent_t get() {
-        if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }
-        hipEvent_t e = nullptr;
-        if ((err = hipEventCreate(&e)) != hipSuccess) return nullptr;
-        return e;
-    }
-    void begin(hipStream_t st, int) override { cur_a = get(); if (cur_a) (void)hipEventRecord(cur_a, st); }
-    void end(hipStream_t st, int kind) override {
-        hipEvent_t b = get();
-        if (!cur_a || !b) return;
-        (void)hipEventRecord(b, st);
-        zr_ctx::Pending pe{}; pe.a = cur_a; pe.b = b; pe.render_id = c->render_id; pe.kind = kind;
-        c->pending.push_back(pe);
-        cur_a = nullptr;
-    }
-};
-
 // ---- variant 2: the streaming wavefront pipeline (zr_stream.hip), in the steps of render_stream below -------------------------------------------------
-
-// the plan's pixels in tile order, x | y << 16 (ST_MAX_FRAME_SIDE)
-std::vector<uint32_t> plan_pixels(const Plan& plan) {
-    std::vector<uint32_t> pix;
-    pix.reserve((size_t)plan.tiles.size() * plan.ts * plan.ts);
-    for (int32_t t : plan.tiles) {
-        const TileRect r = plan.clip(t);
-        for (int y = r.ya; y < r.yb; y++) for (int x = r.xa; x < r.xb; x++) pix.push_back((uint32_t)x | ((uint32_t)y << 16));
-    }
-    return pix;
-}
 
 // the plan's pixels as the pipeline's pixel list, uploaded when the plan differs from the cached list's
 int upload_pixel_list(zr_ctx* c, const Plan& plan) {
@@ -264,13 +112,13 @@ int upload_pixel_list(zr_ctx* c, const Plan& plan) {
     // 60 ms of a rank's 1/8 share).  The drain is as long as the paths started last, so the list runs BOTTOM-UP: the top
     // of a frame is where the sky is, and a sky sample ends in one round.  The image does not depend on the order (every
     // sample is written once and reduced in a fixed order).
-    const double bottom_up = env_double("ZR_STREAM_BOTTOM_UP", 1);
+    const bool reversed = list_runs_reversed();
     std::vector<int32_t> key = {plan.W, plan.H, plan.ts, plan.x0, plan.y0, plan.x1, plan.y1, (int32_t)plan.tiles.size(),
                                 plan.tiles.empty() ? -1 : plan.tiles.front(), plan.tiles.empty() ? -1 : plan.tiles.back(),
-                                (int32_t)bottom_up};
+                                (int32_t)reversed};
     if (key == c->pix_key && c->d_pixels.p) return ZR_OK;
     std::vector<uint32_t> pix = plan_pixels(plan);
-    if (bottom_up != 0) std::reverse(pix.begin(), pix.end());
+    if (reversed) std::reverse(pix.begin(), pix.end());
     int rc = c->d_pixels.upload(pix);
     if (rc == ZR_OK) c->pix_key = key;
     return rc;
@@ -364,7 +212,7 @@ int sky_prepass(zr_ctx* c, const zr_scene* s, const FrameJob& job, const uint32_
     HIP_OK(zr::launch_sky_prepass(s->ds, job.dc, job.de, job.seed, pixels, n_pix, (uint32_t)job.dc.spp, job.sample0, job.d_out, c->d_sky_flag.p, c->d_sky_blocks.p,
                                   c->d_walk_pixels.p, c->d_n_walk.p, job.stream));
     timer.end(job.stream, 0);
-    if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
+    if ((rc = timer.status())) return rc;
     HIP_OK(hipMemcpyAsync(c->h_active, c->d_n_walk.p, sizeof(uint32_t), hipMemcpyDeviceToHost, job.stream));   // (pinned; the round loop's copies come later)
     HIP_OK(hipStreamSynchronize(job.stream));
     *n_walk = c->h_active[0];
@@ -372,241 +220,8 @@ int sky_prepass(zr_ctx* c, const zr_scene* s, const FrameJob& job, const uint32_
     return ZR_OK;
 }
 
-// Renders job.plan into job.d_out through the pipeline or, for a small world, the fused kernel.  The frame must fit the pipeline (fits_stream: both callers ask
-// first).  Synchronises the stream internally (the round loop needs the active-slot count), so zr_render_device returns with the frame complete.
-// mode 0: the render; 1 / 2: beauty pass and replay pass of the reflection / refraction split (zr_stream.hip, stream_shade)
-int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode = 0) {
-    int rc = ZR_OK;
-    // the caller's own list leaves the cached one (zr_ctx::d_pixels, pix_key) alone: a later render of the plan gets the plan's list
-    if (!job.d_list && (rc = upload_pixel_list(c, job.plan))) return rc;
-    const uint32_t* pixels = job.d_list ? job.d_list : c->d_pixels.p;
-    uint32_t n_pix = job.d_list ? job.n_list : (uint32_t)c->d_pixels.n;
-    const uint32_t spp = (uint32_t)job.dc.spp;
-    if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
-    c->render_id++; c->last_stream = job.stream; c->last_counted = job.count; c->last_rounds = 0;
-    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
-    if (n_pix == 0) return ZR_OK;
-    uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
-    // per-sample radiance first: without it this pipeline cannot run at all (the caller falls back to the pixel-group kernel)
-    size_t samples_n = (size_t)units * 3;
-    if (c->d_partial.n < samples_n) {
-        HIP_OK(hipStreamSynchronize(job.stream));
-        if (c->d_partial.alloc(samples_n) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes)", samples_n * sizeof(double));
-    }
-    hipStream_t streams[ST_MAX_POOLS];
-    streams[0] = job.stream;
-    for (int k = 1; k < ST_MAX_POOLS; k++) streams[k] = c->sub[k];
-    const bool fused = mode == 0 && s->fused_ok && s->leaf_level <= 2 && s->leaf_objects > 0 && (double)s->leaf_objects <= env_double("ZR_FUSED_MAX", ZR_FUSED_OBJECTS) &&
-                       env_double("ZR_FUSED", 1) != 0;
-    // A frame that the pipeline reduces into d_out from the plan's own list first loses its sky pixels (sky_prepass): they never become work units.  Not the counting
-    // render (the instrument: every unit goes through the pipeline), not a batch of an accumulator (d_out == nullptr, its own list), not the split passes.
-    if (mode == 0 && !fused && job.d_out && !job.d_list && !job.count && s->ds.shade_escape && env_double("ZR_SKY_PREPASS", 1) != 0) {
-        uint32_t n_walk = n_pix;
-        if ((rc = sky_prepass(c, s, job, pixels, n_pix, &n_walk))) return rc;
-        c->presolved = n_pix - n_walk; c->presolved_render = c->render_id;
-        if (n_walk < n_pix) { pixels = c->d_walk_pixels.p; n_pix = n_walk; units = (uint64_t)n_pix * spp; samples_n = (size_t)units * 3; }
-        if (n_pix == 0) { c->last_path = 2; return ZR_OK; }   // (the stream is idle: sky_prepass synchronised it)
-    }
-    zr::StreamJob sj{};
-    sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, pixels, c->d_partial.p, job.d_out, job.d_out2, job.count, job.sample0};
-    sj.ctx = zr::StreamContext{c->d_ctl.p, nullptr, 0, c->st_blocks, c->d_ctr.p, streams, 1, c->st_event, c->h_active};
-    sj.hooks = zr::StreamHooks{nullptr, job.keep_going, job.progress, nullptr};
-    const bool polled = job.keep_going || job.progress;   // a cancelled frame / a preview reduces what exists: the samples start at zero
-    if (fused) {
-        if (polled) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), job.stream));
-        return render_fused(c, s, sj);
-    }
-    c->last_path = 2;
-    if ((rc = ensure_stack_slabs(c, s))) return rc;
-    sj.ctx.overflow = c->d_st_overflow.p; sj.ctx.ovf_levels = c->st_ovf_levels;
-    // Two sub-pools, a fraction of a round apart on two streams, let one pool's SHADE run beside the other's EXTEND.  Until round 3 that paid on a rank's share only
-    // (the whole frame: 366.6 against 365.7 ms): SHADE needed 124 registers and found no room beside EXTEND's waves.  The lean builds of both kernels use 80
-    // (zr_stream.hip), a SIMD holds three waves of each, and a whole cfg3 frame gains 3.5 % with 64 Mi slots, 5.4 % with 128 Mi (profiles/r4_experiments_ab.txt); the
-    // general builds (demo: 128 + 117 registers) do not fit beside each other and lose 2 %: one pool for those
-    const bool lean_pair = s->leaf_level == 0 && s->ds.shade_lean != 0 && mode == 0;
-    if ((rc = size_slot_pool(c, units, spp, lean_pair, job.stream, sj.pool))) return rc;
-    if (polled) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), job.stream));
-    sj.split.mode = mode;
-    if (mode != 0 && (rc = split_buffers(c, units, mode, job.stream, sj.split))) return rc;
-    const bool sharded = job.plan.tiles.size() < (size_t)job.plan.tiles_x * job.plan.tiles_y;
-    sj.ctx.n_pools = c->st_pools > 0 ? c->st_pools : ((sharded || lean_pair) ? 2 : 1);
-    HostTimer timer(c);
-    int rounds = 0;
-    sj.hooks.timer = &timer; sj.hooks.done_out = &rounds;
-    hipError_t e = zr::stream_render(s->ds, sj, s->leaf_level);
-    if (e != hipSuccess) return fail(ZR_E_DEVICE, "streaming pipeline failed: %s", hipGetErrorString(e));
-    c->last_rounds = (uint64_t)(rounds < 0 ? -rounds : rounds);
-    HIP_OK(hipStreamSynchronize(job.stream));
-    if (rounds < 0) return fail(ZR_E_CANCELLED, "render cancelled after %d rounds", -rounds);
-    return ZR_OK;
-}
-
-// ---- progressive accumulation: a frame in batches of samples (zr_accum, include/zr_capi.h) ----------------------------------------------------------
-
-// What a zr_accum holds.  The lane sums live in d_partial ([pixel][channel][lane], zr_launch.h: ACCUM_DOUBLES_PER_PIXEL), pixel k being the k-th of the plan's
-// pixels in tile order (d_pixels) whichever way the pipeline's own list runs.
-struct AccumState {
-    zr_ctx* ctx = nullptr; int device = 0;
-    Plan plan;
-    DevBuf<double> d_partial; DevBuf<uint32_t> d_pixels; uint32_t n_pix = 0;
-    int first = 0, done = 0;
-    int route = 2;                 // zr_counters::path of the batches so far: which one-shot kernel's pairing the resolve follows
-    bool bound = false;            // a batch has been added since create / reset: later ones must bring the same camera, seed and scene
-    zr_camera cam{}; uint64_t seed = 0; const zr_scene* scene = nullptr;
-    // adaptive sampling (zr_render_adaptive), allocated by its first run: the sample count per pixel, the active list and its slot index
-    // (two of each: a pass compacts one into the other), the flags per list position and the compaction's block counts and totals
-    bool adaptive = false;         // an adaptive pass has completed since create / reset: the counts are per pixel (d_count) and `done` is the largest
-    DevBuf<int32_t> d_count; DevBuf<uint32_t> d_list[2], d_slot[2], d_flag, d_block_active, d_block_at_max, d_totals;
-    size_t device_bytes() const {
-        return (size_t)n_pix * (zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double) + sizeof(uint32_t)) + d_count.n * sizeof(int32_t) +
-               (d_list[0].n + d_list[1].n + d_slot[0].n + d_slot[1].n + d_flag.n + d_block_active.n + d_block_at_max.n + d_totals.n) * sizeof(uint32_t);
-    }
-};
-
-int accum_init(AccumState& a, zr_ctx* c, const zr_camera& cam, const zr_region* region) {
-    int rc = make_plan(cam, region, a.plan);
-    if (rc) return rc;
-    if (a.plan.W > zr::ST_MAX_FRAME_SIDE || a.plan.H > zr::ST_MAX_FRAME_SIDE) return fail(ZR_E_INVALID, "an accumulator's frame may be at most %d pixels a side", zr::ST_MAX_FRAME_SIDE);
-    const std::vector<uint32_t> pix = plan_pixels(a.plan);
-    if (pix.size() > 0xFFFFFFFFull) return fail(ZR_E_INVALID, "too many pixels for one accumulator");
-    a.ctx = c; a.device = c->device; a.n_pix = (uint32_t)pix.size();
-    if ((rc = a.d_pixels.upload(pix))) return rc;
-    if (a.d_partial.alloc((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL) != ZR_OK)
-        return fail(ZR_E_NOMEM, "no device memory for the lane sums of %u pixels (%zu bytes)", a.n_pix, (size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double));
-    HIP_OK(hipMemset(a.d_partial.p, 0, std::max<size_t>((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double), 64)));
-    HIP_OK(hipDeviceSynchronize());   // the context's streams do not wait for the null stream
-    a.first = 0; a.done = 0; a.bound = false; a.route = 2; a.adaptive = false;
-    return ZR_OK;
-}
-
-// The samples [sample0, sample0 + n) of n_pix listed pixels as per-sample radiance in zr_ctx::d_partial ([pixel][n][3]), by the route zr_render takes for this scene and
-// camera.  job: plan, camera, environment, seed, stream, count and keep_going as prepare_frame and the caller left them.  `pixels` is what the pixel-group route
-// renders; the pipeline renders job.d_list when that is set (the same list) and otherwise the plan's cached list, *flipped then saying that it ran in the reverse of
-// the plan's order (ZR_STREAM_BOTTOM_UP).  Nothing but d_partial and the counters is written: the caller adds the samples to its sums, or drops them.
-int render_batch_samples(zr_ctx* c, const zr_scene* s, FrameJob& job, const uint32_t* pixels, uint32_t n_pix, int sample0, int n, HostTimer& timer, bool* flipped) {
-    job.dc.spp = n; job.sample0 = (uint32_t)sample0; job.d_out = nullptr; job.d_out2 = nullptr; job.progress = nullptr; job.rows_done = nullptr;
-    *flipped = false;
-    if (job.keep_going && *job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled before it began");
-    const uint64_t units = (uint64_t)n_pix * (uint64_t)n;
-    if (fits_stream(c, s, job.plan, job.dc, 1, 0)) {
-        if (units > zr::ST_MAX_UNITS) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu work units, the pipeline numbers 2^32 - 1 per run: ask for fewer samples", n, (unsigned long long)units);
-        *flipped = !job.d_list && env_double("ZR_STREAM_BOTTOM_UP", 1) != 0;
-        return render_stream(c, s, job);
-    }
-    // the pixel-group route: the batch's per-sample radiance
-    if (units > (1ull << 37)) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu samples of radiance: ask for fewer", n, (unsigned long long)units);
-    if (c->d_partial.n < units * 3) {
-        HIP_OK(hipStreamSynchronize(job.stream));
-        if (c->d_partial.alloc(units * 3) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes): ask for fewer samples", (size_t)units * 3 * sizeof(double));
-    }
-    c->last_path = 0;
-    if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
-    c->render_id++; c->last_stream = job.stream; c->last_counted = job.count;
-    timer.begin(job.stream, 1);
-    HIP_OK(zr::launch_render_samples(s->ds, job.dc, job.de, job.seed, pixels, n_pix, (uint32_t)sample0, (uint32_t)n, c->d_partial.p, c->d_ctr.p, job.count, job.stream));
-    timer.end(job.stream, 1);
-    if (job.keep_going) {
-        HIP_OK(hipStreamSynchronize(job.stream));
-        if (*job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled");
-    }
-    return ZR_OK;
-}
-
-// One batch: the samples [sample0, sample0 + n) of every pixel of the accumulator by the route zr_render takes for this scene and camera, added to the lane sums.
-// The batch is rendered whole before the sums are touched: on any failure — ZR_E_CANCELLED, ZR_E_NOMEM (this many samples do not fit the route in one run) — they
-// are as they were.
-int accumulate_batch(zr_ctx* c, const zr_scene* s, FrameJob& job, AccumState& a, int sample0, int n) {
-    c->last_rounds = 0;
-    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
-    if (a.n_pix == 0) return ZR_OK;
-    HostTimer timer(c);
-    bool flipped = false;
-    int rc = render_batch_samples(c, s, job, a.d_pixels.p, a.n_pix, sample0, n, timer, &flipped);
-    if (rc) return rc;
-    timer.begin(job.stream, 3);
-    HIP_OK(zr::launch_accumulate(c->d_partial.p, a.n_pix, (uint32_t)n, (uint32_t)sample0, flipped, a.d_partial.p, job.stream));
-    timer.end(job.stream, 3);
-    if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
-    HIP_OK(hipStreamSynchronize(job.stream));
-    a.route = c->last_path;
-    return ZR_OK;
-}
-
-// the mean of the samples held, into the accumulator's pixels of the device frame d_out, with the pairing of the kernel that rendered them (zr_stream.hip: accum_resolve)
-int accum_resolve_into(const AccumState& a, double* d_out, hipStream_t stream) {
-    // per-pixel counts are all at least 64, where lanes_for gives 64
-    if (a.adaptive) HIP_OK(zr::launch_accum_resolve_counts(a.d_partial.p, a.d_pixels.p, a.d_count.p, a.n_pix, a.plan.W, a.route == 0 ? 64 : 1, d_out, stream));
-    else HIP_OK(zr::launch_accum_resolve(a.d_partial.p, a.d_pixels.p, a.n_pix, a.plan.W, a.done, a.route == 0 ? lanes_for(a.done) : 1, d_out, stream));
-    return ZR_OK;
-}
-
 // work units one run of the pipeline may have: the packing limit, or less (ZR_STREAM_BATCH_UNITS: a development switch that makes a small frame render in batches)
 uint64_t stream_unit_limit() { return (uint64_t)std::min((double)zr::ST_MAX_UNITS, std::max(1.0, env_double("ZR_STREAM_BATCH_UNITS", (double)zr::ST_MAX_UNITS))); }
-
-// A frame whose only misfit is its size — more work units than one run numbers, or no memory for 24 bytes of samples[] per unit — rendered through the pipeline in
-// batches of samples with an accumulator of its own.  Same image bit for bit (the lane sums do not know where the batches were cut), counters are the frame's totals.
-// Batches are equal, a multiple of 64 samples where possible, at most `n_max` samples; a batch that meets ZR_E_NOMEM is retried at half the size.  ZR_E_NOMEM from here:
-// not even small batches fit (or the lane sums themselves do not): the caller falls back to the pixel-group kernel.
-int render_batched(zr_ctx* c, const zr_scene* s, const FrameJob& frame, int n_max) {
-    const int spp = frame.dc.spp;
-    AccumState a;
-    a.plan = frame.plan;
-    {
-        const std::vector<uint32_t> pix = plan_pixels(a.plan);
-        a.ctx = c; a.device = c->device; a.n_pix = (uint32_t)pix.size();
-        int rc = a.d_pixels.upload(pix);
-        if (rc) return rc;
-        HIP_OK(hipStreamSynchronize(frame.stream));
-        if (a.d_partial.alloc((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL) != ZR_OK)
-            return fail(ZR_E_NOMEM, "no device memory for the lane sums of %u pixels (%zu bytes)", a.n_pix, (size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double));
-        HIP_OK(hipMemsetAsync(a.d_partial.p, 0, std::max<size_t>((size_t)a.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double), 64), frame.stream));
-    }
-    n_max = std::max(1, std::min(n_max, spp));
-    const int n_batches = (spp + n_max - 1) / n_max;
-    int n = (spp + n_batches - 1) / n_batches;
-    if (n >= 64) n = (n + 63) / 64 * 64 <= n_max ? (n + 63) / 64 * 64 : std::max(n_max / 64 * 64, 1);
-    FrameJob job = frame;
-    unsigned long long totals[zr::CTR_WORDS] = {0};
-    uint64_t rounds = 0;
-    const uint64_t id0 = c->render_id;
-    bool cancelled = false;
-    while (a.done < spp) {
-        const int nb = std::min(n, spp - a.done);
-        int rc = accumulate_batch(c, s, job, a, a.done, nb);
-        if (rc == ZR_E_NOMEM && nb > 1) {
-            n = nb / 2 >= 64 ? nb / 2 / 64 * 64 : nb / 2;
-            std::fprintf(stderr, "[zr] %s: retrying with batches of %d samples\n", zr_host::last_error(), n);
-            continue;
-        }
-        if (rc == ZR_E_CANCELLED) { cancelled = true; break; }
-        if (rc) return rc;
-        if (frame.count) {
-            unsigned long long h[zr::CTR_WORDS];
-            HIP_OK(hipMemcpy(h, c->d_ctr.p, sizeof h, hipMemcpyDeviceToHost));
-            for (int w = 0; w < zr::CTR_WORDS; w++) totals[w] += h[w];
-        }
-        rounds += c->last_rounds;
-        a.done += nb;
-        if (a.done < spp) {
-            const double f = (double)a.done / spp;
-            if (frame.rows_done) { const int r = std::min(frame.plan.H - 1, (int)(f * frame.plan.H)); if (r > *frame.rows_done) *frame.rows_done = r; }
-            if (frame.progress) {   // the preview between batches is the exact image of the samples done
-                const bool wants = frame.d_out && frame.progress->wants_frame();
-                if (wants) { if ((rc = accum_resolve_into(a, frame.d_out, frame.stream))) return rc; HIP_OK(hipStreamSynchronize(frame.stream)); }
-                frame.progress->report(f, wants);
-            }
-            if (frame.keep_going && *frame.keep_going == 0) { cancelled = true; break; }
-        }
-    }
-    // one render as far as zr_get_counters is concerned: the launches of every batch count towards its times
-    for (auto& p : c->pending) if (p.render_id > id0) p.render_id = c->render_id;
-    if (a.done > 0 && frame.d_out) { int rc = accum_resolve_into(a, frame.d_out, frame.stream); if (rc) return rc; }
-    if (frame.count) HIP_OK(hipMemcpyAsync(c->d_ctr.p, totals, sizeof totals, hipMemcpyHostToDevice, frame.stream));
-    HIP_OK(hipStreamSynchronize(frame.stream));
-    c->last_counted = frame.count; c->last_rounds = rounds;
-    if (cancelled) return fail(ZR_E_CANCELLED, "render cancelled after %d of %d samples per pixel", a.done, spp);
-    return ZR_OK;
-}
 
 // ---- the tile-list paths ------------------------------------------------------------------------------------------------------------------------------
 
@@ -674,8 +289,7 @@ int enqueue_render(zr_ctx* c, const zr_scene* s, const FrameJob& job) {
             timer.begin(job.stream, 1);
             HIP_OK(zr::launch_render(s->ds, job.dc, job.de, job.seed, work_desc(plan, c->d_tiles.p, first, count, lanes_for(job.dc.spp)), job.d_out, c->d_ctr.p, job.count, job.stream));
             timer.end(job.stream, 1);
-            if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
-            return ZR_OK;
+            return timer.status();
         },
         [&](int last_tile, bool) {
             const int rows = std::min(plan.H, (last_tile / plan.tiles_x) * plan.ts);
@@ -683,265 +297,212 @@ int enqueue_render(zr_ctx* c, const zr_scene* s, const FrameJob& job) {
         });
 }
 
-// what the queries of an accumulator's contents share (zr_accum_error, zr_accum_sample_counts, zr_accum_lane_sums): something has been rendered
-int query_ready(const AccumState& st, const char* entry) {
-    if (st.done == 0) return fail(ZR_E_STATE, "zr_render_accumulate or zr_render_adaptive must precede %s", entry);
+int check_debug_params(const zr_bvh_debug_params* dp) {
+    if (!dp) return fail(ZR_E_INVALID, "null argument");
+    if (dp->level < -1) return fail(ZR_E_INVALID, "BVH debug level %d below -1", dp->level);
+    if (!(dp->thickness > 0.0f) || !std::isfinite(dp->thickness)) return fail(ZR_E_INVALID, "BVH debug thickness must be a positive finite number");
     return ZR_OK;
 }
-// per-slot values -> the plan's pixels of a W*H array
-template <class T>
-void scatter_to_frame(const Plan& plan, const std::vector<T>& per_slot, T* out) {
-    const std::vector<uint32_t> pix = plan_pixels(plan);
-    for (size_t k = 0; k < pix.size(); k++) out[(size_t)(pix[k] >> 16) * plan.W + (pix[k] & 0xFFFFu)] = per_slot[k];
+
+// The end of a frame entry that polls, `rrc` being its driver's answer: a cancelled render still delivers what it rendered (`copy`), then reports the cancellation.
+template <class Copy>
+int deliver(zr_ctx* c, int rrc, Copy copy, volatile int* rows_done, int H) {
+    if (rrc != ZR_OK && rrc != ZR_E_CANCELLED) return rrc;
+    std::string cancel_msg = zr_host::last_error();
+    HIP_OK(hipStreamSynchronize(c->stream));
+    if (int rc = copy()) return rc;
+    if (rrc == ZR_E_CANCELLED) return fail(rrc, "%s", cancel_msg.c_str());
+    if (rows_done) *rows_done = H;  // camera.hpp:576-578
+    return ZR_OK;
+}
+
+// The device half of a trace or known-answer entry: `in` uploaded, `launch(d_in, d_out)` on the context's stream, its n_out results back on the host.
+template <class In, class Out, class Launch>
+int run_on_device(zr_ctx* c, const In* in, size_t n_in, Out* out, size_t n_out, Launch launch) {
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<In> d_in; DevBuf<Out> d_out;
+    int rc;
+    if ((rc = d_in.upload(in, n_in)) || (rc = d_out.alloc(n_out))) return rc;
+    HIP_OK(launch(d_in.p, d_out.p));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    HIP_OK(hipMemcpy(out, d_out.p, n_out * sizeof(Out), hipMemcpyDeviceToHost));
+    return ZR_OK;
 }
 
 }  // namespace
 
-struct zr_accum { AccumState st; };
+// lanes of a wave that share a pixel in the tile-list kernels: the largest power of two <= n samples, at most 64
+int lanes_for(int n) { int lanes = 64; while (lanes > n) lanes >>= 1; return lanes; }
+
+int make_plan(const zr_camera& cam, const zr_region* region, Plan& p) {
+    p.W = cam.image_width < 1 ? 1 : cam.image_width;
+    p.H = cam.image_height < 1 ? 1 : cam.image_height;
+    p.ts = 32; int mod = 1, rem = 0, skew = 0;
+    p.x0 = 0; p.y0 = 0; p.x1 = p.W; p.y1 = p.H;
+    if (region) {
+        if (region->tile_size > 0) p.ts = region->tile_size;
+        if (region->tile_mod > 1) { mod = region->tile_mod; rem = region->tile_rem; skew = region->tile_skew; }
+        if (region->w > 0 && region->h > 0) { p.x0 = region->x0; p.y0 = region->y0; p.x1 = region->x0 + region->w; p.y1 = region->y0 + region->h; }
+    }
+    if (p.x0 < 0 || p.y0 < 0 || p.x1 > p.W || p.y1 > p.H || rem < 0 || rem >= mod || skew < 0 || p.ts > 1024)
+        return fail(ZR_E_INVALID, "region outside the %dx%d frame or bad tile parameters", p.W, p.H);
+    p.tiles_x = (p.W + p.ts - 1) / p.ts; p.tiles_y = (p.H + p.ts - 1) / p.ts;
+    p.tiles.clear();
+    for (int ty = p.y0 / p.ts; ty <= (p.y1 - 1) / p.ts; ty++)
+        for (int tx = p.x0 / p.ts; tx <= (p.x1 - 1) / p.ts; tx++) {
+            int t = ty * p.tiles_x + tx;
+            const int part = skew > 0 ? (int)(((long long)tx + (long long)skew * ty) % mod) : t % mod;   // zr_region::tile_skew
+            if (part == rem) p.tiles.push_back(t);
+        }
+    return ZR_OK;
+}
+
+// the plan's pixels of the device frame -> the caller's frame, through `scratch`; no other pixel of `out` is touched (null: an output the caller did not ask for)
+int copy_region(const Plan& p, const double* d_frame, double* out, std::vector<double>& scratch) {
+    if (!out) return ZR_OK;
+    scratch.resize(p.npx() * 3);
+    HIP_OK(hipMemcpy(scratch.data(), d_frame, scratch.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int32_t t : p.tiles) {
+        const TileRect r = p.clip(t);
+        for (int y = r.ya; y < r.yb; y++)
+            if (r.xb > r.xa) std::memcpy(out + ((size_t)y * p.W + r.xa) * 3, scratch.data() + ((size_t)y * p.W + r.xa) * 3, (size_t)(r.xb - r.xa) * 3 * sizeof(double));
+    }
+    return ZR_OK;
+}
+
+// the scene half of an entry point's argument preamble (the null tests differ per entry and stay there)
+int scene_ready(const zr_ctx* c, const zr_scene* s, const char* entry, bool any_context) {
+    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede %s", entry);
+    if (!any_context && s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
+    return ZR_OK;
+}
+
+// the shared validation, in the order every entry has had it: region and tile parameters (`plan`: an accumulator's own, in place of the one `region` describes), then the
+// environment (`env` is null for the AOV passes, which have none)
+int prepare_frame(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region, FrameJob& job, const Plan* plan) {
+    HIP_OK(hipSetDevice(c->device));
+    if (plan) job.plan = *plan;
+    else if (int rc = make_plan(*cam, region, job.plan)) return rc;
+    make_camera(*cam, job.dc);
+    if (env) { make_env(*env, job.de); if (int rc = check_env(job.de, s)) return rc; }
+    job.seed = seed; job.stream = c->stream;
+    return ZR_OK;
+}
+
+// Does the frame fit the streaming pipeline's packing (zr_launch.h: ST_MAX_*)?  Otherwise the pixel-group kernels render it: slower, same results.
+// depth_factor: paths per sample (the split passes trace two and count both in the bounce byte); units: the caller's count of work units
+bool fits_stream(const zr_ctx* c, const zr_scene* s, const Plan& plan, const zr::DCamera& dc, int depth_factor, uint64_t units) {
+    return c->variant == 2 && s->quad_ok /* ST_MAX_LEAF_PRIMS */ && depth_factor * dc.max_depth <= zr::ST_MAX_BOUNCES && units <= zr::ST_MAX_UNITS &&
+           plan.W <= zr::ST_MAX_FRAME_SIDE && plan.H <= zr::ST_MAX_FRAME_SIDE;
+}
+
+int resolve_times(zr_ctx* c) {
+    if (c->pending.empty()) return ZR_OK;
+    bool fresh = false;
+    for (auto& p : c->pending) {
+        HIP_OK(hipEventSynchronize(p.b));
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, p.a, p.b));
+        if (p.kind == c->log_kind) c->log.push_back(ms);  // default: the dominant kernel's launches (render_* / stream_extend)
+        if (p.render_id == c->render_id) {
+            if (!fresh) { c->last_render_ms = 0; c->last_extend_ms = 0; c->last_shade_ms = 0; fresh = true; }
+            c->last_render_ms += ms;
+            if (p.kind == 1) c->last_extend_ms += ms;
+            if (p.kind == 2) c->last_shade_ms += ms;
+        }
+        c->pool.push_back(p.a); c->pool.push_back(p.b);
+    }
+    c->pending.clear();
+    if (c->log.size() > (1u << 20)) c->log.erase(c->log.begin(), c->log.begin() + (c->log.size() - (1u << 20)));
+    return ZR_OK;
+}
+
+// the plan's pixels in tile order, x | y << 16 (ST_MAX_FRAME_SIDE)
+std::vector<uint32_t> plan_pixels(const Plan& plan) {
+    std::vector<uint32_t> pix;
+    pix.reserve((size_t)plan.tiles.size() * plan.ts * plan.ts);
+    for (int32_t t : plan.tiles) {
+        const TileRect r = plan.clip(t);
+        for (int y = r.ya; y < r.yb; y++) for (int x = r.xa; x < r.xb; x++) pix.push_back((uint32_t)x | ((uint32_t)y << 16));
+    }
+    return pix;
+}
+
+// the one reader of the switch: upload_pixel_list, and in zr_accum.cpp whoever pairs a list position with a pixel (render_batch_samples, an adaptive run's first list)
+bool list_runs_reversed() { return env_double("ZR_STREAM_BOTTOM_UP", 1) != 0; }
+
+// Renders job.plan into job.d_out through the pipeline or, for a small world, the fused kernel.  The frame must fit the pipeline (fits_stream: both callers ask
+// first).  Synchronises the stream internally (the round loop needs the active-slot count), so zr_render_device returns with the frame complete.
+// mode 0: the render; 1 / 2: beauty pass and replay pass of the reflection / refraction split (zr_stream.hip, stream_shade)
+int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode) {
+    int rc = ZR_OK;
+    // the caller's own list leaves the cached one (zr_ctx::d_pixels, pix_key) alone: a later render of the plan gets the plan's list
+    if (!job.d_list && (rc = upload_pixel_list(c, job.plan))) return rc;
+    const uint32_t* pixels = job.d_list ? job.d_list : c->d_pixels.p;
+    uint32_t n_pix = job.d_list ? job.n_list : (uint32_t)c->d_pixels.n;
+    const uint32_t spp = (uint32_t)job.dc.spp;
+    if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
+    c->render_id++; c->last_stream = job.stream; c->last_counted = job.count; c->last_rounds = 0;
+    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
+    if (n_pix == 0) return ZR_OK;
+    uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
+    // per-sample radiance first: without it this pipeline cannot run at all (the caller falls back to the pixel-group kernel)
+    size_t samples_n = (size_t)units * 3;
+    if (c->d_partial.n < samples_n) {
+        HIP_OK(hipStreamSynchronize(job.stream));
+        if (c->d_partial.alloc(samples_n) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes)", samples_n * sizeof(double));
+    }
+    hipStream_t streams[ST_MAX_POOLS];
+    streams[0] = job.stream;
+    for (int k = 1; k < ST_MAX_POOLS; k++) streams[k] = c->sub[k];
+    const bool fused = mode == 0 && s->fused_ok && s->leaf_level <= 2 && s->leaf_objects > 0 && (double)s->leaf_objects <= env_double("ZR_FUSED_MAX", ZR_FUSED_OBJECTS) &&
+                       env_double("ZR_FUSED", 1) != 0;
+    // A frame that the pipeline reduces into d_out from the plan's own list first loses its sky pixels (sky_prepass): they never become work units.  Not the counting
+    // render (the instrument: every unit goes through the pipeline), not a batch of an accumulator (d_out == nullptr, its own list), not the split passes.
+    if (mode == 0 && !fused && job.d_out && !job.d_list && !job.count && s->ds.shade_escape && env_double("ZR_SKY_PREPASS", 1) != 0) {
+        uint32_t n_walk = n_pix;
+        if ((rc = sky_prepass(c, s, job, pixels, n_pix, &n_walk))) return rc;
+        c->presolved = n_pix - n_walk; c->presolved_render = c->render_id;
+        if (n_walk < n_pix) { pixels = c->d_walk_pixels.p; n_pix = n_walk; units = (uint64_t)n_pix * spp; samples_n = (size_t)units * 3; }
+        if (n_pix == 0) { c->last_path = 2; return ZR_OK; }   // (the stream is idle: sky_prepass synchronised it)
+    }
+    zr::StreamJob sj{};
+    sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, pixels, c->d_partial.p, job.d_out, job.d_out2, job.count, job.sample0};
+    sj.ctx = zr::StreamContext{c->d_ctl.p, nullptr, 0, c->st_blocks, c->d_ctr.p, streams, 1, c->st_event, c->h_active};
+    sj.hooks = zr::StreamHooks{nullptr, job.keep_going, job.progress, nullptr};
+    const bool polled = job.keep_going || job.progress;   // a cancelled frame / a preview reduces what exists: the samples start at zero
+    if (fused) {
+        if (polled) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), job.stream));
+        return render_fused(c, s, sj);
+    }
+    c->last_path = 2;
+    if ((rc = ensure_stack_slabs(c, s))) return rc;
+    sj.ctx.overflow = c->d_st_overflow.p; sj.ctx.ovf_levels = c->st_ovf_levels;
+    // Two sub-pools, a fraction of a round apart on two streams, let one pool's SHADE run beside the other's EXTEND.  Until round 3 that paid on a rank's share only
+    // (the whole frame: 366.6 against 365.7 ms): SHADE needed 124 registers and found no room beside EXTEND's waves.  The lean builds of both kernels use 80
+    // (zr_stream.hip), a SIMD holds three waves of each, and a whole cfg3 frame gains 3.5 % with 64 Mi slots, 5.4 % with 128 Mi (profiles/r4_experiments_ab.txt); the
+    // general builds (demo: 128 + 117 registers) do not fit beside each other and lose 2 %: one pool for those
+    const bool lean_pair = s->leaf_level == 0 && s->ds.shade_lean != 0 && mode == 0;
+    if ((rc = size_slot_pool(c, units, spp, lean_pair, job.stream, sj.pool))) return rc;
+    if (polled) HIP_OK(hipMemsetAsync(c->d_partial.p, 0, samples_n * sizeof(double), job.stream));
+    sj.split.mode = mode;
+    if (mode != 0 && (rc = split_buffers(c, units, mode, job.stream, sj.split))) return rc;
+    const bool sharded = job.plan.tiles.size() < (size_t)job.plan.tiles_x * job.plan.tiles_y;
+    sj.ctx.n_pools = c->st_pools > 0 ? c->st_pools : ((sharded || lean_pair) ? 2 : 1);
+    HostTimer timer(c);
+    int rounds = 0;
+    sj.hooks.timer = &timer; sj.hooks.done_out = &rounds;
+    hipError_t e = zr::stream_render(s->ds, sj, s->leaf_level);
+    if (e != hipSuccess) return fail(ZR_E_DEVICE, "streaming pipeline failed: %s", hipGetErrorString(e));
+    c->last_rounds = (uint64_t)(rounds < 0 ? -rounds : rounds);
+    HIP_OK(hipStreamSynchronize(job.stream));
+    if (rounds < 0) return fail(ZR_E_CANCELLED, "render cancelled after %d rounds", -rounds);
+    return ZR_OK;
+}
+
+}  // namespace zr_host
 
 extern "C" {
-
-zr_accum* zr_accum_create(zr_ctx* c, int width, int height, const zr_region* region) {
-    if (!c) { fail(ZR_E_INVALID, "null argument"); return nullptr; }
-    if (width < 1 || height < 1) { fail(ZR_E_INVALID, "accumulator size %d x %d not supported", width, height); return nullptr; }
-    if (hipSetDevice(c->device) != hipSuccess) { fail(ZR_E_DEVICE, "hipSetDevice(%d) failed", c->device); return nullptr; }
-    zr_camera shape{}; shape.image_width = width; shape.image_height = height;
-    std::unique_ptr<zr_accum> a(new zr_accum);
-    if (accum_init(a->st, c, shape, region)) return nullptr;
-    return a.release();
-}
-
-void zr_accum_destroy(zr_accum* a) {
-    if (!a) return;
-    (void)hipSetDevice(a->st.device);
-    delete a;
-}
-
-int zr_accum_reset(zr_accum* a, int first_sample) {
-    if (!a) return fail(ZR_E_INVALID, "null argument");
-    if (first_sample < 0) return fail(ZR_E_INVALID, "first sample %d below zero", first_sample);
-    AccumState& st = a->st;
-    HIP_OK(hipSetDevice(st.device));
-    HIP_OK(hipMemset(st.d_partial.p, 0, std::max<size_t>((size_t)st.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL * sizeof(double), 64)));
-    HIP_OK(hipDeviceSynchronize());   // the context's streams do not wait for the null stream
-    st.first = first_sample; st.done = 0; st.bound = false; st.adaptive = false;
-    return ZR_OK;
-}
-
-int zr_render_accumulate(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, zr_accum* a, int n_samples,
-                         int collect_counters, volatile const uint8_t* keep_going) {
-    if (!c || !s || !cam || !env || !a) return fail(ZR_E_INVALID, "null argument");
-    AccumState& st = a->st;
-    if (st.ctx != c) return fail(ZR_E_INVALID, "accumulator belongs to another context");
-    if (n_samples < 1) return fail(ZR_E_INVALID, "a batch has at least one sample (%d asked for)", n_samples);
-    int rc = scene_ready(c, s, "zr_render_accumulate");
-    if (rc) return rc;
-    const int W = cam->image_width < 1 ? 1 : cam->image_width, H = cam->image_height < 1 ? 1 : cam->image_height;
-    if (W != st.plan.W || H != st.plan.H) return fail(ZR_E_INVALID, "camera of %d x %d px, accumulator of %d x %d", W, H, st.plan.W, st.plan.H);
-    zr_camera key = *cam; key.samples_per_pixel = 0;   // ignored here
-    if (st.bound && (std::memcmp(&key, &st.cam, sizeof key) != 0 || seed != st.seed || s != st.scene))
-        return fail(ZR_E_INVALID, "camera, seed or scene differ from the first batch's: zr_accum_reset starts a new frame");
-    if ((long long)st.first + st.done + n_samples > 0x7FFFFFFFll) return fail(ZR_E_INVALID, "sample range beyond 2^31");
-    if (st.adaptive) return fail(ZR_E_STATE, "the accumulator holds an adaptive run's per-pixel counts: zr_accum_reset starts a new frame");
-    FrameJob job;
-    HIP_OK(hipSetDevice(c->device));
-    job.plan = st.plan;
-    make_camera(*cam, job.dc);
-    make_env(*env, job.de);
-    if ((rc = check_env(job.de, s))) return rc;
-    job.seed = seed; job.stream = c->stream; job.count = collect_counters != 0; job.keep_going = keep_going;
-    if ((rc = accumulate_batch(c, s, job, st, st.first + st.done, n_samples))) return rc;
-    st.done += n_samples;
-    if (!st.bound) { st.bound = true; st.cam = key; st.seed = seed; st.scene = s; }
-    return ZR_OK;
-}
-
-int zr_accum_resolve_device(zr_accum* a, void* d_out_rgb, void* hip_stream) {
-    if (!a || !d_out_rgb) return fail(ZR_E_INVALID, "null argument");
-    if (a->st.done == 0) return fail(ZR_E_STATE, "zr_render_accumulate must precede zr_accum_resolve");
-    HIP_OK(hipSetDevice(a->st.device));
-    int rc = accum_resolve_into(a->st, (double*)d_out_rgb, (hipStream_t)hip_stream);
-    if (rc) return rc;
-    HIP_OK(hipStreamSynchronize((hipStream_t)hip_stream));
-    return ZR_OK;
-}
-
-int zr_accum_resolve(zr_accum* a, double* out_rgb) {
-    if (!a || !out_rgb) return fail(ZR_E_INVALID, "null argument");
-    AccumState& st = a->st;
-    if (st.done == 0) return fail(ZR_E_STATE, "zr_render_accumulate must precede zr_accum_resolve");
-    HIP_OK(hipSetDevice(st.device));
-    DevBuf<double> d_frame;   // only the plan's pixels of it are written, and only they are copied out
-    int rc = d_frame.alloc(st.plan.npx() * 3);
-    if (rc) return rc;
-    if ((rc = accum_resolve_into(st, d_frame.p, nullptr))) return rc;
-    HIP_OK(hipStreamSynchronize(nullptr));
-    std::vector<double> staging;
-    return copy_region(st.plan, d_frame.p, out_rgb, staging);
-}
-
-int zr_accum_state(const zr_accum* a, int64_t out[4]) {
-    if (!a || !out) return fail(ZR_E_INVALID, "null argument");
-    out[0] = a->st.first; out[1] = a->st.done; out[2] = (int64_t)a->st.n_pix; out[3] = (int64_t)a->st.device_bytes();
-    return ZR_OK;
-}
-
-// ---- adaptive sampling ----------------------------------------------------------------------------------------------------------------------
-
-int zr_render_adaptive(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, zr_accum* a, const zr_adaptive_params* p,
-                       int collect_counters, volatile const uint8_t* keep_going, zr_adaptive_stats* out) {
-    if (out) std::memset(out, 0, sizeof *out);   // whatever happens below, `out` holds the statistics of the passes that completed
-    if (!p) return fail(ZR_E_INVALID, "null argument");
-    // the parameters first: they need no device and no other argument
-    const int counts[3] = {p->min_samples, p->max_samples, p->step_samples};
-    const char* names[3] = {"min_samples", "max_samples", "step_samples"};
-    for (int k = 0; k < 3; k++)
-        if (counts[k] < 64 || counts[k] % 64 != 0) return fail(ZR_E_INVALID, "%s = %d is not a positive multiple of 64", names[k], counts[k]);
-    if (p->max_samples < p->min_samples) return fail(ZR_E_INVALID, "max_samples %d below min_samples %d", p->max_samples, p->min_samples);
-    if (!(p->threshold >= 0) || !std::isfinite(p->threshold)) return fail(ZR_E_INVALID, "threshold %g is negative or not finite", p->threshold);
-    if (!(p->dark_floor >= 0) || !std::isfinite(p->dark_floor)) return fail(ZR_E_INVALID, "dark_floor %g is negative or not finite", p->dark_floor);
-    if (!c || !s || !cam || !env || !a) return fail(ZR_E_INVALID, "null argument");
-    AccumState& st = a->st;
-    if (st.ctx != c) return fail(ZR_E_INVALID, "accumulator belongs to another context");
-    int rc = scene_ready(c, s, "zr_render_adaptive");
-    if (rc) return rc;
-    const int W = cam->image_width < 1 ? 1 : cam->image_width, H = cam->image_height < 1 ? 1 : cam->image_height;
-    if (W != st.plan.W || H != st.plan.H) return fail(ZR_E_INVALID, "camera of %d x %d px, accumulator of %d x %d", W, H, st.plan.W, st.plan.H);
-    zr_camera key = *cam; key.samples_per_pixel = 0;   // ignored here
-    if (st.bound && (std::memcmp(&key, &st.cam, sizeof key) != 0 || seed != st.seed || s != st.scene))
-        return fail(ZR_E_INVALID, "camera, seed or scene differ from the first batch's: zr_accum_reset starts a new frame");
-    if ((long long)st.first + p->max_samples > 0x7FFFFFFFll) return fail(ZR_E_INVALID, "sample range beyond 2^31");
-    if (st.adaptive) return fail(ZR_E_STATE, "the accumulator holds an adaptive run's per-pixel counts: zr_accum_reset starts a new frame");
-    if (st.done % 64 != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, not a multiple of 64: the noise estimate is not defined", st.done);
-    if (st.done > p->min_samples) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, more than min_samples = %d", st.done, p->min_samples);
-    FrameJob job;
-    HIP_OK(hipSetDevice(c->device));
-    job.plan = st.plan;
-    make_camera(*cam, job.dc);
-    make_env(*env, job.de);
-    if ((rc = check_env(job.de, s))) return rc;
-    job.seed = seed; job.stream = c->stream; job.count = collect_counters != 0; job.keep_going = keep_going;
-    c->last_rounds = 0;
-    HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
-    if (st.n_pix == 0) return ZR_OK;
-    // the run's buffers, and the first list: every pixel, in the order the pipeline's own list has (upload_pixel_list: bottom-up shortens the drain)
-    const size_t n_blocks = ((size_t)st.n_pix + 255) / 256;
-    if ((rc = st.d_count.alloc(st.n_pix)) || (rc = st.d_flag.alloc(st.n_pix)) || (rc = st.d_block_active.alloc(n_blocks)) ||
-        (rc = st.d_block_at_max.alloc(n_blocks)) || (rc = st.d_totals.alloc(2)))
-        return rc;
-    for (int k = 0; k < 2; k++) if ((rc = st.d_list[k].alloc(st.n_pix)) || (rc = st.d_slot[k].alloc(st.n_pix))) return rc;
-    {
-        std::vector<uint32_t> pix = plan_pixels(st.plan), slot(pix.size());
-        for (size_t k = 0; k < slot.size(); k++) slot[k] = (uint32_t)k;
-        if (env_double("ZR_STREAM_BOTTOM_UP", 1) != 0) { std::reverse(pix.begin(), pix.end()); std::reverse(slot.begin(), slot.end()); }
-        HIP_OK(hipMemcpy(st.d_list[0].p, pix.data(), pix.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(st.d_slot[0].p, slot.data(), slot.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_OK(hipDeviceSynchronize());   // the context's streams do not wait for the null stream
-    }
-    // counts lie in {min + j * step}: the last of them at or below max_samples is where a pixel that is still noisy stops
-    const int last_count = p->min_samples + (p->max_samples - p->min_samples) / p->step_samples * p->step_samples;
-    zr_adaptive_stats stats{};
-    unsigned long long totals[zr::CTR_WORDS] = {0};
-    uint64_t rounds = 0;
-    const uint64_t id0 = c->render_id;
-    uint32_t n_active = st.n_pix;
-    int cur = 0, count_now = st.done, stop = ZR_OK;
-    std::string stop_msg;
-    while (n_active > 0) {
-        const int target = stats.passes == 0 ? p->min_samples : count_now + p->step_samples;
-        const int n = target - count_now;
-        if (keep_going && *keep_going == 0) { stop = ZR_E_CANCELLED; stop_msg = "adaptive render cancelled after " + std::to_string(stats.passes) + " passes"; break; }
-        HostTimer timer(c);
-        if (n > 0) {   // (0: the accumulator came with min_samples already; pass 0 is then the estimate alone)
-            job.d_list = st.d_list[cur].p; job.n_list = n_active;
-            HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
-            bool flipped = false;
-            rc = render_batch_samples(c, s, job, st.d_list[cur].p, n_active, st.first + count_now, n, timer, &flipped);
-            if (rc) {   // the pass is discarded whole; the accumulator is as the pass before left it
-                stop = rc; stop_msg = zr_host::last_error();
-                if (rc == ZR_E_NOMEM) stop_msg += " (adaptive pass " + std::to_string(stats.passes) + ": lower step_samples" + (stats.passes == 0 ? " / min_samples)" : ")");
-                break;
-            }
-        }
-        timer.begin(job.stream, 3);
-        HIP_OK(zr::launch_adaptive_accumulate(c->d_partial.p, st.d_slot[cur].p, n_active, (uint32_t)n, (uint32_t)(st.first + count_now), st.d_partial.p, st.d_count.p,
-                                              st.d_flag.p, target, last_count, p->threshold, p->dark_floor, job.stream));
-        HIP_OK(zr::launch_adaptive_compact(st.d_flag.p, n_active, st.d_list[cur].p, st.d_slot[cur].p, st.d_list[cur ^ 1].p, st.d_slot[cur ^ 1].p, st.d_block_active.p,
-                                           st.d_block_at_max.p, st.d_totals.p, job.stream));
-        timer.end(job.stream, 3);
-        if (timer.err != hipSuccess) return fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(timer.err));
-        uint32_t h_totals[2] = {0, 0};   // the read-back of a pass: how many pixels go on, how many max_samples stopped (a counting run also reads the counter block)
-        HIP_OK(hipMemcpyAsync(h_totals, st.d_totals.p, sizeof h_totals, hipMemcpyDeviceToHost, job.stream));
-        HIP_OK(hipStreamSynchronize(job.stream));
-        if (n > 0) {
-            st.route = c->last_path;
-            if (job.count) {
-                unsigned long long h[zr::CTR_WORDS];
-                HIP_OK(hipMemcpy(h, c->d_ctr.p, sizeof h, hipMemcpyDeviceToHost));
-                for (int w = 0; w < zr::CTR_WORDS; w++) totals[w] += h[w];
-            }
-            rounds += c->last_rounds;
-        }
-        st.adaptive = true; st.done = target; count_now = target;
-        if (!st.bound) { st.bound = true; st.cam = key; st.seed = seed; st.scene = s; }
-        stats.passes++; stats.samples += (uint64_t)n_active * (uint64_t)n; stats.stopped_at_max += h_totals[1];
-        stats.stopped_by_threshold += n_active - h_totals[0] - h_totals[1];
-        n_active = h_totals[0]; cur ^= 1;
-        if (out) *out = stats;
-    }
-    // one render as far as zr_get_counters is concerned: the totals over all passes, the launches of every pass in its times
-    for (auto& pe : c->pending) if (pe.render_id > id0) pe.render_id = c->render_id;
-    if (job.count) HIP_OK(hipMemcpyAsync(c->d_ctr.p, totals, sizeof totals, hipMemcpyHostToDevice, job.stream));
-    HIP_OK(hipStreamSynchronize(job.stream));
-    c->last_counted = job.count; c->last_rounds = rounds;
-    if (stop != ZR_OK) return fail(stop, "%s", stop_msg.c_str());
-    return ZR_OK;
-}
-
-int zr_accum_error(zr_accum* a, double dark_floor, double* out) {
-    if (!a || !out) return fail(ZR_E_INVALID, "null argument");
-    if (!(dark_floor >= 0) || !std::isfinite(dark_floor)) return fail(ZR_E_INVALID, "dark_floor %g is negative or not finite", dark_floor);
-    AccumState& st = a->st;
-    int rc = query_ready(st, "zr_accum_error");
-    if (rc) return rc;
-    if (!st.adaptive && st.done % 64 != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, not a multiple of 64: the noise estimate is not defined", st.done);
-    HIP_OK(hipSetDevice(st.device));
-    DevBuf<double> d_err;
-    if ((rc = d_err.alloc(st.n_pix))) return rc;
-    HIP_OK(zr::launch_accum_error(st.d_partial.p, st.adaptive ? st.d_count.p : nullptr, st.done, st.n_pix, dark_floor, d_err.p, nullptr));
-    HIP_OK(hipStreamSynchronize(nullptr));
-    std::vector<double> h(st.n_pix);
-    if (st.n_pix) HIP_OK(hipMemcpy(h.data(), d_err.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-    scatter_to_frame(st.plan, h, out);
-    return ZR_OK;
-}
-
-int zr_accum_sample_counts(zr_accum* a, int32_t* out) {
-    if (!a || !out) return fail(ZR_E_INVALID, "null argument");
-    AccumState& st = a->st;
-    int rc = query_ready(st, "zr_accum_sample_counts");
-    if (rc) return rc;
-    std::vector<int32_t> h(st.n_pix, (int32_t)st.done);
-    if (st.adaptive && st.n_pix) {
-        HIP_OK(hipSetDevice(st.device));
-        HIP_OK(hipMemcpy(h.data(), st.d_count.p, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    scatter_to_frame(st.plan, h, out);
-    return ZR_OK;
-}
-
-int64_t zr_accum_lane_sums(zr_accum* a, double* out, size_t cap_doubles) {
-    if (!a || (!out && cap_doubles != 0)) return fail(ZR_E_INVALID, "null argument");
-    AccumState& st = a->st;
-    int rc = query_ready(st, "zr_accum_lane_sums");
-    if (rc) return rc;
-    const size_t n = (size_t)st.n_pix * zr::ACCUM_DOUBLES_PER_PIXEL;
-    if (!out) return (int64_t)n;
-    if (cap_doubles < n) return fail(ZR_E_INVALID, "room for %zu doubles, the lane sums are %zu", cap_doubles, n);
-    HIP_OK(hipSetDevice(st.device));
-    if (n) HIP_OK(hipMemcpy(out, st.d_partial.p, n * sizeof(double), hipMemcpyDeviceToHost));
-    return (int64_t)n;
-}
 
 int zr_render_device(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region,
                      int collect_counters, void* d_out_rgb, void* hip_stream) {
@@ -991,14 +552,7 @@ int zr_render(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* 
     preview.rows = rows_done; preview.H = plan.H; preview.copy = copy_out; preview.period = env_double("ZR_PREVIEW_PERIOD_S", 0.2); preview.last = Preview::now();
     job.count = collect_counters != 0; job.d_out = c->d_out.p;
     job.keep_going = keep_going; job.rows_done = rows_done; job.progress = rows_done ? &preview : nullptr;
-    int rrc = enqueue_render(c, s, job);
-    if (rrc != ZR_OK && rrc != ZR_E_CANCELLED) return rrc;
-    std::string cancel_msg = zr_host::last_error();
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if ((rc = copy_out())) return rc;
-    if (rrc == ZR_E_CANCELLED) return fail(rrc, "%s", cancel_msg.c_str());
-    if (rows_done) *rows_done = plan.H;  // camera.hpp:576-578
-    return ZR_OK;
+    return deliver(c, enqueue_render(c, s, job), copy_out, rows_done, plan.H);
 }
 
 int zr_render_aov(zr_ctx* c, const zr_scene* s, const zr_camera* cam, uint64_t seed, const zr_region* region, const zr_aov_params* ap,
@@ -1073,199 +627,6 @@ int zr_render_passes(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const z
     return ZR_OK;
 }
 
-int zr_post_process(zr_ctx* c, const zr_post_params* pp, const double* frame, int W, int H, int is_data_pass, int apply_gamma, uint8_t* out) {
-    if (!c || !pp || !frame || !out) return fail(ZR_E_INVALID, "null argument");
-    if (W < 2 || H < 2 || (size_t)W * H > (1ull << 31)) return fail(ZR_E_INVALID, "frame size %d x %d not supported", W, H);
-    if (pp->use_bloom && (pp->bloom_radius < 0 || pp->bloom_radius > 4096)) return fail(ZR_E_INVALID, "bloom radius out of range");
-    HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)W * H;
-    DevBuf<double> d_frame, t0, t1, t2; DevBuf<uint8_t> d_out;
-    int rc;
-    if ((rc = d_frame.alloc(n * 3)) || (rc = d_out.alloc(n * 3))) return rc;
-    const bool bloom = !is_data_pass && pp->use_bloom, sharpen = !is_data_pass && pp->use_sharpening;
-    if (bloom && ((rc = t0.alloc(n * 3)) || (rc = t1.alloc(n * 3)))) return rc;
-    if (sharpen && (rc = t2.alloc(n * 3))) return rc;
-    HIP_OK(hipMemcpyAsync(d_frame.p, frame, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const double ev = std::pow(2.0, (double)pp->exposure);   // camera.hpp:711
-    HIP_OK(zr::launch_post(d_frame.p, W, H, *pp, is_data_pass, apply_gamma, ev, t0.p, t1.p, t2.p, d_out.p, c->stream));
-    HIP_OK(hipMemcpyAsync(out, d_out.p, n * 3, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return ZR_OK;
-}
-
-int zr_denoise(zr_ctx* c, const zr_denoise_params* dp, const double* color, const double* albedo, const double* normal, const double* zdepth,
-               int W, int H, double* out) {
-    if (!c || !dp || !color || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
-    if (W < 1 || H < 1 || (size_t)W * H > (1ull << 31)) return fail(ZR_E_INVALID, "frame size %d x %d not supported", W, H);
-    if (dp->iterations < 0 || dp->iterations > 8) return fail(ZR_E_INVALID, "denoise iterations %d outside 0..8", dp->iterations);
-    if (!(dp->sigma_color > 0.0f) || !(dp->sigma_normal > 0.0f) || !(dp->sigma_albedo > 0.0f) || dp->sigma_depth < 0.0f || std::isnan(dp->sigma_depth))
-        return fail(ZR_E_INVALID, "denoise sigmas must be positive (sigma_depth: >= 0, 0 = no depth guide)");
-    HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)W * H;
-    DevBuf<double> d_c, d_a, d_n, d_z; DevBuf<float4> col0, col1, g0, g1;
-    int rc;
-    if ((rc = d_c.alloc(n * 3)) || (rc = d_a.alloc(n * 3)) || (rc = d_n.alloc(n * 3)) || (zdepth && (rc = d_z.alloc(n * 3)))) return rc;
-    if ((rc = col0.alloc(n)) || (rc = col1.alloc(n)) || (rc = g0.alloc(n)) || (rc = g1.alloc(n))) return rc;
-    HIP_OK(hipMemcpyAsync(d_c.p, color, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(d_a.p, albedo, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(d_n.p, normal, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (zdepth) HIP_OK(hipMemcpyAsync(d_z.p, zdepth, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    // the colour frame has been packed before the unpack kernel overwrites it
-    HIP_OK(zr::launch_denoise(d_c.p, d_a.p, d_n.p, zdepth ? d_z.p : nullptr, W, H, *dp, col0.p, col1.p, g0.p, g1.p, d_c.p, c->stream));
-    HIP_OK(hipMemcpyAsync(out, d_c.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return ZR_OK;
-}
-
-// ---- variance-guided denoising ------------------------------------------------------------------------------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-// the checks of a zr_denoise_guided_params, which need no device
-int check_guided_params(const zr_denoise_guided_params* dp) {
-    if (dp->iterations < 0 || dp->iterations > 8) return fail(ZR_E_INVALID, "denoise iterations %d outside 0..8", dp->iterations);
-    auto positive = [](float v) { return v > 0.0f && std::isfinite(v); };
-    if (!positive(dp->sigma_variance) || !positive(dp->sigma_normal) || !positive(dp->sigma_albedo) || !(dp->sigma_depth >= 0.0f) || !std::isfinite(dp->sigma_depth))
-        return fail(ZR_E_INVALID, "denoise sigmas must be positive and finite (sigma_depth: >= 0, 0 = no depth guide)");
-    if (!positive(dp->epsilon)) return fail(ZR_E_INVALID, "denoise epsilon %g is not positive and finite", (double)dp->epsilon);
-    return ZR_OK;
-}
-
-// what the queries of the variance share (zr_accum_variance, zr_accum_denoise): zr_accum_error's state rules
-int variance_ready(const AccumState& st, const char* entry) {
-    int rc = query_ready(st, entry);
-    if (rc) return rc;
-    if (!st.adaptive && st.done % 64 != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, not a multiple of 64: the variance is not defined", st.done);
-    return ZR_OK;
-}
-
-int accum_variance_into(const AccumState& a, double* d_out, hipStream_t stream) {
-    HIP_OK(zr::launch_accum_variance(a.d_partial.p, a.d_pixels.p, a.adaptive ? a.d_count.p : nullptr, a.done, a.n_pix, a.plan.W, d_out, stream));
-    return ZR_OK;
-}
-
-// The guided filter on device frames of n = W * H pixels: d_c / d_v hold colour and variance and receive the results; the guides are uploaded from the host.
-int denoise_guided_device(zr_ctx* c, const zr_denoise_guided_params* dp, DevBuf<double>& d_c, DevBuf<double>& d_v, const double* albedo, const double* normal,
-                          const double* zdepth, int W, int H, double* out, double* out_variance) {
-    const size_t n = (size_t)W * H;
-    DevBuf<double> d_a, d_n, d_z; DevBuf<float4> col0, col1, var0, var1, g0, g1;
-    int rc;
-    if ((rc = d_a.alloc(n * 3)) || (rc = d_n.alloc(n * 3)) || (zdepth && (rc = d_z.alloc(n * 3)))) return rc;
-    if ((rc = col0.alloc(n)) || (rc = col1.alloc(n)) || (rc = var0.alloc(n)) || (rc = var1.alloc(n)) || (rc = g0.alloc(n)) || (rc = g1.alloc(n))) return rc;
-    HIP_OK(hipMemcpyAsync(d_a.p, albedo, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(d_n.p, normal, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (zdepth) HIP_OK(hipMemcpyAsync(d_z.p, zdepth, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    // colour and variance have been packed before the unpack kernels overwrite them
-    HIP_OK(zr::launch_denoise_guided(d_c.p, d_v.p, d_a.p, d_n.p, zdepth ? d_z.p : nullptr, W, H, *dp, col0.p, col1.p, var0.p, var1.p, g0.p, g1.p, d_c.p,
-                                     out_variance ? d_v.p : nullptr, c->stream));
-    HIP_OK(hipMemcpyAsync(out, d_c.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (out_variance) HIP_OK(hipMemcpyAsync(out_variance, d_v.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return ZR_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int zr_accum_variance(zr_accum* a, double* out_var) {
-    if (!a || !out_var) return fail(ZR_E_INVALID, "null argument");
-    AccumState& st = a->st;
-    int rc = variance_ready(st, "zr_accum_variance");
-    if (rc) return rc;
-    HIP_OK(hipSetDevice(st.device));
-    DevBuf<double> d_frame;   // only the plan's pixels of it are written, and only they are copied out
-    if ((rc = d_frame.alloc(st.plan.npx() * 3))) return rc;
-    if ((rc = accum_variance_into(st, d_frame.p, nullptr))) return rc;
-    HIP_OK(hipStreamSynchronize(nullptr));
-    std::vector<double> staging;
-    return copy_region(st.plan, d_frame.p, out_var, staging);
-}
-
-int zr_denoise_guided(zr_ctx* c, const zr_denoise_guided_params* dp, const double* color, const double* variance, const double* albedo, const double* normal,
-                      const double* zdepth, int W, int H, double* out, double* out_variance) {
-    if (!c || !dp || !color || !variance || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
-    if (W < 1 || H < 1 || (size_t)W * H > (1ull << 31)) return fail(ZR_E_INVALID, "frame size %d x %d not supported", W, H);
-    int rc = check_guided_params(dp);
-    if (rc) return rc;
-    HIP_OK(hipSetDevice(c->device));
-    const size_t n = (size_t)W * H;
-    DevBuf<double> d_c, d_v;
-    if ((rc = d_c.alloc(n * 3)) || (rc = d_v.alloc(n * 3))) return rc;
-    HIP_OK(hipMemcpyAsync(d_c.p, color, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(d_v.p, variance, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    return denoise_guided_device(c, dp, d_c, d_v, albedo, normal, zdepth, W, H, out, out_variance);
-}
-
-int zr_accum_denoise(zr_accum* a, const zr_denoise_guided_params* dp, const double* albedo, const double* normal, const double* zdepth, double* out,
-                     double* out_variance) {
-    if (!a || !dp || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
-    int rc = check_guided_params(dp);
-    if (rc) return rc;
-    AccumState& st = a->st;
-    if (!st.plan.whole()) return fail(ZR_E_INVALID, "zr_accum_denoise filters whole frames: the accumulator was made with a region");
-    if ((rc = variance_ready(st, "zr_accum_denoise"))) return rc;
-    zr_ctx* c = st.ctx;
-    HIP_OK(hipSetDevice(st.device));
-    DevBuf<double> d_c, d_v;
-    if ((rc = d_c.alloc(st.plan.npx() * 3)) || (rc = d_v.alloc(st.plan.npx() * 3))) return rc;
-    // a whole-frame plan: the two kernels write every pixel of the two frames
-    if ((rc = accum_resolve_into(st, d_c.p, c->stream)) || (rc = accum_variance_into(st, d_v.p, c->stream))) return rc;
-    return denoise_guided_device(c, dp, d_c, d_v, albedo, normal, zdepth, st.plan.W, st.plan.H, out, out_variance);
-}
-
-int zr_sharpen_frame(zr_ctx* c, const double* in, int W, int H, double amount, double* out) {
-    if (!c || !in || !out) return fail(ZR_E_INVALID, "null argument");
-    if (W < 1 || H < 1 || (size_t)W * H > (1ull << 31)) return fail(ZR_E_INVALID, "frame size %d x %d not supported", W, H);
-    const size_t n = (size_t)W * H;
-    if (!(amount > 0.0)) {   // color_processing.hpp:208-210: nothing to do
-        if (out != in) std::memmove(out, in, n * 3 * sizeof(double));
-        return ZR_OK;
-    }
-    HIP_OK(hipSetDevice(c->device));
-    DevBuf<double> d_in, d_out;
-    int rc;
-    if ((rc = d_in.alloc(n * 3)) || (rc = d_out.alloc(n * 3))) return rc;
-    HIP_OK(hipMemcpyAsync(d_in.p, in, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(zr::launch_sharpen(d_in.p, d_out.p, W, H, amount, c->stream));
-    HIP_OK(hipMemcpyAsync(out, d_out.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return ZR_OK;
-}
-
-int zr_analyze_frame(zr_ctx* c, const double* frame, size_t n, zr_image_stats* out) {
-    if (!c || !frame || !out) return fail(ZR_E_INVALID, "null argument");
-    if (n == 0 || n > (1ull << 31)) return fail(ZR_E_INVALID, "pixel count not supported");
-    HIP_OK(hipSetDevice(c->device));
-    const size_t blocks = (n + 255) / 256;
-    DevBuf<double> d_frame, d_log; DevBuf<float> d_max; DevBuf<int> d_hist;
-    int rc;
-    if ((rc = d_frame.alloc(n * 3)) || (rc = d_log.alloc(blocks)) || (rc = d_max.alloc(blocks)) || (rc = d_hist.alloc(256))) return rc;
-    HIP_OK(hipMemcpyAsync(d_frame.p, frame, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(zr::launch_analyze(d_frame.p, n, d_log.p, d_max.p, d_hist.p, c->stream));
-    std::vector<double> plog(blocks); std::vector<float> pmax(blocks);
-    HIP_OK(hipMemcpyAsync(plog.data(), d_log.p, blocks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(pmax.data(), d_max.p, blocks * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(out->histogram, d_hist.p, 256 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    double total = 0.0; float mx = 0.0f;
-    for (size_t b = 0; b < blocks; b++) { total += plog[b]; if (pmax[b] > mx) mx = pmax[b]; }
-    out->max_luminance = mx;
-    out->average_luminance = std::pow(2.0f, static_cast<float>(total / (double)n));   // color_processing.hpp:180
-    return ZR_OK;
-}
-
-namespace {
-int check_debug_params(const zr_bvh_debug_params* dp) {
-    if (!dp) return fail(ZR_E_INVALID, "null argument");
-    if (dp->level < -1) return fail(ZR_E_INVALID, "BVH debug level %d below -1", dp->level);
-    if (!(dp->thickness > 0.0f) || !std::isfinite(dp->thickness)) return fail(ZR_E_INVALID, "BVH debug thickness must be a positive finite number");
-    return ZR_OK;
-}
-}  // namespace
-
 int zr_render_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const zr_env* env, uint64_t seed, const zr_region* region,
                         const zr_bvh_debug_params* dp, double* out_rgb, volatile const uint8_t* keep_going, volatile int* rows_done) {
     if (!c || !s || !cam || !env || !out_rgb) return fail(ZR_E_INVALID, "null argument");
@@ -1290,30 +651,18 @@ int zr_render_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_camera* cam, cons
             const int rows = std::min(plan.H, (last_tile / plan.tiles_x + 1) * plan.ts);
             if (rows > *rows_done) *rows_done = last_batch ? plan.H : rows;
         });
-    if (rrc != ZR_OK && rrc != ZR_E_CANCELLED) return rrc;
-    std::string cancel_msg = zr_host::last_error();
-    HIP_OK(hipStreamSynchronize(c->stream));
     std::vector<double> staging;
-    if ((rc = copy_region(plan, c->d_out.p, out_rgb, staging))) return rc;
-    if (rrc == ZR_E_CANCELLED) return fail(rrc, "%s", cancel_msg.c_str());
-    if (rows_done) *rows_done = plan.H;
-    return ZR_OK;
+    return deliver(c, rrc, [&]() { return copy_region(plan, c->d_out.p, out_rgb, staging); }, rows_done, plan.H);
 }
 
 int zr_trace_bvh_debug(zr_ctx* c, const zr_scene* s, const zr_bvh_debug_params* dp, const double* rays6, size_t n, double tmin, uint64_t seed,
                        uint64_t pixel, uint32_t bounce, zr_bvh_debug_hit* out) {
     if (!c || !s || (n && (!rays6 || !out))) return fail(ZR_E_INVALID, "null argument");
     int rc = check_debug_params(dp);
-    if (rc) return rc;
-    if (int rc0 = scene_ready(c, s, "zr_trace_bvh_debug")) return rc0;
+    if (rc || (rc = scene_ready(c, s, "zr_trace_bvh_debug"))) return rc;
     if (n == 0) return ZR_OK;
-    HIP_OK(hipSetDevice(c->device));
-    DevBuf<double> d_rays; DevBuf<zr_bvh_debug_hit> d_out;
-    if ((rc = d_rays.upload(std::vector<double>(rays6, rays6 + n * 6))) || (rc = d_out.alloc(n))) return rc;
-    HIP_OK(zr::launch_trace_bvh_debug(s->ds, d_rays.p, n, tmin, seed, pixel, bounce, dp->level, dp->thickness, d_out.p, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipMemcpy(out, d_out.p, n * sizeof(zr_bvh_debug_hit), hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return run_on_device(c, rays6, n * 6, out, n, [&](const double* d_rays, zr_bvh_debug_hit* d_out) {
+        return zr::launch_trace_bvh_debug(s->ds, d_rays, n, tmin, seed, pixel, bounce, dp->level, dp->thickness, d_out, c->stream); });
 }
 
 int zr_trace_paths(zr_ctx* c, const zr_scene* s, const zr_camera* cam, uint64_t seed, const int32_t* requests, int n, int max_segments, double* out) {
@@ -1321,21 +670,12 @@ int zr_trace_paths(zr_ctx* c, const zr_scene* s, const zr_camera* cam, uint64_t 
     if (int rc0 = scene_ready(c, s, "zr_trace_paths", true)) return rc0;   // a scene of any context is accepted here, unlike everywhere else: kept as it has always been
     if (n <= 0 || max_segments <= 0) return ZR_OK;
     static_assert(ZR_PATH_RECORD == ZR_PATH_REC, "record size");
-    HIP_OK(hipSetDevice(c->device));
     zr::DCamera dc; make_camera(*cam, dc);
     for (int k = 0; k < n; k++)
         if (requests[3 * k] < 0 || requests[3 * k] >= dc.W || requests[3 * k + 1] < 0 || requests[3 * k + 1] >= dc.H || requests[3 * k + 2] < 0)
             return fail(ZR_E_INVALID, "path request %d outside the frame", k);
-    DevBuf<int32_t> d_req; DevBuf<double> d_out;
-    std::vector<int32_t> r(requests, requests + (size_t)n * 3);
-    int rc;
-    if ((rc = d_req.upload(r))) return rc;
-    const size_t words = (size_t)n * max_segments * ZR_PATH_RECORD;
-    if ((rc = d_out.alloc(words))) return rc;
-    HIP_OK(zr::launch_path_records(s->ds, dc, seed, d_req.p, n, max_segments, d_out.p, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipMemcpy(out, d_out.p, words * sizeof(double), hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return run_on_device(c, requests, (size_t)n * 3, out, (size_t)n * max_segments * ZR_PATH_RECORD, [&](const int32_t* d_req, double* d_out) {
+        return zr::launch_path_records(s->ds, dc, seed, d_req, n, max_segments, d_out, c->stream); });
 }
 
 int zr_get_counters(zr_ctx* c, zr_counters* out) {
@@ -1444,14 +784,7 @@ int zr_kat_texture(zr_ctx* c, const zr_scene* s, uint32_t texture_id, const doub
     if (int rc0 = scene_ready(c, s, "zr_kat_texture")) return rc0;
     if (texture_id >= s->textures.size()) return fail(ZR_E_INVALID, "texture id %u out of range", texture_id);
     if (n == 0) return ZR_OK;
-    HIP_OK(hipSetDevice(c->device));
-    DevBuf<double> d_in, d_out;
-    int rc;
-    if ((rc = d_in.upload(std::vector<double>(uvp5, uvp5 + n * 5))) || (rc = d_out.alloc(n * 3))) return rc;
-    HIP_OK(zr::launch_kat_texture(s->ds, texture_id, d_in.p, n, d_out.p, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipMemcpy(out_rgb, d_out.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return run_on_device(c, uvp5, n * 5, out_rgb, n * 3, [&](const double* d_in, double* d_out) { return zr::launch_kat_texture(s->ds, texture_id, d_in, n, d_out, c->stream); });
 }
 
 int zr_kat_background(zr_ctx* c, const zr_scene* s, const zr_env* env, const double* dirs3, size_t n, double* out_rgb) {
@@ -1460,14 +793,7 @@ int zr_kat_background(zr_ctx* c, const zr_scene* s, const zr_env* env, const dou
     zr::DEnv de; make_env(*env, de);
     if (int rc0 = check_env(de, s)) return rc0;
     if (n == 0) return ZR_OK;
-    HIP_OK(hipSetDevice(c->device));
-    DevBuf<double> d_in, d_out;
-    int rc;
-    if ((rc = d_in.upload(std::vector<double>(dirs3, dirs3 + n * 3))) || (rc = d_out.alloc(n * 3))) return rc;
-    HIP_OK(zr::launch_kat_background(s->ds, de, d_in.p, n, d_out.p, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipMemcpy(out_rgb, d_out.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return run_on_device(c, dirs3, n * 3, out_rgb, n * 3, [&](const double* d_in, double* d_out) { return zr::launch_kat_background(s->ds, de, d_in, n, d_out, c->stream); });
 }
 
 int zr_kat_camera_rays(zr_ctx* c, const zr_camera* cam, uint64_t seed, const int32_t* requests3, size_t n, double* out7) {
@@ -1477,14 +803,7 @@ int zr_kat_camera_rays(zr_ctx* c, const zr_camera* cam, uint64_t seed, const int
     for (size_t k = 0; k < n; k++)
         if (requests3[3 * k] < 0 || requests3[3 * k] >= dc.W || requests3[3 * k + 1] < 0 || requests3[3 * k + 1] >= dc.H || requests3[3 * k + 2] < 0)
             return fail(ZR_E_INVALID, "camera-ray request %zu outside the frame", k);
-    HIP_OK(hipSetDevice(c->device));
-    DevBuf<int32_t> d_req; DevBuf<double> d_out;
-    int rc;
-    if ((rc = d_req.upload(std::vector<int32_t>(requests3, requests3 + n * 3))) || (rc = d_out.alloc(n * 7))) return rc;
-    HIP_OK(zr::launch_kat_camera_rays(dc, seed, d_req.p, n, d_out.p, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipMemcpy(out7, d_out.p, n * 7 * sizeof(double), hipMemcpyDeviceToHost));
-    return ZR_OK;
+    return run_on_device(c, requests3, n * 3, out7, n * 7, [&](const int32_t* d_req, double* d_out) { return zr::launch_kat_camera_rays(dc, seed, d_req, n, d_out, c->stream); });
 }
 
 }  // extern "C"
