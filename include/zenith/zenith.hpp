@@ -204,9 +204,15 @@ struct noinit_allocator : std::allocator<T> {
 };
 template <class T> using nvec = std::vector<T, noinit_allocator<T>>;
 
+// a texture coordinate of a triangle's corner (u to the right, v = 0 the image's first row: texture::value's convention)
+struct texcoord { double u = 0, v = 0; };
+
 struct flat_scene {
     std::vector<double> spheres, cubes;
     nvec<double> tri_v, tri_n;
+    // per-vertex texture coordinates, 6 per triangle (u0 v0 u1 v1 u2 v2), or EMPTY: the array appears with the first triangle that brings coordinates
+    // (zeros for the triangles before it, and for every later one that brings none), so a world without any flattens to what it always did
+    nvec<double> tri_uv;
     std::vector<uint32_t> sphere_mat, cube_mat;
     nvec<uint32_t> tri_mat;
     std::vector<zr_medium> media;
@@ -220,7 +226,7 @@ struct flat_scene {
     // empties the scene but keeps the arrays' memory: a camera flattens its world on every render, and a quarter of a gigabyte of
     // freshly mapped pages costs more to touch than a million triangles cost to copy
     void clear() {
-        spheres.clear(); cubes.clear(); tri_v.clear(); tri_n.clear(); sphere_mat.clear(); cube_mat.clear(); tri_mat.clear(); media.clear(); ops.clear();
+        spheres.clear(); cubes.clear(); tri_v.clear(); tri_n.clear(); tri_uv.clear(); sphere_mat.clear(); cube_mat.clear(); tri_mat.clear(); media.clear(); ops.clear();
         objects.clear(); groups.clear(); materials.clear(); textures.clear(); texels.clear(); warnings.clear();
     }
     zr_scene_desc desc() const {
@@ -236,6 +242,19 @@ struct flat_scene {
         d.texels = texels.data(); d.texel_bytes = texels.size();
         d.groups = groups.data(); d.n_groups = groups.size();
         return d;
+    }
+    // tri_uv in step with the n triangles there are now (call only once the array exists, or to create it): new entries are zero
+    void sync_uv(size_t n) {
+        const size_t had = tri_uv.size();
+        tri_uv.resize(n * 6);
+        if (n * 6 > had) std::memset(tri_uv.data() + had, 0, (n * 6 - had) * sizeof(double));
+    }
+    // hands the scene to the C ABI: the arrays borrowed until the commit (zr_scene_set_all_borrowed), the texture coordinates, if any, copied
+    int give_to(zr_scene* sc) const {
+        const zr_scene_desc d = desc();
+        int rc = zr_scene_set_all_borrowed(sc, &d);
+        if (rc == ZR_OK && !tri_uv.empty()) rc = zr_scene_set_triangle_uvs(sc, tri_uv.data(), tri_mat.size());
+        return rc;
     }
 };
 
@@ -266,8 +285,12 @@ public:
         emit(ZR_PRIM_SPHERE, (uint32_t)fs.sphere_mat.size() - 1);
     }
     // (the hot call of a flatten: a million-triangle world comes through here once per render, on the caller's clock)
-    void emit_triangle(const point3 v[3], const vec3 n[3], const shared_ptr<material>& m) {
+    void emit_triangle(const point3 v[3], const vec3 n[3], const shared_ptr<material>& m, const texcoord* uv = nullptr) {
         const size_t i = fs.tri_mat.size();
+        if (uv || !fs.tri_uv.empty()) {
+            fs.sync_uv(i + 1);
+            if (uv) { double* t = fs.tri_uv.data() + i * 6; for (int k = 0; k < 3; k++) { t[2 * k] = uv[k].u; t[2 * k + 1] = uv[k].v; } }
+        }
         fs.tri_v.resize(i * 9 + 9); fs.tri_n.resize(i * 9 + 9);
         double* tv = fs.tri_v.data() + i * 9; double* tn = fs.tri_n.data() + i * 9;
         for (int k = 0; k < 3; k++) { tv[3 * k] = v[k].x(); tv[3 * k + 1] = v[k].y(); tv[3 * k + 2] = v[k].z(); tn[3 * k] = n[k].x(); tn[3 * k + 1] = n[k].y(); tn[3 * k + 2] = n[k].z(); }
@@ -290,6 +313,7 @@ public:
     }
     void end_bulk_triangles(size_t first_tri, size_t run, size_t n_obj, bool entries) {   // the run is `run` long: cut the arrays back; in a template, note it
         fs.tri_v.resize((first_tri + run) * 9); fs.tri_n.resize((first_tri + run) * 9); fs.tri_mat.resize(first_tri + run);
+        if (!fs.tri_uv.empty()) fs.sync_uv(first_tri + run);
         if (entries) { fs.objects.resize(n_obj); return; }
         tmpl& t = templates[caps.back().tmpl];
         if (!t.items.empty() && t.items.back().what == 0 && t.items.back().inner.empty() && t.items.back().index + t.items.back().count == first_tri) { t.items.back().count += (uint32_t)run; return; }
@@ -799,7 +823,11 @@ namespace zenith { template <class Get> size_t flatten_triangle_run(scene_builde
 class triangle : public hittable {
 public:
     triangle(const point3& a, const point3& b, const point3& c, const vec3& n0, const vec3& n1, const vec3& n2, shared_ptr<material> m)
-        : v{a, b, c}, n{n0, n1, n2}, mat(m) {}
+        : v{a, b, c}, n{n0, n1, n2}, mat(m) {}   // no texture coordinates: u = v = 0 on every hit, as the reference's triangle::hit leaves them
+    // with per-vertex texture coordinates: hits carry the interpolated (u, v) and a tangent frame, so image textures and bump maps work on meshes
+    triangle(const point3& a, const point3& b, const point3& c, const vec3& n0, const vec3& n1, const vec3& n2, const zenith::texcoord& t0,
+             const zenith::texcoord& t1, const zenith::texcoord& t2, shared_ptr<material> m)
+        : v{a, b, c}, n{n0, n1, n2}, mat(m), uv{t0, t1, t2}, has_uv(true) {}
     bool hit(const ray& r, interval ray_t, hit_record& rec, int = 0, bool = false) const override { return zenith::device_hit(*this, r, ray_t, rec); }
     aabb bounding_box() const override {  // triangle.hpp:84-101
         double lo[3], hi[3];
@@ -810,10 +838,11 @@ public:
         return aabb(point3(lo[0], lo[1], lo[2]), point3(hi[0], hi[1], hi[2]));
     }
     void set_material(shared_ptr<material> m) { mat = m; zr_device_cache_.reset(); }
-    void flatten(zenith::scene_builder& b) const override { b.emit_triangle(v, n, mat); }
+    void flatten(zenith::scene_builder& b) const override { b.emit_triangle(v, n, mat, has_uv ? uv : nullptr); }
 private:
     template <class Get> friend size_t zenith::flatten_triangle_run(zenith::scene_builder&, size_t, Get&&);
     point3 v[3]; vec3 n[3]; shared_ptr<material> mat;
+    zenith::texcoord uv[3]; bool has_uv = false;
 };
 
 // A world is flattened once per render, on the caller's clock (the reference rebuilds its world on every restart, main.cpp:1492-1500):
@@ -835,6 +864,7 @@ inline size_t flatten_triangle_run(scene_builder& b, size_t n, Get&& get) {
     const unsigned hw = std::thread::hardware_concurrency();
     const size_t T = std::max<size_t>(1, std::min<size_t>(std::min<unsigned>(16u, hw ? hw : 1u), n / 8192));
     std::vector<size_t> stop(T, n);
+    std::vector<char> saw_uv(T, 0);   // per thread: one of its triangles carries texture coordinates
     auto work = [&](size_t t, size_t a, size_t e) {
         for (size_t k = a; k < e; k++) {
             const hittable& h = get(k);
@@ -843,6 +873,7 @@ inline size_t flatten_triangle_run(scene_builder& b, size_t n, Get&& get) {
             double* tv = b.fs.tri_v.data() + (first_tri + k) * 9; double* tn = b.fs.tri_n.data() + (first_tri + k) * 9;
             for (int c = 0; c < 3; c++) { tv[3 * c] = tr.v[c].x(); tv[3 * c + 1] = tr.v[c].y(); tv[3 * c + 2] = tr.v[c].z(); tn[3 * c] = tr.n[c].x(); tn[3 * c + 1] = tr.n[c].y(); tn[3 * c + 2] = tr.n[c].z(); }
             mp[k] = tr.mat.get();
+            if (tr.has_uv) saw_uv[t] = 1;
             if (entries) { zr_object o{}; o.type = ZR_PRIM_TRIANGLE; o.index = (uint32_t)(first_tri + k); o.chain_first = cf; o.chain_count = cc; b.fs.objects[first_obj + k] = o; }
         }
     };
@@ -853,6 +884,25 @@ inline size_t flatten_triangle_run(scene_builder& b, size_t n, Get&& get) {
     size_t run = n;
     for (size_t t = 0; t < T; t++) if (stop[t] < n) { run = stop[t]; break; }   // (chunks are in order: the first one that stopped ends the run)
     b.end_bulk_triangles(first_tri, run, first_obj + run, entries);
+    {   // texture coordinates: a second pass, and only for a world that has any (the array appears with the first triangle that brings some)
+        bool any = !b.fs.tri_uv.empty();
+        for (size_t t = 0; t < T; t++) any = any || saw_uv[t];   // (a thread may have seen one beyond the run's end: then the array is merely created early, all zero)
+        if (any) {
+            b.fs.sync_uv(first_tri + run);
+            auto uvwork = [&](size_t a, size_t e) {
+                for (size_t k = a; k < e; k++) {
+                    const triangle& tr = static_cast<const triangle&>(get(k));
+                    if (!tr.has_uv) continue;
+                    double* q = b.fs.tri_uv.data() + (first_tri + k) * 6;
+                    for (int c = 0; c < 3; c++) { q[2 * c] = tr.uv[c].u; q[2 * c + 1] = tr.uv[c].v; }
+                }
+            };
+            std::vector<std::thread> th2;
+            for (size_t t = 1; t < T; t++) th2.emplace_back(uvwork, run * t / T, run * (t + 1) / T);
+            uvwork(0, run / T);
+            for (auto& x : th2) x.join();
+        }
+    }
     {   // pointers -> ids, in order; the triangle itself is visited again only when its material has not been seen just before
         const material* last = nullptr; uint32_t last_id = 0; bool have = false;
         for (size_t k = 0; k < run; k++) {
@@ -1053,11 +1103,15 @@ private:
 // Semantics kept: the bounding box is taken over ALL `v` lines; x/z are centred on it and y-min moves to 0
 // (model.hpp:23-42); vertex = (v - offset) * scale in double (model.hpp:47-53); a face uses its vn normals when
 // its first corner has one, otherwise one flat normal unit(cross(v1-v0, v2-v0)) (model.hpp:70-85).
+// use_texcoords (off by default: the reference's triangles carry no coordinates, and the worlds that are compared with it are built without): the
+// `vt` index of `f v/vt` and `f v/vt/vn` corners is resolved like the others, negative ones from the end of the `vt` lines read so far, and a
+// corner's coordinate is (vt.u, 1 - vt.v) from the floats as parsed — OBJ's v = 0 is the bottom of the image, texture::value's the first row.  A
+// face with a corner that has no valid `vt` gets zeros; the corners of quads and fans keep their own coordinates through the split.
 class model : public hittable {
 public:
-    model(const std::string& filename, shared_ptr<material> mat, double scale = 1.0) : mat(mat) {
-        std::vector<float> V, N;
-        struct corner { int v, n; };
+    model(const std::string& filename, shared_ptr<material> mat, double scale = 1.0, bool use_texcoords = false) : mat(mat) {
+        std::vector<float> V, N, VT;
+        struct corner { int v, n, t; };
         std::vector<std::vector<corner>> faces;
         std::ifstream f(filename);
         if (!f) { std::cerr << "Cannot load the model: " << filename << std::endl; return; }
@@ -1071,6 +1125,9 @@ public:
             } else if (p[0] == 'v' && p[1] == 'n' && (p[2] == ' ' || p[2] == '\t')) {
                 char* e; p += 3;
                 for (int k = 0; k < 3; k++) { N.push_back((float)std::strtod(p, &e)); p = e; }
+            } else if (use_texcoords && p[0] == 'v' && p[1] == 't' && (p[2] == ' ' || p[2] == '\t')) {
+                char* e; p += 3;
+                for (int k = 0; k < 2; k++) { VT.push_back((float)std::strtod(p, &e)); p = e; }
             } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
                 p += 2;
                 std::vector<corner> fc;
@@ -1078,17 +1135,18 @@ public:
                     while (*p == ' ' || *p == '\t') p++;
                     if (*p == 0 || *p == '\r' || *p == '\n' || *p == '#') break;
                     char* e;
-                    long vi = std::strtol(p, &e, 10), ni = 0; bool has_n = false;
+                    long vi = std::strtol(p, &e, 10), ni = 0, ti = 0; bool has_n = false, has_t = false;
                     if (e == p) break;
                     p = e;
                     if (*p == '/') {
                         p++;
-                        if (*p != '/') { (void)std::strtol(p, &e, 10); p = e; }   // vt
+                        if (*p != '/') { ti = std::strtol(p, &e, 10); has_t = e != p; p = e; }   // vt
                         if (*p == '/') { p++; ni = std::strtol(p, &e, 10); has_n = e != p; p = e; }
                     }
                     corner c;
                     c.v = vi > 0 ? (int)vi - 1 : (int)(V.size() / 3) + (int)vi;
                     c.n = !has_n ? -1 : (ni > 0 ? (int)ni - 1 : (int)(N.size() / 3) + (int)ni);
+                    c.t = !has_t || ti == 0 ? -1 : (ti > 0 ? (int)ti - 1 : (int)(VT.size() / 2) + (int)ti);
                     fc.push_back(c);
                 }
                 if (fc.size() >= 3) faces.push_back(fc);
@@ -1107,6 +1165,13 @@ public:
             vec3 n0, n1, n2;
             if (a.n >= 0 && b.n >= 0 && c.n >= 0 && (size_t)(3 * std::max(a.n, std::max(b.n, c.n)) + 2) < N.size()) { n0 = norm(a.n); n1 = norm(b.n); n2 = norm(c.n); }
             else n0 = n1 = n2 = unit_vector(cross(v1 - v0, v2 - v0));
+            if (use_texcoords) {
+                auto has = [&](const corner& q) { return q.t >= 0 && (size_t)(2 * q.t + 1) < VT.size(); };
+                auto tc = [&](const corner& q) { return zenith::texcoord{(double)VT[2 * q.t], 1.0 - (double)VT[2 * q.t + 1]}; };
+                const bool all = has(a) && has(b) && has(c);
+                const zenith::texcoord zero{};
+                tris.push_back(make_shared<triangle>(v0, v1, v2, n0, n1, n2, all ? tc(a) : zero, all ? tc(b) : zero, all ? tc(c) : zero, mat));
+            } else
             tris.push_back(make_shared<triangle>(v0, v1, v2, n0, n1, n2, mat));
             bbox = aabb(bbox, tris.back()->bounding_box());
         };
@@ -1328,8 +1393,7 @@ inline shared_ptr<device_object> device_commit(shared_ptr<device_object>& cache,
     d->mats = b.mat_ptrs;
     for (const auto& w : d->fs.warnings) std::cerr << "[zenith] " << w << "\n";
     d->sc = zr_scene_create(ctx);
-    zr_scene_desc desc = d->fs.desc();
-    if (!d->sc || zr_scene_set_all_borrowed(d->sc, &desc) != ZR_OK || zr_scene_commit(d->sc) != ZR_OK)
+    if (!d->sc || d->fs.give_to(d->sc) != ZR_OK || zr_scene_commit(d->sc) != ZR_OK)
         throw std::runtime_error(std::string(what) + ": " + zr_last_error());
     cache = d;
     return d;
@@ -1498,8 +1562,7 @@ public:
         zr_ctx* ctx = lease;
         if (!ctx) { std::cerr << "[zenith] render failed: " << zr_last_error() << "\n"; return; }
         zr_scene* sc = zr_scene_create(ctx);
-        zr_scene_desc d = fs.desc();
-        rc = sc ? zr_scene_set_all_borrowed(sc, &d) : ZR_E_DEVICE;
+        rc = sc ? fs.give_to(sc) : ZR_E_DEVICE;
         if (rc == ZR_OK) rc = zr_scene_commit(sc);
         ph("commit");
         if (rc == ZR_OK) {

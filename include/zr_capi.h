@@ -241,6 +241,12 @@ void zr_scene_destroy(zr_scene*);
 int zr_scene_set_spheres(zr_scene*, const double* cxyz_r, const uint32_t* mat, size_t n);
 /* triangle(a,b,c,n0,n1,n2,mat): 9 doubles of vertices, 9 doubles of vertex normals */
 int zr_scene_set_triangles(zr_scene*, const double* v9, const double* n9, const uint32_t* mat, size_t n);
+/* per-vertex texture coordinates of the triangles given by zr_scene_set_triangles / _set_all / _set_all_borrowed:
+ * 6 doubles per triangle = u0, v0, u1, v1, u2, v2 (vertex order of v9).  The array is copied.  n must equal the current triangle count and every
+ * value must be finite (ZR_E_INVALID otherwise, nothing changed); uv6 == NULL with n == 0 removes the coordinates, and so does every later call that
+ * replaces the triangles.  A hit on a triangle then carries the interpolated (u, v) and a world-space tangent frame; without
+ * coordinates u = v = 0 and the frame is zero, as the reference's triangle::hit leaves them. */
+int zr_scene_set_triangle_uvs(zr_scene*, const double* uv6, size_t n);
 /* cube: 12 doubles = half_extents, center, min_p, max_p exactly as the cube members (cube.hpp:92-97) */
 int zr_scene_set_cubes(zr_scene*, const double* hcmm12, const uint32_t* mat, size_t n);
 int zr_scene_set_media(zr_scene*, const zr_medium*, size_t n);

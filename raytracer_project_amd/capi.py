@@ -234,7 +234,7 @@ _scenes = None
 # every symbol include/zr_capi.h declares (tests check that the library exports all of them)
 CAPI_SYMBOLS = [
     "zr_abi_version", "zr_last_error", "zr_create", "zr_destroy", "zr_scene_create", "zr_scene_destroy",
-    "zr_scene_set_spheres", "zr_scene_set_triangles", "zr_scene_set_cubes", "zr_scene_set_media",
+    "zr_scene_set_spheres", "zr_scene_set_triangles", "zr_scene_set_triangle_uvs", "zr_scene_set_cubes", "zr_scene_set_media",
     "zr_scene_set_xform_ops", "zr_scene_set_objects", "zr_scene_set_groups", "zr_scene_set_materials", "zr_scene_set_textures",
     "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_kernels", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device",
     "zr_accum_create", "zr_accum_destroy", "zr_accum_reset", "zr_render_accumulate", "zr_accum_resolve", "zr_accum_resolve_device", "zr_accum_state",
@@ -266,6 +266,8 @@ def load():
     lib.zr_scene_set_all_borrowed.argtypes = [vp, C.POINTER(SceneDesc)]
     lib.zr_scene_set_spheres.argtypes = [vp, vp, vp, C.c_size_t]
     lib.zr_scene_set_triangles.argtypes = [vp, vp, vp, vp, C.c_size_t]
+    if hasattr(lib, "zr_scene_set_triangle_uvs"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
+        lib.zr_scene_set_triangle_uvs.argtypes = [vp, vp, C.c_size_t]
     lib.zr_scene_set_cubes.argtypes = [vp, vp, vp, C.c_size_t]
     lib.zr_scene_set_media.argtypes = [vp, vp, C.c_size_t]
     lib.zr_scene_set_xform_ops.argtypes = [vp, vp, C.c_size_t]
@@ -718,7 +720,9 @@ class Accumulator:
 
 
 class Scene:
-    def __init__(self, ctx, desc):
+    def __init__(self, ctx, desc, tri_uv=None):
+        """tri_uv: per-vertex texture coordinates of the description's triangles, (n_tris, 3, 2) or (n_tris, 6) float64 = u0 v0 u1 v1 u2 v2 per
+        triangle (zr_scene_set_triangle_uvs); None: the triangles carry none (u = v = 0 on every triangle hit)"""
         self.ctx = ctx
         self.lib = ctx.lib
         self._s = self.lib.zr_scene_create(ctx._c)
@@ -726,6 +730,11 @@ class Scene:
             raise ZrError(self.lib.zr_last_error().decode())
         # the description's arrays outlive this call (the caller holds them): no need for the library to copy 200 MB of triangles
         _check(self.lib.zr_scene_set_all_borrowed(self._s, C.byref(desc)))
+        if tri_uv is not None:
+            uv = np.ascontiguousarray(tri_uv, dtype=np.float64)
+            if uv.ndim not in (2, 3) or uv.size != uv.shape[0] * 6:
+                raise ValueError(f"tri_uv must be (n_tris, 3, 2) or (n_tris, 6), not {uv.shape}")
+            _check(self.lib.zr_scene_set_triangle_uvs(self._s, uv.ctypes.data, uv.shape[0]))   # (the library copies it)
         _check(self.lib.zr_scene_commit(self._s))
 
     def stats(self):

@@ -19,6 +19,7 @@ namespace zr {
 struct BuildSceneIn {
     const double* spheres = nullptr; const uint32_t* sphere_mat = nullptr;
     const double* tri_v = nullptr; const double* tri_n = nullptr; const uint32_t* tri_mat = nullptr;
+    const double* tri_uv = nullptr;      // 6 per triangle, or null
     const double* cubes = nullptr; const uint32_t* cube_mat = nullptr;
     const zr_medium* media = nullptr; const zr_xform_op* ops = nullptr;
     const double* group_box = nullptr;   // per zr_group: lo[3], hi[3] of its triangles in their own space
@@ -39,6 +40,7 @@ struct BuildParams {   // no defaults here: zr_commit.cpp fills every field from
 struct BuildPrimOut {
     double* spheres = nullptr; uint32_t* sphere_mat = nullptr;
     double* tri_v = nullptr; double* tri_s = nullptr;
+    double* tri_uv = nullptr;            // null when the scene has no texture coordinates
     double* cubes = nullptr; uint32_t* cube_mat = nullptr;
     double* pcubes = nullptr; uint32_t* pcube_mat = nullptr;
     DInstance* insts = nullptr; uint32_t* inst_group = nullptr;

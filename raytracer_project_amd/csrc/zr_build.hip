@@ -690,6 +690,11 @@ __device__ void put_triangle_raw(const BuildPrimOut& out, size_t di, const doubl
     t[18] = __longlong_as_double((long long)(unsigned long long)mat);
     t[19] = __longlong_as_double(force_front ? 1ll : 0ll);
 }
+// a stored triangle's texture coordinates travel with it, unchanged (Flattener::put_triangle_uv)
+__device__ void put_triangle_uv(const BuildSceneIn& in, const BuildPrimOut& out, size_t di, uint32_t idx) {
+    if (!out.tri_uv) return;
+    for (int k = 0; k < 6; k++) out.tri_uv[di * 6 + k] = in.tri_uv[(size_t)idx * 6 + k];
+}
 __global__ __launch_bounds__(256) void k_emit(BuildSceneIn in, const zr_object* __restrict__ objs, const uint8_t* __restrict__ code, uint32_t first_triangle, uint32_t n,
                                               const uint32_t* __restrict__ dfs_obj, const uint8_t* __restrict__ dfs_kind, const uint32_t* __restrict__ rank, BuildPrimOut out,
                                               uint32_t* __restrict__ compound, uint32_t* __restrict__ n_compound) {
@@ -736,6 +741,7 @@ __global__ __launch_bounds__(256) void k_emit(BuildSceneIn in, const zr_object* 
             if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
         }
         put_triangle_raw(out, di, v, nn, mat, force_front);
+        put_triangle_uv(in, out, di, o.index);
     } else if (bk == 3) {   // put_baked_sphere: uniform scale / translate / material_instance
         const double* q = in.spheres + (size_t)o.index * 4;
         double c[3] = {q[0], q[1], q[2]}, r = fmax(0.0, q[3]);
@@ -774,6 +780,7 @@ __global__ __launch_bounds__(256) void k_emit(BuildSceneIn in, const zr_object* 
             double v[9], nn[9];
             for (int k = 0; k < 9; k++) { v[k] = in.tri_v[(size_t)o.index * 9 + k]; nn[k] = in.tri_n[(size_t)o.index * 9 + k]; }
             put_triangle_raw(out, di, v, nn, in.tri_mat[o.index], false);
+            put_triangle_uv(in, out, di, o.index);
         } else {
             const double* q = in.cubes + (size_t)o.index * 12;
             for (int k = 0; k < 6; k++) out.cubes[di * 6 + k] = q[k];

@@ -5,15 +5,17 @@
 
 namespace {
 
-// The scene's primitive arrays, one by one: f(device array, the flattener's staging array, leaf kind, elements per record); stops at the first failure.
+// The scene's primitive arrays, one by one: f(device array, the flattener's staging array, leaf kind, elements per record, elements per record of the array's
+// tail — tri_s alone has one: the triangles' texture coordinates behind its last record, when the scene has any); stops at the first failure.
 template <class F>
 int each_prim_array(zr_scene* s, Flattener& fl, F&& f) {
     int rc;
-    if ((rc = f(s->d_spheres, fl.spheres, ZR_PRIM_SPHERE, ZR_SPHERE_DOUBLES)) || (rc = f(s->d_sphere_mat, fl.sphere_mat, ZR_PRIM_SPHERE, 1)) ||
-        (rc = f(s->d_tri_v, fl.tri_v, ZR_PRIM_TRIANGLE, ZR_TRI_STRIDE)) || (rc = f(s->d_tri_s, fl.tri_s, ZR_PRIM_TRIANGLE, ZR_TRI_SHADE_DOUBLES)) ||
-        (rc = f(s->d_cubes, fl.cubes, ZR_PRIM_CUBE, ZR_CUBE_DOUBLES)) || (rc = f(s->d_cube_mat, fl.cube_mat, ZR_PRIM_CUBE, 1)) ||
-        (rc = f(s->d_pcubes, fl.pcubes, ZR_KIND_PCUBE, ZR_PCUBE_STRIDE)) || (rc = f(s->d_pcube_mat, fl.pcube_mat, ZR_KIND_PCUBE, 1)) ||
-        (rc = f(s->d_media, fl.media, ZR_PRIM_MEDIUM, 1)) || (rc = f(s->d_wrapped, fl.wrapped, ZR_KIND_WRAPPED, 1))) return rc;
+    const size_t uv = s->tri_uv.empty() ? 0 : 6;
+    if ((rc = f(s->d_spheres, fl.spheres, ZR_PRIM_SPHERE, ZR_SPHERE_DOUBLES, 0)) || (rc = f(s->d_sphere_mat, fl.sphere_mat, ZR_PRIM_SPHERE, 1, 0)) ||
+        (rc = f(s->d_tri_v, fl.tri_v, ZR_PRIM_TRIANGLE, ZR_TRI_STRIDE, 0)) || (rc = f(s->d_tri_s, fl.tri_s, ZR_PRIM_TRIANGLE, ZR_TRI_SHADE_DOUBLES, uv)) ||
+        (rc = f(s->d_cubes, fl.cubes, ZR_PRIM_CUBE, ZR_CUBE_DOUBLES, 0)) || (rc = f(s->d_cube_mat, fl.cube_mat, ZR_PRIM_CUBE, 1, 0)) ||
+        (rc = f(s->d_pcubes, fl.pcubes, ZR_KIND_PCUBE, ZR_PCUBE_STRIDE, 0)) || (rc = f(s->d_pcube_mat, fl.pcube_mat, ZR_KIND_PCUBE, 1, 0)) ||
+        (rc = f(s->d_media, fl.media, ZR_PRIM_MEDIUM, 1, 0)) || (rc = f(s->d_wrapped, fl.wrapped, ZR_KIND_WRAPPED, 1, 0))) return rc;
     return ZR_OK;
 }
 
@@ -32,7 +34,7 @@ int commit_host(zr_scene* s, std::shared_ptr<const CommitPlan> plan, PhaseTimer&
     const int device = s->ctx ? s->ctx->device : 0;
     fl.after_primitives = [&]() {
         uploader = std::thread([&, device]() {
-            auto go = [&]() -> int { HIP_OK(hipSetDevice(device)); return each_prim_array(s, fl, [](auto& d, auto& a, uint32_t, size_t) { return d.upload(a); }); };
+            auto go = [&]() -> int { HIP_OK(hipSetDevice(device)); return each_prim_array(s, fl, [](auto& d, auto& a, uint32_t, size_t, size_t) { return d.upload(a); }); };
             up_rc = go();
             if (up_rc != ZR_OK) up_err = zr_host::last_error();   // the error text is per thread
         });
@@ -68,7 +70,7 @@ enum class DeviceBuild { Done, UseHost, Failed };
 
 struct DeviceTemps {   // the builder (its scratch arena, the trees' local records), the as-given copies, the groups' tables: freed off the caller's clock
     std::unique_ptr<zr::DeviceBuilder> builder;
-    DevBuf<double> sph, tri_v, tri_n, cubes, gbox;
+    DevBuf<double> sph, tri_v, tri_n, tri_uv, cubes, gbox;
     DevBuf<uint32_t> sph_mat, tri_mat, cube_mat, inst_group, run_demand, run_root, run_qroot;
     DevBuf<zr_medium> media; DevBuf<zr_object> objs; DevBuf<uint8_t> code;
 };
@@ -115,17 +117,19 @@ int commit_device(zr_scene* s, const CommitPlan& plan, const PhaseTimer& outer, 
         return ZR_OK;
     };
     if ((rc = send(t.tri_v, s->tri_v.data(), s->tri_v.size())) || (rc = send(t.tri_n, s->tri_n.data(), s->tri_n.size())) ||
+        (!s->tri_uv.empty() && (rc = send(t.tri_uv, s->tri_uv.data(), s->tri_uv.size()))) ||
         (rc = send(t.objs, objs.data(), objs.size())) || (rc = send(t.tri_mat, s->tri_mat.data(), s->tri_mat.size())) ||
         (rc = send(t.sph, s->spheres.data(), s->spheres.size())) || (rc = send(t.sph_mat, s->sphere_mat.data(), s->sphere_mat.size())) ||
         (rc = send(t.cubes, s->cubes.data(), s->cubes.size())) || (rc = send(t.cube_mat, s->cube_mat.data(), s->cube_mat.size())) ||
         (rc = send(t.media, s->media.data(), s->media.size())) || (rc = s->d_ops.upload(s->ops.data(), s->ops.size())) || (rc = send(t.code, plan.code.data(), plan.code.size()))) return rc;
     static const zr::BuildResult no_tree;
     Flattener fl{*s, objs, no_tree};   // the compound objects' staging (step 5), filled by the flattener's own routines
-    if ((rc = each_prim_array(s, fl, [&](auto& d, auto&, uint32_t kind, size_t per) { return room(d.alloc(z[kind] * per)); })) ||
+    if ((rc = each_prim_array(s, fl, [&](auto& d, auto&, uint32_t kind, size_t per, size_t tail) { return room(d.alloc(z[kind] * (per + tail))); })) ||
         (rc = room(s->d_insts.alloc(z[ZR_KIND_INSTANCE]))) || (rc = room(t.inst_group.alloc(z[ZR_KIND_INSTANCE])))) return rc;
     ph("upload as given");
     zr::BuildSceneIn in;
     in.spheres = t.sph.p; in.sphere_mat = t.sph_mat.p; in.tri_v = t.tri_v.p; in.tri_n = t.tri_n.p; in.tri_mat = t.tri_mat.p;
+    if (!s->tri_uv.empty()) in.tri_uv = t.tri_uv.p;
     in.cubes = t.cubes.p; in.cube_mat = t.cube_mat.p; in.media = t.media.p; in.ops = s->d_ops.p;   // (d_ops: the scene's own, uploaded above, alive beyond the build)
     const BuildKnobs& kn = plan.kn;
     zr::BuildParams bp;
@@ -151,6 +155,7 @@ int commit_device(zr_scene* s, const CommitPlan& plan, const PhaseTimer& outer, 
     zr::BuildPrimOut out;
     for (int k = 0; k < 7; k++) out.src[k] = d_src[k].p;
     out.spheres = s->d_spheres.p; out.sphere_mat = s->d_sphere_mat.p; out.tri_v = s->d_tri_v.p; out.tri_s = s->d_tri_s.p;
+    if (!s->tri_uv.empty() && z[ZR_PRIM_TRIANGLE]) out.tri_uv = s->d_tri_s.p + z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES;   // behind the last shading record
     out.cubes = s->d_cubes.p; out.cube_mat = s->d_cube_mat.p; out.pcubes = s->d_pcubes.p; out.pcube_mat = s->d_pcube_mat.p;
     out.insts = s->d_insts.p; out.inst_group = t.inst_group.p;
     t.builder.reset(new zr::DeviceBuilder(st));
@@ -237,9 +242,12 @@ int commit_device(zr_scene* s, const CommitPlan& plan, const PhaseTimer& outer, 
         std::sort(todo.begin(), todo.end(), [](const Flattener::Compound& a, const Flattener::Compound& b) { return a.kind != b.kind ? a.kind < b.kind : a.di < b.di; });
         fl.finish_compounds(todo);
         if (!fl.filled(plan)) return fail(ZR_E_DEVICE, "device BVH build: compound objects do not add up (internal error)");
-        rc = each_prim_array(s, fl, [&](auto& d, auto& a, uint32_t kind, size_t per) -> int {
-            const size_t from = (kind == ZR_PRIM_MEDIUM || kind == ZR_KIND_WRAPPED ? 0 : z[kind] - plan.inner[kind]) * per, to = z[kind] * per;
+        rc = each_prim_array(s, fl, [&](auto& d, auto& a, uint32_t kind, size_t per, size_t tail) -> int {
+            const size_t first = kind == ZR_PRIM_MEDIUM || kind == ZR_KIND_WRAPPED ? 0 : z[kind] - plan.inner[kind];
+            const size_t from = first * per, to = z[kind] * per;
             if (to > from) HIP_OK(hipMemcpyAsync(d.p + from, &a[from], (to - from) * sizeof(a[0]), hipMemcpyHostToDevice, st));
+            const size_t tfrom = to + first * tail, tto = to + z[kind] * tail;   // the same records' share of the tail
+            if (tto > tfrom) HIP_OK(hipMemcpyAsync(d.p + tfrom, &a[tfrom], (tto - tfrom) * sizeof(a[0]), hipMemcpyHostToDevice, st));
             return ZR_OK;
         });
         if (rc) return rc;
@@ -293,6 +301,9 @@ int finish_commit(zr_scene* s, const CommitPlan& plan, const CommitSummary& cs) 
     d.nodes = s->d_nodes.p; d.quads = s->d_quads.p;
     d.spheres = s->d_spheres.p; d.sphere_mat = s->d_sphere_mat.p;
     d.tri_v = s->d_tri_v.p; d.tri_s = s->d_tri_s.p;
+    if (!s->tri_uv.empty() && z[ZR_PRIM_TRIANGLE] * (ZR_TRI_SHADE_DOUBLES / 4) > 0xFFFFFFFFull) return fail(ZR_E_INVALID, "too many triangles for texture coordinates (%zu stored)", z[ZR_PRIM_TRIANGLE]);
+    // (the kernels' builds that read texture coordinates are launched when this is not zero; ZR_TRI_SHADE_DOUBLES / 4 units a record)
+    d.tri_uv_at = s->tri_uv.empty() ? 0u : (uint32_t)(z[ZR_PRIM_TRIANGLE] * (ZR_TRI_SHADE_DOUBLES / 4));
     d.cubes = s->d_cubes.p; d.cube_mat = s->d_cube_mat.p;
     d.pcubes = s->d_pcubes.p; d.pcube_mat = s->d_pcube_mat.p;
     d.media = s->d_media.p; d.wrapped = s->d_wrapped.p; d.insts = s->d_insts.p; d.ops = s->d_ops.p;
@@ -302,7 +313,7 @@ int finish_commit(zr_scene* s, const CommitPlan& plan, const CommitSummary& cs) 
     for (const zr_material& m : s->materials) d.mat_kinds |= 1u << m.kind;
     d.root = cs.root;
     s->leaf_objects = 0;
-    for (int k = 0; k < 8; k++) { d.leaf_cnt[k] = plan.cnt[k]; s->leaf_objects += plan.cnt[k]; }
+    for (int k = 0; k < 7; k++) { d.leaf_cnt[k] = plan.cnt[k]; s->leaf_objects += plan.cnt[k]; }   // (no leaf kind 7 exists)
     // a small world's objects for the fused kernel's arguments (zr_launch.h: FusedObjs): read back from the arrays just built,
     // whichever builder made them (a few hundred bytes)
     s->fused_ok = false;
@@ -357,7 +368,8 @@ int finish_commit(zr_scene* s, const CommitPlan& plan, const CommitSummary& cs) 
     if (std::getenv("ZR_QUANT_STATS")) std::fprintf(stderr, "[zr] 4-wide tree: depth %d, worst-case traversal stack %u entries\n", cs.quad_depth, s->stack_demand);
     s->stats[0] = cs.n_pairs; s->stats[1] = (uint64_t)cs.max_depth; s->stats[2] = plan.objs.size();
     s->stats[3] = cs.n_pairs * sizeof(zr::NodePair) + cs.n_quads * sizeof(zr::NodeQ) + (z[ZR_PRIM_SPHERE] * ZR_SPHERE_DOUBLES + z[ZR_PRIM_TRIANGLE] * (ZR_TRI_STRIDE + ZR_TRI_SHADE_DOUBLES) + z[ZR_PRIM_CUBE] * ZR_CUBE_DOUBLES +
-                   z[ZR_KIND_PCUBE] * ZR_PCUBE_STRIDE) * sizeof(double) + (z[ZR_PRIM_SPHERE] + z[ZR_PRIM_CUBE]) * sizeof(uint32_t) + s->texels.size();
+                   z[ZR_KIND_PCUBE] * ZR_PCUBE_STRIDE) * sizeof(double) + (z[ZR_PRIM_SPHERE] + z[ZR_PRIM_CUBE]) * sizeof(uint32_t) + s->texels.size() +
+                  (s->tri_uv.empty() ? 0 : z[ZR_PRIM_TRIANGLE] * 6 * sizeof(double));
     s->builder = cs.builder;
     if (std::getenv("ZR_COMMIT_HASH")) {   // development / test aid: a hash of the committed 4-wide node array and pair records — the tree AND its layout in memory
         (void)hipDeviceSynchronize();
@@ -372,7 +384,7 @@ int finish_commit(zr_scene* s, const CommitPlan& plan, const CommitSummary& cs) 
     }
     s->committed = true;
     if (s->borrowed) {   // the caller's arrays are not read again: forget them (a second commit needs a new zr_scene_set_*)
-        s->spheres.drop(); s->sphere_mat.drop(); s->tri_v.drop(); s->tri_n.drop(); s->tri_mat.drop(); s->cubes.drop(); s->cube_mat.drop();
+        s->spheres.drop(); s->sphere_mat.drop(); s->tri_v.drop(); s->tri_n.drop(); s->tri_mat.drop(); s->tri_uv.drop(); s->cubes.drop(); s->cube_mat.drop();
         s->media.drop(); s->ops.drop(); s->objects.drop(); s->texels.drop(); s->objects_set = false; s->borrowed = false; s->released = true;
     }
     return ZR_OK;
@@ -412,7 +424,19 @@ int zr_scene_set_triangles(zr_scene* s, const double* v9, const double* n9, cons
     CHECK_SCENE(s);
     if (n && (!v9 || !n9 || !mat)) return fail(ZR_E_INVALID, "null triangle arrays");
     s->tri_v.copy(v9, n * 9); s->tri_n.copy(n9, n * 9); s->tri_mat.copy(mat, n);
+    s->tri_uv.drop();   // texture coordinates belong to the triangles they were given for
     GEOMETRY_SET(s, SET_TRIANGLES);
+    return ZR_OK;
+}
+int zr_scene_set_triangle_uvs(zr_scene* s, const double* uv6, size_t n) {
+    if (!s) return fail(ZR_E_INVALID, "null scene");
+    if (!uv6 && n) return fail(ZR_E_INVALID, "null texture-coordinate array for %zu triangles", n);
+    if (!uv6) { s->committed = false; s->tri_uv.drop(); return ZR_OK; }
+    if (n != s->tri_mat.size()) return fail(ZR_E_INVALID, "texture coordinates for %zu triangles, the scene has %zu", n, s->tri_mat.size());
+    for (size_t k = 0; k < n * 6; k++)
+        if (!std::isfinite(uv6[k])) return fail(ZR_E_INVALID, "texture coordinate %zu of triangle %zu is not finite", k % 6, k / 6);
+    s->committed = false;
+    s->tri_uv.copy(uv6, n * 6);
     return ZR_OK;
 }
 int zr_scene_set_cubes(zr_scene* s, const double* q, const uint32_t* mat, size_t n) {
@@ -485,6 +509,7 @@ int zr_scene_set_all_borrowed(zr_scene* s, const zr_scene_desc* d) {
         return fail(ZR_E_INVALID, "null array in the scene description");
     s->spheres.borrow(d->spheres, d->n_spheres * 4); s->sphere_mat.borrow(d->sphere_mat, d->n_spheres);
     s->tri_v.borrow(d->tri_v, d->n_tris * 9); s->tri_n.borrow(d->tri_n, d->n_tris * 9); s->tri_mat.borrow(d->tri_mat, d->n_tris);
+    s->tri_uv.drop();
     s->cubes.borrow(d->cubes, d->n_cubes * 12); s->cube_mat.borrow(d->cube_mat, d->n_cubes);
     s->media.borrow(d->media, d->n_media);
     s->ops.borrow(d->ops, d->n_ops);

@@ -178,14 +178,16 @@ __device__ __forceinline__ bool world_walk(const DScene& sc, const Ray& r, doubl
 }
 
 // what a debug hit emits: the frame / volume colour, or the surface's emitted()
+template <bool UV>
 __device__ __forceinline__ V3 hit_emission(const DScene& sc, const Ray& r, const DHit& h) {
     if (h.cls != ZR_BVH_SURFACE) return debug_color(h.cls, h.depth);
     Rec rec;
-    object_rec(sc, h.kind, h.idx, r, h.t, rec);
+    object_rec<true, UV>(sc, h.kind, h.idx, r, h.t, rec);
     return emitted(sc, rec);
 }
 
 // one primary sample of the debug view: camera.hpp:455-461, 519-520 with ray_color_from_hit (989-1004) and ray_color's debug branch (928-953)
+template <bool UV>
 __device__ V3 debug_sample(const DScene& sc, const DCamera& cam, const DEnv& env, int px, int py, int level, float thick, Rng& g, uint32_t* stk) {
     const Ray r = camera_ray(cam, px, py, g);
     DHit h;
@@ -194,7 +196,7 @@ __device__ V3 debug_sample(const DScene& sc, const DCamera& cam, const DEnv& env
     if (!hit) return background(sc, env, r.d);
     if (h.cls != ZR_BVH_SURFACE) return debug_color(h.cls, h.depth);   // diffuse_light: emits, does not scatter
     Rec rec;
-    object_rec(sc, h.kind, h.idx, r, h.t, rec);
+    object_rec<true, UV>(sc, h.kind, h.idx, r, h.t, rec);
     const V3 L0 = emitted(sc, rec);
     V3 att; Ray sr;
     if (!scatter(sc, r, rec, att, sr, g)) return L0;
@@ -202,7 +204,7 @@ __device__ V3 debug_sample(const DScene& sc, const DCamera& cam, const DEnv& env
     if (cam.max_depth - 1 > 0) {
         DHit h2;
         if (world_walk(sc, sr, 0.001, level, thick, g, stk, h2)) {
-            const V3 e = hit_emission(sc, sr, h2);
+            const V3 e = hit_emission<UV>(sc, sr, h2);
             c = len(e) > 0.1 ? e : mk(0.01, 0.01, 0.01);
         }
         g.bounce++;
@@ -210,6 +212,8 @@ __device__ V3 debug_sample(const DScene& sc, const DCamera& cam, const DEnv& env
     return L0 + att * c;
 }
 
+// UV: the build for scenes whose triangles carry texture coordinates (zr_device.h: triangle_rec_uv)
+template <bool UV>
 __global__ __launch_bounds__(ZR_DBG_BLOCK) void bvh_debug_pixels(DScene sc, DCamera cam, DEnv env, uint64_t seed, WorkDesc wd, int level, float thick,
                                                                   double* __restrict__ out) {
     __shared__ uint32_t lds_stack[2 * ZR_STACK_DEPTH * ZR_DBG_BLOCK];
@@ -226,13 +230,15 @@ __global__ __launch_bounds__(ZR_DBG_BLOCK) void bvh_debug_pixels(DScene sc, DCam
     V3 sum = mk(0, 0, 0);
     for (int s = 0; s < cam.spp; s++) {
         Rng g; g.key = zr_stream_key(seed, pixel, (uint64_t)s); g.k = 0; g.bounce = 0;
-        sum = sum + debug_sample(sc, cam, env, px, py, level, thick, g, stk);
+        sum = sum + debug_sample<UV>(sc, cam, env, px, py, level, thick, g, stk);
     }
     const double scale = 1.0 / cam.spp;   // camera.hpp:437,531
     double* o = out + (size_t)pixel * 3;
     o[0] = sum.x * scale; o[1] = sum.y * scale; o[2] = sum.z * scale;
 }
 
+// UV: the build for scenes whose triangles carry texture coordinates (zr_device.h: triangle_rec_uv)
+template <bool UV>
 __global__ __launch_bounds__(ZR_DBG_BLOCK) void bvh_debug_trace(DScene sc, const double* __restrict__ rays, size_t n, double tmin, uint64_t seed, uint64_t pixel,
                                                                  uint32_t bounce, int level, float thick, zr_bvh_debug_hit* __restrict__ out) {
     __shared__ uint32_t lds_stack[2 * ZR_STACK_DEPTH * ZR_DBG_BLOCK];
@@ -250,7 +256,7 @@ __global__ __launch_bounds__(ZR_DBG_BLOCK) void bvh_debug_trace(DScene sc, const
         V3 e;
         if (h.cls == ZR_BVH_SURFACE) {
             Rec rec;
-            object_rec(sc, h.kind, h.idx, r, h.t, rec, true);
+            object_rec<true, UV>(sc, h.kind, h.idx, r, h.t, rec, true);
             o.hit.p[0] = rec.p.x; o.hit.p[1] = rec.p.y; o.hit.p[2] = rec.p.z;
             o.hit.normal[0] = rec.n.x; o.hit.normal[1] = rec.n.y; o.hit.normal[2] = rec.n.z;
             o.hit.tangent[0] = rec.tan.x; o.hit.tangent[1] = rec.tan.y; o.hit.tangent[2] = rec.tan.z;
@@ -275,14 +281,17 @@ hipError_t launch_bvh_debug(const DScene& sc, const DCamera& cam, const DEnv& en
     const long long blocks = (pixels + ZR_DBG_BLOCK - 1) / ZR_DBG_BLOCK;
     if (blocks <= 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bvh_debug_pixels, dim3((unsigned)blocks), dim3(ZR_DBG_BLOCK), 0, stream, sc, cam, env, seed, wd, level, thickness, out);
+    if (sc.tri_uv_at) hipLaunchKernelGGL(bvh_debug_pixels<true>, dim3((unsigned)blocks), dim3(ZR_DBG_BLOCK), 0, stream, sc, cam, env, seed, wd, level, thickness, out);
+    else hipLaunchKernelGGL(bvh_debug_pixels<false>, dim3((unsigned)blocks), dim3(ZR_DBG_BLOCK), 0, stream, sc, cam, env, seed, wd, level, thickness, out);
     return hipGetLastError();
 }
 
 hipError_t launch_trace_bvh_debug(const DScene& sc, const double* rays, size_t n, double tmin, uint64_t seed, uint64_t pixel, uint32_t bounce, int level,
                                   float thickness, zr_bvh_debug_hit* out, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(bvh_debug_trace, dim3((unsigned)((n + ZR_DBG_BLOCK - 1) / ZR_DBG_BLOCK)), dim3(ZR_DBG_BLOCK), 0, stream, sc, rays, n, tmin, seed, pixel,
+    if (sc.tri_uv_at) hipLaunchKernelGGL(bvh_debug_trace<true>, dim3((unsigned)((n + ZR_DBG_BLOCK - 1) / ZR_DBG_BLOCK)), dim3(ZR_DBG_BLOCK), 0, stream, sc, rays, n, tmin, seed, pixel,
+                       bounce, level, thickness, out);
+    else hipLaunchKernelGGL(bvh_debug_trace<false>, dim3((unsigned)((n + ZR_DBG_BLOCK - 1) / ZR_DBG_BLOCK)), dim3(ZR_DBG_BLOCK), 0, stream, sc, rays, n, tmin, seed, pixel,
                        bounce, level, thickness, out);
     return hipGetLastError();
 }

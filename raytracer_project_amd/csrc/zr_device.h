@@ -586,6 +586,38 @@ __device__ inline void sphere_rec(const DScene& sc, uint32_t idx, const Ray& r, 
     rec.bit = cross(rec.n, rec.tan);
 }
 
+// ---- per-vertex texture coordinates of triangles (DScene::tri_uv) -------------------------------------------------------
+// The kernels are built twice where they make hit records: UV = false is the code of a world without coordinates, instruction for instruction what it was
+// before coordinates existed; UV = true is launched for a scene that has them (the launchers choose by sc.tri_uv_at, as they choose EXTEND's level).
+__device__ __forceinline__ const double* tri_uv(const DScene& sc) { return sc.tri_uv_at ? sc.tri_s + (size_t)sc.tri_uv_at * 4 : nullptr; }
+// The unnormalised tangent: the direction of increasing u in the space of the edges e1 = V1 - V0, e2 = V2 - V0; zero for a degenerate chart
+__device__ __forceinline__ V3 tri_tangent_dir(const double* q, V3 e1, V3 e2) {
+    const double d1u = q[2] - q[0], d1v = q[3] - q[1], d2u = q[4] - q[0], d2v = q[5] - q[1];
+    const double det = d1u * d2v - d2u * d1v;
+    if (det == 0) return mk(0, 0, 0);
+    const V3 T = d2v * e1 - d1v * e2;
+    return det < 0 ? mk(-T.x, -T.y, -T.z) : T;
+}
+// a direction through the second half of a wrapper: rotations turn it, scale stretches it, translate and material_instance leave it alone
+__device__ inline void apply_op_dir(const zr_xform_op& op, V3& d) {
+    const double s = op.a[0], c = op.a[1];
+    switch (op.kind) {
+        case ZR_OP_ROTATE_Y: { const double x = d.x, z = d.z; d.x = c * x - s * z; d.z = s * x + c * z; } break;
+        case ZR_OP_ROTATE_X: { const double y = d.y, z = d.z; d.y = c * y - s * z; d.z = s * y + c * z; } break;
+        case ZR_OP_ROTATE_Z: { const double x = d.x, y = d.y; d.x = c * x - s * y; d.y = s * x + c * y; } break;
+        case ZR_OP_SCALE: d = mk(d.x * op.a[0], d.y * op.a[1], d.z * op.a[2]); break;
+        default: break;
+    }
+}
+// tangent = the world-space T made orthogonal to the record's FINAL normal, bitangent = cross(n, tangent) as sphere_rec and cube_rec_q have it (a
+// mirrored chart therefore flips the frame's handedness); both zero when nothing is left of T
+__device__ __forceinline__ void tri_tangent_finish(Rec& rec, V3 T) {
+    const V3 Tp = T - dot(T, rec.n) * rec.n;
+    const double l2 = len2(Tp);
+    if (l2 > 0) { rec.tan = vdiv(Tp, sqrt(l2)); rec.bit = cross(rec.n, rec.tan); }
+    else { rec.tan = mk(0, 0, 0); rec.bit = mk(0, 0, 0); }
+}
+
 __device__ inline void triangle_rec(const DScene& sc, uint32_t idx, const Ray& r, double t, Rec& rec) {  // triangle.hpp:40-79
     const double* v = sc.tri_s + (size_t)idx * 20;  // one record = everything the hit record needs
     const double* nn = v + 9;
@@ -606,6 +638,30 @@ __device__ inline void triangle_rec(const DScene& sc, uint32_t idx, const Ray& r
     if ((uint32_t)__double_as_longlong(v[19]) & 1u) rec.front = true;   // baked from under a translate / rotate_y (zr_flatten.h)
     // u, v, tangent, bitangent are not written by triangle::hit: fresh-record values
     rec.u = 0; rec.v = 0; rec.tan = mk(0, 0, 0); rec.bit = mk(0, 0, 0);
+}
+// The UV builds' triangle record: triangle_rec, then u, v from the vertices' coordinates with the barycentrics triangle_rec interpolates the normal with
+// (the same expressions: the compiler computes them once), and the tangent.  Coordinates are read only when something consumes them.
+// T_chain: the caller (object_rec, a triangle under a wrapper chain) takes the unnormalised tangent through the chain and finishes it itself
+__device__ inline void triangle_rec_uv(const DScene& sc, uint32_t idx, const Ray& r, double t, Rec& rec, bool full, V3* T_chain = nullptr) {
+    triangle_rec(sc, idx, r, t, rec);
+    V3 T = mk(0, 0, 0);
+    if (sc.tri_uv_at && (full || mat_needs_uv(sc, rec.mat))) {
+        const double* v = sc.tri_s + (size_t)idx * 20;
+        const double* q = tri_uv(sc) + (size_t)idx * 6;
+        V3 v0 = ld3(v), v1 = ld3(v + 3), v2 = ld3(v + 6);
+        V3 normal = cross(v1 - v0, v2 - v0);
+        V3 C0 = cross(v1 - v0, rec.p - v0);
+        V3 C2 = cross(v0 - v2, rec.p - v2);
+        double area2 = dot(normal, normal);
+        double ub = dot(normal, C2) / area2;
+        double wb = dot(normal, C0) / area2;
+        double w0 = 1.0 - ub - wb;
+        rec.u = w0 * q[0] + ub * q[2] + wb * q[4];
+        rec.v = w0 * q[1] + ub * q[3] + wb * q[5];
+        T = tri_tangent_dir(q, v1 - v0, v2 - v0);
+    }
+    if (T_chain) *T_chain = T;
+    else tri_tangent_finish(rec, T);
 }
 
 // uv = false: u, v, tangent and bitangent are left zero — nothing reads them (the hit's material looks up no image and has no bump map: mat_needs_uv);
@@ -650,10 +706,11 @@ __device__ inline void cube_rec(const DScene& sc, uint32_t idx, const Ray& r, do
     cube_rec_q(sc.cubes + (size_t)idx * 6, mat, r, t, rec, full || mat_needs_uv(sc, mat));
 }
 
+template <bool UV = false>
 __device__ inline void bare_rec(const DScene& sc, uint32_t kind, uint32_t idx, const Ray& r, double t, Rec& rec, bool full) {
     if (kind == ZR_PRIM_SPHERE) sphere_rec(sc, idx, r, t, rec, full);
     else if (kind == ZR_PRIM_CUBE) cube_rec(sc, idx, r, t, rec, full);
-    else if (kind == ZR_PRIM_TRIANGLE) triangle_rec(sc, idx, r, t, rec);
+    else if (kind == ZR_PRIM_TRIANGLE) { if constexpr (UV) triangle_rec_uv(sc, idx, r, t, rec, full); else triangle_rec(sc, idx, r, t, rec); }
     else {  // medium: constant_medium.hpp:70-75
         rec.t = t;
         rec.p = at(r, t);
@@ -666,7 +723,8 @@ __device__ inline void bare_rec(const DScene& sc, uint32_t kind, uint32_t idx, c
 
 // hit record of leaf object (kind, idx) hit by world ray r at distance t
 // `full`: compute every field (known-answer entry); otherwise u/v/tangent only when the material reads them
-template <bool PSCALE = true>
+// UV: the build for scenes whose triangles carry texture coordinates (triangle_rec above)
+template <bool PSCALE = true, bool UV = false>
 __device__ inline void object_rec(const DScene& sc, uint32_t kind, uint32_t idx, const Ray& r, double t, Rec& rec, bool full = false) {
     if (kind == ZR_KIND_PCUBE) {   // cube::hit's record in object space, then the second halves of scale::hit, rotate_y::hit and translate::hit, inside-out
         const double* q = sc.pcubes + (size_t)idx * ZR_PCUBE_STRIDE;
@@ -680,11 +738,26 @@ __device__ inline void object_rec(const DScene& sc, uint32_t kind, uint32_t idx,
         return;
     }
     const bool placed_run = (kind & 0xFFu) == ZR_KIND_INSTANCE;   // a triangle of a run: the record of a triangle under the instance's chain
-    if (kind != ZR_KIND_WRAPPED && !placed_run) { bare_rec(sc, kind, idx, r, t, rec, full); return; }
+    if (kind != ZR_KIND_WRAPPED && !placed_run) { bare_rec<UV>(sc, kind, idx, r, t, rec, full); return; }
     DWrapped w;
     if (placed_run) { const DInstance in = sc.insts[kind >> 8]; w.type = ZR_PRIM_TRIANGLE; w.index = idx; w.chain_first = in.chain_first; w.chain_count = in.chain_count; }
     else w = sc.wrapped[idx];
     Ray lr = chain_ray(sc, w.chain_first, w.chain_count, r);
+    if constexpr (UV) {
+        // a triangle's tangent is a WORLD-space quantity however the triangle is stored: the unnormalised tangent travels through the chain as a direction
+        // and is finished against the final normal (a cube's stays in object space, as the reference leaves it: apply_op_rec moves p and n only)
+        if (w.type == ZR_PRIM_TRIANGLE) {
+            V3 T;
+            triangle_rec_uv(sc, w.index, lr, t, rec, true, &T);
+            for (int k = (int)w.chain_count - 1; k >= 0; k--) {
+                Ray outer = chain_ray(sc, w.chain_first, (uint32_t)k, r);
+                apply_op_rec(sc.ops[w.chain_first + k], outer.d, rec);
+                apply_op_dir(sc.ops[w.chain_first + k], T);
+            }
+            tri_tangent_finish(rec, T);
+            return;
+        }
+    }
     bare_rec(sc, w.type, w.index, lr, t, rec, true);  // a material_instance in the chain may replace the material
     for (int k = (int)w.chain_count - 1; k >= 0; k--) {
         Ray outer = chain_ray(sc, w.chain_first, (uint32_t)k, r);

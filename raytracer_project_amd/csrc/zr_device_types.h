@@ -70,7 +70,7 @@ struct DScene {
     const double* spheres;      // 4 per sphere: cx cy cz max(0, r)
     const uint32_t* sphere_mat;
     const double* tri_v;        // 9 per triangle
-    const double* tri_s;        // shading record, 20 doubles (160 B, two 128-B lines at any 32-B phase) per triangle:
+    const double* tri_s;        // (then the texture coordinates: tri_uv_at) shading record, 20 doubles (160 B, two 128-B lines at any 32-B phase) per triangle:
                                 // [0..8] vertices, [9..17] vertex normals (need not be unit), [18] low word = material id,
                                 // [19] low word bit 0 = front_face forced true (triangle baked from under a translate / rotate_y)
     const double* cubes;        // 6 per cube: half extents, centre
@@ -87,7 +87,11 @@ struct DScene {
     uint32_t n_mats;
     uint32_t mat_kinds;  // bit k set: a material of kind k exists (SHADE sorts by kind only when more than one does)
     uint32_t shade_lean; // 1: SHADE may run its lean build (bare triangles / spheres, lambertian / metal / dielectric / light over solid colours, no bump maps)
-    uint32_t leaf_cnt[8]; // leaf objects per kind (the first leaf_cnt[k] records of kind k's array): the fused small-scene kernel tests them all
+    uint32_t leaf_cnt[7]; // leaf objects per kind (the first leaf_cnt[k] records of kind k's array): the fused small-scene kernel tests them all
+    uint32_t tri_uv_at;   // per-vertex texture coordinates of the triangles, 6 doubles each (u0 v0 u1 v1 u2 v2) in the order of tri_s: they start tri_uv_at * 4
+                          // doubles behind tri_s[0], in the same allocation, right after the last shading record; 0: the scene has none.
+                          // In the place of the never-used leaf_cnt[7]: the struct keeps its size and layout — a pointer member made it 8 bytes longer, and
+                          // the pixel-group kernel, which keeps a copy of the struct in scratch, 16 bytes of scratch heavier (profiles/texcoord_kernel_regs.txt)
     NodeF root;          // variant 2: the root of the 4-wide tree
     uint32_t shade_escape; // 1: lean SHADE finishes a scattered ray that provably leaves the world in the round that made it (zr_device.h: ray_escapes).
                            // Behind `root`, in the struct's tail padding: no other member moves

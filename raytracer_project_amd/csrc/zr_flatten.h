@@ -317,6 +317,7 @@ struct Flattener {
     zr::RawArray<uint32_t> leaf_first; // per build node: device index of a leaf's first primitive
     int quad_depth = 0;
     zr::RawArray<double> spheres, tri_v, tri_s, cubes, pcubes;
+    size_t uv_base = 0;            // the triangles' texture coordinates, 6 per stored triangle, start at tri_s[uv_base], behind the last shading record (0: the scene has none)
     zr::RawArray<uint32_t> sphere_mat, cube_mat, pcube_mat;
     zr::RawArray<zr::DMedium> media;
     zr::RawArray<zr::DWrapped> wrapped;
@@ -408,7 +409,12 @@ struct Flattener {
         uint64_t mbits = mat, fbits = force_front ? 1u : 0u;
         std::memcpy(t + 18, &mbits, 8); std::memcpy(t + 19, &fbits, 8);
     }
-    void put_triangle(size_t di, uint32_t idx) { put_triangle_raw(di, &s.tri_v[(size_t)idx * 9], &s.tri_n[(size_t)idx * 9], s.tri_mat[idx], false); }
+    // a stored triangle's texture coordinates travel with it, unchanged (baked or not: they are no geometry)
+    void put_triangle_uv(size_t di, uint32_t idx) { if (uv_base) std::memcpy(&tri_s[uv_base + di * 6], &s.tri_uv[(size_t)idx * 6], 48); }
+    void put_triangle(size_t di, uint32_t idx) {
+        put_triangle_raw(di, &s.tri_v[(size_t)idx * 9], &s.tri_n[(size_t)idx * 9], s.tri_mat[idx], false);
+        put_triangle_uv(di, idx);
+    }
     void put_cube(size_t di, uint32_t idx, uint32_t mat) {
         std::memcpy(&cubes[di * ZR_CUBE_DOUBLES], &s.cubes[(size_t)idx * 12], ZR_CUBE_DOUBLES * sizeof(double));
         cube_mat[di] = mat != kKeepMaterial ? mat : s.cube_mat[idx];
@@ -447,6 +453,7 @@ struct Flattener {
             if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
         }
         put_triangle_raw(di, v, nn, mat, force_front);
+        put_triangle_uv(di, o.index);
     }
     // A sphere under uniform scale / translate / material_instance wrappers (the demo scene's instanced spheres:
     // scale -> material_instance -> translate) is the sphere (c s + offset, r s): same t, same unit normal, same u/v and
@@ -592,7 +599,8 @@ struct Flattener {
     void allocate_arrays(const CommitPlan& p) {
         const size_t* z = p.size;
         spheres.allocate(z[ZR_PRIM_SPHERE] * ZR_SPHERE_DOUBLES); sphere_mat.allocate(z[ZR_PRIM_SPHERE]);
-        tri_v.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_STRIDE); tri_s.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES);
+        uv_base = s.tri_uv.empty() ? 0 : z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES;
+        tri_v.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_STRIDE); tri_s.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES + (uv_base ? z[ZR_PRIM_TRIANGLE] * 6 : 0));
         cubes.allocate(z[ZR_PRIM_CUBE] * ZR_CUBE_DOUBLES); cube_mat.allocate(z[ZR_PRIM_CUBE]);
         pcubes.allocate(z[ZR_KIND_PCUBE] * ZR_PCUBE_STRIDE); pcube_mat.allocate(z[ZR_KIND_PCUBE]);
         media.allocate(z[ZR_PRIM_MEDIUM]); wrapped.allocate(z[ZR_KIND_WRAPPED]);

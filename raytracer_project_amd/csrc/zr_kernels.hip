@@ -12,7 +12,34 @@
 #include "zr_device.h"
 #include "zr_launch.h"
 
+// This file is compiled twice.  As itself (ZR_UV 0) it is the code of scenes whose triangles carry no texture coordinates: the module the compiler sees
+// is what it was before coordinates existed, so its kernels are too, bit for bit (with the second build as template instantiations in the same
+// module the counting pixel-group kernels came out with other inlining and other last bits).  zr_kernels_uv.hip compiles it again with ZR_UV 1, in
+// the namespace zr::uvbuild: the kernels that read the coordinates (zr_device.h: triangle_rec_uv), which the launchers below hand scenes with
+// DScene::tri_uv_at != 0 to.
+#ifndef ZR_UV
+#define ZR_UV 0
+#endif
+#if ZR_UV
+#define ZR_UV_DISPATCH(call)
+namespace zr { namespace uvbuild {
+#else
+#define ZR_UV_DISPATCH(call) if (sc.tri_uv_at) return uvbuild::call;
 namespace zr {
+namespace uvbuild {   // zr_kernels_uv.hip
+hipError_t launch_render(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, double* out, unsigned long long* gctr, bool count,
+                         hipStream_t stream);
+hipError_t launch_render_samples(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const uint32_t* pixels, uint32_t n_pix, uint32_t sample0,
+                                 uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream);
+hipError_t launch_aov(const DScene& sc, const DCamera& cam, uint64_t seed, const WorkDesc& wd, int aux, double zmax, const double* uvw9, double* out_albedo,
+                      double* out_normal, double* out_zdepth, hipStream_t stream);
+hipError_t launch_passes(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, double* out_beauty, double* out_reflection,
+                         double* out_refraction, unsigned long long* gctr, hipStream_t stream);
+hipError_t launch_path_records(const DScene& sc, const DCamera& cam, uint64_t seed, const int32_t* req, int n_req, int max_seg, double* out, hipStream_t stream);
+hipError_t launch_trace(const DScene& sc, const double* rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* out,
+                        hipStream_t stream);
+}
+#endif
 
 __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -35,7 +62,7 @@ __device__ inline V3 path_radiance(const DScene& sc, const DEnv& env, Ray cur, i
         if (!h) { missed = true; break; }
         hits++;
         Rec rec;
-        object_rec(sc, kind, idx, cur, t, rec);
+        object_rec<true, ZR_UV != 0>(sc, kind, idx, cur, t, rec);
         L = L + beta * emitted(sc, rec);
         V3 att; Ray out;
         if (!scatter(sc, cur, rec, att, out, g)) break;
@@ -65,7 +92,7 @@ __device__ inline V3 sample_radiance(const DScene& sc, const DCamera& cam, const
     if (!h) return background(sc, env, r.d);
     hits++;
     Rec rec;
-    object_rec(sc, kind, idx, r, t, rec);
+    object_rec<true, ZR_UV != 0>(sc, kind, idx, r, t, rec);
     V3 L0 = emitted(sc, rec);
     V3 att0; Ray cur;
     if (!scatter(sc, r, rec, att0, cur, g)) return L0;
@@ -85,7 +112,7 @@ __device__ inline void sample_passes(const DScene& sc, const DCamera& cam, const
     if (!h) { beauty = beauty + background(sc, env, r.d); return; }
     hits++;
     Rec rec;
-    object_rec(sc, kind, idx, r, t, rec);
+    object_rec<true, ZR_UV != 0>(sc, kind, idx, r, t, rec);
     {
         V3 L0 = emitted(sc, rec);
         V3 att0; Ray cur;
@@ -276,7 +303,7 @@ __global__ __launch_bounds__(ZR_BLOCK) void aov_pixels(DScene sc, DCamera cam, u
             double t; uint32_t kind, idx;
             if (closest_hit<false>(sc, r, 0.001, g, stack, ZR_BLOCK, t, kind, idx, ctr)) {
                 Rec rec;
-                object_rec(sc, kind, idx, r, t, rec);
+                object_rec<true, ZR_UV != 0>(sc, kind, idx, r, t, rec);
                 a = a + get_albedo(sc, rec);
                 V3 un = unit(rec.n);
                 n = n + mk((dot(un, mk(cu.x, cu.y, cu.z)) + 1.0) * 0.5, (dot(un, mk(cv.x, cv.y, cv.z)) + 1.0) * 0.5, (dot(un, mk(cw.x, cw.y, cw.z)) + 1.0) * 0.5);
@@ -315,7 +342,7 @@ __global__ __launch_bounds__(ZR_BLOCK) void trace_rays(DScene sc, const double* 
     zr_hit o;
     if (h) {
         Rec rec;
-        object_rec(sc, kind, idx, r, t, rec, true);
+        object_rec<true, ZR_UV != 0>(sc, kind, idx, r, t, rec, true);
         o.p[0] = rec.p.x; o.p[1] = rec.p.y; o.p[2] = rec.p.z;
         o.normal[0] = rec.n.x; o.normal[1] = rec.n.y; o.normal[2] = rec.n.z;
         o.tangent[0] = rec.tan.x; o.tangent[1] = rec.tan.y; o.tangent[2] = rec.tan.z;
@@ -404,7 +431,7 @@ __global__ __launch_bounds__(ZR_BLOCK) void path_records(DScene sc, DCamera cam,
         g.bounce++;
         if (!h) { o[6] = 0; o[16] = (double)g.k; break; }
         Rec rec;
-        object_rec(sc, kind, idx, cur, t, rec);
+        object_rec<true, ZR_UV != 0>(sc, kind, idx, cur, t, rec);
         V3 em = emitted(sc, rec);
         V3 att; Ray nxt;
         bool ok = scatter(sc, cur, rec, att, nxt, g);
@@ -429,6 +456,7 @@ __global__ __launch_bounds__(ZR_BLOCK) void path_records(DScene sc, DCamera cam,
 // ---- launch wrappers (called from zr_render.cpp) -------------------------------------------------------
 hipError_t launch_render(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, double* out,
                          unsigned long long* gctr, bool count, hipStream_t stream) {
+    ZR_UV_DISPATCH(launch_render(sc, cam, env, seed, wd, out, gctr, count, stream))
     const int groups_per_block = ZR_BLOCK / wd.lanes_per_pixel;
     const long long pixels = (long long)wd.n_tiles * wd.tile_size * wd.tile_size;
     const long long blocks = (pixels + groups_per_block - 1) / groups_per_block;
@@ -442,6 +470,7 @@ hipError_t launch_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
 
 hipError_t launch_render_samples(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const uint32_t* pixels, uint32_t n_pix, uint32_t sample0,
                                  uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream) {
+    ZR_UV_DISPATCH(launch_render_samples(sc, cam, env, seed, pixels, n_pix, sample0, n, samples, gctr, count, stream))
     const unsigned long long blocks = ((unsigned long long)n_pix * n + ZR_BLOCK - 1) / ZR_BLOCK;
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
@@ -453,6 +482,7 @@ hipError_t launch_render_samples(const DScene& sc, const DCamera& cam, const DEn
 
 hipError_t launch_aov(const DScene& sc, const DCamera& cam, uint64_t seed, const WorkDesc& wd, int aux, double zmax, const double* uvw9,
                       double* out_albedo, double* out_normal, double* out_zdepth, hipStream_t stream) {
+    ZR_UV_DISPATCH(launch_aov(sc, cam, seed, wd, aux, zmax, uvw9, out_albedo, out_normal, out_zdepth, stream))
     const int groups_per_block = ZR_BLOCK / wd.lanes_per_pixel;
     const long long pixels = (long long)wd.n_tiles * wd.tile_size * wd.tile_size;
     const long long blocks = (pixels + groups_per_block - 1) / groups_per_block;
@@ -465,6 +495,7 @@ hipError_t launch_aov(const DScene& sc, const DCamera& cam, uint64_t seed, const
 
 hipError_t launch_passes(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, double* out_beauty,
                          double* out_reflection, double* out_refraction, unsigned long long* gctr, hipStream_t stream) {
+    ZR_UV_DISPATCH(launch_passes(sc, cam, env, seed, wd, out_beauty, out_reflection, out_refraction, gctr, stream))
     const int groups_per_block = ZR_BLOCK / wd.lanes_per_pixel;
     const long long pixels = (long long)wd.n_tiles * wd.tile_size * wd.tile_size;
     const long long blocks = (pixels + groups_per_block - 1) / groups_per_block;
@@ -476,6 +507,7 @@ hipError_t launch_passes(const DScene& sc, const DCamera& cam, const DEnv& env, 
 
 hipError_t launch_path_records(const DScene& sc, const DCamera& cam, uint64_t seed, const int32_t* req, int n_req, int max_seg, double* out,
                                hipStream_t stream) {
+    ZR_UV_DISPATCH(launch_path_records(sc, cam, seed, req, n_req, max_seg, out, stream))
     if (n_req <= 0) return hipSuccess;
     hipLaunchKernelGGL(path_records, dim3((unsigned)((n_req + ZR_BLOCK - 1) / ZR_BLOCK)), dim3(ZR_BLOCK), 0, stream, sc, cam, seed, req, n_req, max_seg, out);
     return hipGetLastError();
@@ -505,10 +537,14 @@ hipError_t launch_kat_camera_rays(const DCamera& cam, uint64_t seed, const int32
 
 hipError_t launch_trace(const DScene& sc, const double* rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel,
                         uint32_t bounce, zr_hit* out, hipStream_t stream) {
+    ZR_UV_DISPATCH(launch_trace(sc, rays, n, tmin, tmax, seed, pixel, bounce, out, stream))
     if (n == 0) return hipSuccess;
     dim3 grid((unsigned)((n + ZR_BLOCK - 1) / ZR_BLOCK)), block(ZR_BLOCK);
     hipLaunchKernelGGL(trace_rays, grid, block, 0, stream, sc, rays, n, tmin, tmax, seed, pixel, bounce, out);
     return hipGetLastError();
 }
 
+#if ZR_UV
+}  // namespace uvbuild
+#endif
 }  // namespace zr

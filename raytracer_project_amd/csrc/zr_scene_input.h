@@ -54,6 +54,7 @@ struct HostArray {
 // the world as given: copies, or borrowed views until the commit (zr_scene is this plus the device side)
 struct SceneInput {
     HostArray<double> spheres, tri_v, tri_n, cubes;
+    HostArray<double> tri_uv;       // per-vertex texture coordinates, 6 per triangle, or empty (zr_scene_set_triangle_uvs: always a copy)
     HostArray<uint32_t> sphere_mat, tri_mat, cube_mat;
     HostArray<zr_medium> media;
     HostArray<zr_xform_op> ops;

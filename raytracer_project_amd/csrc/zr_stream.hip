@@ -514,7 +514,8 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
 #ifndef ST_SHADE_WAVES_LEAN
 #define ST_SHADE_WAVES_LEAN 6
 #endif
-template <bool COUNT, int MODE, bool LEAN = false>
+// UV: the general build for scenes whose triangles carry texture coordinates (zr_device.h: triangle_rec_uv); the lean build reads none
+template <bool COUNT, int MODE, bool LEAN = false, bool UV = false>
 __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) void stream_shade(DScene sc, DCamera cam, DEnv env, uint64_t seed, StreamBuf B,
                                                     unsigned long long* __restrict__ gctr) {
     const uint32_t slot0 = blockIdx.x * 256 + threadIdx.x;
@@ -651,7 +652,7 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
                     sc_ok = lean_shade(sc, ray, rec, em, att, nr, g);
                 } else {
                     Rec rec;
-                    object_rec(sc, ki.x, ki.y, ray, t, rec);
+                    object_rec<true, UV>(sc, ki.x, ki.y, ray, t, rec);
                     em = emitted(sc, rec);
                     if (MODE == 2 && first) {   // the stream continues where the beauty path of this sample stopped
                         const uint2 ke = B.kend[mb_now.x];
@@ -867,7 +868,7 @@ __device__ __forceinline__ void brute_hit(const DScene& sc, const FusedObjs& fo,
     }
 }
 
-template <int LEVEL, bool COUNT>
+template <int LEVEL, bool COUNT, bool UV = false>
 __global__ __launch_bounds__(256, ST_FUSED_WAVES) void fused_render(DScene sc, DCamera cam, DEnv env, uint64_t seed, FusedBuf B, unsigned long long* __restrict__ gctr, FusedObjs fo) {
     const int lane = threadIdx.x & 63;
     const uint32_t wave_id = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -938,7 +939,7 @@ __global__ __launch_bounds__(256, ST_FUSED_WAVES) void fused_render(DScene sc, D
                 ended = true;
             } else {
                 Rec rec;
-                object_rec<false>(sc, kind, idx, ray, t_hit, rec);
+                object_rec<false, UV>(sc, kind, idx, ray, t_hit, rec);
                 const V3 em = emitted(sc, rec);
                 V3 att; Ray nr;
                 const bool sc_ok = scatter(sc, ray, rec, att, nr, g);
@@ -1124,6 +1125,7 @@ __global__ __launch_bounds__(256) void stream_load_rays(StreamBuf B, const doubl
     B.st2(SF_MA, slot, ma);
 }
 
+template <bool UV>
 __global__ __launch_bounds__(256) void stream_hits_out(DScene sc, StreamBuf B, uint32_t n, zr_hit* __restrict__ out) {
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
     if (slot >= n) return;
@@ -1132,7 +1134,7 @@ __global__ __launch_bounds__(256) void stream_hits_out(DScene sc, StreamBuf B, u
     if (ki.x != 0xFFFFFFFFu) {
         Ray r; r.o = B.ld3(SF_RAY, slot); r.d = B.ld3(SF_RAY + 3, slot);
         Rec rec;
-        object_rec(sc, ki.x, ki.y, r, B.ld(SF_HIT_T, slot), rec, true);
+        object_rec<true, UV>(sc, ki.x, ki.y, r, B.ld(SF_HIT_T, slot), rec, true);
         o.p[0] = rec.p.x; o.p[1] = rec.p.y; o.p[2] = rec.p.z;
         o.normal[0] = rec.n.x; o.normal[1] = rec.n.y; o.normal[2] = rec.n.z;
         o.tangent[0] = rec.tan.x; o.tangent[1] = rec.tan.y; o.tangent[2] = rec.tan.z;
@@ -1248,6 +1250,12 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
         if (sc.shade_lean && mode == 0) {   // the lean build: same arithmetic, fewer registers, 6 waves per SIMD instead of 4 (see lean_rec, zr_device.h)
             if (F.count) hipLaunchKernelGGL((stream_shade<true, 0, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
             else hipLaunchKernelGGL((stream_shade<false, 0, true>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
+        }
+        else if (sc.tri_uv_at) {   // the general builds that read the triangles' texture coordinates
+            if (mode == 1) hipLaunchKernelGGL((stream_shade<true, 1, false, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+            else if (mode == 2) hipLaunchKernelGGL((stream_shade<true, 2, false, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+            else if (F.count) hipLaunchKernelGGL((stream_shade<true, 0, false, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+            else hipLaunchKernelGGL((stream_shade<false, 0, false, true>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
         }
         else if (shade_pad && mode == 0 && !F.count) hipLaunchKernelGGL((stream_shade<false, 0>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
         else if (mode == 1) hipLaunchKernelGGL((stream_shade<true, 1>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);        // the split passes always count
@@ -1369,7 +1377,11 @@ hipError_t fused_render_frame(const DScene& sc, const StreamFrame& F, const Stre
         const unsigned long long want_blocks = ((unsigned long long)(B.chunk_hi - B.chunk_lo) + 3) / 4;   // no more waves than chunks
         const dim3 grid((unsigned)(want_blocks < (unsigned long long)blocks ? (want_blocks ? want_blocks : 1) : blocks)), block(256);
         if (H.timer) H.timer->begin(stream, 1);
-        if (level <= 1) { if (F.count) hipLaunchKernelGGL((fused_render<1, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<1, false>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
+        if (sc.tri_uv_at) {   // the builds that read the triangles' texture coordinates
+            if (level <= 1) { if (F.count) hipLaunchKernelGGL((fused_render<1, true, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<1, false, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
+            else { if (F.count) hipLaunchKernelGGL((fused_render<2, true, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<2, false, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
+        }
+        else if (level <= 1) { if (F.count) hipLaunchKernelGGL((fused_render<1, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<1, false>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
         else { if (F.count) hipLaunchKernelGGL((fused_render<2, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<2, false>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
         if (H.timer) H.timer->end(stream, 1);
         done = p + 1;
@@ -1418,7 +1430,8 @@ hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint
     hipLaunchKernelGGL(stream_load_rays, dim3((P + 255) / 256), dim3(256), 0, stream, B, d_rays, n, seed, pixel, bounce);
     const int eb = (int)(P / 64 < (uint32_t)X.extend_blocks ? P / 64 : (uint32_t)X.extend_blocks);
     launch_extend<false>(sc, B, X.overflow, X.ovf_levels, eb, X.gctr, leaf_level, stream);
-    hipLaunchKernelGGL(stream_hits_out, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out);
+    if (sc.tri_uv_at) hipLaunchKernelGGL(stream_hits_out<true>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out);
+    else hipLaunchKernelGGL(stream_hits_out<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out);
     return hipGetLastError();
 }
 

@@ -22,7 +22,7 @@ timeout -k 10 400 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_RE
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmcD_${TAG}_$WL -- python3 $R/bench.py --steps 1 --warmup 0 --workload $WL --no-cpu-baseline > /dev/null 2> $OUT/pmcD_${TAG}_$WL.err || stop "FP64 pass"
 SHA=$(python3 $R/bench.py --kernel-src-sha)
 python3 - "$OUT" "$TAG" "$WL" "$SHA" <<'PY'
-import csv, glob, json, os, sys, collections
+import csv, glob, json, os, re, sys, collections
 out, tag, wl, sha = sys.argv[1:5]
 f = sorted(glob.glob(f'{out}/prof_{tag}_{wl}/*/*kernel_stats.csv'), key=os.path.getmtime)
 if f: open(f'{out}/{tag}_{wl}_kernel_stats.csv', 'w').write(open(f[-1]).read())
@@ -33,7 +33,7 @@ def sums(d, counter):
     for r in csv.DictReader(open(fs[-1])):
         if r['Counter_Name'] != counter: continue
         k = r['Kernel_Name']
-        name = 'stream_extend' if 'stream_extend<false' in k else 'stream_shade' if 'stream_shade<false' in k else 'fused_render' if ('fused_render<' in k and 'false' in k) else None
+        name = 'stream_extend' if 'stream_extend<false' in k else 'stream_shade' if 'stream_shade<false' in k else 'fused_render' if re.search(r'fused_render<\d, false', k) else None   # (COUNT is the second argument; the third is the UV build)
         if not name: continue
         agg[name] += float(r['Counter_Value'])
         if (name, r['Dispatch_Id']) not in seen: seen.add((name, r['Dispatch_Id'])); n[name] += 1
