@@ -288,6 +288,93 @@ static tile_result render_tile(const built_scene& b, ref_camera cam, int x0, int
     return r;
 }
 
+// ---- the post stack on a given frame: shared by `post` (a rendered scene) and `post_raw` (a frame from a file) ----------------
+// The loop of camera::process_framebuffer_to_image (camera.hpp:701-780), restated because camera.hpp is unbuildable here; every
+// call it makes is to the GENUINE post_processor / bloom_filter / linear_to_gamma.  The statistics are analyze_framebuffer's on the
+// INPUT frame, and apply_auto_exposure's answer with auto-exposure on (compensation 0.5 stops) and off.
+struct post_result {
+    std::vector<unsigned char> bytes;
+    image_statistics st;
+    double auto_on = 0, auto_off = 0;
+};
+
+static void frame_statistics(const post_processor& pp, const std::vector<color>& buffer, post_result& r) {
+    r.st = pp.analyze_framebuffer(buffer);
+    { post_processor q = pp; q.use_auto_exposure = true; q.exposure_compensation_stops = 0.5f; r.auto_on = q.apply_auto_exposure(r.st); }
+    r.auto_off = pp.apply_auto_exposure(r.st);
+}
+
+static post_result run_post(const post_processor& pp, const std::vector<color>& buffer, int W, int H, bool is_data_pass, bool apply_gamma) {
+    post_result r;
+    // camera.hpp:707-733
+    std::vector<color> work = buffer;
+    double ev = std::pow(2.0, (double)pp.exposure);
+    if (!is_data_pass && pp.use_bloom) {
+        for (auto& pix : work) pix *= ev;
+        std::vector<color> glow(work.size(), color(0.0, 0.0, 0.0));
+        bloom_filter bloom(pp.bloom_threshold, pp.bloom_intensity, pp.bloom_radius);
+        bloom.generate_bloom_overlay(work, glow, W, H, 1.0f);
+        double back = 1.0 / ev;
+        for (size_t i = 0; i < work.size(); ++i) work[i] = buffer[i] + (glow[i] * back);
+    } else {
+        work = buffer;
+    }
+    if (!is_data_pass && pp.use_sharpening) pp.apply_sharpening(work, W, H, pp.sharpen_amount);
+    r.bytes.resize((size_t)W * H * 3);
+    for (int j = 0; j < H; j++)
+        for (int i = 0; i < W; i++) {
+            size_t k = static_cast<size_t>(j) * W + i;
+            color c3 = work[k];
+            if (!is_data_pass) {
+                c3 *= ev;
+                float u = static_cast<float>(i) / (W - 1);
+                float v = static_cast<float>(j) / (H - 1);
+                c3 = pp.process(c3, u, v, render_pass::RGB);
+            } else {
+                c3 = color(std::clamp(c3.x(), 0.0, 1.0), std::clamp(c3.y(), 0.0, 1.0), std::clamp(c3.z(), 0.0, 1.0));
+                if (apply_gamma) c3 = linear_to_gamma(c3);
+            }
+            size_t idx = k * 3;
+            r.bytes[idx + 0] = static_cast<unsigned char>(255.999 * c3.x());
+            r.bytes[idx + 1] = static_cast<unsigned char>(255.999 * c3.y());
+            r.bytes[idx + 2] = static_cast<unsigned char>(255.999 * c3.z());
+        }
+    frame_statistics(pp, buffer, r);
+    return r;
+}
+
+static void write_post_result(const std::string& out, const post_result& r, int W, int H, bool with_bytes) {
+    if (with_bytes) write_npy(out + "_rgb8.npy", "|u1", {(size_t)H, (size_t)W, 3}, r.bytes.data(), r.bytes.size());
+    std::vector<int32_t> hist(r.st.histogram, r.st.histogram + 256);
+    write_npy(out + "_hist.npy", "<i4", {256}, hist.data(), hist.size() * 4);
+}
+
+// the tail of the JSON line of `post` / `post_raw`: every parameter and the statistics.  A non-finite statistic is printed as a
+// string ("inf", "-inf", "nan") so that the line stays JSON.
+static std::string json_num(double v, const char* fmt) {
+    char buf[64];
+    if (std::isfinite(v)) std::snprintf(buf, sizeof buf, fmt, v);
+    else std::snprintf(buf, sizeof buf, "\"%s\"", std::isnan(v) ? "nan" : (v > 0 ? "inf" : "-inf"));
+    return buf;
+}
+static void print_post_stats(const post_result& r) {
+    std::printf("\"average_luminance\": %s, \"max_luminance\": %s, \"auto_exposure_on\": %s, \"auto_exposure_off\": %s}\n",
+                json_num(r.st.average_luminance, "%.9g").c_str(), json_num(r.st.max_luminance, "%.9g").c_str(), json_num(r.auto_on, "%.17g").c_str(),
+                json_num(r.auto_off, "%.17g").c_str());
+}
+static void print_post_meta(const post_processor& pp, bool is_data_pass, bool apply_gamma, const post_result& r) {
+    std::printf("\"is_data_pass\": %d, \"apply_gamma\": %d, "
+                "\"exposure\": %.9g, \"saturation\": %.9g, \"contrast\": %.9g, \"hue_shift\": %.9g, \"vignette_intensity\": %.9g, "
+                "\"bloom_threshold\": %.9g, \"bloom_intensity\": %.9g, \"bloom_radius\": %d, \"color_balance\": [%.17g, %.17g, %.17g], "
+                "\"sharpen_amount\": %.17g, \"use_aces_tone_mapping\": %d, \"use_bloom\": %d, \"use_sharpening\": %d, "
+                "\"debug\": [%d, %d, %d, %d, %d], ",
+                (int)is_data_pass, (int)apply_gamma, pp.exposure, pp.saturation, pp.contrast, pp.hue_shift,
+                pp.vignette_intensity, pp.bloom_threshold, pp.bloom_intensity, pp.bloom_radius, pp.color_balance.x(), pp.color_balance.y(),
+                pp.color_balance.z(), pp.sharpen_amount, (int)pp.use_aces_tone_mapping, (int)pp.use_bloom, (int)pp.use_sharpening,
+                (int)pp.debug.red, (int)pp.debug.green, (int)pp.debug.blue, (int)pp.debug.luminance, (int)pp.debug.bvh);
+    print_post_stats(r);
+}
+
 static int usage() {
     std::fprintf(stderr,
                  "usage:\n"
@@ -297,6 +384,7 @@ static int usage() {
                  "  zenith_ref aov    <scene> <x0> <y0> <w> <h> <zmax> <out_prefix> - [a0 a1 a2 a3]\n"
                  "  zenith_ref passes <scene> <x0> <y0> <w> <h> <spp|0> <out_prefix> [a0 a1 a2 a3]\n"
                  "  zenith_ref post   <scene> <preset 0-7> <out_prefix> [spp]\n"
+                 "  zenith_ref post_raw <frame.bin> <w> <h> <out_prefix> [22 parameters]\n"
                  "  zenith_ref kat    <scene> hits|tex|bg|cam <in.bin> <n> <out_prefix>\n"
                  "  zenith_ref texels <w> <h> <out.npy>\n");
     return 2;
@@ -442,58 +530,52 @@ int main(int argc, char** argv) {
             case 7: is_data_pass = true; apply_gamma = false; break;
             default: return usage();
         }
-        // camera.hpp:707-733
-        std::vector<color> work = buffer;
-        double ev = std::pow(2.0, (double)pp.exposure);
-        if (!is_data_pass && pp.use_bloom) {
-            for (auto& pix : work) pix *= ev;
-            std::vector<color> glow(work.size(), color(0.0, 0.0, 0.0));
-            bloom_filter bloom(pp.bloom_threshold, pp.bloom_intensity, pp.bloom_radius);
-            bloom.generate_bloom_overlay(work, glow, W, H, 1.0f);
-            double back = 1.0 / ev;
-            for (size_t i = 0; i < work.size(); ++i) work[i] = buffer[i] + (glow[i] * back);
-        } else {
-            work = buffer;
-        }
-        if (!is_data_pass && pp.use_sharpening) pp.apply_sharpening(work, W, H, pp.sharpen_amount);
-        std::vector<unsigned char> bytes((size_t)W * H * 3);
-        for (int j = 0; j < H; j++)
-            for (int i = 0; i < W; i++) {
-                size_t k = static_cast<size_t>(j) * W + i;
-                color c3 = work[k];
-                if (!is_data_pass) {
-                    c3 *= ev;
-                    float u = static_cast<float>(i) / (W - 1);
-                    float v = static_cast<float>(j) / (H - 1);
-                    c3 = pp.process(c3, u, v, render_pass::RGB);
-                } else {
-                    c3 = color(std::clamp(c3.x(), 0.0, 1.0), std::clamp(c3.y(), 0.0, 1.0), std::clamp(c3.z(), 0.0, 1.0));
-                    if (apply_gamma) c3 = linear_to_gamma(c3);
-                }
-                size_t idx = k * 3;
-                bytes[idx + 0] = static_cast<unsigned char>(255.999 * c3.x());
-                bytes[idx + 1] = static_cast<unsigned char>(255.999 * c3.y());
-                bytes[idx + 2] = static_cast<unsigned char>(255.999 * c3.z());
-            }
-        image_statistics st = pp.analyze_framebuffer(buffer);
-        double auto_on; { post_processor q = pp; q.use_auto_exposure = true; q.exposure_compensation_stops = 0.5f; auto_on = q.apply_auto_exposure(st); }
-        double auto_off = pp.apply_auto_exposure(st);
+        post_result r = run_post(pp, buffer, W, H, is_data_pass, apply_gamma);
         write_npy(out + "_frame.npy", "<f8", {(size_t)H, (size_t)W, 3}, mean.data(), mean.size() * 8);
-        write_npy(out + "_rgb8.npy", "|u1", {(size_t)H, (size_t)W, 3}, bytes.data(), bytes.size());
-        std::vector<int32_t> hist(st.histogram, st.histogram + 256);
-        write_npy(out + "_hist.npy", "<i4", {256}, hist.data(), hist.size() * 4);
-        std::printf("{\"scene\": \"%s\", \"preset\": %d, \"w\": %d, \"h\": %d, \"spp\": %d, \"is_data_pass\": %d, \"apply_gamma\": %d, "
-                    "\"exposure\": %.9g, \"saturation\": %.9g, \"contrast\": %.9g, \"hue_shift\": %.9g, \"vignette_intensity\": %.9g, "
-                    "\"bloom_threshold\": %.9g, \"bloom_intensity\": %.9g, \"bloom_radius\": %d, \"color_balance\": [%.17g, %.17g, %.17g], "
-                    "\"sharpen_amount\": %.17g, \"use_aces_tone_mapping\": %d, \"use_bloom\": %d, \"use_sharpening\": %d, "
-                    "\"debug\": [%d, %d, %d, %d, %d], \"average_luminance\": %.9g, \"max_luminance\": %.9g, \"auto_exposure_on\": %.17g, "
-                    "\"auto_exposure_off\": %.17g}\n",
-                    argv[2], preset, W, H, spp, (int)is_data_pass, (int)apply_gamma, pp.exposure, pp.saturation, pp.contrast, pp.hue_shift,
-                    pp.vignette_intensity, pp.bloom_threshold, pp.bloom_intensity, pp.bloom_radius, pp.color_balance.x(), pp.color_balance.y(),
-                    pp.color_balance.z(), pp.sharpen_amount, (int)pp.use_aces_tone_mapping, (int)pp.use_bloom, (int)pp.use_sharpening,
-                    (int)pp.debug.red, (int)pp.debug.green, (int)pp.debug.blue, (int)pp.debug.luminance, (int)pp.debug.bvh,
-                    st.average_luminance, st.max_luminance, auto_on, auto_off);
+        write_post_result(out, r, W, H, true);
+        std::printf("{\"scene\": \"%s\", \"preset\": %d, \"w\": %d, \"h\": %d, \"spp\": %d, ", argv[2], preset, W, H, spp);
+        print_post_meta(pp, is_data_pass, apply_gamma, r);
         cleanup(b);
+        return 0;
+    }
+
+    if (cmd == "post_raw" && (argc == 6 || argc == 28)) {
+        // zenith_ref post_raw <frame.bin> <w> <h> <out_prefix> [parameters]: the same post stack as `post` on a frame given as h*w*3 raw
+        // little-endian doubles.  The 22 parameters are the fields of zr_post_params in their order (exposure saturation contrast hue_shift
+        // vignette_intensity bloom_threshold bloom_intensity bloom_radius color_balance[3] sharpen_amount use_aces_tone_mapping use_bloom
+        // use_sharpening debug red green blue luminance bvh), then is_data_pass and apply_gamma; numbers go through strtod, so hexadecimal
+        // floats arrive exactly.  Without parameters only the statistics of analyze_framebuffer are computed (any w, h >= 1).
+        const int W = iarg(3, 0), H = iarg(4, 0);
+        if (W < 1 || H < 1) return usage();
+        std::string out = argv[5];
+        std::vector<double> in((size_t)W * H * 3);
+        { FILE* f = std::fopen(argv[2], "rb"); if (!f || std::fread(in.data(), 8, in.size(), f) != in.size()) { std::fprintf(stderr, "cannot read %s\n", argv[2]); return 2; } std::fclose(f); }
+        std::vector<color> buffer((size_t)W * H);
+        for (size_t i = 0; i < buffer.size(); i++) buffer[i] = color(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+        post_processor pp;
+        if (argc == 6) {
+            post_result r;
+            frame_statistics(pp, buffer, r);
+            write_post_result(out, r, W, H, false);
+            std::printf("{\"w\": %d, \"h\": %d, \"exposure\": %.9g, ", W, H, pp.exposure);
+            print_post_stats(r);
+            return 0;
+        }
+        if (W < 2 || H < 2) return usage();
+        auto darg = [&](int k) { return std::strtod(argv[6 + k], nullptr); };
+        auto barg = [&](int k) { return std::atoi(argv[6 + k]) != 0; };
+        pp.exposure = (float)darg(0); pp.saturation = (float)darg(1); pp.contrast = (float)darg(2); pp.hue_shift = (float)darg(3);
+        pp.vignette_intensity = (float)darg(4); pp.bloom_threshold = (float)darg(5); pp.bloom_intensity = (float)darg(6);
+        pp.bloom_radius = std::atoi(argv[6 + 7]);
+        pp.color_balance = vec3(darg(8), darg(9), darg(10));
+        pp.sharpen_amount = darg(11);
+        pp.use_aces_tone_mapping = barg(12); pp.use_bloom = barg(13); pp.use_sharpening = barg(14);
+        pp.debug.red = barg(15); pp.debug.green = barg(16); pp.debug.blue = barg(17); pp.debug.luminance = barg(18); pp.debug.bvh = barg(19);
+        const bool is_data_pass = barg(20), apply_gamma = barg(21);
+        post_result r = run_post(pp, buffer, W, H, is_data_pass, apply_gamma);
+        write_post_result(out, r, W, H, true);
+        std::printf("{\"w\": %d, \"h\": %d, ", W, H);
+        print_post_meta(pp, is_data_pass, apply_gamma, r);
         return 0;
     }
 

@@ -26,6 +26,10 @@ __device__ __forceinline__ double luminance(C3 c) { return 0.2126 * c.x + 0.7152
 __device__ __forceinline__ double clamp01(double v) { return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); }       // std::clamp(v, 0.0, 1.0)
 __device__ __forceinline__ double gamma22(double v) { return v > 0 ? pow(v, 1.0 / 2.2) : 0.0; }           // common.hpp:70-75
 
+// static_cast<unsigned char>(255.999 * v) of camera.hpp:768-770.  v lies in [0, 1] or is NaN (a data pass without gamma clamps a NaN to NaN); C++ leaves
+// the conversion of a NaN undefined and the reference binary's gives 0: decided here, not by the compiler.
+__device__ __forceinline__ unsigned char to_byte(double v) { const double s = 255.999 * v; return s == s ? (unsigned char)s : (unsigned char)0; }
+
 // bright pass of bloom_filter::generate_bloom_overlay with exposure = 1.0f on the EV-scaled buffer (camera.hpp:714-722, bloom.hpp:28-39)
 __global__ void post_bright(const double* __restrict__ frame, size_t n, double ev, float threshold, float intensity, double* __restrict__ bright) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -189,9 +193,9 @@ __global__ void post_final(const double* __restrict__ in, int W, int H, double e
         c.x = clamp01(c.x); c.y = clamp01(c.y); c.z = clamp01(c.z);
         if (apply_gamma) { c.x = gamma22(c.x); c.y = gamma22(c.y); c.z = gamma22(c.z); }
     }
-    out[3 * i] = (unsigned char)(255.999 * c.x);
-    out[3 * i + 1] = (unsigned char)(255.999 * c.y);
-    out[3 * i + 2] = (unsigned char)(255.999 * c.z);
+    out[3 * i] = to_byte(c.x);
+    out[3 * i + 1] = to_byte(c.y);
+    out[3 * i + 2] = to_byte(c.z);
 }
 
 // analyze_framebuffer (color_processing.hpp:150-183): per-block partial sums; the host adds the partials in block order
@@ -208,10 +212,15 @@ __global__ __launch_bounds__(256) void post_analyze(const double* __restrict__ f
         const float lum = (float)luminance(ld(frame, i));
         mx = lum;
         const float cl = fmaxf(0.0001f, lum);
-        const float l2 = log2f(cl);
+        // The correctly rounded float log2: the device's log2f is good to one ulp, the host libm's is exact on all but a few floats in ten
+        // thousand.  On a frame of equal luminances (everything below the floor) that ulp is systematic and moved the mean by 9 float spacings.
+        const float l2 = (float)log2((double)cl);
         lg = (double)l2;
         const float nl = (l2 - (-10.0f)) / 20.0f;
-        int bin = (int)(nl * 255.0f);
+        // An infinite luminance makes nl infinite, and C++ leaves the conversion of that to int undefined: the reference binary's gives INT_MIN,
+        // which the clamp sends to bin 0 (the device's would saturate to bin 255).  Decided here, not by the compiler.
+        const float scaled = nl * 255.0f;
+        int bin = isfinite(scaled) ? (int)scaled : 0;
         bin = bin < 0 ? 0 : (bin > 255 ? 255 : bin);
         atomicAdd(&s_hist[bin], 1);
     }

@@ -19,6 +19,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))   # tests/post_model.py: the edge inputs of the post stack
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = os.path.join(ROOT, "oracle", "_ref", "zenith_ref")
 
@@ -89,6 +90,42 @@ POSTS = {
     "post_cfg1": ("cfg1", 4, [0, 1, 2, 3, 4, 5, 6, 7]),
     "post_mix0": ("mix0", 8, [1, 3]),
 }
+# the post stack at its edges is a family of its own, "post_edges": make_post_edges() below, inputs from tests/post_model.py
+
+
+def make_post_edges(tmp):
+    """post_edges.npz: the post stack at its edges.  tests/post_model.py describes frames, parameter sets and cases; `zenith_ref post_raw` runs the genuine
+    post_processor / bloom_filter on each.  Hundreds of tiny arrays would cost more in archive headers than in data, so they are packed: `frames` holds
+    every input frame end to end, `rgb8` the 8-bit image of every case, `hist` one histogram row per frame; meta lists per frame its shape, offset, row,
+    average / maximum luminance and both auto-exposure values, and per case its frame, parameters and offset."""
+    import post_model as pm
+    meta = {"cases": [], "frames": {}}
+    frames = dict(pm.post_frames())
+    packed_frames, packed_rgb8, hists, at = [], [], [], 0
+    for name, frame in list(frames.items()) + list(pm.stat_frames().items()):
+        pre = os.path.join(tmp, "pe_" + name)
+        np.ascontiguousarray(frame, dtype="<f8").tofile(pre + ".bin")
+        m = run("post_raw", pre + ".bin", frame.shape[1], frame.shape[0], pre)
+        meta["frames"][name] = dict({k: m[k] for k in ("average_luminance", "max_luminance", "auto_exposure_on", "auto_exposure_off", "exposure")},
+                                    shape=list(frame.shape), offset=at, row=len(hists))
+        packed_frames.append(frame.ravel()); at += frame.size
+        hists.append(np.load(pre + "_hist.npy"))
+    at = 0
+    for name, fname, p, data, gamma in pm.cases():
+        frame = frames[fname]
+        pre = os.path.join(tmp, "pe_case_" + name)
+        m = run("post_raw", os.path.join(tmp, "pe_" + fname + ".bin"), frame.shape[1], frame.shape[0], pre, *pm.ref_arguments(p, data, gamma))
+        for k in pm.FLOAT_FIELDS:   # the harness parsed what was meant
+            assert np.float32(m[k]) == np.float32(p[k]), (name, k, m[k], p[k])
+        assert m["bloom_radius"] == p["bloom_radius"] and m["debug"] == p["debug"] and m["is_data_pass"] == int(data) and m["apply_gamma"] == int(gamma)
+        assert m["color_balance"] == p["color_balance"] and m["sharpen_amount"] == p["sharpen_amount"]
+        rgb8 = np.load(pre + "_rgb8.npy")
+        assert rgb8.shape == frame.shape
+        meta["cases"].append({"name": name, "frame": fname, "params": p, "is_data_pass": data, "apply_gamma": gamma, "offset": at})
+        packed_rgb8.append(rgb8.ravel()); at += rgb8.size
+    out = os.path.join(HERE, "post_edges.npz")
+    np.savez_compressed(out, meta=np.array(json.dumps(meta)), frames=np.concatenate(packed_frames), rgb8=np.concatenate(packed_rgb8), hist=np.stack(hists))
+    print("post_edges", len(meta["cases"]), "cases,", len(meta["frames"]), "frames,", os.path.getsize(out), "bytes")
 
 
 def kat_inputs():
@@ -310,6 +347,8 @@ def main():
                 arrays["hist"] = np.load(pre + "_hist.npy")
             np.savez_compressed(os.path.join(HERE, name + ".npz"), meta=np.array(json.dumps(metas)), **arrays)
             print(name, [m["preset"] for m in metas])
+        if not want or "post_edges" in want:
+            make_post_edges(tmp)
         if not want or "refdemo" in want:
             from refdemo_assets import store
             store()   # tests/golden/refdemo_assets.npz: the images tests/test_refdemo.py gives the scene code
