@@ -683,12 +683,12 @@ __global__ void k_pair_leaf_root(const BNode* __restrict__ bn, const uint32_t* _
 }
 
 // ---- 7. primitive records (the host's Flattener::put_* rules) ------------------------------------------------------------------
-__device__ void put_triangle_raw(const BuildPrimOut& out, size_t di, const double* v, const double* nn, uint32_t mat, bool force_front) {
+__device__ void put_triangle_raw(const BuildPrimOut& out, size_t di, const double* v, const double* nn, uint32_t mat, uint32_t refaced) {
     double* tv = out.tri_v + di * ZR_TRI_STRIDE;
     double* t = out.tri_s + di * 20;
     for (int k = 0; k < 9; k++) { tv[k] = v[k]; t[k] = v[k]; t[9 + k] = nn[k]; }
     t[18] = __longlong_as_double((long long)(unsigned long long)mat);
-    t[19] = __longlong_as_double(force_front ? 1ll : 0ll);
+    t[19] = __longlong_as_double(refaced ? (refaced % 2 ? 1ll : 3ll) : 0ll);   // bit 0: under translate / rotate_y wrappers, bit 1: an even number of them
 }
 // a stored triangle's texture coordinates travel with it, unchanged (Flattener::put_triangle_uv)
 __device__ void put_triangle_uv(const BuildSceneIn& in, const BuildPrimOut& out, size_t di, uint32_t idx) {
@@ -720,7 +720,7 @@ __global__ __launch_bounds__(256) void k_emit(BuildSceneIn in, const zr_object* 
         double v[9], nn[9];
         for (int k = 0; k < 9; k++) { v[k] = in.tri_v[(size_t)o.index * 9 + k]; nn[k] = in.tri_n[(size_t)o.index * 9 + k]; }
         uint32_t mat = in.tri_mat[o.index];
-        bool force_front = false;
+        uint32_t refaced = 0;
         for (int k = (int)o.chain_count - 1; k >= 0; k--) {
             const zr_xform_op op = in.ops[o.chain_first + k];
             const double sn = op.a[0], co = op.a[1];
@@ -737,25 +737,25 @@ __global__ __launch_bounds__(256) void k_emit(BuildSceneIn in, const zr_object* 
                     default: break;
                 }
             }
-            if (op.kind == ZR_OP_TRANSLATE || op.kind == ZR_OP_ROTATE_Y) force_front = true;
+            if (op.kind == ZR_OP_TRANSLATE || op.kind == ZR_OP_ROTATE_Y) refaced++;
             if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
         }
-        put_triangle_raw(out, di, v, nn, mat, force_front);
+        put_triangle_raw(out, di, v, nn, mat, refaced);
         put_triangle_uv(in, out, di, o.index);
     } else if (bk == 3) {   // put_baked_sphere: uniform scale / translate / material_instance
         const double* q = in.spheres + (size_t)o.index * 4;
         double c[3] = {q[0], q[1], q[2]}, r = fmax(0.0, q[3]);
         uint32_t mat = in.sphere_mat[o.index];
-        bool force_front = false;
+        bool refaced = false;   // (at most one translate: classify_object)
         for (int k = (int)o.chain_count - 1; k >= 0; k--) {
             const zr_xform_op op = in.ops[o.chain_first + k];
             if (op.kind == ZR_OP_SCALE) { c[0] *= op.a[0]; c[1] *= op.a[0]; c[2] *= op.a[0]; r *= op.a[0]; }
-            else if (op.kind == ZR_OP_TRANSLATE) { c[0] += op.a[0]; c[1] += op.a[1]; c[2] += op.a[2]; force_front = true; }
+            else if (op.kind == ZR_OP_TRANSLATE) { c[0] += op.a[0]; c[1] += op.a[1]; c[2] += op.a[2]; refaced = true; }
             else if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
         }
         double* d = out.spheres + di * 4;
         d[0] = c[0]; d[1] = c[1]; d[2] = c[2]; d[3] = r;
-        out.sphere_mat[di] = force_front ? (mat | 0x80000000u) : mat;
+        out.sphere_mat[di] = refaced ? (mat | 0x80000000u) : mat;
     } else if (bk == 4) {   // put_pcube: cube -> [scale] -> [rotate_y] -> translate in one record
         const double* q = in.cubes + (size_t)o.index * 12;
         double rec[ZR_PCUBE_STRIDE] = {q[0], q[1], q[2], q[3], q[4], q[5], 0, 0, 0, 0, 1, 0, 1, 1, 1, 0};

@@ -51,6 +51,15 @@ __device__ __forceinline__ void set_face(Rec& rec, V3 rd, V3 outward) {  // hitt
     rec.front = dot(rd, outward) < 0;
     rec.n = rec.front ? outward : -outward;
 }
+// A primitive stored in world space from under translate / rotate_y wrappers (zr_flatten.h put_baked_triangle / put_baked_sphere): each of them calls
+// set_face_normal again on the normal the primitive has already turned against the ray (translate.hpp:29, rotate_y.hpp:70).  With x = dot(d, outward) of the
+// primitive's own call: for x != 0 the turned normal faces the ray, so every later call answers front_face = true and keeps it; for x == 0 (or NaN) the first
+// call leaves -outward with front_face = false, and every later one finds dot == -0 or +0, answers false again and flips the normal once more — after an odd
+// number of wrappers the record holds +outward, after an even number -outward.
+__device__ __forceinline__ void reface(bool& front, V3& n, double x, V3 outward, bool even) {
+    front = x < 0 || x > 0;
+    if (!front && !even) n = outward;
+}
 
 struct Rng {
     uint64_t key, k;
@@ -574,16 +583,20 @@ __device__ inline void sphere_rec(const DScene& sc, uint32_t idx, const Ray& r, 
     V3 outward = vdiv(rec.p - center, s[3]);
     set_face(rec, r.d, outward);
     rec.mat = sc.sphere_mat[idx];
-    if (rec.mat != 0xFFFFFFFFu && (rec.mat & 0x80000000u)) { rec.mat &= 0x7FFFFFFFu; rec.front = true; }   // baked from under a translate (zr_flatten.h)
-    if (!full && !mat_needs_uv(sc, rec.mat)) { rec.u = 0; rec.v = 0; rec.tan = mk(0, 0, 0); rec.bit = mk(0, 0, 0); return; }
-    double theta = acos(-outward.y);
-    double phi = atan2(-outward.z, outward.x) + 3.14159265358979323846;
-    rec.u = phi / (2 * 3.14159265358979323846);
-    rec.v = theta / 3.14159265358979323846;
-    rec.tan = cross(mk(0, 1, 0), rec.n);
-    if (len2(rec.tan) < 0.001) rec.tan = cross(mk(0, 0, 1), rec.n);
-    rec.tan = unit(rec.tan);
-    rec.bit = cross(rec.n, rec.tan);
+    const bool refaced = rec.mat != 0xFFFFFFFFu && (rec.mat & 0x80000000u);   // baked from under ONE translate (zr_flatten.h)
+    if (refaced) rec.mat &= 0x7FFFFFFFu;
+    if (!full && !mat_needs_uv(sc, rec.mat)) { rec.u = 0; rec.v = 0; rec.tan = mk(0, 0, 0); rec.bit = mk(0, 0, 0); }
+    else {
+        double theta = acos(-outward.y);
+        double phi = atan2(-outward.z, outward.x) + 3.14159265358979323846;
+        rec.u = phi / (2 * 3.14159265358979323846);
+        rec.v = theta / 3.14159265358979323846;
+        rec.tan = cross(mk(0, 1, 0), rec.n);
+        if (len2(rec.tan) < 0.001) rec.tan = cross(mk(0, 0, 1), rec.n);
+        rec.tan = unit(rec.tan);
+        rec.bit = cross(rec.n, rec.tan);
+    }
+    if (refaced) reface(rec.front, rec.n, dot(r.d, outward), outward, false);   // last: sphere::hit makes its tangent frame from the normal of its own call
 }
 
 // ---- per-vertex texture coordinates of triangles (DScene::tri_uv) -------------------------------------------------------
@@ -635,7 +648,8 @@ __device__ inline void triangle_rec(const DScene& sc, uint32_t idx, const Ray& r
     rec.p = p;
     rec.mat = (uint32_t)__double_as_longlong(v[18]);
     set_face(rec, r.d, smooth);
-    if ((uint32_t)__double_as_longlong(v[19]) & 1u) rec.front = true;   // baked from under a translate / rotate_y (zr_flatten.h)
+    const uint32_t refaced = (uint32_t)__double_as_longlong(v[19]);   // baked from under translate / rotate_y wrappers (zr_flatten.h): bit 0 any, bit 1 an even number
+    if (refaced & 1u) reface(rec.front, rec.n, dot(r.d, smooth), smooth, (refaced & 2u) != 0);
     // u, v, tangent, bitangent are not written by triangle::hit: fresh-record values
     rec.u = 0; rec.v = 0; rec.tan = mk(0, 0, 0); rec.bit = mk(0, 0, 0);
 }
@@ -903,6 +917,16 @@ __device__ inline V3 bumped_normal(const DScene& sc, const Rec& rec, uint32_t bu
 
 // ---- materials --------------------------------------------------------------------------------------
 __device__ inline V3 reflect(V3 v, V3 n) { return v - (2 * dot(v, n)) * n; }
+// dot(a, b) as the reference rounds it: every product rounded, then the sums, no fused multiply-add (vec3.hpp's u0 v0 + u1 v1 + u2 v2).  Under
+// -ffp-contract=fast the backend fuses whatever multiply feeds an add, `#pragma clang fp contract(off)` notwithstanding; an empty asm on each product
+// hides the multiply from it and emits nothing (three v_mul_f64 and two v_add_f64).
+__device__ __forceinline__ double rounded(double x) { asm("" : "+v"(x)); return x; }
+__device__ __forceinline__ double dot_rn(V3 a, V3 b) { return rounded(a.x * b.x) + rounded(a.y * b.y) + rounded(a.z * b.z); }
+// metal::scatter (material.hpp:139-149) on a ray exactly perpendicular to the normal — a tangent ray on a sphere, a bent vertex normal: dot(v, n) = q q' - q q'
+// is exactly 0 in the reference, the reflection is v itself, dot(reflected, n) is 0 again and the ray is absorbed.  Contracted, the same dot is the rounding
+// error of one product, ~1e-17 of either sign, and that sign decided.  So: the contracted value as ever (the frames' last bits stay what they were) unless
+// the reference's own arithmetic cancels to 0, and the decision itself from the uncontracted dot.
+__device__ __forceinline__ V3 reflect_metal(V3 v, V3 n) { const double d = dot_rn(v, n) == 0 ? 0.0 : dot(v, n); return v - (2 * d) * n; }
 
 __device__ inline V3 emitted(const DScene& sc, const Rec& rec) {  // material.hpp:12-14, 261-263
     if (rec.mat >= sc.n_mats) return mk(0, 0, 0);
@@ -950,12 +974,12 @@ __device__ inline bool scatter(const DScene& sc, const Ray& rin, const Rec& rec,
             return true;
         }
         case ZR_MAT_METAL: {  // material.hpp:129-151
-            V3 refl = reflect(ud, wn);
+            V3 refl = reflect_metal(ud, wn);
             V3 dir = unit(refl + (m.param * ruv));
             out.o = rec.p + (0.0001 * rec.n);
             out.d = dir;
             att = tv;
-            return dot(dir, rec.n) > 0;
+            return dot_rn(dir, rec.n) > 0;
         }
         case ZR_MAT_DIELECTRIC: {  // material.hpp:192-224, 237-241
             att = mk(m.tint[0], m.tint[1], m.tint[2]);
@@ -1004,12 +1028,12 @@ __device__ __forceinline__ double pow5(double x) { const double x2 = x * x; retu
 __device__ __forceinline__ void lean_rec(const DScene& sc, uint32_t kind, uint32_t idx, const Ray& r, double t, RecL& rec) {
     rec.p = at(r, t);
     V3 outward;
-    bool force_front = false;
+    uint32_t refaced = 0;   // bit 0: stored in world space from under translate / rotate_y wrappers, bit 1: an even number of them (reface())
     if (kind == ZR_PRIM_SPHERE) {   // sphere.hpp:42-46
         const double* s = sc.spheres + (size_t)idx * 4;
         outward = vdiv(rec.p - mk(s[0], s[1], s[2]), s[3]);
         rec.mat = sc.sphere_mat[idx];
-        if (rec.mat != 0xFFFFFFFFu && (rec.mat & 0x80000000u)) { rec.mat &= 0x7FFFFFFFu; force_front = true; }
+        if (rec.mat != 0xFFFFFFFFu && (rec.mat & 0x80000000u)) { rec.mat &= 0x7FFFFFFFu; refaced = 1; }
     } else {                        // triangle.hpp:40-79
         const double* v = sc.tri_s + (size_t)idx * 20;
         const double* nn = v + 9;
@@ -1023,11 +1047,12 @@ __device__ __forceinline__ void lean_rec(const DScene& sc, uint32_t kind, uint32
         double w0 = 1.0 - u - w_;
         outward = unit(w0 * ld3(nn) + u * ld3(nn + 3) + w_ * ld3(nn + 6));
         rec.mat = (uint32_t)__double_as_longlong(v[18]);
-        force_front = ((uint32_t)__double_as_longlong(v[19]) & 1u) != 0;
+        refaced = (uint32_t)__double_as_longlong(v[19]);
     }
-    rec.front = dot(r.d, outward) < 0;   // hittable.hpp:22-25
+    const double x = dot(r.d, outward);
+    rec.front = x < 0;   // hittable.hpp:22-25
     rec.n = rec.front ? outward : -outward;
-    if (force_front) rec.front = true;
+    if (refaced & 1u) reface(rec.front, rec.n, x, outward, (refaced & 2u) != 0);
 }
 __device__ __forceinline__ V3 lean_color(const DScene& sc, uint32_t tex) { const zr_texture& t = sc.texs[tex]; return mk(t.color[0], t.color[1], t.color[2]); }
 // emitted + scatter of the hit's material in one look at it
@@ -1050,12 +1075,12 @@ __device__ __forceinline__ bool lean_shade(const DScene& sc, const Ray& rin, con
         return true;
     }
     if (kind == ZR_MAT_METAL) {  // material.hpp:129-151
-        V3 refl = reflect(ud, rec.n);
+        V3 refl = reflect_metal(ud, rec.n);
         V3 dir = unit(refl + (m.param * ruv));
         out.o = rec.p + (0.0001 * rec.n);
         out.d = dir;
         att = lean_color(sc, m.tex);
-        return dot(dir, rec.n) > 0;
+        return dot_rn(dir, rec.n) > 0;
     }
     if (kind == ZR_MAT_DIELECTRIC) {  // material.hpp:192-224, 237-241
         att = mk(m.tint[0], m.tint[1], m.tint[2]);

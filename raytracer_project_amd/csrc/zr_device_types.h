@@ -72,7 +72,7 @@ struct DScene {
     const double* tri_v;        // 9 per triangle
     const double* tri_s;        // (then the texture coordinates: tri_uv_at) shading record, 20 doubles (160 B, two 128-B lines at any 32-B phase) per triangle:
                                 // [0..8] vertices, [9..17] vertex normals (need not be unit), [18] low word = material id,
-                                // [19] low word bit 0 = front_face forced true (triangle baked from under a translate / rotate_y)
+                                // [19] low word bit 0 = baked from under translate / rotate_y wrappers, bit 1 = an even number of them (zr_device.h reface())
     const double* cubes;        // 6 per cube: half extents, centre
     const uint32_t* cube_mat;
     const double* pcubes;       // placed cubes, ZR_PCUBE_STRIDE (16) per cube: half extents, centre | translate offset | rotate_y sin, cos, has_rotation | scale x, y, z, has_scale

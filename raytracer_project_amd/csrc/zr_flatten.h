@@ -87,15 +87,15 @@ inline void classify_object(const SceneInput& s, const zr_object& o, bool bake, 
         if (ok) { baked = 1; kind = ZR_PRIM_TRIANGLE; }
     }
     if (o.type == ZR_PRIM_SPHERE) {   // see Flattener::put_baked_sphere
-        bool ok = true, moved = false; uint32_t mat = s.sphere_mat[o.index];
+        bool ok = true, moved = false; uint32_t mat = s.sphere_mat[o.index], translates = 0;
         for (int q = (int)o.chain_count - 1; q >= 0 && ok; q--) {
             const zr_xform_op& op = s.ops[o.chain_first + q];
             if (op.kind == ZR_OP_SCALE) { ok = op.a[0] > 0 && op.a[0] == op.a[1] && op.a[1] == op.a[2]; moved = true; }
-            else if (op.kind == ZR_OP_TRANSLATE) moved = true;
+            else if (op.kind == ZR_OP_TRANSLATE) { moved = true; translates++; }
             else if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
             else ok = false;
         }
-        if (ok && moved && mat < 0x7FFFFFFFu) { baked = 3; kind = ZR_PRIM_SPHERE; }
+        if (ok && moved && translates <= 1 && mat < 0x7FFFFFFFu) { baked = 3; kind = ZR_PRIM_SPHERE; }
     }
     if (o.type == ZR_PRIM_CUBE) {   // see Flattener::put_pcube: [translate], [translate, rotate_y], each optionally followed by a scale — outermost first
         int pat = 0; bool ok = true;   // 0 nothing yet, 1 translate seen, 2 translate then rotate_y seen, 3 ... then a scale (the innermost wrapper)
@@ -402,17 +402,17 @@ struct Flattener {
         d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = std::fmax(0, q[3]);  // sphere.hpp:9
         sphere_mat[di] = mat != kKeepMaterial ? mat : s.sphere_mat[idx];
     }
-    void put_triangle_raw(size_t di, const double* v, const double* nn, uint32_t mat, bool force_front) {
+    void put_triangle_raw(size_t di, const double* v, const double* nn, uint32_t mat, uint32_t refaced) {
         std::memcpy(&tri_v[di * ZR_TRI_STRIDE], v, 72);
         double* t = &tri_s[di * ZR_TRI_SHADE_DOUBLES];
         std::memcpy(t, v, 72); std::memcpy(t + 9, nn, 72);
-        uint64_t mbits = mat, fbits = force_front ? 1u : 0u;
+        uint64_t mbits = mat, fbits = refaced ? (refaced % 2 ? 1u : 3u) : 0u;   // bit 0: under translate / rotate_y wrappers, bit 1: an even number of them
         std::memcpy(t + 18, &mbits, 8); std::memcpy(t + 19, &fbits, 8);
     }
     // a stored triangle's texture coordinates travel with it, unchanged (baked or not: they are no geometry)
     void put_triangle_uv(size_t di, uint32_t idx) { if (uv_base) std::memcpy(&tri_s[uv_base + di * 6], &s.tri_uv[(size_t)idx * 6], 48); }
     void put_triangle(size_t di, uint32_t idx) {
-        put_triangle_raw(di, &s.tri_v[(size_t)idx * 9], &s.tri_n[(size_t)idx * 9], s.tri_mat[idx], false);
+        put_triangle_raw(di, &s.tri_v[(size_t)idx * 9], &s.tri_n[(size_t)idx * 9], s.tri_mat[idx], 0);
         put_triangle_uv(di, idx);
     }
     void put_cube(size_t di, uint32_t idx, uint32_t mat) {
@@ -422,8 +422,10 @@ struct Flattener {
     // A triangle under a chain of translate / rotate_x,y,z / material_instance wrappers is stored in WORLD space as a bare
     // triangle: vertices and (un-normalised) vertex normals mapped object -> world with the wrappers' own forward maps
     // (translate.hpp:24-27, rotate_*.hpp hit(): the maps apply_op_rec uses for hit points), material = the outermost
-    // material_instance, plus a flag when the chain holds a translate or a rotate_y, which force front_face = true
-    // (SURVEY §8 a-17 quirk).  t is the same in both spaces (the wrappers do not normalise the transformed direction), so
+    // material_instance, plus how many translate / rotate_y wrappers the chain holds: each calls set_face_normal again on the
+    // normal the triangle has already turned against the ray, which answers front_face = true unless dot(d, normal) is exactly
+    // 0 (zr_device.h reface() restates both cases from the world-space dot product — the wrappers' maps are
+    // exact where sin and cos are 0 and 1, and elsewhere a dot product within rounding of 0 has no sign to agree on in either space).  t is the same in both spaces (the wrappers do not normalise the transformed direction), so
     // only the last bits of the hit differ from transforming the ray — and every mesh the reference's scenes place in the
     // world (model -> material_instance -> rotate -> translate) runs on the bare-triangle fast path instead of paying a
     // chain transform per candidate.  scale is excluded: it would change which triangles count as degenerate.
@@ -432,7 +434,7 @@ struct Flattener {
         std::memcpy(v, &s.tri_v[(size_t)o.index * 9], sizeof v);
         std::memcpy(nn, &s.tri_n[(size_t)o.index * 9], sizeof nn);
         uint32_t mat = s.tri_mat[o.index];
-        bool force_front = false;
+        uint32_t refaced = 0;
         for (int k = (int)o.chain_count - 1; k >= 0; k--) {   // innermost wrapper first, as the hit record travels outwards
             const zr_xform_op& op = s.ops[o.chain_first + k];
             const double sn = op.a[0], co = op.a[1];
@@ -449,29 +451,30 @@ struct Flattener {
                     default: break;
                 }
             }
-            if (op.kind == ZR_OP_TRANSLATE || op.kind == ZR_OP_ROTATE_Y) force_front = true;
+            if (op.kind == ZR_OP_TRANSLATE || op.kind == ZR_OP_ROTATE_Y) refaced++;
             if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
         }
-        put_triangle_raw(di, v, nn, mat, force_front);
+        put_triangle_raw(di, v, nn, mat, refaced);
         put_triangle_uv(di, o.index);
     }
     // A sphere under uniform scale / translate / material_instance wrappers (the demo scene's instanced spheres:
     // scale -> material_instance -> translate) is the sphere (c s + offset, r s): same t, same unit normal, same u/v and
-    // tangent (no rotation involved); bit 31 of its material word records the front_face = true a translate forces.
+    // tangent (no rotation involved); bit 31 of its material word records that a translate calls set_face_normal again on the turned
+    // normal (zr_device.h reface(); one bit: classify_object leaves a sphere under two or more translates to the interpreter).
     void put_baked_sphere(size_t di, const zr_object& o) {
         const double* q = &s.spheres[(size_t)o.index * 4];
         double c[3] = {q[0], q[1], q[2]}, r = std::fmax(0, q[3]);
         uint32_t mat = s.sphere_mat[o.index];
-        bool force_front = false;
+        bool refaced = false;
         for (int k = (int)o.chain_count - 1; k >= 0; k--) {
             const zr_xform_op& op = s.ops[o.chain_first + k];
             if (op.kind == ZR_OP_SCALE) { for (double& x : c) x *= op.a[0]; r *= op.a[0]; }
-            else if (op.kind == ZR_OP_TRANSLATE) { c[0] += op.a[0]; c[1] += op.a[1]; c[2] += op.a[2]; force_front = true; }
+            else if (op.kind == ZR_OP_TRANSLATE) { c[0] += op.a[0]; c[1] += op.a[1]; c[2] += op.a[2]; refaced = true; }
             else if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
         }
         double* d = &spheres[di * ZR_SPHERE_DOUBLES];
         d[0] = c[0]; d[1] = c[1]; d[2] = c[2]; d[3] = r;
-        sphere_mat[di] = force_front ? (mat | 0x80000000u) : mat;
+        sphere_mat[di] = refaced ? (mat | 0x80000000u) : mat;
     }
     // A cube under translate, or under rotate_y then translate, either with a scale as the innermost wrapper (material_instance wrappers
     // anywhere) — how every cube of the reference's scenes is placed (scene_management.hpp:132-139 and the scaled, turned instances of its

@@ -477,8 +477,128 @@ static inline void zr_build_kat0(zr_demo_scene& s, const std::string& tmpdir = "
     s.cam.defocus_angle = 2.0; s.cam.focus_dist = 17.0;
 }
 
+// "kat1": wrapper chains at their edges (translate, rotate_x / rotate_y / rotate_z, scale, material_instance, and constant_medium under them) for the
+// known-answer fixture tests/golden/kat_kat1.npz; tests/golden/make_golden.py kat1_inputs() places the rays and mirrors this layout.  Isolated objects,
+// one per cell of a grid with pitch 8 (cell k is centred at (8 (k % 10) - 36, 8 (k / 10) - 28, 8 ((k % 10 + k / 10) % 11) - 40): no two cells of a row or
+// of a column share their z, so an axis-parallel ray through one cell meets no other), every number a small integer or a dyadic fraction, opaque materials on cubes (glass on a cube is chaotic in the reference itself, DESIGN §1), glass and metal on wrapped spheres and
+// triangles so that front_face and the normal reach scatter.  Cubes are origin-centred under their wrappers (cube.hpp:45-58).
+// rotate_y builds its box with the inverse rotation (rotate_y.hpp:26-27) while this project bounds the true geometry: here rotate_y only ever holds a
+// child whose box is symmetric about the y axis, or turns by an angle of 0, where both boxes are the same.
+static inline void zr_build_kat1(zr_demo_scene& s) {
+    s.name = "kat1"; s.seed = 0x5EED3100ull;
+    zr_hook_seed_scene(s.seed, 0);   // the shared mesh's bvh_node draws its split axes (bvh.hpp:17)
+    typedef shared_ptr<hittable> H;
+    typedef shared_ptr<material> M;
+    M m_glass = make_shared<dielectric>(1.5);
+    M m_water = make_shared<dielectric>(1.33);
+    M m_mirror = make_shared<metal>(color(0.9, 0.8, 0.7), 0.0);
+    M m_fuzzy = make_shared<metal>(color(0.7, 0.8, 0.9), 0.25);
+    M m_red = make_shared<lambertian>(color(0.7, 0.2, 0.2));
+    M m_green = make_shared<lambertian>(color(0.2, 0.7, 0.3));
+    M m_blue = make_shared<lambertian>(color(0.2, 0.3, 0.7));
+    M none = nullptr;
+    auto at = [](int k) { return vec3(8.0 * (k % 10) - 36.0, 8.0 * (k / 10) - 28.0, 8.0 * ((k % 10 + k / 10) % 11) - 40.0); };
+    const vec3 O(0, 0, 0);
+    auto ball = [](vec3 c, M m) -> H { return make_shared<sphere>(c, 1.0, m); };
+    auto box = [](M m) -> H { return make_shared<cube>(point3(-1.0, -0.5, -0.75), point3(1.0, 0.5, 0.75), m); };
+    // "bent": axis-aligned vertex normals that disagree, so the interpolated normal at the hit ( = (1, 0, 1) / sqrt 2 where vertex B weighs 1/2)
+    // is exactly perpendicular to the direction (1, 0, -1) although the geometric normal (0, 0, 1) is not
+    auto bent = [](vec3 c, M m) -> H { return make_shared<triangle>(c + vec3(-1, -1, 0), c + vec3(1, -1, 0), c + vec3(-1, 1, 0), vec3(0, 0, 1), vec3(1, 0, 0), vec3(0, 0, 1), m); };
+    auto flat = [](vec3 c, M m) -> H { return make_shared<triangle>(c + vec3(-1, -1, 0), c + vec3(1, -1, 0), c + vec3(0, 1, 0), vec3(0, 0, 1), vec3(0, 0, 1), vec3(0, 0, 1), m); };
+    auto T = [](H h, vec3 v) -> H { return make_shared<translate>(h, v); };
+    auto S = [](H h, vec3 f) -> H { return make_shared<scale>(h, f); };
+    auto RX = [](H h, double degrees) -> H { return make_shared<rotate_x>(h, degrees); };
+    auto RY = [](H h, double radians) -> H { return make_shared<rotate_y>(h, radians); };
+    auto RZ = [](H h, double degrees) -> H { return make_shared<rotate_z>(h, degrees); };
+    auto MI = [](H h, M m) -> H { return make_shared<material_instance>(h, m); };
+    const double half_pi = 1.57079632679489661923;   // pi / 2 as a double: rotate_y takes radians, sin(k half_pi) is ~1e-16 where it "should" be 0
+
+    // cells 0-9: spheres whose tangent rays tie dot(d, outward) at exactly 0
+    s.world.add(T(ball(O, m_glass), at(0)));                                          // translate: refreshes front_face with the normal already turned
+    s.world.add(RY(ball(at(1), m_glass), 0.0));                                       // rotate_y(0): does the same, sin = 0 and cos = 1 exactly
+    s.world.add(S(T(ball(O, m_glass), 0.5 * at(2)), vec3(2, 2, 2)));                  // translate inside a positive uniform scale
+    s.world.add(T(ball(O, m_mirror), at(3)));
+    s.world.add(T(ball(at(4), m_red), vec3(0, 0, 0)));                                // identity wrappers
+    s.world.add(S(ball(at(5), m_fuzzy), vec3(1, 1, 1)));
+    s.world.add(RX(ball(at(6), m_glass), 0.0));                                       // rotate_x / rotate_z do not refresh front_face
+    s.world.add(RZ(ball(at(7), m_fuzzy), 0.0));
+    s.world.add(T(T(ball(O, m_glass), vec3(1, 0, 0)), at(8) - vec3(1, 0, 0)));        // refreshed twice
+    s.world.add(T(MI(RX(ball(O, m_red), 0.0), m_water), at(9)));
+    // cells 10-16: the same ties on triangles with bent vertex normals
+    s.world.add(T(bent(O, m_mirror), at(10)));
+    s.world.add(RY(bent(at(11), m_glass), 0.0));
+    s.world.add(RX(bent(at(12), m_glass), 0.0));
+    s.world.add(RZ(bent(at(13), m_mirror), 0.0));
+    s.world.add(T(S(bent(O, m_glass), vec3(2, 2, 2)), at(14)));                       // under a scale: never stored in world space
+    s.world.add(T(RY(bent(O, m_water), 0.0), at(15)));                                // refreshed twice
+    s.world.add(T(MI(bent(O, m_red), m_fuzzy), at(16)));
+    // cells 20-64: rotate_x / rotate_y / rotate_z by 0, 90, -90, 180, 360 in the constructors' own units around a sphere, a cube and a triangle
+    const double turns[5] = {0.0, 1.0, -1.0, 2.0, 4.0};
+    for (int axis = 0; axis < 3; axis++)
+        for (int j = 0; j < 5; j++)
+            for (int shape = 0; shape < 3; shape++) {
+                const vec3 off = axis == 1 ? vec3(0, 0, 0) : vec3(1, 1, 0);   // (rotate_y: children symmetric about the y axis)
+                H h = shape == 0 ? ball(off, j % 2 ? m_mirror : m_glass) : shape == 1 ? (axis == 1 ? box(j % 2 ? m_fuzzy : m_green) : T(box(j % 2 ? m_fuzzy : m_green), off)) : flat(off, j % 2 ? m_water : m_fuzzy);
+                h = axis == 0 ? RX(h, 90.0 * turns[j]) : axis == 1 ? RY(h, turns[j] * half_pi) : RZ(h, 90.0 * turns[j]);
+                s.world.add(T(h, at(20 + (axis * 5 + j) * 3 + shape)));
+            }
+    // cells 65-82: mirrors and extreme scales around an off-centre sphere, a triangle and a cube, each sized so that the scaled object is about one unit
+    const double tiny = std::ldexp(1.0, -20), huge = std::ldexp(1.0, 20);
+    const vec3 factors[6] = {vec3(-1, 1, 1), vec3(1, -2, 1), vec3(-1, -1, -1), vec3(tiny, tiny, tiny), vec3(huge, huge, huge), vec3(1024.0, 1.0 / 1024.0, 1.0)};
+    for (int i = 0; i < 6; i++)
+        for (int shape = 0; shape < 3; shape++) {
+            const vec3 f = factors[i];
+            const vec3 inv(1.0 / std::fabs(f.x()), 1.0 / std::fabs(f.y()), 1.0 / std::fabs(f.z()));
+            const double r = std::fmin(inv.x(), std::fmin(inv.y(), inv.z()));
+            H h;
+            if (shape == 0) h = make_shared<sphere>(point3(0.5 * r, 0.25 * r, 0.0), r, i % 2 ? m_mirror : m_glass);
+            else if (shape == 1) h = make_shared<triangle>(point3(-inv.x(), -inv.y(), 0), point3(inv.x(), -inv.y(), 0), point3(0, inv.y(), 0), vec3(0, 0, 1), vec3(0, 0, 1), vec3(0, 0, 1), i % 2 ? m_glass : m_mirror);
+            else h = make_shared<cube>(point3(-inv.x(), -0.5 * inv.y(), -0.75 * inv.z()), point3(inv.x(), 0.5 * inv.y(), 0.75 * inv.z()), i % 2 ? m_blue : m_fuzzy);
+            s.world.add(T(S(h, f), at(65 + 3 * i + shape)));   // (a cube here is the placed-cube pattern translate -> scale)
+        }
+    s.world.add(T(RY(S(box(m_fuzzy), vec3(-1, 1, 1)), 0.5), at(83)));                 // translate -> rotate_y -> scale with a negative factor
+    s.world.add(T(RY(S(box(m_red), vec3(-1, 2, -0.5)), -0.75), at(84)));              // ... and with a mixed-sign triple
+    // cells 85-92 and the origin: order and depth
+    s.world.add(T(RX(box(m_green), 90.0), at(85)));
+    s.world.add(RX(T(box(m_green), vec3(at(86).x(), at(86).z(), -at(86).y())), 90.0));   // the same cube, wrappers swapped: rotate_x(90) takes (x, z, -y) to (x, y, z)
+    s.world.add(T(RZ(S(box(m_blue), vec3(2, 1, 1)), 90.0), at(87)));                  // scale inside / outside a rotation
+    s.world.add(T(S(RZ(box(m_blue), 90.0), vec3(2, 1, 1)), at(88)));
+    s.world.add(T(RZ(S(MI(RX(T(RY(S(ball(O, m_red), vec3(0.5, 0.5, 0.5)), 0.0), vec3(0.5, 0, 0)), 180.0), m_glass), vec3(2, 2, 2)), 90.0), at(89)));   // ZR_MAX_CHAIN = 8 wrappers
+    s.world.add(T(MI(MI(ball(O, m_red), m_green), m_mirror), at(90)));                // nested material_instance: the outer one wins
+    s.world.add(MI(MI(T(ball(O, m_red), at(91)), m_blue), m_water));
+    s.world.add(MI(ball(at(92), m_red), m_fuzzy));
+    s.world.add(MI(MI(box(m_red), m_green), m_blue));                                 // at the origin, which is no cell's centre
+    // cells 93-99: constant_medium in a sphere and in a cube, under translate, a non-uniform scale and rotate_z; the last one has the wrapper on its boundary
+    auto fog = [](H boundary) -> H { return zr_hook_medium(make_shared<constant_medium>(boundary, 0.6, color(0.3, 0.5, 0.8))); };
+    s.world.add(T(fog(ball(O, none)), at(93)));
+    s.world.add(T(fog(box(none)), at(94)));
+    s.world.add(T(S(fog(ball(O, none)), vec3(2, 0.5, 1)), at(95)));
+    s.world.add(T(S(fog(box(none)), vec3(2, 0.5, 1)), at(96)));
+    s.world.add(T(RZ(fog(ball(vec3(1, 1, 0), none)), 90.0), at(97)));
+    s.world.add(T(RZ(fog(box(none)), 90.0), at(98)));
+    s.world.add(fog(T(ball(O, none), at(99))));
+    // cells 100-102: one shared mesh of six triangles (a fan of four around the origin in the plane y = 0 and a fin of two in the plane x = 0) placed three times
+    {
+        const point3 a(-1, 0, -1), b(1, 0, -1), c(1, 0, 1), d(-1, 0, 1), e(0, 0.25, -1), f(0, 1.25, -1), g(0, 1.25, 1), h(0, 0.25, 1);
+        const vec3 up(0, 1, 0), side(1, 0, 0);
+        hittable_list parts;
+        parts.add(make_shared<triangle>(a, b, O, up, up, up, m_fuzzy)); parts.add(make_shared<triangle>(b, c, O, up, up, up, m_fuzzy));
+        parts.add(make_shared<triangle>(c, d, O, up, up, up, m_fuzzy)); parts.add(make_shared<triangle>(d, a, O, up, up, up, m_fuzzy));
+        parts.add(make_shared<triangle>(e, f, g, side, side, side, m_water)); parts.add(make_shared<triangle>(e, g, h, side, side, side, m_water));
+        H mesh = make_shared<bvh_node>(parts);
+        s.world.add(T(S(mesh, vec3(-1, 1, 1)), at(100)));
+        s.world.add(T(RX(mesh, 90.0), at(101)));
+        s.world.add(T(RY(S(mesh, vec3(2, 2, 2)), 2.0 * half_pi), at(102)));   // (the mesh's box is symmetric about the y axis)
+    }
+    zr_cam_defaults(s.cam);
+    s.cam.image_width = 64; s.cam.image_height = 48; s.cam.samples_per_pixel = 4; s.cam.max_depth = 8;
+    s.cam.vfov = 40; zr_set3(s.cam.lookfrom, 10, 20, 120); zr_set3(s.cam.lookat, 0, 12, 0);
+    s.cam.defocus_angle = 0; s.cam.focus_dist = 10;
+}
+
 static inline bool zr_build_scene_mix(const std::string& name, zr_demo_scene& s, int arg0 = 0) {
     if (name == "kat0") { zr_build_kat0(s); return true; }
+    if (name == "kat1") { zr_build_kat1(s); return true; }
     if (name == "demo") { zr_build_demo(s); return true; }
     if (name == "mesh0") { zr_build_mesh0(s); return true; }
     if (name == "inst0") { zr_build_inst0(s); return true; }

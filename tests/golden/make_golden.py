@@ -250,6 +250,154 @@ def make_kat(tmp):
     print("kat_kat0", {k: v.shape for k, v in arrays.items()})
 
 
+def kat1_inputs():
+    """Hand-placed rays of the wrapper-chain fixture (scene "kat1", scenes/zr_scenes_mix.inc, whose cell layout this mirrors): rows of (o, d, tmin, tmax).
+    Object k sits in cell k, centred at (8 (k % 10) - 36, 8 (k // 10) - 28, 8 ((k % 10 + k // 10) % 11) - 40): an axis-parallel ray through one cell
+    meets no other, so no record carries another object's u, v or tangent (triangle::hit and constant_medium::hit leave them as they find them).  Every
+    comment names the behaviour its rays pin.  Returns the rays and the rows of the exact face-normal ties."""
+    INF = float("inf")
+    R, ties = [], []
+
+    def ray(o, d, tmin=0.001, tmax=INF):
+        R.append([float(x) for x in o] + [float(x) for x in d] + [tmin, tmax])
+
+    def tie(o, d):
+        ties.append(len(R)); ray(o, d)
+
+    def at(k):
+        return np.array([8.0 * (k % 10) - 36.0, 8.0 * (k // 10) - 28.0, 8.0 * ((k % 10 + k // 10) % 11) - 40.0])
+
+    def step(x, way, meets=None):
+        """x one representable step up (+1) or down (-1).  The step is one unit in the last place of x or, where the ray meets the object at a coordinate
+        `meets` of larger magnitude, of that: a smaller one is lost as soon as the hit point is written down in world coordinates, and the neighbour is
+        the tie again for every form that is stored there"""
+        return float(x + way * np.spacing(max(abs(x), abs(x if meets is None else meets))))
+
+    def linear(ops):
+        """the 3x3 matrix of a wrapper chain's object -> world map (innermost wrapper first) for quarter turns, scales and translates"""
+        m = np.eye(3)
+        for kind, a in ops:
+            c, s = {0: (1, 0), 1: (0, 1), -1: (0, -1), 2: (-1, 0), 4: (1, 0)}[a] if kind in ("rx", "ry", "rz") else (0, 0)
+            if kind == "rx":
+                m = np.array([[1, 0, 0], [0, c, -s], [0, s, c]], float) @ m      # rotate_x.hpp:59-60
+            elif kind == "ry":
+                m = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]], float) @ m      # rotate_y.hpp:63-64
+            elif kind == "rz":
+                m = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], float) @ m      # rotate_z.hpp:56-57
+            elif kind == "s":
+                m = np.diag(a) @ m
+        return m
+
+    def place(ops, p):
+        p = np.array(p, float)
+        for k, (kind, a) in enumerate(ops):
+            p = p + np.array(a, float) if kind == "t" else linear(ops[k:k + 1]) @ p
+        return p
+
+    def probe(a, axes=(0, 1, 2), dist=3.0):
+        """axis-parallel rays from both sides towards the world point a"""
+        for k in axes:
+            e = np.zeros(3); e[k] = 1.0
+            ray(a + dist * e, -e); ray(a - dist * e, e)
+
+    # ---- face-normal ties on spheres (cells 0-9): the tangent ray x = centre + r, straight down -z, has discriminant exactly 0 and an outward normal
+    # exactly perpendicular to it; a wrapper that calls set_face_normal again (translate, rotate_y) then ends with front_face = false and the OUTWARD normal
+    for k, r in ((0, 1), (1, 1), (2, 2), (3, 1), (6, 1), (7, 1), (8, 1), (9, 1), (4, 1), (5, 1)):
+        c = at(k)
+        tie(c + (r, 0, 5), (0, 0, -1))                                          # the tie
+        if k not in (4, 5):   # (|x| >= 8 there: one step of x moves the discriminant by whole units of its last place, whatever the contraction)
+            ray((step(c[0] + r, -1), c[1], c[2] + 5), (0, 0, -1))               # one step inside: a grazing hit
+            ray((step(c[0] + r, +1), c[1], c[2] + 5), (0, 0, -1))               # one step outside: a miss
+        tie(c + (0, r, 5), (0, 0, -2))                                       # the same tie at the top, direction not unit
+        probe(c, (2,))
+    c = at(2)   # radius 2 under scale(2): t is the world ray's although the local direction is half as long — kat0's interval ends again (strict for a sphere)
+    ray(c + (0, 0, 5), (0, 0, -1), 0.001, 3.0); ray(c + (0, 0, 5), (0, 0, -1), 0.001, 3.000001); ray(c + (0, 0, 5), (0, 0, -1), 3.0, INF)
+    # ---- ... and on triangles with bent vertex normals (cells 10-16): at (0, -1/2, 0) vertex B weighs 1/2, the interpolated normal is (1, 0, 1) / sqrt 2 and
+    # the direction (1, 0, -1) is exactly perpendicular to it while N.d = -1 for the geometric normal; from behind, (-1, 0, 1) ties the same way
+    for k, f in ((10, 1), (11, 1), (12, 1), (13, 1), (14, 2), (15, 1), (16, 1)):
+        c = at(k)
+        h = c + f * np.array([0, -0.5, 0])
+        tie(h + (-4, 0, 4), (1, 0, -1))                                     # the tie, front
+        ray((step(h[0] - 4, -1, h[0]), h[1], h[2] + 4), (1, 0, -1)); ray((step(h[0] - 4, +1, h[0]), h[1], h[2] + 4), (1, 0, -1))   # one step to either side
+        tie(h + (4, 0, -4), (-1, 0, 1))                                     # the tie, from behind
+        ray((step(h[0] + 4, -1, h[0]), h[1], h[2] - 4), (-1, 0, 1)); ray((step(h[0] + 4, +1, h[0]), h[1], h[2] - 4), (-1, 0, 1))
+        probe(h, (2,))
+    c = at(14) + (-0.5, -1, 0)   # under scale(2), t = 3 exactly: contains() is inclusive for a triangle
+    ray(c + (0, 0, 3), (0, 0, -1), 0.001, 3.0); ray(c + (0, 0, 3), (0, 0, -1), 0.001, 2.999999999); ray(c + (0, 0, 3), (0, 0, -1), 3.0, INF)
+    # ---- exact angles (cells 20-64): rotate_x / rotate_y / rotate_z by 0, 90, -90, 180, 360 around a sphere, a cube and a triangle; the probes aim at the
+    # round point where the turned centre lands (rotate_y's children sit on the axis)
+    for axis, name in enumerate(("rx", "ry", "rz")):
+        for j, quarter in enumerate((0, 1, -1, 2, 4)):
+            for shape in range(3):
+                off = (0, 0, 0) if axis == 1 else (1, 1, 0)
+                inner = (0, -0.5, 0) if shape == 2 else (0, 0, 0)   # a point inside the triangle
+                ops = [("t", off), (name, quarter), ("t", at(20 + (axis * 5 + j) * 3 + shape))]
+                a = place(ops, inner)
+                probe(a)
+                if shape == 2:   # the triangle's plane after the turn: both faces along its normal
+                    n = linear(ops) @ np.array([0, 0, 1.0])
+                    ray(a + 2.5 * n + (0.125, 0.125, 0.125), -n); ray(a - 2.5 * n + (0.125, 0.125, 0.125), n)
+    # ---- mirrors and extreme scales (cells 65-82) around an off-centre sphere, a triangle (both faces) and a cube (the placed-cube pattern)
+    tiny, huge = 2.0 ** -20, 2.0 ** 20
+    for i, f in enumerate(((-1, 1, 1), (1, -2, 1), (-1, -1, -1), (tiny,) * 3, (huge,) * 3, (1024.0, 1.0 / 1024.0, 1.0))):
+        inv = 1.0 / np.abs(np.array(f)); r = inv.min()
+        for shape in range(3):
+            ops = [("s", f), ("t", at(65 + 3 * i + shape))]
+            a = place(ops, (0.5 * r, 0.25 * r, 0) if shape == 0 else (0, -0.25 * inv[1], 0) if shape == 1 else (0, 0, 0))
+            probe(a)
+            ray(a + (0.0625, 0.03125, 3), (0, 0, -4)); ray(a + (0.0625, 0.03125, -3), (0, 0, 0.25))   # off the centre, directions of length 4 and 1/4
+    c = at(68) + (0.25, -0.25, 0)   # sphere r = 1/2 under scale(1, -2, 1): the local direction is not unit, t = 4.5 at the pole z = 1/2; strict ends
+    ray(c + (0, 0, 5), (0, 0, -1), 0.001, 4.5); ray(c + (0, 0, 5), (0, 0, -1), 0.001, 4.500001); ray(c + (0, 0, 5), (0, 0, -1), 4.5, INF)
+    c = at(70) + (0.25, 0.125, 0)   # the cube beside it (half extents (1, 1/4, 3/4) x (1, -2, 1)): t = 4.25 on the face z = 3/4; tmax < tmin is what misses
+    ray(c + (0, 0, 5), (0, 0, -1), 0.001, 4.25); ray(c + (0, 0, 5), (0, 0, -1), 0.001, 4.249999); ray(c + (0, 0, 5), (0, 0, -1), 4.25, INF)
+    for k in (83, 84):              # translate -> rotate_y -> scale with negative factors, at angles that are nothing special
+        probe(at(k)); ray(at(k) + (0.25, 0.125, 4), (0, 0, -1)); ray(at(k) + (3, 0.25, 3), (-1, 0, -1)); ray(at(k) + (-3, -0.125, 3), (1, 0, -1))
+    # ---- order and depth (cells 85-92 and the origin)
+    for k in (85, 86, 87, 88):      # translate(rotate_x(cube)) against rotate_x(translate(cube)); scale inside / outside rotate_z
+        probe(at(k)); ray(at(k) + (0.25, 0.125, 4), (0, 0, -1)); ray(at(k) + (4, 0.375, 0.25), (-1, 0, 0)); ray(at(k) + (0.5, 4, 0.125), (0, -1, 0))
+    a = at(89) + (0, 1, 0)          # eight wrappers (ZR_MAX_CHAIN): the sphere ends with radius 1 around cell + (0, 1, 0)
+    probe(a); ray(a + (1, 0, 5), (0, 0, -1)); ray(a + (0.5, 0.25, 5), (0, 0, -1))
+    for k in (90, 91, 92):          # nested material_instance, inside and outside a translate: the outer one wins
+        probe(at(k), (2,)); ray(at(k) + (0.5, 0.25, 5), (0, 0, -1)); ray(at(k) + (1, 0, 5), (0, 0, -1))
+    probe(np.zeros(3)); ray((0.25, 0.125, 5), (0, 0, -1))   # (the axes through the origin pass between the cells)
+    # ---- media under wrappers (cells 93-99): from outside, from inside with d.x > 0 and d.x < 0 (translate re-faces the arbitrary (1, 0, 0) normal), with
+    # ray_t.max inside the boundary, with a direction that is not unit, and along +-x from outside
+    for k in range(93, 100):
+        a = at(k) + ((-1, 1, 0) if k == 97 else (0, 0, 0))
+        for rep in range(2):
+            ray(a + (0, 0, 5), (0, 0, -1)); ray(a, (1, 0, 0)); ray(a, (-1, 0, 0)); ray(a + (0.125, 0, 0.25), (0.5, 0.25, -0.125))
+            ray(a + (0, 0, 5), (0, 0, -1), 0.001, 5.0); ray(a + (0, 0, 5), (0, 0, -2)); ray(a + (-5, 0, 0.25), (1, 0, 0)); ray(a + (5, 0.125, 0.25), (-1, 0, 0))
+            ray(a + (0, 5, 0.125), (0, -1, 0)); ray(a + (0, 0, 5), (0, 0, -1), 4.5, INF)
+    # ---- a shared mesh under three chains (cells 100-102): a fan of four triangles around the origin in the plane y = 0 and a fin of two in the plane x = 0
+    faces = [(0, 0, -0.5), (0.5, 0, 0), (0, 0, 0.5), (-0.5, 0, 0)]
+    for k, ops in ((100, [("s", (-1, 1, 1))]), (101, [("rx", 1)]), (102, [("s", (2, 2, 2)), ("ry", 2)])):
+        ops = ops + [("t", at(k))]
+        m = linear(ops)
+        down = m @ np.array([0, -1.0, 0]); side = m @ np.array([1.0, 0, 0])
+        for q in faces:             # each fan face from below (its front is up) and, beside the fin, from above
+            ray(place(ops, (q[0], -2, q[2])), -down)
+            ray(place(ops, (q[0] + 0.25, 2, q[2] + 0.125)), down)
+        for q in ((0, 0.75, -0.5), (0, 0.5, 0.5)):   # each fin face from both sides
+            ray(place(ops, (2, q[1], q[2])), -side); ray(place(ops, (-2, q[1], q[2])), side)
+        if k == 100:                # exact under the mirror: the shared vertex of all four fan faces, and the edge origin-c, from below
+            ray(place(ops, (0, -2, 0)), -down); ray(place(ops, (0.5, -2, 0.5)), -down); ray(place(ops, (1, -2, 1)), -down); ray(place(ops, (1.0000001, -2, 1)), -down)
+    # ---- between the cells: nothing there
+    for k in range(0, 103, 3):
+        ray(at(k) + (4, 4, 5), (0, 0, -1)); ray(at(k) + (4, 3.5, -5), (0.0078125, 0, 1))
+    return np.array(R, dtype=np.float64), np.array(ties)
+
+
+def make_kat1(tmp):
+    rays, _ = kat1_inputs()
+    f = os.path.join(tmp, "kat1_hits.bin"); pre = os.path.join(tmp, "kat1_hits")
+    rays.tofile(f)
+    meta = run("kat", "kat1", "hits", f, len(rays), pre)
+    recs = np.load(pre + "_recs.npy")
+    meta["rays_hit"] = int((recs[:, 0] > 0).sum())
+    np.savez_compressed(os.path.join(HERE, "kat_kat1.npz"), meta=np.array(json.dumps({"hits": meta})), rays=rays, recs=recs, scat=np.load(pre + "_scat.npy"))
+    print("kat_kat1", len(rays), "rays,", meta["rays_hit"], "hit,", os.path.getsize(os.path.join(HERE, "kat_kat1.npz")), "bytes")
+
+
 def make_refdemo(tmp):
     """The reference's OWN demo world (load_materials + sceneAssetsLoader + build_geometry, scene_management.hpp:28-236) for the GPU: the scene reads the
     reference's assets/ at run time, which never travel — so the world travels FLATTENED.  oracle/_ref/refscene_dropin (the reference's scene code compiled
@@ -355,6 +503,8 @@ def main():
             make_refdemo(tmp)
         if not want or "kat" in want or "kat0" in want:
             make_kat(tmp)
+        if not want or "kat" in want or "kat1" in want:
+            make_kat1(tmp)
         if not want or "texels" in want:
             out = os.path.join(tmp, "texels.npy")
             subprocess.run([REF, "texels", "64", "32", out], check=True)

@@ -233,3 +233,116 @@ def test_oracle_matches_reference_kat(built):
         d2 = demo_scene(scene)
         assert d2.seed == fx["meta"][f"cam_{scene}"]["seed"]
         assert np.array_equal(zo.kat_camera_rays(d2.camera, d2.seed, fx[f"cam_req_{scene}"]), fx[f"cam_rays_{scene}"])
+
+
+# ---- wrapper chains at their edges (tests/golden/kat_kat1.npz, scene "kat1") ---------------------------------------------------------
+def kat1_inputs():
+    """the hand-placed rays of tests/golden/make_golden.py and the rows of the exact face-normal ties"""
+    import importlib.util
+    import os
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(ROOT, "tests", "golden", "make_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.kat1_inputs()
+
+
+def test_oracle_matches_reference_kat1(built):
+    """translate / rotate_x / rotate_y / rotate_z / scale / material_instance chains, and constant_medium under them, at their edges: face-normal ties
+    (dot(d, normal) exactly 0 under wrappers that call set_face_normal again and under ones that do not), turns by exactly 0, 90, -90, 180 and 360, mirror
+    and 2^-20 ... 2^20 scales, wrapper order, a chain of ZR_MAX_CHAIN wrappers, nested material_instance, media from inside and with ray_t.max inside, a shared
+    mesh under three chains — the CPU restatement against the genuine reference functions, bit for bit on every field."""
+    from oracle import zr_oracle_py as zo
+    fx = load_golden("kat_kat1")
+    m = fx["meta"]["hits"]
+    ds = demo_scene("kat1")
+    assert not ds.warnings, ds.warnings
+    osc = zo.OracleScene(ds.desc)
+    rays, recs, scat = fx["rays"], fx["recs"], fx["scat"]
+    want_rays, ties = kat1_inputs()
+    assert np.array_equal(rays, want_rays), "the fixture was not made from kat1_inputs()"
+    hits = kat_trace(lambda r, a, b: osc.trace(r, a, b, seed=m["seed"], pixel=m["stream_pixel"], bounce=0), rays)
+    ref_hit = recs[:, 0] > 0
+    assert np.array_equal(ref_hit, hits["mat"] != 0xFFFFFFFF)
+    assert m["rays_hit"] == ref_hit.sum() and ref_hit.sum() >= 0.3 * len(rays) and (~ref_hit).sum() >= 0.1 * len(rays), "the fixture must hold hits and misses"
+    # every exact tie is a hit whose normal is perpendicular to the ray and whose front_face is false; which way the normal points is the wrappers' doing
+    assert len(ties) == 34 and ref_hit[ties].all() and not recs[ties, 8].any()
+    assert np.all(np.einsum("ij,ij->i", rays[ties, 3:6], recs[ties, 5:8]) == 0)
+    h = ref_hit
+    assert np.array_equal(hits["t"][h], recs[h, 1])
+    assert np.array_equal(hits["p"][h], recs[h, 2:5])
+    assert np.array_equal(hits["normal"][h], recs[h, 5:8])
+    assert np.array_equal(hits["front_face"][h], recs[h, 8].astype(np.uint32))
+    assert np.array_equal(hits["u"][h], recs[h, 9]) and np.array_equal(hits["v"][h], recs[h, 10])   # fresh records: triangles / media report 0
+    assert np.array_equal(hits["tangent"][h], recs[h, 11:14])
+    pairs = set(zip(recs[h, 14].astype(int).tolist(), hits["mat"][h].tolist()))
+    assert len(pairs) == len({a for a, _ in pairs}) == len({b for _, b in pairs}) >= 8
+    keys = np.array([zo.stream_key(m["seed"], m["stream_pixel"], k) for k in range(len(rays))], dtype=np.uint64)
+    so = osc.kat_scatter(rays[h, :6], hits[h], keys[h])
+    assert np.array_equal(so["scattered"], scat[h, 0].astype(np.uint32))
+    assert np.array_equal(so["draws"], scat[h, 13].astype(np.uint32))
+    assert np.array_equal(so["attenuation"], scat[h, 1:4]) and np.array_equal(so["origin"], scat[h, 4:7])
+    assert np.array_equal(so["direction"], scat[h, 7:10]) and np.array_equal(so["emitted"], scat[h, 10:13])
+    assert (so["draws"] == 0).sum() >= 3 and (so["draws"] >= 3).sum() >= 3
+
+
+# the stored form classify_object (zr_flatten.h) gives every world-list entry of "kat1", in the order zr_build_kat1 adds them
+KAT1_FORMS = (["baked sphere", "interpreter", "baked sphere", "baked sphere", "baked sphere", "baked sphere", "interpreter", "interpreter", "interpreter", "interpreter"]   # cells 0-9
+              + ["baked triangle"] * 4 + ["interpreter", "baked triangle", "baked triangle"]                                                                         # cells 10-16
+              + (["interpreter", "interpreter", "baked triangle"] * 5 + ["interpreter", "placed cube", "baked triangle"] * 5 + ["interpreter", "interpreter", "baked triangle"] * 5)   # exact angles
+              + ["interpreter", "interpreter", "placed cube with scale"] * 3 + ["baked sphere", "interpreter", "placed cube with scale"] * 2 + ["interpreter", "interpreter", "placed cube with scale"]
+              + ["placed cube with scale"] * 2                                                                                                                        # cells 83, 84
+              + ["interpreter"] * 5 + ["baked sphere", "baked sphere", "material-only chain", "material-only chain"]                                                # order and depth
+              + ["interpreter"] * 6 + ["medium"] + ["instance"] * 3)
+
+
+@pytest.fixture(scope="module")
+def classify_checker(tmp_path_factory):
+    import os
+    import subprocess
+    from conftest import ROOT
+    csrc = os.path.join(ROOT, "raytracer_project_amd", "csrc")
+    out = str(tmp_path_factory.mktemp("classify") / "classify_check")
+    subprocess.run(["g++", "-std=c++20", "-O1", "-pthread", "-I", csrc, "-o", out, os.path.join(ROOT, "tests", "native", "classify_check.cpp"), os.path.join(csrc, "zr_bvh.cpp")], check=True)
+    return out
+
+
+@pytest.mark.parametrize("bake", ["1", "0"])
+def test_kat1_objects_land_in_their_stored_forms(bake, built, classify_checker, tmp_path):
+    """The edges of "kat1" only pin the code they run through: the commit plan (make_plan / classify_object, read without a device through
+    tests/native/classify_check.cpp) must store every object of the scene in the form the scene intends — baked triangle, baked sphere, placed cube (with and
+    without a scale), material-only chain, op-list interpreter, instance — and, with ZR_BAKE_TRIANGLES=0, leave every wrapped object to the interpreter."""
+    import ctypes as C
+    import json
+    import os
+    import subprocess
+    from raytracer_project_amd import capi
+    d = demo_scene("kat1").desc
+    objs = C.cast(d.objects, C.POINTER(capi.Object))
+    ops = C.cast(d.ops, C.POINTER(capi.XformOp))
+    media = C.cast(d.media, C.POINTER(capi.Medium))
+    smat = C.cast(d.sphere_mat, C.POINTER(C.c_uint32))
+    lines = [f"spheres {d.n_spheres}"] + [str(smat[k]) for k in range(d.n_spheres)]
+    lines += [f"media {d.n_media}"] + [f"{media[k].boundary_type} {media[k].boundary_index}" for k in range(d.n_media)]
+    lines += [f"ops {d.n_ops}"] + [f"{ops[k].kind} {ops[k].mat} {float(ops[k].a[0]).hex()} {float(ops[k].a[1]).hex()} {float(ops[k].a[2]).hex()}" for k in range(d.n_ops)]
+    lines += [f"objects {d.n_objects}"] + [f"{objs[k].type} {objs[k].index} {objs[k].chain_first} {objs[k].chain_count}" for k in range(d.n_objects)]
+    path = tmp_path / "kat1_world.txt"
+    path.write_text("\n".join(lines) + "\n")
+    p = subprocess.run([classify_checker, str(path)], env=dict(os.environ, ZR_BAKE_TRIANGLES=bake), capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    code = json.loads(p.stdout.strip().splitlines()[-1])["code"]
+    assert len(code) == d.n_objects == len(KAT1_FORMS)
+    SPHERE, TRIANGLE, CUBE, MEDIUM, WRAPPED, PCUBE, INSTANCE = 0, 1, 2, 3, 4, 5, 6   # leaf kinds (zr_capi.h ZR_PRIM_*, zr_device_types.h ZR_KIND_*)
+    got = []
+    for k, c in enumerate(code):
+        kind, stored = c & 7, c >> 4
+        has_scale = any(ops[objs[k].chain_first + q].kind == 4 for q in range(objs[k].chain_count))   # ZR_OP_SCALE
+        got.append({(SPHERE, 3): "baked sphere", (TRIANGLE, 1): "baked triangle", (PCUBE, 4): "placed cube with scale" if has_scale else "placed cube", (SPHERE, 2): "material-only chain",
+                    (CUBE, 2): "material-only chain", (WRAPPED, 0): "interpreter", (INSTANCE, 0): "instance", (MEDIUM, 0): "medium"}.get((kind, stored), f"kind {kind} stored {stored}"))
+    if bake == "1":
+        want = list(KAT1_FORMS)
+        assert set(want) >= {"baked triangle", "baked sphere", "placed cube", "placed cube with scale", "material-only chain", "interpreter", "instance"}
+    else:   # nothing is baked: every wrapped object runs the op list
+        want = [f if f in ("instance", "medium") else "interpreter" for f in KAT1_FORMS]
+    wrong = [(k, got[k], want[k]) for k in range(len(want)) if got[k] != want[k]]
+    assert not wrong, wrong
