@@ -1366,6 +1366,19 @@ struct flat_lease {
 // the device hit() / scatter() calls of scene objects use: the one of the camera that rendered last (camera::device), 0 before that
 inline std::atomic<int>& object_device() { static std::atomic<int> d{0}; return d; }
 
+// a frame of colours as the C ABI takes it: three doubles per pixel
+inline double* doubles(std::vector<color>& frame) { return reinterpret_cast<double*>(frame.data()); }
+inline const double* doubles(const std::vector<color>& frame) { return reinterpret_cast<const double*>(frame.data()); }
+// the caller's render flag and row counter as the C ABI polls and advances them
+static_assert(sizeof(std::atomic<bool>) == 1 && sizeof(std::atomic<int>) == sizeof(int), "flag layout");
+inline volatile const uint8_t* flag_ptr(std::atomic<bool>& flag) { return reinterpret_cast<volatile const uint8_t*>(&flag); }
+inline volatile int* rows_ptr(std::atomic<int>& rows) { return reinterpret_cast<volatile int*>(&rows); }
+// owning handles of the C ABI's scene and accumulator
+struct scene_deleter { void operator()(zr_scene* sc) const { zr_scene_destroy(sc); } };   // (frees the scene's device arrays; touches no context state: no lease)
+struct accum_deleter { void operator()(zr_accum* acc) const { zr_accum_destroy(acc); } };
+using scene_handle = std::unique_ptr<zr_scene, scene_deleter>;
+using accum_handle = std::unique_ptr<zr_accum, accum_deleter>;
+
 // ---- callable hit() / scatter(): one ray through the device ---------------------------------------------------------
 // The object is flattened once and committed as a scene of its own (cached in the object, per context; set_material drops
 // the cache, any other mutation of a child after the first call needs zenith::forget(obj)).  hit() = zr_trace over
@@ -1374,10 +1387,9 @@ inline std::atomic<int>& object_device() { static std::atomic<int> d{0}; return 
 // i.e. the call consumes random_double() exactly as the reference's scatter would (common.hpp:29-34, material.hpp).
 // A constant_medium draws its distance from the off-stream medium key of the current stream position (zr_rng.h).
 struct device_object {
-    zr_ctx* ctx = nullptr; zr_scene* sc = nullptr; int device = 0;
+    zr_ctx* ctx = nullptr; scene_handle sc; int device = 0;
     flat_scene fs;
     std::unordered_map<uint32_t, shared_ptr<material>> mats;
-    ~device_object() { if (sc) zr_scene_destroy(sc); }   // (frees the scene's device arrays; touches no context state: no lease)
 };
 template <class Flatten>
 inline shared_ptr<device_object> device_commit(shared_ptr<device_object>& cache, const char* what, Flatten&& flatten) {
@@ -1392,8 +1404,8 @@ inline shared_ptr<device_object> device_commit(shared_ptr<device_object>& cache,
     b.finish();
     d->mats = b.mat_ptrs;
     for (const auto& w : d->fs.warnings) std::cerr << "[zenith] " << w << "\n";
-    d->sc = zr_scene_create(ctx);
-    if (!d->sc || d->fs.give_to(d->sc) != ZR_OK || zr_scene_commit(d->sc) != ZR_OK)
+    d->sc.reset(zr_scene_create(ctx));
+    if (!d->sc || d->fs.give_to(d->sc.get()) != ZR_OK || zr_scene_commit(d->sc.get()) != ZR_OK)
         throw std::runtime_error(std::string(what) + ": " + zr_last_error());
     cache = d;
     return d;
@@ -1408,7 +1420,7 @@ inline bool device_hit(const hittable& self, const ray& r, const interval& ray_t
     zr_hit h{};
     context_lease lease(d->ctx);   // the object's scene lives on that context: exclusive for the call
     // stream key of this call = (host key, host draw position, 0): a medium's off-stream draw changes as the host stream advances
-    if (zr_trace(d->ctx, d->sc, rays6, 1, ray_t.min, ray_t.max, g.key, g.k, 0, &h) != ZR_OK) throw std::runtime_error(std::string("hittable::hit: ") + zr_last_error());
+    if (zr_trace(d->ctx, d->sc.get(), rays6, 1, ray_t.min, ray_t.max, g.key, g.k, 0, &h) != ZR_OK) throw std::runtime_error(std::string("hittable::hit: ") + zr_last_error());
     if (!d->fs.media.empty()) g.k++;   // constant_medium::hit consumes a draw (constant_medium.hpp:64)
     if (h.mat == 0xFFFFFFFFu && h.t == 0.0) return false;
     rec.p = point3(h.p[0], h.p[1], h.p[2]); rec.normal = vec3(h.normal[0], h.normal[1], h.normal[2]);
@@ -1430,7 +1442,7 @@ inline bool device_scatter(const material& self, const ray& r_in, const hit_reco
     host_rng& g = rng_state();
     zr_scatter_out o{};
     context_lease lease(d->ctx);
-    if (zr_kat_scatter(d->ctx, d->sc, rays6, &h, &g.key, &g.k, 1, &o) != ZR_OK) throw std::runtime_error(std::string("material::scatter: ") + zr_last_error());
+    if (zr_kat_scatter(d->ctx, d->sc.get(), rays6, &h, &g.key, &g.k, 1, &o) != ZR_OK) throw std::runtime_error(std::string("material::scatter: ") + zr_last_error());
     g.k += o.draws;
     if (!o.scattered) return false;
     attenuation = vec3(o.attenuation[0], o.attenuation[1], o.attenuation[2]);
@@ -1444,7 +1456,7 @@ inline void post_processor::apply_sharpening(std::vector<color>& buffer, int wid
     if (width < 1 || height < 1 || buffer.size() != (size_t)width * height) { std::cerr << "[zenith] apply_sharpening: buffer size mismatch\n"; return; }
     zenith::context_lease lease(zenith::object_device().load());
     zr_ctx* ctx = lease;
-    double* p = reinterpret_cast<double*>(buffer.data());
+    double* p = zenith::doubles(buffer);
     if (!ctx || zr_sharpen_frame(ctx, p, width, height, amount, p) != ZR_OK) std::cerr << "[zenith] apply_sharpening failed: " << zr_last_error() << "\n";
 }
 
@@ -1516,7 +1528,7 @@ public:
         zr_ctx* ctx = lease;
         if (!ctx || buffer.size() != (size_t)image_width * image_height) { std::cerr << "[zenith] process_framebuffer: " << (ctx ? "buffer size mismatch" : zr_last_error()) << "\n"; return false; }
         zr_post_params p = pp.to_zr();
-        int rc = zr_post_process(ctx, &p, reinterpret_cast<const double*>(buffer.data()), image_width, image_height, is_data_pass, apply_gamma, rgb8.data());
+        int rc = zr_post_process(ctx, &p, zenith::doubles(buffer), image_width, image_height, is_data_pass, apply_gamma, rgb8.data());
         if (rc != ZR_OK) std::cerr << "[zenith] process_framebuffer failed: " << zr_last_error() << "\n";
         return rc == ZR_OK;
     }
@@ -1526,7 +1538,7 @@ public:
         zenith::context_lease lease(device);
         zr_ctx* ctx = lease;
         zr_image_stats z{};
-        if (ctx && !buffer.empty() && zr_analyze_frame(ctx, reinterpret_cast<const double*>(buffer.data()), buffer.size(), &z) == ZR_OK) {
+        if (ctx && !buffer.empty() && zr_analyze_frame(ctx, zenith::doubles(buffer), buffer.size(), &z) == ZR_OK) {
             st.average_luminance = z.average_luminance; st.max_luminance = z.max_luminance;
             for (int i = 0; i < 256; i++) st.histogram[i] = z.histogram[i];
             st.normalize();
@@ -1536,12 +1548,11 @@ public:
 
     // camera.hpp:236.  Blocking; fills render_accumulator (mean radiance, row-major, idx = j*W + i)."
     void render(const hittable& world, const EnvironmentSettings& env, const post_processor& post, std::atomic<bool>& render_flag) {
-        static_assert(sizeof(std::atomic<bool>) == 1 && sizeof(std::atomic<int>) == sizeof(int), "flag layout");
         if (image_width < 1) image_width = 1;
         if (image_height < 1) image_height = 1;
         aspect_ratio = double(image_width) / image_height;
         lines_rendered = 0;
-        render_accumulator.assign((size_t)image_width * image_height, color(0, 0, 0));  // the reference only fills (camera.hpp:420)
+        render_accumulator.assign(pixels(), color(0, 0, 0));  // the reference only fills (camera.hpp:420)
         const bool stats = std::getenv("ZR_COMMIT_STATS") != nullptr;
         auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         double t_ph = now_s();
@@ -1552,176 +1563,189 @@ public:
         world.flatten(b);
         b.finish();
         ph("flatten");
-        zr_env zenv = zenith::to_zr_env(env, b);
+        const zr_env zenv = zenith::to_zr_env(env, b);
         for (const auto& w : fs.warnings) std::cerr << "[zenith] " << w << "\n";
         zenith::object_device() = device;
+        // the debug view fills render_accumulator only: the AOV, split-pass and denoise buffers stay as reset_accumulator left them
+        // (the reference would feed them the debug frame's records)
+        const bool debug = global_settings::bvh_debug_mode;
+        guide_frames guides;
         int rc;
-        std::vector<color> guide_albedo, guide_normal;   // the denoiser's guides when the public AOV buffers are off
         {
-        zenith::context_lease lease(device);   // one context of the process-wide pool, exclusively, for this frame
-        zr_ctx* ctx = lease;
-        if (!ctx) { std::cerr << "[zenith] render failed: " << zr_last_error() << "\n"; return; }
-        zr_scene* sc = zr_scene_create(ctx);
-        rc = sc ? fs.give_to(sc) : ZR_E_DEVICE;
-        if (rc == ZR_OK) rc = zr_scene_commit(sc);
-        ph("commit");
-        if (rc == ZR_OK) {
-            zr_camera zc{};
-            zc.image_width = image_width; zc.image_height = image_height; zc.samples_per_pixel = samples_per_pixel; zc.max_depth = max_depth;
-            zc.vfov = vfov; zc.defocus_angle = defocus_angle; zc.focus_dist = focus_dist;
-            for (int k = 0; k < 3; k++) { zc.lookfrom[k] = lookfrom[k]; zc.lookat[k] = lookat[k]; zc.vup[k] = vup[k]; }
-            sample_counts.clear();
-            variance_buffer.clear(); denoise_used_variance = false;
-            const bool want_variance = use_denoiser && denoise_variance_guided;
-            // the variance of the accumulator's pixel means, fetched before the accumulator is destroyed
-            auto fetch_variance = [&](zr_accum* acc) {
-                variance_buffer.assign((size_t)image_width * image_height, color(0, 0, 0));
-                const int vrc = zr_accum_variance(acc, reinterpret_cast<double*>(variance_buffer.data()));
-                if (vrc != ZR_OK) variance_buffer.clear();
-                return vrc;
-            };
-            if (global_settings::bvh_debug_mode) {
-                // the debug view fills render_accumulator only: the AOV, split-pass and denoise buffers stay as reset_accumulator left them
-                // (the reference would feed them the debug frame's records)
-                const zr_bvh_debug_params dp{global_settings::debug_bvh_level, global_settings::bvh_thickness};
-                rc = zr_render_bvh_debug(ctx, sc, &zc, &zenv, seed, nullptr, &dp, reinterpret_cast<double*>(render_accumulator.data()),
-                                         reinterpret_cast<volatile const uint8_t*>(&render_flag), reinterpret_cast<volatile int*>(&lines_rendered));
-                ph("zr_render_bvh_debug");
-            } else {
-            bool adaptive = adaptive_threshold > 0;
-            if (adaptive && samples_per_pixel < 64) { std::cerr << "[zenith] adaptive_threshold ignored: samples_per_pixel is below 64\n"; adaptive = false; }
-            if (adaptive) {
-                static_assert(sizeof(int) == sizeof(int32_t), "sample_counts layout");
-                zr_adaptive_params ap{};
-                ap.max_samples = samples_per_pixel / 64 * 64;
-                ap.min_samples = std::min(adaptive_min_samples, ap.max_samples); ap.step_samples = adaptive_step;
-                ap.threshold = adaptive_threshold; ap.dark_floor = adaptive_dark_floor;
-                current_samples_count = 0; passes_rendered = 0;
-                zr_accum* acc = zr_accum_create(ctx, image_width, image_height, nullptr);
-                rc = acc ? ZR_OK : ZR_E_DEVICE;
-                if (rc == ZR_OK) {
-                    // a cancelled run leaves the image of the passes that completed; a refused one (bad counts) leaves nothing
-                    const int arc = zr_render_adaptive(ctx, sc, &zc, &zenv, seed, acc, &ap, 0, reinterpret_cast<volatile const uint8_t*>(&render_flag), &last_adaptive);
-                    rc = arc;
-                    if ((arc == ZR_OK || arc == ZR_E_CANCELLED) && last_adaptive.passes > 0) {
-                        sample_counts.assign((size_t)image_width * image_height, 0);
-                        int64_t st4[4] = {0, 0, 0, 0};
-                        int qrc = zr_accum_resolve(acc, reinterpret_cast<double*>(render_accumulator.data()));
-                        if (qrc == ZR_OK) qrc = zr_accum_sample_counts(acc, reinterpret_cast<int32_t*>(sample_counts.data()));
-                        if (qrc == ZR_OK) qrc = zr_accum_state(acc, st4);
-                        if (qrc == ZR_OK && arc == ZR_OK && want_variance) qrc = fetch_variance(acc);
-                        if (qrc != ZR_OK) rc = qrc;
-                        else { current_samples_count = (int)st4[1]; passes_rendered = (int)last_adaptive.passes; }
-                    }
-                    if (rc == ZR_OK) lines_rendered = image_height;
-                }
-                if (acc) zr_accum_destroy(acc);
-            } else if (samples_per_pass > 0) {
-                // progressive (the reference's "real-time sample accumulation"): passes of samples_per_pass samples into a device accumulator
-                const int spp = samples_per_pixel < 1 ? 1 : samples_per_pixel;
-                current_samples_count = 0; passes_rendered = 0;
-                zr_accum* acc = zr_accum_create(ctx, image_width, image_height, nullptr);
-                rc = acc ? ZR_OK : ZR_E_DEVICE;
-                while (rc == ZR_OK && current_samples_count < spp) {
-                    const int n = std::min(samples_per_pass, spp - current_samples_count);
-                    rc = zr_render_accumulate(ctx, sc, &zc, &zenv, seed, acc, n, 0, reinterpret_cast<volatile const uint8_t*>(&render_flag));
-                    if (rc != ZR_OK) break;   // (a cancelled pass is discarded whole: the image stays the one of the passes before it)
-                    rc = zr_accum_resolve(acc, reinterpret_cast<double*>(render_accumulator.data()));
-                    if (rc != ZR_OK) break;
-                    current_samples_count += n; passes_rendered++;
-                    lines_rendered = current_samples_count < spp ? (int)((long long)image_height * current_samples_count / spp) : image_height;
-                    if (current_samples_count < spp && !render_flag.load()) { rc = ZR_E_CANCELLED; break; }
-                }
-                if (rc == ZR_OK && acc && want_variance && spp % 64 == 0) rc = fetch_variance(acc);
-                if (acc) zr_accum_destroy(acc);
-            } else
-            rc = zr_render(ctx, sc, &zc, &zenv, seed, nullptr, 0, reinterpret_cast<double*>(render_accumulator.data()),
-                           reinterpret_cast<volatile const uint8_t*>(&render_flag), reinterpret_cast<volatile int*>(&lines_rendered));
-            zr_get_counters(ctx, &last_counters);
-            ph("zr_render");
-            if (rc == ZR_OK && (use_albedo_buffer || use_normal_buffer || use_z_depth_buffer || use_denoiser)) {
-                const size_t npx = (size_t)image_width * image_height;
-                if (use_albedo_buffer) albedo_buffer.assign(npx, color(0, 0, 0));
-                if (use_normal_buffer) normal_buffer.assign(npx, color(0, 0, 0));
-                if (use_z_depth_buffer) z_depth_buffer.assign(npx, color(0, 0, 0));
-                // the denoiser's guides: the public buffers when their flags are set, private scratch otherwise (the reference would
-                // hand OIDN zero guides then)
-                if (use_denoiser && !use_albedo_buffer) guide_albedo.assign(npx, color(0, 0, 0));
-                if (use_denoiser && !use_normal_buffer) guide_normal.assign(npx, color(0, 0, 0));
-                double* pa = use_albedo_buffer ? reinterpret_cast<double*>(albedo_buffer.data()) : use_denoiser ? reinterpret_cast<double*>(guide_albedo.data()) : nullptr;
-                double* pn = use_normal_buffer ? reinterpret_cast<double*>(normal_buffer.data()) : use_denoiser ? reinterpret_cast<double*>(guide_normal.data()) : nullptr;
-                zr_aov_params ap{post.z_depth_max_dist};
-                rc = zr_render_aov(ctx, sc, &zc, seed, nullptr, &ap, pa, pn,
-                                   use_z_depth_buffer ? reinterpret_cast<double*>(z_depth_buffer.data()) : nullptr);
+            zenith::context_lease lease(device);   // one context of the process-wide pool, exclusively, for this frame
+            if (!lease.ctx) { std::cerr << "[zenith] render failed: " << zr_last_error() << "\n"; return; }
+            const zenith::scene_handle sc(zr_scene_create(lease.ctx));
+            rc = sc ? fs.give_to(sc.get()) : ZR_E_DEVICE;
+            if (rc == ZR_OK) rc = zr_scene_commit(sc.get());
+            ph("commit");
+            if (rc == ZR_OK) {
+                const frame_job job{lease.ctx, sc.get(), to_zr(), zenv, render_flag};
+                sample_counts.clear();
+                variance_buffer.clear(); denoise_used_variance = false;
+                if (debug) rc = render_debug_view(job);
+                else if (wants_adaptive()) rc = render_adaptive(job);
+                else if (samples_per_pass > 0) rc = render_progressive(job);
+                else rc = render_one_shot(job);
+                if (!debug) zr_get_counters(lease.ctx, &last_counters);
+                ph(debug ? "zr_render_bvh_debug" : "zr_render");
+                if (rc == ZR_OK && !debug) rc = render_aovs(job, post, guides);
+                if (rc == ZR_OK && !debug) rc = render_split_passes(job);
             }
-            if (rc == ZR_OK && (use_reflection || use_refraction)) {
-                // camera.hpp:490: either flag runs the second path and fills BOTH frames; the beauty image above is what the
-                // reference's loop produces with the flags on (same stream prefix), so it is not rendered again
-                const size_t npx = (size_t)image_width * image_height;
-                reflection_buffer.assign(npx, color(0, 0, 0));
-                refraction_buffer.assign(npx, color(0, 0, 0));
-                rc = zr_render_passes(ctx, sc, &zc, &zenv, seed, nullptr, nullptr, reinterpret_cast<double*>(reflection_buffer.data()),
-                                      reinterpret_cast<double*>(refraction_buffer.data()));
-            }
-            }
-        }
-        if (rc != ZR_OK && rc != ZR_E_CANCELLED) std::cerr << "[zenith] render failed: " << zr_last_error() << "\n";
-        if (sc) zr_scene_destroy(sc);
-        }   // (the lease ends here: analyze() below takes its own)
+            if (rc != ZR_OK && rc != ZR_E_CANCELLED) std::cerr << "[zenith] render failed: " << zr_last_error() << "\n";
+        }   // (the scene is destroyed and the lease ends here: analyze() and the denoiser below take their own)
         if (rc == ZR_OK && post.use_auto_exposure) {   // camera.hpp:258-266
             image_statistics stats = analyze(render_accumulator);
             post.last_stats = stats;
             post.exposure = static_cast<float>(post.apply_auto_exposure(stats));
         }
-        if (rc == ZR_OK && use_denoiser && !global_settings::bvh_debug_mode) {   // camera.hpp:268-291; the a-trous filter of zr_denoise stands in for OIDN
-            const std::vector<color>& ga = use_albedo_buffer ? albedo_buffer : guide_albedo;
-            const std::vector<color>& gn = use_normal_buffer ? normal_buffer : guide_normal;
-            denoise_buffer = render_accumulator;
-            bool ok;
-            if (denoise_variance_guided && variance_buffer.size() == render_accumulator.size()) {
-                ok = denoise_guided(denoise_buffer, variance_buffer, ga, gn);
-                denoise_used_variance = ok;
-            } else {
-                if (denoise_variance_guided)
-                    std::cerr << "[zenith] denoise_variance_guided ignored: no variance (it needs adaptive_threshold, or samples_per_pass with a multiple of 64 samples)\n";
-                ok = denoise(denoise_buffer, ga, gn);
-            }
-            if (ok && use_reflection) {
-                ok = denoise(reflection_buffer, ga, gn);
-                if (ok && post.use_sharpening) post.apply_sharpening(reflection_buffer, image_width, image_height, post.sharpen_amount);
-            }
-            if (ok && use_refraction) {
-                ok = denoise(refraction_buffer, ga, gn);
-                if (ok && post.use_sharpening) post.apply_sharpening(refraction_buffer, image_width, image_height, post.sharpen_amount);
-            }
-        }
+        if (rc == ZR_OK && use_denoiser && !debug) denoise_frames(post, guides);
     }
 
 private:
-    // apply_denoising (camera.hpp:581-699) in place, with zr_denoise's default parameters; false (and a message) on failure
-    bool denoise(std::vector<color>& buffer, const std::vector<color>& albedo, const std::vector<color>& normal) const {
+    // what the stages of one render share
+    struct frame_job {
+        zr_ctx* ctx; const zr_scene* sc;
+        zr_camera cam; zr_env env;
+        std::atomic<bool>& flag;
+    };
+    // the denoiser's guides when the public AOV buffers are off (the reference would hand OIDN zero guides then)
+    struct guide_frames { std::vector<color> albedo, normal; };
+
+    size_t pixels() const { return (size_t)image_width * image_height; }
+    zr_camera to_zr() const {
+        zr_camera zc{};
+        zc.image_width = image_width; zc.image_height = image_height; zc.samples_per_pixel = samples_per_pixel; zc.max_depth = max_depth;
+        zc.vfov = vfov; zc.defocus_angle = defocus_angle; zc.focus_dist = focus_dist;
+        for (int k = 0; k < 3; k++) { zc.lookfrom[k] = lookfrom[k]; zc.lookat[k] = lookat[k]; zc.vup[k] = vup[k]; }
+        return zc;
+    }
+    bool wants_adaptive() const {
+        if (adaptive_threshold > 0 && samples_per_pixel < 64) std::cerr << "[zenith] adaptive_threshold ignored: samples_per_pixel is below 64\n";
+        return adaptive_threshold > 0 && samples_per_pixel >= 64;
+    }
+    // the variance of the accumulator's pixel means, when the denoiser will ask for it (fetched before the accumulator is destroyed)
+    int fetch_variance(zr_accum* acc) {
+        if (!(use_denoiser && denoise_variance_guided)) return ZR_OK;
+        variance_buffer.assign(pixels(), color(0, 0, 0));
+        const int rc = zr_accum_variance(acc, zenith::doubles(variance_buffer));
+        if (rc != ZR_OK) variance_buffer.clear();
+        return rc;
+    }
+
+    int render_debug_view(const frame_job& j) {
+        const zr_bvh_debug_params dp{global_settings::debug_bvh_level, global_settings::bvh_thickness};
+        return zr_render_bvh_debug(j.ctx, j.sc, &j.cam, &j.env, seed, nullptr, &dp, zenith::doubles(render_accumulator), zenith::flag_ptr(j.flag),
+                                   zenith::rows_ptr(lines_rendered));
+    }
+    int render_one_shot(const frame_job& j) {
+        return zr_render(j.ctx, j.sc, &j.cam, &j.env, seed, nullptr, 0, zenith::doubles(render_accumulator), zenith::flag_ptr(j.flag), zenith::rows_ptr(lines_rendered));
+    }
+    int render_adaptive(const frame_job& j) {
+        static_assert(sizeof(int) == sizeof(int32_t), "sample_counts layout");
+        zr_adaptive_params ap{};
+        ap.max_samples = samples_per_pixel / 64 * 64;
+        ap.min_samples = std::min(adaptive_min_samples, ap.max_samples); ap.step_samples = adaptive_step;
+        ap.threshold = adaptive_threshold; ap.dark_floor = adaptive_dark_floor;
+        current_samples_count = 0; passes_rendered = 0;
+        const zenith::accum_handle acc(zr_accum_create(j.ctx, image_width, image_height, nullptr));
+        if (!acc) return ZR_E_DEVICE;
+        // a cancelled run leaves the image of the passes that completed; a refused one (bad counts) leaves nothing
+        const int rc = zr_render_adaptive(j.ctx, j.sc, &j.cam, &j.env, seed, acc.get(), &ap, 0, zenith::flag_ptr(j.flag), &last_adaptive);
+        if ((rc == ZR_OK || rc == ZR_E_CANCELLED) && last_adaptive.passes > 0) {
+            sample_counts.assign(pixels(), 0);
+            int64_t st4[4] = {0, 0, 0, 0};
+            int qrc = zr_accum_resolve(acc.get(), zenith::doubles(render_accumulator));
+            if (qrc == ZR_OK) qrc = zr_accum_sample_counts(acc.get(), reinterpret_cast<int32_t*>(sample_counts.data()));
+            if (qrc == ZR_OK) qrc = zr_accum_state(acc.get(), st4);
+            if (qrc == ZR_OK && rc == ZR_OK) qrc = fetch_variance(acc.get());
+            if (qrc != ZR_OK) return qrc;
+            current_samples_count = (int)st4[1]; passes_rendered = (int)last_adaptive.passes;
+        }
+        if (rc == ZR_OK) lines_rendered = image_height;
+        return rc;
+    }
+    // progressive (the reference's "real-time sample accumulation"): passes of samples_per_pass samples into a device accumulator
+    int render_progressive(const frame_job& j) {
+        const int spp = samples_per_pixel < 1 ? 1 : samples_per_pixel;
+        current_samples_count = 0; passes_rendered = 0;
+        const zenith::accum_handle acc(zr_accum_create(j.ctx, image_width, image_height, nullptr));
+        if (!acc) return ZR_E_DEVICE;
+        while (current_samples_count < spp) {
+            const int n = std::min(samples_per_pass, spp - current_samples_count);
+            int rc = zr_render_accumulate(j.ctx, j.sc, &j.cam, &j.env, seed, acc.get(), n, 0, zenith::flag_ptr(j.flag));
+            // (a cancelled pass is discarded whole: the image stays the one of the passes before it)
+            if (rc == ZR_OK) rc = zr_accum_resolve(acc.get(), zenith::doubles(render_accumulator));
+            if (rc != ZR_OK) return rc;
+            current_samples_count += n; passes_rendered++;
+            lines_rendered = current_samples_count < spp ? (int)((long long)image_height * current_samples_count / spp) : image_height;
+            if (current_samples_count < spp && !j.flag.load()) return ZR_E_CANCELLED;
+        }
+        return spp % 64 == 0 ? fetch_variance(acc.get()) : ZR_OK;
+    }
+    // the first-hit passes whose flags are set, and the denoiser's guides: the public buffers when their flags are set, `guides` otherwise
+    int render_aovs(const frame_job& j, const post_processor& post, guide_frames& guides) {
+        std::vector<color>* const albedo = use_albedo_buffer ? &albedo_buffer : use_denoiser ? &guides.albedo : nullptr;
+        std::vector<color>* const normal = use_normal_buffer ? &normal_buffer : use_denoiser ? &guides.normal : nullptr;
+        std::vector<color>* const zdepth = use_z_depth_buffer ? &z_depth_buffer : nullptr;
+        if (!albedo && !normal && !zdepth) return ZR_OK;
+        auto cleared = [&](std::vector<color>* frame) -> double* { if (frame) frame->assign(pixels(), color(0, 0, 0)); return frame ? zenith::doubles(*frame) : nullptr; };
+        const zr_aov_params ap{post.z_depth_max_dist};
+        return zr_render_aov(j.ctx, j.sc, &j.cam, seed, nullptr, &ap, cleared(albedo), cleared(normal), cleared(zdepth));
+    }
+    // camera.hpp:490: either flag runs the second path and fills BOTH frames; the beauty image is what the reference's loop produces with the
+    // flags on (same stream prefix), so it is not rendered again
+    int render_split_passes(const frame_job& j) {
+        if (!use_reflection && !use_refraction) return ZR_OK;
+        reflection_buffer.assign(pixels(), color(0, 0, 0));
+        refraction_buffer.assign(pixels(), color(0, 0, 0));
+        return zr_render_passes(j.ctx, j.sc, &j.cam, &j.env, seed, nullptr, nullptr, zenith::doubles(reflection_buffer), zenith::doubles(refraction_buffer));
+    }
+    // camera.hpp:268-291; the a-trous filter of zr_denoise stands in for OIDN.  Each frame is filtered only if the one before succeeded.
+    int denoise_frames(const post_processor& post, const guide_frames& guides) {
+        const std::vector<color>& ga = use_albedo_buffer ? albedo_buffer : guides.albedo;
+        const std::vector<color>& gn = use_normal_buffer ? normal_buffer : guides.normal;
+        denoise_buffer = render_accumulator;
+        int rc;
+        if (denoise_variance_guided && variance_buffer.size() == render_accumulator.size()) {
+            rc = denoise_guided(denoise_buffer, variance_buffer, ga, gn);
+            denoise_used_variance = rc == ZR_OK;
+        } else {
+            if (denoise_variance_guided)
+                std::cerr << "[zenith] denoise_variance_guided ignored: no variance (it needs adaptive_threshold, or samples_per_pass with a multiple of 64 samples)\n";
+            rc = denoise(denoise_buffer, ga, gn);
+        }
+        if (rc == ZR_OK && use_reflection) rc = denoise_split_pass(reflection_buffer, post, ga, gn);
+        if (rc == ZR_OK && use_refraction) rc = denoise_split_pass(refraction_buffer, post, ga, gn);
+        return rc;
+    }
+    // a split-pass frame has no variance: the plain filter, then the sharpening the reference applies to it
+    int denoise_split_pass(std::vector<color>& frame, const post_processor& post, const std::vector<color>& albedo, const std::vector<color>& normal) const {
+        const int rc = denoise(frame, albedo, normal);
+        if (rc == ZR_OK && post.use_sharpening) post.apply_sharpening(frame, image_width, image_height, post.sharpen_amount);
+        return rc;
+    }
+    // one call of the denoiser on a context leased for it; a message on failure
+    template <class Call>
+    int on_leased_context(Call&& call) const {
         zenith::context_lease lease(device);
-        zr_ctx* ctx = lease;
+        const int rc = lease.ctx ? call(lease.ctx) : ZR_E_DEVICE;
+        if (rc != ZR_OK) std::cerr << "[zenith] denoise failed: " << zr_last_error() << "\n";
+        return rc;
+    }
+    // apply_denoising (camera.hpp:581-699) in place, with zr_denoise's default parameters
+    int denoise(std::vector<color>& buffer, const std::vector<color>& albedo, const std::vector<color>& normal) const {
         const zr_denoise_params dp{ZR_DENOISE_DEFAULT_ITERATIONS, ZR_DENOISE_DEFAULT_DEMODULATE, ZR_DENOISE_DEFAULT_SIGMA_COLOR, ZR_DENOISE_DEFAULT_SIGMA_NORMAL,
                                    ZR_DENOISE_DEFAULT_SIGMA_ALBEDO, 0.0f};
-        double* p = reinterpret_cast<double*>(buffer.data());
-        const int rc = ctx ? zr_denoise(ctx, &dp, p, reinterpret_cast<const double*>(albedo.data()), reinterpret_cast<const double*>(normal.data()),
-                                        nullptr, image_width, image_height, p)
-                           : ZR_E_DEVICE;
-        if (rc != ZR_OK) std::cerr << "[zenith] denoise failed: " << zr_last_error() << "\n";
-        return rc == ZR_OK;
+        double* p = zenith::doubles(buffer);
+        return on_leased_context([&](zr_ctx* ctx) { return zr_denoise(ctx, &dp, p, zenith::doubles(albedo), zenith::doubles(normal), nullptr, image_width, image_height, p); });
     }
     // the variance-guided filter with zr_denoise_guided's default parameters: `buffer` in place, `variance` left as zr_accum_variance gave it
-    bool denoise_guided(std::vector<color>& buffer, const std::vector<color>& variance, const std::vector<color>& albedo, const std::vector<color>& normal) const {
-        zenith::context_lease lease(device);
-        zr_ctx* ctx = lease;
+    int denoise_guided(std::vector<color>& buffer, const std::vector<color>& variance, const std::vector<color>& albedo, const std::vector<color>& normal) const {
         const zr_denoise_guided_params dp{ZR_DENOISE_GUIDED_DEFAULT_ITERATIONS, ZR_DENOISE_GUIDED_DEFAULT_DEMODULATE, ZR_DENOISE_GUIDED_DEFAULT_SIGMA_VARIANCE,
                                           ZR_DENOISE_GUIDED_DEFAULT_SIGMA_NORMAL, ZR_DENOISE_GUIDED_DEFAULT_SIGMA_ALBEDO, 0.0f, ZR_DENOISE_GUIDED_DEFAULT_EPSILON};
-        double* p = reinterpret_cast<double*>(buffer.data());
-        const int rc = ctx ? zr_denoise_guided(ctx, &dp, p, reinterpret_cast<const double*>(variance.data()), reinterpret_cast<const double*>(albedo.data()),
-                                               reinterpret_cast<const double*>(normal.data()), nullptr, image_width, image_height, p, nullptr)
-                           : ZR_E_DEVICE;
-        if (rc != ZR_OK) std::cerr << "[zenith] denoise failed: " << zr_last_error() << "\n";
-        return rc == ZR_OK;
+        double* p = zenith::doubles(buffer);
+        return on_leased_context([&](zr_ctx* ctx) {
+            return zr_denoise_guided(ctx, &dp, p, zenith::doubles(variance), zenith::doubles(albedo), zenith::doubles(normal), nullptr, image_width, image_height, p, nullptr);
+        });
     }
 };

@@ -331,15 +331,25 @@ def load_scenes():
     if not os.path.exists(SCENES_LIB_PATH):
         raise OSError(f"{SCENES_LIB_PATH} not built: run __graft_entry__.build()")
     s = C.CDLL(SCENES_LIB_PATH)
-    s.zrs_build.restype = C.c_void_p; s.zrs_build.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]
-    s.zrs_free.argtypes = [C.c_void_p]
-    s.zrs_desc.restype = C.POINTER(SceneDesc); s.zrs_desc.argtypes = [C.c_void_p]
-    s.zrs_camera.restype = C.POINTER(Camera); s.zrs_camera.argtypes = [C.c_void_p]
-    s.zrs_env.restype = C.POINTER(Env); s.zrs_env.argtypes = [C.c_void_p]
-    s.zrs_seed.restype = C.c_uint64; s.zrs_seed.argtypes = [C.c_void_p]
-    s.zrs_warnings.restype = C.c_char_p; s.zrs_warnings.argtypes = [C.c_void_p]
-    s.zrs_render_dropin.restype = C.c_int
-    s.zrs_render_dropin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Counters)]
+    vp, i32 = C.c_void_p, C.c_int
+    s.zrs_build.restype = vp; s.zrs_build.argtypes = [C.c_char_p, i32, i32, i32, i32]
+    s.zrs_free.argtypes = [vp]
+    s.zrs_desc.restype = C.POINTER(SceneDesc); s.zrs_desc.argtypes = [vp]
+    s.zrs_camera.restype = C.POINTER(Camera); s.zrs_camera.argtypes = [vp]
+    s.zrs_env.restype = C.POINTER(Env); s.zrs_env.argtypes = [vp]
+    s.zrs_seed.restype = C.c_uint64; s.zrs_seed.argtypes = [vp]
+    s.zrs_warnings.restype = C.c_char_p; s.zrs_warnings.argtypes = [vp]
+    s.zrs_kat_textures.argtypes = [vp, vp, i32]
+    frame = [vp, i32, i32, i32, i32]   # every zrs_render_dropin* begins: handle, width, height, spp, device
+    s.zrs_render_dropin.argtypes = frame + [vp, C.POINTER(Counters)]
+    s.zrs_render_dropin_progressive.argtypes = frame + [i32, vp, vp, i32]
+    s.zrs_render_dropin_adaptive.argtypes = frame + [C.c_double, i32, i32, vp, vp, vp, i32]
+    s.zrs_render_dropin_threads.argtypes = frame + [i32, vp]
+    s.zrs_render_dropin_denoise.argtypes = frame + [i32] + [vp] * 6
+    s.zrs_render_dropin_denoise_guided.argtypes = frame + [C.c_double, i32, i32] + [vp] * 4
+    s.zrs_render_dropin_bvh_debug.argtypes = frame + [i32, C.c_float, vp, vp]
+    s.zrs_dropin_virtuals.argtypes = [vp, vp, i32, C.c_uint64, C.c_uint64, vp, vp]
+    s.zrs_dropin_frame_to_rgb8.argtypes = [vp, i32, i32, vp, vp, C.POINTER(C.c_float)]
     _scenes = s
     return s
 
@@ -370,105 +380,82 @@ class DemoScene:
         self.seed = int(s.zrs_seed(self._h))
         self.warnings = s.zrs_warnings(self._h).decode()
         ids = (C.c_uint32 * 64)()
-        s.zrs_kat_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         self.kat_textures = [int(ids[k]) for k in range(min(64, s.zrs_kat_textures(self._h, ids, 64)))]
+
+    def _frames(self, width, height, *names):
+        """zeroed (H, W, 3) float64 outputs by name for a drop-in render at width x height (0: the scene's own)"""
+        w = width or self.camera.image_width
+        h = height or self.camera.image_height
+        return {k: np.zeros((h, w, 3), dtype=np.float64) for k in names}
+
+    @staticmethod
+    def _rendered(ok):
+        if not ok:
+            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
 
     def render_dropin(self, width=0, height=0, spp=0, device=0):
         """camera::render(world, env, post, flag) of include/zenith/zenith.hpp, end to end."""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        out = np.zeros((h, w, 3), dtype=np.float64)
+        out = self._frames(width, height, "out")["out"]
         ctr = Counters()
-        rc = load_scenes().zrs_render_dropin(self._h, width, height, spp, device, out.ctypes.data, C.byref(ctr))
-        if rc != 0:
-            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        self._rendered(load_scenes().zrs_render_dropin(self._h, width, height, spp, device, out.ctypes.data, C.byref(ctr)) == 0)
         return out, ctr
 
-    def render_dropin_progressive(self, samples_per_pass, width=0, height=0, spp=0, device=0):
+    def render_dropin_progressive(self, samples_per_pass, width=0, height=0, spp=0, device=0, flag=True):
         """camera::render with camera::samples_per_pass set: (frame, current_samples_count afterwards, refreshes of render_accumulator).
-        current_samples_count is -7 going in, so a render that does not touch it (samples_per_pass = 0) reports -7."""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        out = np.zeros((h, w, 3), dtype=np.float64)
+        current_samples_count is -7 going in, so a render that does not touch it (samples_per_pass = 0) reports -7.
+        flag: render_flag going in; with False an unfinished render is the expected outcome and is not raised."""
+        out = self._frames(width, height, "out")["out"]
         info = (C.c_int * 2)()
-        lib = load_scenes()
-        lib.zrs_render_dropin_progressive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        if lib.zrs_render_dropin_progressive(self._h, width, height, spp, device, int(samples_per_pass), out.ctypes.data, info) != 0:
-            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        rc = load_scenes().zrs_render_dropin_progressive(self._h, width, height, spp, device, int(samples_per_pass), out.ctypes.data, info, int(bool(flag)))
+        self._rendered(rc == 0 or (rc == -1 and not flag))
         return out, int(info[0]), int(info[1])
 
-    def render_dropin_adaptive(self, threshold, min_samples=0, step=0, width=0, height=0, spp=0, device=0):
+    def render_dropin_adaptive(self, threshold, min_samples=0, step=0, width=0, height=0, spp=0, device=0, flag=True):
         """camera::render with camera::adaptive_threshold set (min_samples / step 0: the camera's defaults of 64): (frame, camera::sample_counts as
-        (H, W) int32 — all -1 when the render was not adaptive —, current_samples_count afterwards (-7 going in), passes)"""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        out = np.zeros((h, w, 3), dtype=np.float64)
-        counts = np.full((h, w), -1, dtype=np.int32)
+        (H, W) int32 — all -1 when the render was not adaptive —, current_samples_count afterwards (-7 going in), passes).
+        flag: render_flag going in; with False an unfinished render is the expected outcome and is not raised."""
+        out = self._frames(width, height, "out")["out"]
+        counts = np.full(out.shape[:2], -1, dtype=np.int32)
         info = (C.c_int * 2)()
-        lib = load_scenes()
-        lib.zrs_render_dropin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        if lib.zrs_render_dropin_adaptive(self._h, width, height, spp, device, float(threshold), int(min_samples), int(step), out.ctypes.data, counts.ctypes.data,
-                                          info) != 0:
-            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        rc = load_scenes().zrs_render_dropin_adaptive(self._h, width, height, spp, device, float(threshold), int(min_samples), int(step), out.ctypes.data,
+                                                      counts.ctypes.data, info, int(bool(flag)))
+        self._rendered(rc == 0 or (rc == -1 and not flag))
         return out, counts, int(info[0]), int(info[1])
 
     def render_dropin_threads(self, n, width=0, height=0, spp=0, device=0):
         """n drop-in renders, each on a fresh host thread, one after the other (the reference's render-restart pattern,
         main.cpp:1520-1531): (last frame, device contexts the process has created so far)"""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        out = np.zeros((h, w, 3), dtype=np.float64)
-        lib = load_scenes()
-        lib.zrs_render_dropin_threads.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        rc = lib.zrs_render_dropin_threads(self._h, width, height, spp, device, n, out.ctypes.data)
-        if rc < 0:
-            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        out = self._frames(width, height, "out")["out"]
+        rc = load_scenes().zrs_render_dropin_threads(self._h, width, height, spp, device, n, out.ctypes.data)
+        self._rendered(rc >= 0)
         return out, rc
 
     def render_dropin_denoise(self, width=0, height=0, spp=0, device=0, passes=False, sharpening=False):
         """camera::render with use_denoiser (and optionally use_reflection / use_refraction, post.use_sharpening) through
         include/zenith/zenith.hpp: dict of render_accumulator, denoise_buffer, reflection_buffer, refraction_buffer,
         albedo_buffer, normal_buffer as (H, W, 3) float64"""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        names = ("render_accumulator", "denoise_buffer", "reflection_buffer", "refraction_buffer", "albedo_buffer", "normal_buffer")
-        outs = {k: np.zeros((h, w, 3), dtype=np.float64) for k in names}
-        lib = load_scenes()
-        lib.zrs_render_dropin_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+        outs = self._frames(width, height, "render_accumulator", "denoise_buffer", "reflection_buffer", "refraction_buffer", "albedo_buffer", "normal_buffer")
         flags = (1 if passes else 0) | (2 if sharpening else 0)
-        rc = lib.zrs_render_dropin_denoise(self._h, width, height, spp, device, flags, *[outs[k].ctypes.data for k in names])
-        if rc != 0:
-            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        self._rendered(load_scenes().zrs_render_dropin_denoise(self._h, width, height, spp, device, flags, *[o.ctypes.data for o in outs.values()]) == 0)
         return outs
 
     def render_dropin_denoise_guided(self, threshold, samples_per_pass=0, guided=True, width=0, height=0, spp=0, device=0):
         """camera::render with use_denoiser and (guided) denoise_variance_guided, adaptively when threshold > 0, progressively when
         samples_per_pass > 0, else in one shot: dict of render_accumulator, denoise_buffer, variance_buffer ((H, W, 3) float64; all -1 when the
         render left variance_buffer empty) and "guided" (whether the guided filter made denoise_buffer)"""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        names = ("render_accumulator", "denoise_buffer", "variance_buffer")
-        outs = {k: np.zeros((h, w, 3), dtype=np.float64) for k in names}
+        outs = self._frames(width, height, "render_accumulator", "denoise_buffer", "variance_buffer")
         info = (C.c_int * 2)()
-        lib = load_scenes()
-        lib.zrs_render_dropin_denoise_guided.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 4
-        rc = lib.zrs_render_dropin_denoise_guided(self._h, width, height, spp, device, float(threshold), int(samples_per_pass), 1 if guided else 0,
-                                                  *[outs[k].ctypes.data for k in names], info)
-        if rc != 0:
-            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        self._rendered(load_scenes().zrs_render_dropin_denoise_guided(self._h, width, height, spp, device, float(threshold), int(samples_per_pass),
+                                                                      1 if guided else 0, *[o.ctypes.data for o in outs.values()], info) == 0)
         outs["guided"] = bool(info[0])
         return outs
 
     def render_dropin_bvh_debug(self, level, thickness, width=0, height=0, spp=0, device=0):
         """camera::render with global_settings::bvh_debug_mode set through include/zenith/zenith.hpp: (render_accumulator,
         albedo_buffer) as (H, W, 3) float64 (the debug view leaves the AOV buffers as reset_accumulator made them)"""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        out = np.zeros((h, w, 3), dtype=np.float64); aux = np.full((h, w, 3), -1.0)
-        lib = load_scenes()
-        lib.zrs_render_dropin_bvh_debug.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-        if lib.zrs_render_dropin_bvh_debug(self._h, width, height, spp, device, level, thickness, out.ctypes.data, aux.ctypes.data) != 0:
-            raise ZrError(f"drop-in render failed: {load().zr_last_error().decode()}")
+        out, aux = self._frames(width, height, "out", "aux").values()
+        aux.fill(-1.0)
+        self._rendered(load_scenes().zrs_render_dropin_bvh_debug(self._h, width, height, spp, device, level, thickness, out.ctypes.data, aux.ctypes.data) == 0)
         return out, aux
 
     def dropin_virtuals(self, rays8, seed, pixel=0x7ACE):
@@ -476,9 +463,7 @@ class DemoScene:
         (recs[n,16], scat[n,14]) in the layout of `zenith_ref kat <scene> hits`"""
         rays8 = np.ascontiguousarray(rays8, dtype=np.float64).reshape(-1, 8)
         recs = np.zeros((len(rays8), 16)); scat = np.zeros((len(rays8), 14))
-        lib = load_scenes()
-        lib.zrs_dropin_virtuals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-        if lib.zrs_dropin_virtuals(self._h, rays8.ctypes.data, len(rays8), seed, pixel, recs.ctypes.data, scat.ctypes.data) != 0:
+        if load_scenes().zrs_dropin_virtuals(self._h, rays8.ctypes.data, len(rays8), seed, pixel, recs.ctypes.data, scat.ctypes.data) != 0:
             raise ZrError("drop-in hit()/scatter() failed (see stderr)")
         return recs, scat
 
@@ -487,9 +472,7 @@ class DemoScene:
         w, h = self.camera.image_width, self.camera.image_height
         a = np.zeros((h, w, 3), dtype=np.uint8); b = np.zeros((h, w, 3), dtype=np.uint8)
         ex = C.c_float(0)
-        lib = load_scenes()
-        lib.zrs_dropin_frame_to_rgb8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-        rc = lib.zrs_dropin_frame_to_rgb8(self._h, spp, device, a.ctypes.data, b.ctypes.data, C.byref(ex))
+        rc = load_scenes().zrs_dropin_frame_to_rgb8(self._h, spp, device, a.ctypes.data, b.ctypes.data, C.byref(ex))
         if rc != 0:
             raise ZrError(f"drop-in frame pipeline failed ({rc}): {load().zr_last_error().decode()}")
         return a, b, ex.value

@@ -24,6 +24,35 @@ struct handle {
     std::string warnings;
     std::vector<uint32_t> kat_tex;   // flattened ids of zr_demo_scene::kat_textures
 };
+
+// The scene's camera as a drop-in `camera` (which cannot be copied or moved: it holds an atomic, so this is a constructor and not a function that
+// returns one).  spp/width/height <= 0 keep the scene's values.  reset_accumulator() is left to the caller, who sets the camera's flags first.
+struct scene_camera : camera {
+    scene_camera(const handle& h, int width, int height, int spp, int device) {
+        const zr_camera& c = h.s.cam;
+        image_width = width > 0 ? width : c.image_width;
+        image_height = height > 0 ? height : c.image_height;
+        samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
+        max_depth = c.max_depth; vfov = c.vfov;
+        lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
+        lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
+        vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
+        defocus_angle = c.defocus_angle; focus_dist = c.focus_dist;
+        seed = h.s.seed; this->device = device;
+    }
+};
+
+// camera::render over bvh_node(world) as the reference's caller makes it (main.cpp:204, 1520-1521), with render_flag = flag0 going in: whether the frame finished
+bool render_world(const handle& h, camera& cam, const post_processor& post, bool flag0 = true) {
+    std::atomic<bool> flag{flag0};
+    auto bvh_world = make_shared<bvh_node>(h.s.world);
+    cam.render(*bvh_world, h.s.env, post, flag);
+    return cam.lines_rendered.load() == cam.image_height;
+}
+
+void copy_out(const std::vector<color>& frame, double* out) {
+    if (out) std::memcpy(out, frame.data(), frame.size() * sizeof(color));
+}
 }  // namespace
 
 extern "C" {
@@ -58,118 +87,66 @@ int zrs_kat_textures(void* p, uint32_t* ids, int cap) {
 // Renders through the drop-in C++ API exactly as the reference's caller does.  out = W*H*3 doubles.
 // spp/width/height <= 0 keep the scene's values.  Returns 0, or -1 if the accumulator stayed empty.
 int zrs_render_dropin(void* p, int width, int height, int spp, int device, double* out, zr_counters* ctr) {
-    handle* h = (handle*)p;
-    camera cam;
-    const zr_camera& c = h->s.cam;
-    cam.image_width = width > 0 ? width : c.image_width;
-    cam.image_height = height > 0 ? height : c.image_height;
-    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
-    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
-    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
-    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
-    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
-    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
-    cam.seed = h->s.seed; cam.device = device;
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
     cam.reset_accumulator();
-    post_processor post;
-    std::atomic<bool> flag{true};
-    auto bvh_world = make_shared<bvh_node>(h->s.world);  // main.cpp:204
-    cam.render(*bvh_world, h->s.env, post, flag);
-    if (cam.lines_rendered.load() != cam.image_height) return -1;
-    std::memcpy(out, cam.render_accumulator.data(), cam.render_accumulator.size() * sizeof(color));
+    if (!render_world(h, cam, post_processor())) return -1;
+    copy_out(cam.render_accumulator, out);
     if (ctr) *ctr = cam.last_counters;
     return 0;
 }
 
-// camera::render with camera::samples_per_pass set (the progressive render of include/zenith/zenith.hpp).  info[0] = current_samples_count after the render,
-// info[1] = the number of times render_accumulator was refreshed.  current_samples_count holds -7 when render() is called, so a render that leaves it alone
-// (samples_per_pass = 0) reports -7.  Returns 0, or -1 if the render did not finish.
-int zrs_render_dropin_progressive(void* p, int width, int height, int spp, int device, int samples_per_pass, double* out, int* info) {
-    handle* h = (handle*)p;
-    camera cam;
-    const zr_camera& c = h->s.cam;
-    cam.image_width = width > 0 ? width : c.image_width;
-    cam.image_height = height > 0 ? height : c.image_height;
-    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
-    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
-    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
-    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
-    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
-    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
-    cam.seed = h->s.seed; cam.device = device;
+// camera::render with camera::samples_per_pass set (the progressive render of include/zenith/zenith.hpp) and render_flag = flag0 going in.  info[0] =
+// current_samples_count after the render, info[1] = the number of times render_accumulator was refreshed.  current_samples_count holds -7 when render() is
+// called, so a render that leaves it alone (samples_per_pass = 0) reports -7.  Returns 0, or -1 if the render did not finish; `out` and `info` are filled either way.
+int zrs_render_dropin_progressive(void* p, int width, int height, int spp, int device, int samples_per_pass, double* out, int* info, int flag0) {
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
     cam.reset_accumulator();
     cam.samples_per_pass = samples_per_pass;
     cam.current_samples_count = -7;
-    post_processor post;
-    std::atomic<bool> flag{true};
-    auto bvh_world = make_shared<bvh_node>(h->s.world);
-    cam.render(*bvh_world, h->s.env, post, flag);
+    const bool done = render_world(h, cam, post_processor(), flag0 != 0);
     if (info) { info[0] = cam.current_samples_count; info[1] = cam.passes_rendered; }
-    if (cam.lines_rendered.load() != cam.image_height) return -1;
-    std::memcpy(out, cam.render_accumulator.data(), cam.render_accumulator.size() * sizeof(color));
-    return 0;
+    copy_out(cam.render_accumulator, out);
+    return done ? 0 : -1;
 }
 
-// camera::render with camera::adaptive_threshold set (min_samples and step <= 0 keep the camera's defaults).  counts = W*H ints (camera::sample_counts; left alone when
-// the render was not adaptive), info[0] = current_samples_count after the render (-7 going in), info[1] = passes.  Returns 0, or -1 if the render did not finish.
-int zrs_render_dropin_adaptive(void* p, int width, int height, int spp, int device, double threshold, int min_samples, int step, double* out, int* counts, int* info) {
-    handle* h = (handle*)p;
-    camera cam;
-    const zr_camera& c = h->s.cam;
-    cam.image_width = width > 0 ? width : c.image_width;
-    cam.image_height = height > 0 ? height : c.image_height;
-    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
-    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
-    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
-    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
-    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
-    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
-    cam.seed = h->s.seed; cam.device = device;
+// camera::render with camera::adaptive_threshold set (min_samples and step <= 0 keep the camera's defaults) and render_flag = flag0 going in.  counts = W*H ints
+// (camera::sample_counts; left alone when the render left it empty), info[0] = current_samples_count after the render (-7 going in), info[1] = passes.  Returns 0,
+// or -1 if the render did not finish; `out`, `counts` and `info` are filled either way.
+int zrs_render_dropin_adaptive(void* p, int width, int height, int spp, int device, double threshold, int min_samples, int step, double* out, int* counts, int* info,
+                               int flag0) {
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
     cam.reset_accumulator();
     cam.adaptive_threshold = threshold;
     if (min_samples > 0) cam.adaptive_min_samples = min_samples;
     if (step > 0) cam.adaptive_step = step;
     cam.current_samples_count = -7;
-    post_processor post;
-    std::atomic<bool> flag{true};
-    auto bvh_world = make_shared<bvh_node>(h->s.world);
-    cam.render(*bvh_world, h->s.env, post, flag);
+    const bool done = render_world(h, cam, post_processor(), flag0 != 0);
     if (info) { info[0] = cam.current_samples_count; info[1] = cam.passes_rendered; }
-    if (cam.lines_rendered.load() != cam.image_height) return -1;
-    std::memcpy(out, cam.render_accumulator.data(), cam.render_accumulator.size() * sizeof(color));
+    copy_out(cam.render_accumulator, out);
     if (counts && !cam.sample_counts.empty()) std::memcpy(counts, cam.sample_counts.data(), cam.sample_counts.size() * sizeof(int));
-    return 0;
+    return done ? 0 : -1;
 }
 
 // camera::render with global_settings::bvh_debug_mode set (debug_bvh_level = level, bvh_thickness = thickness) through the drop-in API; the
 // settings are restored afterwards.  `aux`, when not null, receives albedo_buffer (which the debug view leaves as reset_accumulator made it).
 // Returns 0, or -1 if the render did not finish.
 int zrs_render_dropin_bvh_debug(void* p, int width, int height, int spp, int device, int level, float thickness, double* out, double* aux) {
-    handle* h = (handle*)p;
-    camera cam;
-    const zr_camera& c = h->s.cam;
-    cam.image_width = width > 0 ? width : c.image_width;
-    cam.image_height = height > 0 ? height : c.image_height;
-    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
-    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
-    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
-    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
-    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
-    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
-    cam.seed = h->s.seed; cam.device = device;
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
     cam.use_albedo_buffer = aux != nullptr;
     cam.reset_accumulator();
     post_processor post;
     post.debug.bvh = true;   // main.cpp:1039-1044
     const bool m0 = global_settings::bvh_debug_mode; const float t0 = global_settings::bvh_thickness; const int l0 = global_settings::debug_bvh_level;
     global_settings::bvh_debug_mode = true; global_settings::bvh_thickness = thickness; global_settings::debug_bvh_level = level;
-    std::atomic<bool> flag{true};
-    auto bvh_world = make_shared<bvh_node>(h->s.world);
-    cam.render(*bvh_world, h->s.env, post, flag);
+    const bool done = render_world(h, cam, post);
     global_settings::bvh_debug_mode = m0; global_settings::bvh_thickness = t0; global_settings::debug_bvh_level = l0;
-    if (cam.lines_rendered.load() != cam.image_height) return -1;
-    std::memcpy(out, cam.render_accumulator.data(), cam.render_accumulator.size() * sizeof(color));
-    if (aux) std::memcpy(aux, cam.albedo_buffer.data(), cam.albedo_buffer.size() * sizeof(color));
+    if (!done) return -1;
+    copy_out(cam.render_accumulator, out);
+    copy_out(cam.albedo_buffer, aux);
     return 0;
 }
 
@@ -190,26 +167,14 @@ int zrs_render_dropin_threads(void* p, int width, int height, int spp, int devic
 // what main.cpp's render thread followed by save_render_pass(RGB) / save_render_pass(REFLECTIONS) does.
 // rgb8 / refl8: W*H*3 bytes each; exposure_out: the auto-exposure value written back to post.exposure (camera.hpp:258-266)
 int zrs_dropin_frame_to_rgb8(void* p, int spp, int device, unsigned char* rgb8, unsigned char* refl8, float* exposure_out) {
-    handle* h = (handle*)p;
-    camera cam;
-    const zr_camera& c = h->s.cam;
-    cam.image_width = c.image_width; cam.image_height = c.image_height;
-    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
-    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
-    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
-    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
-    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
-    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
-    cam.seed = h->s.seed; cam.device = device;
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, 0, 0, spp, device);
     cam.use_reflection = true;
     cam.reset_accumulator();
     post_processor post;
     post.use_auto_exposure = true; post.exposure_compensation_stops = 0.5f;
     post.use_bloom = true; post.bloom_threshold = 0.8f; post.use_sharpening = true; post.use_aces_tone_mapping = true;
-    std::atomic<bool> flag{true};
-    auto bvh_world = make_shared<bvh_node>(h->s.world);
-    cam.render(*bvh_world, h->s.env, post, flag);
-    if (cam.lines_rendered.load() != cam.image_height) return -1;
+    if (!render_world(h, cam, post)) return -1;
     std::vector<unsigned char> a, b;
     if (!cam.process_framebuffer(cam.render_accumulator, post, a) || !cam.process_framebuffer(cam.reflection_buffer, post, b, true, true)) return -2;
     std::memcpy(rgb8, a.data(), a.size());
@@ -225,31 +190,17 @@ int zrs_dropin_frame_to_rgb8(void* p, int spp, int device, unsigned char* rgb8, 
 // render did not finish.
 int zrs_render_dropin_denoise(void* p, int width, int height, int spp, int device, int flags, double* acc, double* den, double* refl, double* refr,
                               double* alb, double* nrm) {
-    handle* h = (handle*)p;
-    camera cam;
-    const zr_camera& c = h->s.cam;
-    cam.image_width = width > 0 ? width : c.image_width;
-    cam.image_height = height > 0 ? height : c.image_height;
-    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
-    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
-    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
-    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
-    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
-    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
-    cam.seed = h->s.seed; cam.device = device;
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
     cam.use_denoiser = true;
     cam.use_reflection = cam.use_refraction = (flags & 1) != 0;
     cam.reset_accumulator();
     post_processor post;
     post.use_sharpening = (flags & 2) != 0;
-    std::atomic<bool> flag{true};
-    auto bvh_world = make_shared<bvh_node>(h->s.world);
-    cam.render(*bvh_world, h->s.env, post, flag);
-    if (cam.lines_rendered.load() != cam.image_height) return -1;
-    const std::pair<const std::vector<color>*, double*> outs[] = {{&cam.render_accumulator, acc}, {&cam.denoise_buffer, den}, {&cam.reflection_buffer, refl},
-                                                                  {&cam.refraction_buffer, refr}, {&cam.albedo_buffer, alb}, {&cam.normal_buffer, nrm}};
-    for (const auto& o : outs)
-        if (o.second) std::memcpy(o.second, o.first->data(), o.first->size() * sizeof(color));
+    if (!render_world(h, cam, post)) return -1;
+    copy_out(cam.render_accumulator, acc); copy_out(cam.denoise_buffer, den);
+    copy_out(cam.reflection_buffer, refl); copy_out(cam.refraction_buffer, refr);
+    copy_out(cam.albedo_buffer, alb); copy_out(cam.normal_buffer, nrm);
     return 0;
 }
 
@@ -259,35 +210,17 @@ int zrs_render_dropin_denoise(void* p, int width, int height, int spp, int devic
 // or -1 if the render did not finish.
 int zrs_render_dropin_denoise_guided(void* p, int width, int height, int spp, int device, double threshold, int samples_per_pass, int guided, double* acc,
                                      double* den, double* var, int* info) {
-    handle* h = (handle*)p;
-    camera cam;
-    const zr_camera& c = h->s.cam;
-    cam.image_width = width > 0 ? width : c.image_width;
-    cam.image_height = height > 0 ? height : c.image_height;
-    cam.samples_per_pixel = spp > 0 ? spp : c.samples_per_pixel;
-    cam.max_depth = c.max_depth; cam.vfov = c.vfov;
-    cam.lookfrom = point3(c.lookfrom[0], c.lookfrom[1], c.lookfrom[2]);
-    cam.lookat = point3(c.lookat[0], c.lookat[1], c.lookat[2]);
-    cam.vup = vec3(c.vup[0], c.vup[1], c.vup[2]);
-    cam.defocus_angle = c.defocus_angle; cam.focus_dist = c.focus_dist;
-    cam.seed = h->s.seed; cam.device = device;
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
     cam.use_denoiser = true;
     cam.denoise_variance_guided = guided != 0;
     cam.adaptive_threshold = threshold;
     cam.samples_per_pass = samples_per_pass;
     cam.reset_accumulator();
-    post_processor post;
-    std::atomic<bool> flag{true};
-    auto bvh_world = make_shared<bvh_node>(h->s.world);
-    cam.render(*bvh_world, h->s.env, post, flag);
-    if (cam.lines_rendered.load() != cam.image_height) return -1;
-    const size_t n = cam.render_accumulator.size() * 3;
-    if (acc) std::memcpy(acc, cam.render_accumulator.data(), n * sizeof(double));
-    if (den) std::memcpy(den, cam.denoise_buffer.data(), n * sizeof(double));
-    if (var) {
-        if (cam.variance_buffer.size() * 3 == n) std::memcpy(var, cam.variance_buffer.data(), n * sizeof(double));
-        else std::fill(var, var + n, -1.0);
-    }
+    if (!render_world(h, cam, post_processor())) return -1;
+    copy_out(cam.render_accumulator, acc); copy_out(cam.denoise_buffer, den);
+    if (cam.variance_buffer.size() == cam.render_accumulator.size()) copy_out(cam.variance_buffer, var);
+    else if (var) std::fill(var, var + cam.render_accumulator.size() * 3, -1.0);
     if (info) { info[0] = cam.denoise_used_variance ? 1 : 0; info[1] = cam.current_samples_count; }
     return 0;
 }

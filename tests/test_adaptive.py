@@ -636,3 +636,20 @@ def test_dropin_adaptive(ctx):
     small, _ = ds.render_dropin(spp=20)
     frame1, counts1, current1, _ = ds.render_dropin_adaptive(thr, spp=20)
     assert np.array_equal(frame1, small) and (counts1 == -1).all() and current1 == -7
+
+
+@pytest.mark.gpu
+def test_dropin_adaptive_cancelled_before_the_first_pass(ctx):
+    """render_flag clear going in: zr_render_adaptive looks at the flag before its first pass and is cancelled after 0 passes, so nothing is resolved — the
+    frame stays zero, sample_counts stays empty (counts all -1), current_samples_count is the 0 the route reset it to (from -7) and passes is 0.  The leased
+    context stays usable: the same render with the flag set gives afterwards, byte for byte, what it gave before."""
+    ds = demo_scene("mix0")
+    size = dict(width=96, height=64, spp=128)
+    before = ds.render_dropin_adaptive(0.05, **size)
+    assert before[2] > 0 and before[3] > 0 and (before[1] > 0).all()
+    frame, counts, current, passes = ds.render_dropin_adaptive(0.05, flag=False, **size)
+    assert frame.shape == (64, 96, 3) and not frame.any()
+    assert counts.shape == (64, 96) and (counts == -1).all()
+    assert (current, passes) == (0, 0)
+    after = ds.render_dropin_adaptive(0.05, flag=True, **size)
+    assert after[0].tobytes() == before[0].tobytes() and after[1].tobytes() == before[1].tobytes() and after[2:] == before[2:]

@@ -380,3 +380,19 @@ def test_dropin_samples_per_pass(ctx):
     frame0, count0, updates0 = ds.render_dropin_progressive(0, spp=20)
     assert np.array_equal(frame0, one_shot)
     assert (count0, updates0) == (-7, 0)
+
+
+@pytest.mark.gpu
+def test_dropin_cancelled_before_the_first_pass(ctx):
+    """render_flag clear going in: zr_render_accumulate refuses the first batch before it begins, so the frame stays zero, the route has reset
+    current_samples_count from -7 to 0 and no pass reached render_accumulator.  The leased context stays usable: the same render with the flag set
+    gives afterwards, byte for byte, what it gave before."""
+    ds = demo_scene("mix0")
+    size = dict(width=96, height=64, spp=20)
+    before = ds.render_dropin_progressive(8, **size)
+    assert before[1:] == (20, 3)
+    frame, count, updates = ds.render_dropin_progressive(8, flag=False, **size)
+    assert frame.shape == (64, 96, 3) and not frame.any()
+    assert (count, updates) == (0, 0)
+    after = ds.render_dropin_progressive(8, flag=True, **size)
+    assert after[0].tobytes() == before[0].tobytes() and after[1:] == before[1:]
