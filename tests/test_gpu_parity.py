@@ -949,7 +949,8 @@ def test_other_kernel_variants_match_reference(name, variant, built, monkeypatch
 
 def test_frames_beyond_the_streaming_limits_fall_back(ctx):
     """The streaming pipeline packs the bounce counter into 8 bits (max_depth <= 250); a deeper camera is rendered by the
-    pixel-group megakernel automatically — same image contract, checked against the oracle (mix2: grey sky, long paths)."""
+    pixel-group megakernel automatically — same image contract, checked against the oracle (mix2: grey sky, long paths).
+    Its paths end long before 250; tests/test_frame_edges.py has paths that run 250 segments, the switch at 251 and a side of 65536."""
     from oracle import zr_oracle_py as zo
     from raytracer_project_amd import capi
     ds = demo_scene("mix2")
