@@ -11,19 +11,9 @@
 
 #include <vector>
 
-#include "zr_device_types.h"
+#include "zr_entry.h"   // BuildSceneIn, BuildPrimOut: the views the entry rules work over
 
 namespace zr {
-
-// the scene as the caller gave it, uploaded unchanged
-struct BuildSceneIn {
-    const double* spheres = nullptr; const uint32_t* sphere_mat = nullptr;
-    const double* tri_v = nullptr; const double* tri_n = nullptr; const uint32_t* tri_mat = nullptr;
-    const double* tri_uv = nullptr;      // 6 per triangle, or null
-    const double* cubes = nullptr; const uint32_t* cube_mat = nullptr;
-    const zr_medium* media = nullptr; const zr_xform_op* ops = nullptr;
-    const double* group_box = nullptr;   // per zr_group: lo[3], hi[3] of its triangles in their own space
-};
 
 struct BuildParams {   // no defaults here: zr_commit.cpp fills every field from the knobs both builders share (zr_flatten.h: read_build_knobs)
     float ct;            // cost of a node visit
@@ -34,18 +24,6 @@ struct BuildParams {   // no defaults here: zr_commit.cpp fills every field from
     int radius;          // PLOC search radius (clusters on either side in Morton order)
     int top_clusters;    // PLOC stops at this many clusters and the host's binned-SAH builder arranges them (0: PLOC to the root); worlds under 8 x this: PLOC alone.
                          // zr_commit.cpp picks n / 64 within 4096 ... 65536
-};
-
-// where a tree's leaves put their primitive records: the scene's final arrays and the first index this tree may use per leaf kind
-struct BuildPrimOut {
-    double* spheres = nullptr; uint32_t* sphere_mat = nullptr;
-    double* tri_v = nullptr; double* tri_s = nullptr;
-    double* tri_uv = nullptr;            // null when the scene has no texture coordinates
-    double* cubes = nullptr; uint32_t* cube_mat = nullptr;
-    double* pcubes = nullptr; uint32_t* pcube_mat = nullptr;
-    DInstance* insts = nullptr; uint32_t* inst_group = nullptr;
-    uint32_t base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t* src[8] = {};   // per leaf kind (may be null): each leaf primitive's index in the caller's arrays, as Flattener::note_src
 };
 
 // a built tree: device records with indices local to the tree (relocate() moves them into the scene's arrays)

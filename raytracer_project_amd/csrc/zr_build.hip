@@ -18,7 +18,7 @@
 //                 of the wider node keeps every box within `open_ratio` of its true area (Flattener::plan_quad's rule), writes
 //                 its 64-byte record and names its inner children quad roots.  Forward over the batches: exact stack demand.
 //   6. pairs      one 64-byte sibling-pair record per inner node (pair-BVH walk of the megakernel / zr_trace / AOV kernels)
-//   7. emit       one thread per primitive: its record(s) in leaf order (bare, baked, placed: the host's put_* rules)
+//   7. emit       one thread per primitive: its record(s) in leaf order (bare, baked, placed: zr_entry.h put_entry, the host's own rules)
 // Media and wrapped objects (a handful per scene, each dragging inner primitives behind it) are listed for the host to finish.
 //
 // Quantisation is exact without long double: origin + q * scale (float + small integer x power of two) is compared with a box
@@ -62,76 +62,7 @@ __device__ __forceinline__ float half_area(const float* lo, const float* hi) {
     return dx * dy + dy * dz + dz * dx;
 }
 
-// ---- 1. boxes ---------------------------------------------------------------------------------------------------------
-struct DBox { double lo[3], hi[3]; };
-
-__device__ DBox prim_box(const BuildSceneIn& in, uint32_t type, uint32_t idx);
-__device__ DBox apply_op_box(const zr_xform_op& op, const DBox& b) {
-    DBox o;
-    if (op.kind == ZR_OP_TRANSLATE) { for (int k = 0; k < 3; k++) { o.lo[k] = b.lo[k] + op.a[k]; o.hi[k] = b.hi[k] + op.a[k]; } return o; }   // translate.hpp:12
-    if (op.kind == ZR_OP_SCALE) {   // scale.hpp:11-17
-        for (int k = 0; k < 3; k++) { const double a0 = b.lo[k] * op.a[k], a1 = b.hi[k] * op.a[k]; o.lo[k] = fmin(a0, a1); o.hi[k] = fmax(a0, a1); }
-        return o;
-    }
-    if (op.kind == ZR_OP_MATERIAL) return b;
-    // rotate_*.hpp constructors: the box of the eight rotated corners (rotate_y: of the TRUE geometry).  A rotation
-    // about one axis turns the rectangle [a0, a1] x [b0, b1] of the other two; its four corners, with the constructors' arithmetic
-    // (scalars only: no indexed local arrays — the first version indexed a local double[3] inside the corner loop and
-    // came back from the gfx950 compiler with the unrotated coordinate overwritten, found by ZR_BUILD_CHECK)
-    const double sn = op.a[0], co = op.a[1];
-    const int ia = op.kind == ZR_OP_ROTATE_X ? 1 : 0, ib = op.kind == ZR_OP_ROTATE_Z ? 1 : 2, ic = 3 - ia - ib;   // (a, b) plane, c = the axis
-    const double a0 = ia == 0 ? b.lo[0] : b.lo[1], a1 = ia == 0 ? b.hi[0] : b.hi[1];
-    const double b0 = ib == 1 ? b.lo[1] : b.lo[2], b1 = ib == 1 ? b.hi[1] : b.hi[2];
-    const double c0 = ic == 0 ? b.lo[0] : (ic == 1 ? b.lo[1] : b.lo[2]), c1 = ic == 0 ? b.hi[0] : (ic == 1 ? b.hi[1] : b.hi[2]);
-    // rotate_y: x' = co x - sn z, z' = sn x + co z   (a = x, b = z)
-    // rotate_x: y' = co y - sn z, z' = sn y + co z   (a = y, b = z)
-    // rotate_z: x' = co x - sn y, y' = sn x + co y   (a = x, b = y)
-    const double u00 = co * a0 - sn * b0, u10 = co * a1 - sn * b0, u01 = co * a0 - sn * b1, u11 = co * a1 - sn * b1;
-    const double v00 = sn * a0 + co * b0, v10 = sn * a1 + co * b0, v01 = sn * a0 + co * b1, v11 = sn * a1 + co * b1;
-    const double ulo = fmin(fmin(u00, u10), fmin(u01, u11)), uhi = fmax(fmax(u00, u10), fmax(u01, u11));
-    const double vlo = fmin(fmin(v00, v10), fmin(v01, v11)), vhi = fmax(fmax(v00, v10), fmax(v01, v11));
-    if (op.kind == ZR_OP_ROTATE_Y) { o.lo[0] = ulo; o.hi[0] = uhi; o.lo[1] = c0; o.hi[1] = c1; o.lo[2] = vlo; o.hi[2] = vhi; }
-    else if (op.kind == ZR_OP_ROTATE_X) { o.lo[0] = c0; o.hi[0] = c1; o.lo[1] = ulo; o.hi[1] = uhi; o.lo[2] = vlo; o.hi[2] = vhi; }
-    else { o.lo[0] = ulo; o.hi[0] = uhi; o.lo[1] = vlo; o.hi[1] = vhi; o.lo[2] = c0; o.hi[2] = c1; }
-    return o;
-}
-__device__ DBox chain_box(const BuildSceneIn& in, uint32_t type, uint32_t idx, uint32_t cf, uint32_t cn) {
-    DBox b = prim_box(in, type, idx);
-    for (int k = (int)cn - 1; k >= 0; k--) b = apply_op_box(in.ops[cf + k], b);   // innermost wrapper first
-    return b;
-}
-__device__ DBox prim_box(const BuildSceneIn& in, uint32_t type, uint32_t idx) {
-    DBox b;
-    if (type == ZR_PRIM_GROUP) { for (int k = 0; k < 3; k++) { b.lo[k] = in.group_box[(size_t)idx * 6 + k]; b.hi[k] = in.group_box[(size_t)idx * 6 + 3 + k]; } return b; }
-    if (type == ZR_PRIM_SPHERE) {   // sphere.hpp:12-14 (raw radius argument)
-        const double* q = in.spheres + (size_t)idx * 4;
-        for (int k = 0; k < 3; k++) { b.lo[k] = fmin(q[k] - q[3], q[k] + q[3]); b.hi[k] = fmax(q[k] - q[3], q[k] + q[3]); }
-    } else if (type == ZR_PRIM_TRIANGLE) {   // triangle.hpp:84-101
-        const double* v = in.tri_v + (size_t)idx * 9;
-        for (int k = 0; k < 3; k++) {
-            b.lo[k] = fmin(v[k], fmin(v[3 + k], v[6 + k]));
-            b.hi[k] = fmax(v[k], fmax(v[3 + k], v[6 + k]));
-            if (b.hi[k] - b.lo[k] < 0.0001) { b.lo[k] -= 0.0001; b.hi[k] += 0.0001; }
-        }
-    } else if (type == ZR_PRIM_CUBE) {   // cube.hpp:34-41
-        const double* q = in.cubes + (size_t)idx * 12;
-        for (int k = 0; k < 3; k++) { b.lo[k] = q[6 + k] - 0.00005; b.hi[k] = q[9 + k] + 0.00005; }
-    } else {   // constant_medium.hpp:79-81: the boundary's box (a sphere or a cube under the medium's own chain)
-        const zr_medium m = in.media[idx];
-        DBox bb;
-        if (m.boundary_type == ZR_PRIM_SPHERE) {
-            const double* q = in.spheres + (size_t)m.boundary_index * 4;
-            for (int k = 0; k < 3; k++) { bb.lo[k] = fmin(q[k] - q[3], q[k] + q[3]); bb.hi[k] = fmax(q[k] - q[3], q[k] + q[3]); }
-        } else {
-            const double* q = in.cubes + (size_t)m.boundary_index * 12;
-            for (int k = 0; k < 3; k++) { bb.lo[k] = q[6 + k] - 0.00005; bb.hi[k] = q[9 + k] + 0.00005; }
-        }
-        for (int k = (int)m.chain_count - 1; k >= 0; k--) bb = apply_op_box(in.ops[m.chain_first + k], bb);
-        b = bb;
-    }
-    return b;
-}
-
+// ---- 1. boxes (the rules: zr_entry.h chain_box / prim_box) --------------------------------------------------------------------------
 // order-preserving map float <-> uint for atomic min / max
 __device__ __forceinline__ uint32_t f2o(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 __device__ __forceinline__ float o2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
@@ -144,7 +75,7 @@ __global__ __launch_bounds__(256) void k_boxes(BuildSceneIn in, const zr_object*
     bool ok = true;
     const bool live = i < n;
     if (live) {
-        DBox b; uint32_t kind;
+        BuildBox b; uint32_t kind;
         if (objs) { const zr_object o = objs[i]; b = chain_box(in, o.type, o.index, o.chain_first, o.chain_count); kind = code[i] & 7u; }
         else { b = prim_box(in, ZR_PRIM_TRIANGLE, first_triangle + i); kind = ZR_PRIM_TRIANGLE; }
         PBox p;
@@ -682,19 +613,7 @@ __global__ void k_pair_leaf_root(const BNode* __restrict__ bn, const uint32_t* _
     pairs[0] = pr;
 }
 
-// ---- 7. primitive records (the host's Flattener::put_* rules) ------------------------------------------------------------------
-__device__ void put_triangle_raw(const BuildPrimOut& out, size_t di, const double* v, const double* nn, uint32_t mat, uint32_t refaced) {
-    double* tv = out.tri_v + di * ZR_TRI_STRIDE;
-    double* t = out.tri_s + di * 20;
-    for (int k = 0; k < 9; k++) { tv[k] = v[k]; t[k] = v[k]; t[9 + k] = nn[k]; }
-    t[18] = __longlong_as_double((long long)(unsigned long long)mat);
-    t[19] = __longlong_as_double(refaced ? (refaced % 2 ? 1ll : 3ll) : 0ll);   // bit 0: under translate / rotate_y wrappers, bit 1: an even number of them
-}
-// a stored triangle's texture coordinates travel with it, unchanged (Flattener::put_triangle_uv)
-__device__ void put_triangle_uv(const BuildSceneIn& in, const BuildPrimOut& out, size_t di, uint32_t idx) {
-    if (!out.tri_uv) return;
-    for (int k = 0; k < 6; k++) out.tri_uv[di * 6 + k] = in.tri_uv[(size_t)idx * 6 + k];
-}
+// ---- 7. primitive records (the rules: zr_entry.h put_entry) ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_emit(BuildSceneIn in, const zr_object* __restrict__ objs, const uint8_t* __restrict__ code, uint32_t first_triangle, uint32_t n,
                                               const uint32_t* __restrict__ dfs_obj, const uint8_t* __restrict__ dfs_kind, const uint32_t* __restrict__ rank, BuildPrimOut out,
                                               uint32_t* __restrict__ compound, uint32_t* __restrict__ n_compound) {
@@ -705,88 +624,13 @@ __global__ __launch_bounds__(256) void k_emit(BuildSceneIn in, const zr_object* 
     zr_object o; uint32_t bk = 0;
     if (objs) { o = objs[oi]; bk = code[oi] >> 4; }
     else { o.type = ZR_PRIM_TRIANGLE; o.index = first_triangle + oi; o.chain_first = 0; o.chain_count = 0; }
-    if (out.src[kind]) out.src[kind][di] = (kind == ZR_KIND_WRAPPED || kind == ZR_KIND_INSTANCE) ? oi : o.index;
+    note_src(out, kind, di, oi, o);
     if (kind == ZR_PRIM_MEDIUM || kind == ZR_KIND_WRAPPED) {   // compound: the host finishes these few (inner primitives behind the leaf ranges)
         const uint32_t at = atomicAdd(n_compound, 1u);
         compound[2 * at] = oi; compound[2 * at + 1] = (uint32_t)di;
         return;
     }
-    if (o.type == ZR_PRIM_GROUP) {
-        DInstance inst; inst.chain_first = o.chain_first; inst.chain_count = o.chain_count; inst.root = 0; inst.pad_ = 0;
-        out.insts[di] = inst; out.inst_group[di] = o.index;
-        return;
-    }
-    if (bk == 1) {   // put_baked_triangle: a triangle under translate / rotate_* / material_instance wrappers, stored in world space
-        double v[9], nn[9];
-        for (int k = 0; k < 9; k++) { v[k] = in.tri_v[(size_t)o.index * 9 + k]; nn[k] = in.tri_n[(size_t)o.index * 9 + k]; }
-        uint32_t mat = in.tri_mat[o.index];
-        uint32_t refaced = 0;
-        for (int k = (int)o.chain_count - 1; k >= 0; k--) {
-            const zr_xform_op op = in.ops[o.chain_first + k];
-            const double sn = op.a[0], co = op.a[1];
-            for (int c = 0; c < 3; c++) {
-                double* pp = v + 3 * c; double* q = nn + 3 * c;
-                switch (op.kind) {
-                    case ZR_OP_TRANSLATE: pp[0] += op.a[0]; pp[1] += op.a[1]; pp[2] += op.a[2]; break;
-                    case ZR_OP_ROTATE_Y: { double x = pp[0], z = pp[2]; pp[0] = co * x - sn * z; pp[2] = sn * x + co * z;
-                                           x = q[0]; z = q[2]; q[0] = co * x - sn * z; q[2] = sn * x + co * z; } break;
-                    case ZR_OP_ROTATE_X: { double y = pp[1], z = pp[2]; pp[1] = co * y - sn * z; pp[2] = sn * y + co * z;
-                                           y = q[1]; z = q[2]; q[1] = co * y - sn * z; q[2] = sn * y + co * z; } break;
-                    case ZR_OP_ROTATE_Z: { double x = pp[0], y = pp[1]; pp[0] = co * x - sn * y; pp[1] = sn * x + co * y;
-                                           x = q[0]; y = q[1]; q[0] = co * x - sn * y; q[1] = sn * x + co * y; } break;
-                    default: break;
-                }
-            }
-            if (op.kind == ZR_OP_TRANSLATE || op.kind == ZR_OP_ROTATE_Y) refaced++;
-            if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
-        }
-        put_triangle_raw(out, di, v, nn, mat, refaced);
-        put_triangle_uv(in, out, di, o.index);
-    } else if (bk == 3) {   // put_baked_sphere: uniform scale / translate / material_instance
-        const double* q = in.spheres + (size_t)o.index * 4;
-        double c[3] = {q[0], q[1], q[2]}, r = fmax(0.0, q[3]);
-        uint32_t mat = in.sphere_mat[o.index];
-        bool refaced = false;   // (at most one translate: classify_object)
-        for (int k = (int)o.chain_count - 1; k >= 0; k--) {
-            const zr_xform_op op = in.ops[o.chain_first + k];
-            if (op.kind == ZR_OP_SCALE) { c[0] *= op.a[0]; c[1] *= op.a[0]; c[2] *= op.a[0]; r *= op.a[0]; }
-            else if (op.kind == ZR_OP_TRANSLATE) { c[0] += op.a[0]; c[1] += op.a[1]; c[2] += op.a[2]; refaced = true; }
-            else if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
-        }
-        double* d = out.spheres + di * 4;
-        d[0] = c[0]; d[1] = c[1]; d[2] = c[2]; d[3] = r;
-        out.sphere_mat[di] = refaced ? (mat | 0x80000000u) : mat;
-    } else if (bk == 4) {   // put_pcube: cube -> [scale] -> [rotate_y] -> translate in one record
-        const double* q = in.cubes + (size_t)o.index * 12;
-        double rec[ZR_PCUBE_STRIDE] = {q[0], q[1], q[2], q[3], q[4], q[5], 0, 0, 0, 0, 1, 0, 1, 1, 1, 0};
-        uint32_t mat = in.cube_mat[o.index];
-        for (int k = (int)o.chain_count - 1; k >= 0; k--) {
-            const zr_xform_op op = in.ops[o.chain_first + k];
-            if (op.kind == ZR_OP_TRANSLATE) { rec[6] = op.a[0]; rec[7] = op.a[1]; rec[8] = op.a[2]; }
-            else if (op.kind == ZR_OP_ROTATE_Y) { rec[9] = op.a[0]; rec[10] = op.a[1]; rec[11] = 1.0; }
-            else if (op.kind == ZR_OP_SCALE) { rec[12] = op.a[0]; rec[13] = op.a[1]; rec[14] = op.a[2]; rec[15] = 1.0; }
-            else if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
-        }
-        for (int k = 0; k < ZR_PCUBE_STRIDE; k++) out.pcubes[di * ZR_PCUBE_STRIDE + k] = rec[k];
-        out.pcube_mat[di] = mat;
-    } else {
-        const bool mat_only = bk == 2;   // material-only chain: the outermost wrapper is applied last
-        if (o.type == ZR_PRIM_SPHERE) {
-            const double* q = in.spheres + (size_t)o.index * 4;
-            double* d = out.spheres + di * 4;
-            d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = fmax(0.0, q[3]);   // sphere.hpp:9
-            out.sphere_mat[di] = mat_only ? in.ops[o.chain_first].mat : in.sphere_mat[o.index];
-        } else if (o.type == ZR_PRIM_TRIANGLE) {
-            double v[9], nn[9];
-            for (int k = 0; k < 9; k++) { v[k] = in.tri_v[(size_t)o.index * 9 + k]; nn[k] = in.tri_n[(size_t)o.index * 9 + k]; }
-            put_triangle_raw(out, di, v, nn, in.tri_mat[o.index], false);
-            put_triangle_uv(in, out, di, o.index);
-        } else {
-            const double* q = in.cubes + (size_t)o.index * 12;
-            for (int k = 0; k < 6; k++) out.cubes[di * 6 + k] = q[k];
-            out.cube_mat[di] = mat_only ? in.ops[o.chain_first].mat : in.cube_mat[o.index];
-        }
-    }
+    put_entry(in, out, o, bk, di);
 }
 
 // ---- relocation: a tree's local indices -> the scene's arrays ------------------------------------------------------------------

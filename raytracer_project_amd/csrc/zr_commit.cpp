@@ -200,13 +200,12 @@ int commit_device(zr_scene* s, const CommitPlan& plan, const PhaseTimer& outer, 
     if (ph.on)
         std::fprintf(stderr, "[zr] device build: boxes+keys %.2f, sort %.2f, PLOC %.2f (%u iterations), order %.2f, 4-wide %.2f, pairs %.2f, emit %.2f ms; depth %u, %u pairs, %u quads\n",
                      world.ms[0], world.ms[1], world.ms[2], world.ploc_iterations, world.ms[3], world.ms[4], world.ms[5], world.ms[6], world.depth, world.n_pairs, world.n_quads);
-    if (world.want_boxes) {   // self-check: every object's device box must contain the box the host's Boxer computes for it
-        std::vector<zr::BuildBox> gb(ng);
-        for (size_t g = 0; g < ng; g++) for (int k = 0; k < 3; k++) { gb[g].lo[k] = gbox[g * 6 + k]; gb[g].hi[k] = gbox[g * 6 + 3 + k]; }
-        Boxer boxer{*s, &gb};
+    if (world.want_boxes) {   // self-check: every object's device box must contain the box the host's compilation of chain_box (zr_entry.h) computes for it
+        zr::BuildSceneIn hin = scene_view(*s);
+        hin.group_box = gbox.data();
         size_t bad = 0;
         for (uint32_t k = 0; k < n; k++) {
-            const zr::BuildBox hb = boxer.chain(objs[k].type, objs[k].index, objs[k].chain_first, objs[k].chain_count);
+            const zr::BuildBox hb = zr::chain_box(hin, objs[k].type, objs[k].index, objs[k].chain_first, objs[k].chain_count);
             const float* d = &world.dbg_boxes[(size_t)k * 8];
             bool ok = true;
             for (int a = 0; a < 3; a++) if (!((double)d[a] <= hb.lo[a]) || !((double)d[4 + a] >= hb.hi[a])) ok = false;

@@ -51,7 +51,7 @@ __device__ __forceinline__ void set_face(Rec& rec, V3 rd, V3 outward) {  // hitt
     rec.front = dot(rd, outward) < 0;
     rec.n = rec.front ? outward : -outward;
 }
-// A primitive stored in world space from under translate / rotate_y wrappers (zr_flatten.h put_baked_triangle / put_baked_sphere): each of them calls
+// A primitive stored in world space from under translate / rotate_y wrappers (zr_entry.h put_triangle / put_baked_sphere): each of them calls
 // set_face_normal again on the normal the primitive has already turned against the ray (translate.hpp:29, rotate_y.hpp:70).  With x = dot(d, outward) of the
 // primitive's own call: for x != 0 the turned normal faces the ray, so every later call answers front_face = true and keeps it; for x == 0 (or NaN) the first
 // call leaves -outward with front_face = false, and every later one finds dot == -0 or +0, answers false again and flips the normal once more — after an odd

@@ -1,67 +1,22 @@
-// zr_flatten.h — from the caller's world list to the arrays the kernels read: bounding boxes the way the reference's constructors compute them (Boxer), the
-// classification of world entries (bare / baked / placed / wrapped), validation, the commit plan both builders work from, the Flattener, which turns the
-// builder's tree into sibling-pair records, 4-wide quantised nodes and the primitive arrays in leaf order, and the host builder's CPU half.  No HIP in
-// here: zr_commit.cpp includes it for the library, tests/native/flatten_check.cpp compiles it with zr_bvh.cpp alone.
+// zr_flatten.h — from the caller's world list to the arrays the kernels read: the classification of world entries (bare / baked / placed / wrapped),
+// validation, the commit plan both builders work from, the Flattener, which turns the builder's tree into sibling-pair records, 4-wide quantised nodes and
+// the primitive arrays in leaf order, and the host builder's CPU half.  An entry's bounding box and its stored record are zr_entry.h's, shared with the
+// device builder.  No HIP in here: zr_commit.cpp includes it for the library, tests/native/flatten_check.cpp compiles it with zr_bvh.cpp alone.
 #pragma once
+#include "zr_entry.h"
 #include "zr_scene_input.h"
 
 namespace {
 
-// ---- bounding boxes of world-list entries, following the reference's constructors --------------------
-struct Boxer {
-    const SceneInput& s;
-    const std::vector<zr::BuildBox>* group_box = nullptr;   // per zr_group: the box of its triangles in their own space
-    zr::BuildBox prim(uint32_t type, uint32_t idx) const {
-        zr::BuildBox b;
-        if (type == ZR_PRIM_GROUP) return (*group_box)[idx];
-        if (type == ZR_PRIM_SPHERE) {  // sphere.hpp:12-14 (raw radius argument)
-            const double* q = &s.spheres[(size_t)idx * 4];
-            for (int k = 0; k < 3; k++) { b.lo[k] = std::fmin(q[k] - q[3], q[k] + q[3]); b.hi[k] = std::fmax(q[k] - q[3], q[k] + q[3]); }
-        } else if (type == ZR_PRIM_TRIANGLE) {  // triangle.hpp:84-101
-            const double* v = &s.tri_v[(size_t)idx * 9];
-            for (int k = 0; k < 3; k++) {
-                b.lo[k] = std::fmin(v[k], std::fmin(v[3 + k], v[6 + k]));
-                b.hi[k] = std::fmax(v[k], std::fmax(v[3 + k], v[6 + k]));
-                if (b.hi[k] - b.lo[k] < 0.0001) { b.lo[k] -= 0.0001; b.hi[k] += 0.0001; }
-            }
-        } else if (type == ZR_PRIM_CUBE) {  // cube.hpp:34-41
-            const double* q = &s.cubes[(size_t)idx * 12];
-            for (int k = 0; k < 3; k++) { b.lo[k] = q[6 + k] - 0.00005; b.hi[k] = q[9 + k] + 0.00005; }
-        } else {  // constant_medium.hpp:79-81
-            const zr_medium& m = s.media[idx];
-            b = chain(m.boundary_type, m.boundary_index, m.chain_first, m.chain_count);
-        }
-        return b;
-    }
-    zr::BuildBox chain(uint32_t type, uint32_t idx, uint32_t cf, uint32_t cn) const {
-        if (cn == 0) return prim(type, idx);
-        zr::BuildBox in = chain(type, idx, cf + 1, cn - 1), b;
-        const zr_xform_op& op = s.ops[cf];
-        if (op.kind == ZR_OP_TRANSLATE) {  // translate.hpp:12
-            for (int k = 0; k < 3; k++) { b.lo[k] = in.lo[k] + op.a[k]; b.hi[k] = in.hi[k] + op.a[k]; }
-            return b;
-        }
-        if (op.kind == ZR_OP_SCALE) {  // scale.hpp:11-17
-            for (int k = 0; k < 3; k++) { double a0 = in.lo[k] * op.a[k], a1 = in.hi[k] * op.a[k]; b.lo[k] = std::fmin(a0, a1); b.hi[k] = std::fmax(a0, a1); }
-            return b;
-        }
-        if (op.kind == ZR_OP_MATERIAL) return in;
-        for (int k = 0; k < 3; k++) { b.lo[k] = kInf; b.hi[k] = -kInf; }
-        const double sn = op.a[0], co = op.a[1];  // rotate_*.hpp constructors: the 8 corners
-        for (int i = 0; i < 2; i++) for (int j = 0; j < 2; j++) for (int k = 0; k < 2; k++) {
-            double x = i ? in.hi[0] : in.lo[0], y = j ? in.hi[1] : in.lo[1], z = k ? in.hi[2] : in.lo[2];
-            double t[3] = {x, y, z};
-            // rotate_y.hpp:26-27 builds its box with the INVERSE rotation (+sin) although hit() maps object points with
-            // (cos x - sin z, sin x + cos z) (rotate_y.hpp:63-64): for children that are not symmetric about the y axis the
-            // reference's box misses real geometry and what gets culled depends on its random tree.  Bound the true geometry.
-            if (op.kind == ZR_OP_ROTATE_Y) { t[0] = co * x - sn * z; t[2] = sn * x + co * z; }
-            else if (op.kind == ZR_OP_ROTATE_X) { t[1] = co * y - sn * z; t[2] = sn * y + co * z; }
-            else { t[0] = co * x - sn * y; t[1] = sn * x + co * y; }
-            for (int q = 0; q < 3; q++) { b.lo[q] = std::fmin(b.lo[q], t[q]); b.hi[q] = std::fmax(b.hi[q], t[q]); }
-        }
-        return b;
-    }
-};
+// the host's arrays as the entry rules read them (zr_entry.h); group_box: per zr_group the box of its triangles in their own space, or null
+inline zr::BuildSceneIn scene_view(const SceneInput& s, const std::vector<zr::BuildBox>* group_box = nullptr) {
+    zr::BuildSceneIn in;
+    in.spheres = s.spheres.data(); in.sphere_mat = s.sphere_mat.data();
+    in.tri_v = s.tri_v.data(); in.tri_n = s.tri_n.data(); in.tri_mat = s.tri_mat.data(); in.tri_uv = s.tri_uv.empty() ? nullptr : s.tri_uv.data();
+    in.cubes = s.cubes.data(); in.cube_mat = s.cube_mat.data(); in.media = s.media.data(); in.ops = s.ops.data();
+    if (group_box && !group_box->empty()) in.group_box = group_box->data()->lo;
+    return in;
+}
 
 inline float f_down(double x) {
     float f = (float)x;
@@ -75,18 +30,18 @@ inline float f_up(double x) {
 }
 
 // what a world-list entry becomes in the tree: its leaf kind, and whether the host stores it "baked" (0 as is, 1 baked triangle,
-// 2 material-only chain, 3 baked sphere, 4 placed cube) — see Flattener::put_baked_triangle / put_baked_sphere / put_pcube
+// 2 material-only chain, 3 baked sphere, 4 placed cube) — see zr_entry.h: put_triangle under a chain, put_baked_sphere, put_pcube
 inline void classify_object(const SceneInput& s, const zr_object& o, bool bake, uint32_t& kind, uint8_t& baked) {
     kind = o.chain_count ? ZR_KIND_WRAPPED : o.type;
     baked = 0;
     if (o.type == ZR_PRIM_GROUP) { kind = ZR_KIND_INSTANCE; return; }   // placed as one object, whatever its chain
     if (!bake || o.chain_count == 0) return;
-    if (o.type == ZR_PRIM_TRIANGLE) {   // see Flattener::put_baked_triangle
+    if (o.type == ZR_PRIM_TRIANGLE) {   // see zr_entry.h put_triangle
         bool ok = true;
         for (uint32_t q = 0; q < o.chain_count; q++) if (s.ops[o.chain_first + q].kind == ZR_OP_SCALE) ok = false;
         if (ok) { baked = 1; kind = ZR_PRIM_TRIANGLE; }
     }
-    if (o.type == ZR_PRIM_SPHERE) {   // see Flattener::put_baked_sphere
+    if (o.type == ZR_PRIM_SPHERE) {   // see zr_entry.h put_baked_sphere
         bool ok = true, moved = false; uint32_t mat = s.sphere_mat[o.index], translates = 0;
         for (int q = (int)o.chain_count - 1; q >= 0 && ok; q--) {
             const zr_xform_op& op = s.ops[o.chain_first + q];
@@ -97,7 +52,7 @@ inline void classify_object(const SceneInput& s, const zr_object& o, bool bake, 
         }
         if (ok && moved && translates <= 1 && mat < 0x7FFFFFFFu) { baked = 3; kind = ZR_PRIM_SPHERE; }
     }
-    if (o.type == ZR_PRIM_CUBE) {   // see Flattener::put_pcube: [translate], [translate, rotate_y], each optionally followed by a scale — outermost first
+    if (o.type == ZR_PRIM_CUBE) {   // see zr_entry.h put_pcube: [translate], [translate, rotate_y], each optionally followed by a scale — outermost first
         int pat = 0; bool ok = true;   // 0 nothing yet, 1 translate seen, 2 translate then rotate_y seen, 3 ... then a scale (the innermost wrapper)
         for (uint32_t q = 0; q < o.chain_count && ok; q++) {
             const zr_xform_op& op = s.ops[o.chain_first + q];
@@ -317,7 +272,8 @@ struct Flattener {
     zr::RawArray<uint32_t> leaf_first; // per build node: device index of a leaf's first primitive
     int quad_depth = 0;
     zr::RawArray<double> spheres, tri_v, tri_s, cubes, pcubes;
-    size_t uv_base = 0;            // the triangles' texture coordinates, 6 per stored triangle, start at tri_s[uv_base], behind the last shading record (0: the scene has none)
+    const zr::BuildSceneIn in = scene_view(s);   // what the entry rules (zr_entry.h) read ...
+    zr::BuildPrimOut out;                        // ... and where they write: the arrays above and below (allocate_arrays; a group's flattener: the world's, base[] moved)
     zr::RawArray<uint32_t> sphere_mat, cube_mat, pcube_mat;
     zr::RawArray<zr::DMedium> media;
     zr::RawArray<zr::DWrapped> wrapped;
@@ -326,6 +282,8 @@ struct Flattener {
     const std::vector<zr::BuildResult>* runs = nullptr;   // per zr_group: the tree over its triangles (object space), built by the caller
     std::vector<uint32_t> run_root;                       // per group: pair index of its subtree's root
     std::vector<uint32_t> run_tri_base, run_qroot, run_demand;   // per group: first triangle (device index), its root among the 4-wide nodes, its worst-case stack entries
+    std::vector<std::vector<zr_object>> run_objs;         // per group, while run() works: its triangles as a world list of bare entries ...
+    std::vector<std::unique_ptr<Flattener>> run_fl;       // ... and the flattener of its tree over them: leaf order, pair records and 4-wide nodes on local indices
     bool root_in_array = false;                           // a group's own flattener: the root is a quantised node like any other (quads[0])
     size_t n_sph = 0, n_tri = 0, n_cube = 0, n_media = 0;   // filled sizes of the arrays that grow behind their leaf ranges (the arrays are sized exactly)
     std::function<void()> after_primitives;   // called by run() once spheres / triangles / cubes / media / wrapped are complete
@@ -392,188 +350,15 @@ struct Flattener {
         for (auto& x : th) x.join();
     }
 
-    // ---- one primitive record at a given index of its kind's array ------------------------------------------------------
-    static constexpr uint32_t kKeepMaterial = 0xFFFFFFFEu;
-    // `mat` != kKeepMaterial: the primitive sits under material_instance wrappers only, which do nothing but replace rec.mat
-    // (material_instance.hpp:12-28) — it is stored bare with the outermost instance's material
-    void put_sphere(size_t di, uint32_t idx, uint32_t mat) {
-        const double* q = &s.spheres[(size_t)idx * 4];
-        double* d = &spheres[di * ZR_SPHERE_DOUBLES];
-        d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = std::fmax(0, q[3]);  // sphere.hpp:9
-        sphere_mat[di] = mat != kKeepMaterial ? mat : s.sphere_mat[idx];
-    }
-    void put_triangle_raw(size_t di, const double* v, const double* nn, uint32_t mat, uint32_t refaced) {
-        std::memcpy(&tri_v[di * ZR_TRI_STRIDE], v, 72);
-        double* t = &tri_s[di * ZR_TRI_SHADE_DOUBLES];
-        std::memcpy(t, v, 72); std::memcpy(t + 9, nn, 72);
-        uint64_t mbits = mat, fbits = refaced ? (refaced % 2 ? 1u : 3u) : 0u;   // bit 0: under translate / rotate_y wrappers, bit 1: an even number of them
-        std::memcpy(t + 18, &mbits, 8); std::memcpy(t + 19, &fbits, 8);
-    }
-    // a stored triangle's texture coordinates travel with it, unchanged (baked or not: they are no geometry)
-    void put_triangle_uv(size_t di, uint32_t idx) { if (uv_base) std::memcpy(&tri_s[uv_base + di * 6], &s.tri_uv[(size_t)idx * 6], 48); }
-    void put_triangle(size_t di, uint32_t idx) {
-        put_triangle_raw(di, &s.tri_v[(size_t)idx * 9], &s.tri_n[(size_t)idx * 9], s.tri_mat[idx], 0);
-        put_triangle_uv(di, idx);
-    }
-    void put_cube(size_t di, uint32_t idx, uint32_t mat) {
-        std::memcpy(&cubes[di * ZR_CUBE_DOUBLES], &s.cubes[(size_t)idx * 12], ZR_CUBE_DOUBLES * sizeof(double));
-        cube_mat[di] = mat != kKeepMaterial ? mat : s.cube_mat[idx];
-    }
-    // A triangle under a chain of translate / rotate_x,y,z / material_instance wrappers is stored in WORLD space as a bare
-    // triangle: vertices and (un-normalised) vertex normals mapped object -> world with the wrappers' own forward maps
-    // (translate.hpp:24-27, rotate_*.hpp hit(): the maps apply_op_rec uses for hit points), material = the outermost
-    // material_instance, plus how many translate / rotate_y wrappers the chain holds: each calls set_face_normal again on the
-    // normal the triangle has already turned against the ray, which answers front_face = true unless dot(d, normal) is exactly
-    // 0 (zr_device.h reface() restates both cases from the world-space dot product — the wrappers' maps are
-    // exact where sin and cos are 0 and 1, and elsewhere a dot product within rounding of 0 has no sign to agree on in either space).  t is the same in both spaces (the wrappers do not normalise the transformed direction), so
-    // only the last bits of the hit differ from transforming the ray — and every mesh the reference's scenes place in the
-    // world (model -> material_instance -> rotate -> translate) runs on the bare-triangle fast path instead of paying a
-    // chain transform per candidate.  scale is excluded: it would change which triangles count as degenerate.
-    void put_baked_triangle(size_t di, const zr_object& o) {
-        double v[9], nn[9];
-        std::memcpy(v, &s.tri_v[(size_t)o.index * 9], sizeof v);
-        std::memcpy(nn, &s.tri_n[(size_t)o.index * 9], sizeof nn);
-        uint32_t mat = s.tri_mat[o.index];
-        uint32_t refaced = 0;
-        for (int k = (int)o.chain_count - 1; k >= 0; k--) {   // innermost wrapper first, as the hit record travels outwards
-            const zr_xform_op& op = s.ops[o.chain_first + k];
-            const double sn = op.a[0], co = op.a[1];
-            for (int c = 0; c < 3; c++) {
-                double* p = v + 3 * c; double* q = nn + 3 * c;
-                switch (op.kind) {
-                    case ZR_OP_TRANSLATE: p[0] += op.a[0]; p[1] += op.a[1]; p[2] += op.a[2]; break;
-                    case ZR_OP_ROTATE_Y: { double x = p[0], z = p[2]; p[0] = co * x - sn * z; p[2] = sn * x + co * z;
-                                           x = q[0]; z = q[2]; q[0] = co * x - sn * z; q[2] = sn * x + co * z; } break;
-                    case ZR_OP_ROTATE_X: { double y = p[1], z = p[2]; p[1] = co * y - sn * z; p[2] = sn * y + co * z;
-                                           y = q[1]; z = q[2]; q[1] = co * y - sn * z; q[2] = sn * y + co * z; } break;
-                    case ZR_OP_ROTATE_Z: { double x = p[0], y = p[1]; p[0] = co * x - sn * y; p[1] = sn * x + co * y;
-                                           x = q[0]; y = q[1]; q[0] = co * x - sn * y; q[1] = sn * x + co * y; } break;
-                    default: break;
-                }
-            }
-            if (op.kind == ZR_OP_TRANSLATE || op.kind == ZR_OP_ROTATE_Y) refaced++;
-            if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
-        }
-        put_triangle_raw(di, v, nn, mat, refaced);
-        put_triangle_uv(di, o.index);
-    }
-    // A sphere under uniform scale / translate / material_instance wrappers (the demo scene's instanced spheres:
-    // scale -> material_instance -> translate) is the sphere (c s + offset, r s): same t, same unit normal, same u/v and
-    // tangent (no rotation involved); bit 31 of its material word records that a translate calls set_face_normal again on the turned
-    // normal (zr_device.h reface(); one bit: classify_object leaves a sphere under two or more translates to the interpreter).
-    void put_baked_sphere(size_t di, const zr_object& o) {
-        const double* q = &s.spheres[(size_t)o.index * 4];
-        double c[3] = {q[0], q[1], q[2]}, r = std::fmax(0, q[3]);
-        uint32_t mat = s.sphere_mat[o.index];
-        bool refaced = false;
-        for (int k = (int)o.chain_count - 1; k >= 0; k--) {
-            const zr_xform_op& op = s.ops[o.chain_first + k];
-            if (op.kind == ZR_OP_SCALE) { for (double& x : c) x *= op.a[0]; r *= op.a[0]; }
-            else if (op.kind == ZR_OP_TRANSLATE) { c[0] += op.a[0]; c[1] += op.a[1]; c[2] += op.a[2]; refaced = true; }
-            else if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
-        }
-        double* d = &spheres[di * ZR_SPHERE_DOUBLES];
-        d[0] = c[0]; d[1] = c[1]; d[2] = c[2]; d[3] = r;
-        sphere_mat[di] = refaced ? (mat | 0x80000000u) : mat;
-    }
-    // A cube under translate, or under rotate_y then translate, either with a scale as the innermost wrapper (material_instance wrappers
-    // anywhere) — how every cube of the reference's scenes is placed (scene_management.hpp:132-139 and the scaled, turned instances of its
-    // master cube, :178-201; cfg5's walls and boxes) — is stored as a PLACED CUBE: the cube's own numbers plus the wrappers' parameters in one
-    // 128-byte record.  The device applies the wrappers' ray and hit-record maps in the
-    // chain's order with the chain's arithmetic (zr_device.h pcube_ray / object_rec), so results are those of the wrapped object;
-    // what is saved is the op-list loop, its loads and the registers of the generic chain code in the traversal kernel.
-    void put_pcube(size_t di, const zr_object& o) {
-        const double* q = &s.cubes[(size_t)o.index * 12];
-        double rec[ZR_PCUBE_STRIDE] = {q[0], q[1], q[2], q[3], q[4], q[5], 0, 0, 0, 0, 1, 0, 1, 1, 1, 0};
-        uint32_t mat = s.cube_mat[o.index];
-        for (int k = (int)o.chain_count - 1; k >= 0; k--) {   // inside-out: the outermost material_instance is applied last
-            const zr_xform_op& op = s.ops[o.chain_first + k];
-            if (op.kind == ZR_OP_TRANSLATE) { rec[6] = op.a[0]; rec[7] = op.a[1]; rec[8] = op.a[2]; }
-            else if (op.kind == ZR_OP_ROTATE_Y) { rec[9] = op.a[0]; rec[10] = op.a[1]; rec[11] = 1.0; }
-            else if (op.kind == ZR_OP_SCALE) { rec[12] = op.a[0]; rec[13] = op.a[1]; rec[14] = op.a[2]; rec[15] = 1.0; }
-            else if (op.kind == ZR_OP_MATERIAL) mat = op.mat;
-        }
-        std::memcpy(&pcubes[di * ZR_PCUBE_STRIDE], rec, sizeof rec);
-        pcube_mat[di] = mat;
-    }
-    // where leaf primitive `di` of kind `kind` came from: the world-list entry for wrapped objects and placed runs, else the primitive's own index
-    void note_src(uint32_t kind, size_t di, uint32_t oi) {
-        if (want_src) src[kind & 7][di] = (kind == ZR_KIND_WRAPPED || kind == ZR_KIND_INSTANCE) ? oi : objs[oi].index;
-    }
-    // object `oi` as a leaf primitive of a plain kind (sphere / triangle / cube / placed cube) at index di of that kind's array
-    void put_leaf_object(uint32_t oi, size_t di) {
-        const zr_object& o = objs[oi];
-        const uint8_t bk = commit_plan ? commit_plan->code[oi] >> 4 : 0;
-        if (o.type == ZR_PRIM_GROUP) { zr::DInstance in{}; in.chain_first = o.chain_first; in.chain_count = o.chain_count; in.root = run_root[o.index]; insts[di] = in; inst_group[di] = o.index; }
-        else if (bk == 1) put_baked_triangle(di, o);
-        else if (bk == 3) put_baked_sphere(di, o);
-        else if (bk == 4) put_pcube(di, o);
-        else {
-            const uint32_t mat = bk == 2 ? s.ops[o.chain_first].mat : kKeepMaterial;   // material-only chain: the outermost wrapper is applied last
-            if (o.type == ZR_PRIM_SPHERE) put_sphere(di, o.index, mat);
-            else if (o.type == ZR_PRIM_TRIANGLE) put_triangle(di, o.index);
-            else put_cube(di, o.index, mat);
-        }
-    }
     // a primitive that is not a leaf object itself — a medium's boundary, the object inside a wrapper chain — goes behind the leaf
     // ranges of its kind's array (serial: such objects are few)
     uint32_t append_inner(uint32_t type, uint32_t idx) {
         switch (type) {
-            case ZR_PRIM_SPHERE: put_sphere(n_sph, idx, kKeepMaterial); return (uint32_t)n_sph++;
-            case ZR_PRIM_TRIANGLE: put_triangle(n_tri, idx); return (uint32_t)n_tri++;
-            case ZR_PRIM_CUBE: put_cube(n_cube, idx, kKeepMaterial); return (uint32_t)n_cube++;
+            case ZR_PRIM_SPHERE: zr::put_sphere(in, out, n_sph, idx, zr::kKeepMaterial); return (uint32_t)n_sph++;
+            case ZR_PRIM_TRIANGLE: zr::put_triangle(in, out, n_tri, idx); return (uint32_t)n_tri++;
+            case ZR_PRIM_CUBE: zr::put_cube(in, out, n_cube, idx, zr::kKeepMaterial); return (uint32_t)n_cube++;
             default: { const size_t di = n_media++; put_medium(di, idx); return (uint32_t)di; }
         }
-    }
-    // A group's subtree: its triangles, unbaked, behind the leaf ranges of the triangle arrays in the order its leaves name them, and
-    // its sibling-pair records from pair index `base` on, numbered in pre-order (= ascending build-node id, as in index_nodes).
-    // Returns the number of pair records written (at least one: a run that fits one leaf gets a pair with an empty second child).
-    uint32_t emit_run(uint32_t g, uint32_t base) {
-        const zr::BuildResult& rb = (*runs)[g];
-        static_assert(zr::NodeArray::zero_filled, "the id-range scans below read slots the builder never wrote: they must read as zero");
-        const zr_group& grp = s.groups[g];
-        // the run's triangles in the order of its leaves by ascending node id — the order index_nodes() gives a tree's leaves, so that
-        // the run's 4-wide nodes (emit_run_quads, numbered by a flattener of their own) name the same indices
-        run_tri_base[g] = (uint32_t)n_tri;
-        std::vector<uint32_t> first_of(rb.nodes.size(), 0);
-        for (size_t id = 0; id < rb.nodes.size(); id++) {
-            const zr::BuildNode& n = rb.nodes[id];
-            if (!n.count) continue;
-            first_of[id] = (uint32_t)n_tri;
-            for (uint32_t k = 0; k < n.count; k++) {
-                if (want_src) src[ZR_PRIM_TRIANGLE][n_tri] = grp.first_triangle + rb.order[n.first + k];
-                put_triangle(n_tri, grp.first_triangle + rb.order[n.first + k]); n_tri++;
-            }
-        }
-        auto leaf_tris = [&](const zr::BuildNode& n) { return first_of[(size_t)(&n - &rb.nodes[0])]; };
-        if (rb.nodes[0].count) {
-            const zr::BuildNode& n = rb.nodes[0];
-            for (int k = 0; k < 3; k++) { pairs[base].lo[0][k] = f_down(n.box.lo[k]); pairs[base].hi[0][k] = f_up(n.box.hi[k]); }
-            pairs[base].child[0] = leaf_tris(n); pairs[base].meta[0] = ((ZR_PRIM_TRIANGLE + 1u) << 16) | n.count;
-            empty_child(base, 1);
-            return 1;
-        }
-        std::vector<uint32_t> ids;   // inner nodes, ascending id = pre-order
-        for (size_t id = 0; id < rb.nodes.size(); id++) { const zr::BuildNode& n = rb.nodes[id]; if (n.count == 0 && n.left == (int32_t)id + 1) ids.push_back((uint32_t)id); }
-        auto pair_index = [&](uint32_t id) { return base + (uint32_t)(std::lower_bound(ids.begin(), ids.end(), id) - ids.begin()); };
-        for (size_t p = 0; p < ids.size(); p++) {
-            const zr::BuildNode& n = rb.nodes[ids[p]];
-            const int32_t ch[2] = {n.left, n.right};
-            for (int slot = 0; slot < 2; slot++) {
-                const zr::BuildNode& c = rb.nodes[ch[slot]];
-                zr::NodePair& pr = pairs[base + p];
-                for (int k = 0; k < 3; k++) { pr.lo[slot][k] = f_down(c.box.lo[k]); pr.hi[slot][k] = f_up(c.box.hi[k]); }
-                if (c.count) { pr.child[slot] = leaf_tris(c); pr.meta[slot] = ((ZR_PRIM_TRIANGLE + 1u) << 16) | c.count; }
-                else { pr.child[slot] = pair_index((uint32_t)ch[slot]); pr.meta[slot] = 0; }
-            }
-        }
-        return (uint32_t)ids.size();
-    }
-    static uint32_t run_pairs(const zr::BuildResult& rb) {   // pair records emit_run will write
-        if (rb.nodes.empty() || rb.nodes[0].count) return 1;
-        uint32_t n = 0;
-        for (size_t id = 0; id < rb.nodes.size(); id++) { const zr::BuildNode& q = rb.nodes[id]; if (q.count == 0 && q.left == (int32_t)id + 1) n++; }
-        return n;
     }
     void put_medium(size_t di, uint32_t idx) {
         const zr_medium& m = s.media[idx];
@@ -590,7 +375,7 @@ struct Flattener {
     void finish_compounds(const std::vector<Compound>& todo) {
         for (const Compound& c : todo) {
             const zr_object& o = objs[c.oi];
-            note_src(c.kind, c.di, c.oi);
+            zr::note_src(out, c.kind, c.di, c.oi, o);
             if (c.kind == ZR_PRIM_MEDIUM) { put_medium(c.di, o.index); continue; }
             zr::DWrapped w{};
             w.type = o.type; w.chain_first = o.chain_first; w.chain_count = o.chain_count;
@@ -602,12 +387,15 @@ struct Flattener {
     void allocate_arrays(const CommitPlan& p) {
         const size_t* z = p.size;
         spheres.allocate(z[ZR_PRIM_SPHERE] * ZR_SPHERE_DOUBLES); sphere_mat.allocate(z[ZR_PRIM_SPHERE]);
-        uv_base = s.tri_uv.empty() ? 0 : z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES;
-        tri_v.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_STRIDE); tri_s.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES + (uv_base ? z[ZR_PRIM_TRIANGLE] * 6 : 0));
+        const size_t uv = s.tri_uv.empty() ? 0 : 6;   // the triangles' texture coordinates, 6 per stored triangle, behind the last shading record
+        tri_v.allocate(z[ZR_PRIM_TRIANGLE] * ZR_TRI_STRIDE); tri_s.allocate(z[ZR_PRIM_TRIANGLE] * (ZR_TRI_SHADE_DOUBLES + uv));
         cubes.allocate(z[ZR_PRIM_CUBE] * ZR_CUBE_DOUBLES); cube_mat.allocate(z[ZR_PRIM_CUBE]);
         pcubes.allocate(z[ZR_KIND_PCUBE] * ZR_PCUBE_STRIDE); pcube_mat.allocate(z[ZR_KIND_PCUBE]);
         media.allocate(z[ZR_PRIM_MEDIUM]); wrapped.allocate(z[ZR_KIND_WRAPPED]);
         n_sph = p.cnt[ZR_PRIM_SPHERE]; n_tri = p.cnt[ZR_PRIM_TRIANGLE]; n_cube = p.cnt[ZR_PRIM_CUBE]; n_media = p.cnt[ZR_PRIM_MEDIUM];
+        out.spheres = spheres.data(); out.sphere_mat = sphere_mat.data(); out.tri_v = tri_v.data(); out.tri_s = tri_s.data();
+        out.tri_uv = uv && z[ZR_PRIM_TRIANGLE] ? tri_s.data() + z[ZR_PRIM_TRIANGLE] * ZR_TRI_SHADE_DOUBLES : nullptr;
+        out.cubes = cubes.data(); out.cube_mat = cube_mat.data(); out.pcubes = pcubes.data(); out.pcube_mat = pcube_mat.data();
     }
     bool plain_media() const {   // every medium's boundary is an unwrapped sphere or cube
         for (size_t k = 0; k < media.size(); k++) if (media[k].chain_count != 0) return false;
@@ -754,8 +542,11 @@ struct Flattener {
         int32_t* kids = qp.kids; int nk = 0;
         zr::NodeQ nq{};
         for (int ax = 0; ax < 3; ax++) nq.scale[ax] = 1;
-        if (br.nodes[node_id].count) kids[nk++] = node_id;  // a world that is a single leaf
-        else {
+        if (br.nodes[node_id].count) {   // a tree that is a single leaf: as a stored root (a group's) a node with one child
+            kids[nk++] = node_id;
+            double w = 1;
+            if (!is_root && !quantise(kids, nk, nq, &w)) const_cast<Flattener*>(this)->quant_ok_a = false;
+        } else {
             nk = 2;
             kids[0] = br.nodes[node_id].left; kids[1] = br.nodes[node_id].right;
             double worst = 1;
@@ -888,44 +679,43 @@ struct Flattener {
         }
         if (threads > 1 && br.nodes.size() > 65536) pool.reset(new Pool(threads - 1));
         struct Unpool { std::unique_ptr<Pool>& p; ~Unpool() { p.reset(); } } unpool{pool};   // the workers end with run()
-        leaf_first.allocate(br.nodes.size());   // fresh pages: zero
         if (br.nodes.empty()) {
             pairs.allocate(1); empty_child(0, 0); empty_child(0, 1);
             for (int k = 0; k < 4; k++) root.ref[k] = ZR_REF_EMPTY;
             return ZR_OK;
         }
-        // 1. indices
-        pair_of.allocate(br.nodes.size());
-        if (br.nodes[0].count) { leaf_first[0] = 0; cnt[br.nodes[0].kind & 7] = br.nodes[0].count; leaves.push_back(0); }   // the whole world fits one leaf
-        else index_nodes();
+        // 1. indices: the world's tree, and every group's by a flattener of its own over the group's triangles — the world's own code, on indices local to the group
+        index_tree();
+        const size_t ng = runs ? runs->size() : 0;
+        run_objs.resize(ng); run_fl.resize(ng);
+        for (size_t g = 0; g < ng; g++) {
+            const zr_group& grp = s.groups[g];
+            run_objs[g].reserve(grp.triangle_count);
+            for (uint32_t k = 0; k < grp.triangle_count; k++) run_objs[g].push_back({ZR_PRIM_TRIANGLE, grp.first_triangle + k, 0, 0});
+            run_fl[g].reset(new Flattener{s, run_objs[g], (*runs)[g]});
+            run_fl[g]->open_ratio = open_ratio; run_fl[g]->root_in_array = true;
+            run_fl[g]->index_tree();
+        }
         ph("index pass");
         // 2. the arrays at the plan's sizes; what the walk counted must be what the plan classified
         for (int k = 0; k < 8; k++)
             if (cnt[k] != commit_plan->cnt[k]) return fail(ZR_E_DEVICE, "flattener: %u leaf objects of kind %d, the plan has %u (internal error)", cnt[k], k, commit_plan->cnt[k]);
         allocate_arrays(*commit_plan);
-        size_t run_pair_total = 0;
-        if (runs) for (size_t g = 0; g < runs->size(); g++) run_pair_total += run_pairs((*runs)[g]);
         insts.allocate(cnt[ZR_KIND_INSTANCE]); inst_group.assign(cnt[ZR_KIND_INSTANCE], 0);
-        const size_t main_pairs = std::max<size_t>(1, inner.size());
-        pairs.allocate(main_pairs + run_pair_total);
-        if (runs) {   // where each group's subtree will start (the records follow the world's own)
-            run_root.resize(runs->size()); run_tri_base.assign(runs->size(), 0);
-            size_t at = main_pairs;
-            for (size_t g = 0; g < runs->size(); g++) { run_root[g] = (uint32_t)at; at += run_pairs((*runs)[g]); }
+        out.insts = insts.data(); out.inst_group = inst_group.data();
+        if (want_src) for (int k = 0; k < 8; k++) { src[k].assign(commit_plan->size[k], 0xFFFFFFFFu); out.src[k] = src[k].data(); }
+        // every group's records follow the world's own, its triangles the leaf triangles: where each group's start
+        run_root.resize(ng); run_tri_base.resize(ng); run_qroot.resize(ng); run_demand.resize(ng);
+        size_t n_pairs = std::max<size_t>(1, inner.size());
+        for (size_t g = 0; g < ng; g++) {
+            run_root[g] = (uint32_t)n_pairs; n_pairs += std::max<size_t>(1, run_fl[g]->inner.size());
+            run_tri_base[g] = (uint32_t)n_tri; n_tri += s.groups[g].triangle_count;
+            run_fl[g]->out = out; run_fl[g]->out.base[ZR_PRIM_TRIANGLE] = run_tri_base[g];
         }
-        if (want_src) for (int k = 0; k < 8; k++) src[k].assign(commit_plan->size[k], 0xFFFFFFFFu);
-        // 3. leaf primitives of the plain kinds: all threads
-        parallel_for(leaves.size(), 2048, [&](size_t a, size_t b) {
-            for (size_t i = a; i < b; i++) {
-                const zr::BuildNode& n = br.nodes[leaves[i]];
-                if (n.kind == ZR_PRIM_MEDIUM || n.kind == ZR_KIND_WRAPPED) continue;
-                for (uint32_t k = 0; k < n.count; k++) {
-                    put_leaf_object(br.order[n.first + k], (size_t)leaf_first[leaves[i]] + k);
-                    note_src(n.kind, (size_t)leaf_first[leaves[i]] + k, br.order[n.first + k]);
-                }
-            }
-        });
-        if (runs) for (size_t g = 0; g < runs->size(); g++) emit_run((uint32_t)g, run_root[g]);   // serial: runs are shared, hence few
+        pairs.allocate(n_pairs);
+        // 3. leaf primitives of the plain kinds: all threads; a group's triangles in the order of its leaves (serial: groups are shared, hence few)
+        put_leaves();
+        for (size_t g = 0; g < ng; g++) run_fl[g]->put_leaves();
         ph("primitive records");
         std::vector<Compound> todo;   // media and wrapped objects, in emit order
         if (cnt[ZR_PRIM_MEDIUM] + cnt[ZR_KIND_WRAPPED]) for (int32_t lf : leaves) {   // (a million-leaf scan for nothing otherwise)
@@ -937,10 +727,21 @@ struct Flattener {
         if (!filled(*commit_plan)) return fail(ZR_E_DEVICE, "flattener: the primitive arrays do not add up to the plan's sizes (internal error)");
         ph("media / wrapped");
         if (after_primitives) after_primitives();   // the primitive arrays are final: their upload can run beside the rest
-        // 4. pair records: all threads
-        if (inner.empty()) fill_leaf_root();
-        else {
-            parallel_for(inner.size(), 4096, [&](size_t a, size_t b) { for (size_t p = a; p < b; p++) fill_pair((uint32_t)p, inner[p]); });
+        // 4. pair records: all threads; a group's are copied behind the world's with the indices moved (what DeviceBuilder::relocate does) — inner
+        // references by the group's first pair, triangle references by the group's first triangle
+        fill_pairs();
+        for (size_t g = 0; g < ng; g++) {
+            Flattener& sub = *run_fl[g];
+            sub.pairs.allocate(std::max<size_t>(1, sub.inner.size()));
+            sub.fill_pairs();
+            for (size_t i = 0; i < sub.pairs.size(); i++) {
+                zr::NodePair p = sub.pairs[i];
+                for (int c = 0; c < 2; c++) {
+                    if (p.meta[c] == 0) p.child[c] += run_root[g];
+                    else if (p.meta[c] & 0xFFFFu) p.child[c] += run_tri_base[g];   // (an empty child names nothing)
+                }
+                pairs[run_root[g] + i] = p;
+            }
         }
         ph("pair records");
         // 5. 4-wide nodes
@@ -948,49 +749,53 @@ struct Flattener {
         ph("4-wide plan");
         number_quads(0);
         ph("4-wide numbering");
-        if (runs) { emit_run_quads(); ph("groups' 4-wide nodes"); }
-        return ZR_OK;
-    }
-    // The 4-wide quantised nodes of every group, behind the world's own: planned and numbered by a flattener of the group's tree
-    // (same collapse, same quantisation; its root is a stored node, not kernel arguments), then copied with the indices moved —
-    // inner references by the group's first node, triangle references by the group's first triangle.  Placements get the root.
-    void emit_run_quads() {
-        run_qroot.assign(runs->size(), 0); run_demand.assign(runs->size(), 0);
-        const std::vector<zr_object> none;
-        for (size_t g = 0; g < runs->size(); g++) {
-            const zr::BuildResult& rb = (*runs)[g];
-            Flattener sub{s, none, rb};
-            sub.threads = 1; sub.open_ratio = open_ratio; sub.root_in_array = true;
-            sub.leaf_first.allocate(rb.nodes.size()); sub.pair_of.allocate(rb.nodes.size());
-            const uint32_t base = (uint32_t)quads.size();
-            run_qroot[g] = base;
-            if (rb.nodes[0].count) {   // the whole run is one leaf: a node with one child
-                zr::NodeQ nq{};
-                int32_t kid = 0; double w = 1;
-                for (int ax = 0; ax < 3; ax++) nq.scale[ax] = 1;
-                if (!sub.quantise(&kid, 1, nq, &w)) quant_ok_a = false;
-                for (int k = 0; k < 4; k++) nq.ref[k] = ZR_REF_EMPTY;
-                nq.ref[0] = ZR_REF_LEAF | ((uint32_t)ZR_PRIM_TRIANGLE << 28) | ((uint32_t)(rb.nodes[0].count - 1u) << 24) | run_tri_base[g];
-                quads.push_back(nq);
-                run_demand[g] = 1;
-                continue;
-            }
-            sub.index_nodes();
+        if (!ng) return ZR_OK;
+        // a group's 4-wide nodes: same collapse, same quantisation, its root a stored node (a one-leaf group: a node with one child); copied behind the
+        // world's, inner references moved by the group's first node, triangle references by its first triangle.  Placements get the roots.
+        for (size_t g = 0; g < ng; g++) {
+            Flattener& sub = *run_fl[g];
             sub.plan_quads(0);
             sub.number_quads(0);
-            if (!sub.quant_ok) quant_ok_a = false;
+            if (!sub.quant_ok) quant_ok = false;
+            run_qroot[g] = (uint32_t)quads.size();
             for (zr::NodeQ nq : sub.quads) {
                 for (int k = 0; k < 4; k++) {
                     if (nq.ref[k] == ZR_REF_EMPTY) continue;
                     if (nq.ref[k] & ZR_REF_LEAF) nq.ref[k] += run_tri_base[g];   // (the low 24 bits: the first primitive)
-                    else nq.ref[k] += base;
+                    else nq.ref[k] += run_qroot[g];
                 }
                 quads.push_back(nq);
             }
-            run_demand[g] = sub.demand_of(sub.quads[0].ref) + 0u;
+            run_demand[g] = sub.demand_of(sub.quads[0].ref);
         }
-        quant_ok = quant_ok && quant_ok_a.load();
-        for (size_t i = 0; i < insts.size(); i++) insts[i].pad_ = run_qroot[inst_group[i]];   // DInstance::qroot
+        for (size_t i = 0; i < insts.size(); i++) { insts[i].root = run_root[inst_group[i]]; insts[i].pad_ = run_qroot[inst_group[i]]; }   // (pad_: DInstance::qroot)
+        run_fl.clear(); run_objs.clear();
+        ph("groups' 4-wide nodes");
+        return ZR_OK;
+    }
+    // the steps of run(), which a group's own flattener takes too
+    void index_tree() {   // pair numbers and leaf ranges
+        leaf_first.allocate(br.nodes.size()); pair_of.allocate(br.nodes.size());   // fresh pages: zero
+        if (br.nodes[0].count) { leaf_first[0] = 0; cnt[br.nodes[0].kind & 7] = br.nodes[0].count; leaves.push_back(0); }   // the whole tree fits one leaf
+        else index_nodes();
+    }
+    void put_leaves() {   // every leaf object of a plain kind as its record (zr_entry.h), at its leaf's place behind out.base
+        parallel_for(leaves.size(), 2048, [&](size_t a, size_t b) {
+            for (size_t i = a; i < b; i++) {
+                const zr::BuildNode& n = br.nodes[leaves[i]];
+                if (n.kind == ZR_PRIM_MEDIUM || n.kind == ZR_KIND_WRAPPED) continue;
+                for (uint32_t k = 0; k < n.count; k++) {
+                    const uint32_t oi = br.order[n.first + k];
+                    const size_t di = (size_t)out.base[n.kind & 7] + leaf_first[leaves[i]] + k;
+                    zr::put_entry(in, out, objs[oi], commit_plan ? commit_plan->code[oi] >> 4 : 0, di);
+                    zr::note_src(out, n.kind, di, oi, objs[oi]);
+                }
+            }
+        });
+    }
+    void fill_pairs() {
+        if (inner.empty()) fill_leaf_root();
+        else parallel_for(inner.size(), 4096, [&](size_t a, size_t b) { for (size_t p = a; p < b; p++) fill_pair((uint32_t)p, inner[p]); });
     }
     void fill_leaf_root() {   // the whole world in one leaf: a pair whose second child is empty
         const zr::BuildNode& n = br.nodes[0];
@@ -1013,7 +818,7 @@ inline int build_host_tree(const SceneInput& s, std::shared_ptr<const CommitPlan
     const std::vector<zr_object>& objs = plan->objs;
     const BuildKnobs& kn = plan->kn;
     hb.plan = plan; hb.runs.resize(s.groups.size()); hb.group_box.resize(s.groups.size());
-    Boxer tri_boxer{s};
+    const zr::BuildSceneIn tris = scene_view(s);
     const double ck_tri[8] = {1, 1, 1, 1, 1, 1, 1, 1};
     for (size_t g = 0; g < s.groups.size(); g++) {
         const zr_group& grp = s.groups[g];
@@ -1021,20 +826,20 @@ inline int build_host_tree(const SceneInput& s, std::shared_ptr<const CommitPlan
         std::vector<uint32_t> tk(grp.triangle_count, ZR_PRIM_TRIANGLE);
         zr::BuildBox all; for (int a = 0; a < 3; a++) { all.lo[a] = kInf; all.hi[a] = -kInf; }
         for (uint32_t k = 0; k < grp.triangle_count; k++) {
-            tb[k] = tri_boxer.prim(ZR_PRIM_TRIANGLE, grp.first_triangle + k);
+            tb[k] = zr::prim_box(tris, ZR_PRIM_TRIANGLE, grp.first_triangle + k);
             for (int a = 0; a < 3; a++) { all.lo[a] = std::fmin(all.lo[a], tb[k].lo[a]); all.hi[a] = std::fmax(all.hi[a], tb[k].hi[a]); }
         }
         hb.group_box[g] = all;
         zr::build_bvh(tb, tk, 4, ZR_STACK_DEPTH - 2, 1.0, ck_tri, hb.runs[g]);
         if (hb.runs[g].max_depth >= ZR_STACK_DEPTH - 1) return fail(ZR_E_INVALID, "group %zu: BVH depth %d exceeds the traversal stack", g, hb.runs[g].max_depth);
     }
-    Boxer boxer{s, &hb.group_box};
+    const zr::BuildSceneIn in = scene_view(s, &hb.group_box);
     hb.boxes.resize(objs.size()); hb.kinds.resize(objs.size());
     std::atomic<size_t> bad_box{(size_t)-1};
     parallel_split(objs.size(), [&](size_t k0, size_t k1) {
         for (size_t k = k0; k < k1; k++) {
             const zr_object& o = objs[k];
-            hb.boxes[k] = boxer.chain(o.type, o.index, o.chain_first, o.chain_count);
+            hb.boxes[k] = zr::chain_box(in, o.type, o.index, o.chain_first, o.chain_count);
             hb.kinds[k] = plan->kind(k);
             for (int a = 0; a < 3; a++)
                 if (!std::isfinite(hb.boxes[k].lo[a]) || !std::isfinite(hb.boxes[k].hi[a])) { size_t want = (size_t)-1; bad_box.compare_exchange_strong(want, k); }

@@ -1,6 +1,6 @@
 // Host-side check of the host commit's CPU half (raytracer_project_amd/csrc/zr_flatten.h over zr_bvh.cpp): world list, validation, commit plan, boxes,
 // binned-SAH tree, Flattener::run — no HIP.  Compiled and run by tests/test_flatten_native.py.
-//   flatten_check <world> <seed>     world: zero | one | five | mixed | big
+//   flatten_check <world> <seed>     world: zero | one | five | mixed | runs | big
 // Prints one JSON line: an FNV-1a hash of every output array (the same for every ZR_BVH_THREADS) and validity flags.
 #include "zr_flatten.h"
 
@@ -100,6 +100,15 @@ int main(int argc, char** argv) {
         const uint32_t g[3] = {w.group(13), w.group(200), w.group(3)};
         for (uint32_t i = 0; i < 2985; i++) w.mixed_entry(i);
         for (int k = 0; k < 15; k++) w.add(ZR_PRIM_GROUP, g[k % 3], {World::translate(), World::rotate(ZR_OP_ROTATE_Y), World::material()});
+    } else if (world == "runs") {   // groups of 1, 4, 5 and 9 triangles — one leaf, a full leaf, the first two-leaf tree, a three-level tree — each placed twice under
+                                    // different chains, and six bare spheres so that the world's tree has inner nodes
+        const uint32_t g[4] = {w.group(1), w.group(4), w.group(5), w.group(9)};
+        for (int k = 0; k < 4; k++) {
+            w.add(ZR_PRIM_GROUP, g[k], {World::translate()});
+            w.place(); w.add(ZR_PRIM_SPHERE, w.sphere());
+            w.add(ZR_PRIM_GROUP, g[k], {World::material(), World::translate(), World::rotate(k % 2 ? ZR_OP_ROTATE_X : ZR_OP_ROTATE_Y), World::op(ZR_OP_SCALE, 2, 2, 2)});
+        }
+        for (int k = 0; k < 2; k++) { w.place(); w.add(ZR_PRIM_SPHERE, w.sphere()); }
     } else if (world == "big") {   // 140 000 bare triangles and spheres through the implicit world list: beyond the 65 536 where the thread split and the worker pool start
         explicit_list = false;
         for (uint32_t i = 0; i < 140000; i++) { w.place(); if (i % 3) w.triangle(); else w.sphere(); }

@@ -29,8 +29,9 @@ def run(checker, world, threads):
 
 
 # zero / one (the whole world is one leaf) / five (one of each ZR_PRIM_* type) / mixed (3000 entries of every classification, media, wrapped objects,
-# three groups placed five times each) / big (140 000 bare triangles and spheres: past the 65 536 where the thread split and the worker pool start)
-@pytest.mark.parametrize("world,n", [("zero", 0), ("one", 1), ("five", 5), ("mixed", 3000), ("big", 140000)])
+# three groups placed five times each) / runs (groups of 1, 4, 5 and 9 triangles, each placed twice under different chains, among six spheres: a group's
+# tree at its smallest shapes) / big (140 000 bare triangles and spheres: past the 65 536 where the thread split and the worker pool start)
+@pytest.mark.parametrize("world,n", [("zero", 0), ("one", 1), ("five", 5), ("mixed", 3000), ("runs", 14), ("big", 140000)])
 def test_arrays_are_valid_and_independent_of_thread_count(checker, world, n):
     ref = run(checker, world, 1)
     assert ref["n"] == n

@@ -45,7 +45,7 @@ def gpu_scene(ctx, name, args=(), builder=None):
         old = os.environ.get("ZR_BVH_BUILD")
         if builder:
             os.environ["ZR_BVH_BUILD"] = builder
-            os.environ["ZR_BUILD_CHECK"] = "1"   # the device builder checks its object boxes against the host's Boxer and fails the commit on a difference
+            os.environ["ZR_BUILD_CHECK"] = "1"   # the device builder checks its object boxes against the host's (zr_entry.h chain_box) and fails the commit on a difference
         try:
             sc = capi.Scene(ctx, demo_scene(name, args).desc)
         finally:
