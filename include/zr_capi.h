@@ -639,6 +639,12 @@ typedef struct zr_scatter_out {
  * scene's materials; draws come from the contract stream keys[k] (include/zr_rng.h), starting at draw first_draw[k] (NULL = 0) */
 int zr_kat_scatter(zr_ctx*, const zr_scene*, const double* rays6, const zr_hit* recs, const uint64_t* keys, const uint64_t* first_draw,
                    size_t n, zr_scatter_out* out);
+/* The lean pair per call (additive, ABI 3): for n rays, the closest hit over (0.001, inf) as zr_trace finds it, then the record and emitted + scatter as
+ * SHADE's lean build computes them (lean_rec / lean_shade), draws from keys[k] starting at first_draw[k] (NULL = 0).  out_hits holds p, normal, mat,
+ * front_face and t (the other fields are zero; mat = 0xFFFFFFFF on a miss), out is filled as zr_kat_scatter fills it.  A scene that did not commit
+ * with the lean build (zr_scene_kernels: shade_lean = 0) is refused with ZR_E_STATE. */
+int zr_kat_shade_lean(zr_ctx*, const zr_scene*, const double* rays6, const uint64_t* keys, const uint64_t* first_draw, size_t n, zr_hit* out_hits,
+                      zr_scatter_out* out);
 /* texture::value(u, v, p) of the scene's texture `texture_id`; uvp5 = n x (u, v, px, py, pz); out = n x rgb */
 int zr_kat_texture(zr_ctx*, const zr_scene*, uint32_t texture_id, const double* uvp5, size_t n, double* out_rgb);
 /* camera::get_background_color(ray(., dir), env) for n directions (env.hdr_texture indexes the scene's textures) */

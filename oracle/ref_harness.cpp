@@ -714,6 +714,7 @@ int main(int argc, char** argv) {
                 e[8] = rec.front_face ? 1 : 0; e[9] = rec.u; e[10] = rec.v;
                 e[11] = rec.tangent.x(); e[12] = rec.tangent.y(); e[13] = rec.tangent.z();
                 e[14] = id;
+                if (!rec.mat) continue;   // an object without a material: calling through the null pointer is undefined; the record stands, scatter stays all zero
                 double* sc = &scat[k * 14];
                 color em = rec.mat->emitted(rec.u, rec.v, rec.p);
                 ray scattered; color att;

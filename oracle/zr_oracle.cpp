@@ -176,13 +176,16 @@ struct Scene {
         return unit(b);
     }
 
+    // An object without a material (mat = 0xFFFFFFFF; calling through the null pointer is undefined in the reference): emits nothing and absorbs, as on the device.
     V3 emitted(const Rec& rec) const {
+        if (rec.mat >= d.n_materials) return V3(0, 0, 0);
         const zr_material& m = d.materials[rec.mat];
         if (m.kind == ZR_MAT_LIGHT) return tex_value(m.tex, rec.u, rec.v, rec.p);
         return V3(0, 0, 0);
     }
 
     V3 albedo(const Rec& rec) const {  // material::get_albedo, material.hpp:29-31,99-102,154-156,226-229,266-275
+        if (rec.mat >= d.n_materials) return V3(0, 0, 0);
         const zr_material& m = d.materials[rec.mat];
         switch (m.kind) {
             case ZR_MAT_LAMBERTIAN:
@@ -194,6 +197,7 @@ struct Scene {
     }
 
     bool scatter(const Ray& rin, const Rec& rec, V3& att, Ray& out, Rng& g) const {
+        if (rec.mat >= d.n_materials) return false;
         const zr_material& m = d.materials[rec.mat];
         switch (m.kind) {
             case ZR_MAT_LAMBERTIAN: {  // material.hpp:74-96

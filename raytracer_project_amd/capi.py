@@ -242,7 +242,7 @@ CAPI_SYMBOLS = [
     "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
     "zr_accum_variance", "zr_denoise_guided", "zr_accum_denoise",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels",
-    "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
+    "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_shade_lean", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
 
 
@@ -311,6 +311,8 @@ def load():
     lib.zr_get_kernel_times.argtypes = [vp, C.POINTER(C.c_float), i32]
     lib.zr_trace.argtypes = [vp, vp, vp, C.c_size_t, C.c_double, C.c_double, u64, u64, C.c_uint32, vp]
     lib.zr_kat_scatter.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    if hasattr(lib, "zr_kat_shade_lean"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
+        lib.zr_kat_shade_lean.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.zr_kat_texture.argtypes = [vp, vp, C.c_uint32, vp, C.c_size_t, vp]
     lib.zr_kat_background.argtypes = [vp, vp, C.POINTER(Env), vp, C.c_size_t, vp]
     lib.zr_kat_camera_rays.argtypes = [vp, C.POINTER(Camera), u64, vp, C.c_size_t, vp]
@@ -829,6 +831,17 @@ class Scene:
         _check(self.lib.zr_kat_scatter(self.ctx._c, self._s, rays.ctypes.data, hits.ctypes.data, keys.ctypes.data,
                                        fd.ctypes.data if fd is not None else None, len(rays), out.ctypes.data))
         return out
+
+    def kat_shade_lean(self, rays, keys, first_draw=None):
+        """the lean pair per call: closest hit over (0.001, inf), then lean_rec + lean_shade -> (array of HIT_DTYPE, array of SCATTER_DTYPE)"""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        fd = np.ascontiguousarray(first_draw, dtype=np.uint64) if first_draw is not None else None
+        hits = np.zeros(len(rays), dtype=HIT_DTYPE)
+        out = np.zeros(len(rays), dtype=SCATTER_DTYPE)
+        _check(self.lib.zr_kat_shade_lean(self.ctx._c, self._s, rays.ctypes.data, keys.ctypes.data, fd.ctypes.data if fd is not None else None,
+                                          len(rays), hits.ctypes.data, out.ctypes.data))
+        return hits, out
 
     def kat_texture(self, tex, uvp):
         uvp = np.ascontiguousarray(uvp, dtype=np.float64).reshape(-1, 5)

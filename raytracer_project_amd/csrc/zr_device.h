@@ -38,6 +38,19 @@ __device__ __forceinline__ double get(V3 v, int i) { return i == 0 ? v.x : (i ==
 __device__ __forceinline__ V3 ld3(const double* p) { return mk(p[0], p[1], p[2]); }
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (hi < v ? hi : v); }
 
+// dot(a, b) as the reference rounds it: every product rounded, then the sums, no fused multiply-add (vec3.hpp's u0 v0 + u1 v1 + u2 v2).  Under
+// -ffp-contract=fast the backend fuses whatever multiply feeds an add, `#pragma clang fp contract(off)` notwithstanding; an empty asm on each product
+// hides the multiply from it and emits nothing (three v_mul_f64 and two v_add_f64).
+__device__ __forceinline__ double rounded(double x) { asm("" : "+v"(x)); return x; }
+__device__ __forceinline__ double dot_rn(V3 a, V3 b) { return rounded(a.x * b.x) + rounded(a.y * b.y) + rounded(a.z * b.z); }
+// A dot product whose SIGN decides (the face of a hit, the side a scattered ray leaves on): the contracted value as ever, so that frames keep their last
+// bits, unless the reference's own arithmetic cancels to exactly 0 — a ray perpendicular to the normal: q q' - q q' with products that round.  Contracted,
+// that dot is the rounding error of one product, ~1e-17 of either sign, and noise would decide what the reference decides by `0 < 0` being false.
+// (The test reads its first operand through an empty asm of its own: the compiler must not know these products for the ones dot() is about to fuse, or it
+// shares them and fuses dot() differently — which moved the last bits of every frame with glass in it.)
+__device__ __forceinline__ bool dot_cancels(V3 a, V3 b) { return rounded(rounded(a.x) * b.x) + rounded(rounded(a.y) * b.y) + rounded(rounded(a.z) * b.z) == 0; }
+__device__ __forceinline__ double dot_sign(V3 a, V3 b) { return dot_cancels(a, b) ? 0.0 : dot(a, b); }
+
 struct Ray { V3 o, d; };
 __device__ __forceinline__ V3 at(const Ray& r, double t) { return r.o + t * r.d; }
 
@@ -48,7 +61,7 @@ struct Rec {
     bool front;
 };
 __device__ __forceinline__ void set_face(Rec& rec, V3 rd, V3 outward) {  // hittable.hpp:22-25
-    rec.front = dot(rd, outward) < 0;
+    rec.front = dot_sign(rd, outward) < 0;
     rec.n = rec.front ? outward : -outward;
 }
 // A primitive stored in world space from under translate / rotate_y wrappers (zr_entry.h put_triangle / put_baked_sphere): each of them calls
@@ -596,7 +609,7 @@ __device__ inline void sphere_rec(const DScene& sc, uint32_t idx, const Ray& r, 
         rec.tan = unit(rec.tan);
         rec.bit = cross(rec.n, rec.tan);
     }
-    if (refaced) reface(rec.front, rec.n, dot(r.d, outward), outward, false);   // last: sphere::hit makes its tangent frame from the normal of its own call
+    if (refaced) reface(rec.front, rec.n, dot_sign(r.d, outward), outward, false);   // last: sphere::hit makes its tangent frame from the normal of its own call
 }
 
 // ---- per-vertex texture coordinates of triangles (DScene::tri_uv) -------------------------------------------------------
@@ -649,7 +662,7 @@ __device__ inline void triangle_rec(const DScene& sc, uint32_t idx, const Ray& r
     rec.mat = (uint32_t)__double_as_longlong(v[18]);
     set_face(rec, r.d, smooth);
     const uint32_t refaced = (uint32_t)__double_as_longlong(v[19]);   // baked from under translate / rotate_y wrappers (zr_flatten.h): bit 0 any, bit 1 an even number
-    if (refaced & 1u) reface(rec.front, rec.n, dot(r.d, smooth), smooth, (refaced & 2u) != 0);
+    if (refaced & 1u) reface(rec.front, rec.n, dot_sign(r.d, smooth), smooth, (refaced & 2u) != 0);
     // u, v, tangent, bitangent are not written by triangle::hit: fresh-record values
     rec.u = 0; rec.v = 0; rec.tan = mk(0, 0, 0); rec.bit = mk(0, 0, 0);
 }
@@ -917,11 +930,6 @@ __device__ inline V3 bumped_normal(const DScene& sc, const Rec& rec, uint32_t bu
 
 // ---- materials --------------------------------------------------------------------------------------
 __device__ inline V3 reflect(V3 v, V3 n) { return v - (2 * dot(v, n)) * n; }
-// dot(a, b) as the reference rounds it: every product rounded, then the sums, no fused multiply-add (vec3.hpp's u0 v0 + u1 v1 + u2 v2).  Under
-// -ffp-contract=fast the backend fuses whatever multiply feeds an add, `#pragma clang fp contract(off)` notwithstanding; an empty asm on each product
-// hides the multiply from it and emits nothing (three v_mul_f64 and two v_add_f64).
-__device__ __forceinline__ double rounded(double x) { asm("" : "+v"(x)); return x; }
-__device__ __forceinline__ double dot_rn(V3 a, V3 b) { return rounded(a.x * b.x) + rounded(a.y * b.y) + rounded(a.z * b.z); }
 // metal::scatter (material.hpp:139-149) on a ray exactly perpendicular to the normal — a tangent ray on a sphere, a bent vertex normal: dot(v, n) = q q' - q q'
 // is exactly 0 in the reference, the reflection is v itself, dot(reflected, n) is 0 again and the ray is absorbed.  Contracted, the same dot is the rounding
 // error of one product, ~1e-17 of either sign, and that sign decided.  So: the contracted value as ever (the frames' last bits stay what they were) unless
@@ -984,7 +992,11 @@ __device__ inline bool scatter(const DScene& sc, const Ray& rin, const Rec& rec,
         case ZR_MAT_DIELECTRIC: {  // material.hpp:192-224, 237-241
             att = mk(m.tint[0], m.tint[1], m.tint[2]);
             double ri = rec.front ? (1.0 / m.param) : m.param;
-            double ct = fmin(dot(-ud, wn), 1.0);
+            // On a face-normal tie (dot(-ud, n) cancels to exactly 0 in the reference) the reflection is ud itself, dot(direction, n) is 0 again and the
+            // origin moves by -0.0001 n; contracted, both dots are rounding noise and the offset's sign with them: dot_sign, as for metal
+            const bool tie = dot_cancels(ud, wn);
+            const double dn = tie ? 0.0 : dot(-ud, wn);
+            double ct = fmin(dn, 1.0);
             double st = sqrt(1.0 - ct * ct);
             bool refl = ri * st > 1.0;
             if (!refl) {
@@ -994,14 +1006,14 @@ __device__ inline bool scatter(const DScene& sc, const Ray& rin, const Rec& rec,
                 refl = rf > g.next();
             }
             V3 dir;
-            if (refl) dir = reflect(ud, wn);
+            if (refl) dir = tie ? ud : reflect(ud, wn);
             else {  // refract, vec3.hpp:209-214
-                double c2 = fmin(dot(-ud, wn), 1.0);
+                double c2 = fmin(dn, 1.0);
                 V3 perp = ri * (ud + c2 * wn);
                 V3 par = (-sqrt(fabs(1.0 - len2(perp)))) * wn;
                 dir = perp + par;
             }
-            V3 off = (dot(dir, rec.n) > 0) ? (0.0001 * rec.n) : (-0.0001 * rec.n);
+            V3 off = (dot_sign(dir, rec.n) > 0) ? (0.0001 * rec.n) : (-0.0001 * rec.n);
             out.o = rec.p + off;
             out.d = dir;
             return true;
@@ -1049,7 +1061,7 @@ __device__ __forceinline__ void lean_rec(const DScene& sc, uint32_t kind, uint32
         rec.mat = (uint32_t)__double_as_longlong(v[18]);
         refaced = (uint32_t)__double_as_longlong(v[19]);
     }
-    const double x = dot(r.d, outward);
+    const double x = dot_sign(r.d, outward);
     rec.front = x < 0;   // hittable.hpp:22-25
     rec.n = rec.front ? outward : -outward;
     if (refaced & 1u) reface(rec.front, rec.n, x, outward, (refaced & 2u) != 0);
@@ -1085,7 +1097,9 @@ __device__ __forceinline__ bool lean_shade(const DScene& sc, const Ray& rin, con
     if (kind == ZR_MAT_DIELECTRIC) {  // material.hpp:192-224, 237-241
         att = mk(m.tint[0], m.tint[1], m.tint[2]);
         double ri = rec.front ? (1.0 / m.param) : m.param;
-        double ct = fmin(dot(-ud, rec.n), 1.0);
+        const bool tie = dot_cancels(ud, rec.n);
+        const double dn = tie ? 0.0 : dot(-ud, rec.n);   // (see scatter(): the face-normal tie)
+        double ct = fmin(dn, 1.0);
         double st = sqrt(1.0 - ct * ct);
         bool refl = ri * st > 1.0;
         if (!refl) {
@@ -1095,14 +1109,14 @@ __device__ __forceinline__ bool lean_shade(const DScene& sc, const Ray& rin, con
             refl = rf > g.next();
         }
         V3 dir;
-        if (refl) dir = reflect(ud, rec.n);
+        if (refl) dir = tie ? ud : reflect(ud, rec.n);
         else {  // refract, vec3.hpp:209-214
-            double c2 = fmin(dot(-ud, rec.n), 1.0);
+            double c2 = fmin(dn, 1.0);
             V3 perp = ri * (ud + c2 * rec.n);
             V3 par = (-sqrt(fabs(1.0 - len2(perp)))) * rec.n;
             dir = perp + par;
         }
-        V3 off = (dot(dir, rec.n) > 0) ? (0.0001 * rec.n) : (-0.0001 * rec.n);
+        V3 off = (dot_sign(dir, rec.n) > 0) ? (0.0001 * rec.n) : (-0.0001 * rec.n);
         out.o = rec.p + off;
         out.d = dir;
         return true;

@@ -382,6 +382,46 @@ __global__ __launch_bounds__(ZR_BLOCK) void kat_scatter(DScene sc, const double*
     out[k] = o;
 }
 
+// zr_kat_shade_lean: the lean pair per call — closest_hit over (0.001, inf) as trace_rays runs it, then lean_rec and lean_shade (zr_device.h) as the lean build of
+// SHADE calls them (zr_stream.hip), one ray per thread.  Of the record only what RecL holds is written: p, normal, mat, front_face and t; the rest is zero.
+__global__ __launch_bounds__(ZR_BLOCK) void kat_shade_lean(DScene sc, const double* __restrict__ rays, const uint64_t* __restrict__ keys,
+                                                            const uint64_t* __restrict__ first_draw, size_t n, zr_hit* __restrict__ out_hit,
+                                                            zr_scatter_out* __restrict__ out) {
+    __shared__ uint32_t lds_stack[ZR_STACK_DEPTH * ZR_BLOCK];
+    size_t k = (size_t)blockIdx.x * ZR_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    Ray r; r.o = ld3(rays + k * 6); r.d = ld3(rays + k * 6 + 3);
+    Rng g; g.key = keys[k]; g.k = first_draw ? first_draw[k] : 0; g.bounce = 0;
+    const uint64_t k0 = g.k;
+    Counters ctr = {0, 0, 0, 0, 0};
+    double t; uint32_t kind, idx;
+    const bool h = closest_hit<false>(sc, r, 0.001, g, lds_stack + threadIdx.x, ZR_BLOCK, t, kind, idx, ctr);
+    zr_hit oh;
+    for (int c = 0; c < 3; c++) { oh.p[c] = 0; oh.normal[c] = 0; oh.tangent[c] = 0; oh.bitangent[c] = 0; }
+    oh.t = 0; oh.u = 0; oh.v = 0; oh.mat = 0xFFFFFFFFu; oh.front_face = 0;
+    zr_scatter_out o;
+    for (int c = 0; c < 3; c++) { o.attenuation[c] = 0; o.origin[c] = 0; o.direction[c] = 0; o.emitted[c] = 0; }
+    o.scattered = 0; o.draws = 0;
+    if (h) {
+        RecL rec;
+        lean_rec(sc, kind, idx, r, t, rec);
+        oh.p[0] = rec.p.x; oh.p[1] = rec.p.y; oh.p[2] = rec.p.z;
+        oh.normal[0] = rec.n.x; oh.normal[1] = rec.n.y; oh.normal[2] = rec.n.z;
+        oh.t = t; oh.mat = rec.mat; oh.front_face = rec.front ? 1u : 0u;
+        V3 em, att = mk(0, 0, 0); Ray nr; nr.o = mk(0, 0, 0); nr.d = mk(0, 0, 0);
+        const bool ok = lean_shade(sc, r, rec, em, att, nr, g);
+        o.emitted[0] = em.x; o.emitted[1] = em.y; o.emitted[2] = em.z;
+        o.scattered = ok ? 1u : 0u; o.draws = (uint32_t)(g.k - k0);
+        if (ok) {
+            o.attenuation[0] = att.x; o.attenuation[1] = att.y; o.attenuation[2] = att.z;
+            o.origin[0] = nr.o.x; o.origin[1] = nr.o.y; o.origin[2] = nr.o.z;
+            o.direction[0] = nr.d.x; o.direction[1] = nr.d.y; o.direction[2] = nr.d.z;
+        }
+    }
+    out_hit[k] = oh;
+    out[k] = o;
+}
+
 __global__ __launch_bounds__(ZR_BLOCK) void kat_texture(DScene sc, uint32_t tex, const double* __restrict__ uvp, size_t n, double* __restrict__ out) {
     size_t k = (size_t)blockIdx.x * ZR_BLOCK + threadIdx.x;
     if (k >= n) return;
@@ -517,6 +557,12 @@ hipError_t launch_kat_scatter(const DScene& sc, const double* rays, const zr_hit
                               zr_scatter_out* out, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(kat_scatter, dim3((unsigned)((n + ZR_BLOCK - 1) / ZR_BLOCK)), dim3(ZR_BLOCK), 0, stream, sc, rays, recs, keys, first_draw, n, out);
+    return hipGetLastError();
+}
+hipError_t launch_kat_shade_lean(const DScene& sc, const double* rays, const uint64_t* keys, const uint64_t* first_draw, size_t n, zr_hit* out_hit,
+                                 zr_scatter_out* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(kat_shade_lean, dim3((unsigned)((n + ZR_BLOCK - 1) / ZR_BLOCK)), dim3(ZR_BLOCK), 0, stream, sc, rays, keys, first_draw, n, out_hit, out);
     return hipGetLastError();
 }
 hipError_t launch_kat_texture(const DScene& sc, uint32_t tex, const double* uvp, size_t n, double* out, hipStream_t stream) {

@@ -163,6 +163,8 @@ hipError_t launch_path_records(const DScene& sc, const DCamera& cam, uint64_t se
                                hipStream_t stream);
 hipError_t launch_kat_scatter(const DScene& sc, const double* rays, const zr_hit* recs, const uint64_t* keys, const uint64_t* first_draw, size_t n,
                               zr_scatter_out* out, hipStream_t stream);
+hipError_t launch_kat_shade_lean(const DScene& sc, const double* rays, const uint64_t* keys, const uint64_t* first_draw, size_t n, zr_hit* out_hit,
+                                 zr_scatter_out* out, hipStream_t stream);
 hipError_t launch_kat_texture(const DScene& sc, uint32_t tex, const double* uvp, size_t n, double* out, hipStream_t stream);
 hipError_t launch_kat_background(const DScene& sc, const DEnv& env, const double* dirs, size_t n, double* out, hipStream_t stream);
 hipError_t launch_kat_camera_rays(const DCamera& cam, uint64_t seed, const int32_t* req, size_t n, double* out, hipStream_t stream);

@@ -779,6 +779,25 @@ int zr_kat_scatter(zr_ctx* c, const zr_scene* s, const double* rays6, const zr_h
     return ZR_OK;
 }
 
+int zr_kat_shade_lean(zr_ctx* c, const zr_scene* s, const double* rays6, const uint64_t* keys, const uint64_t* first_draw, size_t n, zr_hit* out_hits,
+                      zr_scatter_out* out) {
+    if (!c || !s || (n && (!rays6 || !keys || !out_hits || !out))) return fail(ZR_E_INVALID, "null argument");
+    if (int rc0 = scene_ready(c, s, "zr_kat_shade_lean")) return rc0;
+    if (!s->ds.shade_lean) return fail(ZR_E_STATE, "zr_kat_shade_lean: the scene did not commit with SHADE's lean build (kernels: shade_lean = 0)");
+    if (n == 0) return ZR_OK;
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<double> d_rays; DevBuf<uint64_t> d_keys, d_first; DevBuf<zr_hit> d_hits; DevBuf<zr_scatter_out> d_out;
+    int rc;
+    if ((rc = d_rays.upload(std::vector<double>(rays6, rays6 + n * 6))) || (rc = d_keys.upload(std::vector<uint64_t>(keys, keys + n))) ||
+        (rc = d_hits.alloc(n)) || (rc = d_out.alloc(n))) return rc;
+    if (first_draw && (rc = d_first.upload(std::vector<uint64_t>(first_draw, first_draw + n)))) return rc;
+    HIP_OK(zr::launch_kat_shade_lean(s->ds, d_rays.p, d_keys.p, first_draw ? d_first.p : nullptr, n, d_hits.p, d_out.p, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    HIP_OK(hipMemcpy(out_hits, d_hits.p, n * sizeof(zr_hit), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out, d_out.p, n * sizeof(zr_scatter_out), hipMemcpyDeviceToHost));
+    return ZR_OK;
+}
+
 int zr_kat_texture(zr_ctx* c, const zr_scene* s, uint32_t texture_id, const double* uvp5, size_t n, double* out_rgb) {
     if (!c || !s || (n && (!uvp5 || !out_rgb))) return fail(ZR_E_INVALID, "null argument");
     if (int rc0 = scene_ready(c, s, "zr_kat_texture")) return rc0;

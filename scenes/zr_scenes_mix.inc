@@ -596,9 +596,72 @@ static inline void zr_build_kat1(zr_demo_scene& s) {
     s.cam.defocus_angle = 0; s.cam.focus_dist = 10;
 }
 
+// "kat2": a LEAN world (DScene::shade_lean: bare spheres and triangles, and spheres / triangles under translate and rotate_y chains that the flattener bakes;
+// lambertian / metal / dielectric / light over solid colours) for the known-answer fixture tests/golden/kat_kat2.npz, which pins scatter() and the lean
+// pair lean_rec / lean_shade at their decision edges.  kat1's cells (pitch 8, one object per cell); tests/golden/make_golden.py kat2_inputs() places the
+// rays and mirrors this layout.  Triangle forms 0-5: bare, translate, rotate_y(0), translate(translate), translate(rotate_y(0)), rotate_y(0)(translate) — chains
+// of one and of two wrappers, so that both parities of reface() occur; a sphere is baked from under one translate only (classify_object).
+static inline void zr_build_kat2(zr_demo_scene& s) {
+    s.name = "kat2"; s.seed = 0x5EED3200ull;
+    typedef shared_ptr<hittable> H;
+    typedef shared_ptr<material> M;
+    const M mats[10] = {make_shared<lambertian>(color(0.7, 0.2, 0.2)),
+                        make_shared<metal>(color(0.9, 0.8, 0.7), 0.0), make_shared<metal>(color(0.7, 0.8, 0.9), 0.4), make_shared<metal>(color(0.6, 0.9, 0.6), 1.0),
+                        make_shared<dielectric>(1.5, color(0.9, 0.8, 0.7)), make_shared<dielectric>(1.0, color(0.7, 0.9, 0.8)),
+                        make_shared<dielectric>(1.0 / 1.5, color(0.8, 0.7, 0.9)), make_shared<dielectric>(2.4, color(0.95, 0.9, 0.6)),
+                        make_shared<diffuse_light>(color(4.0, 3.0, 2.0)), nullptr};
+    enum { LAMB = 0, MIRROR = 1, FUZZY = 2, ROUGH = 3, GLASS = 4, LIGHT = 8, NONE = 9 };
+    auto at = [](int k) { return vec3(8.0 * (k % 10) - 36.0, 8.0 * (k / 10) - 28.0, 8.0 * ((k % 10 + k / 10) % 11) - 40.0); };
+    const vec3 O(0, 0, 0), Z(0, 0, 1);
+    // shapes 0-3: "bent" (kat1's: the interpolated normal is (1, 0, 1) / sqrt 2 on the line x = 0), "flat", "opposed" (vertex B's normal points below the
+    // face: the interpolated normal opposes the geometric one for u > 5/9), "cancel" (n0 = -n1: the interpolated normal vanishes on x = 0 and unit_vector answers 0)
+    auto tri = [&](int shape, vec3 c, M m) -> H {
+        if (shape == 1) return make_shared<triangle>(c + vec3(-1, -1, 0), c + vec3(1, -1, 0), c + vec3(0, 1, 0), Z, Z, Z, m);
+        const vec3 nb = shape == 0 ? vec3(1, 0, 0) : shape == 2 ? vec3(0.6, 0, -0.8) : vec3(0, 0, -1);
+        return make_shared<triangle>(c + vec3(-1, -1, 0), c + vec3(1, -1, 0), c + vec3(-1, 1, 0), Z, nb, Z, m);
+    };
+    auto T = [](H h, vec3 v) -> H { return make_shared<translate>(h, v); };
+    auto RY = [](H h, double radians) -> H { return make_shared<rotate_y>(h, radians); };
+    auto placed = [&](int form, int shape, int cell, M m) -> H {
+        const vec3 c = at(cell), e(1, 0, 0);
+        switch (form) {
+            case 0: return tri(shape, c, m);
+            case 1: return T(tri(shape, O, m), c);
+            case 2: return RY(tri(shape, c, m), 0.0);
+            case 3: return T(T(tri(shape, O, m), e), c - e);
+            case 4: return T(RY(tri(shape, O, m), 0.0), c);
+            default: return RY(T(tri(shape, O, m), c), 0.0);
+        }
+    };
+    // cells 0-17: the face-normal ties, every form x (lambertian, the three metals in turn, the four glasses in turn)
+    for (int f = 0; f < 6; f++)
+        for (int j = 0; j < 3; j++) s.world.add(placed(f, 0, 3 * f + j, mats[j == 0 ? LAMB : j == 1 ? MIRROR + f % 3 : GLASS + f % 4]));
+    // cells 18-25: a flat triangle of each glass, bare and under a translate (the dielectric threshold, the hit positions)
+    for (int g = 0; g < 4; g++) { s.world.add(placed(0, 1, 18 + 2 * g, mats[GLASS + g])); s.world.add(placed(1, 1, 19 + 2 * g, mats[GLASS + g])); }
+    s.world.add(placed(0, 1, 26, mats[MIRROR]));
+    s.world.add(T(RY(tri(1, O, mats[FUZZY]), 0.5), at(27)));   // an angle that is nothing special (the box is symmetric about the y axis: see kat1)
+    s.world.add(placed(3, 1, 28, mats[LAMB]));
+    s.world.add(placed(0, 1, 29, mats[LIGHT]));
+    // cells 30-37: vertex normals that oppose the face, and that cancel
+    s.world.add(placed(0, 2, 30, mats[MIRROR])); s.world.add(placed(1, 2, 31, mats[FUZZY])); s.world.add(placed(2, 2, 32, mats[ROUGH]));
+    s.world.add(placed(0, 2, 33, mats[GLASS])); s.world.add(placed(1, 2, 34, mats[LAMB]));
+    s.world.add(placed(0, 3, 35, mats[GLASS])); s.world.add(placed(1, 3, 36, mats[MIRROR])); s.world.add(placed(2, 3, 37, mats[LAMB]));
+    // cells 40-55: a unit sphere of every scattering material, bare and under a translate; 56-59: the light, the null material, a negative radius
+    for (int m = 0; m < 8; m++) { s.world.add(make_shared<sphere>(at(40 + 2 * m), 1.0, mats[m])); s.world.add(T(make_shared<sphere>(O, 1.0, mats[m]), at(41 + 2 * m))); }
+    s.world.add(make_shared<sphere>(at(56), 1.0, mats[LIGHT]));
+    s.world.add(make_shared<sphere>(at(57), 1.0, mats[NONE]));   // (bare: a sphere without a material is not baked from under a wrapper)
+    s.world.add(make_shared<sphere>(at(58), -0.75, mats[LAMB]));   // hit radius max(0, r) = 0 (sphere.hpp:9)
+    s.world.add(placed(0, 1, 59, mats[NONE]));
+    zr_cam_defaults(s.cam);
+    s.cam.image_width = 64; s.cam.image_height = 48; s.cam.samples_per_pixel = 8; s.cam.max_depth = 12;
+    s.cam.vfov = 40; zr_set3(s.cam.lookfrom, 10, 20, 120); zr_set3(s.cam.lookat, 0, -4, 0);
+    s.cam.defocus_angle = 0; s.cam.focus_dist = 10;
+}
+
 static inline bool zr_build_scene_mix(const std::string& name, zr_demo_scene& s, int arg0 = 0) {
     if (name == "kat0") { zr_build_kat0(s); return true; }
     if (name == "kat1") { zr_build_kat1(s); return true; }
+    if (name == "kat2") { zr_build_kat2(s); return true; }
     if (name == "demo") { zr_build_demo(s); return true; }
     if (name == "mesh0") { zr_build_mesh0(s); return true; }
     if (name == "inst0") { zr_build_inst0(s); return true; }

@@ -398,6 +398,197 @@ def make_kat1(tmp):
     print("kat_kat1", len(rays), "rays,", meta["rays_hit"], "hit,", os.path.getsize(os.path.join(HERE, "kat_kat1.npz")), "bytes")
 
 
+def kat2_inputs():
+    """Hand-placed rays of the lean known-answer fixture (scene "kat2", scenes/zr_scenes_mix.inc; layout and models: tests/shade_edge_worlds.py): rows of
+    (o, d, 0.001, inf), ray k drawing from the stream (0x5EED3001, 0x7ACE, k).  Returns the rays, the rows of every class by name, and for the rows of the
+    dielectric threshold the offset they were constructed at.  Every comment names what its rays pin."""
+    import shade_edge_worlds as sw
+    INF = float("inf")
+    R, cls, delta = [], {}, {}
+    at, tris, sphs = sw.at, sw.triangles(), sw.spheres()
+    V = lambda *x: np.array(x, float)   # noqa: E731
+
+    def ray(o, d, *tags):
+        row = len(R)
+        R.append([float(x) for x in o] + [float(x) for x in d] + [0.001, INF])
+        for t in tags:
+            cls.setdefault(t, []).append(row)
+        return row
+
+    def place(cell, q):
+        """the world point of the local point q of a triangle cell (only form 6 turns: rotate_y.hpp:63-64 by 0.5, then the translate)"""
+        if tris[cell][1] == 6:
+            c, s = np.cos(0.5), np.sin(0.5)
+            return np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]]) @ np.array(q, float) + at(cell)
+        return at(cell) + np.array(q, float)
+
+    # ---- face-normal ties on triangles, class (a): on the line x = 0 of a "bent" triangle vertex B weighs exactly 1/2, the interpolated normal is (s, 0, s) and
+    # dot((a, y, -a), n) = a s - a s with both products exact for a = 1, 2; every form (0, 1 and 2 wrappers) x lambertian / metal / dielectric, both faces
+    for cell in range(18):
+        kind = tris[cell][2]
+        for y in (-0.875, -0.75, -0.5, -0.25, -0.125):
+            h = at(cell) + (0, y, 0)
+            for a in (1.0, 2.0):
+                ray(h + (-4, 0, 4), (a, 0, -a), "tie", "tie_a", "tie_a_" + kind); ray(h + (4, 0, -4), (-a, 0, a), "tie", "tie_a", "tie_a_" + kind)
+    # ---- ... class (b): the same ties with a = k / 8 drawn by a seeded search, kept where a s rounds (the two rounded products still cancel exactly in the
+    # reference's order; a fused multiply-add leaves the rounding error of one product, of either sign) and the model of triangle::hit confirms the tie
+    rng = np.random.default_rng(20261019)
+    for cell in range(18):
+        kind = tris[cell][2]
+        verts, normals = sw.tri_local(sw.BENT)
+        verts = [v + at(cell) for v in verts]
+        kept = 0
+        while kept < 8:
+            a = float(2 * rng.integers(1, 64) + 1) / 8.0
+            y = float(rng.integers(1, 16)) / 16.0 - 1.0
+            back = bool(rng.integers(0, 2))
+            dy = float(rng.integers(-3, 4)) / 4.0   # the normal's y is exactly 0: any y of the direction leaves the tie
+            h = at(cell) + (0, y, 0)
+            d = V(-a, dy, a) if back else V(a, dy, -a)
+            o = h - 4.0 * d
+            m = sw.triangle_face(verts, normals, o, d)
+            if m is None or m[3] != 0.0 or not sw.inexact_products(d, m[2]):
+                continue
+            ray(o, d, "tie", "tie_b", "tie_b_" + kind); kept += 1
+    # ---- ... and on spheres.  Class (a): the tangent ray x = centre + r straight down -z (discriminant exactly 0, outward normal (1, 0, 0)), and at the top
+    for cell, (kind, wrapped) in sphs.items():
+        c = at(cell)
+        ray(c + (1, 0, 5), (0, 0, -1), "tie", "tie_a", "tie_a_sphere"); ray(c + (0, 1, 5), (0, 0, -2), "tie", "tie_a", "tie_a_sphere")
+    # Class (b): tangent rays along (a, 0, -a) at the point centre + (s, 0, s), s = sqrt(1/2) to within a few units in the last place, searched with the model
+    # of sphere::hit, 20 000 candidates per sphere at the most (a fraction of a second): kept where the discriminant does not go negative, the products a n.x and a n.z round and still cancel
+    found = 0
+    rng = np.random.default_rng(20261020)
+    s0 = float(np.sqrt(0.5))
+    for cell in (40, 42, 48, 41, 43, 49):
+        kept, tries = 0, 0
+        while kept < 8 and tries < 20000:
+            tries += 1
+            a = float(2 * rng.integers(1, 1 << 25) + 1) / float(1 << 23)   # (26 bits: around |centre| ~ 40 the normal's components keep ~47, so a short a multiplies exactly)
+            sx, sz = s0 + float(rng.integers(-3, 4)) * np.spacing(s0), s0 + float(rng.integers(-3, 4)) * np.spacing(s0)
+            o = at(cell) + V(sx - 4 * a, 0, sz + 4 * a)
+            d = V(a, 0, -a)
+            # the reference meets a sphere under a translate in the translate's frame (translate.hpp: origin - offset), a bare one where it stands
+            m = sw.sphere_face(np.zeros(3), 1.0, o - at(cell), d) if sphs[cell][1] else sw.sphere_face(at(cell), 1.0, o, d)
+            if m is None or m[3] != 0.0 or not sw.inexact_products(d, m[2]):
+                continue
+            ray(o, d, "tie", "tie_b", "tie_b_sphere"); kept += 1; found += 1
+    # ---- the dielectric threshold ri sin(theta) = 1 on the flat glass triangles (cells 18-25, bare and under a translate), for every index and face that has
+    # one (ri > 1: index 1.5 and 2.4 from behind the bare triangle, index 1 / 1.5 from the front and, under the translate, from behind too; with index 1.0 ri sin(theta) never exceeds 1): sin(theta) = (1 / ri) stepped by
+    # whole units in the last place, or (1 / ri)(1 + delta); six keys each, so that below the threshold both the reflect and the refract draw occur
+    steps = [("0", 0, 0.0)] + [(f"{sg}{n}ulp", (1 if sg == "+" else -1) * n, 0.0) for n in (1, 2, 4) for sg in "+-"] + \
+            [(f"{sg}{e:g}", 0, (1 if sg == "+" else -1) * e) for e in (1e-12, 1e-9, 1e-6) for sg in "+-"]
+    for g, index in enumerate(sw.GLASS_INDEX):
+        for cell in (18 + 2 * g, 19 + 2 * g):
+            for front in (True, False):
+                # (under the translate set_face_normal runs again on the turned normal and answers front_face = true from either side: translate.hpp:29)
+                ri = (1.0 / index) if front or cell % 2 else index
+                if not ri > 1.0:
+                    continue
+                hit = at(cell) + (0.125, -0.25, 0)
+                for label, ulps, dl in steps:
+                    s = 1.0 / ri
+                    s = s + ulps * np.spacing(s) if ulps else s * (1.0 + dl)
+                    d = V(s, 0, -np.sqrt(1.0 - s * s)) if front else V(s, 0, np.sqrt(1.0 - s * s))
+                    for rep in range(6):
+                        delta[ray(hit - 4.0 * d, d, "threshold")] = label
+    # ---- exact normal incidence (ct == 1) on every flat glass triangle from both faces, with directions of length 1e-3, 1 and 1e3; the same lengths at an
+    # oblique angle; and grazing incidence, ct = 1e-10 (the direction is long, because triangle::hit rejects |N.d| < 1e-8 before normalising)
+    for cell in range(18, 26):
+        hit = at(cell) + (0.125, -0.25, 0)
+        for sgn in (1.0, -1.0):
+            for ln in (1e-3, 1.0, 1e3):
+                ray(hit + (0, 0, 4 * sgn), (0, 0, -sgn * ln), "normal_incidence", "unnormalised")
+                ray(hit + V(-1.2, -0.4, 4 * sgn), ln * V(0.3, 0.1, -sgn), "unnormalised")
+            ray(hit + V(-4, 0, 4e-10 * sgn), 1e3 * V(1, 0, -1e-10 * sgn), "grazing")
+    # ---- ct clamped by fmin: rays through the centre of every glass sphere along seeded directions that are nothing special: dot(-unit(d), n) comes out a
+    # unit in the last place above 1 on some of them
+    rng = np.random.default_rng(20261021)
+    for cell in range(48, 56):
+        for k in range(24):
+            w = rng.normal(size=3); w /= np.linalg.norm(w)
+            ray(at(cell) + 5.0 * w, -w * (1.0, 0.125, 7.0)[k % 3], "central")
+    # ---- metal: fuzz 0 at normal, 45 degree and grazing incidence on the flat mirror and the mirror spheres ...
+    hit = at(26) + (0.125, -0.25, 0)
+    for d in (V(0, 0, -1), V(1, 0, -1), V(1, 0, -1e-6), V(0, 0, 1), V(1, 0, 1)):
+        ray(hit - 4.0 * d, d, "mirror")
+    for cell in (42, 43):
+        for o, d in (((0, 0, 5), (0, 0, -1)), ((np.sqrt(0.5), 0, 5), (0, 0, -1)), ((0.999999, 0, 5), (0, 0, -1))):
+            ray(at(cell) + o, d, "mirror")
+    # ... and fuzz 0.4 and 1 at grazing incidence on a hundred keys per sphere: the fuzzed reflection dips below the surface on some, scatter answers both ways
+    for cell in (44, 45, 46, 47):
+        for k in range(100):
+            ray(at(cell) + (0.99, 0, 5), (0, 0, -1), "fuzzy_grazing")
+    n27 = place(27, (0, 0, 1)) - at(27)   # the fuzzy triangle turned by 0.5 about y: along its normal from both sides, then low over its face on forty keys
+    t27 = place(27, (1, 0, 0)) - at(27)
+    a27 = place(27, (0.125, -0.25, 0))
+    ray(a27 + 3.0 * n27, -n27, "turned"); ray(a27 - 3.0 * n27, n27, "turned")
+    for k in range(40):
+        ray(a27 + 1.0 * n27 - 3.0 * t27, 3.0 * t27 - 1.0 * n27, "turned", "fuzzy_grazing")
+    # ---- vertex normals that oppose the face (cells 30-34; the interpolated normal's z changes sign at u = 5/9, x = 1/9): straight down, straight up and
+    # obliquely on both sides of that line — a reflection about such a normal goes below the geometric face; four keys each for the fuzzed metals
+    for cell in range(30, 35):
+        for x in (-0.75, -0.5, -0.25, 0.0, 0.125, 0.25, 0.375):
+            hit = at(cell) + (x, -0.5, 0)
+            for d in (V(0, 0, -1), V(0, 0, 1), V(0.5, 0, -1), V(-0.5, 0.25, 1)):
+                for rep in range(4 if cell in (31, 32) else 1):
+                    ray(hit - 3.0 * d, d, "opposed")
+    # ---- vertex normals that cancel (cells 35-37): on x = 0 the interpolated normal is 0, unit_vector answers (0, 0, 0) (its `< 1e-8` branch) and front_face is
+    # false with a normal of zeros; a step of 2^-30 to either side it is (0, 0, +-1) again
+    for cell in (35, 36, 37):
+        for x in (0.0, 2.0 ** -30, -2.0 ** -30):
+            for y in (-0.5, -0.25):
+                ray(at(cell) + (x, y, 3), (0, 0, -1), "cancel"); ray(at(cell) + (x, y, -3), (0, 0, 1), "cancel"); ray(at(cell) + (x - 1.5, y, 3), (0.5, 0, -1), "cancel")
+    # ---- lambertian's degenerate direction, reached on purpose: the unit vector ray k draws depends on k alone, so ray k goes straight at the point of a
+    # lambertian sphere (bare, and under a translate) whose outward normal is -ruv(k): normal + ruv is ~1e-16 in every component and the direction falls
+    # back to the normal; its neighbour arrives 1e-7 to the side, where the sum is ~1e-7 and must stand
+    for k in range(16):
+        for near in (False, True):
+            row = len(R)
+            ruv, _ = sw.random_unit_vector(sw.kat_key(row))
+            if near:
+                side = np.cross(ruv, V(0, 0, 1) if abs(ruv[2]) < 0.9 else V(1, 0, 0)); side /= np.linalg.norm(side)
+                w = ruv + 1e-7 * side; w /= np.linalg.norm(w)
+            else:
+                w = ruv
+            ray(at(40 + k % 2) - 5.0 * w, w, "lambert_near" if near else "lambert_fallback")
+    # ---- triangle hit positions: the vertices, the edge midpoints and the centroid of every triangle from both faces (the turned one: its centroid and a
+    # point beside it only — its baked vertices are rounded, and which side of an edge such a ray passes is the reference's local arithmetic)
+    for cell, (shape, form, kind) in sorted(tris.items()):
+        verts, _ = sw.tri_local(shape)
+        a, b, c = verts
+        pts = [(a + b + c) / 3.0, (a + b + c) / 3.0 + (0.0625, 0.03125, 0)] if form == 6 else [a, b, c, (a + b) / 2, (b + c) / 2, (c + a) / 2, (a + b + c) / 3.0]
+        nrm = place(cell, (0, 0, 1)) - at(cell)
+        for q in pts:
+            ray(place(cell, q) + 3.0 * nrm, -nrm, "tri_positions"); ray(place(cell, q) - 3.0 * nrm, nrm, "tri_positions")
+    # ---- sphere hit positions: the poles, the equator, from outside and from inside, on every sphere (the light, the one without a material and the one with
+    # a negative radius, which nothing hits, among them)
+    for cell in list(sphs) + [58]:
+        c = at(cell) + ((0.125, 0.0625, 0.25) if cell == 58 else (0, 0, 0))   # (beside the centre there: a ray through the centre of a sphere of radius 0 "hits" it with a normal of NaNs)
+        for e in (V(1, 0, 0), V(0, 1, 0), V(0, 0, 1)):
+            ray(c + 5.0 * e, -e, "sphere_positions"); ray(c - 5.0 * e, e, "sphere_positions")
+            ray(c, e, "sphere_positions", "sphere_inside"); ray(c + (0.25, 0.125, -0.5), -0.5 * e, "sphere_positions", "sphere_inside")
+        ray(c + (0.5, 0.25, 5), (0, 0, -1), "sphere_positions")
+    # ---- between the cells: nothing there
+    for k in range(0, 60, 4):
+        ray(at(k) + (4, 4, 5), (0, 0, -1), "between")
+    return np.array(R, dtype=np.float64), {k: np.array(v) for k, v in cls.items()}, delta, found
+
+
+def make_kat2(tmp):
+    rays, cls, delta, found = kat2_inputs()
+    f = os.path.join(tmp, "kat2_hits.bin"); pre = os.path.join(tmp, "kat2_hits")
+    rays.tofile(f)
+    meta = run("kat", "kat2", "hits", f, len(rays), pre)
+    recs = np.load(pre + "_recs.npy")
+    meta["rays_hit"] = int((recs[:, 0] > 0).sum())
+    meta["sphere_ties_b"] = found   # class (b) ties on spheres the search found (0: none among its candidates)
+    meta["absent"] = ("bent normals with dot(-unit(d), n) < 0 (1 - ct > 1): set_face_normal (hittable.hpp:22-25) always leaves the normal against the ray, and a "
+                      "lean world has no bump map to replace it, so no record of this world has it; it occurs by rounding on the ties only, which are here")
+    out = os.path.join(HERE, "kat_kat2.npz")
+    np.savez_compressed(out, meta=np.array(json.dumps({"hits": meta})), rays=rays, recs=recs, scat=np.load(pre + "_scat.npy"))
+    print("kat_kat2", len(rays), "rays,", meta["rays_hit"], "hit,", {k: len(v) for k, v in cls.items()}, os.path.getsize(out), "bytes")
+
+
 def make_refdemo(tmp):
     """The reference's OWN demo world (load_materials + sceneAssetsLoader + build_geometry, scene_management.hpp:28-236) for the GPU: the scene reads the
     reference's assets/ at run time, which never travel — so the world travels FLATTENED.  oracle/_ref/refscene_dropin (the reference's scene code compiled
@@ -505,6 +696,8 @@ def main():
             make_kat(tmp)
         if not want or "kat" in want or "kat1" in want:
             make_kat1(tmp)
+        if not want or "kat" in want or "kat2" in want:
+            make_kat2(tmp)
         if not want or "texels" in want:
             out = os.path.join(tmp, "texels.npy")
             subprocess.run([REF, "texels", "64", "32", out], check=True)
