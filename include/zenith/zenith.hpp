@@ -1376,8 +1376,10 @@ inline volatile int* rows_ptr(std::atomic<int>& rows) { return reinterpret_cast<
 // owning handles of the C ABI's scene and accumulator
 struct scene_deleter { void operator()(zr_scene* sc) const { zr_scene_destroy(sc); } };   // (frees the scene's device arrays; touches no context state: no lease)
 struct accum_deleter { void operator()(zr_accum* acc) const { zr_accum_destroy(acc); } };
+struct temporal_deleter { void operator()(zr_temporal* t) const { zr_temporal_destroy(t); } };
 using scene_handle = std::unique_ptr<zr_scene, scene_deleter>;
 using accum_handle = std::unique_ptr<zr_accum, accum_deleter>;
+using temporal_handle = std::unique_ptr<zr_temporal, temporal_deleter>;
 
 // ---- callable hit() / scatter(): one ray through the device ---------------------------------------------------------
 // The object is flattened once and committed as a scene of its own (cached in the object, per context; set_material drops
@@ -1504,6 +1506,18 @@ public:
     bool denoise_variance_guided = false;
     std::vector<color> variance_buffer;   // extension: filled by a render with use_denoiser and denoise_variance_guided that had a variance; empty otherwise
     bool denoise_used_variance = false;   // extension: the last render's denoise_buffer came from the guided filter
+    // extension: temporal accumulation across render() calls of this camera object (zr_accum_temporal with temporal_params).  A frame that came
+    // through an accumulator with a variance (denoise_variance_guided's condition: adaptive_threshold > 0, or samples_per_pass > 0 with samples_per_pixel a
+    // multiple of 64) is blended with the history of the frames before it, reprojected through the first hits of this camera's pixels: temporal_buffer holds
+    // the blend, variance_buffer its variance and temporal_history_length the frames behind every pixel.  With use_denoiser && denoise_variance_guided the
+    // guided filter takes those two in place of the frame's own.  The history belongs to a frame size and a world object (the `world` argument's address): it
+    // is dropped when either changes, or on reset_temporal_history() — the caller's duty after editing the world in place.  Static worlds only.  Without a
+    // variance a warning is printed and the render is what it is without the flag.  render_accumulator is never touched.  false: exactly the render without it.
+    bool temporal_accumulation = false;
+    zr_temporal_params temporal_params{ZR_TEMPORAL_DEFAULT_ALPHA, ZR_TEMPORAL_DEFAULT_MAX_HISTORY, 0, ZR_TEMPORAL_DEFAULT_PLANE_TOLERANCE, ZR_TEMPORAL_DEFAULT_NORMAL_COS};
+    std::vector<color> temporal_buffer;           // extension: the temporally accumulated frame of the last render; empty when it had none
+    std::vector<int> temporal_history_length;     // extension: frames accumulated per pixel (row-major like render_accumulator); empty likewise
+    void reset_temporal_history() { temporal_.reset(); }
     zr_adaptive_stats last_adaptive{};
     zr_counters last_counters{};
 
@@ -1579,14 +1593,17 @@ public:
             if (rc == ZR_OK) rc = zr_scene_commit(sc.get());
             ph("commit");
             if (rc == ZR_OK) {
-                const frame_job job{lease.ctx, sc.get(), to_zr(), zenv, render_flag};
+                const frame_job job{lease.ctx, sc.get(), to_zr(), zenv, render_flag, &world};
                 sample_counts.clear();
                 variance_buffer.clear(); denoise_used_variance = false;
+                temporal_buffer.clear(); temporal_history_length.clear();
                 if (debug) rc = render_debug_view(job);
                 else if (wants_adaptive()) rc = render_adaptive(job);
                 else if (samples_per_pass > 0) rc = render_progressive(job);
                 else rc = render_one_shot(job);
                 if (!debug) zr_get_counters(lease.ctx, &last_counters);
+                if (rc == ZR_OK && !debug && temporal_accumulation && temporal_buffer.empty())
+                    std::cerr << "[zenith] temporal_accumulation ignored: no variance (it needs adaptive_threshold, or samples_per_pass with a multiple of 64 samples)\n";
                 ph(debug ? "zr_render_bvh_debug" : "zr_render");
                 if (rc == ZR_OK && !debug) rc = render_aovs(job, post, guides);
                 if (rc == ZR_OK && !debug) rc = render_split_passes(job);
@@ -1607,6 +1624,7 @@ private:
         zr_ctx* ctx; const zr_scene* sc;
         zr_camera cam; zr_env env;
         std::atomic<bool>& flag;
+        const hittable* world;
     };
     // the denoiser's guides when the public AOV buffers are off (the reference would hand OIDN zero guides then)
     struct guide_frames { std::vector<color> albedo, normal; };
@@ -1629,6 +1647,22 @@ private:
         variance_buffer.assign(pixels(), color(0, 0, 0));
         const int rc = zr_accum_variance(acc, zenith::doubles(variance_buffer));
         if (rc != ZR_OK) variance_buffer.clear();
+        return rc;
+    }
+
+    // the accumulator's frame into this camera's history (made anew when the frame size, the world object or the context differ from the history's)
+    int accumulate_temporal(const frame_job& j, zr_accum* acc) {
+        if (!temporal_accumulation) return ZR_OK;
+        static_assert(sizeof(int) == sizeof(int32_t), "temporal_history_length layout");
+        if (!temporal_ || temporal_ctx_ != j.ctx || temporal_world_ != j.world || temporal_w_ != image_width || temporal_h_ != image_height) {
+            temporal_.reset(zr_temporal_create(j.ctx, image_width, image_height));
+            if (!temporal_) return ZR_E_DEVICE;
+            temporal_ctx_ = j.ctx; temporal_world_ = j.world; temporal_w_ = image_width; temporal_h_ = image_height;
+        }
+        temporal_buffer.assign(pixels(), color(0, 0, 0)); variance_buffer.assign(pixels(), color(0, 0, 0)); temporal_history_length.assign(pixels(), 0);
+        const int rc = zr_accum_temporal(acc, temporal_.get(), &temporal_params, j.sc, &j.cam, seed, zenith::doubles(temporal_buffer), zenith::doubles(variance_buffer),
+                                         reinterpret_cast<int32_t*>(temporal_history_length.data()));
+        if (rc != ZR_OK) { temporal_buffer.clear(); variance_buffer.clear(); temporal_history_length.clear(); }
         return rc;
     }
 
@@ -1658,6 +1692,7 @@ private:
             if (qrc == ZR_OK) qrc = zr_accum_sample_counts(acc.get(), reinterpret_cast<int32_t*>(sample_counts.data()));
             if (qrc == ZR_OK) qrc = zr_accum_state(acc.get(), st4);
             if (qrc == ZR_OK && rc == ZR_OK) qrc = fetch_variance(acc.get());
+            if (qrc == ZR_OK && rc == ZR_OK) qrc = accumulate_temporal(j, acc.get());
             if (qrc != ZR_OK) return qrc;
             current_samples_count = (int)st4[1]; passes_rendered = (int)last_adaptive.passes;
         }
@@ -1680,7 +1715,9 @@ private:
             lines_rendered = current_samples_count < spp ? (int)((long long)image_height * current_samples_count / spp) : image_height;
             if (current_samples_count < spp && !j.flag.load()) return ZR_E_CANCELLED;
         }
-        return spp % 64 == 0 ? fetch_variance(acc.get()) : ZR_OK;
+        if (spp % 64 != 0) return ZR_OK;
+        const int rc = fetch_variance(acc.get());
+        return rc == ZR_OK ? accumulate_temporal(j, acc.get()) : rc;
     }
     // the first-hit passes whose flags are set, and the denoiser's guides: the public buffers when their flags are set, `guides` otherwise
     int render_aovs(const frame_job& j, const post_processor& post, guide_frames& guides) {
@@ -1704,7 +1741,8 @@ private:
     int denoise_frames(const post_processor& post, const guide_frames& guides) {
         const std::vector<color>& ga = use_albedo_buffer ? albedo_buffer : guides.albedo;
         const std::vector<color>& gn = use_normal_buffer ? normal_buffer : guides.normal;
-        denoise_buffer = render_accumulator;
+        // (a temporally accumulated frame: the guided filter takes it and its variance in place of the frame's own)
+        denoise_buffer = denoise_variance_guided && temporal_buffer.size() == render_accumulator.size() ? temporal_buffer : render_accumulator;
         int rc;
         if (denoise_variance_guided && variance_buffer.size() == render_accumulator.size()) {
             rc = denoise_guided(denoise_buffer, variance_buffer, ga, gn);
@@ -1748,4 +1786,8 @@ private:
             return zr_denoise_guided(ctx, &dp, p, zenith::doubles(variance), zenith::doubles(albedo), zenith::doubles(normal), nullptr, image_width, image_height, p, nullptr);
         });
     }
+
+    // the history of temporal_accumulation and what it was made for
+    zenith::temporal_handle temporal_;
+    zr_ctx* temporal_ctx_ = nullptr; const hittable* temporal_world_ = nullptr; int temporal_w_ = 0, temporal_h_ = 0;
 };

@@ -512,6 +512,63 @@ int zr_denoise_guided(zr_ctx*, const zr_denoise_guided_params*, const double* co
                       const double* normal, const double* zdepth, int width, int height, double* out, double* out_variance);
 int zr_accum_denoise(zr_accum*, const zr_denoise_guided_params*, const double* albedo, const double* normal, const double* zdepth,
                      double* out, double* out_variance);
+/* ---- temporal accumulation: a frame's history reprojected across a moving camera ------------------------------
+ * The temporal stage of SVGF (Schied et al., HPG 2017, section 4.1) for a camera path through a STATIC world; the reference has no counterpart.
+ * zr_render_gbuffer    the first hit of the ray through the centre of every pixel (get_center_ray, camera.hpp:809-814: origin `center`, direction
+ *                      (pixel00_loc + i pixel_delta_u + j pixel_delta_v) - center; no jitter, no defocus disk), W*H pixels row-major: by definition what
+ *                      zr_trace(those rays, tmin 0.001, tmax inf, seed, pixel = ZR_GBUFFER_STREAM, bounce 0) returns — constant-medium hits included — as
+ *                      position rec.p, unit normal, t and material id.  A miss holds the ray DIRECTION in the position plane, normal 0, t 0 and
+ *                      mat 0xFFFFFFFF.  Host memory; any output may be NULL.  Argument checks and error codes as zr_render_aov.
+ * zr_temporal          the history of a width x height frame on the device, double-buffered in FP64: blended colour and variance, history length, the
+ *                      previous frame's geometry buffer and the previous camera.  zr_temporal_reset forgets it (the caller's duty after any change of the
+ *                      scene); zr_temporal_state: out = width, height, frames accumulated since create / reset, 0.
+ * zr_temporal_accumulate  takes one frame — `color` and `variance` (of the pixel means, e.g. zr_accum_resolve / zr_accum_variance), W*H*3 doubles in host
+ *                      memory — makes the camera's geometry buffer and, per pixel p (FP64, no contraction; tests/temporal_model.py restates it):
+ *                        c, V: the inputs with NaN / Inf -> 0 and V <= 0 -> 0 (zr_denoise_guided's rules);
+ *                        the first hit X_p is projected into the previous camera (a miss: its direction, so the sky follows rotation only): a point that is
+ *                        not in front of it has no history; coordinates within 2^-20 px of a whole pixel snap to it, so an unchanged camera and
+ *                        whole-pixel shifts reproject exactly;
+ *                        the four bilinear taps q count when their weight is > 0, they lie in the frame, hold history, mat_q == mat_p and, for hits,
+ *                        |(X_q - X_p) . n_p| <= plane_tolerance depth_p and n_p . n_q >= normal_cos;
+ *                        no counting tap: N = 1, out = c, V_out = V (also the whole first frame after create / reset).  Else, over the counting taps,
+ *                        h = sum w h_q / sum w, Vh = sum w V_q / sum w, N = min(min N_q + 1, max_history), beta = max(1 / N, alpha),
+ *                        out = h + beta (c - h), V_out = (1 - beta)^2 Vh + beta^2 V;
+ *                      out, V_out, N and the geometry buffer become the history.  out_color / out_variance (W*H*3 doubles) and out_history (W*H int32) are
+ *                      host memory and may each be NULL; the first two may be handed to zr_denoise_guided as they are.  ZR_E_INVALID before any device
+ *                      work: parameters out of range or not finite (checked first), NULL, a camera of another size or without a finite view, a scene or
+ *                      history of another context; ZR_E_STATE: scene not committed.  Limits: static worlds; mirrors, glass and media reproject by their
+ *                      first hit; the filtered image is not fed back.
+ * zr_accum_temporal    zr_temporal_accumulate(zr_accum_resolve(), zr_accum_variance(), ...) bit for bit, resolved on the device straight into the kernel.
+ *                      Whole-frame accumulators only (ZR_E_INVALID otherwise); then zr_accum_variance's state rules.
+ * zr_temporal_view     known-answer entry, no device: the camera as the reprojection sees it, out = center 3, pixel00 3, unit w 3, a = du / (du . du) 3,
+ *                      b = dv / (dv . dv) 3, focus_dist — from the quantities zr_render derives (camera::initialize, camera.hpp:358-399). */
+#define ZR_GBUFFER_STREAM 0xFFFFFFFEull   /* the `pixel` of the geometry buffer's RNG keys: ray k draws from zr_stream_key(seed, ZR_GBUFFER_STREAM, k) */
+int zr_render_gbuffer(zr_ctx*, const zr_scene*, const zr_camera*, uint64_t seed, double* out_position, double* out_normal, double* out_t, uint32_t* out_mat);
+typedef struct zr_temporal zr_temporal;
+typedef struct zr_temporal_params {
+    double alpha;            /* floor of the blend weight, in (0, 1]; 1 = no reuse */
+    int32_t max_history;     /* 1..65535 */
+    int32_t pad_;
+    double plane_tolerance;  /* > 0: |(X_q - X_p) . n_p| <= plane_tolerance * depth_p */
+    double normal_cos;       /* in [-1, 1]: n_p . n_q >= normal_cos */
+} zr_temporal_params;
+/* defaults: the setting of scripts/dev/temporal_sweep.py with the best worse-of-two-scenes factor of the guided filter on the temporal frame, on 8-frame paths of
+ * 64-spp frames of cfg5 and mix0 against 4096 spp; what camera::render uses with temporal_accumulation.  The sweep began at alpha 0.2 and plane_tolerance
+ * 0.01: on the textured scene the repeated bilinear resampling costs more than the longer memory of a smaller alpha gains. */
+#define ZR_TEMPORAL_DEFAULT_ALPHA 0.4
+#define ZR_TEMPORAL_DEFAULT_MAX_HISTORY 32
+#define ZR_TEMPORAL_DEFAULT_PLANE_TOLERANCE 0.03
+#define ZR_TEMPORAL_DEFAULT_NORMAL_COS 0.9
+zr_temporal* zr_temporal_create(zr_ctx*, int width, int height);
+void zr_temporal_destroy(zr_temporal*);
+int zr_temporal_reset(zr_temporal*);
+int zr_temporal_state(const zr_temporal*, int64_t out[4]);
+int zr_temporal_accumulate(zr_temporal*, const zr_temporal_params*, const zr_scene*, const zr_camera*, uint64_t seed, const double* color,
+                           const double* variance, double* out_color, double* out_variance, int32_t* out_history);
+int zr_accum_temporal(zr_accum*, zr_temporal*, const zr_temporal_params*, const zr_scene*, const zr_camera*, uint64_t seed, double* out_color,
+                      double* out_variance, int32_t* out_history);
+int zr_temporal_view(const zr_camera*, double out[16]);
+
 /* post_processor::apply_sharpening (color_processing.hpp:207-227) on its own: interior pixels become
  * c (1 - amount) + (5 c - the four neighbours) amount, border pixels are copied.  Double in, double out, byte-exact with
  * the reference; amount <= 0 copies.  Host memory, W*H*3 doubles; out may equal in. */

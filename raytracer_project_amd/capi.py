@@ -121,6 +121,21 @@ class DenoiseGuidedParams(C.Structure):
         return p
 
 
+class TemporalParams(C.Structure):
+    """zr_temporal_params: how a frame's history is reprojected and blended (include/zr_capi.h)"""
+    _fields_ = [("alpha", C.c_double), ("max_history", C.c_int32), ("pad_", C.c_int32), ("plane_tolerance", C.c_double), ("normal_cos", C.c_double)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """ZR_TEMPORAL_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with temporal_accumulation)"""
+        p = cls(0.4, 32, 0, 0.03, 0.9)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"TemporalParams has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class BvhDebugParams(C.Structure):
     """zr_bvh_debug_params: global_settings::debug_bvh_level / bvh_thickness of the BVH debug view (include/zr_capi.h, DESIGN §10)"""
     _fields_ = [("level", C.c_int32), ("thickness", C.c_float)]
@@ -241,6 +256,8 @@ CAPI_SYMBOLS = [
     "zr_render_adaptive", "zr_accum_error", "zr_accum_sample_counts", "zr_accum_lane_sums",
     "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
     "zr_accum_variance", "zr_denoise_guided", "zr_accum_denoise",
+    "zr_render_gbuffer", "zr_temporal_create", "zr_temporal_destroy", "zr_temporal_reset", "zr_temporal_state", "zr_temporal_accumulate", "zr_accum_temporal",
+    "zr_temporal_view",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_shade_lean", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
@@ -300,6 +317,15 @@ def load():
     lib.zr_accum_variance.argtypes = [vp, vp]
     lib.zr_denoise_guided.argtypes = [vp, C.POINTER(DenoiseGuidedParams), vp, vp, vp, vp, vp, i32, i32, vp, vp]
     lib.zr_accum_denoise.argtypes = [vp, C.POINTER(DenoiseGuidedParams), vp, vp, vp, vp, vp]
+    if hasattr(lib, "zr_temporal_create"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
+        lib.zr_render_gbuffer.argtypes = [vp, vp, C.POINTER(Camera), u64, vp, vp, vp, vp]
+        lib.zr_temporal_create.restype = vp; lib.zr_temporal_create.argtypes = [vp, i32, i32]
+        lib.zr_temporal_destroy.argtypes = [vp]; lib.zr_temporal_destroy.restype = None
+        lib.zr_temporal_reset.argtypes = [vp]
+        lib.zr_temporal_state.argtypes = [vp, C.POINTER(C.c_int64 * 4)]
+        lib.zr_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalParams), vp, C.POINTER(Camera), u64, vp, vp, vp, vp, vp]
+        lib.zr_accum_temporal.argtypes = [vp, vp, C.POINTER(TemporalParams), vp, C.POINTER(Camera), u64, vp, vp, vp]
+        lib.zr_temporal_view.argtypes = [C.POINTER(Camera), C.POINTER(C.c_double * 16)]
     lib.zr_render_bvh_debug.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), C.POINTER(BvhDebugParams), vp, vp, vp]
     lib.zr_trace_bvh_debug.argtypes = [vp, vp, C.POINTER(BvhDebugParams), vp, C.c_size_t, C.c_double, u64, u64, C.c_uint32, vp]
     lib.zr_scene_tree_boxes.argtypes = [vp, vp, C.c_size_t]
@@ -349,6 +375,7 @@ def load_scenes():
     s.zrs_render_dropin_threads.argtypes = frame + [i32, vp]
     s.zrs_render_dropin_denoise.argtypes = frame + [i32] + [vp] * 6
     s.zrs_render_dropin_denoise_guided.argtypes = frame + [C.c_double, i32, i32] + [vp] * 4
+    s.zrs_render_dropin_temporal.argtypes = frame + [i32, vp, i32, i32] + [vp] * 5
     s.zrs_render_dropin_bvh_debug.argtypes = frame + [i32, C.c_float, vp, vp]
     s.zrs_dropin_virtuals.argtypes = [vp, vp, i32, C.c_uint64, C.c_uint64, vp, vp]
     s.zrs_dropin_frame_to_rgb8.argtypes = [vp, i32, i32, vp, vp, C.POINTER(C.c_float)]
@@ -450,6 +477,22 @@ class DemoScene:
         self._rendered(load_scenes().zrs_render_dropin_denoise_guided(self._h, width, height, spp, device, float(threshold), int(samples_per_pass),
                                                                       1 if guided else 0, *[o.ctypes.data for o in outs.values()], info) == 0)
         outs["guided"] = bool(info[0])
+        return outs
+
+    def render_dropin_temporal(self, cameras, temporal=True, guided=False, samples_per_pass=0, reset_before_last=False, width=0, height=0, spp=0, device=0):
+        """a camera path through ONE drop-in camera object and one world object: a render per entry of `cameras` (capi.Camera: lookfrom / lookat are
+        taken) with seed = the scene's + k, camera::temporal_accumulation = temporal, use_denoiser and denoise_variance_guided = guided, progressive when
+        samples_per_pass > 0 else one-shot.  Dict of render_accumulator, temporal_buffer, variance_buffer, denoise_buffer ((n, H, W, 3) float64; a frame
+        that left the buffer empty is all -1) and temporal_history_length ((n, H, W) int32, -1 likewise)"""
+        n = len(cameras)
+        w = width or self.camera.image_width
+        h = height or self.camera.image_height
+        cams = np.array([list(c.lookfrom) + list(c.lookat) for c in cameras], dtype=np.float64)
+        outs = {k: np.zeros((n, h, w, 3), dtype=np.float64) for k in ("render_accumulator", "temporal_buffer", "variance_buffer", "denoise_buffer")}
+        outs["temporal_history_length"] = np.zeros((n, h, w), dtype=np.int32)
+        flags = (1 if temporal else 0) | (2 if guided else 0) | (4 if reset_before_last else 0)
+        self._rendered(load_scenes().zrs_render_dropin_temporal(self._h, width, height, spp, device, n, cams.ctypes.data, flags, int(samples_per_pass),
+                                                                *[o.ctypes.data for o in outs.values()]) == 0)
         return outs
 
     def render_dropin_bvh_debug(self, level, thickness, width=0, height=0, spp=0, device=0):
@@ -668,6 +711,15 @@ class Accumulator:
                                          zdepth.ctypes.data if zdepth is not None else None, out.ctypes.data, out_variance.ctypes.data))
         return out, out_variance
 
+    def temporal(self, history, scene, camera, seed, params=None):
+        """zr_accum_temporal: history.accumulate(scene, camera, seed, resolve(), variance(), params) bit for bit, with colour and variance resolved on
+        the device; returns (colour, variance, history length).  Whole-frame accumulators only."""
+        params = params if params is not None else TemporalParams.defaults()
+        out, out_variance, length = history._outputs()
+        _check(self.lib.zr_accum_temporal(self._a, history._t, C.byref(params), scene._s, C.byref(camera), C.c_uint64(seed), out.ctypes.data,
+                                          out_variance.ctypes.data, length.ctypes.data))
+        return out, out_variance, length
+
     def sample_counts(self, out=None):
         """samples per pixel: (H, W) int32; only the region's pixels are written"""
         if out is None:
@@ -702,6 +754,64 @@ class Accumulator:
             self.close()
         except Exception:
             pass
+
+
+class Temporal:
+    """The history of a width x height frame across a moving camera (zr_temporal): blended colour, variance, history length and the
+    previous frame's geometry buffer and camera, all on the device."""
+
+    def __init__(self, ctx, width, height):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.width, self.height = int(width), int(height)
+        self._t = self.lib.zr_temporal_create(ctx._c, self.width, self.height)
+        if not self._t:
+            raise ZrError(self.lib.zr_last_error().decode())
+
+    def _outputs(self):
+        shape = (self.height, self.width, 3)
+        return np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.float64), np.zeros(shape[:2], dtype=np.int32)
+
+    def accumulate(self, scene, camera, seed, color, variance, params=None):
+        """zr_temporal_accumulate: takes the frame (color, variance of the pixel means: (H, W, 3) float64) rendered from `camera` into the history;
+        returns (colour, variance, history length) of the blend"""
+        params = params if params is not None else TemporalParams.defaults()
+        shape = (self.height, self.width, 3)
+        color = np.ascontiguousarray(color, dtype=np.float64); variance = np.ascontiguousarray(variance, dtype=np.float64)
+        if color.shape != shape or variance.shape != shape:
+            raise ValueError(f"frame shapes {color.shape}, {variance.shape} differ from the history's {shape}")
+        out, out_variance, length = self._outputs()
+        _check(self.lib.zr_temporal_accumulate(self._t, C.byref(params), scene._s, C.byref(camera), C.c_uint64(seed), color.ctypes.data,
+                                               variance.ctypes.data, out.ctypes.data, out_variance.ctypes.data, length.ctypes.data))
+        return out, out_variance, length
+
+    def reset(self):
+        """forgets the history (the caller's duty after a scene change): the next frame starts at length 1"""
+        _check(self.lib.zr_temporal_reset(self._t))
+
+    def state(self):
+        out = (C.c_int64 * 4)()
+        _check(self.lib.zr_temporal_state(self._t, C.byref(out)))
+        return {"width": out[0], "height": out[1], "frames": out[2]}
+
+    def close(self):
+        if self._t:
+            self.lib.zr_temporal_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def temporal_view(camera):
+    """zr_temporal_view: the camera as the reprojection sees it (no device): dict of center, pixel00, w, a, b (3 each) and f"""
+    out = (C.c_double * 16)()
+    _check(load().zr_temporal_view(C.byref(camera), C.byref(out)))
+    v = np.array(out[:], dtype=np.float64)
+    return {"center": v[0:3], "pixel00": v[3:6], "w": v[6:9], "a": v[9:12], "b": v[12:15], "f": float(v[15])}
 
 
 class Scene:
@@ -753,6 +863,14 @@ class Scene:
         _check(self.lib.zr_render_aov(self.ctx._c, self._s, C.byref(camera), C.c_uint64(seed), rp, C.byref(ap),
                                       outs[0].ctypes.data, outs[1].ctypes.data, outs[2].ctypes.data))
         return outs
+
+    def render_gbuffer(self, camera, seed):
+        """zr_render_gbuffer: the first hit of every pixel's centre ray: dict of position (H, W, 3), normal (H, W, 3, unit), t (H, W) float64 and
+        mat (H, W) uint32 (0xFFFFFFFF on a miss, where position holds the ray direction)"""
+        h, w = max(camera.image_height, 1), max(camera.image_width, 1)
+        g = {"position": np.zeros((h, w, 3)), "normal": np.zeros((h, w, 3)), "t": np.zeros((h, w)), "mat": np.zeros((h, w), dtype=np.uint32)}
+        _check(self.lib.zr_render_gbuffer(self.ctx._c, self._s, C.byref(camera), C.c_uint64(seed), *[a.ctypes.data for a in g.values()]))
+        return g
 
     PATH_RECORD = 17
 

@@ -443,4 +443,26 @@ int zr_accum_denoise(zr_accum* a, const zr_denoise_guided_params* dp, const doub
     return denoise_guided_device(c, dp, d_c, d_v, albedo, normal, zdepth, st.plan.W, st.plan.H, out, out_variance);
 }
 
+// what an accumulator holds taken into a history (the reprojection itself: zr_temporal.cpp)
+int zr_accum_temporal(zr_accum* a, zr_temporal* t, const zr_temporal_params* p, const zr_scene* s, const zr_camera* cam, uint64_t seed, double* out_color,
+                      double* out_variance, int32_t* out_history) {
+    if (!p) return fail(ZR_E_INVALID, "null argument");
+    int rc = check_temporal_params(p);   // the parameters first: they need no device and no other argument
+    if (rc) return rc;
+    if (!a || !t || !s || !cam) return fail(ZR_E_INVALID, "null argument");
+    AccumState& st = a->st;
+    if (!st.plan.whole()) return fail(ZR_E_INVALID, "zr_accum_temporal takes whole frames: the accumulator was made with a region");
+    if ((rc = temporal_call_ready(t, st.ctx, s, cam, "zr_accum_temporal")) || (rc = variance_ready(st, "zr_accum_temporal"))) return rc;
+    int64_t shape[4];
+    (void)zr_temporal_state(t, shape);
+    if (shape[0] != st.plan.W || shape[1] != st.plan.H) return fail(ZR_E_INVALID, "accumulator of %d x %d px, history of %d x %d", st.plan.W, st.plan.H, (int)shape[0], (int)shape[1]);
+    zr_ctx* c = st.ctx;
+    HIP_OK(hipSetDevice(st.device));
+    DevBuf<double> d_c, d_v;
+    if ((rc = d_c.alloc(st.plan.npx() * 3)) || (rc = d_v.alloc(st.plan.npx() * 3))) return rc;
+    // a whole-frame plan: the two kernels write every pixel of the two frames
+    if ((rc = accum_resolve_into(st, d_c.p, c->stream)) || (rc = accum_variance_into(st, d_v.p, c->stream))) return rc;
+    return temporal_accumulate_device(t, p, s, cam, seed, d_c.p, d_v.p, out_color, out_variance, out_history);
+}
+
 }  // extern "C"

@@ -77,5 +77,15 @@ int render_batched(zr_ctx* c, const zr_scene* s, const FrameJob& frame, int n_ma
 int denoise_guided_device(zr_ctx* c, const zr_denoise_guided_params* dp, DevBuf<double>& d_c, DevBuf<double>& d_v, const double* albedo, const double* normal,
                           const double* zdepth, int W, int H, double* out, double* out_variance);
 int check_guided_params(const zr_denoise_guided_params* dp);
+// zr_render.cpp, for zr_temporal.cpp: camera::initialize's frame, and zr_trace's body for rays that are on the device already
+void camera_frame(const zr_camera& cam, zr::DCamera& dc);
+int trace_device(zr_ctx* c, const zr_scene* s, const double* d_rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel, uint32_t bounce,
+                 zr_hit* d_hits);
+// zr_temporal.cpp, for zr_accum.cpp (zr_accum_temporal calls them): the parameter check, what a call checks before any device work (its null tests aside),
+// and one frame taken from device memory (d_color / d_variance: W*H*3 doubles, complete on the context's stream)
+int check_temporal_params(const zr_temporal_params* p);
+int temporal_call_ready(const zr_temporal* t, const zr_ctx* c, const zr_scene* s, const zr_camera* cam, const char* entry);
+int temporal_accumulate_device(zr_temporal* t, const zr_temporal_params* p, const zr_scene* s, const zr_camera* cam, uint64_t seed, const double* d_color,
+                               const double* d_variance, double* out_color, double* out_variance, int32_t* out_history);
 
 }  // namespace zr_host

@@ -154,6 +154,15 @@ hipError_t launch_denoise(const double* d_color, const double* d_albedo, const d
 hipError_t launch_denoise_guided(const double* d_color, const double* d_variance, const double* d_albedo, const double* d_normal, const double* d_zdepth, int W,
                                  int H, const zr_denoise_guided_params& dp, float4* d_col0, float4* d_col1, float4* d_var0, float4* d_var1, float4* d_g0,
                                  float4* d_g1, double* d_out, double* d_out_var, hipStream_t stream);
+// Temporal accumulation (zr_temporal.hip).  A view is a camera as the reprojection needs it: centre, the first pixel's centre, the unit backward
+// axis w, the inverse of the pixel grid (a = du / (du . du), b = dv / (dv . dv): exact because du is perpendicular to dv) and the focus distance.
+struct TemporalView { double center[3], pixel00[3], w[3], a[3], b[3], f; };
+// one half of a history: the geometry planes of a frame (position / normal 3 doubles a pixel, material id) and the blended colour, variance and history length
+struct TemporalPlanes { double* pos; double* nrm; uint32_t* mat; double* col; double* var; int32_t* len; };
+hipError_t launch_gbuffer_rays(const DCamera& cam, double* d_rays, hipStream_t stream);
+hipError_t launch_gbuffer_pack(const zr_hit* d_hits, const double* d_rays, size_t n, double* d_pos, double* d_nrm, double* d_t, uint32_t* d_mat, hipStream_t stream);
+hipError_t launch_temporal_reproject(int W, int H, const TemporalView& cur, const TemporalView& prev, bool have_prev, const zr_temporal_params& tp,
+                                     const double* d_color, const double* d_variance, const TemporalPlanes& now, const TemporalPlanes& before, hipStream_t stream);
 hipError_t launch_bvh_debug(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, int level, float thickness, double* out,
                             hipStream_t stream);
 hipError_t launch_trace_bvh_debug(const DScene& sc, const double* rays, size_t n, double tmin, uint64_t seed, uint64_t pixel, uint32_t bounce, int level,

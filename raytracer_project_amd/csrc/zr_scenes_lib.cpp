@@ -225,6 +225,46 @@ int zrs_render_dropin_denoise_guided(void* p, int width, int height, int spp, in
     return 0;
 }
 
+// A camera path through ONE camera object and one world object (camera::temporal_accumulation keeps its history across render() calls of the object): n_frames
+// renders with lookfrom / lookat = cams6[k] (6 doubles a frame) and seed = the scene's + k.  flags: 1 = temporal_accumulation, 2 = use_denoiser with
+// denoise_variance_guided, 4 = reset_temporal_history() before the last frame.  samples_per_pass > 0 renders progressively, else in one shot.  Outputs, n_frames frames
+// each, any may be null: render_accumulator, temporal_buffer, variance_buffer, denoise_buffer (W*H*3 doubles a frame; all -1 for a frame that left the buffer
+// empty) and temporal_history_length (W*H ints, -1 likewise).  Returns 0, or -1 if a render did not finish.
+int zrs_render_dropin_temporal(void* p, int width, int height, int spp, int device, int n_frames, const double* cams6, int flags, int samples_per_pass, double* acc,
+                               double* tmp, double* var, double* den, int* hist) {
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
+    cam.temporal_accumulation = (flags & 1) != 0;
+    cam.use_denoiser = cam.denoise_variance_guided = (flags & 2) != 0;
+    cam.samples_per_pass = samples_per_pass;
+    const uint64_t seed0 = cam.seed;
+    const auto bvh_world = make_shared<bvh_node>(h.s.world);
+    const post_processor post;
+    const size_t npx = (size_t)cam.image_width * cam.image_height;
+    auto frame_out = [&](const std::vector<color>& frame, double* out, int k) {
+        if (!out) return;
+        if (frame.size() == npx) std::memcpy(out + (size_t)k * npx * 3, frame.data(), npx * sizeof(color));
+        else std::fill(out + (size_t)k * npx * 3, out + (size_t)(k + 1) * npx * 3, -1.0);
+    };
+    for (int k = 0; k < n_frames; k++) {
+        const double* c = cams6 + (size_t)k * 6;
+        cam.lookfrom = point3(c[0], c[1], c[2]); cam.lookat = point3(c[3], c[4], c[5]);
+        cam.seed = seed0 + (uint64_t)k;
+        if ((flags & 4) && k == n_frames - 1) cam.reset_temporal_history();
+        cam.reset_accumulator();
+        std::atomic<bool> flag{true};
+        cam.render(*bvh_world, h.s.env, post, flag);
+        if (cam.lines_rendered.load() != cam.image_height) return -1;
+        frame_out(cam.render_accumulator, acc, k); frame_out(cam.temporal_buffer, tmp, k); frame_out(cam.variance_buffer, var, k);
+        frame_out(cam.use_denoiser ? cam.denoise_buffer : std::vector<color>(), den, k);
+        if (hist) {
+            if (cam.temporal_history_length.size() == npx) std::memcpy(hist + (size_t)k * npx, cam.temporal_history_length.data(), npx * sizeof(int));
+            else std::fill(hist + (size_t)k * npx, hist + (size_t)(k + 1) * npx, -1);
+        }
+    }
+    return 0;
+}
+
 // The reference's per-ray virtual API through the drop-in classes: for n rays (o, d, tmin, tmax) calls
 // bvh_node(world).hit(r, interval(tmin, tmax), rec), then rec.mat->emitted(...) and rec.mat->scatter(r, rec, att, scattered)
 // with random_double() positioned on the stream (seed, pixel, k) — the layout of `zenith_ref kat <scene> hits`:
@@ -295,6 +335,7 @@ extern "C" size_t zrs_sizeof(int which) {
         case 16: return sizeof(zr_bvh_debug_hit);
         case 17: return sizeof(zr_tree_box);
         case 18: return sizeof(zr_denoise_guided_params);
+        case 19: return sizeof(zr_temporal_params);
         default: return 0;
     }
 }
