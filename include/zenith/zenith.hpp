@@ -1506,6 +1506,18 @@ public:
     bool denoise_variance_guided = false;
     std::vector<color> variance_buffer;   // extension: filled by a render with use_denoiser and denoise_variance_guided that had a variance; empty otherwise
     bool denoise_used_variance = false;   // extension: the last render's denoise_buffer came from the guided filter
+    // extension: with use_denoiser, denoise_buffer comes from the dual-buffer non-local-means filter (zr_denoise_nlm with nlm_params) on a frame
+    // that came through an accumulator with a variance (denoise_variance_guided's condition): the two half images of the accumulator filter each other.
+    // variance_buffer then holds zr_accum_variance and denoise_error_buffer the filter's estimate of the output's variance per channel.  With both this and
+    // denoise_variance_guided set, this one wins.  A temporally accumulated frame has no halves: with temporal_accumulation a warning is printed and the
+    // render is what it is without this flag.  Without a variance a warning is printed and the plain filter runs.  The reflection / refraction frames keep
+    // the plain filter.  false: exactly the render without it.
+    bool denoise_nlm = false;
+    zr_denoise_nlm_params nlm_params{ZR_DENOISE_NLM_DEFAULT_SEARCH_RADIUS, ZR_DENOISE_NLM_DEFAULT_PATCH_RADIUS, ZR_DENOISE_NLM_DEFAULT_DEMODULATE, 0,
+                                     ZR_DENOISE_NLM_DEFAULT_K, ZR_DENOISE_NLM_DEFAULT_ALPHA, ZR_DENOISE_NLM_DEFAULT_SIGMA_NORMAL,
+                                     ZR_DENOISE_NLM_DEFAULT_SIGMA_ALBEDO, ZR_DENOISE_NLM_DEFAULT_EPSILON};
+    bool denoise_used_nlm = false;              // extension: the last render's denoise_buffer came from the non-local-means filter
+    std::vector<color> denoise_error_buffer;    // extension: zr_denoise_nlm's out_error of the last render; empty when that filter did not run
     // extension: temporal accumulation across render() calls of this camera object (zr_accum_temporal with temporal_params).  A frame that came
     // through an accumulator with a variance (denoise_variance_guided's condition: adaptive_threshold > 0, or samples_per_pass > 0 with samples_per_pixel a
     // multiple of 64) is blended with the history of the frames before it, reprojected through the first hits of this camera's pixels: temporal_buffer holds
@@ -1596,6 +1608,7 @@ public:
                 const frame_job job{lease.ctx, sc.get(), to_zr(), zenv, render_flag, &world};
                 sample_counts.clear();
                 variance_buffer.clear(); denoise_used_variance = false;
+                half_a_.clear(); half_b_.clear(); denoise_error_buffer.clear(); denoise_used_nlm = false;
                 temporal_buffer.clear(); temporal_history_length.clear();
                 if (debug) rc = render_debug_view(job);
                 else if (wants_adaptive()) rc = render_adaptive(job);
@@ -1643,12 +1656,19 @@ private:
     }
     // the variance of the accumulator's pixel means, when the denoiser will ask for it (fetched before the accumulator is destroyed)
     int fetch_variance(zr_accum* acc) {
-        if (!(use_denoiser && denoise_variance_guided)) return ZR_OK;
+        if (!(use_denoiser && (denoise_variance_guided || wants_nlm()))) return ZR_OK;
         variance_buffer.assign(pixels(), color(0, 0, 0));
-        const int rc = zr_accum_variance(acc, zenith::doubles(variance_buffer));
+        int rc = zr_accum_variance(acc, zenith::doubles(variance_buffer));
         if (rc != ZR_OK) variance_buffer.clear();
+        if (rc == ZR_OK && wants_nlm()) {   // and the two half images
+            half_a_.assign(pixels(), color(0, 0, 0)); half_b_.assign(pixels(), color(0, 0, 0));
+            rc = zr_accum_halves(acc, zenith::doubles(half_a_), zenith::doubles(half_b_));
+            if (rc != ZR_OK) { half_a_.clear(); half_b_.clear(); }
+        }
         return rc;
     }
+    // the non-local-means filter has been asked for and can run: the blend of temporal_accumulation has no half images
+    bool wants_nlm() const { return denoise_nlm && !temporal_accumulation; }
 
     // the accumulator's frame into this camera's history (made anew when the frame size, the world object or the context differ from the history's)
     int accumulate_temporal(const frame_job& j, zr_accum* acc) {
@@ -1744,10 +1764,24 @@ private:
         // (a temporally accumulated frame: the guided filter takes it and its variance in place of the frame's own)
         denoise_buffer = denoise_variance_guided && temporal_buffer.size() == render_accumulator.size() ? temporal_buffer : render_accumulator;
         int rc;
-        if (denoise_variance_guided && variance_buffer.size() == render_accumulator.size()) {
+        if (denoise_nlm && temporal_accumulation) std::cerr << "[zenith] denoise_nlm ignored: a temporally accumulated frame has no half images\n";
+        if (wants_nlm() && half_a_.size() == render_accumulator.size() && variance_buffer.size() == render_accumulator.size()) {
+            denoise_buffer = half_a_;   // filtered in place
+            denoise_error_buffer.assign(pixels(), color(0, 0, 0));
+            double* p = zenith::doubles(denoise_buffer);
+            rc = on_leased_context([&](zr_ctx* ctx) {
+                return zr_denoise_nlm(ctx, &nlm_params, p, zenith::doubles(half_b_), zenith::doubles(variance_buffer), zenith::doubles(ga), zenith::doubles(gn),
+                                      image_width, image_height, p, zenith::doubles(denoise_error_buffer));
+            });
+            denoise_used_nlm = rc == ZR_OK;
+            if (rc != ZR_OK) denoise_error_buffer.clear();
+            half_a_.clear(); half_b_.clear();
+        } else if (denoise_variance_guided && variance_buffer.size() == render_accumulator.size()) {
             rc = denoise_guided(denoise_buffer, variance_buffer, ga, gn);
             denoise_used_variance = rc == ZR_OK;
         } else {
+            if (wants_nlm())
+                std::cerr << "[zenith] denoise_nlm ignored: no variance (it needs adaptive_threshold, or samples_per_pass with a multiple of 64 samples)\n";
             if (denoise_variance_guided)
                 std::cerr << "[zenith] denoise_variance_guided ignored: no variance (it needs adaptive_threshold, or samples_per_pass with a multiple of 64 samples)\n";
             rc = denoise(denoise_buffer, ga, gn);
@@ -1787,6 +1821,8 @@ private:
         });
     }
 
+    // the accumulator's half images between the render and the denoiser of one render() call (denoise_nlm)
+    std::vector<color> half_a_, half_b_;
     // the history of temporal_accumulation and what it was made for
     zenith::temporal_handle temporal_;
     zr_ctx* temporal_ctx_ = nullptr; const hittable* temporal_world_ = nullptr; int temporal_w_ = 0, temporal_h_ = 0;

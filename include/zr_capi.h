@@ -512,6 +512,60 @@ int zr_denoise_guided(zr_ctx*, const zr_denoise_guided_params*, const double* co
                       const double* normal, const double* zdepth, int width, int height, double* out, double* out_variance);
 int zr_accum_denoise(zr_accum*, const zr_denoise_guided_params*, const double* albedo, const double* normal, const double* zdepth,
                      double* out, double* out_variance);
+/* ---- dual-buffer non-local-means denoising: the two halves of an accumulator's samples filter each other ----
+ * Rousselle, Knaus, Zwicker, "Adaptive rendering with non-local means filtering" (SIGGRAPH Asia 2012): patch distances normalised by the
+ * per-pixel variance, a variance-cancellation term subtracted from every squared difference, and cross filtering — the weights computed
+ * from one half of the samples average the other half, so they are independent of the noise they average.
+ * zr_accum_halves     the two half images, W*H*3 doubles each, laid out like out_rgb; only the plan's pixels are written.  The resolve
+ *                     butterfly stopped one step early: per pixel with k = 64 m samples, per channel (FP64, no contraction), the xor butterfly
+ *                     32, 16, 8, 4, 2 over the lane sums leaves T_A (the even lanes) in lane 0 and T_B (the odd lanes) in lane 1;
+ *                       A = T_A * (1.0 / (k / 2));  B = T_B * (1.0 / (k / 2))
+ *                     For k a power of two (A + B) * 0.5 is the streaming resolve (T_A + T_B) * (1.0 / k) bit for bit.  zr_accum_variance's
+ *                     state rules.
+ * zr_denoise_nlm      half_a / half_b: the two half images; variance: of the FULL pixel mean (zr_accum_variance, or anything else).  Cleaning,
+ *                     normal decoding and the albedo divisor a' are zr_denoise's.  uA = clean(A) / a', uB = clean(B) / a',
+ *                     Vh = 2 max(clean(variance), 0) / (a' a') (a half has twice the variance of the whole), V^ = the 3 x 3 Gaussian of Vh per
+ *                     channel by zr_denoise_guided's stencil rules.  With clamp() moving a coordinate to the nearest frame pixel, for a buffer u,
+ *                     pixels s and t, channel c:
+ *                       delta_c = ((u_s - u_t)^2 - alpha (V^_s + min(V^_t, V^_s))) / (epsilon + k^2 (V^_s + V^_t))
+ *                       e(s, t) = ((delta_x + delta_y) + delta_z) * (1/3)
+ *                       e_D(s) = e(s, clamp(s + D));   D_D(p) = the mean of e_D(clamp(p + tau)) over tau in [-f, f]^2 (tau_y outer, tau_x inner)
+ *                       w_u(p, D) = exp(-max(D_D(p), 0)) w_a w_n for q = p + D inside the frame (no weight outside; w_a, w_n: zr_denoise's albedo
+ *                       and normal weights between p and q); the centre tap has weight 1
+ *                       fB_p = sum_D w_uA(p, D) uB_q / sum_D w_uA(p, D), fA_p likewise with the weights of uB on uA; D in [-r, r]^2, Dy outer, Dx inner
+ *                       out = ((fA + fB) * 0.5) * a';   out_error = (((fA - fB) * 0.5) * a')^2 per channel
+ *                     out_error is a one-degree-of-freedom estimate of the output's variance.  All frames W*H*3 doubles in host memory;
+ *                     out_error may be NULL, out may equal half_a.  ZR_E_INVALID, before any device call: parameters first (search_radius
+ *                     outside 0..10, patch_radius outside 0..3, k, a sigma or epsilon that is not positive and finite, alpha negative or not
+ *                     finite), then NULL and sizes as zr_denoise.  FP32, deterministic, independent of the kernel's tiling;
+ *                     tests/denoise_nlm_model.py restates it as evaluated (zr_nlm.hip's header).
+ * zr_accum_denoise_nlm  zr_denoise_nlm(zr_accum_halves(), zr_accum_variance(), ...) bit for bit, resolved on the device straight into the filter.
+ *                     Whole-frame accumulators only (ZR_E_INVALID otherwise); then zr_accum_variance's state rules.  out_error may be NULL. */
+typedef struct zr_denoise_nlm_params {
+    int32_t search_radius;              /* r: taps q = p + D, D in [-r, r]^2; 0..10 */
+    int32_t patch_radius;               /* f: patches of (2f+1)^2 pixels; 0..3 */
+    int32_t demodulate_albedo;          /* filter halves / albedo (and variance / albedo^2) */
+    int32_t pad_;
+    float k;                            /* > 0: distance scale (the paper's k) */
+    float alpha;                        /* >= 0: strength of the variance cancellation */
+    float sigma_normal, sigma_albedo;   /* as zr_denoise */
+    float epsilon;                      /* > 0, finite: added to the distance's denominator */
+} zr_denoise_nlm_params;
+/* defaults: the cheapest setting of scripts/dev/denoise_nlm_sweep.py within 2 % of the best worse-of-two-scenes factor on 64-spp accumulators
+ * of cfg5 and mix0 against 4096 spp; what camera::render uses with denoise_nlm.  The sweep began at r 5, f 1, k 0.45.  Demodulation is off
+ * here: dividing by the albedo lost on the textured scene at every setting — the patches already tell texture from noise. */
+#define ZR_DENOISE_NLM_DEFAULT_SEARCH_RADIUS 7
+#define ZR_DENOISE_NLM_DEFAULT_PATCH_RADIUS 1
+#define ZR_DENOISE_NLM_DEFAULT_DEMODULATE 0
+#define ZR_DENOISE_NLM_DEFAULT_K 0.7f
+#define ZR_DENOISE_NLM_DEFAULT_ALPHA 1.0f
+#define ZR_DENOISE_NLM_DEFAULT_SIGMA_NORMAL 64.0f
+#define ZR_DENOISE_NLM_DEFAULT_SIGMA_ALBEDO 0.25f
+#define ZR_DENOISE_NLM_DEFAULT_EPSILON 1e-10f
+int zr_accum_halves(zr_accum*, double* out_a, double* out_b);
+int zr_denoise_nlm(zr_ctx*, const zr_denoise_nlm_params*, const double* half_a, const double* half_b, const double* variance,
+                   const double* albedo, const double* normal, int width, int height, double* out, double* out_error);
+int zr_accum_denoise_nlm(zr_accum*, const zr_denoise_nlm_params*, const double* albedo, const double* normal, double* out, double* out_error);
 /* ---- temporal accumulation: a frame's history reprojected across a moving camera ------------------------------
  * The temporal stage of SVGF (Schied et al., HPG 2017, section 4.1) for a camera path through a STATIC world; the reference has no counterpart.
  * zr_render_gbuffer    the first hit of the ray through the centre of every pixel (get_center_ray, camera.hpp:809-814: origin `center`, direction

@@ -121,6 +121,22 @@ class DenoiseGuidedParams(C.Structure):
         return p
 
 
+class DenoiseNlmParams(C.Structure):
+    """zr_denoise_nlm_params: the dual-buffer non-local-means denoiser (include/zr_capi.h)"""
+    _fields_ = [("search_radius", C.c_int32), ("patch_radius", C.c_int32), ("demodulate_albedo", C.c_int32), ("pad_", C.c_int32), ("k", C.c_float),
+                ("alpha", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("epsilon", C.c_float)]
+
+    @classmethod
+    def defaults(cls, **kw):
+        """ZR_DENOISE_NLM_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with denoise_nlm)"""
+        p = cls(7, 1, 0, 0, 0.7, 1.0, 64.0, 0.25, 1e-10)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"DenoiseNlmParams has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
 class TemporalParams(C.Structure):
     """zr_temporal_params: how a frame's history is reprojected and blended (include/zr_capi.h)"""
     _fields_ = [("alpha", C.c_double), ("max_history", C.c_int32), ("pad_", C.c_int32), ("plane_tolerance", C.c_double), ("normal_cos", C.c_double)]
@@ -256,6 +272,7 @@ CAPI_SYMBOLS = [
     "zr_render_adaptive", "zr_accum_error", "zr_accum_sample_counts", "zr_accum_lane_sums",
     "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
     "zr_accum_variance", "zr_denoise_guided", "zr_accum_denoise",
+    "zr_accum_halves", "zr_denoise_nlm", "zr_accum_denoise_nlm",
     "zr_render_gbuffer", "zr_temporal_create", "zr_temporal_destroy", "zr_temporal_reset", "zr_temporal_state", "zr_temporal_accumulate", "zr_accum_temporal",
     "zr_temporal_view",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels",
@@ -317,6 +334,10 @@ def load():
     lib.zr_accum_variance.argtypes = [vp, vp]
     lib.zr_denoise_guided.argtypes = [vp, C.POINTER(DenoiseGuidedParams), vp, vp, vp, vp, vp, i32, i32, vp, vp]
     lib.zr_accum_denoise.argtypes = [vp, C.POINTER(DenoiseGuidedParams), vp, vp, vp, vp, vp]
+    if hasattr(lib, "zr_denoise_nlm"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
+        lib.zr_accum_halves.argtypes = [vp, vp, vp]
+        lib.zr_denoise_nlm.argtypes = [vp, C.POINTER(DenoiseNlmParams), vp, vp, vp, vp, vp, i32, i32, vp, vp]
+        lib.zr_accum_denoise_nlm.argtypes = [vp, C.POINTER(DenoiseNlmParams), vp, vp, vp, vp]
     if hasattr(lib, "zr_temporal_create"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
         lib.zr_render_gbuffer.argtypes = [vp, vp, C.POINTER(Camera), u64, vp, vp, vp, vp]
         lib.zr_temporal_create.restype = vp; lib.zr_temporal_create.argtypes = [vp, i32, i32]
@@ -375,6 +396,7 @@ def load_scenes():
     s.zrs_render_dropin_threads.argtypes = frame + [i32, vp]
     s.zrs_render_dropin_denoise.argtypes = frame + [i32] + [vp] * 6
     s.zrs_render_dropin_denoise_guided.argtypes = frame + [C.c_double, i32, i32] + [vp] * 4
+    s.zrs_render_dropin_denoise_nlm.argtypes = frame + [C.c_double, i32, i32] + [vp] * 5
     s.zrs_render_dropin_temporal.argtypes = frame + [i32, vp, i32, i32] + [vp] * 5
     s.zrs_render_dropin_bvh_debug.argtypes = frame + [i32, C.c_float, vp, vp]
     s.zrs_dropin_virtuals.argtypes = [vp, vp, i32, C.c_uint64, C.c_uint64, vp, vp]
@@ -477,6 +499,19 @@ class DemoScene:
         self._rendered(load_scenes().zrs_render_dropin_denoise_guided(self._h, width, height, spp, device, float(threshold), int(samples_per_pass),
                                                                       1 if guided else 0, *[o.ctypes.data for o in outs.values()], info) == 0)
         outs["guided"] = bool(info[0])
+        return outs
+
+    def render_dropin_denoise_nlm(self, threshold, samples_per_pass=0, nlm=True, guided=False, temporal=False, width=0, height=0, spp=0, device=0):
+        """camera::render with use_denoiser and (nlm) denoise_nlm, (guided) denoise_variance_guided, (temporal) temporal_accumulation; adaptively when
+        threshold > 0, progressively when samples_per_pass > 0, else in one shot: dict of render_accumulator, denoise_buffer, variance_buffer,
+        denoise_error_buffer ((H, W, 3) float64; all -1 when the render left the buffer empty), "nlm" (whether the non-local-means filter made
+        denoise_buffer) and "guided" (whether the guided filter did)"""
+        outs = self._frames(width, height, "render_accumulator", "denoise_buffer", "variance_buffer", "denoise_error_buffer")
+        info = (C.c_int * 3)()
+        flags = (1 if nlm else 0) | (2 if guided else 0) | (4 if temporal else 0)
+        self._rendered(load_scenes().zrs_render_dropin_denoise_nlm(self._h, width, height, spp, device, float(threshold), int(samples_per_pass), flags,
+                                                                   *[o.ctypes.data for o in outs.values()], info) == 0)
+        outs["nlm"] = bool(info[0]); outs["guided"] = bool(info[1])
         return outs
 
     def render_dropin_temporal(self, cameras, temporal=True, guided=False, samples_per_pass=0, reset_before_last=False, width=0, height=0, spp=0, device=0):
@@ -606,6 +641,25 @@ class Context:
                                           zdepth.ctypes.data if zdepth is not None else None, w, h, out.ctypes.data, out_variance.ctypes.data))
         return out, out_variance
 
+    def denoise_nlm(self, params, half_a, half_b, variance, albedo, normal, out=None, out_error=None):
+        """zr_denoise_nlm (dual-buffer non-local means: the weights of one half image filter the other): (H, W, 3) float64 frames -> (frame, error), both
+        (H, W, 3) float64; `variance` is the variance of the full pixel mean.  `out` may be `half_a` itself (in place)."""
+        half_a = np.ascontiguousarray(half_a, dtype=np.float64)
+        h, w = half_a.shape[:2]
+        frames = [np.ascontiguousarray(g, dtype=np.float64) for g in (half_b, variance, albedo, normal)]
+        for g in frames:
+            if g.shape != half_a.shape:
+                raise ValueError(f"frame shape {g.shape} differs from the first half's {half_a.shape}")
+        if out is None:
+            out = np.zeros_like(half_a)
+        if out_error is None:
+            out_error = np.zeros_like(half_a)
+        for o in (out, out_error):
+            assert o.dtype == np.float64 and o.flags.c_contiguous and o.shape == half_a.shape
+        _check(self.lib.zr_denoise_nlm(self._c, C.byref(params), half_a.ctypes.data, *[g.ctypes.data for g in frames], w, h, out.ctypes.data,
+                                       out_error.ctypes.data))
+        return out, out_error
+
     def sharpen(self, frame, amount, out=None):
         """post_processor::apply_sharpening on the device: (H, W, 3) float64 -> (H, W, 3) float64"""
         frame = np.ascontiguousarray(frame, dtype=np.float64)
@@ -710,6 +764,29 @@ class Accumulator:
         _check(self.lib.zr_accum_denoise(self._a, C.byref(params), guides[0].ctypes.data, guides[1].ctypes.data,
                                          zdepth.ctypes.data if zdepth is not None else None, out.ctypes.data, out_variance.ctypes.data))
         return out, out_variance
+
+    def halves(self, out_a=None, out_b=None):
+        """the two half images (zr_accum_halves: the means of the even and of the odd lanes' samples): two (H, W, 3) float64; only the region's pixels
+        are written"""
+        shape = (self.height, self.width, 3)
+        out_a = np.zeros(shape, dtype=np.float64) if out_a is None else out_a
+        out_b = np.zeros(shape, dtype=np.float64) if out_b is None else out_b
+        for o in (out_a, out_b):
+            assert o.dtype == np.float64 and o.flags.c_contiguous and o.shape == shape
+        _check(self.lib.zr_accum_halves(self._a, out_a.ctypes.data, out_b.ctypes.data))
+        return out_a, out_b
+
+    def denoise_nlm(self, params, albedo, normal):
+        """zr_accum_denoise_nlm: Context.denoise_nlm(params, *halves(), variance(), ...) bit for bit, with halves and variance resolved on the device;
+        returns (frame, error).  Whole-frame accumulators only."""
+        shape = (self.height, self.width, 3)
+        guides = [np.ascontiguousarray(g, dtype=np.float64) for g in (albedo, normal)]
+        for g in guides:
+            if g.shape != shape:
+                raise ValueError(f"guide shape {g.shape} differs from the accumulator's frame {shape}")
+        out = np.zeros(shape, dtype=np.float64); out_error = np.zeros(shape, dtype=np.float64)
+        _check(self.lib.zr_accum_denoise_nlm(self._a, C.byref(params), guides[0].ctypes.data, guides[1].ctypes.data, out.ctypes.data, out_error.ctypes.data))
+        return out, out_error
 
     def temporal(self, history, scene, camera, seed, params=None):
         """zr_accum_temporal: history.accumulate(scene, camera, seed, resolve(), variance(), params) bit for bit, with colour and variance resolved on

@@ -111,6 +111,10 @@ int accum_variance_into(const AccumState& a, double* d_out, hipStream_t stream) 
     HIP_OK(zr::launch_accum_variance(a.d_partial.p, a.d_pixels.p, a.adaptive ? a.d_count.p : nullptr, a.done, a.n_pix, a.plan.W, d_out, stream));
     return ZR_OK;
 }
+int accum_halves_into(const AccumState& a, double* d_out_a, double* d_out_b, hipStream_t stream) {
+    HIP_OK(zr::launch_accum_halves(a.d_partial.p, a.d_pixels.p, a.adaptive ? a.d_count.p : nullptr, a.done, a.n_pix, a.plan.W, d_out_a, d_out_b, stream));
+    return ZR_OK;
+}
 
 // One render made of several runs (render_batched's batches, an adaptive run's passes) as zr_get_counters sees it: counters and rounds summed, one render's launch times
 struct RunTotals {
@@ -291,6 +295,19 @@ int zr_accum_variance(zr_accum* a, double* out_var) {
     return rc ? rc : query_frame(a->st, accum_variance_into, out_var);
 }
 
+int zr_accum_halves(zr_accum* a, double* out_a, double* out_b) {
+    if (!a || !out_a || !out_b) return fail(ZR_E_INVALID, "null argument");
+    const AccumState& st = a->st;
+    int rc = variance_ready(st, "zr_accum_halves");
+    if (rc) return rc;
+    HIP_OK(hipSetDevice(st.device));
+    DevBuf<double> d_a, d_b;
+    if ((rc = d_a.alloc(st.plan.npx() * 3)) || (rc = d_b.alloc(st.plan.npx() * 3)) || (rc = accum_halves_into(st, d_a.p, d_b.p, nullptr))) return rc;
+    HIP_OK(hipStreamSynchronize(nullptr));
+    std::vector<double> staging;   // only the plan's pixels are copied out
+    return (rc = copy_region(st.plan, d_a.p, out_a, staging)) ? rc : copy_region(st.plan, d_b.p, out_b, staging);
+}
+
 int zr_accum_state(const zr_accum* a, int64_t out[4]) {
     if (!a || !out) return fail(ZR_E_INVALID, "null argument");
     out[0] = a->st.first; out[1] = a->st.done; out[2] = (int64_t)a->st.n_pix; out[3] = (int64_t)a->st.device_bytes();
@@ -441,6 +458,24 @@ int zr_accum_denoise(zr_accum* a, const zr_denoise_guided_params* dp, const doub
     // a whole-frame plan: the two kernels write every pixel of the two frames
     if ((rc = accum_resolve_into(st, d_c.p, c->stream)) || (rc = accum_variance_into(st, d_v.p, c->stream))) return rc;
     return denoise_guided_device(c, dp, d_c, d_v, albedo, normal, zdepth, st.plan.W, st.plan.H, out, out_variance);
+}
+
+// non-local-means denoising of what an accumulator holds (the filter itself: zr_image.cpp)
+int zr_accum_denoise_nlm(zr_accum* a, const zr_denoise_nlm_params* dp, const double* albedo, const double* normal, double* out, double* out_error) {
+    if (!dp) return fail(ZR_E_INVALID, "null argument");
+    int rc = check_nlm_params(dp);   // the parameters first: they need no device and no other argument
+    if (rc) return rc;
+    if (!a || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
+    AccumState& st = a->st;
+    if (!st.plan.whole()) return fail(ZR_E_INVALID, "zr_accum_denoise_nlm filters whole frames: the accumulator was made with a region");
+    if ((rc = variance_ready(st, "zr_accum_denoise_nlm"))) return rc;
+    zr_ctx* c = st.ctx;
+    HIP_OK(hipSetDevice(st.device));
+    DevBuf<double> d_a, d_b, d_v;
+    if ((rc = d_a.alloc(st.plan.npx() * 3)) || (rc = d_b.alloc(st.plan.npx() * 3)) || (rc = d_v.alloc(st.plan.npx() * 3))) return rc;
+    // a whole-frame plan: the two kernels write every pixel of the three frames
+    if ((rc = accum_halves_into(st, d_a.p, d_b.p, c->stream)) || (rc = accum_variance_into(st, d_v.p, c->stream))) return rc;
+    return denoise_nlm_device(c, dp, d_a, d_b, d_v, albedo, normal, st.plan.W, st.plan.H, out, out_error);
 }
 
 // what an accumulator holds taken into a history (the reprojection itself: zr_temporal.cpp)

@@ -1,6 +1,7 @@
 // zr_adaptive.hip — adaptive sampling over a zr_accum: the noise estimate of a pixel from its 64 lane sums, the pass kernel that adds a pass's
 // samples to the still-active pixels and decides which of them go on, the stable compaction of the active list, the resolve with a sample count per pixel, and
-// the per-channel variance of a pixel's mean that the variance-guided denoiser reads (tests/denoise_guided_model.py restates it).
+// the per-channel variance of a pixel's mean that the variance-guided denoiser reads (tests/denoise_guided_model.py restates it) and the two half
+// images that the non-local-means denoiser cross-filters (tests/denoise_nlm_model.py).
 // Compiled without contraction (csrc/Makefile): tests/adaptive_model.py restates the estimate operation for operation, and the decisions of an adaptive run
 // are exactly `err > threshold` on those numbers.  No atomics: the next pass's pixel list depends on the flags alone, never on the order waves ran in.
 #include <hip/hip_runtime.h>
@@ -98,6 +99,25 @@ __global__ __launch_bounds__(256) void accum_variance(const double* __restrict__
         const uint32_t pk = pixels[i];
         double* o = out + ((size_t)(pk >> 16) * W + (pk & 0xFFFFu)) * 3;
         o[0] = var[0]; o[1] = var[1]; o[2] = var[2];
+    }
+}
+
+// The two half images of every slot (zr_accum_halves), into the slot's pixel of two frames W wide: the resolve butterfly stopped one step early.
+// After the steps 32, 16, 8, 4, 2 lane 0 holds T_A, the sum of the even lanes, and lane 1 T_B, the sum of the odd lanes; with `count` = 64 m samples each half
+// holds count / 2 of them: A = T_A * (1.0 / (count / 2)), B = T_B * (1.0 / (count / 2)).  The step the resolve goes on with is T_A + T_B.  count: as above.
+__global__ __launch_bounds__(256) void accum_halves(const double* __restrict__ partial, const uint32_t* __restrict__ pixels, const int32_t* __restrict__ count,
+                                                     int uniform_count, uint32_t n_pix, int W, double* __restrict__ out_a, double* __restrict__ out_b) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i >= n_pix) return;   // (a whole wave: the butterflies below see all 64 lanes)
+    const double* q = partial + (size_t)i * 192 + lane;
+    double sx = q[0], sy = q[64], sz = q[128];
+    for (int m = 32; m >= 2; m >>= 1) { sx += xor_lane(sx, m); sy += xor_lane(sy, m); sz += xor_lane(sz, m); }
+    if (lane < 2) {
+        const uint32_t pk = pixels[i];
+        const double scale = 1.0 / (double)((count ? count[i] : uniform_count) / 2);
+        double* o = (lane == 0 ? out_a : out_b) + ((size_t)(pk >> 16) * W + (pk & 0xFFFFu)) * 3;
+        o[0] = sx * scale; o[1] = sy * scale; o[2] = sz * scale;
     }
 }
 
@@ -209,6 +229,13 @@ hipError_t launch_accum_variance(const double* partial, const uint32_t* pixels, 
                                  hipStream_t stream) {
     if (n_pix == 0) return hipSuccess;
     hipLaunchKernelGGL(accum_variance, dim3((n_pix + 3) / 4), dim3(256), 0, stream, partial, pixels, count, uniform_count, n_pix, W, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_accum_halves(const double* partial, const uint32_t* pixels, const int32_t* count, int uniform_count, uint32_t n_pix, int W, double* out_a,
+                               double* out_b, hipStream_t stream) {
+    if (n_pix == 0) return hipSuccess;
+    hipLaunchKernelGGL(accum_halves, dim3((n_pix + 3) / 4), dim3(256), 0, stream, partial, pixels, count, uniform_count, n_pix, W, out_a, out_b);
     return hipGetLastError();
 }
 

@@ -77,6 +77,10 @@ int render_batched(zr_ctx* c, const zr_scene* s, const FrameJob& frame, int n_ma
 int denoise_guided_device(zr_ctx* c, const zr_denoise_guided_params* dp, DevBuf<double>& d_c, DevBuf<double>& d_v, const double* albedo, const double* normal,
                           const double* zdepth, int W, int H, double* out, double* out_variance);
 int check_guided_params(const zr_denoise_guided_params* dp);
+// likewise for the non-local-means filter: d_a / d_b hold the two halves and receive out / out_error, d_v holds the variance of the full mean
+int denoise_nlm_device(zr_ctx* c, const zr_denoise_nlm_params* dp, DevBuf<double>& d_a, DevBuf<double>& d_b, DevBuf<double>& d_v, const double* albedo,
+                       const double* normal, int W, int H, double* out, double* out_error);
+int check_nlm_params(const zr_denoise_nlm_params* dp);
 // zr_render.cpp, for zr_temporal.cpp: camera::initialize's frame, and zr_trace's body for rays that are on the device already
 void camera_frame(const zr_camera& cam, zr::DCamera& dc);
 int trace_device(zr_ctx* c, const zr_scene* s, const double* d_rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel, uint32_t bounce,

@@ -1,5 +1,5 @@
 // zr_image.cpp — the image-space entry points of the C ABI (include/zr_capi.h), which need a context and no scene: the post stack, the two a-trous denoisers
-// (the variance-guided one, also behind zr_accum_denoise), sharpening and the frame analysis.
+// (the variance-guided one, also behind zr_accum_denoise), the non-local-means denoiser (also behind zr_accum_denoise_nlm), sharpening and the frame analysis.
 #include "zr_frame.h"
 
 namespace zr_host {
@@ -45,6 +45,34 @@ int denoise_guided_device(zr_ctx* c, const zr_denoise_guided_params* dp, DevBuf<
                                      out_variance ? d_v.p : nullptr, c->stream));
     HIP_OK(hipMemcpyAsync(out, d_c.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (out_variance) HIP_OK(hipMemcpyAsync(out_variance, d_v.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return ZR_OK;
+}
+
+// the checks of a zr_denoise_nlm_params, which need no device
+int check_nlm_params(const zr_denoise_nlm_params* dp) {
+    if (dp->search_radius < 0 || dp->search_radius > 10) return fail(ZR_E_INVALID, "denoise search radius %d outside 0..10", dp->search_radius);
+    if (dp->patch_radius < 0 || dp->patch_radius > 3) return fail(ZR_E_INVALID, "denoise patch radius %d outside 0..3", dp->patch_radius);
+    auto positive = [](float v) { return v > 0.0f && std::isfinite(v); };
+    if (!positive(dp->k)) return fail(ZR_E_INVALID, "denoise distance scale k %g is not positive and finite", (double)dp->k);
+    if (!(dp->alpha >= 0.0f) || !std::isfinite(dp->alpha)) return fail(ZR_E_INVALID, "denoise variance cancellation alpha %g is negative or not finite", (double)dp->alpha);
+    if (!positive(dp->sigma_normal) || !positive(dp->sigma_albedo)) return fail(ZR_E_INVALID, "denoise sigmas must be positive and finite");
+    if (!positive(dp->epsilon)) return fail(ZR_E_INVALID, "denoise epsilon %g is not positive and finite", (double)dp->epsilon);
+    return ZR_OK;
+}
+
+// The non-local-means filter on device frames of n = W * H pixels: d_a / d_b hold the halves and receive out / out_error; the guides are uploaded from the host.
+int denoise_nlm_device(zr_ctx* c, const zr_denoise_nlm_params* dp, DevBuf<double>& d_a, DevBuf<double>& d_b, DevBuf<double>& d_v, const double* albedo,
+                       const double* normal, int W, int H, double* out, double* out_error) {
+    const size_t n = (size_t)W * H;
+    DevBuf<double> d_al, d_n, d_z; DevBuf<float4> ua, ub, vh, vs, g0, g1;
+    int rc;
+    if ((rc = upload_guides(c, albedo, normal, nullptr, n, d_al, d_n, d_z))) return rc;
+    if ((rc = ua.alloc(n)) || (rc = ub.alloc(n)) || (rc = vh.alloc(n)) || (rc = vs.alloc(n)) || (rc = g0.alloc(n)) || (rc = g1.alloc(n))) return rc;
+    // the halves have been packed before the filter kernel overwrites them
+    HIP_OK(zr::launch_denoise_nlm(d_a.p, d_b.p, d_v.p, d_al.p, d_n.p, W, H, *dp, ua.p, ub.p, vh.p, vs.p, g0.p, g1.p, d_a.p, out_error ? d_b.p : nullptr, c->stream));
+    HIP_OK(hipMemcpyAsync(out, d_a.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (out_error) HIP_OK(hipMemcpyAsync(out_error, d_b.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     return ZR_OK;
 }
@@ -107,6 +135,23 @@ int zr_denoise_guided(zr_ctx* c, const zr_denoise_guided_params* dp, const doubl
     HIP_OK(hipMemcpyAsync(d_c.p, color, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_OK(hipMemcpyAsync(d_v.p, variance, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return denoise_guided_device(c, dp, d_c, d_v, albedo, normal, zdepth, W, H, out, out_variance);
+}
+
+int zr_denoise_nlm(zr_ctx* c, const zr_denoise_nlm_params* dp, const double* half_a, const double* half_b, const double* variance, const double* albedo,
+                   const double* normal, int W, int H, double* out, double* out_error) {
+    if (!dp) return fail(ZR_E_INVALID, "null argument");
+    int rc = check_nlm_params(dp);   // the parameters first: they need no device and no other argument
+    if (rc) return rc;
+    if (!c || !half_a || !half_b || !variance || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
+    if ((rc = check_frame_size(W, H, 1))) return rc;
+    HIP_OK(hipSetDevice(c->device));
+    const size_t n = (size_t)W * H;
+    DevBuf<double> d_a, d_b, d_v;
+    if ((rc = d_a.alloc(n * 3)) || (rc = d_b.alloc(n * 3)) || (rc = d_v.alloc(n * 3))) return rc;
+    HIP_OK(hipMemcpyAsync(d_a.p, half_a, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d_b.p, half_b, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d_v.p, variance, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return denoise_nlm_device(c, dp, d_a, d_b, d_v, albedo, normal, W, H, out, out_error);
 }
 
 int zr_sharpen_frame(zr_ctx* c, const double* in, int W, int H, double amount, double* out) {

@@ -130,6 +130,9 @@ hipError_t launch_accum_resolve_counts(const double* partial, const uint32_t* pi
 // the per-channel variance of every slot's mean into the listed pixels of `out` (frame width W, 3 doubles a pixel; count as launch_accum_error's)
 hipError_t launch_accum_variance(const double* partial, const uint32_t* pixels, const int32_t* count, int uniform_count, uint32_t n_pix, int W, double* out,
                                  hipStream_t stream);
+// the two half images of every slot (the even lanes' mean, the odd lanes' mean) into the listed pixels of out_a / out_b (as launch_accum_variance)
+hipError_t launch_accum_halves(const double* partial, const uint32_t* pixels, const int32_t* count, int uniform_count, uint32_t n_pix, int W, double* out_a,
+                               double* out_b, hipStream_t stream);
 // The sky pre-pass (zr_sky.hip): of the n_pix listed pixels, those whose every camera ray of the samples [sample0, sample0 + spp) provably sees only the
 // environment get their mean written to `out` (stream_reduce's value, bit for bit); the others go, in list order, to walk[0 .. *n_walk).  Device scratch:
 // flag and walk n_pix words, block_count ceil(n_pix / 256) words, n_walk one word.
@@ -154,6 +157,11 @@ hipError_t launch_denoise(const double* d_color, const double* d_albedo, const d
 hipError_t launch_denoise_guided(const double* d_color, const double* d_variance, const double* d_albedo, const double* d_normal, const double* d_zdepth, int W,
                                  int H, const zr_denoise_guided_params& dp, float4* d_col0, float4* d_col1, float4* d_var0, float4* d_var1, float4* d_g0,
                                  float4* d_g1, double* d_out, double* d_out_var, hipStream_t stream);
+// the dual-buffer non-local-means filter (zr_nlm.hip): halves, variance and guides W*H*3 doubles; d_ua .. d_g1 W*H float4 scratch; d_out may be
+// d_half_a, d_out_error may be null or d_half_b
+hipError_t launch_denoise_nlm(const double* d_half_a, const double* d_half_b, const double* d_variance, const double* d_albedo, const double* d_normal, int W, int H,
+                              const zr_denoise_nlm_params& dp, float4* d_ua, float4* d_ub, float4* d_vh, float4* d_vs, float4* d_g0, float4* d_g1, double* d_out,
+                              double* d_out_error, hipStream_t stream);
 // Temporal accumulation (zr_temporal.hip).  A view is a camera as the reprojection needs it: centre, the first pixel's centre, the unit backward
 // axis w, the inverse of the pixel grid (a = du / (du . du), b = dv / (dv . dv): exact because du is perpendicular to dv) and the focus distance.
 struct TemporalView { double center[3], pixel00[3], w[3], a[3], b[3], f; };

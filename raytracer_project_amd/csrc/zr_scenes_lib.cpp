@@ -225,6 +225,32 @@ int zrs_render_dropin_denoise_guided(void* p, int width, int height, int spp, in
     return 0;
 }
 
+// camera::render with use_denoiser and the extension flags 1 = denoise_nlm, 2 = denoise_variance_guided, 4 = temporal_accumulation through the drop-in API:
+// adaptively when threshold > 0 (min = step = 64), progressively when samples_per_pass > 0, else in one shot.  Outputs (W*H*3 doubles each, any may be null):
+// render_accumulator, denoise_buffer, variance_buffer, denoise_error_buffer (all -1 when the render left it empty); info (may be null): denoise_used_nlm,
+// denoise_used_variance, current_samples_count.  Returns 0, or -1 if the render did not finish.
+int zrs_render_dropin_denoise_nlm(void* p, int width, int height, int spp, int device, double threshold, int samples_per_pass, int flags, double* acc,
+                                  double* den, double* var, double* err, int* info) {
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
+    cam.use_denoiser = true;
+    cam.denoise_nlm = (flags & 1) != 0;
+    cam.denoise_variance_guided = (flags & 2) != 0;
+    cam.temporal_accumulation = (flags & 4) != 0;
+    cam.adaptive_threshold = threshold;
+    cam.samples_per_pass = samples_per_pass;
+    cam.reset_accumulator();
+    if (!render_world(h, cam, post_processor())) return -1;
+    const size_t n = cam.render_accumulator.size();
+    copy_out(cam.render_accumulator, acc); copy_out(cam.denoise_buffer, den);
+    if (cam.variance_buffer.size() == n) copy_out(cam.variance_buffer, var);
+    else if (var) std::fill(var, var + n * 3, -1.0);
+    if (cam.denoise_error_buffer.size() == n) copy_out(cam.denoise_error_buffer, err);
+    else if (err) std::fill(err, err + n * 3, -1.0);
+    if (info) { info[0] = cam.denoise_used_nlm ? 1 : 0; info[1] = cam.denoise_used_variance ? 1 : 0; info[2] = cam.current_samples_count; }
+    return 0;
+}
+
 // A camera path through ONE camera object and one world object (camera::temporal_accumulation keeps its history across render() calls of the object): n_frames
 // renders with lookfrom / lookat = cams6[k] (6 doubles a frame) and seed = the scene's + k.  flags: 1 = temporal_accumulation, 2 = use_denoiser with
 // denoise_variance_guided, 4 = reset_temporal_history() before the last frame.  samples_per_pass > 0 renders progressively, else in one shot.  Outputs, n_frames frames
@@ -336,6 +362,7 @@ extern "C" size_t zrs_sizeof(int which) {
         case 17: return sizeof(zr_tree_box);
         case 18: return sizeof(zr_denoise_guided_params);
         case 19: return sizeof(zr_temporal_params);
+        case 20: return sizeof(zr_denoise_nlm_params);
         default: return 0;
     }
 }
