@@ -704,6 +704,11 @@ int zr_get_counters(zr_ctx*, zr_counters*);
 /* pixels the last render on this context finished in the sky pre-pass (every camera ray of the pixel provably sees only the environment, so the pixel never
  * entered the streaming pipeline; ZR_SKY_PREPASS=0 switches the pre-pass off); 0 for a render that took any other path, the counting render among them */
 uint64_t zr_last_presolved_pixels(zr_ctx*);
+/* the round loop of the last render that went through the streaming pipeline: *drain_round = the loop round after which the paths still alive were moved to the
+ * small drain pool (0: they never were), *sub_pools = the sub-pools the frame began with (0: the render took another path).  Either pointer may be null.  With
+ * zr_counters::rounds = R and no drain, the launch log holds (sub_pools - 1) + sub_pools * (R - [sub_pools > 1]) EXTEND launches for the frame; rounds after
+ * drain_round contribute one each.  ZR_STREAM_POLL_LAG (default 1; 0: the host drains the streams at every poll) says how many rounds old the host's knowledge is. */
+int zr_last_round_loop(zr_ctx*, int* drain_round, int* sub_pools);
 /* drains the log of render-kernel launch durations (ms, measured with HIP events on the launch stream) recorded
  * since the previous call: copies the newest min(cap, n) of them, oldest first, and returns n */
 int zr_get_kernel_times(zr_ctx*, float* ms, int cap);

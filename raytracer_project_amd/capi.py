@@ -275,7 +275,7 @@ CAPI_SYMBOLS = [
     "zr_accum_halves", "zr_denoise_nlm", "zr_accum_denoise_nlm",
     "zr_render_gbuffer", "zr_temporal_create", "zr_temporal_destroy", "zr_temporal_reset", "zr_temporal_state", "zr_temporal_accumulate", "zr_accum_temporal",
     "zr_temporal_view",
-    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels",
+    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_shade_lean", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
 
@@ -355,6 +355,8 @@ def load():
     lib.zr_get_counters.argtypes = [vp, C.POINTER(Counters)]
     if hasattr(lib, "zr_last_presolved_pixels"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
         lib.zr_last_presolved_pixels.argtypes = [vp]; lib.zr_last_presolved_pixels.restype = u64
+    if hasattr(lib, "zr_last_round_loop"):   # (likewise)
+        lib.zr_last_round_loop.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.zr_get_kernel_times.argtypes = [vp, C.POINTER(C.c_float), i32]
     lib.zr_trace.argtypes = [vp, vp, vp, C.c_size_t, C.c_double, C.c_double, u64, u64, C.c_uint32, vp]
     lib.zr_kat_scatter.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
@@ -685,6 +687,12 @@ class Context:
     def presolved_pixels(self):
         """pixels the last render finished in the sky pre-pass (zr_last_presolved_pixels); 0 for every other path"""
         return int(self.lib.zr_last_presolved_pixels(self._c))
+
+    def round_loop(self):
+        """(drain_round, sub_pools) of the last pipeline render (zr_last_round_loop)"""
+        d, k = C.c_int(0), C.c_int(0)
+        _check(self.lib.zr_last_round_loop(self._c, C.byref(d), C.byref(k)))
+        return d.value, k.value
 
     def kernel_times_ms(self, cap=256):
         buf = (C.c_float * cap)()

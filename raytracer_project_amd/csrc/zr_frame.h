@@ -58,6 +58,11 @@ struct HostTimer : zr::StreamTimer {
         c->pending.push_back(pe);
         cur_a = nullptr;
     }
+    size_t logged() override { return c->pending.size(); }
+    void drop_from(size_t n) override {
+        for (size_t i = n; i < c->pending.size(); i++) { c->pool.push_back(c->pending[i].a); c->pool.push_back(c->pending[i].b); }
+        if (n < c->pending.size()) c->pending.resize(n);
+    }
     int status() const { return err == hipSuccess ? ZR_OK : fail(ZR_E_DEVICE, "hipEventCreate(&e) failed: %s", hipGetErrorString(err)); }
 };
 

@@ -60,7 +60,10 @@ zr_ctx* zr_create(int device_ordinal) {
         if (env_double("ZR_STREAM_OVERLAP", -1) == 0) c->st_pools = 1;
         if (c->d_ctl.alloc((ST_MAX_POOLS + 1) * zr::stream_ctl_words()) != ZR_OK ||
             hipEventCreateWithFlags(&c->st_event, hipEventDisableTiming) != hipSuccess ||
-            hipHostMalloc((void**)&c->h_active, (ST_MAX_POOLS + 1) * zr::stream_ctl_words() * sizeof(unsigned int), 0) != hipSuccess) { fail(ZR_E_DEVICE, "variant-2 buffers: out of memory"); delete c; return nullptr; }
+            hipHostMalloc((void**)&c->h_active, (ST_MAX_POOLS + 1) * zr::stream_ctl_words() * sizeof(unsigned int), 0) != hipSuccess ||
+            hipHostMalloc((void**)&c->h_polls, (size_t)zr::POLL_RING * ST_MAX_POOLS * zr::POLL_WORDS * sizeof(unsigned int), 0) != hipSuccess) { fail(ZR_E_DEVICE, "variant-2 buffers: out of memory"); delete c; return nullptr; }
+        for (hipEvent_t& e : c->poll_events)   // the round loop waits on these and never times them
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { fail(ZR_E_DEVICE, "variant-2 buffers: no event for the round loop's polls"); delete c; return nullptr; }
     }
     return c;
 }
@@ -75,6 +78,8 @@ void zr_destroy(zr_ctx* c) {
     c->d_ctr.release(); c->d_out.release(); c->d_tiles.release();
     c->d_pool.release(); c->d_pixels.release(); c->d_partial.release(); c->d_kend.release(); c->d_cls.release(); c->d_cpart.release(); c->d_ctl.release(); c->d_st_overflow.release();
     if (c->h_active) (void)hipHostFree(c->h_active);
+    if (c->h_polls) (void)hipHostFree(c->h_polls);
+    for (hipEvent_t e : c->poll_events) if (e) (void)hipEventDestroy(e);
     if (c->st_event) (void)hipEventDestroy(c->st_event);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     for (int k = 1; k < ST_MAX_POOLS; k++) if (c->sub[k]) (void)hipStreamDestroy(c->sub[k]);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/zr_capi.h"
+#include "zr_round_polls.h"
 
 #define ZR_BLOCK 256
 
@@ -43,6 +44,8 @@ hipError_t launch_render(const DScene& sc, const DCamera& cam, const DEnv& env, 
 struct StreamTimer {  // host-provided HIP-event recorder; kind: 0 init, 1 extend, 2 shade, 3 reduce
     virtual void begin(hipStream_t, int kind) = 0;
     virtual void end(hipStream_t, int kind) = 0;
+    virtual size_t logged() { return 0; }      // launches recorded so far
+    virtual void drop_from(size_t) {}          // forget the launches recorded after the first `logged()` ones (the rounds queued behind the one that emptied the pools)
     virtual ~StreamTimer() = default;
 };
 // host-provided progress sink of the round loop (camera::lines_rendered and the live preview of camera.hpp:548-552 / main.cpp:1576):
@@ -76,15 +79,19 @@ struct StreamFrame {     // what is rendered: one work unit per primary sample o
 struct StreamPool {      // the frame's slot pool; the small pool the survivors of its drain are moved to (null: not used); chunk of the XCD-affine hand-out (0: striped)
     void* slots; uint32_t P; void* drain; uint32_t drain_slots, unit_chunk;
 };
-struct StreamContext {   // what the context owns (zr_ctx): control block, EXTEND's spill slabs and persistent grid, counter block (CTR_*), streams, pinned copy of ctl
+struct StreamContext {   // what the context owns (zr_ctx): control block, EXTEND's spill slabs and persistent grid, counter block (CTR_*), streams, pinned copy of ctl, poll ring
     unsigned int* ctl; void* overflow; uint32_t ovf_levels; int extend_blocks; unsigned long long* gctr;
     hipStream_t* streams; int n_pools;   // streams[0] is the caller's stream, the others are internal; n_pools: sub-pools wanted
     hipEvent_t event; unsigned int* h_active;
+    // the round loop's polls (zr_round_polls.h): pinned [POLL_RING][ST_MAX_POOLS][POLL_WORDS] words that the device writes, and one event (no timing) per sub-pool and
+    // ring slot, [POLL_RING][ST_MAX_POOLS].  stream_trace does not poll: null there
+    unsigned int* h_polls = nullptr; hipEvent_t* poll_events = nullptr;
 };
 struct StreamSplit { int mode; void* kend; void* cls; unsigned long long* cpart; };   // mode 0: the render; 1 / 2: the passes of the reflection / refraction split, with their buffers
 struct StreamHooks {     // the host's view into the loop
     StreamTimer* timer; volatile const uint8_t* keep_going /* host memory, polled between rounds: 0 cancels */; StreamProgress* progress;
-    int* done_out;       // rounds run (stream_render) or parts launched (fused_render_frame); negative: cancelled after that many
+    int* done_out;       // rounds run (stream_render: up to and including the one that emptied the pools) or parts launched (fused_render_frame); negative: cancelled after that many
+    int* drain_out = nullptr;   // stream_render: the round after which the survivors moved to the drain pool (0: they never did); [1]: the sub-pools the frame began with
 };
 struct StreamJob { StreamFrame frame; StreamPool pool; StreamContext ctx; StreamSplit split; StreamHooks hooks; };
 // leaf_level: the EXTEND build the scene needs (zr_scene::leaf_level)
@@ -135,7 +142,7 @@ hipError_t launch_accum_halves(const double* partial, const uint32_t* pixels, co
                                double* out_b, hipStream_t stream);
 // The sky pre-pass (zr_sky.hip): of the n_pix listed pixels, those whose every camera ray of the samples [sample0, sample0 + spp) provably sees only the
 // environment get their mean written to `out` (stream_reduce's value, bit for bit); the others go, in list order, to walk[0 .. *n_walk).  Device scratch:
-// flag and walk n_pix words, block_count ceil(n_pix / 256) words, n_walk one word.
+// flag and walk n_pix words, block_count ceil(n_pix / 256) words, n_walk one word.  ZR_SKY_SIEVE=1 puts a one-ray sieve in front (same flags, frame and list).
 hipError_t launch_sky_prepass(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const uint32_t* pixels, uint32_t n_pix, uint32_t spp,
                               uint32_t sample0, double* out, uint32_t* flag, uint32_t* block_count, uint32_t* walk, uint32_t* n_walk, hipStream_t stream);
 // closest hits of n rays in [0.001, inf) through the EXTEND kernel on ctx.streams[0]; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes

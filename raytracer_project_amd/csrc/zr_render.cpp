@@ -442,7 +442,7 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode) {
     uint32_t n_pix = job.d_list ? job.n_list : (uint32_t)c->d_pixels.n;
     const uint32_t spp = (uint32_t)job.dc.spp;
     if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
-    c->render_id++; c->last_stream = job.stream; c->last_counted = job.count; c->last_rounds = 0;
+    c->render_id++; c->last_stream = job.stream; c->last_counted = job.count; c->last_rounds = 0; c->last_drain_round = 0; c->last_sub_pools = 0;
     HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
     if (n_pix == 0) return ZR_OK;
     uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
@@ -468,7 +468,7 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode) {
     }
     zr::StreamJob sj{};
     sj.frame = zr::StreamFrame{&job.dc, &job.de, job.seed, spp, n_pix, pixels, c->d_partial.p, job.d_out, job.d_out2, job.count, job.sample0};
-    sj.ctx = zr::StreamContext{c->d_ctl.p, nullptr, 0, c->st_blocks, c->d_ctr.p, streams, 1, c->st_event, c->h_active};
+    sj.ctx = zr::StreamContext{c->d_ctl.p, nullptr, 0, c->st_blocks, c->d_ctr.p, streams, 1, c->st_event, c->h_active, c->h_polls, c->poll_events};
     sj.hooks = zr::StreamHooks{nullptr, job.keep_going, job.progress, nullptr};
     const bool polled = job.keep_going || job.progress;   // a cancelled frame / a preview reduces what exists: the samples start at zero
     if (fused) {
@@ -490,11 +490,11 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode) {
     const bool sharded = job.plan.tiles.size() < (size_t)job.plan.tiles_x * job.plan.tiles_y;
     sj.ctx.n_pools = c->st_pools > 0 ? c->st_pools : ((sharded || lean_pair) ? 2 : 1);
     HostTimer timer(c);
-    int rounds = 0;
-    sj.hooks.timer = &timer; sj.hooks.done_out = &rounds;
+    int rounds = 0, drain[2] = {0, 0};
+    sj.hooks.timer = &timer; sj.hooks.done_out = &rounds; sj.hooks.drain_out = drain;
     hipError_t e = zr::stream_render(s->ds, sj, s->leaf_level);
     if (e != hipSuccess) return fail(ZR_E_DEVICE, "streaming pipeline failed: %s", hipGetErrorString(e));
-    c->last_rounds = (uint64_t)(rounds < 0 ? -rounds : rounds);
+    c->last_rounds = (uint64_t)(rounds < 0 ? -rounds : rounds); c->last_drain_round = drain[0]; c->last_sub_pools = drain[1];
     HIP_OK(hipStreamSynchronize(job.stream));
     if (rounds < 0) return fail(ZR_E_CANCELLED, "render cancelled after %d rounds", -rounds);
     return ZR_OK;
@@ -739,6 +739,13 @@ int zr_get_counters(zr_ctx* c, zr_counters* out) {
             std::fprintf(stderr, "   of %llu\n", tot);
         }
     }
+    return ZR_OK;
+}
+
+int zr_last_round_loop(zr_ctx* c, int* drain_round, int* sub_pools) {
+    if (!c) return fail(ZR_E_INVALID, "null argument");
+    if (drain_round) *drain_round = c->last_drain_round;
+    if (sub_pools) *sub_pools = c->last_sub_pools;
     return ZR_OK;
 }
 

@@ -985,25 +985,65 @@ __global__ __launch_bounds__(256, ST_FUSED_WAVES) void fused_render(DScene sc, D
 // walks its share of the slot pool to find them).  So when no unit is left and fewer than 1/16 of the slots are active, the
 // host has the survivors MOVED to the front of a small pool of their own (all 23 state rows of a slot: a slot is self-contained,
 // its unit id travels with it) and runs the remaining rounds on that.  Which slot holds a path changes; nothing else does.
+// A block takes ST_COMPACT_PER x 256 slots and reserves room for all its survivors with ONE atomic: every survivor count goes through one word, which sustains
+// ~90 atomics/us (see ST_SHARDS), and with an atomic per wave that has a survivor the compaction of cfg3's two 52 Mi-slot sub-pools took 6.5 ms when 1 slot in
+// 100 was alive (800 K atomics) against 1.3 ms at 1 in 900: the earlier the switch, the dearer.  Now at most 27 K atomics whatever the survivors' number.
+#define ST_COMPACT_PER 16
 __global__ __launch_bounds__(256) void stream_compact(StreamBuf S, StreamBuf D, unsigned int* __restrict__ counter) {
-    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
-    bool act = false;
-    if (slot < S.P) act = (S.ld2(SF_MA, slot).y & F_ACTIVE) != 0;
-    const unsigned long long bm = __ballot(act);
-    if (bm == 0ull) return;
-    const int wl = threadIdx.x & 63, lead = (int)__builtin_ctzll(bm);
-    uint32_t base = 0;
-    if (wl == lead) base = atomicAdd(counter, (unsigned int)__popcll(bm));
-    base = __shfl(base, lead, 64);
-    if (!act) return;
-    const uint32_t d = base + (uint32_t)__popcll(bm & ((1ull << wl) - 1ull));
-    if (d >= D.P) return;   // (cannot happen: the host sized D from the same count)
+    __shared__ uint32_t s_wave[4];
+    __shared__ uint32_t s_base;
+    const int wl = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t slot0 = blockIdx.x * (256u * ST_COMPACT_PER) + threadIdx.x;   // pass j: slot0 + 256 j (grid: ceil(S.P / (256 PER)) blocks, so slot0 < 2^32)
+    unsigned long long bm[ST_COMPACT_PER];   // (wave-uniform)
+    uint32_t wave_total = 0;
 #pragma unroll
-    for (int f = 0; f <= SF_MB; f++) D.st(f, d, S.ld(f, slot));   // the 23 rows in use (the 24th is spare)
+    for (int j = 0; j < ST_COMPACT_PER; j++) {
+        const unsigned long long slot = (unsigned long long)slot0 + 256ull * (unsigned)j;
+        const bool act = slot < S.P && (S.ld2(SF_MA, (uint32_t)slot).y & F_ACTIVE) != 0;
+        bm[j] = __ballot(act);
+        wave_total += (uint32_t)__popcll(bm[j]);
+    }
+    if (wl == 0) s_wave[w] = wave_total;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (int k = 0; k < 4; k++) { const uint32_t c = s_wave[k]; total += c; if (k < w) before += c; }
+    if (total == 0) return;   // (the whole block)
+    if (threadIdx.x == 0) s_base = atomicAdd(counter, total);
+    __syncthreads();
+    uint32_t base = s_base + before;
+#pragma unroll
+    for (int j = 0; j < ST_COMPACT_PER; j++) {
+        if ((bm[j] >> wl) & 1ull) {
+            const uint32_t slot = slot0 + 256u * (unsigned)j;
+            const uint32_t d = base + (uint32_t)__popcll(bm[j] & ((1ull << wl) - 1ull));
+            // (d >= D.P cannot happen: the host sized D from a poll's count, which bounds this one — zr_round_polls.h, drain_condition)
+            if (d < D.P)
+                for (int f = 0; f <= SF_MB; f++) D.st(f, d, S.ld(f, slot));   // the 23 rows in use (the 24th is spare)
+        }
+        base += (uint32_t)__popcll(bm[j]);
+    }
 }
-__global__ __launch_bounds__(256) void stream_compact_pad(StreamBuf D, uint32_t from) {   // the slots behind the survivors: inactive
-    const uint32_t slot = from + blockIdx.x * 256 + threadIdx.x;
-    if (slot < D.P) { uint2 z; z.x = 0; z.y = 0; D.st2(SF_MA, slot, z); }
+// the slots behind the survivors: inactive.  How many survivors there are is *counter (stream_compact has run): the host's figure may be a few rounds old
+__global__ __launch_bounds__(256) void stream_compact_pad(StreamBuf D, const unsigned int* __restrict__ counter) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    if (slot >= *counter && slot < D.P) { uint2 z; z.x = 0; z.y = 0; D.st2(SF_MA, slot, z); }
+}
+
+// THE POLL of a round (zr_round_polls.h), one wave behind a sub-pool's SHADE on its stream: lane s reads shard s.  `host` is pinned host memory: a kernel's store
+// reaches it without leaving the stream for a copy engine, and the event the host records behind this launch says when it is there.
+__global__ __launch_bounds__(64) void stream_poll(StreamBuf B, unsigned int* __restrict__ host) {
+    const uint32_t sh = threadIdx.x;
+    uint32_t active = B.ctl[CTL_SHARD0 + CTL_STRIDE * sh + CTL_SH_ACTIVE];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) active += __shfl_xor(active, m, 64);   // (<= B.P: fits)
+    // shard sh has handed out every k below its counter (SHADE: unit = st_unit_of(.., k)); the counters only grow
+    const unsigned long long k = (unsigned long long)B.shard_k0 + B.uctl[CTL_STRIDE * sh + CTL_SH_UNITS];
+    const bool left = st_unit_of(B.unit_chunk, B.unit_base, sh, k) < (unsigned long long)B.n_units;
+    const unsigned long long any_left = __ballot(left);
+    if (sh == 0) {
+        host[POLL_ACTIVE] = active; host[POLL_CAPPED] = B.ctl[CTL_CAPPED]; host[POLL_UNITS_LEFT] = any_left != 0ull ? 1u : 0u;
+        __threadfence_system();
+    }
 }
 
 // one wave per pixel: lane l sums samples l, l + 64, ... in order, then a fixed xor butterfly — the order depends on
@@ -1273,14 +1313,84 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
         init(Q[k], X.streams[k]);
         shade(Q[k - 1], X.streams[k - 1]);
     }
-    int rounds = K > 1 ? 1 : 0;
+    // THE ROUND LOOP.  A loop round is EXTEND, SHADE and the round's poll (stream_poll) on every sub-pool's stream.  The host has to learn three things from
+    // the device: that the pools are empty, that the survivors are few enough for the drain pool, that a wave was capped.
+    //  - The LAGGED loop (a frame nobody polls: the timed path) keeps lag + 1 rounds in flight and waits for the event behind the OLDEST round's poll only, so a
+    //    stream never runs dry and one sub-pool's SHADE always has the other's EXTEND beside it.  What it learns is `lag` rounds old: the frame ends with up to
+    //    `lag` rounds on empty pools, which nobody sees (the round count and the launch log stop at the round that emptied the pools), the drain switch and a
+    //    capped wave are noticed up to `lag` rounds late.
+    //  - The CADENCED loop (ZR_STREAM_POLL_LAG=0, and every frame with keep_going or progress: camera::render cancels within two rounds and previews what is
+    //    finished) enqueues check_every rounds, copies the control words and synchronises every stream.
+    // Both count their rounds in RoundPolls (zr_round_polls.h), which also says why a poll's stale count may size the drain pool.
+    // Measured on cfg3 (profiles/r25_round_loop_ab.txt): the streams were never empty for long (0.55 ms of a frame without any kernel, before and after); what the
+    // lag buys is the drain switch one round after its condition holds instead of four (the cadenced loop was in a run of 8 rounds when it came true, and each late round walks two
+    // 52 Mi-slot pools for a few hundred thousand paths): 296.5 against 300.5 ms, lag 0 299.8, lag 2 298.2 (a second queued round on the big pools).
+    const int start_rounds = K > 1 ? 1 : 0, K0 = K;
+    const char* lag_env = std::getenv("ZR_STREAM_POLL_LAG");
+    int lag = lag_env ? std::atoi(lag_env) : 1;
+    lag = lag < 0 ? 0 : (lag > POLL_MAX_LAG ? POLL_MAX_LAG : lag);
+    const bool cadenced = lag == 0 || H.keep_going || H.progress || !X.h_polls || !X.poll_events;
+    RoundPolls rp(cadenced ? POLL_RING : lag + 1);
+    auto poll_words = [&](int slot, int k) { return X.h_polls + ((size_t)slot * ST_MAX_POOLS + (size_t)k) * POLL_WORDS; };
+    auto poll_event = [&](int slot, int k) { return X.poll_events[(size_t)slot * ST_MAX_POOLS + (size_t)k]; };
+    auto enqueue_round = [&](bool with_events) {   // on the current K sub-pools
+        const int s = rp.slot(rp.enqueued + 1);
+        for (int k = K - 1; k >= 0; k--) {
+            extend(Q[k], ov[k], X.streams[k]); shade(Q[k], X.streams[k]);
+            if (!X.h_polls) continue;
+            hipLaunchKernelGGL(stream_poll, dim3(1), dim3(64), 0, X.streams[k], Q[k], poll_words(s, k));
+            if (with_events && e == hipSuccess) e = hipEventRecord(poll_event(s, k), X.streams[k]);
+        }
+        rp.push(K, H.timer ? H.timer->logged() : 0);
+    };
+    // the survivors of Q[0 .. K) move to the drain pool of D_P slots (see stream_compact), on stream 0, which the caller has ordered behind the other streams
+    auto compact_to_drain = [&](uint32_t D_P) {
+        StreamBuf D = Q[0];
+        D.pool = (double*)job.pool.drain; D.P = D_P; D.unit0 = 0;
+        unsigned int* counter = X.ctl + CTL_COMPACT;   // (of pool 0)
+        for (int k = 0; k < K; k++) {
+            const uint32_t per_block = 256u * ST_COMPACT_PER;
+            hipLaunchKernelGGL(stream_compact, dim3((uint32_t)(((unsigned long long)Q[k].P + per_block - 1) / per_block)), dim3(256), 0, stream, Q[k], D, counter);
+        }
+        hipLaunchKernelGGL(stream_compact_pad, dim3(D.P / 256), dim3(256), 0, stream, D, counter);
+        Q[0] = D; K = 1;
+    };
+    int rounds = start_rounds, drain_round = 0;
     int check_every = H.progress ? 2 : 8;
     bool cancelled = false, drained = false, capped = false;
-    for (;;) {
-        for (int r = 0; r < check_every; r++) {
-            for (int k = K - 1; k >= 0; k--) { extend(Q[k], ov[k], X.streams[k]); shade(Q[k], X.streams[k]); }
-            rounds++;
+    static const bool trace_polls = std::getenv("ZR_STREAM_POLL_TRACE") != nullptr;   // development aid: one line per poll on stderr
+    if (!cadenced) for (;;) {
+        while (rp.may_enqueue() && e == hipSuccess) enqueue_round(true);
+        if (e != hipSuccess) break;
+        const int s = rp.slot(rp.oldest());
+        PollResult p;
+        for (int k = 0; k < rp.pools[s] && e == hipSuccess; k++) {
+            e = hipEventSynchronize(poll_event(s, k));
+            p.add(poll_words(s, k));
         }
+        if (e != hipSuccess) break;
+        const RoundPolls::Action a = rp.take(p, P, job.pool.drain_slots, job.pool.drain != nullptr);
+        if (trace_polls) std::fprintf(stderr, "[zr] poll of round %d (%d queued behind it): active %llu, units left %d, drain condition %d%s\n", rp.polled, rp.in_flight(),
+                                      p.active, (int)p.units_left, (int)drain_condition(p, P, job.pool.drain_slots), a.drain ? " -> compaction" : "");
+        if (a.finished) break;
+        if (a.drain) {
+            // stream 0 waits for what the other streams still hold: the event of the newest round stands behind a stream's last queued launch.  No host wait.
+            const int newest = rp.slot(rp.enqueued);
+            for (int k = 1; k < K && e == hipSuccess; k++) e = hipStreamWaitEvent(stream, poll_event(newest, k), 0);
+            if (e != hipSuccess) break;
+            compact_to_drain(a.drain_P);
+            drained = true; drain_round = rp.enqueued;
+        }
+        if (rp.enqueued > (1 << 22)) { e = hipErrorLaunchFailure; break; }
+    }
+    if (!cadenced && e == hipSuccess) {
+        // the rounds queued behind the emptying one run on empty pools; the frame's last kernels (stream 0) follow the other streams' share of them
+        const int newest = rp.slot(rp.enqueued);
+        for (int k = 1; k < K && e == hipSuccess; k++) e = hipStreamWaitEvent(stream, poll_event(newest, k), 0);
+        capped = rp.capped;
+    }
+    if (cadenced) for (;;) {
+        for (int r = 0; r < check_every; r++) { enqueue_round(false); rounds++; }
         for (int k = 0; k < K && e == hipSuccess; k++)
             e = hipMemcpyAsync(X.h_active + (size_t)k * W, X.ctl + (size_t)k * W, W * sizeof(unsigned int), hipMemcpyDeviceToHost, X.streams[k]);
         if (e == hipSuccess)   // the work-unit counters: how many samples have been started
@@ -1291,6 +1401,15 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
         for (int k = 0; k < K; k++) {
             if (X.h_active[(size_t)k * W + CTL_CAPPED] != 0) capped = true;   // (looked at here, for every sub-pool: the drain below folds them into one)
             for (int sh = 0; sh < ST_SHARDS; sh++) active += X.h_active[(size_t)k * W + CTL_SHARD0 + CTL_STRIDE * sh + CTL_SH_ACTIVE];
+        }
+        while (rp.in_flight() > 0) {   // which of these rounds emptied the pools: the rounds' own polls say (the copies above show the last round only)
+            PollResult p;
+            const int s = rp.slot(rp.oldest());
+            if (X.h_polls) for (int k = 0; k < rp.pools[s]; k++) p.add(poll_words(s, k));
+            else p.active = rp.in_flight() == 1 ? active : 1ull;
+            (void)rp.take(p, P, job.pool.drain_slots, false);
+            if (trace_polls) std::fprintf(stderr, "[zr] poll of round %d (drained with %d behind it): active %llu, units left %d, drain condition %d\n", rp.polled, rp.in_flight(),
+                                          p.active, (int)p.units_left, (int)(p.active != 0 && drain_condition(p, P, job.pool.drain_slots)));
         }
         if (H.progress && active != 0) {
             unsigned long long started = 0;   // the first P units are dealt at initialisation, the rest through the sharded counters
@@ -1320,13 +1439,10 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
             for (int sh = 0; sh < ST_SHARDS && !units_left; sh++)
                 if (st_unit_of(unit_chunk, P, (uint32_t)sh, (unsigned long long)(unit_chunk ? P / ST_SHARDS : 0u) + h_units[CTL_STRIDE * sh + CTL_SH_UNITS]) < (unsigned long long)n_units) units_left = true;
             if (!units_left) {   // see stream_compact
-                StreamBuf D = Q[0];
-                D.pool = (double*)job.pool.drain; D.P = (uint32_t)((active + 255ull) / 256ull * 256ull); D.unit0 = 0;
-                unsigned int* counter = X.ctl + CTL_COMPACT;   // (of pool 0)
-                for (int k = 0; k < K; k++) hipLaunchKernelGGL(stream_compact, dim3((Q[k].P + 255) / 256), dim3(256), 0, stream, Q[k], D, counter);
-                if (D.P > (uint32_t)active) hipLaunchKernelGGL(stream_compact_pad, dim3((D.P - (uint32_t)active + 255) / 256), dim3(256), 0, stream, D, (uint32_t)active);
+                compact_to_drain(drain_pool_slots(active));
+                if (trace_polls) std::fprintf(stderr, "[zr] compaction behind round %d\n", rp.enqueued);
                 if ((e = hipStreamSynchronize(stream)) != hipSuccess) break;
-                Q[0] = D; K = 1; drained = true;
+                drained = true; drain_round = rp.enqueued;
             }
         }
         check_every = active > P / 2 ? 8 : (active > P / 16 ? 4 : 2);
@@ -1336,6 +1452,10 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
     }
     if (e != hipSuccess) return e;
     if (capped) return hipErrorLaunchFailure;  // an EXTEND wave of some sub-pool hit its iteration cap: its rays were abandoned mid-walk
+    if (rp.emptied != 0) {   // the rounds behind the one that emptied the pools changed nothing: the caller does not see them, nor their launches
+        rounds = start_rounds + rp.emptied;
+        if (H.timer) H.timer->drop_from(rp.log_keep());
+    }
     const StreamBuf& A = Q[0];
     if (H.timer) H.timer->begin(stream, 3);
     if (job.split.cpart) hipLaunchKernelGGL(stream_sum_counters, dim3(1), dim3(256), 0, stream, job.split.cpart, cpart_blocks, X.gctr);
@@ -1343,6 +1463,7 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
     else if (F.out) hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, A, cam, F.out);
     if (H.timer) H.timer->end(stream, 3);
     if (H.done_out) *H.done_out = cancelled ? -rounds : rounds;
+    if (H.drain_out) { H.drain_out[0] = drain_round; H.drain_out[1] = K0; }
     return hipGetLastError();
 }
 
