@@ -256,6 +256,21 @@ struct flat_scene {
         if (rc == ZR_OK && !tri_uv.empty()) rc = zr_scene_set_triangle_uvs(sc, tri_uv.data(), tri_mat.size());
         return rc;
     }
+    // the same with every array COPIED by the library (zr_scene_set_all): a scene that is to be moved in place (camera::reuse_scene)
+    int give_copied_to(zr_scene* sc) const {
+        const zr_scene_desc d = desc();
+        int rc = zr_scene_set_all(sc, &d);
+        if (rc == ZR_OK && !tri_uv.empty()) rc = zr_scene_set_triangle_uvs(sc, tri_uv.data(), tri_mat.size());
+        return rc;
+    }
+    // equal to `o` in everything an update cannot change: all arrays byte for byte, except the a[3] of the ops and the numbers of the spheres
+    bool same_but_placements(const flat_scene& o) const {
+        auto eq = [](const auto& a, const auto& b) { return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0); };
+        if (spheres.size() != o.spheres.size() || ops.size() != o.ops.size()) return false;
+        for (size_t k = 0; k < ops.size(); k++) if (ops[k].kind != o.ops[k].kind || ops[k].mat != o.ops[k].mat) return false;
+        return eq(cubes, o.cubes) && eq(tri_v, o.tri_v) && eq(tri_n, o.tri_n) && eq(tri_uv, o.tri_uv) && eq(sphere_mat, o.sphere_mat) && eq(cube_mat, o.cube_mat) && eq(tri_mat, o.tri_mat) &&
+               eq(media, o.media) && eq(objects, o.objects) && eq(groups, o.groups) && eq(materials, o.materials) && eq(textures, o.textures) && eq(texels, o.texels);
+    }
 };
 
 class scene_builder {
@@ -1530,6 +1545,15 @@ public:
     std::vector<color> temporal_buffer;           // extension: the temporally accumulated frame of the last render; empty when it had none
     std::vector<int> temporal_history_length;     // extension: frames accumulated per pixel (row-major like render_accumulator); empty likewise
     void reset_temporal_history() { temporal_.reset(); }
+    // extension: moving worlds (zr_scene_update_* / zr_scene_refit).  Off: every render() commits a fresh scene, as always.  On: the camera keeps the
+    // committed scene between renders, as it keeps the temporal history; when the newly flattened world equals the kept one in everything but the arguments of
+    // its wrappers (a translate's offset, a rotation's angle, a scale's factors) and the numbers of its spheres — the reference's way to move things: the same
+    // objects under re-created translate / rotate_y wrappers — it updates the kept scene and refits its trees instead of building them again; any other
+    // change, a refused update, another device context or a failed refit commits anew.  last_scene_refit says which it was: 0 committed, 1 refitted.
+    // The frame is the same bit for bit either way.  The temporal history knows no object motion: reset_temporal_history() stays the caller's duty.
+    bool reuse_scene = false;
+    int last_scene_refit = 0;
+    void forget_scene() { kept_scene_.reset(); kept_ctx_ = nullptr; }
     zr_adaptive_stats last_adaptive{};
     zr_counters last_counters{};
 
@@ -1600,12 +1624,22 @@ public:
         {
             zenith::context_lease lease(device);   // one context of the process-wide pool, exclusively, for this frame
             if (!lease.ctx) { std::cerr << "[zenith] render failed: " << zr_last_error() << "\n"; return; }
-            const zenith::scene_handle sc(zr_scene_create(lease.ctx));
-            rc = sc ? fs.give_to(sc.get()) : ZR_E_DEVICE;
-            if (rc == ZR_OK) rc = zr_scene_commit(sc.get());
-            ph("commit");
+            zenith::scene_handle fresh;   // this frame's own scene, unless the camera keeps one (reuse_scene)
+            const zr_scene* scene = nullptr;
+            last_scene_refit = 0;
+            if (reuse_scene) {
+                rc = scene_for_frame(lease.ctx, fs);
+                scene = kept_scene_.get();
+            } else {
+                forget_scene();
+                fresh.reset(zr_scene_create(lease.ctx));
+                rc = fresh ? fs.give_to(fresh.get()) : ZR_E_DEVICE;
+                if (rc == ZR_OK) rc = zr_scene_commit(fresh.get());
+                scene = fresh.get();
+            }
+            ph(last_scene_refit ? "update + refit" : "commit");
             if (rc == ZR_OK) {
-                const frame_job job{lease.ctx, sc.get(), to_zr(), zenv, render_flag, &world};
+                const frame_job job{lease.ctx, scene, to_zr(), zenv, render_flag, &world};
                 sample_counts.clear();
                 variance_buffer.clear(); denoise_used_variance = false;
                 half_a_.clear(); half_b_.clear(); denoise_error_buffer.clear(); denoise_used_nlm = false;
@@ -1641,6 +1675,39 @@ private:
     };
     // the denoiser's guides when the public AOV buffers are off (the reference would hand OIDN zero guides then)
     struct guide_frames { std::vector<color> albedo, normal; };
+
+    // reuse_scene: the kept scene made to hold the world just flattened — by updates and a refit where only placements changed, else by a commit
+    int scene_for_frame(zr_ctx* ctx, const zenith::flat_scene& fs) {
+        if (kept_scene_ && kept_ctx_ == ctx && fs.same_but_placements(kept_fs_)) {
+            int rc = ZR_OK;
+            auto differ = [](const zr_xform_op& a, const zr_xform_op& b) { return std::memcmp(a.a, b.a, sizeof a.a) != 0; };
+            for (size_t k = 0; k < fs.ops.size() && rc == ZR_OK;) {   // one update per run of changed ops
+                if (!differ(fs.ops[k], kept_fs_.ops[k])) { k++; continue; }
+                size_t e = k + 1;
+                while (e < fs.ops.size() && differ(fs.ops[e], kept_fs_.ops[e])) e++;
+                rc = zr_scene_update_xform_ops(kept_scene_.get(), k, fs.ops.data() + k, e - k);
+                k = e;
+            }
+            const size_t ns = fs.sphere_mat.size();
+            for (size_t k = 0; k < ns && rc == ZR_OK;) {
+                auto moved = [&](size_t i) { return std::memcmp(&fs.spheres[i * 4], &kept_fs_.spheres[i * 4], 4 * sizeof(double)) != 0; };
+                if (!moved(k)) { k++; continue; }
+                size_t e = k + 1;
+                while (e < ns && moved(e)) e++;
+                rc = zr_scene_update_spheres(kept_scene_.get(), k, fs.spheres.data() + k * 4, e - k);
+                k = e;
+            }
+            if (rc == ZR_OK) rc = zr_scene_refit(kept_scene_.get(), nullptr);
+            if (rc == ZR_OK) { kept_fs_.ops = fs.ops; kept_fs_.spheres = fs.spheres; last_scene_refit = 1; return ZR_OK; }
+            // (a refused update — the world would be stored in another form — or a failed refit: build it anew)
+        }
+        forget_scene();
+        kept_scene_.reset(zr_scene_create(ctx));
+        int rc = kept_scene_ ? fs.give_copied_to(kept_scene_.get()) : ZR_E_DEVICE;
+        if (rc == ZR_OK) rc = zr_scene_commit(kept_scene_.get());
+        if (rc == ZR_OK) { kept_fs_ = fs; kept_ctx_ = ctx; } else forget_scene();
+        return rc;
+    }
 
     size_t pixels() const { return (size_t)image_width * image_height; }
     zr_camera to_zr() const {
@@ -1825,5 +1892,9 @@ private:
     std::vector<color> half_a_, half_b_;
     // the history of temporal_accumulation and what it was made for
     zenith::temporal_handle temporal_;
+    // the scene reuse_scene keeps, the context it lives on and the flattened world it holds
+    zenith::scene_handle kept_scene_;
+    zr_ctx* kept_ctx_ = nullptr;
+    zenith::flat_scene kept_fs_;
     zr_ctx* temporal_ctx_ = nullptr; const hittable* temporal_world_ = nullptr; int temporal_w_ = 0, temporal_h_ = 0;
 };

@@ -283,6 +283,45 @@ uint32_t zr_scene_traversal_stack(const zr_scene*);
  * bvh_node's constructor (/root/reference/bvh.hpp:11-44), which the reference runs on every render restart (main.cpp:1492-1500). */
 const char* zr_scene_builder(const zr_scene*);
 
+/* ---- moving worlds: update placements in place, refit the trees on the device ---------------- */
+/* A committed scene whose arrays were COPIED (zr_scene_set_* / zr_scene_set_all; not zr_scene_set_all_borrowed, whose arrays the commit releases) can be
+ * moved without a new commit.  What can move: the parameters a[3] of wrapper ops (a translate's offset, a rotation's sin / cos, a scale's factors) and the
+ * four numbers of spheres that are leaf primitives of their own.  The tree keeps its topology: the moved entries' records and boxes are rewritten, and the
+ * boxes of the world's trees are fitted anew on the device, level by level.  A refitted scene answers every ray as a fresh commit of the moved world would
+ * (closest hit does not depend on the tree); how good the old topology still is for the new positions shows in zr_refit_info::area_ratio, and when to commit
+ * anew is the caller's call.
+ *   zr_scene_update_xform_ops  replaces ops [first, first + n) of the committed op array.  Only a[3] may differ from the committed op.
+ *   zr_scene_update_spheres    replaces the numbers (cx, cy, cz, radius) of spheres [first, first + n).
+ *     Both change the scene's host copy and mark the scene STALE; they do not touch the device and do not clear "committed".  ZR_E_STATE: the scene is not
+ *     committed, or was committed from borrowed arrays.  ZR_E_INVALID, with NOTHING changed: NULL, a range that leaves the committed arrays, a value that is
+ *     not finite, an op whose kind or mat differs from the committed one, a sphere that is a medium's boundary or sits inside a generic wrapper chain, or a
+ *     change after which a world-list entry would be stored in another form than the commit chose (a uniform scale over a baked sphere made non-uniform, a
+ *     scale factor of a placed cube set to 0): such a world needs a new commit.
+ *     While a scene is stale every entry point that reads the device scene (zr_render*, zr_trace*, zr_kat_*, zr_render_gbuffer, zr_scene_tree_boxes, the
+ *     accumulator and temporal entries) returns ZR_E_STATE, "scene updated but not refitted".
+ *   zr_scene_refit             makes the device scene agree with the updates since the last refit: queued on the context's stream, so renders on that
+ *     context follow it; one stream synchronisation (the new root box is a kernel argument).  With nothing stale it still runs (dirty_entries = 0): a
+ *     legal way to ask for area_ratio.  ZR_E_STATE as for the updates.  On ANY failure the scene becomes uncommitted — a render then says "commit first";
+ *     a moved box that no 4-wide node's grid can hold (not finite, beyond 1e30) is such a failure (ZR_E_INVALID, "commit anew").  The first refit after a
+ *     commit builds its state (reverse indices, schedule, device buffers) and is slower; later ones allocate nothing.  (A world of at most ZR_FUSED_MAX
+ *     objects also re-reads the fused kernel's argument copy.)
+ * An accumulator binds (scene, epoch): a batch after a refit is refused like a batch with another scene (ZR_E_INVALID) until zr_accum_reset.  A zr_temporal
+ * must be reset by the caller after a refit.
+ * Out of scope, each needs a new commit: triangle vertices and cubes' own numbers; adding or removing entries; material or texture changes; the triangles
+ * inside a group (a placement of the group may move; the group's own tree is never touched); motion vectors for the temporal stage. */
+typedef struct zr_refit_info {
+    uint64_t epoch;          /* refits applied to this commit (0 after zr_scene_commit) */
+    uint32_t dirty_entries;  /* world-list entries whose record or box was recomputed (media reached through their inner chain included) */
+    uint32_t levels;         /* launches of the 4-wide refit kernel = levels of the world's 4-wide tree below its root */
+    double area_ratio;       /* sum of the half-areas of the world tree's pair boxes now / over the committed world, both as the refit computes them:
+                                exactly 1.0 when everything is where the commit had it */
+    double host_ms;          /* wall time of the call */
+    double device_ms;        /* of it, device time from the first patch copy to the last tree kernel (HIP events) */
+} zr_refit_info;
+int zr_scene_update_xform_ops(zr_scene*, size_t first, const zr_xform_op* ops, size_t n);
+int zr_scene_update_spheres(zr_scene*, size_t first, const double* cxyz_r, size_t n);
+int zr_scene_refit(zr_scene*, zr_refit_info* out /* may be NULL */);
+
 /* ---- render: replaces camera::render's sample loop (camera.hpp:236-248, 404-579) ----------- */
 /* Fills out_rgb[(j*W+i)*3 + c] (host memory, W*H*3 doubles, row 0 = top, mean over spp — the layout of
  * camera::render_accumulator) for the pixels of `region`; other pixels are left untouched.
@@ -575,7 +614,7 @@ int zr_accum_denoise_nlm(zr_accum*, const zr_denoise_nlm_params*, const double* 
  *                      mat 0xFFFFFFFF.  Host memory; any output may be NULL.  Argument checks and error codes as zr_render_aov.
  * zr_temporal          the history of a width x height frame on the device, double-buffered in FP64: blended colour and variance, history length, the
  *                      previous frame's geometry buffer and the previous camera.  zr_temporal_reset forgets it (the caller's duty after any change of the
- *                      scene); zr_temporal_state: out = width, height, frames accumulated since create / reset, 0.
+ *                      scene, a zr_scene_refit included: the history carries no motion vectors); zr_temporal_state: out = width, height, frames accumulated since create / reset, 0.
  * zr_temporal_accumulate  takes one frame — `color` and `variance` (of the pixel means, e.g. zr_accum_resolve / zr_accum_variance), W*H*3 doubles in host
  *                      memory — makes the camera's geometry buffer and, per pixel p (FP64, no contraction; tests/temporal_model.py restates it):
  *                        c, V: the inputs with NaN / Inf -> 0 and V <= 0 -> 0 (zr_denoise_guided's rules);

@@ -246,6 +246,15 @@ TREE_BOX_DTYPE = np.dtype([("lo", "<f4", 3), ("hi", "<f4", 3), ("id", "<u4"), ("
                            ("leaf", "<u4"), ("kind", "<u4"), ("count", "<u4"), ("first", "<u4"), ("subtree", "<u4"), ("src", "<u4", 4)])
 
 
+class RefitInfo(C.Structure):
+    """zr_refit_info: what zr_scene_refit reports (include/zr_capi.h)"""
+    _fields_ = [("epoch", C.c_uint64), ("dirty_entries", C.c_uint32), ("levels", C.c_uint32), ("area_ratio", C.c_double), ("host_ms", C.c_double),
+                ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("spheres", C.c_void_p), ("sphere_mat", C.c_void_p), ("n_spheres", C.c_uint64),
                 ("tri_v", C.c_void_p), ("tri_n", C.c_void_p), ("tri_mat", C.c_void_p), ("n_tris", C.c_uint64),
@@ -267,7 +276,7 @@ CAPI_SYMBOLS = [
     "zr_abi_version", "zr_last_error", "zr_create", "zr_destroy", "zr_scene_create", "zr_scene_destroy",
     "zr_scene_set_spheres", "zr_scene_set_triangles", "zr_scene_set_triangle_uvs", "zr_scene_set_cubes", "zr_scene_set_media",
     "zr_scene_set_xform_ops", "zr_scene_set_objects", "zr_scene_set_groups", "zr_scene_set_materials", "zr_scene_set_textures",
-    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_stats", "zr_scene_kernels", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device",
+    "zr_scene_set_all", "zr_scene_set_all_borrowed", "zr_scene_commit", "zr_scene_update_xform_ops", "zr_scene_update_spheres", "zr_scene_refit", "zr_scene_stats", "zr_scene_kernels", "zr_scene_traversal_stack", "zr_scene_builder", "zr_render", "zr_render_device",
     "zr_accum_create", "zr_accum_destroy", "zr_accum_reset", "zr_render_accumulate", "zr_accum_resolve", "zr_accum_resolve_device", "zr_accum_state",
     "zr_render_adaptive", "zr_accum_error", "zr_accum_sample_counts", "zr_accum_lane_sums",
     "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
@@ -309,6 +318,10 @@ def load():
     lib.zr_scene_set_materials.argtypes = [vp, vp, C.c_size_t]
     lib.zr_scene_set_textures.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
     lib.zr_scene_commit.argtypes = [vp]
+    if hasattr(lib, "zr_scene_refit"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
+        lib.zr_scene_update_xform_ops.argtypes = [vp, C.c_size_t, vp, C.c_size_t]
+        lib.zr_scene_update_spheres.argtypes = [vp, C.c_size_t, vp, C.c_size_t]
+        lib.zr_scene_refit.argtypes = [vp, C.POINTER(RefitInfo)]
     lib.zr_scene_stats.argtypes = [vp, C.POINTER(u64 * 4)]
     lib.zr_scene_kernels.argtypes = [vp, C.POINTER(C.c_uint32 * 4)]
     lib.zr_scene_traversal_stack.argtypes = [vp]; lib.zr_scene_traversal_stack.restype = C.c_uint32
@@ -401,6 +414,7 @@ def load_scenes():
     s.zrs_render_dropin_denoise_nlm.argtypes = frame + [C.c_double, i32, i32] + [vp] * 5
     s.zrs_render_dropin_temporal.argtypes = frame + [i32, vp, i32, i32] + [vp] * 5
     s.zrs_render_dropin_bvh_debug.argtypes = frame + [i32, C.c_float, vp, vp]
+    s.zrs_render_dropin_animated.argtypes = frame + [i32, i32, i32, vp, vp]
     s.zrs_dropin_virtuals.argtypes = [vp, vp, i32, C.c_uint64, C.c_uint64, vp, vp]
     s.zrs_dropin_frame_to_rgb8.argtypes = [vp, i32, i32, vp, vp, C.POINTER(C.c_float)]
     _scenes = s
@@ -539,6 +553,18 @@ class DemoScene:
         aux.fill(-1.0)
         self._rendered(load_scenes().zrs_render_dropin_bvh_debug(self._h, width, height, spp, device, level, thickness, out.ctypes.data, aux.ctypes.data) == 0)
         return out, aux
+
+    def render_dropin_animated(self, n_frames, reuse_scene, add_at=-1, width=0, height=0, spp=0, device=0):
+        """n_frames renders of the shim's small moving world through ONE drop-in camera object with camera::reuse_scene = reuse_scene: one translate and
+        one rotate_y re-created around a shared cube with new arguments for every frame, a sphere that rises, and from frame add_at on (-1: never) one
+        object more.  Returns (frames (n, H, W, 3) float64, camera::last_scene_refit after each render as a list: 0 committed, 1 refitted)"""
+        w = width or self.camera.image_width
+        h = height or self.camera.image_height
+        out = np.zeros((n_frames, h, w, 3), dtype=np.float64)
+        refit = (C.c_int * n_frames)()
+        self._rendered(load_scenes().zrs_render_dropin_animated(self._h, width, height, spp, device, int(n_frames), 1 if reuse_scene else 0, int(add_at),
+                                                                out.ctypes.data, refit) == 0)
+        return out, [int(x) for x in refit]
 
     def dropin_virtuals(self, rays8, seed, pixel=0x7ACE):
         """bvh_node(world).hit + rec.mat->emitted / scatter through the drop-in classes (one device launch per call):
@@ -900,22 +926,47 @@ def temporal_view(camera):
 
 
 class Scene:
-    def __init__(self, ctx, desc, tri_uv=None):
+    def __init__(self, ctx, desc, tri_uv=None, animated=False):
         """tri_uv: per-vertex texture coordinates of the description's triangles, (n_tris, 3, 2) or (n_tris, 6) float64 = u0 v0 u1 v1 u2 v2 per
-        triangle (zr_scene_set_triangle_uvs); None: the triangles carry none (u = v = 0 on every triangle hit)"""
+        triangle (zr_scene_set_triangle_uvs); None: the triangles carry none (u = v = 0 on every triangle hit).
+        animated: the library copies the description's arrays (zr_scene_set_all) instead of borrowing them, so that update_ops / update_spheres /
+        refit can move the committed world"""
         self.ctx = ctx
         self.lib = ctx.lib
         self._s = self.lib.zr_scene_create(ctx._c)
         if not self._s:
             raise ZrError(self.lib.zr_last_error().decode())
         # the description's arrays outlive this call (the caller holds them): no need for the library to copy 200 MB of triangles
-        _check(self.lib.zr_scene_set_all_borrowed(self._s, C.byref(desc)))
+        _check((self.lib.zr_scene_set_all if animated else self.lib.zr_scene_set_all_borrowed)(self._s, C.byref(desc)))
         if tri_uv is not None:
             uv = np.ascontiguousarray(tri_uv, dtype=np.float64)
             if uv.ndim not in (2, 3) or uv.size != uv.shape[0] * 6:
                 raise ValueError(f"tri_uv must be (n_tris, 3, 2) or (n_tris, 6), not {uv.shape}")
             _check(self.lib.zr_scene_set_triangle_uvs(self._s, uv.ctypes.data, uv.shape[0]))   # (the library copies it)
         _check(self.lib.zr_scene_commit(self._s))
+
+    def update_ops(self, first, ops):
+        """zr_scene_update_xform_ops: replaces wrapper ops [first, first + len(ops)) of the committed scene (only a[3] may differ).  ops: a NumPy array
+        with XformOp's layout, or a sequence of XformOp.  The scene is stale until refit()."""
+        if isinstance(ops, np.ndarray):
+            arr = np.ascontiguousarray(ops)
+            assert arr.dtype.itemsize == C.sizeof(XformOp), "ops must have zr_xform_op's layout"
+            ptr, n = arr.ctypes.data, len(arr)
+        else:
+            arr = (XformOp * len(ops))(*ops)
+            ptr, n = C.cast(arr, C.c_void_p), len(ops)
+        _check(self.lib.zr_scene_update_xform_ops(self._s, int(first), ptr, n))
+
+    def update_spheres(self, first, cxyz_r):
+        """zr_scene_update_spheres: replaces the numbers (cx, cy, cz, radius) of spheres [first, first + len(cxyz_r)).  Stale until refit()."""
+        q = np.ascontiguousarray(cxyz_r, dtype=np.float64).reshape(-1, 4)
+        _check(self.lib.zr_scene_update_spheres(self._s, int(first), q.ctypes.data, len(q)))
+
+    def refit(self):
+        """zr_scene_refit: the device scene made to agree with the updates -> dict of zr_refit_info"""
+        info = RefitInfo()
+        _check(self.lib.zr_scene_refit(self._s, C.byref(info)))
+        return info.as_dict()
 
     def stats(self):
         out = (C.c_uint64 * 4)()

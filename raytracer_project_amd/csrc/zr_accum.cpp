@@ -14,13 +14,13 @@ struct AccumState {
     int first = 0, done = 0;
     int route = 2;                 // zr_counters::path of the batches so far: which one-shot kernel's pairing the resolve follows
     bool bound = false;            // a batch has been added since create / reset: later ones must bring the same camera, seed and scene
-    zr_camera cam{}; uint64_t seed = 0; const zr_scene* scene = nullptr;
+    zr_camera cam{}; uint64_t seed = 0; const zr_scene* scene = nullptr; uint64_t scene_epoch = 0;   // (the scene as refitted so often: zr_scene_refit)
     // adaptive sampling (zr_render_adaptive), allocated by its first run: the sample count per pixel, the active list and its slot index
     // (two of each: a pass compacts one into the other), the flags per list position and the compaction's block counts and totals
     bool adaptive = false;         // an adaptive pass has completed since create / reset: the counts are per pixel (d_count) and `done` is the largest
     DevBuf<int32_t> d_count; DevBuf<uint32_t> d_list[2], d_slot[2], d_flag, d_block_active, d_block_at_max, d_totals;
     static zr_camera key_of(zr_camera c) { c.samples_per_pixel = 0; return c; }   // the camera as the binding compares it: its sample count is ignored here
-    void bind(const zr_camera& c, uint64_t sd, const zr_scene* s) { if (!bound) { bound = true; cam = key_of(c); seed = sd; scene = s; } }   // by the first samples added
+    void bind(const zr_camera& c, uint64_t sd, const zr_scene* s) { if (!bound) { bound = true; cam = key_of(c); seed = sd; scene = s; scene_epoch = s->epoch; } }   // by the first samples added
     size_t sums() const { return (size_t)n_pix * zr::ACCUM_DOUBLES_PER_PIXEL; }
     size_t device_bytes() const {
         return sums() * sizeof(double) + (size_t)n_pix * sizeof(uint32_t) + d_count.n * sizeof(int32_t) +
@@ -145,7 +145,7 @@ int accum_call_ready(const zr_ctx* c, const zr_scene* s, const zr_camera* cam, u
     const int W = cam->image_width < 1 ? 1 : cam->image_width, H = cam->image_height < 1 ? 1 : cam->image_height;
     if (W != st.plan.W || H != st.plan.H) return fail(ZR_E_INVALID, "camera of %d x %d px, accumulator of %d x %d", W, H, st.plan.W, st.plan.H);
     const zr_camera key = AccumState::key_of(*cam);
-    if (st.bound && (std::memcmp(&key, &st.cam, sizeof key) != 0 || seed != st.seed || s != st.scene))
+    if (st.bound && (std::memcmp(&key, &st.cam, sizeof key) != 0 || seed != st.seed || s != st.scene || s->epoch != st.scene_epoch))
         return fail(ZR_E_INVALID, "camera, seed or scene differ from the first batch's: zr_accum_reset starts a new frame");
     if (end > 0x7FFFFFFFll) return fail(ZR_E_INVALID, "sample range beyond 2^31");
     if (st.adaptive) return fail(ZR_E_STATE, "the accumulator holds an adaptive run's per-pixel counts: zr_accum_reset starts a new frame");

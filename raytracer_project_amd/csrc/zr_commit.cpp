@@ -53,6 +53,7 @@ int commit_host(zr_scene* s, std::shared_ptr<const CommitPlan> plan, PhaseTimer&
     cs.root = fl.root; cs.quant_ok = fl.quant_ok; cs.n_pairs = fl.pairs.size(); cs.n_quads = fl.quads.size(); cs.plain_media = fl.plain_media();
     cs.stack_demand = fl.stack_demand(); cs.quad_depth = fl.quad_depth; cs.max_depth = hb->br.max_depth; cs.kept_closed = fl.n_kept_closed;
     cs.builder = "host (binned SAH)";
+    s->group_box = hb->group_box;
     staging = std::move(hb);
     return ZR_OK;
 }
@@ -262,6 +263,8 @@ int commit_device(zr_scene* s, const CommitPlan& plan, const PhaseTimer& outer, 
     cs.n_pairs = n_pairs; cs.n_quads = n_quads; cs.plain_media = fl.plain_media();
     cs.stack_demand = world.demand; cs.quad_depth = (int)world.quad_depth; cs.max_depth = (int)world.depth;
     cs.builder = "device (PLOC)";
+    s->group_box.resize(ng);
+    for (size_t g = 0; g < ng; g++) for (int k = 0; k < 3; k++) { s->group_box[g].lo[k] = gbox[g * 6 + k]; s->group_box[g].hi[k] = gbox[g * 6 + 3 + k]; }
     s->ctx->free_later([tmp = std::move(tmp), device = s->ctx->device]() mutable { (void)hipSetDevice(device); tmp.reset(); });
     ph("release");
     outcome = DeviceBuild::Done;
@@ -313,37 +316,9 @@ int finish_commit(zr_scene* s, const CommitPlan& plan, const CommitSummary& cs) 
     d.root = cs.root;
     s->leaf_objects = 0;
     for (int k = 0; k < 7; k++) { d.leaf_cnt[k] = plan.cnt[k]; s->leaf_objects += plan.cnt[k]; }   // (no leaf kind 7 exists)
-    // a small world's objects for the fused kernel's arguments (zr_launch.h: FusedObjs): read back from the arrays just built,
-    // whichever builder made them (a few hundred bytes)
-    s->fused_ok = false;
-    if (s->leaf_objects > 0 && s->leaf_objects <= ZR_FUSED_OBJECTS && plan.cnt[ZR_KIND_INSTANCE] == 0) {
-        zr::FusedObjs fo{};
-        auto take = [&](uint32_t kind, const double* d_src, size_t stride, size_t doubles) -> int {
-            for (uint32_t i = 0; i < plan.cnt[kind]; i++) {
-                fo.kind[fo.n] = kind; fo.index[fo.n] = i;
-                HIP_OK(hipMemcpy(fo.rec[fo.n], d_src + (size_t)i * stride, doubles * sizeof(double), hipMemcpyDeviceToHost));
-                fo.n++;
-            }
-            return ZR_OK;
-        };
-        if ((rc = take(ZR_PRIM_SPHERE, s->d_spheres.p, ZR_SPHERE_DOUBLES, ZR_SPHERE_DOUBLES)) || (rc = take(ZR_PRIM_TRIANGLE, s->d_tri_v.p, ZR_TRI_STRIDE, 9)) ||
-            (rc = take(ZR_PRIM_CUBE, s->d_cubes.p, ZR_CUBE_DOUBLES, ZR_CUBE_DOUBLES)) || (rc = take(ZR_KIND_PCUBE, s->d_pcubes.p, ZR_PCUBE_STRIDE, ZR_PCUBE_STRIDE))) return rc;
-        std::vector<zr::DMedium> hm(plan.cnt[ZR_PRIM_MEDIUM]);
-        if (!hm.empty()) HIP_OK(hipMemcpy(hm.data(), s->d_media.p, hm.size() * sizeof(zr::DMedium), hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < hm.size(); i++) {
-            if (hm[i].chain_count != 0) continue;   // a wrapped boundary: tested through the scene's arrays (level 2)
-            fo.kind[fo.n] = ZR_PRIM_MEDIUM; fo.index[fo.n] = i;
-            const bool sph = hm[i].btype == ZR_PRIM_SPHERE;
-            HIP_OK(hipMemcpy(fo.rec[fo.n], sph ? s->d_spheres.p + (size_t)hm[i].bindex * ZR_SPHERE_DOUBLES : s->d_cubes.p + (size_t)hm[i].bindex * ZR_CUBE_DOUBLES, (sph ? ZR_SPHERE_DOUBLES : ZR_CUBE_DOUBLES) * sizeof(double), hipMemcpyDeviceToHost));
-            fo.rec[fo.n][6] = hm[i].neg_inv_density;
-            const uint64_t idb = hm[i].id, tb = hm[i].btype;
-            std::memcpy(&fo.rec[fo.n][7], &idb, 8); std::memcpy(&fo.rec[fo.n][8], &tb, 8);
-            fo.n++;
-        }
-        bool scaled = false;   // the fused kernel's placed-cube code carries no scale (zr_device.h pcube_ray<false>): such a world takes the pipeline
-        for (uint32_t i = 0; i < fo.n; i++) if (fo.kind[i] == ZR_KIND_PCUBE && fo.rec[i][15] != 0.0) scaled = true;
-        s->fused = fo; s->fused_ok = !scaled;
-    }
+    // a small world's objects for the fused kernel's arguments (refresh_fused_objects, below; a refit runs it again)
+    for (int k = 0; k < 8; k++) s->plan_cnt[k] = plan.cnt[k];
+    if ((rc = refresh_fused_objects(s))) return rc;
     {   // which build of the EXTEND kernel this world needs (zr_stream.hip)
         if (z[ZR_KIND_INSTANCE]) s->leaf_level = 3;   // placed runs of triangles: the build with the nested walk
         else if (z[ZR_KIND_WRAPPED] || !cs.plain_media) s->leaf_level = 2;
@@ -382,6 +357,7 @@ int finish_commit(zr_scene* s, const CommitPlan& plan, const CommitSummary& cs) 
                      fnv(s->d_nodes.p, cs.n_pairs * sizeof(zr::NodePair)), cs.n_pairs);
     }
     s->committed = true;
+    if (!s->borrowed) { s->plan_objs = plan.objs; s->plan_code = plan.code; s->plan_bake = plan.kn.bake; }   // a copied scene can be baked again: zr_scene_update_*
     if (s->borrowed) {   // the caller's arrays are not read again: forget them (a second commit needs a new zr_scene_set_*)
         s->spheres.drop(); s->sphere_mat.drop(); s->tri_v.drop(); s->tri_n.drop(); s->tri_mat.drop(); s->tri_uv.drop(); s->cubes.drop(); s->cube_mat.drop();
         s->media.drop(); s->ops.drop(); s->objects.drop(); s->texels.drop(); s->objects_set = false; s->borrowed = false; s->released = true;
@@ -390,6 +366,42 @@ int finish_commit(zr_scene* s, const CommitPlan& plan, const CommitSummary& cs) 
 }
 
 }  // namespace
+
+// A small world's objects for the fused kernel's arguments (zr_launch.h: FusedObjs): read back from the device arrays, whichever builder made them and
+// whatever a refit has rewritten since (a few hundred bytes).  The arguments are copies, so a refit calls this again.
+int refresh_fused_objects(zr_scene* s) {
+    int rc;
+    s->fused_ok = false;
+    if (s->leaf_objects > 0 && s->leaf_objects <= ZR_FUSED_OBJECTS && s->plan_cnt[ZR_KIND_INSTANCE] == 0) {
+        zr::FusedObjs fo{};
+        auto take = [&](uint32_t kind, const double* d_src, size_t stride, size_t doubles) -> int {
+            for (uint32_t i = 0; i < s->plan_cnt[kind]; i++) {
+                fo.kind[fo.n] = kind; fo.index[fo.n] = i;
+                HIP_OK(hipMemcpy(fo.rec[fo.n], d_src + (size_t)i * stride, doubles * sizeof(double), hipMemcpyDeviceToHost));
+                fo.n++;
+            }
+            return ZR_OK;
+        };
+        if ((rc = take(ZR_PRIM_SPHERE, s->d_spheres.p, ZR_SPHERE_DOUBLES, ZR_SPHERE_DOUBLES)) || (rc = take(ZR_PRIM_TRIANGLE, s->d_tri_v.p, ZR_TRI_STRIDE, 9)) ||
+            (rc = take(ZR_PRIM_CUBE, s->d_cubes.p, ZR_CUBE_DOUBLES, ZR_CUBE_DOUBLES)) || (rc = take(ZR_KIND_PCUBE, s->d_pcubes.p, ZR_PCUBE_STRIDE, ZR_PCUBE_STRIDE))) return rc;
+        std::vector<zr::DMedium> hm(s->plan_cnt[ZR_PRIM_MEDIUM]);
+        if (!hm.empty()) HIP_OK(hipMemcpy(hm.data(), s->d_media.p, hm.size() * sizeof(zr::DMedium), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < hm.size(); i++) {
+            if (hm[i].chain_count != 0) continue;   // a wrapped boundary: tested through the scene's arrays (level 2)
+            fo.kind[fo.n] = ZR_PRIM_MEDIUM; fo.index[fo.n] = i;
+            const bool sph = hm[i].btype == ZR_PRIM_SPHERE;
+            HIP_OK(hipMemcpy(fo.rec[fo.n], sph ? s->d_spheres.p + (size_t)hm[i].bindex * ZR_SPHERE_DOUBLES : s->d_cubes.p + (size_t)hm[i].bindex * ZR_CUBE_DOUBLES, (sph ? ZR_SPHERE_DOUBLES : ZR_CUBE_DOUBLES) * sizeof(double), hipMemcpyDeviceToHost));
+            fo.rec[fo.n][6] = hm[i].neg_inv_density;
+            const uint64_t idb = hm[i].id, tb = hm[i].btype;
+            std::memcpy(&fo.rec[fo.n][7], &idb, 8); std::memcpy(&fo.rec[fo.n][8], &tb, 8);
+            fo.n++;
+        }
+        bool scaled = false;   // the fused kernel's placed-cube code carries no scale (zr_device.h pcube_ray<false>): such a world takes the pipeline
+        for (uint32_t i = 0; i < fo.n; i++) if (fo.kind[i] == ZR_KIND_PCUBE && fo.rec[i][15] != 0.0) scaled = true;
+        s->fused = fo; s->fused_ok = !scaled;
+    }
+    return ZR_OK;
+}
 
 extern "C" {
 
@@ -528,6 +540,8 @@ int zr_scene_commit(zr_scene* s) {
     if (s->released) return fail(ZR_E_STATE, "the arrays given to zr_scene_set_all_borrowed were released by the previous commit: set the scene again");
     s->committed = false;
     HIP_OK(hipSetDevice(s->ctx->device));
+    s->stale = false; s->epoch = 0; s->refit.reset();   // what updates and refits built on the previous commit (the refit state holds device memory)
+    std::vector<zr_object>().swap(s->plan_objs); std::vector<uint8_t>().swap(s->plan_code); s->group_box.clear();
     PhaseTimer ph{"commit", 22};
     std::vector<zr_object> objs = world_list(*s);
     int rc = validate(*s, objs);

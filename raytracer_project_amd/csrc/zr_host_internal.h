@@ -2,6 +2,7 @@
 //   zr_host.cpp    context life cycle, error string, small C-ABI entry points
 //   zr_commit.cpp  scene setters, the commit plan, zr_scene_commit through the host builder or the device builder (zr_flatten.h: validation, the plan, the
 //                  flattener and the host builder's CPU half — no HIP, built on zr_scene_input.h: the world as given)
+//   zr_update.cpp  moving worlds: zr_scene_update_* on the host copy, zr_scene_refit and its state (zr_update.h: the rules, no HIP; zr_refit.h / .hip: the device side)
 //   zr_scene_query.cpp  what a committed scene answers: statistics, kernel builds, traversal stack, builder, zr_scene_tree_boxes
 //   zr_render.cpp  camera frame / sky constants, the frame job every render entry prepares (tile plan, validation) and its drivers (streaming pipeline, fused
 //                  kernel, pixel-group kernel), AOV / split passes, BVH debug view, counters, known-answer entry points
@@ -134,6 +135,8 @@ struct zr_ctx {
     void drain_trash() { std::lock_guard<std::mutex> lk(trash_m); if (trash.joinable()) trash.join(); }
 };
 
+struct RefitState;   // zr_update.cpp
+
 struct zr_scene : SceneInput {   // the world as given (host side), then what the commit made of it
     zr_ctx* ctx = nullptr;
     int device = 0;               // the context's device ordinal, kept here so that zr_scene_destroy needs no live context (a scene may outlive its context)
@@ -164,7 +167,20 @@ struct zr_scene : SceneInput {   // the world as given (host side), then what th
     const char* builder = "";   // which builder made the committed tree (zr_scene_builder)
     std::vector<uint32_t> leaf_src[8];   // per leaf kind, in that kind's array order: a leaf primitive's index in the caller's arrays (zr_scene_tree_boxes);
                                          // 0xFFFFFFFF for the primitives inside media and wrapper chains
+    // ---- moving worlds (zr_update.cpp: zr_scene_update_*, zr_scene_refit).  What the commit keeps for them — only of a scene it may bake again, i.e. one
+    // whose arrays were copied — and the state of the updates since
+    std::vector<zr_object> plan_objs;    // the commit plan's world list ...
+    std::vector<uint8_t> plan_code;      // ... its classification per entry (leaf kind | baked << 4): an update must not change it
+    bool plan_bake = true;               // ... and the knob it was made with (BuildKnobs::bake)
+    uint32_t plan_cnt[8] = {};           // leaf objects per kind
+    std::vector<zr::BuildBox> group_box; // per zr_group: the box of its triangles in their own space, as the builder that made the tree computed it
+    bool stale = false;                  // an update changed the host copy of the world and no refit has followed: nothing may read the device scene
+    uint64_t epoch = 0;                  // refits applied to this commit
+    std::shared_ptr<RefitState> refit;   // reverse indices, leaf boxes, the trees' schedule, device buffers: made by the first update or refit after a commit, dropped by the next
 };
+
+// the small world's objects as the fused kernel's arguments (zr_launch.h: FusedObjs), read back from the device arrays: by a commit and again by a refit
+int refresh_fused_objects(zr_scene* s);
 
 struct CommitSummary {   // what the shared end of a commit needs to know about the tree either builder produced (counts and array sizes: the CommitPlan's)
     zr::NodeF root{}; bool quant_ok = true;

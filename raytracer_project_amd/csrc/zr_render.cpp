@@ -373,6 +373,7 @@ int copy_region(const Plan& p, const double* d_frame, double* out, std::vector<d
 // the scene half of an entry point's argument preamble (the null tests differ per entry and stay there)
 int scene_ready(const zr_ctx* c, const zr_scene* s, const char* entry, bool any_context) {
     if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede %s", entry);
+    if (s->stale) return fail(ZR_E_STATE, "scene updated but not refitted: zr_scene_refit must precede %s", entry);
     if (!any_context && s->ctx != c) return fail(ZR_E_INVALID, "scene belongs to another context");
     return ZR_OK;
 }

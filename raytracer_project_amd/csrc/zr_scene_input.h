@@ -47,6 +47,7 @@ struct HostArray {
     size_t size() const { return n; }
     bool empty() const { return n == 0; }
     const T* data() const { return p; }
+    T* own_data() { return own.empty() ? nullptr : own.data(); }   // the library's copy, writable (zr_scene_update_*); null for a view of the caller's memory
     const T* begin() const { return p; }
     const T* end() const { return p + n; }
 };

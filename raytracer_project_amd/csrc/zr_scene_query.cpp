@@ -20,6 +20,7 @@ int zr_scene_kernels(const zr_scene* s, uint32_t out[4]) {
 int zr_scene_tree_boxes(const zr_scene* s, zr_tree_box* out, size_t cap) {
     if (!s) return fail(ZR_E_INVALID, "null scene");
     if (!s->committed) return fail(ZR_E_STATE, "scene not committed");
+    if (s->stale) return fail(ZR_E_STATE, "scene updated but not refitted: zr_scene_refit must precede zr_scene_tree_boxes");
     if (cap && !out) return fail(ZR_E_INVALID, "null output array");
     HIP_OK(hipSetDevice(s->device));
     const size_t n_pairs = s->d_nodes.n;

@@ -291,6 +291,40 @@ int zrs_render_dropin_temporal(void* p, int width, int height, int spp, int devi
     return 0;
 }
 
+// A moving world through ONE drop-in camera object (camera::reuse_scene = reuse != 0): n_frames renders of a small world of the shim's own — a
+// ground sphere, a sphere that rises, and one shared cube placed twice — whose placements are moved the way reference code moves things: the same objects
+// under a translate and a rotate_y re-created with new arguments for every frame.  From frame add_at on (add_at < 0: never) the world holds one object more.
+// The handle supplies environment and seed; the camera looks at the shim's world.  out: n_frames frames of W*H*3 doubles (render_accumulator); refit: n_frames
+// ints, camera::last_scene_refit after each render.  Returns 0, or -1 if a render did not finish.
+int zrs_render_dropin_animated(void* p, int width, int height, int spp, int device, int n_frames, int reuse, int add_at, double* out, int* refit) {
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
+    cam.reuse_scene = reuse != 0;
+    cam.max_depth = 8; cam.vfov = 40; cam.defocus_angle = 0;
+    cam.lookfrom = point3(0.5, 2.5, 7); cam.lookat = point3(0.3, 0.4, 0); cam.vup = vec3(0, 1, 0);
+    const auto ground = make_shared<lambertian>(color(0.5, 0.6, 0.4)), red = make_shared<lambertian>(color(0.8, 0.2, 0.2)), blue = make_shared<lambertian>(color(0.2, 0.3, 0.8)),
+               white = make_shared<lambertian>(color(0.8, 0.8, 0.8));
+    const shared_ptr<hittable> box = make_shared<cube>(point3(-0.5, -0.5, -0.5), point3(0.5, 0.5, 0.5), red);   // the shared object
+    const post_processor post;
+    const size_t npx = (size_t)cam.image_width * cam.image_height;
+    for (int k = 0; k < n_frames; k++) {
+        hittable_list world;
+        world.add(make_shared<sphere>(point3(0, -100.5, 0), 100.0, ground));
+        world.add(make_shared<sphere>(point3(0.2, 0.3 + 0.15 * k, 1.5), 0.4, blue));
+        world.add(make_shared<translate>(make_shared<rotate_y>(box, 0.3 + 0.25 * k), vec3(-1.2 + 0.4 * k, 0.0, 0.0)));
+        world.add(make_shared<translate>(make_shared<rotate_y>(box, -0.2 * k), vec3(1.6, 0.2 * k, -1.0)));
+        if (add_at >= 0 && k >= add_at) world.add(make_shared<sphere>(point3(-1.5, 0.2, 2.0), 0.3, white));
+        const auto bvh_world = make_shared<bvh_node>(world);
+        cam.reset_accumulator();
+        std::atomic<bool> flag{true};
+        cam.render(*bvh_world, h.s.env, post, flag);
+        if (cam.lines_rendered.load() != cam.image_height) return -1;
+        if (out) std::memcpy(out + (size_t)k * npx * 3, cam.render_accumulator.data(), npx * sizeof(color));
+        if (refit) refit[k] = cam.last_scene_refit;
+    }
+    return 0;
+}
+
 // The reference's per-ray virtual API through the drop-in classes: for n rays (o, d, tmin, tmax) calls
 // bvh_node(world).hit(r, interval(tmin, tmax), rec), then rec.mat->emitted(...) and rec.mat->scatter(r, rec, att, scattered)
 // with random_double() positioned on the stream (seed, pixel, k) — the layout of `zenith_ref kat <scene> hits`:
