@@ -68,7 +68,21 @@ class Region(C.Structure):
                 ("tile_mod", C.c_int32), ("tile_rem", C.c_int32), ("tile_skew", C.c_int32)]
 
 
-class PostParams(C.Structure):
+class _Defaults:
+    """defaults(**kw) of a parameter struct: the class's _defaults_ in field order, then the fields named in kw (an unknown name raises AttributeError)"""
+    _defaults_ = ()
+
+    @classmethod
+    def defaults(cls, **kw):
+        p = cls(*cls._defaults_)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(f"{cls.__name__} has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+
+class PostParams(_Defaults, C.Structure):
     """zr_post_params: post_processor's fields (color_processing.hpp:46-75); defaults are the reference's"""
     _fields_ = [("exposure", C.c_float), ("saturation", C.c_float), ("contrast", C.c_float), ("hue_shift", C.c_float),
                 ("vignette_intensity", C.c_float), ("bloom_threshold", C.c_float), ("bloom_intensity", C.c_float), ("bloom_radius", C.c_int32),
@@ -76,95 +90,61 @@ class PostParams(C.Structure):
                 ("use_bloom", C.c_int32), ("use_sharpening", C.c_int32), ("debug_red", C.c_int32), ("debug_green", C.c_int32),
                 ("debug_blue", C.c_int32), ("debug_luminance", C.c_int32), ("debug_bvh", C.c_int32)]
 
+    _defaults_ = (0.5, 1.0, 1.0, 0.0, 1.0, 1.0, 0.3, 4, (1.0, 1.0, 1.0), 0.2, 0, 0, 0, 0, 0, 0, 0, 0)
+
     @classmethod
     def defaults(cls, **kw):
-        p = cls(0.5, 1.0, 1.0, 0.0, 1.0, 1.0, 0.3, 4, (C.c_double * 3)(1.0, 1.0, 1.0), 0.2, 0, 0, 0, 0, 0, 0, 0, 0)
-        for k, v in kw.items():
-            if k == "color_balance":
-                p.color_balance = (C.c_double * 3)(*v)
-            elif k == "debug":
-                p.debug_red, p.debug_green, p.debug_blue, p.debug_luminance, p.debug_bvh = [int(x) for x in v]
-            else:
-                setattr(p, k, v)
+        """color_balance takes any three numbers; debug=(red, green, blue, luminance, bvh) sets the five debug flags"""
+        debug = kw.pop("debug", None)
+        if "color_balance" in kw:
+            kw["color_balance"] = (C.c_double * 3)(*kw["color_balance"])
+        p = super().defaults(**kw)
+        if debug is not None:
+            p.debug_red, p.debug_green, p.debug_blue, p.debug_luminance, p.debug_bvh = [int(x) for x in debug]
         return p
 
 
-class DenoiseParams(C.Structure):
+class DenoiseParams(_Defaults, C.Structure):
     """zr_denoise_params: the a-trous denoiser behind camera::use_denoiser (not OIDN; include/zr_capi.h)"""
     _fields_ = [("iterations", C.c_int32), ("demodulate_albedo", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
 
-    @classmethod
-    def defaults(cls, **kw):
-        """ZR_DENOISE_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses); depth guide off"""
-        p = cls(5, 0, 1.5, 64.0, 0.25, 0.0)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise AttributeError(f"DenoiseParams has no field {k!r}")
-            setattr(p, k, v)
-        return p
+    # defaults(): ZR_DENOISE_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses); depth guide off
+    _defaults_ = (5, 0, 1.5, 64.0, 0.25, 0.0)
 
 
-class DenoiseGuidedParams(C.Structure):
+class DenoiseGuidedParams(_Defaults, C.Structure):
     """zr_denoise_guided_params: the variance-guided form of the a-trous denoiser (include/zr_capi.h)"""
     _fields_ = [("iterations", C.c_int32), ("demodulate_albedo", C.c_int32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float), ("epsilon", C.c_float)]
 
-    @classmethod
-    def defaults(cls, **kw):
-        """ZR_DENOISE_GUIDED_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with denoise_variance_guided); depth guide off"""
-        p = cls(4, 1, 3.0, 64.0, 0.25, 0.0, 1e-8)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise AttributeError(f"DenoiseGuidedParams has no field {k!r}")
-            setattr(p, k, v)
-        return p
+    # defaults(): ZR_DENOISE_GUIDED_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with denoise_variance_guided); depth guide off
+    _defaults_ = (4, 1, 3.0, 64.0, 0.25, 0.0, 1e-8)
 
 
-class DenoiseNlmParams(C.Structure):
+class DenoiseNlmParams(_Defaults, C.Structure):
     """zr_denoise_nlm_params: the dual-buffer non-local-means denoiser (include/zr_capi.h)"""
     _fields_ = [("search_radius", C.c_int32), ("patch_radius", C.c_int32), ("demodulate_albedo", C.c_int32), ("pad_", C.c_int32), ("k", C.c_float),
                 ("alpha", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("epsilon", C.c_float)]
 
-    @classmethod
-    def defaults(cls, **kw):
-        """ZR_DENOISE_NLM_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with denoise_nlm)"""
-        p = cls(7, 1, 0, 0, 0.7, 1.0, 64.0, 0.25, 1e-10)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise AttributeError(f"DenoiseNlmParams has no field {k!r}")
-            setattr(p, k, v)
-        return p
+    # defaults(): ZR_DENOISE_NLM_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with denoise_nlm)
+    _defaults_ = (7, 1, 0, 0, 0.7, 1.0, 64.0, 0.25, 1e-10)
 
 
-class TemporalParams(C.Structure):
+class TemporalParams(_Defaults, C.Structure):
     """zr_temporal_params: how a frame's history is reprojected and blended (include/zr_capi.h)"""
     _fields_ = [("alpha", C.c_double), ("max_history", C.c_int32), ("pad_", C.c_int32), ("plane_tolerance", C.c_double), ("normal_cos", C.c_double)]
 
-    @classmethod
-    def defaults(cls, **kw):
-        """ZR_TEMPORAL_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with temporal_accumulation)"""
-        p = cls(0.4, 32, 0, 0.03, 0.9)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise AttributeError(f"TemporalParams has no field {k!r}")
-            setattr(p, k, v)
-        return p
+    # defaults(): ZR_TEMPORAL_DEFAULT_* of include/zr_capi.h (what the drop-in's camera::render uses with temporal_accumulation)
+    _defaults_ = (0.4, 32, 0, 0.03, 0.9)
 
 
-class BvhDebugParams(C.Structure):
+class BvhDebugParams(_Defaults, C.Structure):
     """zr_bvh_debug_params: global_settings::debug_bvh_level / bvh_thickness of the BVH debug view (include/zr_capi.h, DESIGN §10)"""
     _fields_ = [("level", C.c_int32), ("thickness", C.c_float)]
 
-    @classmethod
-    def defaults(cls, **kw):
-        """ZR_BVH_DEBUG_DEFAULT_LEVEL / _THICKNESS (the reference's global_settings defaults: leaves, 0.01)"""
-        p = cls(-1, 0.01)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise AttributeError(f"BvhDebugParams has no field {k!r}")
-            setattr(p, k, v)
-        return p
+    # defaults(): ZR_BVH_DEBUG_DEFAULT_LEVEL / _THICKNESS (the reference's global_settings defaults: leaves, 0.01)
+    _defaults_ = (-1, 0.01)
 
 
 BVH_MISS, BVH_EDGE, BVH_VOLUME, BVH_SURFACE = 0, 1, 2, 3
@@ -194,19 +174,12 @@ class Counters(C.Structure):
                 + 48 * self.cubes_tested + 76 * self.hits)
 
 
-class AdaptiveParams(C.Structure):
+class AdaptiveParams(_Defaults, C.Structure):
     """zr_adaptive_params: the three counts are positive multiples of 64; a pixel goes on while err > threshold"""
     _fields_ = [("min_samples", C.c_int32), ("max_samples", C.c_int32), ("step_samples", C.c_int32), ("pad_", C.c_int32),
                 ("threshold", C.c_double), ("dark_floor", C.c_double)]
 
-    @classmethod
-    def defaults(cls, **kw):
-        p = cls(64, 512, 64, 0, 0.02, 0.01)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise AttributeError(k)
-            setattr(p, k, v)
-        return p
+    _defaults_ = (64, 512, 64, 0, 0.02, 0.01)
 
 
 class AdaptiveStats(C.Structure):
@@ -431,6 +404,23 @@ def _check(rc, allow_cancel=False):
     raise ZrError(f"zr error {rc}: {load().zr_last_error().decode()}")
 
 
+def _like(shape, what, frames=(), outs=(), dtype=np.float64):
+    """Frames like this one: `frames` as contiguous float64 arrays of `shape` (None stays None; another shape raises ValueError naming `what`), then one
+    output per entry of `outs`, made (zeroed, of `dtype`) where it is None and otherwise asserted to be a contiguous `dtype` array of `shape`"""
+    frames = [np.ascontiguousarray(f, dtype=np.float64) if f is not None else None for f in frames]
+    for f in frames:
+        if f is not None and f.shape != shape:
+            raise ValueError(f"frame shape {f.shape} differs from {what} {shape}")
+    outs = [np.zeros(shape, dtype=dtype) if o is None else o for o in outs]
+    for o in outs:
+        assert o.dtype == dtype and o.flags.c_contiguous and o.shape == shape
+    return frames + outs
+
+
+def _ptr(a):
+    return a.ctypes.data if a is not None else None
+
+
 class DemoScene:
     """One of the BASELINE.json scenes, built through the drop-in C++ scene API and flattened."""
 
@@ -449,11 +439,14 @@ class DemoScene:
         ids = (C.c_uint32 * 64)()
         self.kat_textures = [int(ids[k]) for k in range(min(64, s.zrs_kat_textures(self._h, ids, 64)))]
 
-    def _frames(self, width, height, *names):
-        """zeroed (H, W, 3) float64 outputs by name for a drop-in render at width x height (0: the scene's own)"""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        return {k: np.zeros((h, w, 3), dtype=np.float64) for k in names}
+    def _size(self, width, height):
+        """(H, W) of a drop-in render at width x height (0: the scene's own)"""
+        return height or self.camera.image_height, width or self.camera.image_width
+
+    def _frames(self, width, height, *names, n=0):
+        """zeroed (H, W, 3) float64 outputs by name for a drop-in render at width x height; n > 0: (n, H, W, 3), a frame per render"""
+        shape = ((n,) if n else ()) + self._size(width, height) + (3,)
+        return {k: np.zeros(shape, dtype=np.float64) for k in names}
 
     @staticmethod
     def _rendered(ok):
@@ -536,11 +529,9 @@ class DemoScene:
         samples_per_pass > 0 else one-shot.  Dict of render_accumulator, temporal_buffer, variance_buffer, denoise_buffer ((n, H, W, 3) float64; a frame
         that left the buffer empty is all -1) and temporal_history_length ((n, H, W) int32, -1 likewise)"""
         n = len(cameras)
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
         cams = np.array([list(c.lookfrom) + list(c.lookat) for c in cameras], dtype=np.float64)
-        outs = {k: np.zeros((n, h, w, 3), dtype=np.float64) for k in ("render_accumulator", "temporal_buffer", "variance_buffer", "denoise_buffer")}
-        outs["temporal_history_length"] = np.zeros((n, h, w), dtype=np.int32)
+        outs = self._frames(width, height, "render_accumulator", "temporal_buffer", "variance_buffer", "denoise_buffer", n=n)
+        outs["temporal_history_length"] = np.zeros((n, *self._size(width, height)), dtype=np.int32)
         flags = (1 if temporal else 0) | (2 if guided else 0) | (4 if reset_before_last else 0)
         self._rendered(load_scenes().zrs_render_dropin_temporal(self._h, width, height, spp, device, n, cams.ctypes.data, flags, int(samples_per_pass),
                                                                 *[o.ctypes.data for o in outs.values()]) == 0)
@@ -558,9 +549,7 @@ class DemoScene:
         """n_frames renders of the shim's small moving world through ONE drop-in camera object with camera::reuse_scene = reuse_scene: one translate and
         one rotate_y re-created around a shared cube with new arguments for every frame, a sphere that rises, and from frame add_at on (-1: never) one
         object more.  Returns (frames (n, H, W, 3) float64, camera::last_scene_refit after each render as a list: 0 committed, 1 refitted)"""
-        w = width or self.camera.image_width
-        h = height or self.camera.image_height
-        out = np.zeros((n_frames, h, w, 3), dtype=np.float64)
+        out = self._frames(width, height, "out", n=n_frames)["out"]
         refit = (C.c_int * n_frames)()
         self._rendered(load_scenes().zrs_render_dropin_animated(self._h, width, height, spp, device, int(n_frames), 1 if reuse_scene else 0, int(add_at),
                                                                 out.ctypes.data, refit) == 0)
@@ -635,17 +624,8 @@ class Context:
         `out` may be `color` itself (in place)."""
         color = np.ascontiguousarray(color, dtype=np.float64)
         h, w = color.shape[:2]
-        guides = [np.ascontiguousarray(g, dtype=np.float64) for g in (albedo, normal)]
-        if zdepth is not None:
-            zdepth = np.ascontiguousarray(zdepth, dtype=np.float64)
-        for g in guides + ([zdepth] if zdepth is not None else []):
-            if g.shape != color.shape:
-                raise ValueError(f"guide shape {g.shape} differs from the colour frame's {color.shape}")
-        if out is None:
-            out = np.zeros_like(color)
-        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == color.shape
-        _check(self.lib.zr_denoise(self._c, C.byref(params), color.ctypes.data, guides[0].ctypes.data, guides[1].ctypes.data,
-                                   zdepth.ctypes.data if zdepth is not None else None, w, h, out.ctypes.data))
+        albedo, normal, zdepth, out = _like(color.shape, "the colour frame's", (albedo, normal, zdepth), (out,))
+        _check(self.lib.zr_denoise(self._c, C.byref(params), color.ctypes.data, albedo.ctypes.data, normal.ctypes.data, _ptr(zdepth), w, h, out.ctypes.data))
         return out
 
     def denoise_guided(self, params, color, variance, albedo, normal, zdepth=None, out=None, out_variance=None):
@@ -653,20 +633,9 @@ class Context:
         (H, W, 3) float64.  `out` may be `color` itself and `out_variance` may be `variance` itself (in place)."""
         color = np.ascontiguousarray(color, dtype=np.float64)
         h, w = color.shape[:2]
-        frames = [np.ascontiguousarray(g, dtype=np.float64) for g in (variance, albedo, normal)]
-        if zdepth is not None:
-            zdepth = np.ascontiguousarray(zdepth, dtype=np.float64)
-        for g in frames + ([zdepth] if zdepth is not None else []):
-            if g.shape != color.shape:
-                raise ValueError(f"frame shape {g.shape} differs from the colour frame's {color.shape}")
-        if out is None:
-            out = np.zeros_like(color)
-        if out_variance is None:
-            out_variance = np.zeros_like(color)
-        for o in (out, out_variance):
-            assert o.dtype == np.float64 and o.flags.c_contiguous and o.shape == color.shape
-        _check(self.lib.zr_denoise_guided(self._c, C.byref(params), color.ctypes.data, frames[0].ctypes.data, frames[1].ctypes.data, frames[2].ctypes.data,
-                                          zdepth.ctypes.data if zdepth is not None else None, w, h, out.ctypes.data, out_variance.ctypes.data))
+        variance, albedo, normal, zdepth, out, out_variance = _like(color.shape, "the colour frame's", (variance, albedo, normal, zdepth), (out, out_variance))
+        _check(self.lib.zr_denoise_guided(self._c, C.byref(params), color.ctypes.data, variance.ctypes.data, albedo.ctypes.data, normal.ctypes.data,
+                                          _ptr(zdepth), w, h, out.ctypes.data, out_variance.ctypes.data))
         return out, out_variance
 
     def denoise_nlm(self, params, half_a, half_b, variance, albedo, normal, out=None, out_error=None):
@@ -674,16 +643,7 @@ class Context:
         (H, W, 3) float64; `variance` is the variance of the full pixel mean.  `out` may be `half_a` itself (in place)."""
         half_a = np.ascontiguousarray(half_a, dtype=np.float64)
         h, w = half_a.shape[:2]
-        frames = [np.ascontiguousarray(g, dtype=np.float64) for g in (half_b, variance, albedo, normal)]
-        for g in frames:
-            if g.shape != half_a.shape:
-                raise ValueError(f"frame shape {g.shape} differs from the first half's {half_a.shape}")
-        if out is None:
-            out = np.zeros_like(half_a)
-        if out_error is None:
-            out_error = np.zeros_like(half_a)
-        for o in (out, out_error):
-            assert o.dtype == np.float64 and o.flags.c_contiguous and o.shape == half_a.shape
+        *frames, out, out_error = _like(half_a.shape, "the first half's", (half_b, variance, albedo, normal), (out, out_error))
         _check(self.lib.zr_denoise_nlm(self._c, C.byref(params), half_a.ctypes.data, *[g.ctypes.data for g in frames], w, h, out.ctypes.data,
                                        out_error.ctypes.data))
         return out, out_error
@@ -692,9 +652,7 @@ class Context:
         """post_processor::apply_sharpening on the device: (H, W, 3) float64 -> (H, W, 3) float64"""
         frame = np.ascontiguousarray(frame, dtype=np.float64)
         h, w = frame.shape[:2]
-        if out is None:
-            out = np.zeros_like(frame)
-        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == frame.shape
+        out, = _like(frame.shape, "the frame's", outs=(out,))
         _check(self.lib.zr_sharpen_frame(self._c, frame.ctypes.data, w, h, C.c_double(amount), out.ctypes.data))
         return out
 
@@ -740,6 +698,9 @@ class Accumulator:
         if not self._a:
             raise ZrError(self.lib.zr_last_error().decode())
 
+    def _like(self, frames=(), outs=()):
+        return _like((self.height, self.width, 3), "the accumulator's frame", frames, outs)
+
     def accumulate(self, scene, camera, env, seed, n_samples, count=False, keep_going=None):
         """renders the next n_samples samples of every pixel and adds them (camera.samples_per_pixel is ignored); keep_going: a
         ctypes.c_uint8 polled like zr_render's — a cancelled batch raises nothing, returns ZR_E_CANCELLED and leaves the accumulator as it was"""
@@ -749,9 +710,7 @@ class Accumulator:
 
     def resolve(self, out=None):
         """the mean of the samples accumulated so far: (H, W, 3) float64; only the region's pixels of `out` are written"""
-        if out is None:
-            out = np.zeros((self.height, self.width, 3), dtype=np.float64)
-        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.height, self.width, 3)
+        out, = self._like(outs=(out,))
         _check(self.lib.zr_accum_resolve(self._a, out.ctypes.data))
         return out
 
@@ -770,56 +729,35 @@ class Accumulator:
 
     def error(self, dark_floor=0.01, out=None):
         """the noise estimate of the sums held (relative standard error of the pixel mean): (H, W) float64; only the region's pixels are written"""
-        if out is None:
-            out = np.zeros((self.height, self.width), dtype=np.float64)
-        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.height, self.width)
+        out, = _like((self.height, self.width), "the accumulator's plane", outs=(out,))
         _check(self.lib.zr_accum_error(self._a, C.c_double(dark_floor), out.ctypes.data))
         return out
 
     def variance(self, out=None):
         """the variance of every pixel's mean per channel (zr_accum_variance): (H, W, 3) float64; only the region's pixels are written"""
-        if out is None:
-            out = np.zeros((self.height, self.width, 3), dtype=np.float64)
-        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (self.height, self.width, 3)
+        out, = self._like(outs=(out,))
         _check(self.lib.zr_accum_variance(self._a, out.ctypes.data))
         return out
 
     def denoise(self, params, albedo, normal, zdepth=None):
         """zr_accum_denoise: Context.denoise_guided(params, resolve(), variance(), ...) bit for bit, with colour and variance resolved on the device;
         returns (frame, variance).  Whole-frame accumulators only."""
-        shape = (self.height, self.width, 3)
-        guides = [np.ascontiguousarray(g, dtype=np.float64) for g in (albedo, normal)]
-        if zdepth is not None:
-            zdepth = np.ascontiguousarray(zdepth, dtype=np.float64)
-        for g in guides + ([zdepth] if zdepth is not None else []):
-            if g.shape != shape:
-                raise ValueError(f"guide shape {g.shape} differs from the accumulator's frame {shape}")
-        out = np.zeros(shape, dtype=np.float64); out_variance = np.zeros(shape, dtype=np.float64)
-        _check(self.lib.zr_accum_denoise(self._a, C.byref(params), guides[0].ctypes.data, guides[1].ctypes.data,
-                                         zdepth.ctypes.data if zdepth is not None else None, out.ctypes.data, out_variance.ctypes.data))
+        albedo, normal, zdepth, out, out_variance = self._like((albedo, normal, zdepth), (None, None))
+        _check(self.lib.zr_accum_denoise(self._a, C.byref(params), albedo.ctypes.data, normal.ctypes.data, _ptr(zdepth), out.ctypes.data, out_variance.ctypes.data))
         return out, out_variance
 
     def halves(self, out_a=None, out_b=None):
         """the two half images (zr_accum_halves: the means of the even and of the odd lanes' samples): two (H, W, 3) float64; only the region's pixels
         are written"""
-        shape = (self.height, self.width, 3)
-        out_a = np.zeros(shape, dtype=np.float64) if out_a is None else out_a
-        out_b = np.zeros(shape, dtype=np.float64) if out_b is None else out_b
-        for o in (out_a, out_b):
-            assert o.dtype == np.float64 and o.flags.c_contiguous and o.shape == shape
+        out_a, out_b = self._like(outs=(out_a, out_b))
         _check(self.lib.zr_accum_halves(self._a, out_a.ctypes.data, out_b.ctypes.data))
         return out_a, out_b
 
     def denoise_nlm(self, params, albedo, normal):
         """zr_accum_denoise_nlm: Context.denoise_nlm(params, *halves(), variance(), ...) bit for bit, with halves and variance resolved on the device;
         returns (frame, error).  Whole-frame accumulators only."""
-        shape = (self.height, self.width, 3)
-        guides = [np.ascontiguousarray(g, dtype=np.float64) for g in (albedo, normal)]
-        for g in guides:
-            if g.shape != shape:
-                raise ValueError(f"guide shape {g.shape} differs from the accumulator's frame {shape}")
-        out = np.zeros(shape, dtype=np.float64); out_error = np.zeros(shape, dtype=np.float64)
-        _check(self.lib.zr_accum_denoise_nlm(self._a, C.byref(params), guides[0].ctypes.data, guides[1].ctypes.data, out.ctypes.data, out_error.ctypes.data))
+        albedo, normal, out, out_error = self._like((albedo, normal), (None, None))
+        _check(self.lib.zr_accum_denoise_nlm(self._a, C.byref(params), albedo.ctypes.data, normal.ctypes.data, out.ctypes.data, out_error.ctypes.data))
         return out, out_error
 
     def temporal(self, history, scene, camera, seed, params=None):

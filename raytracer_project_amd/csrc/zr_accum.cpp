@@ -164,6 +164,22 @@ int variance_ready(const AccumState& st, const char* entry) {   // zr_accum_vari
     return rc ? rc : whole_lanes(st, "the variance");
 }
 
+// What zr_accum_denoise, zr_accum_denoise_nlm and zr_accum_temporal share once their arguments have passed.  whole_frame: `entry` `does` whole frames only;
+// device_frames: what the entry works on, made on the context's stream — d_a the mean, or with d_b the two halves, and d_v the variance of the mean (a
+// whole-frame plan: the kernels write every pixel of the frames)
+int whole_frame(const AccumState& st, const char* entry, const char* does) {
+    return st.plan.whole() ? ZR_OK : fail(ZR_E_INVALID, "%s %s whole frames: the accumulator was made with a region", entry, does);
+}
+int device_frames(const AccumState& st, DevBuf<double>& d_a, DevBuf<double>* d_b, DevBuf<double>& d_v) {
+    HIP_OK(hipSetDevice(st.device));
+    const size_t n = st.plan.npx() * 3;
+    const hipStream_t stream = st.ctx->stream;
+    int rc;
+    if ((rc = d_a.alloc(n)) || (d_b && (rc = d_b->alloc(n))) || (rc = d_v.alloc(n))) return rc;
+    if ((rc = d_b ? accum_halves_into(st, d_a.p, d_b->p, stream) : accum_resolve_into(st, d_a.p, stream))) return rc;
+    return accum_variance_into(st, d_v.p, stream);
+}
+
 // a frame-shaped query (the mean, the variance): `into` runs on the null stream into a device frame of which only the plan's pixels are written, and only they are copied out
 int query_frame(const AccumState& st, int (*into)(const AccumState&, double*, hipStream_t), double* out) {
     HIP_OK(hipSetDevice(st.device));
@@ -449,15 +465,9 @@ int zr_accum_denoise(zr_accum* a, const zr_denoise_guided_params* dp, const doub
     int rc = check_guided_params(dp);
     if (rc) return rc;
     AccumState& st = a->st;
-    if (!st.plan.whole()) return fail(ZR_E_INVALID, "zr_accum_denoise filters whole frames: the accumulator was made with a region");
-    if ((rc = variance_ready(st, "zr_accum_denoise"))) return rc;
-    zr_ctx* c = st.ctx;
-    HIP_OK(hipSetDevice(st.device));
     DevBuf<double> d_c, d_v;
-    if ((rc = d_c.alloc(st.plan.npx() * 3)) || (rc = d_v.alloc(st.plan.npx() * 3))) return rc;
-    // a whole-frame plan: the two kernels write every pixel of the two frames
-    if ((rc = accum_resolve_into(st, d_c.p, c->stream)) || (rc = accum_variance_into(st, d_v.p, c->stream))) return rc;
-    return denoise_guided_device(c, dp, d_c, d_v, albedo, normal, zdepth, st.plan.W, st.plan.H, out, out_variance);
+    if ((rc = whole_frame(st, "zr_accum_denoise", "filters")) || (rc = variance_ready(st, "zr_accum_denoise")) || (rc = device_frames(st, d_c, nullptr, d_v))) return rc;
+    return denoise_guided_device(st.ctx, dp, d_c, d_v, albedo, normal, zdepth, st.plan.W, st.plan.H, out, out_variance);
 }
 
 // non-local-means denoising of what an accumulator holds (the filter itself: zr_image.cpp)
@@ -467,15 +477,9 @@ int zr_accum_denoise_nlm(zr_accum* a, const zr_denoise_nlm_params* dp, const dou
     if (rc) return rc;
     if (!a || !albedo || !normal || !out) return fail(ZR_E_INVALID, "null argument");
     AccumState& st = a->st;
-    if (!st.plan.whole()) return fail(ZR_E_INVALID, "zr_accum_denoise_nlm filters whole frames: the accumulator was made with a region");
-    if ((rc = variance_ready(st, "zr_accum_denoise_nlm"))) return rc;
-    zr_ctx* c = st.ctx;
-    HIP_OK(hipSetDevice(st.device));
     DevBuf<double> d_a, d_b, d_v;
-    if ((rc = d_a.alloc(st.plan.npx() * 3)) || (rc = d_b.alloc(st.plan.npx() * 3)) || (rc = d_v.alloc(st.plan.npx() * 3))) return rc;
-    // a whole-frame plan: the two kernels write every pixel of the three frames
-    if ((rc = accum_halves_into(st, d_a.p, d_b.p, c->stream)) || (rc = accum_variance_into(st, d_v.p, c->stream))) return rc;
-    return denoise_nlm_device(c, dp, d_a, d_b, d_v, albedo, normal, st.plan.W, st.plan.H, out, out_error);
+    if ((rc = whole_frame(st, "zr_accum_denoise_nlm", "filters")) || (rc = variance_ready(st, "zr_accum_denoise_nlm")) || (rc = device_frames(st, d_a, &d_b, d_v))) return rc;
+    return denoise_nlm_device(st.ctx, dp, d_a, d_b, d_v, albedo, normal, st.plan.W, st.plan.H, out, out_error);
 }
 
 // what an accumulator holds taken into a history (the reprojection itself: zr_temporal.cpp)
@@ -486,17 +490,13 @@ int zr_accum_temporal(zr_accum* a, zr_temporal* t, const zr_temporal_params* p, 
     if (rc) return rc;
     if (!a || !t || !s || !cam) return fail(ZR_E_INVALID, "null argument");
     AccumState& st = a->st;
-    if (!st.plan.whole()) return fail(ZR_E_INVALID, "zr_accum_temporal takes whole frames: the accumulator was made with a region");
-    if ((rc = temporal_call_ready(t, st.ctx, s, cam, "zr_accum_temporal")) || (rc = variance_ready(st, "zr_accum_temporal"))) return rc;
+    if ((rc = whole_frame(st, "zr_accum_temporal", "takes")) || (rc = temporal_call_ready(t, st.ctx, s, cam, "zr_accum_temporal")) ||
+        (rc = variance_ready(st, "zr_accum_temporal"))) return rc;
     int64_t shape[4];
     (void)zr_temporal_state(t, shape);
     if (shape[0] != st.plan.W || shape[1] != st.plan.H) return fail(ZR_E_INVALID, "accumulator of %d x %d px, history of %d x %d", st.plan.W, st.plan.H, (int)shape[0], (int)shape[1]);
-    zr_ctx* c = st.ctx;
-    HIP_OK(hipSetDevice(st.device));
     DevBuf<double> d_c, d_v;
-    if ((rc = d_c.alloc(st.plan.npx() * 3)) || (rc = d_v.alloc(st.plan.npx() * 3))) return rc;
-    // a whole-frame plan: the two kernels write every pixel of the two frames
-    if ((rc = accum_resolve_into(st, d_c.p, c->stream)) || (rc = accum_variance_into(st, d_v.p, c->stream))) return rc;
+    if ((rc = device_frames(st, d_c, nullptr, d_v))) return rc;
     return temporal_accumulate_device(t, p, s, cam, seed, d_c.p, d_v.p, out_color, out_variance, out_history);
 }
 

@@ -4,17 +4,18 @@
 // computed from one half filter the other.  FP32, compiled with -ffp-contract=off, no atomics, a fixed evaluation order: tests/denoise_nlm_model.py restates
 // it operation for operation; only expf / exp2f / log2f differ from NumPy's (an ulp or two).
 //
-//   nlm_pack     per pixel: cleaning, normal decoding and the albedo divisor a' exactly as denoise_pack (zr_denoise.hip); uA = clean(A) / a',
-//                uB = clean(B) / a', Vh = 2 max(clean(variance), 0) / (a' a') (a half holds half the samples: twice the variance of the full mean)
-//   nlm_smooth   V^ = the 3 x 3 Gaussian of Vh per channel, guided_atrous's stencil rules: g = g1(kx) g1(ky), g1 = 1/4, 1/2, 1/4, ky outer / kx inner, taps off
-//                the frame skipped, gs = sum g Vh_k, gw = sum g, V^ = gs / gw
+//   nlm_pack     per pixel: cleaning, normal decoding and the albedo divisor a' are denoise_pack's, by the same helpers (zr_filter.h: clean, decode_normal,
+//                albedo_divisor); uA = clean(A) / a', uB = clean(B) / a', Vh = 2 max(clean(variance), 0) / (a' a') (a half holds half the samples: twice the
+//                variance of the full mean)
+//   nlm_smooth   V^ = the 3 x 3 Gaussian of Vh per channel, guided_atrous's stencil (zr_filter.h: gauss3x3): g = g1(kx) g1(ky), g1 = 1/4, 1/2, 1/4, ky outer /
+//                kx inner, taps off the frame skipped, gs = sum g Vh_k, gw = sum g, V^ = gs / gw
 //   nlm_filter   with clamp() moving a coordinate to the nearest frame pixel, for every offset D = (dx, dy) in [-r, r]^2, dy outer / dx inner:
 //                  e_D(s)  = e(s, clamp(s + D)), per buffer u in {uA, uB};  per channel c with vs = V^_s.c, vt = V^_t.c
 //                            canc = alpha (vs + min(vt, vs)),  id = 1 / (eps + kk (vs + vt)),  kk = k k taken on the host,
 //                            delta_c = ((u_s.c - u_t.c)^2 - canc) id;   e = ((delta_x + delta_y) + delta_z) (1/3)
 //                  D_D(p)  = (sum of e_D(clamp(p + tau)) over tau in [-f, f]^2, tau_y outer / tau_x inner, from 0) inv_np,  inv_np = 1 / (2f + 1)^2 taken on the host
 //                  w_u     = exp(-(max(D_D(p), 0) + |a_p - a_q|^2 inv_a)) w_n  for q = p + D inside the frame (no weight outside), inv_a = 1 / sigma_a^2 and
-//                            w_n = exp2(sigma_n log2(max(0, n_p . n_q))) (1 when either normal is 0) as in denoise_atrous; the centre tap's weight is 1
+//                            w_n = exp2(sigma_n log2(max(0, n_p . n_q))) (1 when either normal is 0), denoise_atrous's (zr_filter.h: normal_weight); the centre tap's weight is 1
 //                  fB = sum w_uA uB_q / sum w_uA,  fA = sum w_uB uA_q / sum w_uB
 //                out = ((fA + fB) 0.5) a',  out_error = (((fA - fB) 0.5) a')^2, widened to double
 // As evaluated (the formula of DESIGN §16 up to FP32 rounding): canc and id depend on the variances alone and serve both buffers, so a pair of pixels costs
@@ -31,6 +32,7 @@
 #include <cstdint>
 
 #include "../../include/zr_capi.h"
+#include "zr_filter.h"
 
 namespace zr {
 
@@ -49,53 +51,30 @@ struct NlmArgs {
     float inv_np;     // 1 / (2f + 1)^2
 };
 
-__device__ __forceinline__ float clean(double v) {   // as zr_denoise.hip
-    const float f = (float)v;
-    return isfinite(f) ? f : 0.0f;
-}
-
 __global__ __launch_bounds__(256) void nlm_pack(const double* __restrict__ half_a, const double* __restrict__ half_b, const double* __restrict__ variance,
                                                 const double* __restrict__ albedo, const double* __restrict__ normal, int W, int H, int demodulate,
                                                 float4* __restrict__ uA, float4* __restrict__ uB, float4* __restrict__ Vh, float4* __restrict__ g0,
                                                 float4* __restrict__ g1) {
-    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
-    if (i >= W || j >= H) return;
-    const size_t p = (size_t)j * W + i;
-    const float ax = clean(albedo[3 * p]), ay = clean(albedo[3 * p + 1]), az = clean(albedo[3 * p + 2]);
-    float mx = 2.0f * clean(normal[3 * p]) - 1.0f, my = 2.0f * clean(normal[3 * p + 1]) - 1.0f, mz = 2.0f * clean(normal[3 * p + 2]) - 1.0f;
-    const float len = sqrtf(mx * mx + my * my + mz * mz);
-    float valid = 1.0f;
-    if (len < 1e-6f) { mx = my = mz = 0.0f; valid = 0.0f; }
-    else { mx = mx / len; my = my / len; mz = mz / len; }
-    float dx = demodulate && ax > 1e-3f ? ax : 1.0f, dy = demodulate && ay > 1e-3f ? ay : 1.0f, dz = demodulate && az > 1e-3f ? az : 1.0f;
-    uA[p] = make_float4(clean(half_a[3 * p]) / dx, clean(half_a[3 * p + 1]) / dy, clean(half_a[3 * p + 2]) / dz, 0.0f);
-    uB[p] = make_float4(clean(half_b[3 * p]) / dx, clean(half_b[3 * p + 1]) / dy, clean(half_b[3 * p + 2]) / dz, 0.0f);
+    ZR_PIXEL16(W, H, i, j, p);
+    const float4 a = make_float4(clean(albedo[3 * p]), clean(albedo[3 * p + 1]), clean(albedo[3 * p + 2]), 0.0f);
+    const float4 n = decode_normal(clean(normal[3 * p]), clean(normal[3 * p + 1]), clean(normal[3 * p + 2]));
+    const float3 m = albedo_divisor(a, demodulate);
+    uA[p] = make_float4(clean(half_a[3 * p]) / m.x, clean(half_a[3 * p + 1]) / m.y, clean(half_a[3 * p + 2]) / m.z, 0.0f);
+    uB[p] = make_float4(clean(half_b[3 * p]) / m.x, clean(half_b[3 * p + 1]) / m.y, clean(half_b[3 * p + 2]) / m.z, 0.0f);
     const float vx = fmaxf(clean(variance[3 * p]), 0.0f), vy = fmaxf(clean(variance[3 * p + 1]), 0.0f), vz = fmaxf(clean(variance[3 * p + 2]), 0.0f);
-    Vh[p] = make_float4(2.0f * vx / (dx * dx), 2.0f * vy / (dy * dy), 2.0f * vz / (dz * dz), 0.0f);
-    g0[p] = make_float4(ax, ay, az, 0.0f);
-    g1[p] = make_float4(mx, my, mz, valid);
+    Vh[p] = make_float4(2.0f * vx / (m.x * m.x), 2.0f * vy / (m.y * m.y), 2.0f * vz / (m.z * m.z), 0.0f);
+    g0[p] = a;
+    g1[p] = n;
 }
 
 __global__ __launch_bounds__(256) void nlm_smooth(const float4* __restrict__ Vh, int W, int H, float4* __restrict__ Vs) {
-    const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
-    if (i >= W || j >= H) return;
-    const float g[3] = {1.0f / 4.0f, 1.0f / 2.0f, 1.0f / 4.0f};
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, gw = 0.0f;
-#pragma unroll
-    for (int ky = -1; ky <= 1; ky++) {
-        const int qj = j + ky;
-        if (qj < 0 || qj >= H) continue;
-#pragma unroll
-        for (int kx = -1; kx <= 1; kx++) {
-            const int qi = i + kx;
-            if (qi < 0 || qi >= W) continue;
-            const float gk = g[kx + 1] * g[ky + 1];
-            const float4 v = Vh[(size_t)qj * W + qi];
-            sx = sx + gk * v.x; sy = sy + gk * v.y; sz = sz + gk * v.z;
-            gw = gw + gk;
-        }
-    }
-    Vs[(size_t)j * W + i] = make_float4(sx / gw, sy / gw, sz / gw, 0.0f);
+    ZR_PIXEL16(W, H, i, j, p);
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    const float gw = gauss3x3(i, j, W, H, [&](float gk, size_t q) {
+        const float4 v = Vh[q];
+        sx = sx + gk * v.x; sy = sy + gk * v.y; sz = sz + gk * v.z;
+    });
+    Vs[p] = make_float4(sx / gw, sy / gw, sz / gw, 0.0f);
 }
 
 // one channel of the pixel distance of both buffers: x = buffer A's delta, y = buffer B's
@@ -186,8 +165,7 @@ __global__ __launch_bounds__(256) void nlm_filter(const float4* __restrict__ uA,
                     const float4 aq = g0[q], nq = g1[q];
                     const float cx = ap.x - aq.x, cy = ap.y - aq.y, cz = ap.z - aq.z;
                     const float arg_a = (cx * cx + cy * cy + cz * cz) * inv_a;
-                    float wn = 1.0f;
-                    if (np.w != 0.0f && nq.w != 0.0f) wn = exp2f(sigma_n * log2f(fmaxf(0.0f, np.x * nq.x + np.y * nq.y + np.z * nq.z)));
+                    const float wn = normal_weight(np, nq, sigma_n);
                     wa = expf(-(fmaxf(da, 0.0f) + arg_a)) * wn;
                     wb = expf(-(fmaxf(db, 0.0f) + arg_a)) * wn;
                 }
@@ -201,10 +179,10 @@ __global__ __launch_bounds__(256) void nlm_filter(const float4* __restrict__ uA,
     }
     if (!live) return;
     const float fax = ax / aw, fay = ay / aw, faz = az / aw, fbx = bx / bw, fby = by / bw, fbz = bz / bw;
-    const float mx = a.demodulate && ap.x > 1e-3f ? ap.x : 1.0f, my = a.demodulate && ap.y > 1e-3f ? ap.y : 1.0f, mz = a.demodulate && ap.z > 1e-3f ? ap.z : 1.0f;
-    out[3 * p] = (double)(((fax + fbx) * 0.5f) * mx); out[3 * p + 1] = (double)(((fay + fby) * 0.5f) * my); out[3 * p + 2] = (double)(((faz + fbz) * 0.5f) * mz);
+    const float3 m = albedo_divisor(ap, a.demodulate);
+    out[3 * p] = (double)(((fax + fbx) * 0.5f) * m.x); out[3 * p + 1] = (double)(((fay + fby) * 0.5f) * m.y); out[3 * p + 2] = (double)(((faz + fbz) * 0.5f) * m.z);
     if (out_error) {
-        const float ex = ((fax - fbx) * 0.5f) * mx, ey = ((fay - fby) * 0.5f) * my, ez = ((faz - fbz) * 0.5f) * mz;
+        const float ex = ((fax - fbx) * 0.5f) * m.x, ey = ((fay - fby) * 0.5f) * m.y, ez = ((faz - fbz) * 0.5f) * m.z;
         out_error[3 * p] = (double)(ex * ex); out_error[3 * p + 1] = (double)(ey * ey); out_error[3 * p + 2] = (double)(ez * ez);
     }
 }
@@ -233,7 +211,8 @@ size_t nlm_lds_bytes(int r, int f) {
 hipError_t launch_denoise_nlm(const double* d_half_a, const double* d_half_b, const double* d_variance, const double* d_albedo, const double* d_normal, int W, int H,
                               const zr_denoise_nlm_params& dp, float4* d_ua, float4* d_ub, float4* d_vh, float4* d_vs, float4* d_g0, float4* d_g1, double* d_out,
                               double* d_out_error, hipStream_t stream) {
-    const dim3 block(16, 16), grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
+    static_assert(NLM_TILE == 16, "the filter's tiles are the blocks of grid16");
+    const dim3 block(16, 16), grid = grid16(W, H);
     const int demod = dp.demodulate_albedo ? 1 : 0;
     hipLaunchKernelGGL(nlm_pack, grid, block, 0, stream, d_half_a, d_half_b, d_variance, d_albedo, d_normal, W, H, demod, d_ua, d_ub, d_vh, d_g0, d_g1);
     hipLaunchKernelGGL(nlm_smooth, grid, block, 0, stream, (const float4*)d_vh, W, H, d_vs);
@@ -245,12 +224,11 @@ hipError_t launch_denoise_nlm(const double* d_half_a, const double* d_half_b, co
     a.sigma_n = dp.sigma_normal;
     a.inv_np = 1.0f / (float)np;
     const size_t lds = nlm_lds_bytes(a.r, f);
-    const dim3 tiles((unsigned)((W + NLM_TILE - 1) / NLM_TILE), (unsigned)((H + NLM_TILE - 1) / NLM_TILE));
     switch (f) {
-        case 0: return launch_filter<0>(tiles, lds, stream, d_ua, d_ub, d_vs, d_g0, d_g1, W, H, a, d_out, d_out_error);
-        case 1: return launch_filter<1>(tiles, lds, stream, d_ua, d_ub, d_vs, d_g0, d_g1, W, H, a, d_out, d_out_error);
-        case 2: return launch_filter<2>(tiles, lds, stream, d_ua, d_ub, d_vs, d_g0, d_g1, W, H, a, d_out, d_out_error);
-        default: return launch_filter<3>(tiles, lds, stream, d_ua, d_ub, d_vs, d_g0, d_g1, W, H, a, d_out, d_out_error);
+        case 0: return launch_filter<0>(grid, lds, stream, d_ua, d_ub, d_vs, d_g0, d_g1, W, H, a, d_out, d_out_error);
+        case 1: return launch_filter<1>(grid, lds, stream, d_ua, d_ub, d_vs, d_g0, d_g1, W, H, a, d_out, d_out_error);
+        case 2: return launch_filter<2>(grid, lds, stream, d_ua, d_ub, d_vs, d_g0, d_g1, W, H, a, d_out, d_out_error);
+        default: return launch_filter<3>(grid, lds, stream, d_ua, d_ub, d_vs, d_g0, d_g1, W, H, a, d_out, d_out_error);
     }
 }
 
