@@ -748,6 +748,11 @@ uint64_t zr_last_presolved_pixels(zr_ctx*);
  * zr_counters::rounds = R and no drain, the launch log holds (sub_pools - 1) + sub_pools * (R - [sub_pools > 1]) EXTEND launches for the frame; rounds after
  * drain_round contribute one each.  ZR_STREAM_POLL_LAG (default 1; 0: the host drains the streams at every poll) says how many rounds old the host's knowledge is. */
 int zr_last_round_loop(zr_ctx*, int* drain_round, int* sub_pools);
+/* which SHADE build the launches of the last render through the streaming pipeline took: *in_place = launches of the lean render's in-place build (a world with
+ * one material kind, while work units are left; ZR_SHADE_IN_PLACE=0, read per render, switches it off), *sorted = launches of the builds that sort a block's slots
+ * by what they execute.  Launches enqueued are counted, the rounds queued behind the one that emptied the pools included; both 0 for a render that took another
+ * path.  Either pointer may be null. */
+int zr_last_shade_builds(zr_ctx*, int* in_place, int* sorted);
 /* drains the log of render-kernel launch durations (ms, measured with HIP events on the launch stream) recorded
  * since the previous call: copies the newest min(cap, n) of them, oldest first, and returns n */
 int zr_get_kernel_times(zr_ctx*, float* ms, int cap);

@@ -257,7 +257,7 @@ CAPI_SYMBOLS = [
     "zr_accum_halves", "zr_denoise_nlm", "zr_accum_denoise_nlm",
     "zr_render_gbuffer", "zr_temporal_create", "zr_temporal_destroy", "zr_temporal_reset", "zr_temporal_state", "zr_temporal_accumulate", "zr_accum_temporal",
     "zr_temporal_view",
-    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop",
+    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop", "zr_last_shade_builds",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_shade_lean", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
 
@@ -343,6 +343,8 @@ def load():
         lib.zr_last_presolved_pixels.argtypes = [vp]; lib.zr_last_presolved_pixels.restype = u64
     if hasattr(lib, "zr_last_round_loop"):   # (likewise)
         lib.zr_last_round_loop.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(lib, "zr_last_shade_builds"):   # (likewise)
+        lib.zr_last_shade_builds.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.zr_get_kernel_times.argtypes = [vp, C.POINTER(C.c_float), i32]
     lib.zr_trace.argtypes = [vp, vp, vp, C.c_size_t, C.c_double, C.c_double, u64, u64, C.c_uint32, vp]
     lib.zr_kat_scatter.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
@@ -677,6 +679,12 @@ class Context:
         d, k = C.c_int(0), C.c_int(0)
         _check(self.lib.zr_last_round_loop(self._c, C.byref(d), C.byref(k)))
         return d.value, k.value
+
+    def shade_builds(self):
+        """(in_place, sorted): SHADE launches of the last pipeline render by build (zr_last_shade_builds)"""
+        a, b = C.c_int(0), C.c_int(0)
+        _check(self.lib.zr_last_shade_builds(self._c, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def kernel_times_ms(self, cap=256):
         buf = (C.c_float * cap)()

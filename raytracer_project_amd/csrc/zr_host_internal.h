@@ -109,6 +109,7 @@ struct zr_ctx {
     unsigned int* h_polls = nullptr;      // pinned: the round loop's poll ring (zr_round_polls.h), written by the device
     hipEvent_t poll_events[zr::POLL_RING * ST_MAX_POOLS] = {};   // ... and the event behind each of its slots
     int last_drain_round = 0, last_sub_pools = 0;   // of the last pipeline frame: the loop round after which the survivors moved to the drain pool (0: never), sub-pools it began with
+    int last_shade_launches[2] = {0, 0};            // of the last pipeline frame: SHADE launches of the in-place lean build / of the sorted builds (zr_last_shade_builds)
     std::vector<int32_t> pix_key;         // plan the cached pixel list was built for
     uint64_t last_rounds = 0;
     int last_path = 0;                    // zr_counters::path of the last render

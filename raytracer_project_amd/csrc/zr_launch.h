@@ -92,6 +92,7 @@ struct StreamHooks {     // the host's view into the loop
     StreamTimer* timer; volatile const uint8_t* keep_going /* host memory, polled between rounds: 0 cancels */; StreamProgress* progress;
     int* done_out;       // rounds run (stream_render: up to and including the one that emptied the pools) or parts launched (fused_render_frame); negative: cancelled after that many
     int* drain_out = nullptr;   // stream_render: the round after which the survivors moved to the drain pool (0: they never did); [1]: the sub-pools the frame began with
+    int* shade_out = nullptr;   // stream_render: SHADE launches enqueued, [0] of the in-place lean build, [1] of every sorted build (the rounds queued behind the emptying one included)
 };
 struct StreamJob { StreamFrame frame; StreamPool pool; StreamContext ctx; StreamSplit split; StreamHooks hooks; };
 // leaf_level: the EXTEND build the scene needs (zr_scene::leaf_level)

@@ -444,6 +444,7 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode) {
     const uint32_t spp = (uint32_t)job.dc.spp;
     if (c->pending.size() > 65536) { int rr = resolve_times(c); if (rr) return rr; }
     c->render_id++; c->last_stream = job.stream; c->last_counted = job.count; c->last_rounds = 0; c->last_drain_round = 0; c->last_sub_pools = 0;
+    c->last_shade_launches[0] = c->last_shade_launches[1] = 0;
     HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));
     if (n_pix == 0) return ZR_OK;
     uint64_t units = (uint64_t)n_pix * spp;   // one work unit per primary sample
@@ -491,11 +492,12 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode) {
     const bool sharded = job.plan.tiles.size() < (size_t)job.plan.tiles_x * job.plan.tiles_y;
     sj.ctx.n_pools = c->st_pools > 0 ? c->st_pools : ((sharded || lean_pair) ? 2 : 1);
     HostTimer timer(c);
-    int rounds = 0, drain[2] = {0, 0};
-    sj.hooks.timer = &timer; sj.hooks.done_out = &rounds; sj.hooks.drain_out = drain;
+    int rounds = 0, drain[2] = {0, 0}, shade_launches[2] = {0, 0};
+    sj.hooks.timer = &timer; sj.hooks.done_out = &rounds; sj.hooks.drain_out = drain; sj.hooks.shade_out = shade_launches;
     hipError_t e = zr::stream_render(s->ds, sj, s->leaf_level);
     if (e != hipSuccess) return fail(ZR_E_DEVICE, "streaming pipeline failed: %s", hipGetErrorString(e));
     c->last_rounds = (uint64_t)(rounds < 0 ? -rounds : rounds); c->last_drain_round = drain[0]; c->last_sub_pools = drain[1];
+    c->last_shade_launches[0] = shade_launches[0]; c->last_shade_launches[1] = shade_launches[1];
     HIP_OK(hipStreamSynchronize(job.stream));
     if (rounds < 0) return fail(ZR_E_CANCELLED, "render cancelled after %d rounds", -rounds);
     return ZR_OK;
@@ -747,6 +749,13 @@ int zr_last_round_loop(zr_ctx* c, int* drain_round, int* sub_pools) {
     if (!c) return fail(ZR_E_INVALID, "null argument");
     if (drain_round) *drain_round = c->last_drain_round;
     if (sub_pools) *sub_pools = c->last_sub_pools;
+    return ZR_OK;
+}
+
+int zr_last_shade_builds(zr_ctx* c, int* in_place, int* sorted) {
+    if (!c) return fail(ZR_E_INVALID, "null argument");
+    if (in_place) *in_place = c->last_shade_launches[0];
+    if (sorted) *sorted = c->last_shade_launches[1];
     return ZR_OK;
 }
 

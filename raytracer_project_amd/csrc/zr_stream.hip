@@ -22,6 +22,9 @@
 // depend on the pool size, on scheduling, or on how the frame is sharded over GPUs.
 #include "zr_device.h"
 #include "zr_launch.h"
+#ifdef ZR_SHADE_ASSERT   /* a debug build (ZR_DEFS=-DZR_SHADE_ASSERT): lean SHADE checks its early unit reservation against the lanes that end */
+#include <cassert>
+#endif
 
 namespace zr {
 
@@ -140,9 +143,8 @@ __host__ __device__ inline unsigned long long st_first_unit(uint32_t G, uint32_t
 }
 
 // ---- begin a sample in a slot: camera ray + fresh path state --------------------------------------------
-__device__ inline void begin_sample(const StreamBuf& B, const DCamera& cam, uint64_t seed, const SlotAt& S, uint32_t unit, uint32_t& c_samp) {
-    const uint32_t pix_i = unit / B.spp, sample = unit - pix_i * B.spp + B.sample0;
-    const uint32_t pk = B.pixels[pix_i];
+// sample `sample` of the pixel whose word (B.pixels) is `pk`
+__device__ __forceinline__ void begin_sample_at(const DCamera& cam, uint64_t seed, const SlotAt& S, uint32_t unit, uint32_t sample, uint32_t pk, uint32_t& c_samp) {
     const int px = (int)(pk & 0xFFFFu), py = (int)(pk >> 16);
     Rng g; g.key = zr_stream_key(seed, (uint64_t)py * (uint64_t)cam.W + (uint64_t)px, (uint64_t)sample); g.k = 0; g.bounce = 0;
     Ray r = camera_ray(cam, px, py, g);
@@ -152,6 +154,16 @@ __device__ inline void begin_sample(const StreamBuf& B, const DCamera& cam, uint
     uint2 mb; mb.x = unit; mb.y = 0;
     S.st2(SF_MA, ma); S.st2(SF_MB, mb);
     c_samp++;
+}
+__device__ inline void begin_sample(const StreamBuf& B, const DCamera& cam, uint64_t seed, const SlotAt& S, uint32_t unit, uint32_t& c_samp) {
+    const uint32_t pix_i = unit / B.spp, sample = unit - pix_i * B.spp + B.sample0;
+    const uint32_t pk = B.pixels[pix_i];
+    begin_sample_at(cam, seed, S, unit, sample, pk, c_samp);
+}
+// ... with the unit's pixel word, B.pixels[unit / B.spp], loaded by the caller already (the lean SHADE requests it before its MISS stage)
+__device__ inline void begin_sample(const StreamBuf& B, const DCamera& cam, uint64_t seed, const SlotAt& S, uint32_t unit, uint32_t pk, uint32_t& c_samp) {
+    const uint32_t pix_i = unit / B.spp, sample = unit - pix_i * B.spp + B.sample0;
+    begin_sample_at(cam, seed, S, unit, sample, pk, c_samp);
 }
 
 template <bool COUNT>
@@ -515,10 +527,21 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
 #define ST_SHADE_WAVES_LEAN 6
 #endif
 // UV: the general build for scenes whose triangles carry texture coordinates (zr_device.h: triangle_rec_uv); the lean build reads none
-template <bool COUNT, int MODE, bool LEAN = false, bool UV = false>
-__global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) void stream_shade(DScene sc, DCamera cam, DEnv env, uint64_t seed, StreamBuf B,
+// SORT = false: the IN-PLACE build of the lean render (round 28).  A thread shades the slot it indexes: no partition, no LDS, no barrier, and the segment's
+// first batch of rows is requested together with the meta word instead of one round trip behind it.  For a world with ONE material kind the sort only
+// separates hits from misses, and since the escape stage and the sky pre-pass most hit waves run the MISS stage anyway while the misses EXTEND finds are too
+// few to fill a wave of their own: what is left of the sort is its cost, which sits on the kernel's chain of dependent round trips.
+// Its next work units are reserved, and their pixel words requested, before the MISS stage (RESERVE_EARLY below).  The host takes this build while work units
+// are left (stream_render); once the pool thins out the sorted build packs the survivors into full waves.
+template <bool COUNT, int MODE, bool LEAN = false, bool UV = false, bool SORT = true>
+__global__ __launch_bounds__(SORT ? 256 : 64, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) void stream_shade(DScene sc, DCamera cam, DEnv env, uint64_t seed, StreamBuf B,
                                                     unsigned long long* __restrict__ gctr) {
-    const uint32_t slot0 = blockIdx.x * 256 + threadIdx.x;
+    // the block of 256 slots this workgroup works on, and its thread's place in it.  The in-place build's waves share nothing, so its workgroup is ONE wave, a
+    // quarter of a slot block: a finished wave's registers free without waiting for three siblings (cfg3: 1.5-2 ms of a frame against 256-thread groups, in
+    // ten of ten A/B cycles: profiles/r28_shade_in_place_ab.txt).  The slot block, its shard and the control-word reset are what they are in the sorted build.
+    constexpr bool QUARTER = !SORT;
+    const uint32_t sblock = QUARTER ? blockIdx.x >> 2 : blockIdx.x, sthread = QUARTER ? (blockIdx.x & 3u) * 64u + threadIdx.x : threadIdx.x;
+    const uint32_t slot0 = sblock * 256 + sthread;
     if (slot0 < ST_SHARDS) B.ctl[CTL_SHARD0 + CTL_STRIDE * slot0 + CTL_SH_CHUNK] = 0;  // EXTEND of the next round starts from chunk 0 of every shard
     // the split passes count through LDS into a per-block record (a global atomic per thread costs ~1.5 ms per round and word)
     __shared__ unsigned long long s_cnt[4];
@@ -539,7 +562,19 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
     __shared__ unsigned char x_src[256]; // ... and which slot of the block that is
     uint32_t src;   // which slot of the block this thread shades
     uint2 m, ki;
-    {
+    // the in-place build's first batch: every row a segment reads whose address does not depend on the meta word
+    Ray ray_in; double key_in, t_in; uint2 mb_in;
+    if constexpr (!SORT) {
+        static_assert(LEAN && MODE == 0, "the in-place build exists for the lean render only");
+        src = sthread;
+        m.x = 0; m.y = 0; ki.x = 0xFFFFFFFFu; ki.y = 0;
+        if (slot0 < B.P) {   // (a slot is addressable whether or not it is active; a thread beyond the pool keeps meta = 0)
+            const SlotAt S0 = slot_at(B, sblock, sthread);
+            m = S0.ld2(SF_MA); ki = S0.ld2(SF_HIT_KI); t_in = S0.ld(SF_HIT_T);
+            ray_in.o = S0.ld3(SF_RAY); ray_in.d = S0.ld3(SF_RAY + 3);
+            key_in = S0.ld(SF_KEY); mb_in = S0.ld2(SF_MB);
+        }
+    } else {
         uint2 m0; m0.x = 0; m0.y = 0;
         uint2 k0; k0.x = 0xFFFFFFFFu; k0.y = 0;
         if (slot0 < B.P) { const SlotAt S0 = slot_at(B, blockIdx.x, threadIdx.x); m0 = S0.ld2(SF_MA); k0 = S0.ld2(SF_HIT_KI); }
@@ -577,9 +612,18 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
         src = x_src[threadIdx.x];
         m.x = mk4.x; m.y = mk4.y; ki.x = mk4.z; ki.y = mk4.w;
     }
-    const SlotAt S = slot_at(B, blockIdx.x, src);
+    const SlotAt S = slot_at(B, sblock, src);
     bool active_after = false, want_unit = false;
     uint32_t c_samp = 0, c_seg2 = 0, c_hit2 = 0, c_esc = 0, c_esc_nodes = 0, c_seen = 0; unsigned long long c_draws = 0;
+    // The in-place build reserves a lane's next work unit BEFORE its MISS stage (below): the unit (ST_NO_UNIT: none was reserved, or it lies beyond the frame) and its
+    // pixel word.  Not the sorted lean build: with the two values held across the stages (or the unit alone) it went from 6 scratch operations outside the stages to 32
+    // inside them (scripts/dev/kernel_regs.sh, profiles/r28_shade_in_place_ab.txt), so it hands out units behind MISS as it always has.
+    constexpr uint32_t ST_NO_UNIT = 0xFFFFFFFFu;   // no unit has this number: ST_MAX_UNITS (zr_launch.h)
+    constexpr bool RESERVE_EARLY = LEAN && MODE == 0 && !SORT;
+    uint32_t next_unit = ST_NO_UNIT, next_pk = 0;
+#ifdef ZR_SHADE_ASSERT
+    bool reserved = false;
+#endif
     {
         if (m.y & F_ACTIVE) {   // (a thread beyond the pool got meta = 0 from the prologue)
             const uint32_t NONE = 0xFFFFFFFFu;
@@ -587,10 +631,11 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
             if (COUNT && LEAN && MODE == 0) c_seen++;   // a segment EXTEND traced: CTR_SEGMENTS - CTR_ESCAPED, counted from this side
             // every row this segment reads, requested in one go (a row of a slot is always addressable; what a path does not
             // need is not requested: beta before the second hit, the unit id is 8 bytes)
-            Ray ray; ray.o = S.ld3(SF_RAY); ray.d = S.ld3(SF_RAY + 3);
-            Rng g; g.key = (uint64_t)__double_as_longlong(S.ld(SF_KEY)); g.k = m.x; g.bounce = (m.y & 0xFFu) + 1u;  // this query is complete
-            const uint2 mb_now = S.ld2(SF_MB);
-            const double t_hit = S.ld(SF_HIT_T);
+            Ray ray;
+            if constexpr (SORT) { ray.o = S.ld3(SF_RAY); ray.d = S.ld3(SF_RAY + 3); } else ray = ray_in;
+            Rng g; g.key = (uint64_t)__double_as_longlong(SORT ? S.ld(SF_KEY) : key_in); g.k = m.x; g.bounce = (m.y & 0xFFu) + 1u;  // this query is complete
+            const uint2 mb_now = SORT ? S.ld2(SF_MB) : mb_in;
+            const double t_hit = SORT ? S.ld(SF_HIT_T) : t_in;
             // after the first hit L = 0 and beta = 1 (camera.hpp:930): both stay implicit (two flag bits) until something else is
             // stored, which saves their 48 bytes written and read back per path; the values used are the same (0 + x, 1 * x)
             V3 beta_now = mk(1, 1, 1);
@@ -724,6 +769,28 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
                     active_after = true;
                 }
             }
+            if constexpr (RESERVE_EARLY) {
+                // Which lanes will want a work unit is known here: in the lean render MISS always ends its path, so this is the exact set of lanes that reach
+                // `ended` below.  The wave's one atomic on its block's shard and the pixel word of each lane's next unit are requested now, so that both round
+                // trips run beside the background's texel fetch and arithmetic instead of behind them.  Units reserved == lanes that end, launch for launch.
+                const bool will_end = ended || ki.x == NONE || escaped;
+                const unsigned long long wm = __ballot(will_end);
+                if (wm != 0ull) {
+                    const uint32_t shard = sblock % ST_SHARDS;
+                    const int wl = threadIdx.x & 63, first_lane = (int)__builtin_ctzll(wm);
+                    uint32_t k0 = 0;
+                    if (wl == first_lane) k0 = atomicAdd(&B.uctl[CTL_STRIDE * shard + CTL_SH_UNITS], (unsigned int)__popcll(wm));
+                    k0 = __shfl(k0, first_lane, 64);
+                    if (will_end) {
+                        const unsigned long long k = (unsigned long long)k0 + (unsigned long long)__popcll(wm & ((1ull << wl) - 1ull));
+                        const unsigned long long u = st_unit_of(B.unit_chunk, B.unit_base, shard, (unsigned long long)B.shard_k0 + k);
+                        if (u < (unsigned long long)B.n_units) { next_unit = (uint32_t)u; next_pk = B.pixels[next_unit / B.spp]; }
+                    }
+                }
+#ifdef ZR_SHADE_ASSERT
+                reserved = will_end;
+#endif
+            }
             if (ESC && (ki.x == NONE || escaped)) ZR_MISS_STAGE()
 #undef ZR_MISS_STAGE
             if (ended) {
@@ -747,11 +814,20 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
             }
         }
     }
-    // hand out new work units: one atomic per wave on this block's shard
-    {
+    if constexpr (RESERVE_EARLY) {
+        // the in-place build reserved the units ahead of its MISS stage: the sample starts from registers
+#ifdef ZR_SHADE_ASSERT
+        assert(want_unit == reserved);   // units reserved == lanes that ended (a -DZR_SHADE_ASSERT build only)
+#endif
+        if (want_unit) {
+            if (next_unit != ST_NO_UNIT) { begin_sample(B, cam, seed, S, next_unit, next_pk, c_samp); active_after = true; }
+            else { uint2 z; z.x = 0; z.y = 0; S.st2(SF_MA, z); }
+        }
+    } else {
+        // hand out new work units: one atomic per wave on this block's shard
         const unsigned long long wm = __ballot(want_unit);
         if (wm != 0ull) {
-            const uint32_t shard = blockIdx.x % ST_SHARDS;
+            const uint32_t shard = sblock % ST_SHARDS;
             const int wl = threadIdx.x & 63;
             uint32_t k0 = 0;
             if (wl == (int)__builtin_ctzll(wm)) k0 = atomicAdd(&B.uctl[CTL_STRIDE * shard + CTL_SH_UNITS], (unsigned int)__popcll(wm));
@@ -767,7 +843,7 @@ __global__ __launch_bounds__(256, LEAN ? ST_SHADE_WAVES_LEAN : ST_SHADE_WAVES) v
     // active-slot count for the host's round loop: sharded like the other counters — one contended word would cost
     // ~3 ms per 16 M-slot round (262 144 wave atomics at ~90 per microsecond)
     const unsigned long long am = __ballot(active_after);
-    if ((threadIdx.x & 63) == 0 && am != 0ull) atomicAdd(&B.ctl[CTL_SHARD0 + CTL_STRIDE * (blockIdx.x % ST_SHARDS) + CTL_SH_ACTIVE], (unsigned int)__popcll(am));
+    if ((threadIdx.x & 63) == 0 && am != 0ull) atomicAdd(&B.ctl[CTL_SHARD0 + CTL_STRIDE * (sblock % ST_SHARDS) + CTL_SH_ACTIVE], (unsigned int)__popcll(am));
     if (COUNT && MODE == 0) {
         if (c_samp) atomicAdd(&gctr[CTR_SAMPLES], (unsigned long long)c_samp);
         if (c_draws) atomicAdd(&gctr[CTR_DRAWS], c_draws);
@@ -1284,10 +1360,25 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
     };
     // development aid: ZR_SHADE_LDS_PAD bytes of dynamic LDS per SHADE block lower the blocks a CU can hold (160 KB: 4 fit by registers; > 40 KB: 3, > 53 KB: 2)
     static const unsigned shade_pad = std::getenv("ZR_SHADE_LDS_PAD") ? (unsigned)std::atoi(std::getenv("ZR_SHADE_LDS_PAD")) : 0u;
+    // The lean render of a world with one material kind shades its slots IN PLACE (stream_shade<., 0, true, false, false>) while work units are left: the pool is
+    // full of fresh paths and the sort would only cost.  `units_left` is what the newest poll the loop holds says (true until one arrives); once the hand-out is
+    // over the pool thins out and the sorted build packs the survivors into full waves.  Either build is correct for any launch, so a stale poll only costs time.
+    // ZR_SHADE_IN_PLACE=0 (read per render) forces the sorted build.
+    const char* in_place_env = std::getenv("ZR_SHADE_IN_PLACE");
+    const bool in_place_ok = sc.shade_lean && mode == 0 && (sc.mat_kinds & (sc.mat_kinds - 1u)) == 0 && !(in_place_env && std::atoi(in_place_env) == 0);
+    bool units_left = true;
+    int shade_launches[2] = {0, 0};   // in place, sorted
     auto shade = [&](const StreamBuf& B, hipStream_t st) {
         if (H.timer) H.timer->begin(st, 2);
         const dim3 sg((B.P + 255) / 256), sb(256);
-        if (sc.shade_lean && mode == 0) {   // the lean build: same arithmetic, fewer registers, 6 waves per SIMD instead of 4 (see lean_rec, zr_device.h)
+        const bool in_place = in_place_ok && units_left;
+        shade_launches[in_place ? 0 : 1]++;
+        if (in_place) {
+            const dim3 sg((B.P + 255) / 256 * 4), sb(64);   // one wave per workgroup, four per slot block
+            if (F.count) hipLaunchKernelGGL((stream_shade<true, 0, true, false, false>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+            else hipLaunchKernelGGL((stream_shade<false, 0, true, false, false>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
+        }
+        else if (sc.shade_lean && mode == 0) {   // the lean build: same arithmetic, fewer registers, 6 waves per SIMD instead of 4 (see lean_rec, zr_device.h)
             if (F.count) hipLaunchKernelGGL((stream_shade<true, 0, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
             else hipLaunchKernelGGL((stream_shade<false, 0, true>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
         }
@@ -1370,6 +1461,7 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
         }
         if (e != hipSuccess) break;
         const RoundPolls::Action a = rp.take(p, P, job.pool.drain_slots, job.pool.drain != nullptr);
+        units_left = p.units_left;   // which SHADE build the next rounds take
         if (trace_polls) std::fprintf(stderr, "[zr] poll of round %d (%d queued behind it): active %llu, units left %d, drain condition %d%s\n", rp.polled, rp.in_flight(),
                                       p.active, (int)p.units_left, (int)drain_condition(p, P, job.pool.drain_slots), a.drain ? " -> compaction" : "");
         if (a.finished) break;
@@ -1434,10 +1526,12 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
             H.progress->report(frac, reduced);
         }
         if (active == 0) break;
-        if (!drained && job.pool.drain && active * 16ull <= (unsigned long long)P && active <= (unsigned long long)job.pool.drain_slots) {
-            bool units_left = false;   // shard sh has handed out every k below its counter: unit_base + k * shards + sh
+        if (units_left) {   // this loop's own copy of the unit counters (it also chooses the SHADE build of the next rounds)
+            units_left = false;   // shard sh has handed out every k below its counter: unit_base + k * shards + sh
             for (int sh = 0; sh < ST_SHARDS && !units_left; sh++)
                 if (st_unit_of(unit_chunk, P, (uint32_t)sh, (unsigned long long)(unit_chunk ? P / ST_SHARDS : 0u) + h_units[CTL_STRIDE * sh + CTL_SH_UNITS]) < (unsigned long long)n_units) units_left = true;
+        }
+        if (!drained && job.pool.drain && active * 16ull <= (unsigned long long)P && active <= (unsigned long long)job.pool.drain_slots) {
             if (!units_left) {   // see stream_compact
                 compact_to_drain(drain_pool_slots(active));
                 if (trace_polls) std::fprintf(stderr, "[zr] compaction behind round %d\n", rp.enqueued);
@@ -1464,6 +1558,7 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
     if (H.timer) H.timer->end(stream, 3);
     if (H.done_out) *H.done_out = cancelled ? -rounds : rounds;
     if (H.drain_out) { H.drain_out[0] = drain_round; H.drain_out[1] = K0; }
+    if (H.shade_out) { H.shade_out[0] = shade_launches[0]; H.shade_out[1] = shade_launches[1]; }
     return hipGetLastError();
 }
 
