@@ -1538,7 +1538,8 @@ public:
     // multiple of 64) is blended with the history of the frames before it, reprojected through the first hits of this camera's pixels: temporal_buffer holds
     // the blend, variance_buffer its variance and temporal_history_length the frames behind every pixel.  With use_denoiser && denoise_variance_guided the
     // guided filter takes those two in place of the frame's own.  The history belongs to a frame size and a world object (the `world` argument's address): it
-    // is dropped when either changes, or on reset_temporal_history() — the caller's duty after editing the world in place.  Static worlds only.  Without a
+    // is dropped when either changes, or on reset_temporal_history() — the caller's duty after editing the world in place (a moving world: see
+    // temporal_track_motion below).  Without a
     // variance a warning is printed and the render is what it is without the flag.  render_accumulator is never touched.  false: exactly the render without it.
     bool temporal_accumulation = false;
     zr_temporal_params temporal_params{ZR_TEMPORAL_DEFAULT_ALPHA, ZR_TEMPORAL_DEFAULT_MAX_HISTORY, 0, ZR_TEMPORAL_DEFAULT_PLANE_TOLERANCE, ZR_TEMPORAL_DEFAULT_NORMAL_COS};
@@ -1550,8 +1551,14 @@ public:
     // its wrappers (a translate's offset, a rotation's angle, a scale's factors) and the numbers of its spheres — the reference's way to move things: the same
     // objects under re-created translate / rotate_y wrappers — it updates the kept scene and refits its trees instead of building them again; any other
     // change, a refused update, another device context or a failed refit commits anew.  last_scene_refit says which it was: 0 committed, 1 refitted.
-    // The frame is the same bit for bit either way.  The temporal history knows no object motion: reset_temporal_history() stays the caller's duty.
+    // The frame is the same bit for bit either way.  Without temporal_track_motion the temporal history knows no object motion: reset_temporal_history() stays
+    // the caller's duty.
     bool reuse_scene = false;
+    // extension: the temporal history follows a moving world (zr_temporal_track_motion).  Takes effect together with temporal_accumulation and
+    // reuse_scene: the camera switches tracking on in the history it keeps, and keeps that history across a frame whose scene was refitted
+    // (last_scene_refit == 1) although the `world` argument is a new object — the refit's motion table reprojects the moved objects' pixels.  Every other case
+    // is left to the library's restart rule (a new commit, another scene: the frame starts anew).  false: exactly the renders without it.
+    bool temporal_track_motion = false;
     int last_scene_refit = 0;
     void forget_scene() { kept_scene_.reset(); kept_ctx_ = nullptr; }
     zr_adaptive_stats last_adaptive{};
@@ -1741,11 +1748,15 @@ private:
     int accumulate_temporal(const frame_job& j, zr_accum* acc) {
         if (!temporal_accumulation) return ZR_OK;
         static_assert(sizeof(int) == sizeof(int32_t), "temporal_history_length layout");
-        if (!temporal_ || temporal_ctx_ != j.ctx || temporal_world_ != j.world || temporal_w_ != image_width || temporal_h_ != image_height) {
+        const bool track = temporal_track_motion && reuse_scene;
+        const bool same_world = temporal_world_ == j.world || (track && last_scene_refit == 1);   // (a refitted scene is the kept world, moved)
+        if (!temporal_ || temporal_ctx_ != j.ctx || !same_world || temporal_w_ != image_width || temporal_h_ != image_height) {
             temporal_.reset(zr_temporal_create(j.ctx, image_width, image_height));
             if (!temporal_) return ZR_E_DEVICE;
-            temporal_ctx_ = j.ctx; temporal_world_ = j.world; temporal_w_ = image_width; temporal_h_ = image_height;
+            temporal_ctx_ = j.ctx; temporal_w_ = image_width; temporal_h_ = image_height;
         }
+        temporal_world_ = j.world;
+        if (track || tracking_) { zr_temporal_track_motion(temporal_.get(), track ? 1 : 0); tracking_ = track; }
         temporal_buffer.assign(pixels(), color(0, 0, 0)); variance_buffer.assign(pixels(), color(0, 0, 0)); temporal_history_length.assign(pixels(), 0);
         const int rc = zr_accum_temporal(acc, temporal_.get(), &temporal_params, j.sc, &j.cam, seed, zenith::doubles(temporal_buffer), zenith::doubles(variance_buffer),
                                          reinterpret_cast<int32_t*>(temporal_history_length.data()));
@@ -1897,4 +1908,5 @@ private:
     zr_ctx* kept_ctx_ = nullptr;
     zenith::flat_scene kept_fs_;
     zr_ctx* temporal_ctx_ = nullptr; const hittable* temporal_world_ = nullptr; int temporal_w_ = 0, temporal_h_ = 0;
+    bool tracking_ = false;   // the switch was set in a history this camera made
 };

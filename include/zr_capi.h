@@ -306,9 +306,21 @@ const char* zr_scene_builder(const zr_scene*);
  *     commit builds its state (reverse indices, schedule, device buffers) and is slower; later ones allocate nothing.  (A world of at most ZR_FUSED_MAX
  *     objects also re-reads the fused kernel's argument copy.)
  * An accumulator binds (scene, epoch): a batch after a refit is refused like a batch with another scene (ZR_E_INVALID) until zr_accum_reset.  A zr_temporal
- * must be reset by the caller after a refit.
+ * must be reset by the caller after a refit unless it tracks motion (zr_temporal_track_motion below): then it follows the refit's own motion table.
+ *   zr_scene_motion            known-answer entry: the motion table of the LAST refit, i.e. of the one step epoch - 1 -> epoch.  Every refit
+ *     replaces it, a refit with nothing dirty leaves it empty, a commit drops it.  Per world-list entry out_slot_per_entry holds ZR_MOTION_STATIC (the refit
+ *     did not touch the entry), ZR_MOTION_CUT (it moved but cannot be followed: a radius or scale factor of 0 before or after, or a value that is not finite;
+ *     its pixels get no history) or the index of its record.  A record is 21 doubles, FP64 in a fixed operation order: a[12], row k = a[4k .. 4k+2] linear and
+ *     a[4k+3] translation, of A = M_prev M_now^-1, which takes a world point of the entry now to where that point of the entry was before the refit; then
+ *     nm[9] by rows, (A_lin)^-T, for normals.  M is the entry's object-to-world map: its chain innermost first (translate p + a; rotate co a - sn b,
+ *     sn a + co b; scale p a; a medium's inner chain inside the entry's own; a leaf sphere's own x -> c + max(0, r) x innermost).  *out_count = world-list
+ *     entries; both arrays, when given, must have room for `capacity` >= that many entries (at most one record per entry); both may be NULL to ask for the
+ *     count.  ZR_E_STATE: not committed, stale, or committed from borrowed arrays.
  * Out of scope, each needs a new commit: triangle vertices and cubes' own numbers; adding or removing entries; material or texture changes; the triangles
- * inside a group (a placement of the group may move; the group's own tree is never touched); motion vectors for the temporal stage. */
+ * inside a group (a placement of the group may move; the group's own tree is never touched).  The motion table describes ONE refit: batch all updates of a
+ * frame into one refit. */
+#define ZR_MOTION_STATIC 0xFFFFFFFFu
+#define ZR_MOTION_CUT 0xFFFFFFFEu
 typedef struct zr_refit_info {
     uint64_t epoch;          /* refits applied to this commit (0 after zr_scene_commit) */
     uint32_t dirty_entries;  /* world-list entries whose record or box was recomputed (media reached through their inner chain included) */
@@ -321,6 +333,7 @@ typedef struct zr_refit_info {
 int zr_scene_update_xform_ops(zr_scene*, size_t first, const zr_xform_op* ops, size_t n);
 int zr_scene_update_spheres(zr_scene*, size_t first, const double* cxyz_r, size_t n);
 int zr_scene_refit(zr_scene*, zr_refit_info* out /* may be NULL */);
+int zr_scene_motion(const zr_scene*, uint32_t* out_slot_per_entry, double* out_records21, size_t capacity, size_t* out_count);
 
 /* ---- render: replaces camera::render's sample loop (camera.hpp:236-248, 404-579) ----------- */
 /* Fills out_rgb[(j*W+i)*3 + c] (host memory, W*H*3 doubles, row 0 = top, mean over spp — the layout of
@@ -606,7 +619,8 @@ int zr_denoise_nlm(zr_ctx*, const zr_denoise_nlm_params*, const double* half_a, 
                    const double* albedo, const double* normal, int width, int height, double* out, double* out_error);
 int zr_accum_denoise_nlm(zr_accum*, const zr_denoise_nlm_params*, const double* albedo, const double* normal, double* out, double* out_error);
 /* ---- temporal accumulation: a frame's history reprojected across a moving camera ------------------------------
- * The temporal stage of SVGF (Schied et al., HPG 2017, section 4.1) for a camera path through a STATIC world; the reference has no counterpart.
+ * The temporal stage of SVGF (Schied et al., HPG 2017, section 4.1) for a camera path; through a world that zr_scene_refit moves when the history tracks motion
+ * (zr_temporal_track_motion).  The reference has no counterpart.
  * zr_render_gbuffer    the first hit of the ray through the centre of every pixel (get_center_ray, camera.hpp:809-814: origin `center`, direction
  *                      (pixel00_loc + i pixel_delta_u + j pixel_delta_v) - center; no jitter, no defocus disk), W*H pixels row-major: by definition what
  *                      zr_trace(those rays, tmin 0.001, tmax inf, seed, pixel = ZR_GBUFFER_STREAM, bounce 0) returns — constant-medium hits included — as
@@ -614,7 +628,8 @@ int zr_accum_denoise_nlm(zr_accum*, const zr_denoise_nlm_params*, const double* 
  *                      mat 0xFFFFFFFF.  Host memory; any output may be NULL.  Argument checks and error codes as zr_render_aov.
  * zr_temporal          the history of a width x height frame on the device, double-buffered in FP64: blended colour and variance, history length, the
  *                      previous frame's geometry buffer and the previous camera.  zr_temporal_reset forgets it (the caller's duty after any change of the
- *                      scene, a zr_scene_refit included: the history carries no motion vectors); zr_temporal_state: out = width, height, frames accumulated since create / reset, 0.
+ *                      scene — a zr_scene_refit included unless the history tracks motion); zr_temporal_state: out = width, height, frames accumulated since
+ *                      create / reset, 1 when it tracks motion else 0.
  * zr_temporal_accumulate  takes one frame — `color` and `variance` (of the pixel means, e.g. zr_accum_resolve / zr_accum_variance), W*H*3 doubles in host
  *                      memory — makes the camera's geometry buffer and, per pixel p (FP64, no contraction; tests/temporal_model.py restates it):
  *                        c, V: the inputs with NaN / Inf -> 0 and V <= 0 -> 0 (zr_denoise_guided's rules);
@@ -629,10 +644,22 @@ int zr_accum_denoise_nlm(zr_accum*, const zr_denoise_nlm_params*, const double* 
  *                      out, V_out, N and the geometry buffer become the history.  out_color / out_variance (W*H*3 doubles) and out_history (W*H int32) are
  *                      host memory and may each be NULL; the first two may be handed to zr_denoise_guided as they are.  ZR_E_INVALID before any device
  *                      work: parameters out of range or not finite (checked first), NULL, a camera of another size or without a finite view, a scene or
- *                      history of another context; ZR_E_STATE: scene not committed.  Limits: static worlds; mirrors, glass and media reproject by their
- *                      first hit; the filtered image is not fed back.
+ *                      history of another context; ZR_E_STATE: scene not committed.  Limits: a moving world needs zr_temporal_track_motion; mirrors, glass and
+ *                      media reproject by their first hit (reflections of moving objects are not followed); the filtered image is not fed back.
  * zr_accum_temporal    zr_temporal_accumulate(zr_accum_resolve(), zr_accum_variance(), ...) bit for bit, resolved on the device straight into the kernel.
  *                      Whole-frame accumulators only (ZR_E_INVALID otherwise); then zr_accum_variance's state rules.
+ * zr_temporal_track_motion  on != 0: the history remembers (scene, commit, epoch) of the frame it holds, and zr_temporal_accumulate / zr_accum_temporal choose:
+ *                        same scene, commit and epoch: the path above;
+ *                        same scene and commit, epoch exactly one more: per pixel the world-list entry under it is looked up in the refit's motion table
+ *                        (zr_scene_motion).  STATIC or a miss: the path above.  CUT: no history (N = 1).  A record: Xr = A X_p, nr = Nm n_p / |Nm n_p| (no
+ *                        history unless that length is > 0); Xr is what is projected into the previous camera, the plane test is
+ *                        |(X_q - Xr) . nr| <= plane_tolerance depth_p with depth_p still of X_p in the current camera, the normal test nr . n_q >= normal_cos
+ *                        (tests/temporal_motion_model.py restates it);
+ *                        anything else — another scene, a new commit, two or more refits since the held frame — restarts the frame (N = 1 everywhere, as
+ *                        after zr_temporal_reset) instead of ghosting.  So batch ALL updates of a frame into ONE zr_scene_refit.
+ *                      Default off: the behaviour above, the caller's duty to reset included.  Switching changes nothing the history holds.
+ * zr_render_gbuffer_entries  known-answer entry: the world-list entry under each pixel of zr_render_gbuffer, 0xFFFFFFFF on a miss.  Builds the host half of the
+ *                      scene's refit state if there is none; ZR_E_STATE for a scene committed from borrowed arrays, as the updates say.
  * zr_temporal_view     known-answer entry, no device: the camera as the reprojection sees it, out = center 3, pixel00 3, unit w 3, a = du / (du . du) 3,
  *                      b = dv / (dv . dv) 3, focus_dist — from the quantities zr_render derives (camera::initialize, camera.hpp:358-399). */
 #define ZR_GBUFFER_STREAM 0xFFFFFFFEull   /* the `pixel` of the geometry buffer's RNG keys: ray k draws from zr_stream_key(seed, ZR_GBUFFER_STREAM, k) */
@@ -661,6 +688,8 @@ int zr_temporal_accumulate(zr_temporal*, const zr_temporal_params*, const zr_sce
 int zr_accum_temporal(zr_accum*, zr_temporal*, const zr_temporal_params*, const zr_scene*, const zr_camera*, uint64_t seed, double* out_color,
                       double* out_variance, int32_t* out_history);
 int zr_temporal_view(const zr_camera*, double out[16]);
+int zr_temporal_track_motion(zr_temporal*, int on);
+int zr_render_gbuffer_entries(zr_ctx*, zr_scene*, const zr_camera*, uint64_t seed, uint32_t* out_entry);
 
 /* post_processor::apply_sharpening (color_processing.hpp:207-227) on its own: interior pixels become
  * c (1 - amount) + (5 c - the four neighbours) amount, border pixels are copied.  Double in, double out, byte-exact with

@@ -256,7 +256,7 @@ CAPI_SYMBOLS = [
     "zr_accum_variance", "zr_denoise_guided", "zr_accum_denoise",
     "zr_accum_halves", "zr_denoise_nlm", "zr_accum_denoise_nlm",
     "zr_render_gbuffer", "zr_temporal_create", "zr_temporal_destroy", "zr_temporal_reset", "zr_temporal_state", "zr_temporal_accumulate", "zr_accum_temporal",
-    "zr_temporal_view",
+    "zr_temporal_view", "zr_temporal_track_motion", "zr_render_gbuffer_entries", "zr_scene_motion",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop", "zr_last_shade_builds",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_shade_lean", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
@@ -333,6 +333,10 @@ def load():
         lib.zr_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalParams), vp, C.POINTER(Camera), u64, vp, vp, vp, vp, vp]
         lib.zr_accum_temporal.argtypes = [vp, vp, C.POINTER(TemporalParams), vp, C.POINTER(Camera), u64, vp, vp, vp]
         lib.zr_temporal_view.argtypes = [C.POINTER(Camera), C.POINTER(C.c_double * 16)]
+    if hasattr(lib, "zr_scene_motion"):   # (likewise)
+        lib.zr_temporal_track_motion.argtypes = [vp, i32]
+        lib.zr_render_gbuffer_entries.argtypes = [vp, vp, C.POINTER(Camera), u64, vp]
+        lib.zr_scene_motion.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.zr_render_bvh_debug.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), C.POINTER(BvhDebugParams), vp, vp, vp]
     lib.zr_trace_bvh_debug.argtypes = [vp, vp, C.POINTER(BvhDebugParams), vp, C.c_size_t, C.c_double, u64, u64, C.c_uint32, vp]
     lib.zr_scene_tree_boxes.argtypes = [vp, vp, C.c_size_t]
@@ -390,6 +394,8 @@ def load_scenes():
     s.zrs_render_dropin_temporal.argtypes = frame + [i32, vp, i32, i32] + [vp] * 5
     s.zrs_render_dropin_bvh_debug.argtypes = frame + [i32, C.c_float, vp, vp]
     s.zrs_render_dropin_animated.argtypes = frame + [i32, i32, i32, vp, vp]
+    if hasattr(s, "zrs_render_dropin_animated_temporal"):
+        s.zrs_render_dropin_animated_temporal.argtypes = frame + [i32, i32, vp, vp, vp, vp]
     s.zrs_dropin_virtuals.argtypes = [vp, vp, i32, C.c_uint64, C.c_uint64, vp, vp]
     s.zrs_dropin_frame_to_rgb8.argtypes = [vp, i32, i32, vp, vp, C.POINTER(C.c_float)]
     _scenes = s
@@ -556,6 +562,21 @@ class DemoScene:
         self._rendered(load_scenes().zrs_render_dropin_animated(self._h, width, height, spp, device, int(n_frames), 1 if reuse_scene else 0, int(add_at),
                                                                 out.ctypes.data, refit) == 0)
         return out, [int(x) for x in refit]
+
+    def render_dropin_animated_temporal(self, n_frames, reuse_scene=True, temporal=True, track_motion=False, width=0, height=0, spp=0, device=0):
+        """render_dropin_animated's world (nothing added) through ONE camera with camera::temporal_accumulation (progressive, 64 samples a pass) and
+        camera::temporal_track_motion: dict of render_accumulator, temporal_buffer ((n, H, W, 3); all -1 where a frame left it empty),
+        temporal_history_length ((n, H, W) int32, -1 likewise) and last_scene_refit (list)"""
+        outs = self._frames(width, height, "render_accumulator", "temporal_buffer", n=n_frames)
+        hist = np.zeros((n_frames, *self._size(width, height)), dtype=np.int32)
+        refit = (C.c_int * n_frames)()
+        flags = (1 if reuse_scene else 0) | (2 if temporal else 0) | (4 if track_motion else 0)
+        self._rendered(load_scenes().zrs_render_dropin_animated_temporal(self._h, width, height, spp, device, int(n_frames), flags,
+                                                                         outs["render_accumulator"].ctypes.data, outs["temporal_buffer"].ctypes.data,
+                                                                         hist.ctypes.data, refit) == 0)
+        outs["temporal_history_length"] = hist
+        outs["last_scene_refit"] = [int(x) for x in refit]
+        return outs
 
     def dropin_virtuals(self, rays8, seed, pixel=0x7ACE):
         """bvh_node(world).hit + rec.mat->emitted / scatter through the drop-in classes (one device launch per call):
@@ -815,15 +836,22 @@ class Accumulator:
 
 class Temporal:
     """The history of a width x height frame across a moving camera (zr_temporal): blended colour, variance, history length and the
-    previous frame's geometry buffer and camera, all on the device."""
+    previous frame's geometry buffer and camera, all on the device.  track_motion: follow a world that Scene.refit moves (zr_temporal_track_motion,
+    DESIGN §18) — one refit between two frames is reprojected through its motion table, anything else restarts the frame."""
 
-    def __init__(self, ctx, width, height):
+    def __init__(self, ctx, width, height, track_motion=False):
         self.ctx = ctx
         self.lib = ctx.lib
         self.width, self.height = int(width), int(height)
         self._t = self.lib.zr_temporal_create(ctx._c, self.width, self.height)
         if not self._t:
             raise ZrError(self.lib.zr_last_error().decode())
+        if track_motion:
+            self.track_motion(True)
+
+    def track_motion(self, on):
+        """zr_temporal_track_motion: off (the default) leaves resetting after a refit to the caller"""
+        _check(self.lib.zr_temporal_track_motion(self._t, 1 if on else 0))
 
     def _outputs(self):
         shape = (self.height, self.width, 3)
@@ -851,6 +879,12 @@ class Temporal:
         _check(self.lib.zr_temporal_state(self._t, C.byref(out)))
         return {"width": out[0], "height": out[1], "frames": out[2]}
 
+    def tracks_motion(self):
+        """the switch track_motion sets: zr_temporal_state's fourth value"""
+        out = (C.c_int64 * 4)()
+        _check(self.lib.zr_temporal_state(self._t, C.byref(out)))
+        return bool(out[3])
+
     def close(self):
         if self._t:
             self.lib.zr_temporal_destroy(self._t)
@@ -861,6 +895,9 @@ class Temporal:
             self.close()
         except Exception:
             pass
+
+
+MOTION_STATIC, MOTION_CUT = 0xFFFFFFFF, 0xFFFFFFFE   # ZR_MOTION_STATIC, ZR_MOTION_CUT
 
 
 def temporal_view(camera):
@@ -953,6 +990,23 @@ class Scene:
         g = {"position": np.zeros((h, w, 3)), "normal": np.zeros((h, w, 3)), "t": np.zeros((h, w)), "mat": np.zeros((h, w), dtype=np.uint32)}
         _check(self.lib.zr_render_gbuffer(self.ctx._c, self._s, C.byref(camera), C.c_uint64(seed), *[a.ctypes.data for a in g.values()]))
         return g
+
+    def render_gbuffer_entries(self, camera, seed):
+        """zr_render_gbuffer_entries: the world-list entry under each pixel of render_gbuffer, (H, W) uint32, 0xFFFFFFFF on a miss (animated scenes only)"""
+        h, w = max(camera.image_height, 1), max(camera.image_width, 1)
+        out = np.zeros((h, w), dtype=np.uint32)
+        _check(self.lib.zr_render_gbuffer_entries(self.ctx._c, self._s, C.byref(camera), C.c_uint64(seed), out.ctypes.data))
+        return out
+
+    def motion(self):
+        """zr_scene_motion: the motion table of the last refit -> (slot per world-list entry, uint32: MOTION_STATIC, MOTION_CUT or a record's index;
+        records (n, 21) float64: a[12] rows of (linear 3, translation), nm[9] by rows)"""
+        n = C.c_size_t(0)
+        _check(self.lib.zr_scene_motion(self._s, None, None, 0, C.byref(n)))
+        slot = np.zeros(n.value, dtype=np.uint32); rec = np.zeros((max(n.value, 1), 21))
+        _check(self.lib.zr_scene_motion(self._s, slot.ctypes.data, rec.ctypes.data, n.value, C.byref(n)))
+        used = slot[slot < MOTION_CUT]
+        return slot, rec[:int(used.max()) + 1 if len(used) else 0].copy()
 
     PATH_RECORD = 17
 

@@ -540,7 +540,8 @@ int zr_scene_commit(zr_scene* s) {
     if (s->released) return fail(ZR_E_STATE, "the arrays given to zr_scene_set_all_borrowed were released by the previous commit: set the scene again");
     s->committed = false;
     HIP_OK(hipSetDevice(s->ctx->device));
-    s->stale = false; s->epoch = 0; s->refit.reset();   // what updates and refits built on the previous commit (the refit state holds device memory)
+    static std::atomic<uint64_t> commits{0};
+    s->stale = false; s->epoch = 0; s->serial = ++commits; s->refit.reset();   // (a new serial: a history tells a new commit from a refit)  // what updates and refits built on the previous commit (the refit state holds device memory)
     std::vector<zr_object>().swap(s->plan_objs); std::vector<uint8_t>().swap(s->plan_code); s->group_box.clear();
     PhaseTimer ph{"commit", 22};
     std::vector<zr_object> objs = world_list(*s);

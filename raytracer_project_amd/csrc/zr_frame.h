@@ -89,7 +89,7 @@ int check_nlm_params(const zr_denoise_nlm_params* dp);
 // zr_render.cpp, for zr_temporal.cpp: camera::initialize's frame, and zr_trace's body for rays that are on the device already
 void camera_frame(const zr_camera& cam, zr::DCamera& dc);
 int trace_device(zr_ctx* c, const zr_scene* s, const double* d_rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel, uint32_t bounce,
-                 zr_hit* d_hits);
+                 zr_hit* d_hits, uint2* d_ki = nullptr /* per ray the (kind, index) both engines hold where they fill zr_hit; all ones on a miss */);
 // zr_temporal.cpp, for zr_accum.cpp (zr_accum_temporal calls them): the parameter check, what a call checks before any device work (its null tests aside),
 // and one frame taken from device memory (d_color / d_variance: W*H*3 doubles, complete on the context's stream)
 int check_temporal_params(const zr_temporal_params* p);

@@ -177,8 +177,16 @@ struct zr_scene : SceneInput {   // the world as given (host side), then what th
     std::vector<zr::BuildBox> group_box; // per zr_group: the box of its triangles in their own space, as the builder that made the tree computed it
     bool stale = false;                  // an update changed the host copy of the world and no refit has followed: nothing may read the device scene
     uint64_t epoch = 0;                  // refits applied to this commit
+    uint64_t serial = 0;                 // of this commit among all commits of the process (an epoch alone restarts at 0): what a tracking zr_temporal remembers
     std::shared_ptr<RefitState> refit;   // reverse indices, leaf boxes, the trees' schedule, device buffers: made by the first update or refit after a commit, dropped by the next
 };
+
+// The motion table of a scene's last refit as the temporal stage reads it on the device (zr_update.cpp): the step epoch - 1 -> epoch.
+// leaf_word[leaf_base[kind] + index] = a slot among `records` (21 doubles each), ZR_MOTION_STATIC or ZR_MOTION_CUT.  All null for a scene no refit state exists for.
+struct MotionView { const uint32_t* leaf_word = nullptr; const double* records = nullptr; uint32_t leaf_base[8] = {}; uint32_t n_leaves = 0, n_slots = 0; };
+MotionView scene_motion_view(const zr_scene* s);
+// per leaf primitive of the world's tree (leaf_base[kind] + index) its world-list entry, on the device; builds the host half of the refit state if there is none
+int scene_leaf_entries(zr_scene* s, const uint32_t** d_leaf_entry, MotionView* view);
 
 // the small world's objects as the fused kernel's arguments (zr_launch.h: FusedObjs), read back from the device arrays: by a commit and again by a refit
 int refresh_fused_objects(zr_scene* s);

@@ -36,7 +36,7 @@ hipError_t launch_aov(const DScene& sc, const DCamera& cam, uint64_t seed, const
 hipError_t launch_passes(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, double* out_beauty, double* out_reflection,
                          double* out_refraction, unsigned long long* gctr, hipStream_t stream);
 hipError_t launch_path_records(const DScene& sc, const DCamera& cam, uint64_t seed, const int32_t* req, int n_req, int max_seg, double* out, hipStream_t stream);
-hipError_t launch_trace(const DScene& sc, const double* rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* out,
+hipError_t launch_trace(const DScene& sc, const double* rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* out, uint2* out_ki,
                         hipStream_t stream);
 }
 #endif
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(ZR_BLOCK) void aov_pixels(DScene sc, DCamera cam, u
 
 // known-answer kernel: world.hit(r, interval(tmin, tmax), rec) for a batch of rays, one ray per thread
 __global__ __launch_bounds__(ZR_BLOCK) void trace_rays(DScene sc, const double* __restrict__ rays, size_t n, double tmin, double tmax,
-                                                        uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* __restrict__ out) {
+                                                        uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* __restrict__ out, uint2* __restrict__ out_ki) {
     __shared__ uint32_t lds_stack[ZR_STACK_DEPTH * ZR_BLOCK];
     size_t k = (size_t)blockIdx.x * ZR_BLOCK + threadIdx.x;
     if (k >= n) return;
@@ -353,6 +353,7 @@ __global__ __launch_bounds__(ZR_BLOCK) void trace_rays(DScene sc, const double* 
         o.t = 0; o.u = 0; o.v = 0; o.mat = 0xFFFFFFFFu; o.front_face = 0;
     }
     out[k] = o;
+    if (out_ki) out_ki[k] = h ? make_uint2(kind, idx) : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);   // which leaf primitive answered (zr_render_gbuffer_entries)
 }
 
 // ---- per-function known-answer kernels (zr_kat_*): one thread = one call of the reference's virtual ---------------------
@@ -582,11 +583,11 @@ hipError_t launch_kat_camera_rays(const DCamera& cam, uint64_t seed, const int32
 }
 
 hipError_t launch_trace(const DScene& sc, const double* rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel,
-                        uint32_t bounce, zr_hit* out, hipStream_t stream) {
-    ZR_UV_DISPATCH(launch_trace(sc, rays, n, tmin, tmax, seed, pixel, bounce, out, stream))
+                        uint32_t bounce, zr_hit* out, uint2* out_ki, hipStream_t stream) {
+    ZR_UV_DISPATCH(launch_trace(sc, rays, n, tmin, tmax, seed, pixel, bounce, out, out_ki, stream))
     if (n == 0) return hipSuccess;
     dim3 grid((unsigned)((n + ZR_BLOCK - 1) / ZR_BLOCK)), block(ZR_BLOCK);
-    hipLaunchKernelGGL(trace_rays, grid, block, 0, stream, sc, rays, n, tmin, tmax, seed, pixel, bounce, out);
+    hipLaunchKernelGGL(trace_rays, grid, block, 0, stream, sc, rays, n, tmin, tmax, seed, pixel, bounce, out, out_ki);
     return hipGetLastError();
 }
 

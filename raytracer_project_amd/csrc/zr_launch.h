@@ -146,8 +146,9 @@ hipError_t launch_accum_halves(const double* partial, const uint32_t* pixels, co
 // flag and walk n_pix words, block_count ceil(n_pix / 256) words, n_walk one word.  ZR_SKY_SIEVE=1 puts a one-ray sieve in front (same flags, frame and list).
 hipError_t launch_sky_prepass(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const uint32_t* pixels, uint32_t n_pix, uint32_t spp,
                               uint32_t sample0, double* out, uint32_t* flag, uint32_t* block_count, uint32_t* walk, uint32_t* n_walk, hipStream_t stream);
-// closest hits of n rays in [0.001, inf) through the EXTEND kernel on ctx.streams[0]; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes
-hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, void* pool,
+// closest hits of n rays in [0.001, inf) through the EXTEND kernel on ctx.streams[0]; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes.  d_out_ki (may be null):
+// per ray the (kind, index) of the leaf primitive that answered, as closest_hit names it (a placed group: ZR_KIND_INSTANCE | instance << 8, the triangle); all ones on a miss
+hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, uint2* d_out_ki, void* pool,
                         const StreamContext& ctx, int leaf_level);
 hipError_t launch_aov(const DScene& sc, const DCamera& cam, uint64_t seed, const WorkDesc& wd, int aux, double zmax, const double* uvw9,
                       double* out_albedo, double* out_normal, double* out_zdepth, hipStream_t stream);
@@ -177,8 +178,13 @@ struct TemporalView { double center[3], pixel00[3], w[3], a[3], b[3], f; };
 struct TemporalPlanes { double* pos; double* nrm; uint32_t* mat; double* col; double* var; int32_t* len; };
 hipError_t launch_gbuffer_rays(const DCamera& cam, double* d_rays, hipStream_t stream);
 hipError_t launch_gbuffer_pack(const zr_hit* d_hits, const double* d_rays, size_t n, double* d_pos, double* d_nrm, double* d_t, uint32_t* d_mat, hipStream_t stream);
+// the motion of the refit between the history's frame and this one: this frame's (kind, index) plane as trace_device writes it, one word per leaf
+// primitive of the world's tree at leaf_base[kind] + index (a slot among `records`, ZR_MOTION_STATIC or ZR_MOTION_CUT), the records of 21 doubles
+struct TemporalMotion { const uint2* ki; const uint32_t* leaf_word; const double* records; uint32_t leaf_base[8]; uint32_t n_leaves, n_slots; };
 hipError_t launch_temporal_reproject(int W, int H, const TemporalView& cur, const TemporalView& prev, bool have_prev, const zr_temporal_params& tp,
-                                     const double* d_color, const double* d_variance, const TemporalPlanes& now, const TemporalPlanes& before, hipStream_t stream);
+                                     const double* d_color, const double* d_variance, const TemporalPlanes& now, const TemporalPlanes& before,
+                                     const TemporalMotion* motion /* null: no motion */, hipStream_t stream);
+hipError_t launch_gbuffer_entries(const TemporalMotion& mv, const uint32_t* d_leaf_entry, size_t n, uint32_t* d_out, hipStream_t stream);
 hipError_t launch_bvh_debug(const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const WorkDesc& wd, int level, float thickness, double* out,
                             hipStream_t stream);
 hipError_t launch_trace_bvh_debug(const DScene& sc, const double* rays, size_t n, double tmin, uint64_t seed, uint64_t pixel, uint32_t bounce, int level,
@@ -194,6 +200,6 @@ hipError_t launch_kat_texture(const DScene& sc, uint32_t tex, const double* uvp,
 hipError_t launch_kat_background(const DScene& sc, const DEnv& env, const double* dirs, size_t n, double* out, hipStream_t stream);
 hipError_t launch_kat_camera_rays(const DCamera& cam, uint64_t seed, const int32_t* req, size_t n, double* out, hipStream_t stream);
 hipError_t launch_trace(const DScene& sc, const double* rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel,
-                        uint32_t bounce, zr_hit* out, hipStream_t stream);
+                        uint32_t bounce, zr_hit* out, uint2* out_ki /* may be null: as stream_trace's */, hipStream_t stream);
 
 }  // namespace zr

@@ -36,6 +36,8 @@ struct RefitLevel { uint32_t first, count, block0; };
 struct RefitResult { NodeF root; uint32_t quant_fail; uint32_t pad_[3]; };
 
 hipError_t refit_patch(hipStream_t st, const RefitScene& sc, const RefitBoxPatch* d_box, uint32_t n_box, const RefitRecPatch* d_rec, uint32_t n_rec, const double* d_payload);
+// the motion table's leaf words: d_pairs holds n pairs of 32-bit words (leaf address, new word), each address once; addresses >= n_leaves are ignored
+hipError_t refit_motion(hipStream_t st, const void* d_pairs, uint32_t n, uint32_t* d_leaf_word, uint32_t n_leaves);
 // the 4-wide tree: levels deepest first, then the FP32 root from `root` (its references; the boxes are rewritten) into result->root
 hipError_t refit_quads(hipStream_t st, const RefitScene& sc, const uint32_t* d_order, const RefitLevel* levels, size_t n_levels, const NodeF& root, RefitResult* d_result);
 // the pair records: levels deepest first; d_partial[level.block0 + block] = the sum of the half-areas of the child boxes the block wrote

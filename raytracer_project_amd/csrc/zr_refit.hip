@@ -1,6 +1,7 @@
 // zr_refit.hip — the device side of zr_scene_refit (zr_refit.h): a moved world keeps its trees and gets their boxes anew.
 //
 //   k_refit_patch   one thread per patch: the moved leaf primitives' boxes into the per-kind box arrays, their records into the scene's primitive arrays
+//   k_refit_motion  one thread per leaf word of the motion table that changes: a slot among the refit's motion records, STATIC or CUT (zr_motion.h)
 //   k_refit_quads   one launch per level of the world's 4-wide tree, deepest first, one thread per node: every child's TRUE box — a leaf's is the union of its
 //                   1-4 primitives' boxes, an inner child's was written to the side array by the launch before — goes onto a fresh 8-bit grid with the
 //                   builder's own quant_axis (zr_quant.h), and the node's own true box goes to the side array for its parent.  References are not touched.
@@ -152,6 +153,20 @@ __global__ __launch_bounds__(256) void k_refit_pairs(RefitScene sc, const uint32
 inline dim3 grid_for(uint32_t n) { return dim3((n + 255u) / 256u); }
 
 }  // namespace
+
+// the motion table's leaf words: one thread per (leaf address, word) pair; an address names a leaf primitive of the world's tree once per call
+__global__ __launch_bounds__(256) void k_refit_motion(const uint2* __restrict__ pairs, uint32_t n, uint32_t* __restrict__ leaf_word, uint32_t n_leaves) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint2 p = pairs[i];
+    if (p.x < n_leaves) leaf_word[p.x] = p.y;
+}
+
+hipError_t refit_motion(hipStream_t st, const void* d_pairs, uint32_t n, uint32_t* d_leaf_word, uint32_t n_leaves) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_refit_motion, grid_for(n), dim3(256), 0, st, (const uint2*)d_pairs, n, d_leaf_word, n_leaves);
+    return hipGetLastError();
+}
 
 hipError_t refit_patch(hipStream_t st, const RefitScene& sc, const RefitBoxPatch* d_box, uint32_t n_box, const RefitRecPatch* d_rec, uint32_t n_rec, const double* d_payload) {
     const uint32_t n = n_box > n_rec ? n_box : n_rec;

@@ -508,7 +508,7 @@ void camera_frame(const zr_camera& cam, zr::DCamera& dc) { make_camera(cam, dc);
 // world.hit(r, interval(tmin, tmax), rec) for n rays that are on the device already: what zr_trace does once its rays are uploaded, and where the geometry
 // buffer's centre rays enter (zr_temporal.cpp).  The context's stream is idle on return.
 int trace_device(zr_ctx* c, const zr_scene* s, const double* d_rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel, uint32_t bounce,
-                 zr_hit* d_hits) {
+                 zr_hit* d_hits, uint2* d_ki) {
     // Two engines answer the same question: the pair-BVH walk of variants 0/1 and — for the render interval
     // [0.001, inf) — the EXTEND kernel of the streaming pipeline.  ZR_TRACE_ENGINE=pairs|extend picks one (tests run
     // both); by default the engine of the active render variant is used.
@@ -523,13 +523,13 @@ int trace_device(zr_ctx* c, const zr_scene* s, const double* d_rays, size_t n, d
         if ((rc = pool.alloc(zr::stream_pool_bytes((uint32_t)n) + 65536))) return rc;
         HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), c->stream));
         const zr::StreamContext ctx{c->d_ctl.p, c->d_st_overflow.p, c->st_ovf_levels, c->st_blocks, c->d_ctr.p, &c->stream, 1, c->st_event, c->h_active};
-        HIP_OK(zr::stream_trace(s->ds, d_rays, (uint32_t)n, seed, pixel, bounce, d_hits, pool.p, ctx, s->leaf_level));
+        HIP_OK(zr::stream_trace(s->ds, d_rays, (uint32_t)n, seed, pixel, bounce, d_hits, d_ki, pool.p, ctx, s->leaf_level));
         HIP_OK(hipStreamSynchronize(c->stream));
         unsigned int capped = 0;
         HIP_OK(hipMemcpy(&capped, c->d_ctl.p + zr::CTL_CAPPED, sizeof capped, hipMemcpyDeviceToHost));
         if (capped) return fail(ZR_E_DEVICE, "EXTEND hit its iteration cap on %u wave(s)", capped);
     } else {
-        HIP_OK(zr::launch_trace(s->ds, d_rays, n, tmin, tmax, seed, pixel, bounce, d_hits, c->stream));
+        HIP_OK(zr::launch_trace(s->ds, d_rays, n, tmin, tmax, seed, pixel, bounce, d_hits, d_ki, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
     }
     return ZR_OK;

@@ -325,6 +325,45 @@ int zrs_render_dropin_animated(void* p, int width, int height, int spp, int devi
     return 0;
 }
 
+// zrs_render_dropin_animated's world and camera with camera::temporal_accumulation through a progressive render (samples_per_pass = 64: the variance the
+// history needs).  flags: 1 = reuse_scene, 2 = temporal_accumulation, 4 = temporal_track_motion.  Outputs, n_frames frames each, any may be null:
+// render_accumulator, temporal_buffer (all -1 for a frame that left it empty), temporal_history_length (-1 likewise), last_scene_refit.
+int zrs_render_dropin_animated_temporal(void* p, int width, int height, int spp, int device, int n_frames, int flags, double* acc, double* tmp, int* hist, int* refit) {
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
+    cam.reuse_scene = (flags & 1) != 0; cam.temporal_accumulation = (flags & 2) != 0; cam.temporal_track_motion = (flags & 4) != 0;
+    cam.samples_per_pass = 64;
+    cam.max_depth = 8; cam.vfov = 40; cam.defocus_angle = 0;
+    cam.lookfrom = point3(0.5, 2.5, 7); cam.lookat = point3(0.3, 0.4, 0); cam.vup = vec3(0, 1, 0);
+    const auto ground = make_shared<lambertian>(color(0.5, 0.6, 0.4)), red = make_shared<lambertian>(color(0.8, 0.2, 0.2)), blue = make_shared<lambertian>(color(0.2, 0.3, 0.8));
+    const shared_ptr<hittable> box = make_shared<cube>(point3(-0.5, -0.5, -0.5), point3(0.5, 0.5, 0.5), red);
+    const post_processor post;
+    const size_t npx = (size_t)cam.image_width * cam.image_height;
+    for (int k = 0; k < n_frames; k++) {
+        hittable_list world;   // (frame k of zrs_render_dropin_animated without the added object)
+        world.add(make_shared<sphere>(point3(0, -100.5, 0), 100.0, ground));
+        world.add(make_shared<sphere>(point3(0.2, 0.3 + 0.15 * k, 1.5), 0.4, blue));
+        world.add(make_shared<translate>(make_shared<rotate_y>(box, 0.3 + 0.25 * k), vec3(-1.2 + 0.4 * k, 0.0, 0.0)));
+        world.add(make_shared<translate>(make_shared<rotate_y>(box, -0.2 * k), vec3(1.6, 0.2 * k, -1.0)));
+        const auto bvh_world = make_shared<bvh_node>(world);
+        cam.reset_accumulator();
+        std::atomic<bool> flag{true};
+        cam.render(*bvh_world, h.s.env, post, flag);
+        if (cam.lines_rendered.load() != cam.image_height) return -1;
+        if (acc) std::memcpy(acc + (size_t)k * npx * 3, cam.render_accumulator.data(), npx * sizeof(color));
+        if (tmp) {
+            if (cam.temporal_buffer.size() == npx) std::memcpy(tmp + (size_t)k * npx * 3, cam.temporal_buffer.data(), npx * sizeof(color));
+            else std::fill(tmp + (size_t)k * npx * 3, tmp + (size_t)(k + 1) * npx * 3, -1.0);
+        }
+        if (hist) {
+            if (cam.temporal_history_length.size() == npx) std::memcpy(hist + (size_t)k * npx, cam.temporal_history_length.data(), npx * sizeof(int));
+            else std::fill(hist + (size_t)k * npx, hist + (size_t)(k + 1) * npx, -1);
+        }
+        if (refit) refit[k] = cam.last_scene_refit;
+    }
+    return 0;
+}
+
 // The reference's per-ray virtual API through the drop-in classes: for n rays (o, d, tmin, tmax) calls
 // bvh_node(world).hit(r, interval(tmin, tmax), rec), then rec.mat->emitted(...) and rec.mat->scatter(r, rec, att, scattered)
 // with random_double() positioned on the stream (seed, pixel, k) — the layout of `zenith_ref kat <scene> hits`:

@@ -1242,7 +1242,7 @@ __global__ __launch_bounds__(256) void stream_load_rays(StreamBuf B, const doubl
 }
 
 template <bool UV>
-__global__ __launch_bounds__(256) void stream_hits_out(DScene sc, StreamBuf B, uint32_t n, zr_hit* __restrict__ out) {
+__global__ __launch_bounds__(256) void stream_hits_out(DScene sc, StreamBuf B, uint32_t n, zr_hit* __restrict__ out, uint2* __restrict__ out_ki) {
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
     if (slot >= n) return;
     const uint2 ki = B.ld2(SF_HIT_KI, slot);
@@ -1261,6 +1261,7 @@ __global__ __launch_bounds__(256) void stream_hits_out(DScene sc, StreamBuf B, u
         o.t = 0; o.u = 0; o.v = 0; o.mat = 0xFFFFFFFFu; o.front_face = 0;
     }
     out[slot] = o;
+    if (out_ki) out_ki[slot] = ki.x != 0xFFFFFFFFu ? ki : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);   // as trace_rays reports it
 }
 
 // ---- host-side launch helpers -----------------------------------------------------------------------------------
@@ -1634,7 +1635,7 @@ hipError_t launch_accum_resolve(const double* partial, const uint32_t* pixels, u
 }
 
 // closest hits of n rays in [0.001, inf) through the EXTEND kernel; `pool` holds stream_pool_bytes(round_up(n, 64)) bytes
-hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, void* pool,
+hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint64_t seed, uint64_t pixel, uint32_t bounce, zr_hit* d_out, uint2* d_out_ki, void* pool,
                         const StreamContext& X, int leaf_level) {
     hipStream_t stream = X.streams[0];
     if (n == 0) return hipSuccess;
@@ -1646,8 +1647,8 @@ hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint
     hipLaunchKernelGGL(stream_load_rays, dim3((P + 255) / 256), dim3(256), 0, stream, B, d_rays, n, seed, pixel, bounce);
     const int eb = (int)(P / 64 < (uint32_t)X.extend_blocks ? P / 64 : (uint32_t)X.extend_blocks);
     launch_extend<false>(sc, B, X.overflow, X.ovf_levels, eb, X.gctr, leaf_level, stream);
-    if (sc.tri_uv_at) hipLaunchKernelGGL(stream_hits_out<true>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out);
-    else hipLaunchKernelGGL(stream_hits_out<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out);
+    if (sc.tri_uv_at) hipLaunchKernelGGL(stream_hits_out<true>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out, d_out_ki);
+    else hipLaunchKernelGGL(stream_hits_out<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out, d_out_ki);
     return hipGetLastError();
 }
 

@@ -23,9 +23,9 @@ bool view_finite(const zr::TemporalView& v) {
 static_assert(sizeof(zr::TemporalView) == 16 * sizeof(double), "a view is 16 doubles");
 
 // The centre rays of `dc` through zr_trace's route into d_hits (npx records), the rays left in d_rays (npx * 6 doubles).  The context's stream is idle on return.
-int gbuffer_device(zr_ctx* c, const zr_scene* s, const zr::DCamera& dc, uint64_t seed, double* d_rays, zr_hit* d_hits) {
+int gbuffer_device(zr_ctx* c, const zr_scene* s, const zr::DCamera& dc, uint64_t seed, double* d_rays, zr_hit* d_hits, uint2* d_ki = nullptr) {
     HIP_OK(zr::launch_gbuffer_rays(dc, d_rays, c->stream));
-    return trace_device(c, s, d_rays, (size_t)dc.W * dc.H, 0.001, HUGE_VAL, seed, ZR_GBUFFER_STREAM, 0, d_hits);
+    return trace_device(c, s, d_rays, (size_t)dc.W * dc.H, 0.001, HUGE_VAL, seed, ZR_GBUFFER_STREAM, 0, d_hits, d_ki);
 }
 
 template <class T>
@@ -47,6 +47,10 @@ struct zr_temporal {
     struct Half { DevBuf<double> pos, nrm, col, var; DevBuf<uint32_t> mat; DevBuf<int32_t> len; } half[2];
     DevBuf<double> d_rays, d_in_color, d_in_variance;
     DevBuf<zr_hit> d_hits;
+    // motion tracking (zr_temporal_track_motion): the scene, commit and epoch of the frame in half `cur`, and this frame's (kind, index) plane
+    bool track = false;
+    const zr_scene* held_scene = nullptr; uint64_t held_serial = 0, held_epoch = 0;
+    DevBuf<uint2> d_ki;
     size_t npx() const { return (size_t)W * H; }
     zr::TemporalPlanes planes(int k) { Half& h = half[k]; return zr::TemporalPlanes{h.pos.p, h.nrm.p, h.mat.p, h.col.p, h.var.p, h.len.p}; }
 };
@@ -77,13 +81,27 @@ int temporal_accumulate_device(zr_temporal* t, const zr_temporal_params* p, cons
     zr::DCamera dc; zr::TemporalView v;
     camera_frame(*cam, dc); make_view(*cam, dc, v);
     const int nxt = t->cur ^ 1;
-    int rc = gbuffer_device(c, s, dc, seed, t->d_rays.p, t->d_hits.p);
-    if (rc) return rc;
+    // a tracking history: the same world -> the static path; one refit later -> the motion build with the scene's table; anything else -> the frame restarts
+    zr::TemporalMotion mv{}; bool moved = false;
+    int rc;
+    if (t->track && t->frames > 0) {
+        const bool same = t->held_scene == s && t->held_serial == s->serial;
+        if (same && s->epoch == t->held_epoch + 1) {
+            const MotionView m = scene_motion_view(s);
+            if (!m.leaf_word) return fail(ZR_E_DEVICE, "temporal: a refitted scene without a motion table (internal error)");
+            if ((rc = t->d_ki.alloc(t->npx()))) return rc;
+            mv.ki = t->d_ki.p; mv.leaf_word = m.leaf_word; mv.records = m.records; std::memcpy(mv.leaf_base, m.leaf_base, sizeof mv.leaf_base);
+            mv.n_leaves = m.n_leaves; mv.n_slots = m.n_slots;
+            moved = true;
+        } else if (!(same && s->epoch == t->held_epoch)) t->frames = 0;
+    }
+    if ((rc = gbuffer_device(c, s, dc, seed, t->d_rays.p, t->d_hits.p, moved ? t->d_ki.p : nullptr))) return rc;
     const zr::TemporalPlanes now = t->planes(nxt), before = t->planes(t->cur);
     HIP_OK(zr::launch_gbuffer_pack(t->d_hits.p, t->d_rays.p, t->npx(), now.pos, now.nrm, nullptr, now.mat, c->stream));
-    HIP_OK(zr::launch_temporal_reproject(t->W, t->H, v, t->view, t->frames > 0, *p, d_color, d_variance, now, before, c->stream));
+    HIP_OK(zr::launch_temporal_reproject(t->W, t->H, v, t->view, t->frames > 0, *p, d_color, d_variance, now, before, moved ? &mv : nullptr, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     t->cur = nxt; t->view = v; t->frames++;
+    t->held_scene = s; t->held_serial = s->serial; t->held_epoch = s->epoch;
     if ((rc = copy_out(out_color, now.col, t->npx() * 3)) || (rc = copy_out(out_variance, now.var, t->npx() * 3)) || (rc = copy_out(out_history, now.len, t->npx()))) return rc;
     return ZR_OK;
 }
@@ -144,9 +162,36 @@ int zr_temporal_reset(zr_temporal* t) {
     return ZR_OK;
 }
 
+int zr_temporal_track_motion(zr_temporal* t, int on) {
+    if (!t) return fail(ZR_E_INVALID, "null argument");
+    t->track = on != 0;
+    return ZR_OK;
+}
+
+int zr_render_gbuffer_entries(zr_ctx* c, zr_scene* s, const zr_camera* cam, uint64_t seed, uint32_t* out_entry) {
+    if (!c || !s || !cam) return fail(ZR_E_INVALID, "null argument");
+    int rc = scene_ready(c, s, "zr_render_gbuffer_entries");
+    if (rc) return rc;
+    HIP_OK(hipSetDevice(c->device));
+    const uint32_t* d_leaf_entry = nullptr; MotionView m;
+    if ((rc = scene_leaf_entries(s, &d_leaf_entry, &m))) return rc;
+    if (!out_entry) return ZR_OK;
+    zr::DCamera dc;
+    camera_frame(*cam, dc);
+    const size_t n = (size_t)dc.W * dc.H;
+    DevBuf<double> d_rays; DevBuf<zr_hit> d_hits; DevBuf<uint2> d_ki; DevBuf<uint32_t> d_out;
+    if ((rc = d_rays.alloc(n * 6)) || (rc = d_hits.alloc(n)) || (rc = d_ki.alloc(n)) || (rc = d_out.alloc(n))) return rc;
+    if ((rc = gbuffer_device(c, s, dc, seed, d_rays.p, d_hits.p, d_ki.p))) return rc;
+    zr::TemporalMotion mv{};
+    mv.ki = d_ki.p; std::memcpy(mv.leaf_base, m.leaf_base, sizeof mv.leaf_base); mv.n_leaves = m.n_leaves;
+    HIP_OK(zr::launch_gbuffer_entries(mv, d_leaf_entry, n, d_out.p, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return copy_out(out_entry, d_out.p, n);
+}
+
 int zr_temporal_state(const zr_temporal* t, int64_t out[4]) {
     if (!t || !out) return fail(ZR_E_INVALID, "null argument");
-    out[0] = t->W; out[1] = t->H; out[2] = t->frames; out[3] = 0;
+    out[0] = t->W; out[1] = t->H; out[2] = t->frames; out[3] = t->track ? 1 : 0;
     return ZR_OK;
 }
 

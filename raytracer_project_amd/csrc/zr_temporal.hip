@@ -17,6 +17,14 @@
 //     5. no counting tap: N = 1, out = c, V_out = V.  Else sw = sum w, h = (sum w h_q) / sw, Vh = (sum w V_q) / sw, N = min(min N_q + 1, max_history),
 //        beta = max(1.0 / N, alpha), out = h + beta (c - h), om = 1 - beta, V_out = (om om) Vh + (beta beta) V
 //     6. out, V_out, N are written to the other half of the history; the caller swaps the halves and the views
+//   temporal_reproject<true>  the motion build (its restatement: tests/temporal_motion_model.py), for a frame one refit after the history's.  A hit pixel's
+//     (kind, index) names a leaf primitive of the world's tree (a placed group's triangle: the placement, kind >> 8) and so a word of the refit's motion table:
+//       STATIC, or a miss: Xr = X_p, nr = n_p — the steps above exactly.   CUT: no history, N = 1.
+//       a slot: with its record a[12], nm[9]:  Xr_k = ((a[4k] x + a[4k+1] y) + a[4k+2] z) + a[4k+3],  g_k = (nm[3k] nx + nm[3k+1] ny) + nm[3k+2] nz,
+//       l = sqrt(g . g), nr = g / l; no history unless l > 0.
+//     Step 2 projects Xr (d = Xr - center'); depth_p stays that of X_p in the current view.  Step 4 tests |(X_q - Xr) . nr| <= plane_tolerance depth_p and
+//     nr . n_q >= normal_cos.  Everything else is unchanged.
+//   gbuffer_entries     the (kind, index) plane -> the world-list entry under each pixel through the refit state's inverted slot array; 0xFFFFFFFF on a miss
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -66,9 +74,27 @@ __global__ __launch_bounds__(256) void gbuffer_pack(const zr_hit* __restrict__ h
 __device__ __forceinline__ double clean(double v) { return isfinite(v) ? v : 0.0; }
 __device__ __forceinline__ double clean_var(double v) { return isfinite(v) && v > 0.0 ? v : 0.0; }
 
+// the leaf primitive (kind, index) names, as an address into the per-leaf arrays of the refit state; n_leaves (never an address) when it names none
+__device__ __forceinline__ uint32_t leaf_address(const TemporalMotion& mv, uint2 ki) {
+    const uint32_t k = ki.x & 0xFFu, idx = k == ZR_KIND_INSTANCE ? ki.x >> 8 : ki.y;
+    if (ki.x == 0xFFFFFFFFu || k >= 7u) return mv.n_leaves;
+    uint32_t base = 0, top = 0;   // (selects, not an indexed read of the kernel arguments)
+#pragma unroll
+    for (uint32_t kk = 0; kk < 7u; kk++) { base = k == kk ? mv.leaf_base[kk] : base; top = k == kk ? mv.leaf_base[kk + 1] : top; }
+    return top <= mv.n_leaves && base <= top && idx < top - base ? base + idx : mv.n_leaves;
+}
+
+__global__ __launch_bounds__(256) void gbuffer_entries(TemporalMotion mv, const uint32_t* __restrict__ leaf_entry, size_t n, uint32_t* __restrict__ out) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t at = leaf_address(mv, mv.ki[p]);
+    out[p] = at < mv.n_leaves ? leaf_entry[at] : 0xFFFFFFFFu;
+}
+
+template <bool MOTION>
 __global__ __launch_bounds__(256) void temporal_reproject(int W, int H, TemporalView cur, TemporalView prev, int have_prev, zr_temporal_params tp,
                                                           const double* __restrict__ color, const double* __restrict__ variance, TemporalPlanes now,
-                                                          TemporalPlanes before) {
+                                                          TemporalPlanes before, TemporalMotion mv) {
     const int i = blockIdx.x * 16 + threadIdx.x, j = blockIdx.y * 16 + threadIdx.y;
     if (i >= W || j >= H) return;
     const size_t p = (size_t)j * W + i;
@@ -81,10 +107,32 @@ __global__ __launch_bounds__(256) void temporal_reproject(int W, int H, Temporal
 
     double sw = 0.0, sh[3] = {0.0, 0.0, 0.0}, sv[3] = {0.0, 0.0, 0.0};
     int min_n = 0x7FFFFFFF;
-    if (have_prev) {
+    double Xr[3] = {X[0], X[1], X[2]}, nr[3] = {n[0], n[1], n[2]};   // where the pixel's point was in the history's frame, and its normal there
+    bool followed = true;
+    if constexpr (MOTION) {
+        if (hit && have_prev) {
+            const uint32_t at = leaf_address(mv, mv.ki[p]);
+            const uint32_t word = at < mv.n_leaves ? mv.leaf_word[at] : ZR_MOTION_STATIC;
+            if (word == ZR_MOTION_CUT) followed = false;
+            else if (word < mv.n_slots) {
+                const double* __restrict__ a = mv.records + (size_t)word * 21;
+                const double* __restrict__ nm = a + 12;
+                double g[3];
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    Xr[k] = ((a[4 * k] * X[0] + a[4 * k + 1] * X[1]) + a[4 * k + 2] * X[2]) + a[4 * k + 3];
+                    g[k] = (nm[3 * k] * n[0] + nm[3 * k + 1] * n[1]) + nm[3 * k + 2] * n[2];
+                }
+                const double l = sqrt(dot3(g[0], g[1], g[2], g[0], g[1], g[2]));
+                if (l > 0.0) { nr[0] = g[0] / l; nr[1] = g[1] / l; nr[2] = g[2] / l; }
+                else followed = false;
+            }
+        }
+    }
+    if (have_prev && followed) {
         double d[3];
 #pragma unroll
-        for (int k = 0; k < 3; k++) d[k] = hit ? X[k] - prev.center[k] : X[k];
+        for (int k = 0; k < 3; k++) d[k] = hit ? Xr[k] - prev.center[k] : Xr[k];
         const double zc = -dot3(d[0], d[1], d[2], prev.w[0], prev.w[1], prev.w[2]);
         if (zc > 0.0) {
             const double s = prev.f / zc;
@@ -114,9 +162,9 @@ __global__ __launch_bounds__(256) void temporal_reproject(int W, int H, Temporal
                         const int nq = before.len[qi];
                         if (nq <= 0 || before.mat[qi] != m) continue;
                         if (hit) {
-                            const double ex = before.pos[3 * qi] - X[0], ey = before.pos[3 * qi + 1] - X[1], ez = before.pos[3 * qi + 2] - X[2];
-                            if (!(fabs(dot3(ex, ey, ez, n[0], n[1], n[2])) <= bound)) continue;
-                            if (!(dot3(n[0], n[1], n[2], before.nrm[3 * qi], before.nrm[3 * qi + 1], before.nrm[3 * qi + 2]) >= tp.normal_cos)) continue;
+                            const double ex = before.pos[3 * qi] - Xr[0], ey = before.pos[3 * qi + 1] - Xr[1], ez = before.pos[3 * qi + 2] - Xr[2];
+                            if (!(fabs(dot3(ex, ey, ez, nr[0], nr[1], nr[2])) <= bound)) continue;
+                            if (!(dot3(nr[0], nr[1], nr[2], before.nrm[3 * qi], before.nrm[3 * qi + 1], before.nrm[3 * qi + 2]) >= tp.normal_cos)) continue;
                         }
                         sw = sw + w;
 #pragma unroll
@@ -165,11 +213,21 @@ hipError_t launch_gbuffer_pack(const zr_hit* d_hits, const double* d_rays, size_
 }
 
 // now: this frame's geometry planes (read) and the history half that receives out / V_out / N; before: the previous frame's planes and history (read; ignored
-// without have_prev).  The caller has validated the parameters.
+// without have_prev).  motion (may be null: the build without motion): this frame's (kind, index) plane and the table of the refit between `before` and `now`.
+// The caller has validated the parameters.
 hipError_t launch_temporal_reproject(int W, int H, const TemporalView& cur, const TemporalView& prev, bool have_prev, const zr_temporal_params& tp,
-                                     const double* d_color, const double* d_variance, const TemporalPlanes& now, const TemporalPlanes& before, hipStream_t stream) {
+                                     const double* d_color, const double* d_variance, const TemporalPlanes& now, const TemporalPlanes& before,
+                                     const TemporalMotion* motion, hipStream_t stream) {
     const dim3 block(16, 16), grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
-    hipLaunchKernelGGL(temporal_reproject, grid, block, 0, stream, W, H, cur, prev, have_prev ? 1 : 0, tp, d_color, d_variance, now, before);
+    if (motion) hipLaunchKernelGGL(temporal_reproject<true>, grid, block, 0, stream, W, H, cur, prev, have_prev ? 1 : 0, tp, d_color, d_variance, now, before, *motion);
+    else hipLaunchKernelGGL(temporal_reproject<false>, grid, block, 0, stream, W, H, cur, prev, have_prev ? 1 : 0, tp, d_color, d_variance, now, before, TemporalMotion{});
+    return hipGetLastError();
+}
+
+// out[p] = the world-list entry of the leaf primitive mv.ki[p] names (d_leaf_entry: mv.n_leaves words), 0xFFFFFFFF on a miss
+hipError_t launch_gbuffer_entries(const TemporalMotion& mv, const uint32_t* d_leaf_entry, size_t n, uint32_t* d_out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(gbuffer_entries, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, mv, d_leaf_entry, n, d_out);
     return hipGetLastError();
 }
 

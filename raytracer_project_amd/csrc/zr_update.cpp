@@ -4,6 +4,7 @@
 #include "zr_host_internal.h"
 #include "zr_refit.h"
 #include "zr_update.h"
+#include "zr_motion.h"
 
 // What a refit works from, made once per commit (by the first update or refit after it) and dropped by the next commit.
 struct RefitState {
@@ -20,6 +21,14 @@ struct RefitState {
     // pinned staging: the patches, the changed ops, the read-back
     zr::RefitBoxPatch* h_box = nullptr; zr::RefitRecPatch* h_rec = nullptr; double* h_payload = nullptr; zr_xform_op* h_ops = nullptr; unsigned char* h_result = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the motion of the last refit (zr_motion.h).  Host: every movable entry's map as of the previous epoch and the last refit's records; per leaf
+    // primitive of the world's tree, addressed leaf_base[kind] + index, its entry.  Device, allocated with the rest and never again: one word per leaf primitive
+    // (a slot, STATIC, CUT); the records live in d_payload behind the record patches, from motion_at on, until the next refit overwrites them.
+    MotionTable motion;
+    std::vector<uint32_t> leaf_entry; uint32_t leaf_base[8] = {}, n_leaves = 0;
+    DevBuf<uint32_t> d_leaf_word, d_leaf_entry;
+    std::vector<uint32_t> marked;        // the entries whose leaf word on the device is not STATIC
+    size_t motion_at = 0;
     double area0 = 0;                    // sum of the half-areas of the world tree's pair boxes as the refit kernels compute it over the committed world
     ~RefitState() {
         for (void* p : {(void*)h_box, (void*)h_rec, (void*)h_payload, (void*)h_ops, (void*)h_result}) if (p) (void)hipHostFree(p);
@@ -85,6 +94,11 @@ int ensure_index(zr_scene* s) {
         }
     });
     if (bad.load() != (size_t)-1) return fail(ZR_E_DEVICE, "refit: committed entry %zu has a box that is not finite (internal error)", bad.load());
+    for (int k = 0; k < 7; k++) st->leaf_base[k + 1] = st->leaf_base[k] + s->plan_cnt[k];
+    st->n_leaves = st->leaf_base[7];
+    st->leaf_entry.assign(st->n_leaves, kNoSlot);
+    for (size_t oi = 0; oi < w.objs.size(); oi++) st->leaf_entry[st->leaf_base[w.kind(oi)] + st->ix.slot[oi]] = (uint32_t)oi;
+    st->motion.build(w);
     s->refit = std::move(st);
     return ZR_OK;
 }
@@ -203,7 +217,9 @@ int ensure_device(zr_scene* s, RefitState& st) {
     int rc;
     for (int k = 0; k < 7; k++) { if ((rc = st.prim_box[k].upload(st.host_box[k]))) return rc; std::vector<float>().swap(st.host_box[k]); }
     if ((rc = st.quad_box.alloc(s->d_quads.n * 6)) || (rc = st.pair_box.alloc(s->d_nodes.n * 6)) || (rc = st.d_result.alloc(st.result_bytes()))) return rc;
-    const size_t m = st.ix.movable, md = st.ix.movable_doubles, n_ops = s->ops.size();
+    const size_t m = st.ix.movable, md = st.ix.movable_doubles + m * (kMotionDoubles + 2), n_ops = s->ops.size();   // (behind the record patches: the motion records, then two leaf-word pairs per entry)
+    if ((rc = st.d_leaf_word.alloc(st.n_leaves))) return rc;
+    HIP_OK(hipMemset(st.d_leaf_word.p, 0xFF, std::max<size_t>(st.n_leaves * sizeof(uint32_t), 4)));   // ZR_MOTION_STATIC
     if ((rc = st.d_box.alloc(m)) || (rc = st.d_rec.alloc(m)) || (rc = st.d_payload.alloc(md))) return rc;
     if ((rc = pinned(st.h_box, m)) || (rc = pinned(st.h_rec, m)) || (rc = pinned(st.h_payload, md)) || (rc = pinned(st.h_ops, n_ops)) || (rc = pinned(st.h_result, st.result_bytes()))) return rc;
     HIP_OK(hipEventCreate(&st.ev0));
@@ -250,19 +266,32 @@ int refit(zr_scene* s, zr_refit_info& info) {
         }
     });
     if (bad.load() != (size_t)-1) return fail(ZR_E_INVALID, "refit: world-list entry %zu has a box that is not finite: commit anew", bad.load());
+    // 1b. the motion of this step (zr_motion.h): records behind the record patches, then one (leaf address, word) pair per entry whose word changes — the entries
+    // of the previous table that did not move again go back to STATIC.  They ride in the payload copy; the table is the scene's from here on.
+    st.motion.step(w, ix.dirty_list);
+    st.motion_at = rec_at[nd];
+    const size_t n_mrec = st.motion.records.size();
+    if (n_mrec) std::memcpy(st.h_payload + st.motion_at, st.motion.records.data(), n_mrec * sizeof(double));
+    uint32_t* pairs = (uint32_t*)(st.h_payload + st.motion_at + n_mrec);
+    uint32_t n_pairs = 0;
+    auto leaf_of = [&](uint32_t oi) { return st.leaf_base[w.kind(oi)] + ix.slot[oi]; };
+    for (uint32_t oi : st.marked) if (!ix.dirty[oi]) { pairs[2 * n_pairs] = leaf_of(oi); pairs[2 * n_pairs + 1] = kMotionStatic; n_pairs++; }
+    for (size_t k = 0; k < nd; k++) { pairs[2 * n_pairs] = leaf_of(ix.dirty_list[k]); pairs[2 * n_pairs + 1] = st.motion.slot[k]; n_pairs++; }
+    st.marked = ix.dirty_list;
+    const size_t payload_doubles = st.motion_at + n_mrec + n_pairs;
+    if (payload_doubles > st.d_payload.n) return fail(ZR_E_DEVICE, "refit: motion table beyond its buffer (internal error)");
     // 2. everything on the context's stream: patches and the changed ops up, scatter, the trees level by level, one read-back
     HIP_OK(hipEventRecord(st.ev0, q));
     const uint32_t n_rec = rec_no[nd];
     if (nd) HIP_OK(hipMemcpyAsync(st.d_box.p, st.h_box, nd * sizeof(zr::RefitBoxPatch), hipMemcpyHostToDevice, q));
-    if (n_rec) {
-        HIP_OK(hipMemcpyAsync(st.d_rec.p, st.h_rec, n_rec * sizeof(zr::RefitRecPatch), hipMemcpyHostToDevice, q));
-        HIP_OK(hipMemcpyAsync(st.d_payload.p, st.h_payload, (size_t)rec_at[nd] * sizeof(double), hipMemcpyHostToDevice, q));
-    }
+    if (n_rec) HIP_OK(hipMemcpyAsync(st.d_rec.p, st.h_rec, n_rec * sizeof(zr::RefitRecPatch), hipMemcpyHostToDevice, q));
+    if (payload_doubles) HIP_OK(hipMemcpyAsync(st.d_payload.p, st.h_payload, payload_doubles * sizeof(double), hipMemcpyHostToDevice, q));
     if (ix.op_hi > ix.op_lo) {   // the chains of wrapped objects, media and placed groups live here: patched as one range
         std::memcpy(st.h_ops, s->ops.data() + ix.op_lo, (ix.op_hi - ix.op_lo) * sizeof(zr_xform_op));
         HIP_OK(hipMemcpyAsync(s->d_ops.p + ix.op_lo, st.h_ops, (ix.op_hi - ix.op_lo) * sizeof(zr_xform_op), hipMemcpyHostToDevice, q));
     }
     HIP_OK(zr::refit_patch(q, device_view(s, st), st.d_box.p, (uint32_t)nd, st.d_rec.p, n_rec, st.d_payload.p));
+    HIP_OK(zr::refit_motion(q, st.d_payload.p + st.motion_at + n_mrec, n_pairs, st.d_leaf_word.p, st.n_leaves));
     if ((rc = queue_trees(s, st))) return rc;
     HIP_OK(hipStreamSynchronize(q));   // the one synchronisation: the root is a kernel argument of every render
     double area = 0;
@@ -282,7 +311,46 @@ int refit(zr_scene* s, zr_refit_info& info) {
 
 }  // namespace
 
+MotionView scene_motion_view(const zr_scene* s) {
+    MotionView v;
+    if (!s->refit || !s->refit->on_device) return v;
+    const RefitState& st = *s->refit;
+    v.leaf_word = st.d_leaf_word.p; v.records = st.d_payload.p + st.motion_at;
+    std::memcpy(v.leaf_base, st.leaf_base, sizeof v.leaf_base);
+    v.n_leaves = st.n_leaves; v.n_slots = (uint32_t)(st.motion.records.size() / kMotionDoubles);
+    return v;
+}
+
+int scene_leaf_entries(zr_scene* s, const uint32_t** d_leaf_entry, MotionView* view) {
+    if (int rc = update_ready(s, "zr_render_gbuffer_entries")) return rc;
+    if (int rc = ensure_index(s)) return rc;
+    RefitState& st = *s->refit;
+    if (!st.d_leaf_entry.p) { HIP_OK(hipSetDevice(s->ctx->device)); if (int rc = st.d_leaf_entry.upload(st.leaf_entry)) return rc; }
+    *d_leaf_entry = st.d_leaf_entry.p;
+    std::memcpy(view->leaf_base, st.leaf_base, sizeof view->leaf_base);
+    view->n_leaves = st.n_leaves;
+    return ZR_OK;
+}
+
 extern "C" {
+
+int zr_scene_motion(const zr_scene* s, uint32_t* out_slot_per_entry, double* out_records21, size_t capacity, size_t* out_count) {
+    if (!s) return fail(ZR_E_INVALID, "null scene");
+    if (!s->committed) return fail(ZR_E_STATE, "zr_scene_commit must precede zr_scene_motion");
+    if (s->released) return fail(ZR_E_STATE, "zr_scene_motion: the scene was committed from borrowed arrays, which it has released: give it with zr_scene_set_all to move it");
+    if (s->stale) return fail(ZR_E_STATE, "scene updated but not refitted: zr_scene_refit must precede zr_scene_motion");
+    const size_t n = s->plan_objs.size();
+    if (out_count) *out_count = n;
+    if (!out_slot_per_entry && !out_records21) return ZR_OK;
+    if (capacity < n) return fail(ZR_E_INVALID, "room for %zu world-list entries, the scene has %zu", capacity, n);
+    const MotionTable* t = s->refit ? &s->refit->motion : nullptr;
+    if (out_slot_per_entry) {
+        std::fill(out_slot_per_entry, out_slot_per_entry + n, kMotionStatic);
+        if (t) for (size_t k = 0; k < t->entries.size(); k++) out_slot_per_entry[t->entries[k]] = t->slot[k];
+    }
+    if (out_records21 && t && !t->records.empty()) std::memcpy(out_records21, t->records.data(), t->records.size() * sizeof(double));
+    return ZR_OK;
+}
 
 int zr_scene_update_xform_ops(zr_scene* s, size_t first, const zr_xform_op* ops, size_t n) {
     if (int rc = update_ready(s, "zr_scene_update_xform_ops")) return rc;
