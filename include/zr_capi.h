@@ -782,6 +782,11 @@ int zr_last_round_loop(zr_ctx*, int* drain_round, int* sub_pools);
  * by what they execute.  Launches enqueued are counted, the rounds queued behind the one that emptied the pools included; both 0 for a render that took another
  * path.  Either pointer may be null. */
 int zr_last_shade_builds(zr_ctx*, int* in_place, int* sorted);
+/* how the lean EXTEND kernel (worlds of bare triangles and spheres) fetched its slots in the last COUNTED render on this context: *checked = slots whose meta
+ * word it read and tested before asking for the ray, *skipped = slots it asked for at once because every slot of their pool was active (finished paths regenerate
+ * in place while work units are left; ZR_EXTEND_ALL_ACTIVE=0, read per render, switches the skip off).  Both 0 for an uncounted render and for a world that takes
+ * another EXTEND build.  Either pointer may be null. */
+int zr_last_extend_fetches(zr_ctx*, uint64_t* checked, uint64_t* skipped);
 /* drains the log of render-kernel launch durations (ms, measured with HIP events on the launch stream) recorded
  * since the previous call: copies the newest min(cap, n) of them, oldest first, and returns n */
 int zr_get_kernel_times(zr_ctx*, float* ms, int cap);

@@ -257,7 +257,7 @@ CAPI_SYMBOLS = [
     "zr_accum_halves", "zr_denoise_nlm", "zr_accum_denoise_nlm",
     "zr_render_gbuffer", "zr_temporal_create", "zr_temporal_destroy", "zr_temporal_reset", "zr_temporal_state", "zr_temporal_accumulate", "zr_accum_temporal",
     "zr_temporal_view", "zr_temporal_track_motion", "zr_render_gbuffer_entries", "zr_scene_motion",
-    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop", "zr_last_shade_builds",
+    "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop", "zr_last_shade_builds", "zr_last_extend_fetches",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_shade_lean", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
 ]
 
@@ -347,6 +347,9 @@ def load():
         lib.zr_last_presolved_pixels.argtypes = [vp]; lib.zr_last_presolved_pixels.restype = u64
     if hasattr(lib, "zr_last_round_loop"):   # (likewise)
         lib.zr_last_round_loop.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(lib, "zr_last_extend_fetches"):   # (likewise)
+        lib.zr_last_extend_fetches.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        lib.zr_last_extend_fetches.restype = C.c_int
     if hasattr(lib, "zr_last_shade_builds"):   # (likewise)
         lib.zr_last_shade_builds.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.zr_get_kernel_times.argtypes = [vp, C.POINTER(C.c_float), i32]
@@ -705,6 +708,12 @@ class Context:
         """(in_place, sorted): SHADE launches of the last pipeline render by build (zr_last_shade_builds)"""
         a, b = C.c_int(0), C.c_int(0)
         _check(self.lib.zr_last_shade_builds(self._c, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def extend_fetches(self):
+        """(checked, skipped): slots the lean EXTEND of the last counted render fetched with / without testing their meta word (zr_last_extend_fetches)"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib.zr_last_extend_fetches(self._c, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def kernel_times_ms(self, cap=256):

@@ -22,6 +22,7 @@ enum { CTR_SAMPLES = 0, CTR_SEGMENTS = 1, CTR_NODES = 2, CTR_SPHERES = 3, CTR_TR
        CTR_ESCAPED = 15,                             // segments lean SHADE finished itself (ray_escapes); they are part of CTR_SEGMENTS
        CTR_WORDS = 16,
        CTR_HIST = 16, CTR_HIST_WORDS = 24,           // ZR_WAVE_PROFILE build only: EXTEND's per-phase lane histograms, [phase][8 buckets of 8 lanes]
+       CTR_FETCH_CHECKED = 40, CTR_FETCH_SKIPPED = 41,   // the counting lean EXTEND: slots it fetched with / without testing their meta word (zr_last_extend_fetches)
        CTR_BLOCK = 48 };
 // A -DZR_WAVE_PROFILE build (scripts/wave_profile.sh) runs uninstrumented renders and REUSES words of the block for EXTEND's wave statistics, read back
 // through the zr_counters fields of the words' product meaning (ZR_RAW_COUNTERS=1, scripts/wave_profile.py): phase p = 0 NODE, 1 LEAF, 2 FETCH

@@ -759,6 +759,20 @@ int zr_last_shade_builds(zr_ctx* c, int* in_place, int* sorted) {
     return ZR_OK;
 }
 
+int zr_last_extend_fetches(zr_ctx* c, uint64_t* checked, uint64_t* skipped) {
+    if (!c) return fail(ZR_E_INVALID, "null argument");
+    HIP_OK(hipSetDevice(c->device));
+    unsigned long long h[2] = {0, 0};
+    static_assert(zr::CTR_FETCH_SKIPPED == zr::CTR_FETCH_CHECKED + 1, "read as a pair");
+    if (c->last_counted) {
+        HIP_OK(hipStreamSynchronize(c->stream));
+        HIP_OK(hipMemcpy(h, c->d_ctr.p + zr::CTR_FETCH_CHECKED, sizeof h, hipMemcpyDeviceToHost));
+    }
+    if (checked) *checked = h[0];
+    if (skipped) *skipped = h[1];
+    return ZR_OK;
+}
+
 uint64_t zr_last_presolved_pixels(zr_ctx* c) {
     return c && c->presolved_render == c->render_id ? c->presolved : 0;
 }

@@ -68,6 +68,8 @@ enum { SF_RAY = 0, SF_HIT_T = 6, SF_HIT_KI = 7, SF_BETA = 8, SF_L = 11, SF_ATT0 
 // more behind them for the work-unit counters, which the sub-pools share: that one has no header, shard s counts in uctl[CTL_STRIDE * s + CTL_SH_UNITS].
 // (CTL_CAPPED, the header word the host reads after a trace: zr_launch.h.)
 enum { CTL_COMPACT = 4,      // header: the drain's compaction counter (stream_compact); zero since the frame began
+       CTL_INACTIVE = 5,     // header: WHILE IT IS 0, EVERY SLOT OF THE POOL HAS F_ACTIVE.  Zeroed with the block; whoever leaves a slot without the bit stores 1
+                             // (stream_init, stream_shade, stream_compact_pad, stream_load_rays).  The lean EXTEND reads it once per wave: see its FETCH
        CTL_SHARD0 = 16, CTL_STRIDE = 32,
        CTL_SH_UNITS = 0,     // work units the shard has handed out dynamically (in the unit-counter block only)
        CTL_SH_CHUNK = 8,     // EXTEND's chunk cursor: chunks of ST_CHUNK slots reserved this round
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(256) void stream_init(StreamBuf B, DCamera cam, uin
     const unsigned long long u0 = st_first_unit(B.unit_chunk, B.unit0 + slot);
     const SlotAt S = slot_at(B, blockIdx.x, threadIdx.x);
     if (u0 < (unsigned long long)B.n_units) begin_sample(B, cam, seed, S, (uint32_t)u0, c_samp);
-    else { uint2 z; z.x = 0; z.y = 0; S.st2(SF_MA, z); }
+    else { uint2 z; z.x = 0; z.y = 0; S.st2(SF_MA, z); B.ctl[CTL_INACTIVE] = 1u; }
     if (COUNT && c_samp) atomicAdd(&gctr[CTR_SAMPLES], (unsigned long long)c_samp);
 }
 
@@ -248,11 +250,13 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
     uint32_t pend_i = 0;
     int sp = 0;
     Rng g; g.key = 0; g.k = 0; g.bounce = 0;  // only the medium test reads it
-    bool work_left = true;
+    int work_left = 1;      // wave-uniform: some shard may still have chunks
     uint32_t chunk_next = 0, chunk_end = 0;  // wave-uniform: the private range of ray indices being handed out
     uint32_t head_shard = wave_id % ST_SHARDS, shards_tried = 0;
     if (wave_id == 0 && lane < ST_SHARDS) B.ctl[CTL_SHARD0 + CTL_STRIDE * lane + CTL_SH_ACTIVE] = 0;  // SHADE of this round recounts the active slots
-    uint32_t c_nodes = 0, c_sph = 0, c_tri = 0, c_cube = 0, c_med = 0, c_seg = 0, c_hits = 0;
+    // LEVEL 0: is every slot of the pool active (CTL_INACTIVE)?  The value cannot change under this launch: what stores the word runs before it on the pool's stream.
+    const bool all_active = LEVEL == 0 && __builtin_amdgcn_readfirstlane(B.ctl[CTL_INACTIVE]) == 0u;
+    uint32_t c_nodes = 0, c_sph = 0, c_tri = 0, c_cube = 0, c_med = 0, c_seg = 0, c_hits = 0, c_fetch[2] = {0, 0};
     unsigned long long s_exec[2] = {0, 0}, s_lanes[2] = {0, 0};
 
     auto finish = [&]() {  // traversal of this lane's ray is complete: publish the result
@@ -303,16 +307,24 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
     if (lane < 24) p_hist[threadIdx.x >> 6][lane] = 0;
 #endif
     for (; iter < iter_cap; iter++) {
+        work_left = __builtin_amdgcn_readfirstlane(work_left);
         const uint32_t lkind = (cur >> 28) & 7u;
-        const int n1 = __popcll(__ballot(st == X_NODE));
-        const int n2t = __popcll(__ballot(st == X_LEAF && lkind == ZR_PRIM_TRIANGLE));
-        const int n2s = __popcll(__ballot(st == X_LEAF && lkind == ZR_PRIM_SPHERE));
-        const int n2g = LEVEL > 0 ? __popcll(__ballot(st == X_LEAF)) - n2t - n2s : 0;
-        const int n0 = work_left ? __popcll(__ballot(st == X_IDLE)) : 0;
+        // the lane counts and work_left are wave-uniform, and said to be (readfirstlane): the phase below is chosen by scalar compares and branches and the loop
+        // is left by a scalar branch, where the popcounts used to go back into a VGPR and the loop ran under an exec mask (cfg3 frame -3.3 %)
+        const int n1 = __builtin_amdgcn_readfirstlane(__popcll(__ballot(st == X_NODE)));
+        const int n2t = __builtin_amdgcn_readfirstlane(__popcll(__ballot(st == X_LEAF && lkind == ZR_PRIM_TRIANGLE)));
+        const int n2s = __builtin_amdgcn_readfirstlane(__popcll(__ballot(st == X_LEAF && lkind == ZR_PRIM_SPHERE)));
+        const int n2g = LEVEL > 0 ? __builtin_amdgcn_readfirstlane(__popcll(__ballot(st == X_LEAF))) - n2t - n2s : 0;
+        const int n0 = work_left ? __builtin_amdgcn_readfirstlane(__popcll(__ballot(st == X_IDLE))) : 0;
         const int n2 = n2t + n2s + n2g;
         if (n1 + n2 + n0 == 0) break;
 
-        if (n0 >= ST_FETCH_MIN || (n0 > 0 && n0 >= n1 && n0 >= n2)) {
+        // one phase per iteration, as three separate wave-uniform ifs and not an if / else-if chain: at each join a state variable is (changed | as it was), never
+        // undefined, so the loop-carried state (st, cur, pend_i, sp, tbest, tbest_f, kbest, ibest, slot) keeps its registers around the back-edge instead of being
+        // copied to a second set and back.  A NODE iteration: 198 -> 167 vector instructions, 36 -> 7 of them v_mov; the lean build spills 4 registers instead
+        // of 6.  The launch is 0.5 ms of 193 shorter for it, no more: profiles/r30_extend_loop_ab.txt
+        const int phase = (n0 >= ST_FETCH_MIN || (n0 > 0 && n0 >= n1 && n0 >= n2)) ? X_IDLE : (n1 >= n2 ? X_NODE : X_LEAF);
+        if (phase == X_IDLE) {
             // ================= FETCH: idle lanes take the next ray indices =================
             // rays are handed out from a wave-private chunk; one global atomic per ST_CHUNK rays
             const unsigned long long idle = __ballot(st == X_IDLE);
@@ -332,7 +344,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                     chunk_end = first + ST_CHUNK < (unsigned long long)B.P ? (uint32_t)first + ST_CHUNK : B.P;
                 } else {
                     head_shard = (head_shard + 1) % ST_SHARDS;
-                    if (++shards_tried >= ST_SHARDS) work_left = false;
+                    if (++shards_tried >= ST_SHARDS) work_left = 0;
                 }
             }
             if (!work_left) n = 0;
@@ -345,8 +357,12 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                 if (my < lim) {
                     // LEVEL > 0: meta word and ray requested together, one memory round trip per refill instead of two (an inactive
                     // slot's ray row is addressable like any other): cfg5 -1 %.  The lean build has no registers to hold the ray
-                    // while the meta word is tested (2 more spilled, cfg3 +3 %): it asks for the ray once the slot is known active.
-                    const uint2 m = B.ld2(SF_MA, my);
+                    // while the meta word is tested (2 more spilled, cfg3 +3 %): it asks for the ray once the slot is known active — and reads nothing else from the
+                    // word, so while every slot of the pool is active (all_active: the rounds in which finished paths regenerate in place) it skips the word, its
+                    // 8 bytes and its round trip, and asks for the ray at once.  A wave-uniform branch around the load, one copy of the body.
+                    uint2 m; m.x = 0; m.y = F_ACTIVE;
+                    if (LEVEL > 0 || !all_active) m = B.ld2(SF_MA, my);
+                    if (COUNT && LEVEL == 0) c_fetch[all_active ? 1 : 0]++;
                     V3 ro_ = mk(0, 0, 0), rd_ = mk(0, 0, 0);
                     double key_ = 0;
                     if (LEVEL > 0) {
@@ -372,7 +388,8 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                     }
                 }
             }
-        } else if (n1 >= n2) {
+        }
+        if (phase == X_NODE) {
             // ================= NODE: one 4-wide node per lane =================
             if (COUNT) { s_exec[0]++; s_lanes[0] += n1; }
 #ifdef ZR_WAVE_PROFILE
@@ -423,7 +440,8 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
 #undef ZR_QBOX
                 ZR_DESCEND()
             }
-        } else {
+        }
+        if (phase == X_LEAF) {
             // ================= LEAF: one primitive per lane, every kind that has waiting lanes =================
             // kind by kind, each under a wave-uniform guard: the few lanes at a minority kind (cfg3: the ground sphere every ray meets) do not
             // sit out NODE iterations waiting for company.  Against serving only the kind with most lanes, and with NODE and LEAF lanes
@@ -513,6 +531,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
         atomicAdd(&gctr[CTR_CUBES], (unsigned long long)c_cube);
         atomicAdd(&gctr[CTR_MEDIA], (unsigned long long)c_med);
         atomicAdd(&gctr[CTR_HITS], (unsigned long long)c_hits);
+        if (LEVEL == 0) { atomicAdd(&gctr[CTR_FETCH_CHECKED], (unsigned long long)c_fetch[0]); atomicAdd(&gctr[CTR_FETCH_SKIPPED], (unsigned long long)c_fetch[1]); }
         if (lane == 0) for (int k = 0; k < 2; k++) { atomicAdd(&gctr[CTR_NODE_EXECS + 2 * k], s_exec[k]); atomicAdd(&gctr[CTR_NODE_LANES + 2 * k], s_lanes[k]); }   // k = 1: CTR_LEAF_*
     }
 }
@@ -821,7 +840,7 @@ __global__ __launch_bounds__(SORT ? 256 : 64, LEAN ? ST_SHADE_WAVES_LEAN : ST_SH
 #endif
         if (want_unit) {
             if (next_unit != ST_NO_UNIT) { begin_sample(B, cam, seed, S, next_unit, next_pk, c_samp); active_after = true; }
-            else { uint2 z; z.x = 0; z.y = 0; S.st2(SF_MA, z); }
+            else { uint2 z; z.x = 0; z.y = 0; S.st2(SF_MA, z); B.ctl[CTL_INACTIVE] = 1u; }
         }
     } else {
         // hand out new work units: one atomic per wave on this block's shard
@@ -836,7 +855,7 @@ __global__ __launch_bounds__(SORT ? 256 : 64, LEAN ? ST_SHADE_WAVES_LEAN : ST_SH
                 const unsigned long long k = (unsigned long long)k0 + (unsigned long long)__popcll(wm & ((1ull << wl) - 1ull));
                 const unsigned long long u = st_unit_of(B.unit_chunk, B.unit_base, shard, (unsigned long long)B.shard_k0 + k);
                 if (u < (unsigned long long)B.n_units) { begin_sample(B, cam, seed, S, (uint32_t)u, c_samp); active_after = true; }
-                else { uint2 z; z.x = 0; z.y = 0; S.st2(SF_MA, z); }
+                else { uint2 z; z.x = 0; z.y = 0; S.st2(SF_MA, z); B.ctl[CTL_INACTIVE] = 1u; }
             }
         }
     }
@@ -1102,7 +1121,7 @@ __global__ __launch_bounds__(256) void stream_compact(StreamBuf S, StreamBuf D, 
 // the slots behind the survivors: inactive.  How many survivors there are is *counter (stream_compact has run): the host's figure may be a few rounds old
 __global__ __launch_bounds__(256) void stream_compact_pad(StreamBuf D, const unsigned int* __restrict__ counter) {
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
-    if (slot >= *counter && slot < D.P) { uint2 z; z.x = 0; z.y = 0; D.st2(SF_MA, slot, z); }
+    if (slot >= *counter && slot < D.P) { uint2 z; z.x = 0; z.y = 0; D.st2(SF_MA, slot, z); D.ctl[CTL_INACTIVE] = 1u; }
 }
 
 // THE POLL of a round (zr_round_polls.h), one wave behind a sub-pool's SHADE on its stream: lane s reads shard s.  `host` is pinned host memory: a kernel's store
@@ -1237,7 +1256,7 @@ __global__ __launch_bounds__(256) void stream_load_rays(StreamBuf B, const doubl
         B.st3(SF_RAY, slot, ld3(rays + (size_t)slot * 6)); B.st3(SF_RAY + 3, slot, ld3(rays + (size_t)slot * 6 + 3));
         B.st(SF_KEY, slot, __longlong_as_double((long long)zr_stream_key(seed, pixel, (uint64_t)slot)));
         ma.y = (bounce & 0xFFu) | F_ACTIVE;
-    }
+    } else B.ctl[CTL_INACTIVE] = 1u;
     B.st2(SF_MA, slot, ma);
 }
 
@@ -1296,6 +1315,17 @@ static StreamBuf make_buf(void* pool, uint32_t P, uint32_t spp, uint32_t n_units
     return B;
 }
 
+// The control blocks of a run, zeroed on `stream`.  ZR_EXTEND_ALL_ACTIVE=0 (read per run, like ZR_SHADE_IN_PLACE) starts every pool's CTL_INACTIVE at 1: the lean
+// EXTEND then tests the meta word of every slot it fetches, as it did before the word existed.
+static hipError_t clear_ctl(unsigned int* ctl, hipStream_t stream) {
+    const size_t W = stream_ctl_words();
+    hipError_t e = hipMemsetAsync(ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream);
+    const char* env = std::getenv("ZR_EXTEND_ALL_ACTIVE");
+    if (env && std::atoi(env) == 0)
+        for (int k = 0; k < ST_MAX_POOLS && e == hipSuccess; k++) e = hipMemsetD32Async((hipDeviceptr_t)(ctl + (size_t)k * W + CTL_INACTIVE), 1, 1, stream);
+    return e;
+}
+
 template <bool COUNT>
 static void launch_extend(const DScene& sc, const StreamBuf& B, void* overflow, uint32_t ovf_levels, int blocks, unsigned long long* gctr, int level, hipStream_t st) {
     // `blocks` counts waves (at most stream_extend_blocks(), a multiple of ST_EXT_GROUP: the overflow slabs are sized for that many)
@@ -1344,7 +1374,7 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
     }
     hipError_t e;
     hipStream_t stream = X.streams[0];
-    if ((e = hipMemsetAsync(X.ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
+    if ((e = clear_ctl(X.ctl, stream)) != hipSuccess) return e;
     const size_t cpart_blocks = (size_t)P / 256 + ST_MAX_POOLS + 1;
     if (job.split.cpart && (e = hipMemsetAsync(job.split.cpart, 0, cpart_blocks * 4 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
     auto init = [&](const StreamBuf& B, hipStream_t st) {
@@ -1643,7 +1673,7 @@ hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint
     const size_t W = stream_ctl_words();
     StreamBuf B = make_buf(pool, P, 1, n, n, nullptr, nullptr, X.ctl, X.ctl + (size_t)ST_MAX_POOLS * W, 0, P);
     hipError_t e;
-    if ((e = hipMemsetAsync(X.ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
+    if ((e = clear_ctl(X.ctl, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(stream_load_rays, dim3((P + 255) / 256), dim3(256), 0, stream, B, d_rays, n, seed, pixel, bounce);
     const int eb = (int)(P / 64 < (uint32_t)X.extend_blocks ? P / 64 : (uint32_t)X.extend_blocks);
     launch_extend<false>(sc, B, X.overflow, X.ovf_levels, eb, X.gctr, leaf_level, stream);
