@@ -1554,6 +1554,16 @@ public:
     // The frame is the same bit for bit either way.  Without temporal_track_motion the temporal history knows no object motion: reset_temporal_history() stays
     // the caller's duty.
     bool reuse_scene = false;
+    // extension: the firefly-robust resolve (zr_accum_resolve_robust in ZR_ROBUST_GINI mode with robust_strength).  Wherever render() resolves an
+    // accumulator whose counts are multiples of 64 — the adaptive render, and the progressive render after every pass that leaves such a count —
+    // render_accumulator receives the Gini-trimmed mean of the pixel's 64 lane sums instead of their plain mean, and the variance handed to
+    // denoise_variance_guided, denoise_nlm and temporal_accumulation is the variance of that mean (the half images denoise_nlm reads stay as they are).
+    // Without adaptive_threshold and samples_per_pass, a frame of a multiple of 64 samples takes one pass of samples_per_pixel samples through an accumulator;
+    // any other frame prints a warning and is rendered as without the flag.  resolve_used_robust says which it was.  A trimmed mean darkens pixels whose
+    // samples are genuinely skewed (caustics): opt-in.  false: exactly the render without it.
+    bool robust_resolve = false;
+    double robust_strength = ZR_ROBUST_DEFAULT_STRENGTH;
+    bool resolve_used_robust = false;   // extension: the last render's render_accumulator came from the robust resolve
     // extension: the temporal history follows a moving world (zr_temporal_track_motion).  Takes effect together with temporal_accumulation and
     // reuse_scene: the camera switches tracking on in the history it keeps, and keeps that history across a frame whose scene was refitted
     // (last_scene_refit == 1) although the `world` argument is a new object — the refit's motion table reprojects the moved objects' pixels.  Every other case
@@ -1651,10 +1661,14 @@ public:
                 variance_buffer.clear(); denoise_used_variance = false;
                 half_a_.clear(); half_b_.clear(); denoise_error_buffer.clear(); denoise_used_nlm = false;
                 temporal_buffer.clear(); temporal_history_length.clear();
+                resolve_used_robust = false; robust_variance_.clear();
                 if (debug) rc = render_debug_view(job);
                 else if (wants_adaptive()) rc = render_adaptive(job);
-                else if (samples_per_pass > 0) rc = render_progressive(job);
+                else if (samples_per_pass > 0) rc = render_progressive(job, samples_per_pass);
+                else if (robust_resolve && samples_per_pixel >= 64 && samples_per_pixel % 64 == 0) rc = render_progressive(job, samples_per_pixel);
                 else rc = render_one_shot(job);
+                if (rc == ZR_OK && !debug && robust_resolve && !resolve_used_robust)
+                    std::cerr << "[zenith] robust_resolve ignored: no whole lanes (it needs adaptive_threshold, or a multiple of 64 samples)\n";
                 if (!debug) zr_get_counters(lease.ctx, &last_counters);
                 if (rc == ZR_OK && !debug && temporal_accumulation && temporal_buffer.empty())
                     std::cerr << "[zenith] temporal_accumulation ignored: no variance (it needs adaptive_threshold, or samples_per_pass with a multiple of 64 samples)\n";
@@ -1731,14 +1745,30 @@ private:
     // the variance of the accumulator's pixel means, when the denoiser will ask for it (fetched before the accumulator is destroyed)
     int fetch_variance(zr_accum* acc) {
         if (!(use_denoiser && (denoise_variance_guided || wants_nlm()))) return ZR_OK;
-        variance_buffer.assign(pixels(), color(0, 0, 0));
-        int rc = zr_accum_variance(acc, zenith::doubles(variance_buffer));
+        int rc = ZR_OK;
+        if (!robust_variance_.empty()) variance_buffer = robust_variance_;   // (the frame is the robust mean: so is its variance)
+        else {
+            variance_buffer.assign(pixels(), color(0, 0, 0));
+            rc = zr_accum_variance(acc, zenith::doubles(variance_buffer));
+        }
         if (rc != ZR_OK) variance_buffer.clear();
         if (rc == ZR_OK && wants_nlm()) {   // and the two half images
             half_a_.assign(pixels(), color(0, 0, 0)); half_b_.assign(pixels(), color(0, 0, 0));
             rc = zr_accum_halves(acc, zenith::doubles(half_a_), zenith::doubles(half_b_));
             if (rc != ZR_OK) { half_a_.clear(); half_b_.clear(); }
         }
+        return rc;
+    }
+    // What the accumulator holds into render_accumulator: with robust_resolve and whole lanes (every count a multiple of 64) the Gini-trimmed mean, and with
+    // want_variance the variance of that mean for fetch_variance and accumulate_temporal; else the plain mean
+    int resolve_frame(zr_accum* acc, bool whole_lanes, bool want_variance) {
+        robust_variance_.clear(); resolve_used_robust = false;
+        if (!(robust_resolve && whole_lanes)) return zr_accum_resolve(acc, zenith::doubles(render_accumulator));
+        const zr_robust_params rp{ZR_ROBUST_GINI, 0, robust_strength};
+        if (want_variance) robust_variance_.assign(pixels(), color(0, 0, 0));
+        const int rc = zr_accum_resolve_robust(acc, &rp, zenith::doubles(render_accumulator), want_variance ? zenith::doubles(robust_variance_) : nullptr, nullptr);
+        if (rc != ZR_OK) robust_variance_.clear();
+        resolve_used_robust = rc == ZR_OK;
         return rc;
     }
     // the non-local-means filter has been asked for and can run: the blend of temporal_accumulation has no half images
@@ -1758,8 +1788,12 @@ private:
         temporal_world_ = j.world;
         if (track || tracking_) { zr_temporal_track_motion(temporal_.get(), track ? 1 : 0); tracking_ = track; }
         temporal_buffer.assign(pixels(), color(0, 0, 0)); variance_buffer.assign(pixels(), color(0, 0, 0)); temporal_history_length.assign(pixels(), 0);
-        const int rc = zr_accum_temporal(acc, temporal_.get(), &temporal_params, j.sc, &j.cam, seed, zenith::doubles(temporal_buffer), zenith::doubles(variance_buffer),
-                                         reinterpret_cast<int32_t*>(temporal_history_length.data()));
+        // (a robust frame goes in from the host with its own variance; the plain one is resolved on the device)
+        const int rc = !robust_variance_.empty()
+            ? zr_temporal_accumulate(temporal_.get(), &temporal_params, j.sc, &j.cam, seed, zenith::doubles(render_accumulator), zenith::doubles(robust_variance_),
+                                     zenith::doubles(temporal_buffer), zenith::doubles(variance_buffer), reinterpret_cast<int32_t*>(temporal_history_length.data()))
+            : zr_accum_temporal(acc, temporal_.get(), &temporal_params, j.sc, &j.cam, seed, zenith::doubles(temporal_buffer), zenith::doubles(variance_buffer),
+                                reinterpret_cast<int32_t*>(temporal_history_length.data()));
         if (rc != ZR_OK) { temporal_buffer.clear(); variance_buffer.clear(); temporal_history_length.clear(); }
         return rc;
     }
@@ -1786,7 +1820,7 @@ private:
         if ((rc == ZR_OK || rc == ZR_E_CANCELLED) && last_adaptive.passes > 0) {
             sample_counts.assign(pixels(), 0);
             int64_t st4[4] = {0, 0, 0, 0};
-            int qrc = zr_accum_resolve(acc.get(), zenith::doubles(render_accumulator));
+            int qrc = resolve_frame(acc.get(), true, rc == ZR_OK);   // (an adaptive run's counts are multiples of 64)
             if (qrc == ZR_OK) qrc = zr_accum_sample_counts(acc.get(), reinterpret_cast<int32_t*>(sample_counts.data()));
             if (qrc == ZR_OK) qrc = zr_accum_state(acc.get(), st4);
             if (qrc == ZR_OK && rc == ZR_OK) qrc = fetch_variance(acc.get());
@@ -1798,16 +1832,17 @@ private:
         return rc;
     }
     // progressive (the reference's "real-time sample accumulation"): passes of samples_per_pass samples into a device accumulator
-    int render_progressive(const frame_job& j) {
+    int render_progressive(const frame_job& j, int per_pass) {
         const int spp = samples_per_pixel < 1 ? 1 : samples_per_pixel;
         current_samples_count = 0; passes_rendered = 0;
         const zenith::accum_handle acc(zr_accum_create(j.ctx, image_width, image_height, nullptr));
         if (!acc) return ZR_E_DEVICE;
         while (current_samples_count < spp) {
-            const int n = std::min(samples_per_pass, spp - current_samples_count);
+            const int n = std::min(per_pass, spp - current_samples_count);
             int rc = zr_render_accumulate(j.ctx, j.sc, &j.cam, &j.env, seed, acc.get(), n, 0, zenith::flag_ptr(j.flag));
             // (a cancelled pass is discarded whole: the image stays the one of the passes before it)
-            if (rc == ZR_OK) rc = zr_accum_resolve(acc.get(), zenith::doubles(render_accumulator));
+            const int held = current_samples_count + n;
+            if (rc == ZR_OK) rc = resolve_frame(acc.get(), held % 64 == 0, held == spp);
             if (rc != ZR_OK) return rc;
             current_samples_count += n; passes_rendered++;
             lines_rendered = current_samples_count < spp ? (int)((long long)image_height * current_samples_count / spp) : image_height;
@@ -1901,6 +1936,8 @@ private:
 
     // the accumulator's half images between the render and the denoiser of one render() call (denoise_nlm)
     std::vector<color> half_a_, half_b_;
+    // the variance of the robust mean between the resolve and its readers of one render() call (robust_resolve)
+    std::vector<color> robust_variance_;
     // the history of temporal_accumulation and what it was made for
     zenith::temporal_handle temporal_;
     // the scene reuse_scene keeps, the context it lives on and the flattened world it holds

@@ -618,6 +618,44 @@ int zr_accum_halves(zr_accum*, double* out_a, double* out_b);
 int zr_denoise_nlm(zr_ctx*, const zr_denoise_nlm_params*, const double* half_a, const double* half_b, const double* variance,
                    const double* albedo, const double* normal, int width, int height, double* out, double* out_error);
 int zr_accum_denoise_nlm(zr_accum*, const zr_denoise_nlm_params*, const double* albedo, const double* normal, double* out, double* out_error);
+/* ---- firefly-robust resolve: a Gini-trimmed mean over the accumulator's lanes ------------------------------------
+ * After Buisine et al., "Firefly removal in Monte Carlo rendering with adaptive Median of meaNs" (EGSR 2021).  With k = 64 m samples in a pixel the
+ * 64 lane sums S_l = (x, y, z) are 64 equally weighted, independent estimates of it; the rule rates how unequal they are, trims whole lanes by rank
+ * symmetrically — from no trim (zr_accum_resolve's mean) to the median pair — and averages the rest.  Per pixel (FP64, in this order, no contraction;
+ * tests/robust_model.py restates it; `sum` is the xor butterfly 32, 16, ... 1 in lane order, as in zr_accum_variance):
+ *   key     v_l = (S_l.x + S_l.y) + S_l.z.  A lane is BAD when v_l is not finite; n_bad counts them; k_l = v_l, or +inf for a bad lane.
+ *   rank    r_l = #{ j : k_j < k_l, or k_j == k_l and j < l } with IEEE < and == (-0.0 ties with 0.0): a stable total order, defined by counting and
+ *           so independent of how a kernel finds it.  The good lanes hold the ranks 0 .. 63 - n_bad.
+ *   Gini    K = the key of the good lane of highest rank (the largest finite key), 0.0 if every lane is bad;  k^_l = k_l, or K for a bad lane;
+ *           T = sum k^_l;  A = sum (double)(2 r_l - 63) * k^_l;
+ *           g = 1.0 if T or A is not finite, else 0.0 if T <= 0.0, else q = A / (64.0 * T), q < 0.0 -> 0.0, q > 1.0 -> 1.0
+ *   trim    ZR_ROBUST_GINI: x = strength * g, x > 1.0 -> 1.0, t = min((int)floor(x * 32.0), 31);  ZR_ROBUST_FIXED: t = trim;
+ *           then t = max(t, min(n_bad, 31)).  Lane l is KEPT iff t <= r_l <= 63 - t: n_k = 64 - 2 t >= 2 lanes, none of them bad while n_bad <= 31.
+ *   colour  per channel c: Tk = sum (kept ? S_l.c : 0.0);  out_c = Tk * (1.0 / (double)(m * n_k))
+ *   variance of that mean, per channel: mu = Tk * (1.0 / n_k);  d_l = kept ? S_l.c - mu : 0.0;  Q = sum d_l * d_l;
+ *           var = Q * (1.0 / (n_k - 1)) * (1.0 / n_k) * inv_m * inv_m with inv_m = 1.0 / m; +inf when Tk is not finite (zr_accum_variance's rule)
+ *   n_bad >= 32: colour and variance are +inf in every channel and t = 31.
+ * With t = 0 the colour is zr_accum_resolve of the streaming route and the variance is zr_accum_variance, both bit for bit.  Whole lanes are trimmed by ONE
+ * key, so a kept lane keeps all three channels and no colour shift appears.  A trimmed mean of a skewed distribution is biased low: the feature is opt-in.
+ * zr_accum_resolve_robust  out_rgb, out_variance (may be NULL): W*H*3 doubles laid out like zr_accum_resolve's; out_trim (may be NULL): W*H int32, the
+ *                     pixel's t.  Only the plan's pixels are written (region and tiled accumulators included); the partials are left alone.
+ *                     zr_accum_variance's state rules (a non-uniform accumulator uses each pixel's own count).
+ * zr_kat_resolve_robust    a known-answer entry like zr_kat_scatter: the same kernel on n_pix pixels of caller-supplied lane sums ([n_pix][3][64]) with
+ *                     counts[n_pix]; the outputs are n_pix-long (x 3 for the first two) in input order, out_variance and out_trim may be NULL.
+ * ZR_E_INVALID before any device call: NULL (params, then the other arguments), mode outside {0, 1}, trim outside 0..31, strength negative or not finite;
+ * for the known-answer entry also a count that is not a positive multiple of 64.  Both fields are checked in both modes. */
+#define ZR_ROBUST_GINI 0
+#define ZR_ROBUST_FIXED 1
+typedef struct zr_robust_params {
+    int32_t mode;        /* ZR_ROBUST_GINI 0, ZR_ROBUST_FIXED 1 */
+    int32_t trim;        /* FIXED: lanes trimmed at each end, 0..31 */
+    double strength;     /* GINI: >= 0, finite; 0 = the plain mean unless lanes are bad */
+} zr_robust_params;
+/* default: scripts/dev/robust_sweep.py on 64-, 128- and 256-spp accumulators of cfg5 and mix0 against 4096 spp */
+#define ZR_ROBUST_DEFAULT_STRENGTH 1.0
+int zr_accum_resolve_robust(zr_accum*, const zr_robust_params*, double* out_rgb, double* out_variance, int32_t* out_trim);
+int zr_kat_resolve_robust(zr_ctx*, const zr_robust_params*, const double* lane_sums, const int32_t* counts, size_t n_pix,
+                          double* out_rgb, double* out_variance, int32_t* out_trim);
 /* ---- temporal accumulation: a frame's history reprojected across a moving camera ------------------------------
  * The temporal stage of SVGF (Schied et al., HPG 2017, section 4.1) for a camera path; through a world that zr_scene_refit moves when the history tracks motion
  * (zr_temporal_track_motion).  The reference has no counterpart.

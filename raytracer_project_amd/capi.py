@@ -139,6 +139,18 @@ class TemporalParams(_Defaults, C.Structure):
     _defaults_ = (0.4, 32, 0, 0.03, 0.9)
 
 
+ROBUST_GINI, ROBUST_FIXED = 0, 1
+ROBUST_DEFAULT_STRENGTH = 1.0   # ZR_ROBUST_DEFAULT_STRENGTH of include/zr_capi.h
+
+
+class RobustParams(_Defaults, C.Structure):
+    """zr_robust_params: the firefly-robust resolve (include/zr_capi.h); mode ROBUST_GINI reads strength, ROBUST_FIXED reads trim"""
+    _fields_ = [("mode", C.c_int32), ("trim", C.c_int32), ("strength", C.c_double)]
+
+    # defaults(): Gini mode at ZR_ROBUST_DEFAULT_STRENGTH (what the drop-in's camera::render uses with robust_resolve)
+    _defaults_ = (ROBUST_GINI, 0, ROBUST_DEFAULT_STRENGTH)
+
+
 class BvhDebugParams(_Defaults, C.Structure):
     """zr_bvh_debug_params: global_settings::debug_bvh_level / bvh_thickness of the BVH debug view (include/zr_capi.h, DESIGN §10)"""
     _fields_ = [("level", C.c_int32), ("thickness", C.c_float)]
@@ -255,6 +267,7 @@ CAPI_SYMBOLS = [
     "zr_render_aov", "zr_render_passes", "zr_trace_paths", "zr_post_process", "zr_analyze_frame", "zr_denoise", "zr_sharpen_frame",
     "zr_accum_variance", "zr_denoise_guided", "zr_accum_denoise",
     "zr_accum_halves", "zr_denoise_nlm", "zr_accum_denoise_nlm",
+    "zr_accum_resolve_robust", "zr_kat_resolve_robust",
     "zr_render_gbuffer", "zr_temporal_create", "zr_temporal_destroy", "zr_temporal_reset", "zr_temporal_state", "zr_temporal_accumulate", "zr_accum_temporal",
     "zr_temporal_view", "zr_temporal_track_motion", "zr_render_gbuffer_entries", "zr_scene_motion",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop", "zr_last_shade_builds", "zr_last_extend_fetches",
@@ -324,6 +337,9 @@ def load():
         lib.zr_accum_halves.argtypes = [vp, vp, vp]
         lib.zr_denoise_nlm.argtypes = [vp, C.POINTER(DenoiseNlmParams), vp, vp, vp, vp, vp, i32, i32, vp, vp]
         lib.zr_accum_denoise_nlm.argtypes = [vp, C.POINTER(DenoiseNlmParams), vp, vp, vp, vp]
+    if hasattr(lib, "zr_accum_resolve_robust"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
+        lib.zr_accum_resolve_robust.argtypes = [vp, C.POINTER(RobustParams), vp, vp, vp]
+        lib.zr_kat_resolve_robust.argtypes = [vp, C.POINTER(RobustParams), vp, vp, C.c_size_t, vp, vp, vp]
     if hasattr(lib, "zr_temporal_create"):   # (a ZR_LIB built from older sources, loaded for an A/B, has none)
         lib.zr_render_gbuffer.argtypes = [vp, vp, C.POINTER(Camera), u64, vp, vp, vp, vp]
         lib.zr_temporal_create.restype = vp; lib.zr_temporal_create.argtypes = [vp, i32, i32]
@@ -390,6 +406,7 @@ def load_scenes():
     s.zrs_render_dropin.argtypes = frame + [vp, C.POINTER(Counters)]
     s.zrs_render_dropin_progressive.argtypes = frame + [i32, vp, vp, i32]
     s.zrs_render_dropin_adaptive.argtypes = frame + [C.c_double, i32, i32, vp, vp, vp, i32]
+    s.zrs_render_dropin_robust.argtypes = frame + [C.c_double, C.c_double, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     s.zrs_render_dropin_threads.argtypes = frame + [i32, vp]
     s.zrs_render_dropin_denoise.argtypes = frame + [i32] + [vp] * 6
     s.zrs_render_dropin_denoise_guided.argtypes = frame + [C.c_double, i32, i32] + [vp] * 4
@@ -492,6 +509,24 @@ class DemoScene:
                                                       counts.ctypes.data, info, int(bool(flag)))
         self._rendered(rc == 0 or (rc == -1 and not flag))
         return out, counts, int(info[0]), int(info[1])
+
+    def render_dropin_robust(self, robust=True, strength=None, threshold=0.0, min_samples=0, step=0, samples_per_pass=0, variance=False, temporal=False,
+                             width=0, height=0, spp=0, device=0):
+        """camera::render with camera::robust_resolve = robust and robust_strength = strength (None: the camera's default): adaptively when threshold > 0,
+        progressively when samples_per_pass > 0, else as the flag decides (one pass through an accumulator at a multiple of 64 samples).  variance: also
+        use_denoiser and denoise_variance_guided, which fill variance_buffer; temporal: temporal_accumulation (one frame of a fresh history).  Dict of
+        render_accumulator, variance_buffer, temporal_buffer ((H, W, 3) float64; the last two all -1 when the render left them empty), sample_counts ((H, W) int32, all -1 likewise), robust (camera::resolve_used_robust), current_samples_count (-7 going in)
+        and passes"""
+        outs = self._frames(width, height, "render_accumulator", "variance_buffer", "temporal_buffer")
+        counts = np.full(outs["render_accumulator"].shape[:2], -1, dtype=np.int32)
+        info = (C.c_int * 3)()
+        flags = (1 if robust else 0) | (2 if variance else 0) | (4 if temporal else 0)
+        self._rendered(load_scenes().zrs_render_dropin_robust(self._h, width, height, spp, device, -1.0 if strength is None else float(strength), float(threshold),
+                                                              int(min_samples), int(step), int(samples_per_pass), flags, outs["render_accumulator"].ctypes.data,
+                                                              outs["variance_buffer"].ctypes.data, outs["temporal_buffer"].ctypes.data, counts.ctypes.data,
+                                                              info) == 0)
+        outs.update(sample_counts=counts, robust=bool(info[0]), current_samples_count=int(info[1]), passes=int(info[2]))
+        return outs
 
     def render_dropin_threads(self, n, width=0, height=0, spp=0, device=0):
         """n drop-in renders, each on a fresh host thread, one after the other (the reference's render-restart pattern,
@@ -689,6 +724,20 @@ class Context:
         _check(self.lib.zr_kat_camera_rays(self._c, C.byref(camera), C.c_uint64(seed), req.ctypes.data, len(req), out.ctypes.data))
         return out
 
+    def kat_resolve_robust(self, lane_sums, counts, params=None):
+        """zr_kat_resolve_robust: the robust resolve's kernel on caller-supplied lane sums (n, 3, 64) float64 with counts (n,) int32 -> (colour (n, 3),
+        variance (n, 3), trim (n,) int32), in input order"""
+        params = params if params is not None else RobustParams.defaults()
+        lane_sums = np.ascontiguousarray(lane_sums, dtype=np.float64).reshape(-1, 3, 64)
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        n = len(lane_sums)
+        if len(counts) != n:
+            raise ValueError(f"{len(counts)} counts for {n} pixels of lane sums")
+        out, var, trim = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+        _check(self.lib.zr_kat_resolve_robust(self._c, C.byref(params), lane_sums.ctypes.data, counts.ctypes.data, n, out.ctypes.data, var.ctypes.data,
+                                              trim.ctypes.data))
+        return out, var, trim
+
     def counters(self):
         c = Counters()
         _check(self.lib.zr_get_counters(self._c, C.byref(c)))
@@ -776,6 +825,15 @@ class Accumulator:
         out, = self._like(outs=(out,))
         _check(self.lib.zr_accum_variance(self._a, out.ctypes.data))
         return out
+
+    def resolve_robust(self, params=None, out=None, out_variance=None, out_trim=None):
+        """zr_accum_resolve_robust: the Gini-trimmed mean of every pixel's lane sums, the variance of that mean and the trim: ((H, W, 3), (H, W, 3) float64,
+        (H, W) int32); only the region's pixels are written"""
+        params = params if params is not None else RobustParams.defaults()
+        out, out_variance = self._like(outs=(out, out_variance))
+        out_trim, = _like((self.height, self.width), "the accumulator's plane", outs=(out_trim,), dtype=np.int32)
+        _check(self.lib.zr_accum_resolve_robust(self._a, C.byref(params), out.ctypes.data, out_variance.ctypes.data, out_trim.ctypes.data))
+        return out, out_variance, out_trim
 
     def denoise(self, params, albedo, normal, zdepth=None):
         """zr_accum_denoise: Context.denoise_guided(params, resolve(), variance(), ...) bit for bit, with colour and variance resolved on the device;

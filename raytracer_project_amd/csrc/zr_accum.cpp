@@ -107,8 +107,30 @@ int accum_resolve_into(const AccumState& a, double* d_out, hipStream_t stream) {
     else HIP_OK(zr::launch_accum_resolve(a.d_partial.p, a.d_pixels.p, a.n_pix, a.plan.W, a.done, a.route == 0 ? lanes_for(a.done) : 1, d_out, stream));
     return ZR_OK;
 }
+// A query kernel's launch as zr_get_kernel_times sees it under ZR_TIMELOG_KIND=4 (the variance and the robust resolve: profiles/robust_resolve.txt compares them).
+// It belongs to no render (render_id 0: renders count from 1, and RunTotals::finish adopts only later ids): zr_counters' kernel times stay the renders' own.
+struct QueryTimer {
+    HostTimer t; hipStream_t stream;
+    QueryTimer(zr_ctx* c, hipStream_t stream) : t(c), stream(stream) { if (c->pending.size() > 4096) (void)resolve_times(c); t.begin(stream, 4); }
+    ~QueryTimer() { const size_t n = t.c->pending.size(); t.end(stream, 4); if (t.c->pending.size() > n) t.c->pending.back().render_id = 0; }
+};
 int accum_variance_into(const AccumState& a, double* d_out, hipStream_t stream) {
+    QueryTimer timer(a.ctx, stream);
     HIP_OK(zr::launch_accum_variance(a.d_partial.p, a.d_pixels.p, a.adaptive ? a.d_count.p : nullptr, a.done, a.n_pix, a.plan.W, d_out, stream));
+    return ZR_OK;
+}
+// the robust colour, the variance of that mean and the trim (either may be null) into the accumulator's pixels of device frames (zr_robust.hip)
+int accum_robust_into(const AccumState& a, const zr_robust_params& rp, double* d_out, double* d_var, int32_t* d_trim, hipStream_t stream) {
+    QueryTimer timer(a.ctx, stream);
+    HIP_OK(zr::launch_accum_resolve_robust(a.d_partial.p, a.d_pixels.p, a.adaptive ? a.d_count.p : nullptr, a.done, a.n_pix, a.plan.W, rp.mode, rp.trim, rp.strength,
+                                           d_out, d_var, d_trim, stream));
+    return ZR_OK;
+}
+// zr_robust_params as both robust entries check them, before any device call
+int check_robust_params(const zr_robust_params* rp) {
+    if (rp->mode != ZR_ROBUST_GINI && rp->mode != ZR_ROBUST_FIXED) return fail(ZR_E_INVALID, "mode = %d is neither ZR_ROBUST_GINI (0) nor ZR_ROBUST_FIXED (1)", rp->mode);
+    if (rp->trim < 0 || rp->trim > 31) return fail(ZR_E_INVALID, "trim = %d outside 0..31", rp->trim);
+    if (!(rp->strength >= 0) || !std::isfinite(rp->strength)) return fail(ZR_E_INVALID, "strength %g is negative or not finite", rp->strength);
     return ZR_OK;
 }
 int accum_halves_into(const AccumState& a, double* d_out_a, double* d_out_b, hipStream_t stream) {
@@ -322,6 +344,59 @@ int zr_accum_halves(zr_accum* a, double* out_a, double* out_b) {
     HIP_OK(hipStreamSynchronize(nullptr));
     std::vector<double> staging;   // only the plan's pixels are copied out
     return (rc = copy_region(st.plan, d_a.p, out_a, staging)) ? rc : copy_region(st.plan, d_b.p, out_b, staging);
+}
+
+// ---- the firefly-robust resolve ---------------------------------------------------------------------------------------------------------------
+
+int zr_accum_resolve_robust(zr_accum* a, const zr_robust_params* rp, double* out_rgb, double* out_variance, int32_t* out_trim) {
+    if (!rp) return fail(ZR_E_INVALID, "null argument: params");
+    int rc = check_robust_params(rp);   // the parameters first: they need no device and no other argument
+    if (rc) return rc;
+    if (!a) return fail(ZR_E_INVALID, "null argument: accumulator");
+    if (!out_rgb) return fail(ZR_E_INVALID, "null argument: out_rgb");
+    const AccumState& st = a->st;
+    if ((rc = variance_ready(st, "zr_accum_resolve_robust"))) return rc;
+    HIP_OK(hipSetDevice(st.device));
+    // device frames of which only the plan's pixels are written, and only they are copied out
+    const size_t npx = st.plan.npx();
+    DevBuf<double> d_c, d_v; DevBuf<int32_t> d_t;
+    if ((rc = d_c.alloc(npx * 3)) || (out_variance && (rc = d_v.alloc(npx * 3))) || (out_trim && (rc = d_t.alloc(npx)))) return rc;
+    if ((rc = accum_robust_into(st, *rp, d_c.p, out_variance ? d_v.p : nullptr, out_trim ? d_t.p : nullptr, nullptr))) return rc;
+    HIP_OK(hipStreamSynchronize(nullptr));
+    std::vector<double> staging;
+    if ((rc = copy_region(st.plan, d_c.p, out_rgb, staging)) || (out_variance && (rc = copy_region(st.plan, d_v.p, out_variance, staging)))) return rc;
+    if (out_trim && st.n_pix) {
+        std::vector<int32_t> h(npx);
+        HIP_OK(hipMemcpy(h.data(), d_t.p, npx * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (uint32_t pk : plan_pixels(st.plan)) { const size_t o = (size_t)(pk >> 16) * st.plan.W + (pk & 0xFFFFu); out_trim[o] = h[o]; }
+    }
+    return ZR_OK;
+}
+
+int zr_kat_resolve_robust(zr_ctx* c, const zr_robust_params* rp, const double* lane_sums, const int32_t* counts, size_t n_pix, double* out_rgb,
+                          double* out_variance, int32_t* out_trim) {
+    if (!rp) return fail(ZR_E_INVALID, "null argument: params");
+    int rc = check_robust_params(rp);
+    if (rc) return rc;
+    if (!c) return fail(ZR_E_INVALID, "null argument: context");
+    if (!lane_sums) return fail(ZR_E_INVALID, "null argument: lane_sums");
+    if (!counts) return fail(ZR_E_INVALID, "null argument: counts");
+    if (!out_rgb) return fail(ZR_E_INVALID, "null argument: out_rgb");
+    if (n_pix > 0x7FFFFFFFu) return fail(ZR_E_INVALID, "n_pix = %zu beyond 2^31", n_pix);
+    for (size_t k = 0; k < n_pix; k++)
+        if (counts[k] < 64 || counts[k] % 64 != 0) return fail(ZR_E_INVALID, "counts[%zu] = %d is not a positive multiple of 64", k, counts[k]);
+    if (n_pix == 0) return ZR_OK;
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<double> d_s, d_c, d_v; DevBuf<int32_t> d_n, d_t;
+    if ((rc = d_s.upload(lane_sums, n_pix * zr::ACCUM_DOUBLES_PER_PIXEL)) || (rc = d_n.upload(counts, n_pix)) || (rc = d_c.alloc(n_pix * 3)) ||
+        (out_variance && (rc = d_v.alloc(n_pix * 3))) || (out_trim && (rc = d_t.alloc(n_pix)))) return rc;
+    HIP_OK(zr::launch_accum_resolve_robust(d_s.p, nullptr, d_n.p, 0, (uint32_t)n_pix, 0, rp->mode, rp->trim, rp->strength, d_c.p, out_variance ? d_v.p : nullptr,
+                                           out_trim ? d_t.p : nullptr, nullptr));
+    HIP_OK(hipStreamSynchronize(nullptr));
+    HIP_OK(hipMemcpy(out_rgb, d_c.p, n_pix * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_variance) HIP_OK(hipMemcpy(out_variance, d_v.p, n_pix * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_trim) HIP_OK(hipMemcpy(out_trim, d_t.p, n_pix * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return ZR_OK;
 }
 
 int zr_accum_state(const zr_accum* a, int64_t out[4]) {

@@ -142,6 +142,11 @@ hipError_t launch_accum_variance(const double* partial, const uint32_t* pixels, 
 // the two half images of every slot (the even lanes' mean, the odd lanes' mean) into the listed pixels of out_a / out_b (as launch_accum_variance)
 hipError_t launch_accum_halves(const double* partial, const uint32_t* pixels, const int32_t* count, int uniform_count, uint32_t n_pix, int W, double* out_a,
                                double* out_b, hipStream_t stream);
+// The firefly-robust resolve (zr_accum_resolve_robust, zr_robust.hip): the Gini-trimmed mean of every slot's lane sums, the variance of that mean and the trim,
+// into the listed pixels of out / out_var (3 doubles a pixel) / out_trim (one int32) of a frame W wide.  pixels null: slot i goes to element i
+// (zr_kat_resolve_robust).  out_var / out_trim may be null; count as launch_accum_error's; mode / trim / strength: zr_robust_params, checked by the caller.
+hipError_t launch_accum_resolve_robust(const double* partial, const uint32_t* pixels, const int32_t* count, int uniform_count, uint32_t n_pix, int W, int mode,
+                                       int trim, double strength, double* out, double* out_var, int32_t* out_trim, hipStream_t stream);
 // The sky pre-pass (zr_sky.hip): of the n_pix listed pixels, those whose every camera ray of the samples [sample0, sample0 + spp) provably sees only the
 // environment get their mean written to `out` (stream_reduce's value, bit for bit); the others go, in list order, to walk[0 .. *n_walk).  Device scratch:
 // flag and walk n_pix words, block_count ceil(n_pix / 256) words, n_walk one word.  ZR_SKY_SIEVE=1 puts a one-ray sieve in front (same flags, frame and list).

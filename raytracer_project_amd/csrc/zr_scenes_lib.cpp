@@ -130,6 +130,37 @@ int zrs_render_dropin_adaptive(void* p, int width, int height, int spp, int devi
     return done ? 0 : -1;
 }
 
+// camera::render with camera::robust_resolve (flags & 1) and robust_strength = strength (< 0 keeps the camera's default) through the drop-in API: adaptively when
+// threshold > 0 (min_samples and step <= 0 keep the camera's defaults), progressively when samples_per_pass > 0, else as the flag decides.  flags & 2: use_denoiser and
+// denoise_variance_guided, so that variance_buffer is filled; flags & 4: temporal_accumulation (one frame: the history is the camera's, and the camera ends here).
+// Outputs (any may be null): render_accumulator, variance_buffer, temporal_buffer (W*H*3 doubles each; the last two all -1 when the render left them empty), counts
+// (W*H ints, camera::sample_counts; left alone when empty); info: resolve_used_robust, current_samples_count (-7 going in), passes_rendered.  Returns 0, or -1 if
+// the render did not finish.
+int zrs_render_dropin_robust(void* p, int width, int height, int spp, int device, double strength, double threshold, int min_samples, int step, int samples_per_pass,
+                             int flags, double* out, double* var, double* temporal, int* counts, int* info) {
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
+    cam.robust_resolve = (flags & 1) != 0;
+    if (strength >= 0) cam.robust_strength = strength;
+    cam.use_denoiser = cam.denoise_variance_guided = (flags & 2) != 0;
+    cam.temporal_accumulation = (flags & 4) != 0;
+    cam.adaptive_threshold = threshold;
+    if (min_samples > 0) cam.adaptive_min_samples = min_samples;
+    if (step > 0) cam.adaptive_step = step;
+    cam.samples_per_pass = samples_per_pass;
+    cam.reset_accumulator();
+    cam.current_samples_count = -7;
+    if (!render_world(h, cam, post_processor())) return -1;
+    copy_out(cam.render_accumulator, out);
+    if (cam.variance_buffer.size() == cam.render_accumulator.size()) copy_out(cam.variance_buffer, var);
+    else if (var) std::fill(var, var + cam.render_accumulator.size() * 3, -1.0);
+    if (cam.temporal_buffer.size() == cam.render_accumulator.size()) copy_out(cam.temporal_buffer, temporal);
+    else if (temporal) std::fill(temporal, temporal + cam.render_accumulator.size() * 3, -1.0);
+    if (counts && !cam.sample_counts.empty()) std::memcpy(counts, cam.sample_counts.data(), cam.sample_counts.size() * sizeof(int));
+    if (info) { info[0] = cam.resolve_used_robust ? 1 : 0; info[1] = cam.current_samples_count; info[2] = cam.passes_rendered; }
+    return 0;
+}
+
 // camera::render with global_settings::bvh_debug_mode set (debug_bvh_level = level, bvh_thickness = thickness) through the drop-in API; the
 // settings are restored afterwards.  `aux`, when not null, receives albedo_buffer (which the debug view leaves as reset_accumulator made it).
 // Returns 0, or -1 if the render did not finish.
@@ -436,6 +467,7 @@ extern "C" size_t zrs_sizeof(int which) {
         case 18: return sizeof(zr_denoise_guided_params);
         case 19: return sizeof(zr_temporal_params);
         case 20: return sizeof(zr_denoise_nlm_params);
+        case 21: return sizeof(zr_robust_params);
         default: return 0;
     }
 }
