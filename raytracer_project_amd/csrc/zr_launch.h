@@ -80,12 +80,13 @@ struct StreamFrame {     // what is rendered: one work unit per primary sample o
 struct StreamPool {      // the frame's slot pool; the small pool the survivors of its drain are moved to (null: not used); chunk of the XCD-affine hand-out (0: striped)
     void* slots; uint32_t P; void* drain; uint32_t drain_slots, unit_chunk;
 };
-struct StreamContext {   // what the context owns (zr_ctx): control block, EXTEND's spill slabs and persistent grid, counter block (CTR_*), streams, pinned copy of ctl, poll ring
+struct StreamContext {   // what the context owns (zr_ctx): control block, EXTEND's spill slabs and persistent grid, counter block (CTR_*), streams, pinned copy of ctl (of which a frame with a progress sink fills the unit counters' block), poll ring
     unsigned int* ctl; void* overflow; uint32_t ovf_levels; int extend_blocks; unsigned long long* gctr;
     hipStream_t* streams; int n_pools;   // streams[0] is the caller's stream, the others are internal; n_pools: sub-pools wanted
     hipEvent_t event; unsigned int* h_active;
     // the round loop's polls (zr_round_polls.h): pinned [POLL_RING][ST_MAX_POOLS][POLL_WORDS] words that the device writes, and one event (no timing) per sub-pool and
-    // ring slot, [POLL_RING][ST_MAX_POOLS].  stream_trace does not poll: null there
+    // ring slot, [POLL_RING][ST_MAX_POOLS].  The round loop learns what the device did from them alone: stream_render answers a null ring with
+    // hipErrorInvalidValue.  stream_trace does not poll: null there
     unsigned int* h_polls = nullptr; hipEvent_t* poll_events = nullptr;
 };
 struct StreamSplit { int mode; void* kend; void* cls; unsigned long long* cpart; };   // mode 0: the render; 1 / 2: the passes of the reflection / refraction split, with their buffers

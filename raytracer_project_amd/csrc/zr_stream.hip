@@ -22,6 +22,7 @@
 // depend on the pool size, on scheduling, or on how the frame is sharded over GPUs.
 #include "zr_device.h"
 #include "zr_launch.h"
+#include "zr_units.h"
 #ifdef ZR_SHADE_ASSERT   /* a debug build (ZR_DEFS=-DZR_SHADE_ASSERT): lean SHADE checks its early unit reservation against the lanes that end */
 #include <cassert>
 #endif
@@ -46,7 +47,6 @@ namespace zr {
 #ifndef ST_FETCH_MIN
 #define ST_FETCH_MIN 16  /* idle lanes that trigger a refill even when another phase has more ready lanes */
 #endif
-#define ST_SHARDS 64     /* sharded counters of the control block (CTL_* below): a single contended word sustains only ~90 atomics/us */
 #ifndef ST_LDS_STACK
 #define ST_LDS_STACK 12
 #endif
@@ -123,26 +123,7 @@ __device__ __forceinline__ SlotAt slot_at(const StreamBuf& B, uint32_t block, ui
 }
 
 
-// Which unit is the k-th of shard `shard`.
-//  striped (G = 0): unit_base + k * ST_SHARDS + shard — every shard sweeps the whole frame, one unit in ST_SHARDS.
-//  affine  (G > 0): the frame's units (pixel list in tile order x spp) are cut into chunks of G units and chunk c belongs to
-//    the shard at position c % ST_SHARDS of a round; within its chunks a shard deals consecutive units.  A shard is served by
-//    the SHADE blocks and the EXTEND waves with blockIdx % ST_SHARDS == shard, i.e. by ONE XCD class (blocks b and b + 8 share
-//    an XCD: MI355X_MICROARCH.md, workgroup dispatch), and position (shard % 8) * 8 + shard / 8 puts the eight shards of a class
-//    side by side: at any time an XCD's L2 sees the rays of ~8 neighbouring chunks (screen tiles) instead of every 64th unit of
-//    a front that spans the frame.  The image cannot depend on it: samples[unit] is written once, by whichever slot got the unit.
-__host__ __device__ inline unsigned long long st_unit_of(uint32_t G, uint32_t unit_base, uint32_t shard, unsigned long long k) {
-    if (G == 0) return (unsigned long long)unit_base + k * ST_SHARDS + shard;
-    const uint32_t k32 = (uint32_t)k, q = k32 / G, r = k32 - q * G;
-    const uint32_t pos = (shard & 7u) * (ST_SHARDS / 8u) + (shard >> 3);
-    return ((unsigned long long)q * ST_SHARDS + pos) * G + r;
-}
-// the unit slot g (index over all sub-pools) starts on
-__host__ __device__ inline unsigned long long st_first_unit(uint32_t G, uint32_t g) {
-    if (G == 0) return g;
-    const uint32_t c = g >> 8;
-    return st_unit_of(G, 0, c % ST_SHARDS, (unsigned long long)(c / ST_SHARDS) * 256u + (g & 255u));
-}
+// (which unit a slot starts on, and which a shard hands out next: st_first_unit and st_unit_of, zr_units.h)
 
 // ---- begin a sample in a slot: camera ray + fresh path state --------------------------------------------
 // sample `sample` of the pixel whose word (B.pixels) is `pk`
@@ -1326,44 +1307,117 @@ static hipError_t clear_ctl(unsigned int* ctl, hipStream_t stream) {
     return e;
 }
 
-template <bool COUNT>
-static void launch_extend(const DScene& sc, const StreamBuf& B, void* overflow, uint32_t ovf_levels, int blocks, unsigned long long* gctr, int level, hipStream_t st) {
-    // `blocks` counts waves (at most stream_extend_blocks(), a multiple of ST_EXT_GROUP: the overflow slabs are sized for that many)
-    const dim3 grid((blocks + ST_EXT_GROUP - 1) / ST_EXT_GROUP), group(64 * ST_EXT_GROUP);
-    if (level >= 3) hipLaunchKernelGGL((stream_extend<COUNT, 3>), grid, group, 0, st, sc, B, (SEntry*)overflow, ovf_levels, gctr);
-    else if (level == 2) hipLaunchKernelGGL((stream_extend<COUNT, 2>), grid, group, 0, st, sc, B, (SEntry*)overflow, ovf_levels, gctr);
-    else if (level == 1) hipLaunchKernelGGL((stream_extend<COUNT, 1>), grid, group, 0, st, sc, B, (SEntry*)overflow, ovf_levels, gctr);
-    else hipLaunchKernelGGL((stream_extend<COUNT, 0>), grid, group, 0, st, sc, B, (SEntry*)overflow, ovf_levels, gctr);
+// ---- which build serves a launch: per kernel family one table from the deciding facts to the kernel, and one call site --------------------------------------
+using ExtendKernel = void (*)(DScene, StreamBuf, SEntry*, uint32_t, unsigned long long*);
+using ShadeKernel = void (*)(DScene, DCamera, DEnv, uint64_t, StreamBuf, unsigned long long*);
+using FusedKernel = void (*)(DScene, DCamera, DEnv, uint64_t, FusedBuf, unsigned long long*, FusedObjs);
+
+// `blocks` counts waves (at most stream_extend_blocks(), a multiple of ST_EXT_GROUP: the overflow slabs are sized for that many)
+static void launch_extend(bool count, int level, const DScene& sc, const StreamBuf& B, void* overflow, uint32_t ovf_levels, int blocks, unsigned long long* gctr, hipStream_t st) {
+    static constexpr ExtendKernel build[2][4] = {   // [count][leaf level]
+        {stream_extend<false, 0>, stream_extend<false, 1>, stream_extend<false, 2>, stream_extend<false, 3>},
+        {stream_extend<true, 0>, stream_extend<true, 1>, stream_extend<true, 2>, stream_extend<true, 3>}};
+    const ExtendKernel kernel = build[count ? 1 : 0][level < 0 ? 0 : (level > 3 ? 3 : level)];
+    hipLaunchKernelGGL(kernel, dim3((blocks + ST_EXT_GROUP - 1) / ST_EXT_GROUP), dim3(64 * ST_EXT_GROUP), 0, st, sc, B, (SEntry*)overflow, ovf_levels, gctr);
 }
 
+// SHADE.  in place: the lean build that shades a slot where it lies, one wave per workgroup; lean: same arithmetic as the general build, fewer registers, 6 waves
+// per SIMD instead of 4 (see lean_rec, zr_device.h), sorted like it; uv: the general build that reads the triangles' texture coordinates.
+enum ShadeFamily { SHADE_IN_PLACE = 0, SHADE_LEAN = 1, SHADE_UV = 2, SHADE_GENERAL = 3 };
+static void launch_shade(ShadeFamily family, bool count, int mode, unsigned lds_pad, const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed,
+                         const StreamBuf& B, unsigned long long* gctr, hipStream_t st) {
+    static constexpr ShadeKernel build[4][4] = {   // [family][variant]: plain, counting, the split's reflection pass, its refraction pass (the lean families serve mode 0 only)
+        {stream_shade<false, 0, true, false, false>, stream_shade<true, 0, true, false, false>, nullptr, nullptr},
+        {stream_shade<false, 0, true>, stream_shade<true, 0, true>, nullptr, nullptr},
+        {stream_shade<false, 0, false, true>, stream_shade<true, 0, false, true>, stream_shade<true, 1, false, true>, stream_shade<true, 2, false, true>},
+        {stream_shade<false, 0>, stream_shade<true, 0>, stream_shade<true, 1>, stream_shade<true, 2>}};
+    const int variant = mode != 0 ? 1 + mode : (count ? 1 : 0);   // the split passes always count
+    const unsigned lds = variant == 0 ? lds_pad : 0u;              // the LDS pad goes only to non-counting builds
+    const uint32_t slot_blocks = (B.P + 255) / 256;
+    const bool waves = family == SHADE_IN_PLACE;                   // one wave per workgroup, four per slot block
+    hipLaunchKernelGGL(build[family][variant], dim3(waves ? slot_blocks * 4 : slot_blocks), dim3(waves ? 64 : 256), lds, st, sc, cam, env, seed, B, gctr);
+}
+
+// level: 1 = no wrapped objects and only plain media, 2 = everything but placements; uv: the builds that read the triangles' texture coordinates
+static void launch_fused(int level, bool count, bool uv, dim3 grid, const DScene& sc, const DCamera& cam, const DEnv& env, uint64_t seed, const FusedBuf& B,
+                         unsigned long long* gctr, const FusedObjs& fo, hipStream_t st) {
+    static constexpr FusedKernel build[2][2][2] = {   // [level][count][uv]
+        {{fused_render<1, false>, fused_render<1, false, true>}, {fused_render<1, true>, fused_render<1, true, true>}},
+        {{fused_render<2, false>, fused_render<2, false, true>}, {fused_render<2, true>, fused_render<2, true, true>}}};
+    hipLaunchKernelGGL(build[level <= 1 ? 0 : 1][count ? 1 : 0][uv ? 1 : 0], grid, dim3(256), 0, st, sc, cam, env, seed, B, gctr, fo);
+}
+
+// A polled frame's report, the stream idle: when the sink wants the frame, `out` gets the mean of the samples finished so far (samples[] began at zero: render_stream)
+static hipError_t reduce_and_report(StreamProgress& sink, double finished_fraction, bool reducible, const StreamFrame& F, const StreamBuf& B, hipStream_t stream) {
+    bool reduced = false;
+    if (reducible && F.out && sink.wants_frame()) {
+        hipLaunchKernelGGL(stream_reduce, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, B, *F.cam, F.out);
+        const hipError_t e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return e;
+        reduced = true;
+    }
+    sink.report(finished_fraction, reduced);
+    return hipSuccess;
+}
+
+struct StreamSwitches {
+    unsigned shade_pad;   // ZR_SHADE_LDS_PAD (read once per process), a development aid: bytes of dynamic LDS per SHADE block lower the blocks a CU can hold
+                          // (160 KB: 4 fit by registers; > 40 KB: 3, > 53 KB: 2)
+    bool trace_polls;     // ZR_STREAM_POLL_TRACE (once per process), a development aid: one line per poll on stderr
+    bool in_place;        // ZR_SHADE_IN_PLACE (per render): 0 forces the sorted SHADE build
+    int lag;              // ZR_STREAM_POLL_LAG (per render): rounds the lagged loop's knowledge is behind, 0 .. POLL_MAX_LAG; 0 is the cadenced loop
+};
+static StreamSwitches read_switches() {
+    static const unsigned shade_pad = std::getenv("ZR_SHADE_LDS_PAD") ? (unsigned)std::atoi(std::getenv("ZR_SHADE_LDS_PAD")) : 0u;
+    static const bool trace_polls = std::getenv("ZR_STREAM_POLL_TRACE") != nullptr;
+    const char* in_place_env = std::getenv("ZR_SHADE_IN_PLACE");
+    const char* lag_env = std::getenv("ZR_STREAM_POLL_LAG");
+    const int lag = lag_env ? std::atoi(lag_env) : 1;
+    return StreamSwitches{shade_pad, trace_polls, !(in_place_env && std::atoi(in_place_env) == 0), lag < 0 ? 0 : (lag > POLL_MAX_LAG ? POLL_MAX_LAG : lag)};
+}
+
+// One frame of the pipeline on the device: its sub-pools, the launches of a round, and what the round loop (zr_round_polls.h: run_round_loop) asks of a device.
 // The slot pool can be split into K sub-pools that run a fraction of a round apart on K HIP streams, so that one
 // pool's EXTEND overlaps another's SHADE.  Measured on cfg3: K = 2 gains 1-3 % on a whole frame and 6 % on a rank's
 // 1/8 shard, K >= 3 loses (the stages are throughput-bound, co-running launches only stretch each other).
 // streams[0] is the caller's stream, the others are internal.
-hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level) {
-    const StreamFrame& F = job.frame; const StreamContext& X = job.ctx; const StreamHooks& H = job.hooks;
-    const DCamera& cam = *F.cam; const DEnv& env = *F.env;
-    const uint32_t P = job.pool.P, unit_chunk = job.pool.unit_chunk, n_pix = F.n_pix;
-    const int mode = job.split.mode;
-    const uint32_t n_units = n_pix * F.spp;
+struct PipelineRun {
+    const DScene& sc; const StreamJob& job; const int leaf_level; const StreamSwitches sw;
+    const StreamFrame& F; const StreamContext& X; const StreamHooks& H;
     const size_t W = stream_ctl_words();
-    int K = X.n_pools < 1 ? 1 : (X.n_pools > ST_MAX_POOLS ? ST_MAX_POOLS : X.n_pools);
-    while (K > 1 && P / K < 64u * 1024u) K--;
-    // affine hand-out (st_unit_of): a slot's shard is (slot / 256) % ST_SHARDS counted over ALL sub-pools, and the SHADE block that
-    // serves it must agree (blockIdx % ST_SHARDS inside its sub-pool): pool and sub-pools are whole rounds of ST_SHARDS blocks
-    const uint32_t pool_round = unit_chunk ? ST_SHARDS * 256u : 64u;
-    if (unit_chunk && P % pool_round != 0) return hipErrorInvalidValue;
-    while (K > 1 && P / K < pool_round) K--;
-    StreamBuf Q[ST_MAX_POOLS];
-    void* ov[ST_MAX_POOLS];
-    unsigned int* uctl = X.ctl + (size_t)ST_MAX_POOLS * W;
-    const unsigned int* h_units = X.h_active + (size_t)ST_MAX_POOLS * W;   // the host's copy of it
-    {
+    StreamBuf Q[ST_MAX_POOLS]; void* ov[ST_MAX_POOLS];
+    int K = 1;                        // sub-pools the frame begins on
+    // The lean render of a world with one material kind shades its slots IN PLACE while work units are left: the pool is full of fresh paths and the sort would
+    // only cost.  `units_left` is what the newest poll the loop holds says (true until one arrives); once the hand-out is over the pool thins out and the sorted
+    // build packs the survivors into full waves.  Either build is correct for any launch, so a stale poll only costs time.
+    const bool lean, in_place_ok;
+    const bool cadenced;
+    int shade_launches[2] = {0, 0};   // in place, sorted
+
+    PipelineRun(const DScene& sc_, const StreamJob& job_, int leaf_level_, const StreamSwitches& sw_)
+        : sc(sc_), job(job_), leaf_level(leaf_level_), sw(sw_), F(job_.frame), X(job_.ctx), H(job_.hooks), lean(sc_.shade_lean && job_.split.mode == 0),
+          in_place_ok(lean && (sc_.mat_kinds & (sc_.mat_kinds - 1u)) == 0 && sw_.in_place), cadenced(sw_.lag == 0 || job_.hooks.keep_going || job_.hooks.progress) {}
+
+    unsigned int* uctl() const { return X.ctl + (size_t)ST_MAX_POOLS * W; }   // the unit-counter block, behind the sub-pools' control blocks
+    size_t cpart_blocks() const { return (size_t)job.pool.P / 256 + ST_MAX_POOLS + 1; }
+    unsigned int* poll_words(int slot, int k) const { return X.h_polls + ((size_t)slot * ST_MAX_POOLS + (size_t)k) * POLL_WORDS; }
+    hipEvent_t poll_event(int slot, int k) const { return X.poll_events[(size_t)slot * ST_MAX_POOLS + (size_t)k]; }
+
+    // the pool as K sub-pools Q[] with their spill slabs ov[]
+    hipError_t split_pool() {
+        const uint32_t P = job.pool.P, unit_chunk = job.pool.unit_chunk, n_units = F.n_pix * F.spp;
+        K = X.n_pools < 1 ? 1 : (X.n_pools > ST_MAX_POOLS ? ST_MAX_POOLS : X.n_pools);
+        while (K > 1 && P / K < 64u * 1024u) K--;
+        // affine hand-out (st_unit_of): a slot's shard is (slot / 256) % ST_SHARDS counted over ALL sub-pools, and the SHADE block that
+        // serves it must agree (blockIdx % ST_SHARDS inside its sub-pool): pool and sub-pools are whole rounds of ST_SHARDS blocks
+        const uint32_t pool_round = unit_chunk ? ST_SHARDS * 256u : 64u;
+        if (unit_chunk && P % pool_round != 0) return hipErrorInvalidValue;
+        while (K > 1 && P / K < pool_round) K--;
         uint32_t first = 0;
         unsigned char* base = (unsigned char*)job.pool.slots;
         for (int k = 0; k < K; k++) {
             uint32_t Pk = k == K - 1 ? P - first : (P / K + pool_round - 1) / pool_round * pool_round;
-            Q[k] = make_buf(base, Pk, F.spp, n_units, n_pix, F.pixels, F.samples, X.ctl + (size_t)k * W, uctl, first, P);
+            Q[k] = make_buf(base, Pk, F.spp, n_units, F.n_pix, F.pixels, F.samples, X.ctl + (size_t)k * W, uctl(), first, P);
             Q[k].unit_chunk = unit_chunk; Q[k].shard_k0 = unit_chunk ? P / ST_SHARDS : 0u; Q[k].sample0 = F.sample0;
             Q[k].kend = (uint2*)job.split.kend; Q[k].cls = (unsigned char*)job.split.cls;
             Q[k].cpart = job.split.cpart ? job.split.cpart + ((size_t)first / 256 + (size_t)k) * 4 : nullptr;
@@ -1371,226 +1425,136 @@ hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level)
             base += stream_pool_bytes(Pk);
             first += Pk;
         }
+        return hipSuccess;
     }
-    hipError_t e;
-    hipStream_t stream = X.streams[0];
-    if ((e = clear_ctl(X.ctl, stream)) != hipSuccess) return e;
-    const size_t cpart_blocks = (size_t)P / 256 + ST_MAX_POOLS + 1;
-    if (job.split.cpart && (e = hipMemsetAsync(job.split.cpart, 0, cpart_blocks * 4 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
-    auto init = [&](const StreamBuf& B, hipStream_t st) {
+
+    void init(int k) {
+        const hipStream_t st = X.streams[k];
         if (H.timer) H.timer->begin(st, 0);
-        if (F.count) hipLaunchKernelGGL(stream_init<true>, dim3((B.P + 255) / 256), dim3(256), 0, st, B, cam, F.seed, X.gctr);
-        else hipLaunchKernelGGL(stream_init<false>, dim3((B.P + 255) / 256), dim3(256), 0, st, B, cam, F.seed, X.gctr);
+        if (F.count) hipLaunchKernelGGL(stream_init<true>, dim3((Q[k].P + 255) / 256), dim3(256), 0, st, Q[k], *F.cam, F.seed, X.gctr);
+        else hipLaunchKernelGGL(stream_init<false>, dim3((Q[k].P + 255) / 256), dim3(256), 0, st, Q[k], *F.cam, F.seed, X.gctr);
         if (H.timer) H.timer->end(st, 0);
-    };
-    auto extend = [&](const StreamBuf& B, void* o, hipStream_t st) {
-        const int eb = (int)((B.P + 63) / 64 < (uint32_t)X.extend_blocks ? (B.P + 63) / 64 : (uint32_t)X.extend_blocks);
+    }
+    void extend(int k) {
+        const hipStream_t st = X.streams[k];
+        const uint32_t waves = (Q[k].P + 63) / 64;
         if (H.timer) H.timer->begin(st, 1);
-        if (F.count) launch_extend<true>(sc, B, o, X.ovf_levels, eb, X.gctr, leaf_level, st); else launch_extend<false>(sc, B, o, X.ovf_levels, eb, X.gctr, leaf_level, st);
+        launch_extend(F.count, leaf_level, sc, Q[k], ov[k], X.ovf_levels, (int)(waves < (uint32_t)X.extend_blocks ? waves : (uint32_t)X.extend_blocks), X.gctr, st);
         if (H.timer) H.timer->end(st, 1);
-    };
-    // development aid: ZR_SHADE_LDS_PAD bytes of dynamic LDS per SHADE block lower the blocks a CU can hold (160 KB: 4 fit by registers; > 40 KB: 3, > 53 KB: 2)
-    static const unsigned shade_pad = std::getenv("ZR_SHADE_LDS_PAD") ? (unsigned)std::atoi(std::getenv("ZR_SHADE_LDS_PAD")) : 0u;
-    // The lean render of a world with one material kind shades its slots IN PLACE (stream_shade<., 0, true, false, false>) while work units are left: the pool is
-    // full of fresh paths and the sort would only cost.  `units_left` is what the newest poll the loop holds says (true until one arrives); once the hand-out is
-    // over the pool thins out and the sorted build packs the survivors into full waves.  Either build is correct for any launch, so a stale poll only costs time.
-    // ZR_SHADE_IN_PLACE=0 (read per render) forces the sorted build.
-    const char* in_place_env = std::getenv("ZR_SHADE_IN_PLACE");
-    const bool in_place_ok = sc.shade_lean && mode == 0 && (sc.mat_kinds & (sc.mat_kinds - 1u)) == 0 && !(in_place_env && std::atoi(in_place_env) == 0);
-    bool units_left = true;
-    int shade_launches[2] = {0, 0};   // in place, sorted
-    auto shade = [&](const StreamBuf& B, hipStream_t st) {
+    }
+    void shade(int k, bool units_left) {
+        const hipStream_t st = X.streams[k];
+        const ShadeFamily family = in_place_ok && units_left ? SHADE_IN_PLACE : (lean ? SHADE_LEAN : (sc.tri_uv_at ? SHADE_UV : SHADE_GENERAL));
         if (H.timer) H.timer->begin(st, 2);
-        const dim3 sg((B.P + 255) / 256), sb(256);
-        const bool in_place = in_place_ok && units_left;
-        shade_launches[in_place ? 0 : 1]++;
-        if (in_place) {
-            const dim3 sg((B.P + 255) / 256 * 4), sb(64);   // one wave per workgroup, four per slot block
-            if (F.count) hipLaunchKernelGGL((stream_shade<true, 0, true, false, false>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
-            else hipLaunchKernelGGL((stream_shade<false, 0, true, false, false>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
-        }
-        else if (sc.shade_lean && mode == 0) {   // the lean build: same arithmetic, fewer registers, 6 waves per SIMD instead of 4 (see lean_rec, zr_device.h)
-            if (F.count) hipLaunchKernelGGL((stream_shade<true, 0, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
-            else hipLaunchKernelGGL((stream_shade<false, 0, true>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
-        }
-        else if (sc.tri_uv_at) {   // the general builds that read the triangles' texture coordinates
-            if (mode == 1) hipLaunchKernelGGL((stream_shade<true, 1, false, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
-            else if (mode == 2) hipLaunchKernelGGL((stream_shade<true, 2, false, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
-            else if (F.count) hipLaunchKernelGGL((stream_shade<true, 0, false, true>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
-            else hipLaunchKernelGGL((stream_shade<false, 0, false, true>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
-        }
-        else if (shade_pad && mode == 0 && !F.count) hipLaunchKernelGGL((stream_shade<false, 0>), sg, sb, shade_pad, st, sc, cam, env, F.seed, B, X.gctr);
-        else if (mode == 1) hipLaunchKernelGGL((stream_shade<true, 1>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);        // the split passes always count
-        else if (mode == 2) hipLaunchKernelGGL((stream_shade<true, 2>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
-        else if (F.count) hipLaunchKernelGGL((stream_shade<true, 0>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
-        else hipLaunchKernelGGL((stream_shade<false, 0>), sg, sb, 0, st, sc, cam, env, F.seed, B, X.gctr);
+        shade_launches[family == SHADE_IN_PLACE ? 0 : 1]++;
+        launch_shade(family, F.count, job.split.mode, sw.shade_pad, sc, *F.cam, *F.env, F.seed, Q[k], X.gctr, st);
         if (H.timer) H.timer->end(st, 2);
-    };
+    }
+
     // start-up: pool k is initialised after the control words are cleared and starts once pool k-1 has a round in flight
-    init(Q[0], stream);
-    for (int k = 1; k < K; k++) {
-        extend(Q[k - 1], ov[k - 1], X.streams[k - 1]);
-        if ((e = hipEventRecord(X.event, X.streams[k - 1])) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(X.streams[k], X.event, 0)) != hipSuccess) return e;
-        init(Q[k], X.streams[k]);
-        shade(Q[k - 1], X.streams[k - 1]);
-    }
-    // THE ROUND LOOP.  A loop round is EXTEND, SHADE and the round's poll (stream_poll) on every sub-pool's stream.  The host has to learn three things from
-    // the device: that the pools are empty, that the survivors are few enough for the drain pool, that a wave was capped.
-    //  - The LAGGED loop (a frame nobody polls: the timed path) keeps lag + 1 rounds in flight and waits for the event behind the OLDEST round's poll only, so a
-    //    stream never runs dry and one sub-pool's SHADE always has the other's EXTEND beside it.  What it learns is `lag` rounds old: the frame ends with up to
-    //    `lag` rounds on empty pools, which nobody sees (the round count and the launch log stop at the round that emptied the pools), the drain switch and a
-    //    capped wave are noticed up to `lag` rounds late.
-    //  - The CADENCED loop (ZR_STREAM_POLL_LAG=0, and every frame with keep_going or progress: camera::render cancels within two rounds and previews what is
-    //    finished) enqueues check_every rounds, copies the control words and synchronises every stream.
-    // Both count their rounds in RoundPolls (zr_round_polls.h), which also says why a poll's stale count may size the drain pool.
-    // Measured on cfg3 (profiles/r25_round_loop_ab.txt): the streams were never empty for long (0.55 ms of a frame without any kernel, before and after); what the
-    // lag buys is the drain switch one round after its condition holds instead of four (the cadenced loop was in a run of 8 rounds when it came true, and each late round walks two
-    // 52 Mi-slot pools for a few hundred thousand paths): 296.5 against 300.5 ms, lag 0 299.8, lag 2 298.2 (a second queued round on the big pools).
-    const int start_rounds = K > 1 ? 1 : 0, K0 = K;
-    const char* lag_env = std::getenv("ZR_STREAM_POLL_LAG");
-    int lag = lag_env ? std::atoi(lag_env) : 1;
-    lag = lag < 0 ? 0 : (lag > POLL_MAX_LAG ? POLL_MAX_LAG : lag);
-    const bool cadenced = lag == 0 || H.keep_going || H.progress || !X.h_polls || !X.poll_events;
-    RoundPolls rp(cadenced ? POLL_RING : lag + 1);
-    auto poll_words = [&](int slot, int k) { return X.h_polls + ((size_t)slot * ST_MAX_POOLS + (size_t)k) * POLL_WORDS; };
-    auto poll_event = [&](int slot, int k) { return X.poll_events[(size_t)slot * ST_MAX_POOLS + (size_t)k]; };
-    auto enqueue_round = [&](bool with_events) {   // on the current K sub-pools
-        const int s = rp.slot(rp.enqueued + 1);
-        for (int k = K - 1; k >= 0; k--) {
-            extend(Q[k], ov[k], X.streams[k]); shade(Q[k], X.streams[k]);
-            if (!X.h_polls) continue;
-            hipLaunchKernelGGL(stream_poll, dim3(1), dim3(64), 0, X.streams[k], Q[k], poll_words(s, k));
-            if (with_events && e == hipSuccess) e = hipEventRecord(poll_event(s, k), X.streams[k]);
+    hipError_t start_up() {
+        hipError_t e;
+        if ((e = clear_ctl(X.ctl, X.streams[0])) != hipSuccess) return e;
+        if (job.split.cpart && (e = hipMemsetAsync(job.split.cpart, 0, cpart_blocks() * 4 * sizeof(unsigned long long), X.streams[0])) != hipSuccess) return e;
+        init(0);
+        for (int k = 1; k < K; k++) {
+            extend(k - 1);
+            if ((e = hipEventRecord(X.event, X.streams[k - 1])) != hipSuccess) return e;
+            if ((e = hipStreamWaitEvent(X.streams[k], X.event, 0)) != hipSuccess) return e;
+            init(k);
+            shade(k - 1, true);
         }
-        rp.push(K, H.timer ? H.timer->logged() : 0);
-    };
-    // the survivors of Q[0 .. K) move to the drain pool of D_P slots (see stream_compact), on stream 0, which the caller has ordered behind the other streams
-    auto compact_to_drain = [&](uint32_t D_P) {
+        return hipSuccess;
+    }
+
+    // ---- the round loop's device (zr_round_polls.h); a status is a hipError_t ----
+    int enqueue_round(int slot, int pools, bool with_events, bool units_left) {
+        hipError_t e = hipSuccess;
+        for (int k = pools - 1; k >= 0; k--) {
+            extend(k); shade(k, units_left);
+            hipLaunchKernelGGL(stream_poll, dim3(1), dim3(64), 0, X.streams[k], Q[k], poll_words(slot, k));
+            if (with_events && e == hipSuccess) e = hipEventRecord(poll_event(slot, k), X.streams[k]);
+        }
+        return (int)e;
+    }
+    int wait_poll(int slot, int k) { return (int)hipEventSynchronize(poll_event(slot, k)); }
+    int wait_all(int pools) {
+        hipError_t e = hipSuccess;
+        for (int k = pools - 1; k >= 0 && e == hipSuccess; k--) e = hipStreamSynchronize(X.streams[k]);
+        return (int)e;
+    }
+    int order_behind(int slot, int pools) {
+        hipError_t e = hipSuccess;
+        for (int k = 1; k < pools && e == hipSuccess; k++) e = hipStreamWaitEvent(X.streams[0], poll_event(slot, k), 0);
+        return (int)e;
+    }
+    // the survivors of Q[0 .. pools) move to the drain pool of drain_P slots (see stream_compact), on stream 0, which the loop has ordered behind the other streams
+    int compact(uint32_t drain_P, int pools) {
         StreamBuf D = Q[0];
-        D.pool = (double*)job.pool.drain; D.P = D_P; D.unit0 = 0;
+        D.pool = (double*)job.pool.drain; D.P = drain_P; D.unit0 = 0;
         unsigned int* counter = X.ctl + CTL_COMPACT;   // (of pool 0)
-        for (int k = 0; k < K; k++) {
+        for (int k = 0; k < pools; k++) {
             const uint32_t per_block = 256u * ST_COMPACT_PER;
-            hipLaunchKernelGGL(stream_compact, dim3((uint32_t)(((unsigned long long)Q[k].P + per_block - 1) / per_block)), dim3(256), 0, stream, Q[k], D, counter);
+            hipLaunchKernelGGL(stream_compact, dim3((uint32_t)(((unsigned long long)Q[k].P + per_block - 1) / per_block)), dim3(256), 0, X.streams[0], Q[k], D, counter);
         }
-        hipLaunchKernelGGL(stream_compact_pad, dim3(D.P / 256), dim3(256), 0, stream, D, counter);
-        Q[0] = D; K = 1;
-    };
-    int rounds = start_rounds, drain_round = 0;
-    int check_every = H.progress ? 2 : 8;
-    bool cancelled = false, drained = false, capped = false;
-    static const bool trace_polls = std::getenv("ZR_STREAM_POLL_TRACE") != nullptr;   // development aid: one line per poll on stderr
-    if (!cadenced) for (;;) {
-        while (rp.may_enqueue() && e == hipSuccess) enqueue_round(true);
-        if (e != hipSuccess) break;
-        const int s = rp.slot(rp.oldest());
-        PollResult p;
-        for (int k = 0; k < rp.pools[s] && e == hipSuccess; k++) {
-            e = hipEventSynchronize(poll_event(s, k));
-            p.add(poll_words(s, k));
-        }
-        if (e != hipSuccess) break;
-        const RoundPolls::Action a = rp.take(p, P, job.pool.drain_slots, job.pool.drain != nullptr);
-        units_left = p.units_left;   // which SHADE build the next rounds take
-        if (trace_polls) std::fprintf(stderr, "[zr] poll of round %d (%d queued behind it): active %llu, units left %d, drain condition %d%s\n", rp.polled, rp.in_flight(),
-                                      p.active, (int)p.units_left, (int)drain_condition(p, P, job.pool.drain_slots), a.drain ? " -> compaction" : "");
-        if (a.finished) break;
-        if (a.drain) {
-            // stream 0 waits for what the other streams still hold: the event of the newest round stands behind a stream's last queued launch.  No host wait.
-            const int newest = rp.slot(rp.enqueued);
-            for (int k = 1; k < K && e == hipSuccess; k++) e = hipStreamWaitEvent(stream, poll_event(newest, k), 0);
-            if (e != hipSuccess) break;
-            compact_to_drain(a.drain_P);
-            drained = true; drain_round = rp.enqueued;
-        }
-        if (rp.enqueued > (1 << 22)) { e = hipErrorLaunchFailure; break; }
+        hipLaunchKernelGGL(stream_compact_pad, dim3(D.P / 256), dim3(256), 0, X.streams[0], D, counter);
+        Q[0] = D;
+        return 0;
     }
-    if (!cadenced && e == hipSuccess) {
-        // the rounds queued behind the emptying one run on empty pools; the frame's last kernels (stream 0) follow the other streams' share of them
-        const int newest = rp.slot(rp.enqueued);
-        for (int k = 1; k < K && e == hipSuccess; k++) e = hipStreamWaitEvent(stream, poll_event(newest, k), 0);
-        capped = rp.capped;
+    // the finished fraction: the units started (the one figure no poll carries: the unit counters are copied for it) less those still on their way
+    int report_progress(unsigned long long active) {
+        if (!H.progress) return 0;
+        unsigned int* h_units = X.h_active + (size_t)ST_MAX_POOLS * W;
+        hipError_t e = hipMemcpyAsync(h_units, uctl(), W * sizeof(unsigned int), hipMemcpyDeviceToHost, X.streams[0]);
+        if (e != hipSuccess || (e = hipStreamSynchronize(X.streams[0])) != hipSuccess) return (int)e;
+        const uint32_t n_units = F.n_pix * F.spp;
+        const unsigned long long started = units_started(job.pool.unit_chunk, job.pool.P, n_units, h_units + CTL_SH_UNITS, CTL_STRIDE);
+        const double frac = started > active ? (double)(started - active) / (double)n_units : 0.0;
+        return (int)reduce_and_report(*H.progress, frac, job.split.mode == 0, F, Q[0], X.streams[0]);
     }
-    if (cadenced) for (;;) {
-        for (int r = 0; r < check_every; r++) { enqueue_round(false); rounds++; }
-        for (int k = 0; k < K && e == hipSuccess; k++)
-            e = hipMemcpyAsync(X.h_active + (size_t)k * W, X.ctl + (size_t)k * W, W * sizeof(unsigned int), hipMemcpyDeviceToHost, X.streams[k]);
-        if (e == hipSuccess)   // the work-unit counters: how many samples have been started
-            e = hipMemcpyAsync(X.h_active + (size_t)ST_MAX_POOLS * W, uctl, W * sizeof(unsigned int), hipMemcpyDeviceToHost, X.streams[0]);
-        for (int k = K - 1; k >= 0 && e == hipSuccess; k--) e = hipStreamSynchronize(X.streams[k]);
-        if (e != hipSuccess) break;
-        unsigned long long active = 0;
-        for (int k = 0; k < K; k++) {
-            if (X.h_active[(size_t)k * W + CTL_CAPPED] != 0) capped = true;   // (looked at here, for every sub-pool: the drain below folds them into one)
-            for (int sh = 0; sh < ST_SHARDS; sh++) active += X.h_active[(size_t)k * W + CTL_SHARD0 + CTL_STRIDE * sh + CTL_SH_ACTIVE];
+    bool cancelled() const { return H.keep_going && *H.keep_going == 0; }
+    size_t launches_logged() const { return H.timer ? H.timer->logged() : 0; }
+    void polled(const RoundPolls& rp, const PollResult& p, bool compaction) const {
+        if (!sw.trace_polls) return;
+        const bool condition = drain_condition(p, job.pool.P, job.pool.drain_slots);
+        if (!cadenced)
+            std::fprintf(stderr, "[zr] poll of round %d (%d queued behind it): active %llu, units left %d, drain condition %d%s\n", rp.polled, rp.in_flight(), p.active,
+                         (int)p.units_left, (int)condition, compaction ? " -> compaction" : "");
+        else {
+            std::fprintf(stderr, "[zr] poll of round %d (drained with %d behind it): active %llu, units left %d, drain condition %d\n", rp.polled, rp.in_flight(), p.active,
+                         (int)p.units_left, (int)(p.active != 0 && condition));
+            if (compaction) std::fprintf(stderr, "[zr] compaction behind round %d\n", rp.enqueued);
         }
-        while (rp.in_flight() > 0) {   // which of these rounds emptied the pools: the rounds' own polls say (the copies above show the last round only)
-            PollResult p;
-            const int s = rp.slot(rp.oldest());
-            if (X.h_polls) for (int k = 0; k < rp.pools[s]; k++) p.add(poll_words(s, k));
-            else p.active = rp.in_flight() == 1 ? active : 1ull;
-            (void)rp.take(p, P, job.pool.drain_slots, false);
-            if (trace_polls) std::fprintf(stderr, "[zr] poll of round %d (drained with %d behind it): active %llu, units left %d, drain condition %d\n", rp.polled, rp.in_flight(),
-                                          p.active, (int)p.units_left, (int)(p.active != 0 && drain_condition(p, P, job.pool.drain_slots)));
-        }
-        if (H.progress && active != 0) {
-            unsigned long long started = 0;   // the first P units are dealt at initialisation, the rest through the sharded counters
-            if (!unit_chunk) { started = P; for (int sh = 0; sh < ST_SHARDS; sh++) started += h_units[CTL_STRIDE * sh + CTL_SH_UNITS]; }
-            else for (int sh = 0; sh < ST_SHARDS; sh++) {   // affine: of a shard's sequence, the units that exist (a shard's last chunks may lie beyond the frame)
-                const unsigned long long k_sh = (unsigned long long)(P / ST_SHARDS) + h_units[CTL_STRIDE * sh + CTL_SH_UNITS];
-                const uint32_t pos = ((uint32_t)sh & 7u) * (ST_SHARDS / 8u) + ((uint32_t)sh >> 3);
-                const unsigned long long full = k_sh / unit_chunk, part = k_sh % unit_chunk;
-                for (unsigned long long q = 0; q <= full; q++) {
-                    const unsigned long long c0 = (q * ST_SHARDS + pos) * unit_chunk, len = q < full ? unit_chunk : part;
-                    if (c0 < n_units) started += c0 + len <= n_units ? len : n_units - c0;
-                }
-            }
-            if (started > n_units) started = n_units;
-            const double frac = started > active ? (double)(started - active) / (double)n_units : 0.0;
-            bool reduced = false;
-            if (mode == 0 && F.out && H.progress->wants_frame()) {   // samples[] is zero-initialised in this case (render_stream)
-                hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, Q[0], cam, F.out);
-                if ((e = hipStreamSynchronize(stream)) != hipSuccess) break;
-                reduced = true;
-            }
-            H.progress->report(frac, reduced);
-        }
-        if (active == 0) break;
-        if (units_left) {   // this loop's own copy of the unit counters (it also chooses the SHADE build of the next rounds)
-            units_left = false;   // shard sh has handed out every k below its counter: unit_base + k * shards + sh
-            for (int sh = 0; sh < ST_SHARDS && !units_left; sh++)
-                if (st_unit_of(unit_chunk, P, (uint32_t)sh, (unsigned long long)(unit_chunk ? P / ST_SHARDS : 0u) + h_units[CTL_STRIDE * sh + CTL_SH_UNITS]) < (unsigned long long)n_units) units_left = true;
-        }
-        if (!drained && job.pool.drain && active * 16ull <= (unsigned long long)P && active <= (unsigned long long)job.pool.drain_slots) {
-            if (!units_left) {   // see stream_compact
-                compact_to_drain(drain_pool_slots(active));
-                if (trace_polls) std::fprintf(stderr, "[zr] compaction behind round %d\n", rp.enqueued);
-                if ((e = hipStreamSynchronize(stream)) != hipSuccess) break;
-                drained = true; drain_round = rp.enqueued;
-            }
-        }
-        check_every = active > P / 2 ? 8 : (active > P / 16 ? 4 : 2);
-        if (H.progress && check_every > 2) check_every = 2;   // an interactive caller: report (and poll keep_going) every other round
-        if (H.keep_going && *H.keep_going == 0) { cancelled = true; break; }
-        if (rounds > (1 << 22)) { e = hipErrorLaunchFailure; break; }
     }
-    if (e != hipSuccess) return e;
-    if (capped) return hipErrorLaunchFailure;  // an EXTEND wave of some sub-pool hit its iteration cap: its rays were abandoned mid-walk
-    if (rp.emptied != 0) {   // the rounds behind the one that emptied the pools changed nothing: the caller does not see them, nor their launches
-        rounds = start_rounds + rp.emptied;
-        if (H.timer) H.timer->drop_from(rp.log_keep());
+
+    // counters, the frame, and what the caller wanted to know
+    hipError_t finish(const RoundLoopOutcome& loop) {
+        const hipStream_t stream = X.streams[0];
+        const int rounds = (K > 1 ? 1 : 0) + loop.rounds;   // (the start-up ran a round on all sub-pools but the last)
+        // the rounds behind the one that emptied the pools changed nothing: the caller does not see them, nor their launches
+        if (loop.emptied && H.timer) H.timer->drop_from(loop.log_keep);
+        if (H.timer) H.timer->begin(stream, 3);
+        if (job.split.cpart) hipLaunchKernelGGL(stream_sum_counters, dim3(1), dim3(256), 0, stream, job.split.cpart, cpart_blocks(), X.gctr);
+        if (job.split.mode == 2) hipLaunchKernelGGL(stream_reduce_split, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, Q[0], *F.cam, F.out, F.out2);
+        else if (F.out) hipLaunchKernelGGL(stream_reduce, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, Q[0], *F.cam, F.out);
+        if (H.timer) H.timer->end(stream, 3);
+        if (H.done_out) *H.done_out = loop.cancelled ? -rounds : rounds;
+        if (H.drain_out) { H.drain_out[0] = loop.drain_round; H.drain_out[1] = K; }
+        if (H.shade_out) { H.shade_out[0] = shade_launches[0]; H.shade_out[1] = shade_launches[1]; }
+        return hipGetLastError();
     }
-    const StreamBuf& A = Q[0];
-    if (H.timer) H.timer->begin(stream, 3);
-    if (job.split.cpart) hipLaunchKernelGGL(stream_sum_counters, dim3(1), dim3(256), 0, stream, job.split.cpart, cpart_blocks, X.gctr);
-    if (mode == 2) hipLaunchKernelGGL(stream_reduce_split, dim3((n_pix + 3) / 4), dim3(256), 0, stream, A, cam, F.out, F.out2);
-    else if (F.out) hipLaunchKernelGGL(stream_reduce, dim3((n_pix + 3) / 4), dim3(256), 0, stream, A, cam, F.out);
-    if (H.timer) H.timer->end(stream, 3);
-    if (H.done_out) *H.done_out = cancelled ? -rounds : rounds;
-    if (H.drain_out) { H.drain_out[0] = drain_round; H.drain_out[1] = K0; }
-    if (H.shade_out) { H.shade_out[0] = shade_launches[0]; H.shade_out[1] = shade_launches[1]; }
-    return hipGetLastError();
+};
+
+hipError_t stream_render(const DScene& sc, const StreamJob& job, int leaf_level) {
+    if (!job.ctx.h_polls || !job.ctx.poll_events) return hipErrorInvalidValue;   // the round loop learns what the device did from its polls alone
+    PipelineRun run(sc, job, leaf_level, read_switches());
+    hipError_t e;
+    if ((e = run.split_pool()) != hipSuccess || (e = run.start_up()) != hipSuccess) return e;
+    const int max_run = job.hooks.progress ? 2 : POLL_RING;   // an interactive caller: report (and poll keep_going) every other round
+    const RoundLoopOutcome loop = run_round_loop(run, RoundLoopPlan{run.cadenced, run.sw.lag, run.K, job.pool.P, job.pool.drain_slots, job.pool.drain != nullptr, max_run});
+    if (loop.status != 0) return (hipError_t)loop.status;
+    if (loop.runaway || loop.capped) return hipErrorLaunchFailure;  // capped: an EXTEND wave of some sub-pool hit its iteration cap, its rays were abandoned mid-walk
+    return run.finish(loop);
 }
 
 // the fused small-scene render: one persistent launch over all units, then the pipeline's reduce.  `level`: 1 = no wrapped objects
@@ -1602,7 +1566,6 @@ int fused_blocks() {
     return cus * per_cu;
 }
 hipError_t fused_render_frame(const DScene& sc, const StreamFrame& F, const StreamContext& X, int blocks, int level, const FusedObjs& fo, const StreamHooks& H) {
-    const DCamera& cam = *F.cam; const DEnv& env = *F.env;
     hipStream_t stream = X.streams[0];
     const uint32_t n_units = F.n_pix * F.spp;
     const size_t W = stream_ctl_words();
@@ -1622,32 +1585,19 @@ hipError_t fused_render_frame(const DScene& sc, const StreamFrame& F, const Stre
         if (B.chunk_hi == B.chunk_lo) continue;
         if ((e = hipMemsetAsync(X.ctl, 0, (ST_MAX_POOLS + 1) * W * sizeof(unsigned int), stream)) != hipSuccess) return e;
         const unsigned long long want_blocks = ((unsigned long long)(B.chunk_hi - B.chunk_lo) + 3) / 4;   // no more waves than chunks
-        const dim3 grid((unsigned)(want_blocks < (unsigned long long)blocks ? (want_blocks ? want_blocks : 1) : blocks)), block(256);
+        const dim3 grid((unsigned)(want_blocks < (unsigned long long)blocks ? (want_blocks ? want_blocks : 1) : blocks));
         if (H.timer) H.timer->begin(stream, 1);
-        if (sc.tri_uv_at) {   // the builds that read the triangles' texture coordinates
-            if (level <= 1) { if (F.count) hipLaunchKernelGGL((fused_render<1, true, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<1, false, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
-            else { if (F.count) hipLaunchKernelGGL((fused_render<2, true, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<2, false, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
-        }
-        else if (level <= 1) { if (F.count) hipLaunchKernelGGL((fused_render<1, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<1, false>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
-        else { if (F.count) hipLaunchKernelGGL((fused_render<2, true>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); else hipLaunchKernelGGL((fused_render<2, false>), grid, block, 0, stream, sc, cam, env, F.seed, B, X.gctr, fo); }
+        launch_fused(level, F.count, sc.tri_uv_at != 0, grid, sc, *F.cam, *F.env, F.seed, B, X.gctr, fo, stream);
         if (H.timer) H.timer->end(stream, 1);
         done = p + 1;
         if (parts > 1 && p + 1 < parts) {
             if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-            if (H.progress) {
-                bool reduced = false;
-                if (F.out && H.progress->wants_frame()) {
-                    hipLaunchKernelGGL(stream_reduce, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, R, cam, F.out);
-                    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-                    reduced = true;
-                }
-                H.progress->report((double)(p + 1) / parts, reduced);
-            }
+            if (H.progress && (e = reduce_and_report(*H.progress, (double)(p + 1) / parts, true, F, R, stream)) != hipSuccess) return e;
             if (H.keep_going && *H.keep_going == 0) cancelled = true;
         }
     }
     if (H.timer) H.timer->begin(stream, 3);
-    if (F.out) hipLaunchKernelGGL(stream_reduce, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, R, cam, F.out);
+    if (F.out) hipLaunchKernelGGL(stream_reduce, dim3((F.n_pix + 3) / 4), dim3(256), 0, stream, R, *F.cam, F.out);
     if (H.timer) H.timer->end(stream, 3);
     if (H.done_out) *H.done_out = cancelled ? -done : done;
     return hipGetLastError();
@@ -1676,7 +1626,7 @@ hipError_t stream_trace(const DScene& sc, const double* d_rays, uint32_t n, uint
     if ((e = clear_ctl(X.ctl, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(stream_load_rays, dim3((P + 255) / 256), dim3(256), 0, stream, B, d_rays, n, seed, pixel, bounce);
     const int eb = (int)(P / 64 < (uint32_t)X.extend_blocks ? P / 64 : (uint32_t)X.extend_blocks);
-    launch_extend<false>(sc, B, X.overflow, X.ovf_levels, eb, X.gctr, leaf_level, stream);
+    launch_extend(false, leaf_level, sc, B, X.overflow, X.ovf_levels, eb, X.gctr, stream);
     if (sc.tri_uv_at) hipLaunchKernelGGL(stream_hits_out<true>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out, d_out_ki);
     else hipLaunchKernelGGL(stream_hits_out<false>, dim3((n + 255) / 256), dim3(256), 0, stream, sc, B, n, d_out, d_out_ki);
     return hipGetLastError();

@@ -1,6 +1,7 @@
-"""The host's decisions in the pipeline's round loop (raytracer_project_amd/csrc/zr_round_polls.h: ring indexing, which round emptied the pools, which launches of
-the log belong to the rounds a caller sees, the drain switch and why a stale count may size the drain pool) on their own: tests/native/round_polls_check.cpp is
-compiled for the host with the address and undefined-behaviour sanitizers and driven by scripted poll sequences.  No HIP, no GPU."""
+"""The pipeline's round loop (raytracer_project_amd/csrc/zr_round_polls.h: run_round_loop, the driver stream_render runs, in both poll modes: ring indexing, which
+round emptied the pools, which launches of the log belong to the rounds a caller sees, the drain switch and why a stale count may size the drain pool, the cadenced
+mode's runs, cancellation) and the host's count of started work units (zr_units.h) on their own: tests/native/round_polls_check.cpp is compiled for the host with
+the address and undefined-behaviour sanitizers and runs the driver against scripted devices.  No HIP, no GPU."""
 import os
 import subprocess
 
