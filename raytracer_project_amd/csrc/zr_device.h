@@ -192,7 +192,9 @@ __device__ __forceinline__ bool sphere_t(const double* s, const Ray& r, double t
 
 // ---- EXTEND's conservative FP32 slab test (derivation and error bound: zr_stream.hip, above stream_extend) --------------------
 // Macros over the names of the code they are expanded in: `ray`, the slab constants idx_ idy_ idz_ / cnx cny cnz / cfx cfy cfz, tbest_f, INFf,
-// COUNT and c_nodes.  stream_extend and ray_escapes (below) share this one definition, so both take the same decision about a box.
+// COUNT and c_nodes (ZR_QNODE: also tn0 .. tn3, r0 .. r3).  stream_extend, ray_escapes and camera_ray_escapes (below) share this one definition, so all
+// take the same decision about a box, and tests/native/slab_check.cpp expands it on the host under an exact judge.  Domain: every finite o, every d, planes
+// within 1e18 (device builder) or 1e30 (host builder); the rule that keeps every intermediate finite there is ZR_RAY_CONSTANTS' (slab_id_limit below).
 // one child from the parametric distances of its six planes (absolute slack already inside): entry distance or +inf
 #define ZR_SLAB(X0, X1, Y0, Y1, Z0, Z1, RF_IN, TN, RF)                                                      \
     {                                                                                                       \
@@ -207,16 +209,46 @@ __device__ __forceinline__ bool sphere_t(const double* s, const Ray& r, double t
         TN = hit_ ? n_ : INFf;                                                                              \
         RF = (RF_IN);                                                                                       \
     }
-// the slab constants of `ray`
-#define ZR_RAY_CONSTANTS()                                                                                  \
+// The largest |1/d| an axis may have in a tree whose planes lie within M = the largest |plane| of its root: 2^(115 - ilogb(M)), at most 2^100, a power of two
+// taken from M's exponent bits alone (stream_extend gets it as a kernel argument, computed by its launcher; the escape predicates compute it from the root in
+// their kernel arguments with scalar integer operations).  Then |plane| |id| < 2^116 for the root's planes, and for the grid of
+// any node below it — whose origin lies within M and whose 255 steps span less than four times its children's extent of at most 2 M —
+// |origin id| < 2^116 and 255 |a| < 2^119: with |c| < 2^120 (1 + 2^-22) every plane distance and every b stays finite, far inside the float range.  A world within
+// 2^16 (every benchmarked one) keeps the limit 2^100 it always had; an empty or zero root too; a root with an infinite or NaN plane gets 2^-13 or less.
+__host__ __device__ __forceinline__ float slab_id_limit_of(float m) {
+    const uint32_t mexp = (__builtin_bit_cast(uint32_t, m) >> 23) & 0xFFu;   // biased: ilogb(M) + 127
+    const uint32_t lexp = 369u - mexp;                                       // 115 - ilogb(M) + 127: 114 ... 369
+    return __builtin_bit_cast(float, (lexp < 227u ? lexp : 227u) << 23);
+}
+__host__ __device__ __forceinline__ float slab_id_limit(const NodeF& root) {
+    uint32_t m = 0;   // |x| of non-negative floats orders as their bit patterns do: the maximum in integer arithmetic
+    // (written out, with constant indices: the root stays in the kernel arguments)
+#define ZR_ABS_MAX(X) { const uint32_t b_ = __builtin_bit_cast(uint32_t, (X)) & 0x7FFFFFFFu; m = b_ > m ? b_ : m; }
+#define ZR_ABS_MAX_CHILD(C) \
+    if (root.ref[C] != ZR_REF_EMPTY) { ZR_ABS_MAX(root.lox[C]) ZR_ABS_MAX(root.loy[C]) ZR_ABS_MAX(root.loz[C]) ZR_ABS_MAX(root.hix[C]) ZR_ABS_MAX(root.hiy[C]) ZR_ABS_MAX(root.hiz[C]) }
+    ZR_ABS_MAX_CHILD(0) ZR_ABS_MAX_CHILD(1) ZR_ABS_MAX_CHILD(2) ZR_ABS_MAX_CHILD(3)
+#undef ZR_ABS_MAX_CHILD
+#undef ZR_ABS_MAX
+    return slab_id_limit_of(__builtin_bit_cast(float, m));
+}
+// ... and of a placed run's own tree, whose root is a grid node: its planes lie within |origin| + 255 scale
+__host__ __device__ __forceinline__ float slab_id_limit(const NodeQ& run_root) {
+    float m = 0.0f;
+    for (int k = 0; k < 3; k++) m = fmaxf(m, fmaf(run_root.scale[k], 256.0f, fabsf(run_root.origin[k])));
+    return slab_id_limit_of(m);
+}
+// the slab constants of `ray` in a tree whose limit on |1/d| is ID_LIM (slab_id_limit)
+#define ZR_RAY_CONSTANTS(ID_LIM)                                                                            \
     {                                                                                                       \
         const float NANf = __builtin_nanf("");                                                              \
+        const float lim_ = (ID_LIM);                                                                        \
         idx_ = 1.0f / (float)ray.d.x; idy_ = 1.0f / (float)ray.d.y; idz_ = 1.0f / (float)ray.d.z;            \
         float ocx = (float)(-ray.o.x * (double)idx_), ocy = (float)(-ray.o.y * (double)idy_), ocz = (float)(-ray.o.z * (double)idz_); \
-        /* 2^100 / 2^120: far inside the float range, so that no product with a plane or a scale overflows */ \
-        if (!(fabsf(idx_) < 1.2676506e30f) || !(fabsf(ocx) < 1.3292280e36f)) { idx_ = 0.0f; ocx = NANf; }    \
-        if (!(fabsf(idy_) < 1.2676506e30f) || !(fabsf(ocy) < 1.3292280e36f)) { idy_ = 0.0f; ocy = NANf; }    \
-        if (!(fabsf(idz_) < 1.2676506e30f) || !(fabsf(ocz) < 1.3292280e36f)) { idz_ = 0.0f; ocz = NANf; }    \
+        /* |id| < 2^(115 - ilogb(M)) <= 2^100, |c| < 2^120: no product with a plane of THIS tree, a grid origin or 255 grid steps leaves the float range. */ \
+        /* id == 0 is a direction beyond the float range ((float)d = +-inf): its planes would all evaluate to c = 0, a miss whatever o is */ \
+        if (!(fabsf(idx_) < lim_) || idx_ == 0.0f || !(fabsf(ocx) < 1.3292280e36f)) { idx_ = 0.0f; ocx = NANf; } \
+        if (!(fabsf(idy_) < lim_) || idy_ == 0.0f || !(fabsf(ocy) < 1.3292280e36f)) { idy_ = 0.0f; ocy = NANf; } \
+        if (!(fabsf(idz_) < lim_) || idz_ == 0.0f || !(fabsf(ocz) < 1.3292280e36f)) { idz_ = 0.0f; ocz = NANf; } \
         /* the ENTRY plane of an axis (the lower one when id > 0) gets the smaller constant, the exit plane the larger one */ \
         const float sx = fabsf(ocx) * 2.3841858e-7f, sy = fabsf(ocy) * 2.3841858e-7f, sz = fabsf(ocz) * 2.3841858e-7f; \
         cnx = ocx - sx; cfx = ocx + sx; cny = ocy - sy; cfy = ocy + sy; cnz = ocz - sz; cfz = ocz + sz;      \
@@ -226,6 +258,47 @@ __device__ __forceinline__ bool sphere_t(const double* s, const Ray& r, double t
     ZR_SLAB(fmaf((N).lox[C], idx_, idx_ > 0.0f ? cnx : cfx), fmaf((N).hix[C], idx_, idx_ > 0.0f ? cfx : cnx),  \
             fmaf((N).loy[C], idy_, idy_ > 0.0f ? cny : cfy), fmaf((N).hiy[C], idy_, idy_ > 0.0f ? cfy : cny),  \
             fmaf((N).loz[C], idz_, idz_ > 0.0f ? cnz : cfz), fmaf((N).hiz[C], idz_, idz_ > 0.0f ? cfz : cnz), (N).ref[C], TN, RF)
+// a grid node's planes (once per visit) from its first three 16-byte words W0 W1 W2 (NodeQ: origin, scale, q): declares nx01 nx23 ... fz01 fz23, the
+// entry (n) and exit (f) distances per axis of children 0 1 and 2 3.
+// t = fmaf(q, a, b): a = scale * id, b = the node origin's parametric distance (the entry planes' b moved by -2^-15 |a|,
+// the exit planes' by +2^-15 |a|).  The sign of id says which of an axis' two planes the ray enters through — for all four
+// children at once: the word of lower planes or the word of upper planes — so no per-child min / max is needed, and the
+// children are evaluated two at a time (v_pk_fma_f32): the planes' values are those of a per-child min / max, bit for bit.
+#define ZR_Q2(W, S) ((f2_){(float)(((W) >> (S)) & 0xFFu), (float)(((W) >> ((S) + 8)) & 0xFFu)})
+#define ZR_T2(W, S, A, Bc) __builtin_elementwise_fma(ZR_Q2(W, S), ((f2_){(A), (A)}), ((f2_){(Bc), (Bc)}))
+#define ZR_QPLANES(W0, W1, W2)                                                                              \
+    typedef float f2_ __attribute__((ext_vector_type(2)));                                                  \
+    const float ax_ = __builtin_bit_cast(float, (W0).w) * idx_, ay_ = __builtin_bit_cast(float, (W1).x) * idy_, az_ = __builtin_bit_cast(float, (W1).y) * idz_; \
+    const float bnx = fmaf(fabsf(ax_), -3.0517578e-5f, fmaf(__builtin_bit_cast(float, (W0).x), idx_, cnx)), bfx = fmaf(fabsf(ax_), 3.0517578e-5f, fmaf(__builtin_bit_cast(float, (W0).x), idx_, cfx)); \
+    const float bny = fmaf(fabsf(ay_), -3.0517578e-5f, fmaf(__builtin_bit_cast(float, (W0).y), idy_, cny)), bfy = fmaf(fabsf(ay_), 3.0517578e-5f, fmaf(__builtin_bit_cast(float, (W0).y), idy_, cfy)); \
+    const float bnz = fmaf(fabsf(az_), -3.0517578e-5f, fmaf(__builtin_bit_cast(float, (W0).z), idz_, cnz)), bfz = fmaf(fabsf(az_), 3.0517578e-5f, fmaf(__builtin_bit_cast(float, (W0).z), idz_, cfz)); \
+    const bool px_ = idx_ > 0.0f, py_ = idy_ > 0.0f, pz_ = idz_ > 0.0f;                                     \
+    const uint32_t qnx = px_ ? (W1).z : (W2).y, qfx = px_ ? (W2).y : (W1).z;                                \
+    const uint32_t qny = py_ ? (W1).w : (W2).z, qfy = py_ ? (W2).z : (W1).w;                                \
+    const uint32_t qnz = pz_ ? (W2).x : (W2).w, qfz = pz_ ? (W2).w : (W2).x;                                \
+    const f2_ nx01 = ZR_T2(qnx, 0, ax_, bnx), nx23 = ZR_T2(qnx, 16, ax_, bnx), fx01 = ZR_T2(qfx, 0, ax_, bfx), fx23 = ZR_T2(qfx, 16, ax_, bfx); \
+    const f2_ ny01 = ZR_T2(qny, 0, ay_, bny), ny23 = ZR_T2(qny, 16, ay_, bny), fy01 = ZR_T2(qfy, 0, ay_, bfy), fy23 = ZR_T2(qfy, 16, ay_, bfy); \
+    const f2_ nz01 = ZR_T2(qnz, 0, az_, bnz), nz23 = ZR_T2(qnz, 16, az_, bnz), fz01 = ZR_T2(qfz, 0, az_, bfz), fz23 = ZR_T2(qfz, 16, az_, bfz);
+// one child of a grid node from its entry and exit distances per axis: ZR_SLAB without the per-child min / max
+#define ZR_QBOX(NX, NY, NZ, FX, FY, FZ, RF_IN, TN, RF)                                                      \
+    {                                                                                                       \
+        float n_ = fmaxf(fmaxf(NX, NY), fmaxf(NZ, 0.000999f));                                              \
+        float f_ = fminf(fminf(FX, FY), fminf(FZ, tbest_f));                                                \
+        n_ = fmaf(fabsf(n_), -9.5367432e-7f, n_);                                                           \
+        f_ = fmaf(fabsf(f_), 9.5367432e-7f, f_);                                                            \
+        const bool empty_ = (RF_IN) == ZR_REF_EMPTY;                                                        \
+        const bool hit_ = (n_ <= f_) && !empty_;                                                            \
+        if (COUNT && !empty_) c_nodes++;                                                                    \
+        TN = hit_ ? n_ : INFf;                                                                              \
+        RF = (RF_IN);                                                                                       \
+    }
+// the four children of a grid node: W0 W1 W2 as above, REFS its fourth word
+#define ZR_QNODE(W0, W1, W2, REFS)                                                                          \
+    ZR_QPLANES(W0, W1, W2)                                                                                  \
+    ZR_QBOX(nx01.x, ny01.x, nz01.x, fx01.x, fy01.x, fz01.x, (REFS).x, tn0, r0)                              \
+    ZR_QBOX(nx01.y, ny01.y, nz01.y, fx01.y, fy01.y, fz01.y, (REFS).y, tn1, r1)                              \
+    ZR_QBOX(nx23.x, ny23.x, nz23.x, fx23.x, fy23.x, fz23.x, (REFS).z, tn2, r2)                              \
+    ZR_QBOX(nx23.y, ny23.y, nz23.y, fx23.y, fy23.y, fz23.y, (REFS).w, tn3, r3)
 
 // ---- a ray that provably leaves the world (SHADE's escape stage, zr_stream.hip) ----------------------------------------------
 // sphere_miss_certain: true only if sphere_t(s, r, 0.001, tmax, .) is false for every tmax.  With sphere_t's quantities a = |d|^2, h = d.oc,
@@ -252,7 +325,7 @@ __host__ __device__ __forceinline__ bool ray_escapes(const Ray& ray, const NodeF
     const float INFf = __builtin_huge_valf(), tbest_f = INFf;
     float idx_, idy_, idz_, cnx, cny, cnz, cfx, cfy, cfz;
     uint32_t c_nodes = 0;
-    ZR_RAY_CONSTANTS()
+    ZR_RAY_CONSTANTS(slab_id_limit(root))
     float tn0, tn1, tn2, tn3;
     uint32_t r0, r1, r2, r3;
     ZR_FBOX(root, 0, tn0, r0)
@@ -302,7 +375,7 @@ __host__ __device__ __forceinline__ bool camera_ray_escapes(const Ray& ray, cons
     const float INFf = __builtin_huge_valf(), tbest_f = INFf;
     float idx_, idy_, idz_, cnx, cny, cnz, cfx, cfy, cfz;
     uint32_t c_nodes = 0;
-    ZR_RAY_CONSTANTS()
+    ZR_RAY_CONSTANTS(slab_id_limit(root))
     float tn0, tn1, tn2, tn3;
     uint32_t r0, r1, r2, r3;
     ZR_FBOX(root, 0, tn0, r0)

@@ -474,9 +474,18 @@ struct Flattener {
         return dx * dy + dy * dz + dz * dx;
     }
     // 8-bit planes of one axis: origin + q * scale, as a real number, must not exceed lo (lower plane) and must
-    // reach hi (upper plane).  origin is a float, scale a power of two not smaller than 2^-30 |origin|, so the sum is
-    // exact in long double and the comparison is the real one.
+    // reach hi (upper plane).  The comparison is the real one, as the device builder's is (zr_quant.h: plane_le, plane_ge): a = origin and m = q * scale
+    // are exact doubles and TwoSum gives a + m = s + e exactly.  (A sum in long double is not exact: an origin just below 0 — f_down(0) is the
+    // smallest subnormal — vanishes beside q * scale, and an upper plane that lay 2^-149 below hi passed for reaching it.)
     static long double plane(float origin, float scale, long q) { return (long double)origin + (long double)q * (long double)scale; }
+    static void plane_sum(float origin, float scale, long q, double& s, double& e) {
+        const double a = (double)origin, m = (double)q * (double)scale;
+        s = a + m;
+        const double bb = s - a;
+        e = (a - (s - bb)) + (m - bb);
+    }
+    static bool plane_le(float origin, float scale, long q, double x) { double s, e; plane_sum(origin, scale, q, s, e); return s < x || (s == x && e <= 0.0); }
+    static bool plane_ge(float origin, float scale, long q, double x) { double s, e; plane_sum(origin, scale, q, s, e); return s > x || (s == x && e >= 0.0); }
     static bool quant_axis(const double* lo, const double* hi, int n, float& origin, float& scale, uint8_t* qlo, uint8_t* qhi) {
         double mn = lo[0], mx = hi[0];
         for (int k = 1; k < n; k++) { mn = std::min(mn, lo[k]); mx = std::max(mx, hi[k]); }
@@ -492,12 +501,12 @@ struct Flattener {
             for (int k = 0; k < n && ok; k++) {
                 long ql = (long)std::floor((lo[k] - (double)origin) / (double)scale);
                 ql = std::min(255l, std::max(0l, ql));
-                while (ql > 0 && plane(origin, scale, ql) > (long double)lo[k]) ql--;
-                if (plane(origin, scale, ql) > (long double)lo[k]) ok = false;
+                while (ql > 0 && !plane_le(origin, scale, ql, lo[k])) ql--;
+                if (!plane_le(origin, scale, ql, lo[k])) ok = false;
                 long qh = (long)std::ceil((hi[k] - (double)origin) / (double)scale);
                 qh = std::min(255l, std::max(0l, qh));
-                while (qh < 255 && plane(origin, scale, qh) < (long double)hi[k]) qh++;
-                if (plane(origin, scale, qh) < (long double)hi[k]) ok = false;
+                while (qh < 255 && !plane_ge(origin, scale, qh, hi[k])) qh++;
+                if (!plane_ge(origin, scale, qh, hi[k])) ok = false;
                 qlo[k] = (uint8_t)ql; qhi[k] = (uint8_t)qh;
             }
             if (ok) return true;

@@ -176,9 +176,21 @@ __global__ __launch_bounds__(256) void stream_init(StreamBuf B, DCamera cam, uin
 // The absolute part of that bound is folded, per axis, into the constants: the plane a ray ENTERS an axis' slab through
 // (the lower one when id > 0) uses c_n = c - 2^-22 |c|, the one it leaves through c_f = c + 2^-22 |c| (and b_n, b_f move by a
 // further 2^-15 |a|); a slack shared by the three axes would let an axis with a tiny d inflate the other two.  The
-// relative part lowers the entry distance and raises the exit distance by |t| 2^-20.  An axis whose 1/d or o/d
-// leaves the float range gets id = 0, c = NaN: its planes evaluate to NaN, which fminf/fmaxf ignore, i.e. the slab
-// is dropped (conservative).
+// relative part lowers the entry distance and raises the exit distance by |t| 2^-20.
+// DOMAIN: every finite o, every d, a tree whose planes lie within M (the device builder accepts M <= 1e18, the host builder
+// 1e30).  The bound above assumes every float intermediate is finite, and that is a property of the WORLD, not of the ray
+// alone: a product P id, origin id or 255 a leaves the range once M |id| reaches 2^128, and then a plane that should be
+// moderate is -inf (b = fmaf(origin, id, c) overflows, fmaf(q, a, -inf) stays there: the child is culled) or the entry
+// distance is +inf and its slack makes it NaN (inf - inf: n <= f is false).  RULE: an axis is kept only while
+//   |id| < 2^(115 - ilogb M), at most 2^100   (slab_id_limit, zr_device.h: from the root's planes; a placed run's own tree
+//                                               from its root's grid),   id != 0   ((float)d = +-inf: every plane would be c = 0),
+//   |c| < 2^120
+// so that |P id| < 2^116, |origin id| < 2^116, 255 |a| < 2^119 (a grid's 255 steps span less than four times its children's
+// extent of at most 2 M), |b| and |t| < 2^121: nothing leaves the float range, and no distance is infinite but tbest_f, for
+// which inf <= inf is a hit.  Any other axis gets id = 0, c = NaN: its planes evaluate to NaN, which fminf / fmaxf ignore,
+// i.e. the slab is dropped (conservative).  A world within 2^16 has the limit 2^100 it always had.
+// Checked against exact rational arithmetic over the whole domain on the host, the very macros expanded there
+// (tests/test_slab_native.py), and through both builders and this kernel (tests/test_slab_edges.py).
 enum { X_IDLE = 0, X_NODE = 1, X_LEAF = 2 };
 #define X_LEAF_BIT ZR_REF_LEAF
 
@@ -207,7 +219,7 @@ __device__ __forceinline__ void cswap(float& ta, uint32_t& ra, float& tb, uint32
 #endif
 template <bool COUNT, int LEVEL>
 __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEVEL == 1 ? ST_EXT_WAVES_MID : ST_EXT_WAVES_LEAN)) void stream_extend(DScene sc, StreamBuf B, SEntry* __restrict__ overflow,
-                                                                  uint32_t ovf_levels, unsigned long long* __restrict__ gctr) {
+                                                                  uint32_t ovf_levels, unsigned long long* __restrict__ gctr, float id_lim /* slab_id_limit(sc.root), zr_device.h */) {
     __shared__ SEntry lstack[ST_EXT_GROUP * ST_LDS_STACK * 64];
     const int lane = threadIdx.x & 63;
     const uint32_t wave_id = blockIdx.x * ST_EXT_GROUP + (threadIdx.x >> 6);
@@ -266,7 +278,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
         if (e_.tn <= tbest_f) { cur = e_.node; pend_i = 0; st = (e_.node & X_LEAF_BIT) ? X_LEAF : X_NODE; break; } \
     }
 
-// (ZR_SLAB, ZR_RAY_CONSTANTS, ZR_FBOX — the slab test itself: zr_device.h, shared with SHADE's escape stage)
+// (ZR_SLAB, ZR_RAY_CONSTANTS, ZR_FBOX, ZR_QNODE — the slab test itself: zr_device.h, shared with SHADE's escape stage and with the host check tests/native/slab_check.cpp)
 // the four children by entry distance (5-comparator network): push far -> near, continue with the nearest
 #define ZR_DESCEND()                                                                                        \
     {                                                                                                       \
@@ -354,7 +366,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                         slot = my;
                         if (LEVEL > 0) { ray.o = ro_; ray.d = rd_; } else { ray.o = B.ld3(SF_RAY, my); ray.d = B.ld3(SF_RAY + 3, my); }
                         if (LEVEL > 0) { g.key = (uint64_t)__double_as_longlong(key_); g.bounce = m.y & 0xFFu; }
-                        ZR_RAY_CONSTANTS()
+                        ZR_RAY_CONSTANTS(id_lim)
                         tbest = INF; tbest_f = INFf; kbest = NONE; cur = 0; sp = 0; pend_i = 0; inst_cur = 0;
                         if (COUNT) c_seg++;
                         // the root's FP32 boxes come with the kernel arguments: no memory access for the first step, and a
@@ -382,43 +394,7 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                 uint32_t r0, r1, r2, r3;
                 const uint4* nq = reinterpret_cast<const uint4*>(sc.quads + cur);
                 const uint4 w0 = nq[0], w1 = nq[1], w2 = nq[2], ref = nq[3];
-                // t = fmaf(q, a, b): a = scale * id, b = the node origin's parametric distance (the entry planes' b moved by -2^-15 |a|,
-                // the exit planes' by +2^-15 |a|).  The sign of id says which of an axis' two planes the ray enters through — for all four
-                // children at once: the word of lower planes or the word of upper planes — so no per-child min / max is needed, and the
-                // children are evaluated two at a time (v_pk_fma_f32): the planes' values are those of a per-child min / max, bit for bit.
-                typedef float f2_ __attribute__((ext_vector_type(2)));
-                const float ax_ = __uint_as_float(w0.w) * idx_, ay_ = __uint_as_float(w1.x) * idy_, az_ = __uint_as_float(w1.y) * idz_;
-                const float bnx = fmaf(fabsf(ax_), -3.0517578e-5f, fmaf(__uint_as_float(w0.x), idx_, cnx)), bfx = fmaf(fabsf(ax_), 3.0517578e-5f, fmaf(__uint_as_float(w0.x), idx_, cfx));
-                const float bny = fmaf(fabsf(ay_), -3.0517578e-5f, fmaf(__uint_as_float(w0.y), idy_, cny)), bfy = fmaf(fabsf(ay_), 3.0517578e-5f, fmaf(__uint_as_float(w0.y), idy_, cfy));
-                const float bnz = fmaf(fabsf(az_), -3.0517578e-5f, fmaf(__uint_as_float(w0.z), idz_, cnz)), bfz = fmaf(fabsf(az_), 3.0517578e-5f, fmaf(__uint_as_float(w0.z), idz_, cfz));
-                const bool px_ = idx_ > 0.0f, py_ = idy_ > 0.0f, pz_ = idz_ > 0.0f;
-                const uint32_t qnx = px_ ? w1.z : w2.y, qfx = px_ ? w2.y : w1.z;
-                const uint32_t qny = py_ ? w1.w : w2.z, qfy = py_ ? w2.z : w1.w;
-                const uint32_t qnz = pz_ ? w2.x : w2.w, qfz = pz_ ? w2.w : w2.x;
-#define ZR_Q2(W, S) ((f2_){(float)(((W) >> (S)) & 0xFFu), (float)(((W) >> ((S) + 8)) & 0xFFu)})
-#define ZR_T2(W, S, A, Bc) __builtin_elementwise_fma(ZR_Q2(W, S), ((f2_){(A), (A)}), ((f2_){(Bc), (Bc)}))
-                const f2_ nx01 = ZR_T2(qnx, 0, ax_, bnx), nx23 = ZR_T2(qnx, 16, ax_, bnx), fx01 = ZR_T2(qfx, 0, ax_, bfx), fx23 = ZR_T2(qfx, 16, ax_, bfx);
-                const f2_ ny01 = ZR_T2(qny, 0, ay_, bny), ny23 = ZR_T2(qny, 16, ay_, bny), fy01 = ZR_T2(qfy, 0, ay_, bfy), fy23 = ZR_T2(qfy, 16, ay_, bfy);
-                const f2_ nz01 = ZR_T2(qnz, 0, az_, bnz), nz23 = ZR_T2(qnz, 16, az_, bnz), fz01 = ZR_T2(qfz, 0, az_, bfz), fz23 = ZR_T2(qfz, 16, az_, bfz);
-#undef ZR_T2
-#undef ZR_Q2
-#define ZR_QBOX(NX, NY, NZ, FX, FY, FZ, RF_IN, TN, RF)                                                      \
-    {                                                                                                       \
-        float n_ = fmaxf(fmaxf(NX, NY), fmaxf(NZ, 0.000999f));                                              \
-        float f_ = fminf(fminf(FX, FY), fminf(FZ, tbest_f));                                                \
-        n_ = fmaf(fabsf(n_), -9.5367432e-7f, n_);                                                           \
-        f_ = fmaf(fabsf(f_), 9.5367432e-7f, f_);                                                            \
-        const bool empty_ = (RF_IN) == ZR_REF_EMPTY;                                                        \
-        const bool hit_ = (n_ <= f_) && !empty_;                                                            \
-        if (COUNT && !empty_) c_nodes++;                                                                    \
-        TN = hit_ ? n_ : INFf;                                                                              \
-        RF = (RF_IN);                                                                                       \
-    }
-                ZR_QBOX(nx01.x, ny01.x, nz01.x, fx01.x, fy01.x, fz01.x, ref.x, tn0, r0)
-                ZR_QBOX(nx01.y, ny01.y, nz01.y, fx01.y, fy01.y, fz01.y, ref.y, tn1, r1)
-                ZR_QBOX(nx23.x, ny23.x, nz23.x, fx23.x, fy23.x, fz23.x, ref.z, tn2, r2)
-                ZR_QBOX(nx23.y, ny23.y, nz23.y, fx23.y, fy23.y, fz23.y, ref.w, tn3, r3)
-#undef ZR_QBOX
+                ZR_QNODE(w0, w1, w2, ref)   // zr_device.h: the planes on the node's grid, then the four children
                 ZR_DESCEND()
             }
         }
@@ -471,13 +447,13 @@ __global__ __launch_bounds__(64 * ST_EXT_GROUP, LEVEL >= 2 ? ST_EXT_WAVES : (LEV
                     const DInstance in = sc.insts[prim];
                     ZR_PUSH(ZR_REF_LEAF | (7u << 28), -INFf)
                     ray = chain_ray(sc, in.chain_first, in.chain_count, ray);
-                    ZR_RAY_CONSTANTS()
+                    ZR_RAY_CONSTANTS(slab_id_limit(sc.quads[in.pad_]))   // the run's own tree, in the run's space: the limit of its root's grid
                     inst_cur = prim + 1u;
                     cur = in.pad_; pend_i = 0; st = X_NODE;
                 } else if (LEVEL == 3 && lkind == 7u) {
                     // LEAVE: the run's tree is exhausted (its entries were above the sentinel); the world ray again, from the slot
                     ray.o = B.ld3(SF_RAY, slot); ray.d = B.ld3(SF_RAY + 3, slot);
-                    ZR_RAY_CONSTANTS()
+                    ZR_RAY_CONSTANTS(id_lim)
                     inst_cur = 0;
                     ZR_POP_NEXT()
                 } else {
@@ -1308,7 +1284,7 @@ static hipError_t clear_ctl(unsigned int* ctl, hipStream_t stream) {
 }
 
 // ---- which build serves a launch: per kernel family one table from the deciding facts to the kernel, and one call site --------------------------------------
-using ExtendKernel = void (*)(DScene, StreamBuf, SEntry*, uint32_t, unsigned long long*);
+using ExtendKernel = void (*)(DScene, StreamBuf, SEntry*, uint32_t, unsigned long long*, float);
 using ShadeKernel = void (*)(DScene, DCamera, DEnv, uint64_t, StreamBuf, unsigned long long*);
 using FusedKernel = void (*)(DScene, DCamera, DEnv, uint64_t, FusedBuf, unsigned long long*, FusedObjs);
 
@@ -1318,7 +1294,7 @@ static void launch_extend(bool count, int level, const DScene& sc, const StreamB
         {stream_extend<false, 0>, stream_extend<false, 1>, stream_extend<false, 2>, stream_extend<false, 3>},
         {stream_extend<true, 0>, stream_extend<true, 1>, stream_extend<true, 2>, stream_extend<true, 3>}};
     const ExtendKernel kernel = build[count ? 1 : 0][level < 0 ? 0 : (level > 3 ? 3 : level)];
-    hipLaunchKernelGGL(kernel, dim3((blocks + ST_EXT_GROUP - 1) / ST_EXT_GROUP), dim3(64 * ST_EXT_GROUP), 0, st, sc, B, (SEntry*)overflow, ovf_levels, gctr);
+    hipLaunchKernelGGL(kernel, dim3((blocks + ST_EXT_GROUP - 1) / ST_EXT_GROUP), dim3(64 * ST_EXT_GROUP), 0, st, sc, B, (SEntry*)overflow, ovf_levels, gctr, slab_id_limit(sc.root));
 }
 
 // SHADE.  in place: the lean build that shades a slot where it lies, one wave per workgroup; lean: same arithmetic as the general build, fewer registers, 6 waves
