@@ -1564,6 +1564,14 @@ public:
     bool robust_resolve = false;
     double robust_strength = ZR_ROBUST_DEFAULT_STRENGTH;
     bool resolve_used_robust = false;   // extension: the last render's render_accumulator came from the robust resolve
+    // extension: direct light sampling (zr_accum_set_direct with emitters and the sun): next-event estimation with multiple importance sampling
+    // on the path the plain integrator walks.  render() then goes through an accumulator as robust_resolve does — the adaptive render, the progressive
+    // render, or one pass of samples_per_pixel samples — and everything that reads the accumulator (variance, the guided and non-local-means filters,
+    // temporal accumulation, the robust resolve) works on the direct frame.  The reflection / refraction split replays the plain integrator's paths: with
+    // use_reflection or use_refraction a warning is printed and the render is what it is without the flag.  render_used_direct says which it was.
+    // Same expectation as the plain render, other noise: opt-in.  false: exactly the render without it.
+    bool direct_lighting = false;
+    bool render_used_direct = false;    // extension: the last render's samples came from the direct-light integrator
     // extension: the temporal history follows a moving world (zr_temporal_track_motion).  Takes effect together with temporal_accumulation and
     // reuse_scene: the camera switches tracking on in the history it keeps, and keeps that history across a frame whose scene was refitted
     // (last_scene_refit == 1) although the `world` argument is a new object — the refit's motion table reprojects the moved objects' pixels.  Every other case
@@ -1662,10 +1670,15 @@ public:
                 half_a_.clear(); half_b_.clear(); denoise_error_buffer.clear(); denoise_used_nlm = false;
                 temporal_buffer.clear(); temporal_history_length.clear();
                 resolve_used_robust = false; robust_variance_.clear();
+                render_used_direct = false;
+                direct_now_ = direct_lighting && !debug && !(use_reflection || use_refraction);
+                if (direct_lighting && !debug && !direct_now_)
+                    std::cerr << "[zenith] direct_lighting ignored: the reflection / refraction split replays the plain integrator's paths\n";
                 if (debug) rc = render_debug_view(job);
                 else if (wants_adaptive()) rc = render_adaptive(job);
                 else if (samples_per_pass > 0) rc = render_progressive(job, samples_per_pass);
                 else if (robust_resolve && samples_per_pixel >= 64 && samples_per_pixel % 64 == 0) rc = render_progressive(job, samples_per_pixel);
+                else if (direct_now_) rc = render_progressive(job, samples_per_pixel < 1 ? 1 : samples_per_pixel);
                 else rc = render_one_shot(job);
                 if (rc == ZR_OK && !debug && robust_resolve && !resolve_used_robust)
                     std::cerr << "[zenith] robust_resolve ignored: no whole lanes (it needs adaptive_threshold, or a multiple of 64 samples)\n";
@@ -1771,6 +1784,14 @@ private:
         resolve_used_robust = rc == ZR_OK;
         return rc;
     }
+    // direct_lighting: the integrator bound to the accumulator a render stage has just made
+    int bind_direct(zr_accum* acc) {
+        if (!direct_now_) return ZR_OK;
+        const zr_direct_params dp{ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN, 0};
+        const int rc = zr_accum_set_direct(acc, &dp);
+        render_used_direct = rc == ZR_OK;
+        return rc;
+    }
     // the non-local-means filter has been asked for and can run: the blend of temporal_accumulation has no half images
     bool wants_nlm() const { return denoise_nlm && !temporal_accumulation; }
 
@@ -1815,6 +1836,7 @@ private:
         current_samples_count = 0; passes_rendered = 0;
         const zenith::accum_handle acc(zr_accum_create(j.ctx, image_width, image_height, nullptr));
         if (!acc) return ZR_E_DEVICE;
+        if (const int brc = bind_direct(acc.get())) return brc;
         // a cancelled run leaves the image of the passes that completed; a refused one (bad counts) leaves nothing
         const int rc = zr_render_adaptive(j.ctx, j.sc, &j.cam, &j.env, seed, acc.get(), &ap, 0, zenith::flag_ptr(j.flag), &last_adaptive);
         if ((rc == ZR_OK || rc == ZR_E_CANCELLED) && last_adaptive.passes > 0) {
@@ -1837,6 +1859,7 @@ private:
         current_samples_count = 0; passes_rendered = 0;
         const zenith::accum_handle acc(zr_accum_create(j.ctx, image_width, image_height, nullptr));
         if (!acc) return ZR_E_DEVICE;
+        if (const int brc = bind_direct(acc.get())) return brc;
         while (current_samples_count < spp) {
             const int n = std::min(per_pass, spp - current_samples_count);
             int rc = zr_render_accumulate(j.ctx, j.sc, &j.cam, &j.env, seed, acc.get(), n, 0, zenith::flag_ptr(j.flag));
@@ -1936,6 +1959,7 @@ private:
 
     // the accumulator's half images between the render and the denoiser of one render() call (denoise_nlm)
     std::vector<color> half_a_, half_b_;
+    bool direct_now_ = false;   // this render() call binds the direct-light integrator to its accumulator (direct_lighting, and no split)
     // the variance of the robust mean between the resolve and its readers of one render() call (robust_resolve)
     std::vector<color> robust_variance_;
     // the history of temporal_accumulation and what it was made for

@@ -884,6 +884,86 @@ int zr_kat_background(zr_ctx*, const zr_scene*, const zr_env*, const double* dir
 /* camera::get_ray(i, j) after camera::initialize() for n requests (i, j, sample); out = n x (origin, direction, draws used) */
 int zr_kat_camera_rays(zr_ctx*, const zr_camera*, uint64_t seed, const int32_t* requests3, size_t n, double* out7);
 
+/* ---- direct light sampling: next-event estimation with multiple importance sampling, opt-in ------------------------
+ * An integrator bound to an accumulator.  It walks exactly the vertices of zr_render's path — same camera draws, same scatter() draws, same Russian
+ * roulette, no extra draw from the main stream — so a sample's segments, hits and main-stream draws are the plain integrator's; only the radiance
+ * bookkeeping differs:   L = sum_k beta_k (w_k Le(x_k) + D_k).
+ *   Sampled lights   world-level leaf primitives whose stored material is ZR_MAT_LIGHT and whose stored form is world-space or affine: spheres and triangles
+ *                    (bare or baked), bare cubes (six rectangles about the origin, as cube::hit tests them) and placed cubes (scale -> rotate_y -> translate:
+ *                    six parallelograms).  Emitters under generic wrapper chains, inside groups and media are not sampled: they keep w = 1 when hit.
+ *                    One slot per sphere / triangle / face, weight = area x lum (lum = 0.2126 r + 0.7152 g + 0.0722 b of a solid emission texture, 1.0 for
+ *                    any other); slots whose weight is zero, negative or not finite are skipped.  Order: spheres, triangles, cubes, placed cubes by stored
+ *                    index, a cube's faces -x +x -y +y -z +z.  cdf = the FP64 running sum of the weights in that order.  One draw u selects the first slot
+ *                    with cdf > u * total, so every point of an object has the area density rho = lum / total.
+ *   The sun          with ZR_ENV_PHYSICAL_SUN, the disc on and sun_size > 0: the cone cos(theta) in [sun_thr, 1] uniformly by solid angle,
+ *                    pdf = 1 / (2 pi (1 - sun_thr)), in a fixed frame about the sun direction s: a = (0,1,0) if |s.x| > 0.9 else (1,0,0), t = unit(a x s),
+ *                    b = s x t, direction = sin cos(phi) t + sin sin(phi) b + cos s with cos = 1 - u1 (1 - sun_thr), phi = 2 pi u2.  Its radiance is the
+ *                    sun term of the background alone; the sky always comes from scattering with weight 1.
+ *   Draws            zr_light_key (zr_rng.h), in this order: sun-or-emitter (only when both are sampled: u < 0.5 takes an emitter; each then has P = 1/2),
+ *                    the slot, then the point: sphere c + r random_unit_vector (rejection, three draws a round), triangle u1, u2 folded to 1 - u1, 1 - u2
+ *                    when u1 + u2 > 1, parallelogram o + u1 e1 + u2 e2.
+ *   D_k              at Lambertian and isotropic vertices that have a next segment within max_depth: a shadow query from the scattered ray's origin —
+ *                    the path's own closest hit over (0.001, dist + tol), tol = ZR_DIRECT_T_TOL max(1, dist), its medium draws keyed with
+ *                    bounce | 0x80000000 — sees the sample iff it answers with the chosen object at |t - dist| <= tol (the sun: iff it misses).  Emission
+ *                    comes from that hit's record.  pdf_w = P rho dist^2 / cos_l (cos_l = |n . w| with the slot's geometric normal; <= 1e-12: nothing);
+ *                    Lambertian f cos = albedo max(0, wn . w) / pi and p_b = max(0, wn . w) / pi with scatter()'s shading normal wn, isotropic
+ *                    f = albedo / 4 pi and p_b = 1 / 4 pi;  D = beta f cos Le / (pdf_w + p_b)   (balance heuristic).
+ *   w_k              p_b / (p_b + pdf_w) where the vertex before took a D and x_k is a sampled light (the sun term of a miss likewise); 1 everywhere else.
+ * zr_accum_set_direct  binds the integrator to an accumulator (params NULL: unbinds).  ZR_E_STATE unless the accumulator holds nothing (done == 0);
+ *                      zr_accum_reset keeps the binding.  zr_render_accumulate and zr_render_adaptive then render through the direct kernel (one thread
+ *                      per sample, the pixel-group route's pairing: zr_counters::path 0), and everything that reads an accumulator works unchanged.
+ *                      The light table is built from the device's final primitive arrays at the first direct render of a (commit, refit epoch), and kept.
+ * zr_accum_get_direct  *out = the binding: its flags, pad_ = 1 while an integrator is bound (0: none)
+ * zr_render_direct     zr_accum_create -> zr_accum_set_direct -> zr_render_accumulate(camera.samples_per_pixel) -> zr_accum_resolve, bit for bit
+ * zr_get_direct_stats  of the last direct batch on the context: shadow queries made / that saw their sample, sun queries among them (a counting
+ *                      batch only, else 0), and the table's slots and objects.  zr_get_counters reports the path's own segments, hits and draws only.
+ * Refusals come before any device call and zr_last_error names the argument: NULL, flags outside ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN, more than
+ * ZR_DIRECT_MAX_SLOTS slots (ZR_E_INVALID). */
+#define ZR_DIRECT_EMITTERS 1u
+#define ZR_DIRECT_SUN 2u
+#define ZR_DIRECT_MAX_SLOTS (1u << 22)
+#define ZR_DIRECT_T_TOL 1e-7
+typedef struct zr_direct_params {
+    uint32_t flags;   /* ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN */
+    uint32_t pad_;
+} zr_direct_params;
+typedef struct zr_direct_stats {
+    uint64_t shadow_queries, shadow_visible, sun_queries, slots, sampled_objects;
+} zr_direct_stats;
+int zr_accum_set_direct(zr_accum*, const zr_direct_params* /* or NULL */);
+int zr_accum_get_direct(const zr_accum*, zr_direct_params* out);
+int zr_render_direct(zr_ctx*, const zr_scene*, const zr_camera*, const zr_env*, uint64_t seed, const zr_region* region, const zr_direct_params*,
+                     int collect_counters, double* out_rgb);
+int zr_get_direct_stats(zr_ctx*, zr_direct_stats* out);
+/* known-answer entries.  zr_scene_lights: the light table of the committed scene; copies min(cap, n) slots, returns n (out NULL with cap 0 asks for n) or a
+ * negative ZR_E_*.  zr_kat_light_sample: one light sample per query from origins3[k] with the light stream zr_light_key(keys[k], bounces[k]); draws8
+ * (may be NULL) holds 8 numbers per query that replace the stream's draws 0..7 where they lie in [0, 1).  zr_kat_light_pdf: closest hit of the ray
+ * (origins3[k], dirs3[k]) over (0.001, inf) as the path finds it, then the light density the MIS weight would use there (0: nothing sampled answers) and
+ * the hit's key, kind << 32 | index as closest hit names it (all ones on a miss).  `params` selects what is sampled, `env` describes the sun. */
+enum { ZR_LIGHT_SPHERE = 0, ZR_LIGHT_TRIANGLE = 1, ZR_LIGHT_PARALLELOGRAM = 2 };
+typedef struct zr_light_slot {
+    uint32_t type;            /* ZR_LIGHT_* */
+    uint32_t kind, index;     /* the object as closest hit names it: ZR_PRIM_SPHERE / TRIANGLE / CUBE or 5 (placed cube), index in that kind's stored array */
+    uint32_t face;            /* cube face 0..5 = -x +x -y +y -z +z, else 0 */
+    double o[3], e1[3], e2[3]; /* triangle: v0, v1 - v0, v2 - v0; parallelogram: corner and edges; sphere: o = centre, e1[0] = radius */
+    double area, lum, weight, cdf;
+} zr_light_slot;
+typedef struct zr_light_sample {
+    uint32_t choice;          /* 0 nothing to sample, 1 an emitter, 2 the sun */
+    uint32_t slot;            /* emitter: the slot chosen */
+    uint32_t kind, index;     /* ... and its object */
+    uint32_t draws, pad_;     /* light-stream draws used */
+    double y[3], normal[3], w[3]; /* the point, the slot's geometric normal there, the unit direction from the origin (the sun: y and normal zero) */
+    double dist;              /* +inf for the sun */
+    double pdf;               /* pdf_w as if unoccluded; 0 where the sample contributes nothing */
+} zr_light_sample;
+int64_t zr_scene_lights(zr_ctx*, const zr_scene*, zr_light_slot* out, size_t cap);
+int zr_kat_light_sample(zr_ctx*, const zr_scene*, const zr_env*, const zr_direct_params*, const double* origins3, const uint64_t* keys, const uint32_t* bounces,
+                        const double* draws8, size_t n, zr_light_sample* out);
+int zr_kat_light_pdf(zr_ctx*, const zr_scene*, const zr_env*, const zr_direct_params*, const double* origins3, const double* dirs3, size_t n, double* out_pdf,
+                     uint64_t* out_key);
+uint64_t zr_kat_light_key(uint64_t key, uint32_t bounce);   /* zr_light_key of zr_rng.h, for bindings */
+
 #ifdef __cplusplus
 }
 #endif

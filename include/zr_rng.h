@@ -13,6 +13,8 @@
  *                 (main-stream key, bounce index, medium id): every test of one medium within one
  *                 closest-hit query sees the same xi, which makes the result independent of traversal
  *                 order, culling and the reference's duplicated-leaf double test.
+ *   light draw    direct light sampling draws off-stream too, one stream per path vertex (zr_light_key below), so that a path's main-stream draws are
+ *                 the same with and without it.
  *   scene stream  pixel = 0xFFFFFFFF, sample = stream id: used by scene generators.
  *
  * Mapping to a double follows libstdc++'s std::uniform_real_distribution<double> over a 64-bit URBG
@@ -55,6 +57,14 @@ ZR_HD uint64_t zr_stream_bits(uint64_t key, uint64_t k) {
 /* the off-stream draw of medium `medium_id` during closest-hit query number `bounce` (0 = primary) */
 ZR_HD uint64_t zr_medium_bits(uint64_t key, uint32_t bounce, uint32_t medium_id) {
     return zr_mix64(zr_mix64(key ^ ZR_MEDIUM_TAG) + ZR_GOLDEN * ((uint64_t)bounce * 65536ull + (uint64_t)medium_id + 1ull));
+}
+
+/* Light draws (direct light sampling) are off-stream like the medium draw, so that a path takes the same main-stream draws with and without
+ * them: the light stream of the vertex reached by closest-hit query number `bounce` (1 = the camera ray's hit) of the sample whose main stream is `key`;
+ * its draw j = 0,1,... is zr_stream_bits(zr_light_key(key, bounce), j). */
+#define ZR_LIGHT_TAG 0x4C494748545F5F5Full /* "LIGHT___" */
+ZR_HD uint64_t zr_light_key(uint64_t key, uint32_t bounce) {
+    return zr_mix64(zr_mix64(key ^ ZR_LIGHT_TAG) + ZR_GOLDEN * ((uint64_t)bounce + 1ull));
 }
 
 /* libstdc++ generate_canonical<double,53> over one 64-bit word */

@@ -151,6 +151,35 @@ class RobustParams(_Defaults, C.Structure):
     _defaults_ = (ROBUST_GINI, 0, ROBUST_DEFAULT_STRENGTH)
 
 
+DIRECT_EMITTERS, DIRECT_SUN = 1, 2
+DIRECT_MAX_SLOTS = 1 << 22
+DIRECT_T_TOL = 1e-7
+LIGHT_SPHERE, LIGHT_TRIANGLE, LIGHT_PARALLELOGRAM = 0, 1, 2
+
+
+class DirectParams(_Defaults, C.Structure):
+    """zr_direct_params: what the direct-light integrator samples (include/zr_capi.h): DIRECT_EMITTERS | DIRECT_SUN"""
+    _fields_ = [("flags", C.c_uint32), ("pad_", C.c_uint32)]
+
+    # defaults(): emitters and the sun
+    _defaults_ = (DIRECT_EMITTERS | DIRECT_SUN, 0)
+
+
+class DirectStats(C.Structure):
+    """zr_direct_stats: the shadow queries of the last counted direct batch and the light table it used"""
+    _fields_ = [("shadow_queries", C.c_uint64), ("shadow_visible", C.c_uint64), ("sun_queries", C.c_uint64), ("slots", C.c_uint64),
+                ("sampled_objects", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+LIGHT_SLOT_DTYPE = np.dtype([("type", "<u4"), ("kind", "<u4"), ("index", "<u4"), ("face", "<u4"), ("o", "<f8", 3), ("e1", "<f8", 3), ("e2", "<f8", 3),
+                             ("area", "<f8"), ("lum", "<f8"), ("weight", "<f8"), ("cdf", "<f8")])
+LIGHT_SAMPLE_DTYPE = np.dtype([("choice", "<u4"), ("slot", "<u4"), ("kind", "<u4"), ("index", "<u4"), ("draws", "<u4"), ("pad_", "<u4"), ("y", "<f8", 3),
+                               ("normal", "<f8", 3), ("w", "<f8", 3), ("dist", "<f8"), ("pdf", "<f8")])
+
+
 class BvhDebugParams(_Defaults, C.Structure):
     """zr_bvh_debug_params: global_settings::debug_bvh_level / bvh_thickness of the BVH debug view (include/zr_capi.h, DESIGN §10)"""
     _fields_ = [("level", C.c_int32), ("thickness", C.c_float)]
@@ -272,6 +301,7 @@ CAPI_SYMBOLS = [
     "zr_temporal_view", "zr_temporal_track_motion", "zr_render_gbuffer_entries", "zr_scene_motion",
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop", "zr_last_shade_builds", "zr_last_extend_fetches",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_shade_lean", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
+    "zr_accum_set_direct", "zr_accum_get_direct", "zr_render_direct", "zr_get_direct_stats", "zr_scene_lights", "zr_kat_light_sample", "zr_kat_light_pdf", "zr_kat_light_key",
 ]
 
 
@@ -376,6 +406,15 @@ def load():
     lib.zr_kat_texture.argtypes = [vp, vp, C.c_uint32, vp, C.c_size_t, vp]
     lib.zr_kat_background.argtypes = [vp, vp, C.POINTER(Env), vp, C.c_size_t, vp]
     lib.zr_kat_camera_rays.argtypes = [vp, C.POINTER(Camera), u64, vp, C.c_size_t, vp]
+    if hasattr(lib, "zr_render_direct"):
+        lib.zr_accum_set_direct.argtypes = [vp, C.POINTER(DirectParams)]
+        lib.zr_accum_get_direct.argtypes = [vp, C.POINTER(DirectParams)]
+        lib.zr_render_direct.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), C.POINTER(DirectParams), i32, vp]
+        lib.zr_get_direct_stats.argtypes = [vp, C.POINTER(DirectStats)]
+        lib.zr_scene_lights.restype = C.c_int64; lib.zr_scene_lights.argtypes = [vp, vp, vp, C.c_size_t]
+        lib.zr_kat_light_sample.argtypes = [vp, vp, C.POINTER(Env), C.POINTER(DirectParams), vp, vp, vp, vp, C.c_size_t, vp]
+        lib.zr_kat_light_pdf.argtypes = [vp, vp, C.POINTER(Env), C.POINTER(DirectParams), vp, vp, C.c_size_t, vp, vp]
+        lib.zr_kat_light_key.restype = u64; lib.zr_kat_light_key.argtypes = [u64, C.c_uint32]
     lib.zr_comm_unique_id.argtypes = [vp]
     lib.zr_comm_create.restype = vp; lib.zr_comm_create.argtypes = [vp, i32, i32, vp]
     lib.zr_comm_reduce_frame.argtypes = [vp, vp, C.c_size_t, i32, vp]
@@ -407,6 +446,8 @@ def load_scenes():
     s.zrs_render_dropin_progressive.argtypes = frame + [i32, vp, vp, i32]
     s.zrs_render_dropin_adaptive.argtypes = frame + [C.c_double, i32, i32, vp, vp, vp, i32]
     s.zrs_render_dropin_robust.argtypes = frame + [C.c_double, C.c_double, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    if hasattr(s, "zrs_render_dropin_direct"):
+        s.zrs_render_dropin_direct.argtypes = frame + [i32, i32, i32, vp, vp]
     s.zrs_render_dropin_threads.argtypes = frame + [i32, vp]
     s.zrs_render_dropin_denoise.argtypes = frame + [i32] + [vp] * 6
     s.zrs_render_dropin_denoise_guided.argtypes = frame + [C.c_double, i32, i32] + [vp] * 4
@@ -447,6 +488,20 @@ def _like(shape, what, frames=(), outs=(), dtype=np.float64):
 
 def _ptr(a):
     return a.ctypes.data if a is not None else None
+
+
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def light_key(key, bounce):
+    """zr_light_key of include/zr_rng.h: the key of the light stream of the vertex that closest-hit query number `bounce` of the main stream `key` reached"""
+    return _mix64((_mix64((int(key) ^ 0x4C494748545F5F5F) & _M64) + 0x9E3779B97F4A7C15 * (int(bounce) + 1)) & _M64)
 
 
 class DemoScene:
@@ -527,6 +582,14 @@ class DemoScene:
                                                               info) == 0)
         outs.update(sample_counts=counts, robust=bool(info[0]), current_samples_count=int(info[1]), passes=int(info[2]))
         return outs
+
+    def render_dropin_direct(self, on=True, split=False, samples_per_pass=0, width=0, height=0, spp=0, device=0):
+        """camera::render with camera::direct_lighting (DESIGN §20; split: use_reflection too, with which the flag is ignored) -> (frame, render_used_direct, passes)"""
+        out = self._frames(width, height, "out")["out"]
+        info = (C.c_int * 2)(0, 0)
+        self._rendered(load_scenes().zrs_render_dropin_direct(self._h, width, height, spp, device, 1 if on else 0, 1 if split else 0, samples_per_pass, out.ctypes.data,
+                                                              info) == 0)
+        return out, bool(info[0]), int(info[1])
 
     def render_dropin_threads(self, n, width=0, height=0, spp=0, device=0):
         """n drop-in renders, each on a fresh host thread, one after the other (the reference's render-restart pattern,
@@ -743,6 +806,49 @@ class Context:
         _check(self.lib.zr_get_counters(self._c, C.byref(c)))
         return c
 
+    # ---- direct light sampling ----
+    def render_direct(self, scene, camera, env, seed, params=None, region=None, count=False, out=None):
+        """zr_render_direct: the frame with next-event estimation and MIS — Accumulator + set_direct + accumulate(camera.samples_per_pixel) + resolve, bit for
+        bit: (H, W, 3) float64; only the region's pixels of `out` are written"""
+        params = params if params is not None else DirectParams.defaults()
+        out, = _like((camera.image_height, camera.image_width, 3), "the camera's frame", outs=(out,))
+        _check(self.lib.zr_render_direct(self._c, scene._s, C.byref(camera), C.byref(env), C.c_uint64(seed), C.byref(region) if region is not None else None,
+                                         C.byref(params), 1 if count else 0, out.ctypes.data))
+        return out
+
+    def direct_stats(self):
+        """zr_get_direct_stats -> dict: shadow queries of the last counted direct batch, slots and objects of the table it used"""
+        st = DirectStats()
+        _check(self.lib.zr_get_direct_stats(self._c, C.byref(st)))
+        return st.as_dict()
+
+    def kat_light_sample(self, scene, env, origins, keys, bounces, params=None, draws=None):
+        """zr_kat_light_sample: one light sample per query from origins (n, 3) with the light stream of (keys[k], bounces[k]) -> array of LIGHT_SAMPLE_DTYPE.
+        draws: (n, 8) numbers that replace the stream's first eight draws where they lie in [0, 1)"""
+        params = params if params is not None else DirectParams.defaults()
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        b = np.ascontiguousarray(bounces, dtype=np.uint32).reshape(-1)
+        d = np.ascontiguousarray(draws, dtype=np.float64).reshape(-1, 8) if draws is not None else None
+        if len(k) != len(o) or len(b) != len(o) or (d is not None and len(d) != len(o)):
+            raise ValueError("origins, keys, bounces and draws must have one row per query")
+        out = np.zeros(len(o), dtype=LIGHT_SAMPLE_DTYPE)
+        _check(self.lib.zr_kat_light_sample(self._c, scene._s, C.byref(env), C.byref(params), o.ctypes.data, k.ctypes.data, b.ctypes.data, _ptr(d), len(o),
+                                            out.ctypes.data))
+        return out
+
+    def kat_light_pdf(self, scene, env, origins, dirs, params=None):
+        """zr_kat_light_pdf: per ray the light density the MIS weight would use after the path's closest hit, and the hit's key (kind << 32 | index, all ones
+        on a miss) -> ((n,) float64, (n,) uint64)"""
+        params = params if params is not None else DirectParams.defaults()
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        if len(d) != len(o):
+            raise ValueError("origins and dirs must have one row per ray")
+        pdf, key = np.zeros(len(o)), np.zeros(len(o), dtype=np.uint64)
+        _check(self.lib.zr_kat_light_pdf(self._c, scene._s, C.byref(env), C.byref(params), o.ctypes.data, d.ctypes.data, len(o), pdf.ctypes.data, key.ctypes.data))
+        return pdf, key
+
     def presolved_pixels(self):
         """pixels the last render finished in the sky pre-pass (zr_last_presolved_pixels); 0 for every other path"""
         return int(self.lib.zr_last_presolved_pixels(self._c))
@@ -803,6 +909,19 @@ class Accumulator:
 
     def reset(self, first_sample=0):
         _check(self.lib.zr_accum_reset(self._a, int(first_sample)))
+
+    def set_direct(self, params=None, on=True):
+        """zr_accum_set_direct: binds the direct-light integrator to this (empty) accumulator (params None: DirectParams.defaults()); on=False
+        unbinds.  accumulate and render_adaptive then render with next-event estimation and MIS; every query of the accumulator works as before"""
+        if on and params is None:
+            params = DirectParams.defaults()
+        _check(self.lib.zr_accum_set_direct(self._a, C.byref(params) if on else None))
+
+    def get_direct(self):
+        """zr_accum_get_direct -> the bound integrator's flags, or None"""
+        p = DirectParams()
+        _check(self.lib.zr_accum_get_direct(self._a, C.byref(p)))
+        return int(p.flags) if p.pad_ else None
 
     def render_adaptive(self, scene, camera, env, seed, params, count=False, keep_going=None):
         """zr_render_adaptive: every pixel to params.min_samples, then params.step_samples more per pass for the pixels whose noise estimate is
@@ -1023,6 +1142,17 @@ class Scene:
         _check(self.lib.zr_scene_stats(self._s, C.byref(out)))
         return {"bvh_pairs": out[0], "bvh_depth": out[1], "objects": out[2], "device_bytes": out[3],
                 "traversal_stack": int(self.lib.zr_scene_traversal_stack(self._s)), "builder": self.lib.zr_scene_builder(self._s).decode()}
+
+    def lights(self):
+        """zr_scene_lights: the light table direct light sampling draws from -> array of LIGHT_SLOT_DTYPE, in table order"""
+        n = self.lib.zr_scene_lights(self.ctx._c, self._s, None, 0)
+        if n < 0:
+            _check(n)
+        out = np.zeros(n, dtype=LIGHT_SLOT_DTYPE)
+        m = self.lib.zr_scene_lights(self.ctx._c, self._s, out.ctypes.data if n else None, n)
+        if m < 0:
+            _check(m)
+        return out
 
     def kernels(self):
         """the kernel builds the committed scene renders through (zr_scene_kernels)"""

@@ -13,6 +13,7 @@ struct AccumState {
     DevBuf<double> d_partial; DevBuf<uint32_t> d_pixels; uint32_t n_pix = 0;
     int first = 0, done = 0;
     int route = 2;                 // zr_counters::path of the batches so far: which one-shot kernel's pairing the resolve follows
+    uint32_t direct = 0;           // bound to the direct-light integrator (zr_accum_set_direct): 0x80000000 | its flags; create to destroy, resets included
     bool bound = false;            // a batch has been added since create / reset: later ones must bring the same camera, seed and scene
     zr_camera cam{}; uint64_t seed = 0; const zr_scene* scene = nullptr; uint64_t scene_epoch = 0;   // (the scene as refitted so often: zr_scene_refit)
     // adaptive sampling (zr_render_adaptive), allocated by its first run: the sample count per pixel, the active list and its slot index
@@ -56,6 +57,7 @@ int render_batch_samples(zr_ctx* c, const zr_scene* s, FrameJob& job, const uint
     *flipped = false;
     if (job.keep_going && *job.keep_going == 0) return fail(ZR_E_CANCELLED, "batch cancelled before it began");
     const uint64_t units = (uint64_t)n_pix * (uint64_t)n;
+    if (job.direct) return render_direct_samples(c, s, job, pixels, n_pix, sample0, n, timer);   // the one place a direct accumulator's batches leave the plain routes
     if (fits_stream(c, s, job.plan, job.dc, 1, 0)) {
         if (units > zr::ST_MAX_UNITS) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu work units, the pipeline numbers 2^32 - 1 per run: ask for fewer samples", n, (unsigned long long)units);
         *flipped = !job.d_list && list_runs_reversed();
@@ -304,7 +306,7 @@ int zr_render_accumulate(zr_ctx* c, const zr_scene* s, const zr_camera* cam, con
                          int collect_counters, volatile const uint8_t* keep_going) {
     if (!c || !s || !cam || !env || !a) return fail(ZR_E_INVALID, "null argument");
     AccumState& st = a->st;
-    FrameJob job; job.count = collect_counters != 0; job.keep_going = keep_going;
+    FrameJob job; job.count = collect_counters != 0; job.keep_going = keep_going; job.direct = st.direct;
     int rc = accum_call_ready(c, s, cam, seed, st, "zr_render_accumulate", n_samples, (long long)st.first + st.done + n_samples);
     if (rc || (rc = prepare_frame(c, s, cam, env, seed, nullptr, job, &st.plan)) || (rc = accumulate_batch(c, s, job, st, st.first + st.done, n_samples))) return rc;
     st.done += n_samples;
@@ -399,6 +401,23 @@ int zr_kat_resolve_robust(zr_ctx* c, const zr_robust_params* rp, const double* l
     return ZR_OK;
 }
 
+// ---- direct light sampling (the integrator itself: zr_direct.cpp, zr_direct.hip) -----------------------------------------------------------------
+
+int zr_accum_set_direct(zr_accum* a, const zr_direct_params* dp) {
+    if (dp) { if (int rc = check_direct_params(dp)) return rc; }   // the parameters first: they need no device and no other argument
+    if (!a) return fail(ZR_E_INVALID, "null argument: accumulator");
+    if (a->st.done != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel: zr_accum_set_direct binds an integrator to an empty one (zr_accum_reset)", a->st.done);
+    a->st.direct = dp ? (0x80000000u | dp->flags) : 0u;
+    return ZR_OK;
+}
+
+int zr_accum_get_direct(const zr_accum* a, zr_direct_params* out) {
+    if (!a) return fail(ZR_E_INVALID, "null argument: accumulator");
+    if (!out) return fail(ZR_E_INVALID, "null argument: out");
+    out->flags = a->st.direct & (ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN); out->pad_ = a->st.direct ? 1u : 0u;   // pad_: 1 while an integrator is bound (flags may be 0)
+    return ZR_OK;
+}
+
 int zr_accum_state(const zr_accum* a, int64_t out[4]) {
     if (!a || !out) return fail(ZR_E_INVALID, "null argument");
     out[0] = a->st.first; out[1] = a->st.done; out[2] = (int64_t)a->st.n_pix; out[3] = (int64_t)a->st.device_bytes();
@@ -424,7 +443,7 @@ int zr_render_adaptive(zr_ctx* c, const zr_scene* s, const zr_camera* cam, const
     int rc = accum_call_ready(c, s, cam, seed, st, "zr_render_adaptive", p->min_samples, (long long)st.first + p->max_samples);
     if (rc || (rc = whole_lanes(st, "the noise estimate"))) return rc;
     if (st.done > p->min_samples) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel, more than min_samples = %d", st.done, p->min_samples);
-    FrameJob job; job.count = collect_counters != 0; job.keep_going = keep_going;
+    FrameJob job; job.count = collect_counters != 0; job.keep_going = keep_going; job.direct = st.direct;
     if ((rc = prepare_frame(c, s, cam, env, seed, nullptr, job, &st.plan))) return rc;
     c->last_rounds = 0;
     HIP_OK(hipMemsetAsync(c->d_ctr.p, 0, zr::CTR_BLOCK * sizeof(unsigned long long), job.stream));

@@ -35,6 +35,7 @@ struct FrameJob {
     double* d_out = nullptr; double* d_out2 = nullptr;   // device frames (d_out2: the refraction frame of the split's replay pass)
     volatile const uint8_t* keep_going = nullptr; volatile int* rows_done = nullptr;
     zr::StreamProgress* progress = nullptr;
+    uint32_t direct = 0;                              // an accumulator bound to the direct-light integrator (zr_accum_set_direct): 0x80000000 | its flags
     const uint32_t* d_list = nullptr; uint32_t n_list = 0;   // a device pixel list of the caller's (an adaptive pass: the active pixels) instead of the plan's cached one
     bool interactive() const { return keep_going || rows_done; }   // the caller polls: the tile-list paths need batch boundaries
 };
@@ -90,6 +91,12 @@ int check_nlm_params(const zr_denoise_nlm_params* dp);
 void camera_frame(const zr_camera& cam, zr::DCamera& dc);
 int trace_device(zr_ctx* c, const zr_scene* s, const double* d_rays, size_t n, double tmin, double tmax, uint64_t seed, uint64_t pixel, uint32_t bounce,
                  zr_hit* d_hits, uint2* d_ki = nullptr /* per ray the (kind, index) both engines hold where they fill zr_hit; all ones on a miss */);
+// zr_render.cpp, for zr_direct.cpp: the ray-independent environment of make_env, checked against the scene's textures
+int env_frame(const zr_env& env, const zr_scene* s, zr::DEnv& de);
+// zr_direct.cpp, for zr_accum.cpp (render_batch_samples calls it): a batch of a direct-light accumulator — render_batch_samples' pixel-group branch
+// with the direct kernel; builds the scene's light table on first use
+int check_direct_params(const zr_direct_params* dp);
+int render_direct_samples(zr_ctx* c, const zr_scene* s, FrameJob& job, const uint32_t* pixels, uint32_t n_pix, int sample0, int n, HostTimer& timer);
 // zr_temporal.cpp, for zr_accum.cpp (zr_accum_temporal calls them): the parameter check, what a call checks before any device work (its null tests aside),
 // and one frame taken from device memory (d_color / d_variance: W*H*3 doubles, complete on the context's stream)
 int check_temporal_params(const zr_temporal_params* p);

@@ -7,6 +7,7 @@
 //   zr_render.cpp  camera frame / sky constants, the frame job every render entry prepares (tile plan, validation) and its drivers (streaming pipeline, fused
 //                  kernel, pixel-group kernel), AOV / split passes, BVH debug view, counters, known-answer entry points
 //   zr_accum.cpp   the accumulator (zr_accum): a frame in batches of samples, adaptive sampling, the queries of what it holds, render_batched
+//   zr_direct.cpp  direct light sampling: the scene's light table, the batch driver of a direct accumulator, zr_render_direct, its known-answer entries
 //   zr_image.cpp   the image-space entry points, which need no scene: post stack, the two denoisers, sharpening, frame analysis
 //                  (these three share zr_frame.h: Plan, FrameJob, HostTimer and the drivers one of them calls in another)
 // Plain C++ (host compiler, -ffp-contract=off so that the camera frame and the sky constants are computed with exactly the reference's operation order,
@@ -124,6 +125,8 @@ struct zr_ctx {
     double last_render_ms = 0;        // sum over the launches of the most recent render call
     hipStream_t last_stream = nullptr;
     bool last_counted = false;
+    uint64_t direct_slots = 0, direct_objects = 0;   // the light table of the last direct-light batch (zr_get_direct_stats)
+    uint64_t direct_render = 0;                      // ... and the render it was (render_id): the counter block holds its shadow-query counts while no other render followed
     // memory a commit frees off the caller's clock (staging arrays, the device builder's arena): at most one such thread is outstanding, and zr_destroy joins it —
     // a detached thread could still be inside hipFree while the process tears the HIP runtime down
     std::mutex trash_m;
@@ -137,6 +140,7 @@ struct zr_ctx {
 };
 
 struct RefitState;   // zr_update.cpp
+namespace zr_host { struct LightCache; }   // zr_direct.cpp
 
 struct zr_scene : SceneInput {   // the world as given (host side), then what the commit made of it
     zr_ctx* ctx = nullptr;
@@ -178,6 +182,7 @@ struct zr_scene : SceneInput {   // the world as given (host side), then what th
     bool stale = false;                  // an update changed the host copy of the world and no refit has followed: nothing may read the device scene
     uint64_t epoch = 0;                  // refits applied to this commit
     uint64_t serial = 0;                 // of this commit among all commits of the process (an epoch alone restarts at 0): what a tracking zr_temporal remembers
+    mutable std::shared_ptr<zr_host::LightCache> lights;   // the light table of (serial, epoch), built by the first direct-light render that needs it
     std::shared_ptr<RefitState> refit;   // reverse indices, leaf boxes, the trees' schedule, device buffers: made by the first update or refit after a commit, dropped by the next
 };
 

@@ -504,6 +504,7 @@ int render_stream(zr_ctx* c, const zr_scene* s, const FrameJob& job, int mode) {
 }
 
 void camera_frame(const zr_camera& cam, zr::DCamera& dc) { make_camera(cam, dc); }
+int env_frame(const zr_env& env, const zr_scene* s, zr::DEnv& de) { make_env(env, de); return check_env(de, s); }
 
 // world.hit(r, interval(tmin, tmax), rec) for n rays that are on the device already: what zr_trace does once its rays are uploaded, and where the geometry
 // buffer's centre rays enter (zr_temporal.cpp).  The context's stream is idle on return.
