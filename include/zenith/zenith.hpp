@@ -1572,6 +1572,11 @@ public:
     // Same expectation as the plain render, other noise: opt-in.  false: exactly the render without it.
     bool direct_lighting = false;
     bool render_used_direct = false;    // extension: the last render's samples came from the direct-light integrator
+    // extension: the direct-light integrator also importance-samples the HDR environment map (zr_accum_set_direct_env).  Takes effect only
+    // together with direct_lighting; where the environment has no map to sample the render is direct_lighting's.  render_used_direct_env says whether the
+    // switch was set on the last render's accumulator.
+    bool direct_environment = false;
+    bool render_used_direct_env = false;
     // extension: the temporal history follows a moving world (zr_temporal_track_motion).  Takes effect together with temporal_accumulation and
     // reuse_scene: the camera switches tracking on in the history it keeps, and keeps that history across a frame whose scene was refitted
     // (last_scene_refit == 1) although the `world` argument is a new object — the refit's motion table reprojects the moved objects' pixels.  Every other case
@@ -1670,7 +1675,7 @@ public:
                 half_a_.clear(); half_b_.clear(); denoise_error_buffer.clear(); denoise_used_nlm = false;
                 temporal_buffer.clear(); temporal_history_length.clear();
                 resolve_used_robust = false; robust_variance_.clear();
-                render_used_direct = false;
+                render_used_direct = false; render_used_direct_env = false;
                 direct_now_ = direct_lighting && !debug && !(use_reflection || use_refraction);
                 if (direct_lighting && !debug && !direct_now_)
                     std::cerr << "[zenith] direct_lighting ignored: the reflection / refraction split replays the plain integrator's paths\n";
@@ -1788,8 +1793,12 @@ private:
     int bind_direct(zr_accum* acc) {
         if (!direct_now_) return ZR_OK;
         const zr_direct_params dp{ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN, 0};
-        const int rc = zr_accum_set_direct(acc, &dp);
+        int rc = zr_accum_set_direct(acc, &dp);
         render_used_direct = rc == ZR_OK;
+        if (rc == ZR_OK && direct_environment) {
+            rc = zr_accum_set_direct_env(acc, 1);
+            render_used_direct_env = rc == ZR_OK;
+        }
         return rc;
     }
     // the non-local-means filter has been asked for and can run: the blend of temporal_accumulation has no half images

@@ -964,6 +964,54 @@ int zr_kat_light_pdf(zr_ctx*, const zr_scene*, const zr_env*, const zr_direct_pa
                      uint64_t* out_key);
 uint64_t zr_kat_light_key(uint64_t key, uint32_t bounce);   /* zr_light_key of zr_rng.h, for bindings */
 
+/* ---- direct light sampling of the HDR environment map, opt-in on top of the above -----------------------------------
+ * The third kind of light: with ZR_ENV_HDR_MAP the map itself is importance-sampled.  The lookup reads the nearest texel, so radiance is constant over
+ * texel cells: row j covers theta in [j pi / H, (j + 1) pi / H), column i covers atan2(z, x) in -pi + 2 pi [i, i + 1) / W in map space (the direction after
+ * the environment's yaw, tilt and roll), and a cell of row j has the solid angle omega_j = (2 pi / W)(cos(j pi / H) - cos((j + 1) pi / H)).
+ *   Sampled when     env.mode == ZR_ENV_HDR_MAP, hdr_texture names a ZR_TEX_IMAGE_F32 or ZR_TEX_IMAGE_U8 texture of W x H > 0 texels, intensity is finite
+ *                    and > 0, and T (below) is finite and > 0.  Otherwise nothing of the environment is sampled and every miss keeps weight 1; that is no
+ *                    error, except that a map of more than ZR_DIRECT_ENV_MAX_TEXELS texels is refused (ZR_E_INVALID).
+ *   The table        w_ji = lum(c_ji) omega_j with c_ji the texel's colour at intensity 1 and lum as above; a weight that is zero, negative or not finite
+ *                    counts as 0.  cdf[j][i] = the FP64 running sum of row j's weights (from zero in every row), row_cdf[j] = the running sum of the rows'
+ *                    totals, T = row_cdf[H - 1].  Summation order of a row: 256 chunks of c = ceil(W / 256) consecutive columns, each summed left to
+ *                    right from zero; the chunk sums' running sum in index order gives each chunk's offset; an entry is offset + the chunk's running sum.
+ *                    Built on the device at the first use and kept per (commit, texture): rotation, intensity and refits do not enter it.
+ *   Draws            on the vertex's light stream: emitter-or-map first (only when both are sampled: u < 0.5 takes an emitter; each then has P = 1/2), then
+ *                    u_r (the first row with row_cdf[j] > u_r T), u_c (the first column with cdf[j][i] > u_c cdf[j][W - 1]; either search takes the last
+ *                    entry when none exceeds), u_a: cos theta = cos(j pi / H) - u_a (cos(j pi / H) - cos((j + 1) pi / H)), u_b: phi = -pi + 2 pi (i + u_b) / W.
+ *                    Map-space direction (sin theta cos phi, cos theta, sin theta sin phi), taken to the world by the inverse roll, tilt, yaw.
+ *   The sample       pdf_w = P lum(c_ji) / T (0 on a texel without weight), radiance c_ji x intensity (the chosen texel's, not a second lookup), dist = +inf;
+ *                    the shadow query is the sun's: it sees the sample iff it misses.
+ *   The miss         of a scattered ray whose vertex took a D: all of the background colour bg is weighted by p_b / (p_b + p_l),
+ *                    p_l = P lum(bg) / (intensity T), 0 where that is not finite and positive.
+ * zr_accum_set_direct_env   switches it on (on != 0) or off for an accumulator.  ZR_E_STATE unless the accumulator is empty and a direct integrator is bound;
+ *                           zr_accum_reset keeps it, zr_accum_set_direct(NULL) clears it.  Where nothing of the environment is sampled the accumulator
+ *                           renders exactly as without it.
+ * zr_render_direct_env      zr_accum_create -> zr_accum_set_direct -> zr_accum_set_direct_env(1) -> zr_render_accumulate -> zr_accum_resolve, bit for bit
+ * zr_scene_env_light        the table of (scene, env): *info; row_cdf (H doubles) and cdf (W x H doubles, row-major), each may be NULL, are written when
+ *                           info->sampled
+ * zr_kat_env_light_sample   zr_kat_light_sample with the environment on: choice 3 = the map, slot = j W + i, kind and index all ones, y and normal zero
+ * zr_kat_env_light_pdf      the density a missed ray of direction dirs3[k] (any length) is weighted by
+ * zr_get_direct_env_stats   of the last counted direct batch: shadow queries towards the map, and those that saw it
+ * Refusals come before any device call and zr_last_error names the argument. */
+#define ZR_DIRECT_ENV_MAX_TEXELS (1u << 25)
+typedef struct zr_env_light_info {
+    uint32_t width, height;   /* of the map (0 x 0: the environment has no image map) */
+    uint32_t sampled, pad_;   /* 1: the map is sampled */
+    double total;             /* T */
+    uint64_t weighted;        /* texels with weight */
+    double build_ms;          /* device time of the kernel that built the table, when it was built */
+} zr_env_light_info;
+int zr_accum_set_direct_env(zr_accum*, int on);
+int zr_accum_get_direct_env(const zr_accum*, int* on);
+int zr_render_direct_env(zr_ctx*, const zr_scene*, const zr_camera*, const zr_env*, uint64_t seed, const zr_region* region, const zr_direct_params*,
+                         int collect_counters, double* out_rgb);
+int zr_scene_env_light(zr_ctx*, const zr_scene*, const zr_env*, zr_env_light_info* info, double* row_cdf /* H or NULL */, double* cdf /* W x H or NULL */);
+int zr_kat_env_light_sample(zr_ctx*, const zr_scene*, const zr_env*, const zr_direct_params*, const double* origins3, const uint64_t* keys,
+                            const uint32_t* bounces, const double* draws8, size_t n, zr_light_sample* out);
+int zr_kat_env_light_pdf(zr_ctx*, const zr_scene*, const zr_env*, const zr_direct_params*, const double* dirs3, size_t n, double* out_pdf);
+int zr_get_direct_env_stats(zr_ctx*, uint64_t* env_queries, uint64_t* env_visible);
+
 #ifdef __cplusplus
 }
 #endif

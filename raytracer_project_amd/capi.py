@@ -180,6 +180,15 @@ LIGHT_SAMPLE_DTYPE = np.dtype([("choice", "<u4"), ("slot", "<u4"), ("kind", "<u4
                                ("normal", "<f8", 3), ("w", "<f8", 3), ("dist", "<f8"), ("pdf", "<f8")])
 
 
+DIRECT_ENV_MAX_TEXELS = 1 << 25
+
+
+class EnvLightInfo(C.Structure):
+    """zr_env_light_info: the environment table of a scene and an environment (include/zr_capi.h)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("sampled", C.c_uint32), ("pad_", C.c_uint32), ("total", C.c_double), ("weighted", C.c_uint64),
+                ("build_ms", C.c_double)]
+
+
 class BvhDebugParams(_Defaults, C.Structure):
     """zr_bvh_debug_params: global_settings::debug_bvh_level / bvh_thickness of the BVH debug view (include/zr_capi.h, DESIGN §10)"""
     _fields_ = [("level", C.c_int32), ("thickness", C.c_float)]
@@ -302,6 +311,7 @@ CAPI_SYMBOLS = [
     "zr_render_bvh_debug", "zr_trace_bvh_debug", "zr_scene_tree_boxes", "zr_get_counters", "zr_last_presolved_pixels", "zr_last_round_loop", "zr_last_shade_builds", "zr_last_extend_fetches",
     "zr_get_kernel_times", "zr_trace", "zr_kat_scatter", "zr_kat_shade_lean", "zr_kat_texture", "zr_kat_background", "zr_kat_camera_rays", "zr_comm_unique_id", "zr_comm_create", "zr_comm_reduce_frame", "zr_comm_gather_frame", "zr_comm_destroy",
     "zr_accum_set_direct", "zr_accum_get_direct", "zr_render_direct", "zr_get_direct_stats", "zr_scene_lights", "zr_kat_light_sample", "zr_kat_light_pdf", "zr_kat_light_key",
+    "zr_accum_set_direct_env", "zr_accum_get_direct_env", "zr_render_direct_env", "zr_scene_env_light", "zr_kat_env_light_sample", "zr_kat_env_light_pdf", "zr_get_direct_env_stats",
 ]
 
 
@@ -415,6 +425,14 @@ def load():
         lib.zr_kat_light_sample.argtypes = [vp, vp, C.POINTER(Env), C.POINTER(DirectParams), vp, vp, vp, vp, C.c_size_t, vp]
         lib.zr_kat_light_pdf.argtypes = [vp, vp, C.POINTER(Env), C.POINTER(DirectParams), vp, vp, C.c_size_t, vp, vp]
         lib.zr_kat_light_key.restype = u64; lib.zr_kat_light_key.argtypes = [u64, C.c_uint32]
+    if hasattr(lib, "zr_render_direct_env"):
+        lib.zr_accum_set_direct_env.argtypes = [vp, i32]
+        lib.zr_accum_get_direct_env.argtypes = [vp, C.POINTER(i32)]
+        lib.zr_render_direct_env.argtypes = [vp, vp, C.POINTER(Camera), C.POINTER(Env), u64, C.POINTER(Region), C.POINTER(DirectParams), i32, vp]
+        lib.zr_scene_env_light.argtypes = [vp, vp, C.POINTER(Env), C.POINTER(EnvLightInfo), vp, vp]
+        lib.zr_kat_env_light_sample.argtypes = [vp, vp, C.POINTER(Env), C.POINTER(DirectParams), vp, vp, vp, vp, C.c_size_t, vp]
+        lib.zr_kat_env_light_pdf.argtypes = [vp, vp, C.POINTER(Env), C.POINTER(DirectParams), vp, C.c_size_t, vp]
+        lib.zr_get_direct_env_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     lib.zr_comm_unique_id.argtypes = [vp]
     lib.zr_comm_create.restype = vp; lib.zr_comm_create.argtypes = [vp, i32, i32, vp]
     lib.zr_comm_reduce_frame.argtypes = [vp, vp, C.c_size_t, i32, vp]
@@ -448,6 +466,8 @@ def load_scenes():
     s.zrs_render_dropin_robust.argtypes = frame + [C.c_double, C.c_double, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     if hasattr(s, "zrs_render_dropin_direct"):
         s.zrs_render_dropin_direct.argtypes = frame + [i32, i32, i32, vp, vp]
+    if hasattr(s, "zrs_render_dropin_direct_env"):
+        s.zrs_render_dropin_direct_env.argtypes = frame + [i32, i32, i32, vp, vp]
     s.zrs_render_dropin_threads.argtypes = frame + [i32, vp]
     s.zrs_render_dropin_denoise.argtypes = frame + [i32] + [vp] * 6
     s.zrs_render_dropin_denoise_guided.argtypes = frame + [C.c_double, i32, i32] + [vp] * 4
@@ -590,6 +610,15 @@ class DemoScene:
         self._rendered(load_scenes().zrs_render_dropin_direct(self._h, width, height, spp, device, 1 if on else 0, 1 if split else 0, samples_per_pass, out.ctypes.data,
                                                               info) == 0)
         return out, bool(info[0]), int(info[1])
+
+    def render_dropin_direct_env(self, on=True, env=True, samples_per_pass=0, width=0, height=0, spp=0, device=0):
+        """camera::render with camera::direct_lighting = on and camera::direct_environment = env (DESIGN §21)
+        -> (frame, render_used_direct, render_used_direct_env, passes)"""
+        out = self._frames(width, height, "out")["out"]
+        info = (C.c_int * 3)(0, 0, 0)
+        self._rendered(load_scenes().zrs_render_dropin_direct_env(self._h, width, height, spp, device, 1 if on else 0, 1 if env else 0, samples_per_pass,
+                                                                  out.ctypes.data, info) == 0)
+        return out, bool(info[0]), bool(info[2]), int(info[1])
 
     def render_dropin_threads(self, n, width=0, height=0, spp=0, device=0):
         """n drop-in renders, each on a fresh host thread, one after the other (the reference's render-restart pattern,
@@ -849,6 +878,43 @@ class Context:
         _check(self.lib.zr_kat_light_pdf(self._c, scene._s, C.byref(env), C.byref(params), o.ctypes.data, d.ctypes.data, len(o), pdf.ctypes.data, key.ctypes.data))
         return pdf, key
 
+    # ---- direct light sampling of the HDR environment map ----
+    def render_direct_env(self, scene, camera, env, seed, params=None, region=None, count=False, out=None):
+        """zr_render_direct_env: render_direct with the environment map sampled too — Accumulator + set_direct + set_direct_env + accumulate + resolve, bit for bit"""
+        params = params if params is not None else DirectParams.defaults()
+        out, = _like((camera.image_height, camera.image_width, 3), "the camera's frame", outs=(out,))
+        _check(self.lib.zr_render_direct_env(self._c, scene._s, C.byref(camera), C.byref(env), C.c_uint64(seed), C.byref(region) if region is not None else None,
+                                             C.byref(params), 1 if count else 0, out.ctypes.data))
+        return out
+
+    def direct_env_stats(self):
+        """zr_get_direct_env_stats -> dict: shadow queries towards the environment map of the last counted direct batch, and those that saw it"""
+        q, v = C.c_uint64(0), C.c_uint64(0)
+        _check(self.lib.zr_get_direct_env_stats(self._c, C.byref(q), C.byref(v)))
+        return {"env_queries": int(q.value), "env_visible": int(v.value)}
+
+    def kat_env_light_sample(self, scene, env, origins, keys, bounces, params=None, draws=None):
+        """zr_kat_env_light_sample: kat_light_sample with the environment on (choice 3: the map, slot = j W + i) -> array of LIGHT_SAMPLE_DTYPE"""
+        params = params if params is not None else DirectParams.defaults()
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        b = np.ascontiguousarray(bounces, dtype=np.uint32).reshape(-1)
+        d = np.ascontiguousarray(draws, dtype=np.float64).reshape(-1, 8) if draws is not None else None
+        if len(k) != len(o) or len(b) != len(o) or (d is not None and len(d) != len(o)):
+            raise ValueError("origins, keys, bounces and draws must have one row per query")
+        out = np.zeros(len(o), dtype=LIGHT_SAMPLE_DTYPE)
+        _check(self.lib.zr_kat_env_light_sample(self._c, scene._s, C.byref(env), C.byref(params), o.ctypes.data, k.ctypes.data, b.ctypes.data, _ptr(d), len(o),
+                                                out.ctypes.data))
+        return out
+
+    def kat_env_light_pdf(self, scene, env, dirs, params=None):
+        """zr_kat_env_light_pdf: the density a missed ray of each direction (any length) is weighted by -> (n,) float64"""
+        params = params if params is not None else DirectParams.defaults()
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        pdf = np.zeros(len(d))
+        _check(self.lib.zr_kat_env_light_pdf(self._c, scene._s, C.byref(env), C.byref(params), d.ctypes.data, len(d), pdf.ctypes.data))
+        return pdf
+
     def presolved_pixels(self):
         """pixels the last render finished in the sky pre-pass (zr_last_presolved_pixels); 0 for every other path"""
         return int(self.lib.zr_last_presolved_pixels(self._c))
@@ -922,6 +988,17 @@ class Accumulator:
         p = DirectParams()
         _check(self.lib.zr_accum_get_direct(self._a, C.byref(p)))
         return int(p.flags) if p.pad_ else None
+
+    def set_direct_env(self, on=True):
+        """zr_accum_set_direct_env: the bound direct-light integrator also samples the HDR environment map; needs an empty accumulator with an
+        integrator bound"""
+        _check(self.lib.zr_accum_set_direct_env(self._a, 1 if on else 0))
+
+    def get_direct_env(self):
+        """zr_accum_get_direct_env -> bool"""
+        on = C.c_int32(0)
+        _check(self.lib.zr_accum_get_direct_env(self._a, C.byref(on)))
+        return bool(on.value)
 
     def render_adaptive(self, scene, camera, env, seed, params, count=False, keep_going=None):
         """zr_render_adaptive: every pixel to params.min_samples, then params.step_samples more per pass for the pixels whose noise estimate is
@@ -1152,6 +1229,19 @@ class Scene:
         m = self.lib.zr_scene_lights(self.ctx._c, self._s, out.ctypes.data if n else None, n)
         if m < 0:
             _check(m)
+        return out
+
+    def env_light(self, env, arrays=True):
+        """zr_scene_env_light: the environment table direct light sampling draws from under `env` -> dict: width, height, sampled, total, weighted,
+        build_ms and, where it is sampled and arrays is set, row_cdf (H,) and cdf (H, W)"""
+        info = EnvLightInfo()
+        _check(self.lib.zr_scene_env_light(self.ctx._c, self._s, C.byref(env), C.byref(info), None, None))
+        out = {"width": int(info.width), "height": int(info.height), "sampled": bool(info.sampled), "total": float(info.total), "weighted": int(info.weighted),
+               "build_ms": float(info.build_ms)}
+        if info.sampled and arrays:
+            row, cdf = np.zeros(info.height), np.zeros((info.height, info.width))
+            _check(self.lib.zr_scene_env_light(self.ctx._c, self._s, C.byref(env), C.byref(info), row.ctypes.data, cdf.ctypes.data))
+            out["row_cdf"], out["cdf"] = row, cdf
         return out
 
     def kernels(self):

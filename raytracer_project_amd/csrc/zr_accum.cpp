@@ -407,7 +407,22 @@ int zr_accum_set_direct(zr_accum* a, const zr_direct_params* dp) {
     if (dp) { if (int rc = check_direct_params(dp)) return rc; }   // the parameters first: they need no device and no other argument
     if (!a) return fail(ZR_E_INVALID, "null argument: accumulator");
     if (a->st.done != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel: zr_accum_set_direct binds an integrator to an empty one (zr_accum_reset)", a->st.done);
-    a->st.direct = dp ? (0x80000000u | dp->flags) : 0u;
+    a->st.direct = dp ? (0x80000000u | dp->flags | (a->st.direct & kDirectEnv)) : 0u;   // (unbinding clears zr_accum_set_direct_env's switch, rebinding keeps it)
+    return ZR_OK;
+}
+
+int zr_accum_set_direct_env(zr_accum* a, int on) {
+    if (!a) return fail(ZR_E_INVALID, "null argument: accumulator");
+    if (a->st.done != 0) return fail(ZR_E_STATE, "the accumulator holds %d samples per pixel: zr_accum_set_direct_env needs an empty one (zr_accum_reset)", a->st.done);
+    if (!a->st.direct) return fail(ZR_E_STATE, "no direct-light integrator is bound to the accumulator: zr_accum_set_direct comes first");
+    a->st.direct = on ? (a->st.direct | kDirectEnv) : (a->st.direct & ~kDirectEnv);
+    return ZR_OK;
+}
+
+int zr_accum_get_direct_env(const zr_accum* a, int* on) {
+    if (!a) return fail(ZR_E_INVALID, "null argument: accumulator");
+    if (!on) return fail(ZR_E_INVALID, "null argument: on");
+    *on = (a->st.direct & kDirectEnv) ? 1 : 0;
     return ZR_OK;
 }
 

@@ -3,6 +3,7 @@
 // zr_render_direct, the statistics and the known-answer entries.  The accumulator's own entries (zr_accum_set_direct / _get_direct) live in zr_accum.cpp.
 #include "zr_frame.h"
 #include "zr_light.h"
+#include "zr_envlight.h"
 
 namespace zr_host {
 
@@ -102,6 +103,20 @@ int kat_ready(zr_ctx* c, const zr_scene* s, const zr_env* env, const zr_direct_p
 
 }  // namespace
 
+int direct_tables(zr_ctx* c, const zr_scene* s, uint32_t direct, const zr::DEnv& de, zr::LightTable& lt, zr::EnvLight& el, uint64_t* slots, uint64_t* objects) {
+    const LightCache* lc = nullptr;
+    if (int rc = scene_lights(c, s, &lc)) return rc;
+    lt = make_light_table(*lc, direct & (ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN), de);
+    el = zr::EnvLight{};
+    if (direct & kDirectEnv) {
+        if (int rc = scene_env_light(c, s, de, el)) return rc;
+        if (el.on) { el.p_choice = lt.n ? 0.5 : 1.0; lt.p_choice = el.p_choice; }   // (a map and the sun are different modes: lt.sun is 0 here)
+    }
+    if (slots) *slots = lc->slots.size();
+    if (objects) *objects = lc->objects;
+    return ZR_OK;
+}
+
 int check_direct_params(const zr_direct_params* dp) {
     if (!dp) return fail(ZR_E_INVALID, "null argument: params");
     if (dp->flags & ~(ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN)) return fail(ZR_E_INVALID, "params.flags = 0x%x holds bits outside ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN", dp->flags);
@@ -111,9 +126,9 @@ int check_direct_params(const zr_direct_params* dp) {
 int render_direct_samples(zr_ctx* c, const zr_scene* s, FrameJob& job, const uint32_t* pixels, uint32_t n_pix, int sample0, int n, HostTimer& timer) {
     const uint64_t units = (uint64_t)n_pix * (uint64_t)n;
     if (units > (1ull << 37)) return fail(ZR_E_NOMEM, "a batch of %d samples is %llu samples of radiance: ask for fewer", n, (unsigned long long)units);
-    const LightCache* lc = nullptr;
-    if (int rc = scene_lights(c, s, &lc)) return rc;
-    const zr::LightTable lt = make_light_table(*lc, job.direct & (ZR_DIRECT_EMITTERS | ZR_DIRECT_SUN), job.de);
+    zr::LightTable lt; zr::EnvLight el;
+    uint64_t slots = 0, objects = 0;
+    if (int rc = direct_tables(c, s, job.direct, job.de, lt, el, &slots, &objects)) return rc;
     if (c->d_partial.n < units * 3) {
         HIP_OK(hipStreamSynchronize(job.stream));
         if (c->d_partial.alloc(units * 3) != ZR_OK) return fail(ZR_E_NOMEM, "no device memory for the per-sample radiance buffer (%zu bytes): ask for fewer samples", (size_t)units * 3 * sizeof(double));
@@ -121,9 +136,9 @@ int render_direct_samples(zr_ctx* c, const zr_scene* s, FrameJob& job, const uin
     c->last_path = 0;
     if (c->pending.size() > 4096) { int rr = resolve_times(c); if (rr) return rr; }
     c->render_id++; c->last_stream = job.stream; c->last_counted = job.count;
-    c->direct_slots = lc->slots.size(); c->direct_objects = lc->objects; c->direct_render = c->render_id;
+    c->direct_slots = slots; c->direct_objects = objects; c->direct_render = c->render_id;
     timer.begin(job.stream, 1);
-    HIP_OK(zr::launch_direct_samples(s->ds, job.dc, job.de, lt, job.seed, pixels, n_pix, (uint32_t)sample0, (uint32_t)n, c->d_partial.p, c->d_ctr.p, job.count, job.stream));
+    HIP_OK(zr::launch_direct_samples(s->ds, job.dc, job.de, lt, el, job.seed, pixels, n_pix, (uint32_t)sample0, (uint32_t)n, c->d_partial.p, c->d_ctr.p, job.count, job.stream));
     timer.end(job.stream, 1);
     if (job.keep_going) {
         HIP_OK(hipStreamSynchronize(job.stream));

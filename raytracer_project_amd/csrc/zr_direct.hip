@@ -9,6 +9,7 @@
 #include "zr_device.h"
 #include "zr_launch.h"
 #include "zr_light.h"
+#include "zr_envlight.h"
 
 // Compiled twice like zr_kernels.hip: as itself for scenes whose triangles carry no texture coordinates, and from zr_direct_uv.hip (ZR_UV 1, namespace
 // zr::uvbuild) for those that do.  The table and known-answer kernels read no coordinates and exist once.
@@ -20,12 +21,12 @@ namespace zr { namespace uvbuild {
 #else
 namespace zr {
 namespace uvbuild {   // zr_direct_uv.hip
-hipError_t launch_direct_samples(const DScene& sc, const DCamera& cam, const DEnv& env, const LightTable& lt, uint64_t seed, const uint32_t* pixels, uint32_t n_pix,
-                                 uint32_t sample0, uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream);
+hipError_t launch_direct_samples(const DScene& sc, const DCamera& cam, const DEnv& env, const LightTable& lt, const EnvLight& el, uint64_t seed, const uint32_t* pixels,
+                                 uint32_t n_pix, uint32_t sample0, uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream);
 }
 #endif
 
-struct DirectCtr { uint32_t shadow, visible, sun; };
+struct DirectCtr { uint32_t shadow, visible, sun, env, env_visible; };
 
 // the sun term of background() (zr_device.h) alone: what the cone sample gathers and what a scattered ray's miss is weighted on
 __device__ inline V3 sun_term(const DEnv& env, V3 rd) {
@@ -39,8 +40,10 @@ __device__ inline V3 sun_term(const DEnv& env, V3 rd) {
 
 // D of one vertex, without the path's throughput: albedo-free f cos Le / (pdf_w + p_b) of one light sample seen from the scattered ray's origin.
 // p_next: the density with which scatter() drew the direction it did, for the weight of whatever that ray finds.
-__device__ inline V3 direct_term(const DScene& sc, const DEnv& env, const LightTable& lt, const Rec& rec, const Ray& out, const Rng& g, uint32_t* stack, int stride,
-                                 DirectCtr& dc, double& p_next) {
+// ENV: the environment table el may be sampled too; without it the function is what it was.
+template <bool ENV>
+__device__ inline V3 direct_term(const DScene& sc, const DEnv& env, const LightTable& lt, const EnvLight& el, const Rec& rec, const Ray& out, const Rng& g, uint32_t* stack,
+                                 int stride, DirectCtr& dc, double& p_next) {
     const zr_material& m = sc.mats[rec.mat];
     const bool iso = m.kind == ZR_MAT_ISOTROPIC;
     const double INV_PI = 0.31830988618379067154, INV_4PI = 0.079577471545947667884;
@@ -49,23 +52,29 @@ __device__ inline V3 direct_term(const DScene& sc, const DEnv& env, const LightT
     p_next = iso ? INV_4PI : fmax(0.0, dot(wn, unit(out.d))) * INV_PI;
     LightRng lg; lg.key = zr_light_key(g.key, g.bounce); lg.j = 0; lg.forced = nullptr;
     LightSample s;
-    light_sample(lt, out.o, lg, s);
+    V3 le_env = mk(0, 0, 0);
+    if (ENV) direct_light_sample(sc, env, lt, el, out.o, lg, s, le_env); else light_sample(lt, out.o, lg, s);
     if (!(s.pdf > 0)) return mk(0, 0, 0);
     const double p_b = iso ? INV_4PI : fmax(0.0, dot(wn, s.w)) * INV_PI;   // = f cos / albedo
     if (!(p_b > 0)) return mk(0, 0, 0);
     Ray sr; sr.o = out.o; sr.d = s.w;
     Rng gs; gs.key = g.key; gs.k = 0; gs.bounce = g.bounce | 0x80000000u;
-    const bool sun = s.choice == 2;
+    const bool sun = s.choice == 2, sky = ENV && s.choice == 3;   // sky: a direction of the environment map, seen iff the query misses, like the sun's
     const double tol = ZR_DIRECT_T_TOL * fmax(1.0, s.dist);
     Counters none = {0, 0, 0, 0, 0};
     double t; uint32_t kind, idx;
     dc.shadow++;
     if (sun) dc.sun++;
-    const bool h = closest_hit<false>(sc, sr, 0.001, gs, stack, stride, t, kind, idx, none, sun ? __builtin_huge_val() : s.dist + tol);
+    if (sky) dc.env++;
+    const bool h = closest_hit<false>(sc, sr, 0.001, gs, stack, stride, t, kind, idx, none, sun || sky ? __builtin_huge_val() : s.dist + tol);
     V3 le;
     if (sun) {
         if (h) return mk(0, 0, 0);
         le = sun_term(env, s.w);
+    } else if (sky) {
+        if (h) return mk(0, 0, 0);
+        le = le_env;   // the chosen texel's colour, not a second lookup of the direction
+        dc.env_visible++;
     } else {
         if (!h || kind != s.kind || idx != s.index || !(fabs(t - s.dist) <= tol)) return mk(0, 0, 0);
         Rec lr;
@@ -77,14 +86,14 @@ __device__ inline V3 direct_term(const DScene& sc, const DEnv& env, const LightT
 }
 
 // radiance of one primary sample: sample_radiance + path_radiance (zr_kernels.hip) as one loop, b = path_radiance's loop index (-1: the peeled camera vertex)
-template <bool COUNT>
-__device__ inline V3 direct_radiance(const DScene& sc, const DCamera& cam, const DEnv& env, const LightTable& lt, int i, int j, Rng& g, uint32_t* stack, int stride,
-                                     Counters& ctr, uint32_t& segments, uint32_t& hits, DirectCtr& dc) {
+template <bool COUNT, bool ENV>
+__device__ inline V3 direct_radiance(const DScene& sc, const DCamera& cam, const DEnv& env, const LightTable& lt, const EnvLight& el, int i, int j, Rng& g, uint32_t* stack,
+                                     int stride, Counters& ctr, uint32_t& segments, uint32_t& hits, DirectCtr& dc) {
     Ray cur = camera_ray(cam, i, j, g);
     V3 L0 = mk(0, 0, 0), att0 = mk(1, 1, 1);   // the camera vertex: ray_color_from_hit's emitted + attenuation * ray_color
     V3 L = mk(0, 0, 0), beta = mk(1, 1, 1);
     const int depth = cam.max_depth - 1;
-    const bool sampling = lt.n != 0 || lt.sun != 0;
+    const bool sampling = lt.n != 0 || lt.sun != 0 || (ENV && el.on != 0);
     bool took = false, missed = false;   // took: the vertex before took a D, with p_b the density of the direction it scattered into
     double p_b = 0;
     for (int b = -1;;) {
@@ -108,7 +117,7 @@ __device__ inline V3 direct_radiance(const DScene& sc, const DCamera& cam, const
         took = false;
         const uint32_t mk_ = sc.mats[rec.mat].kind;
         if (sampling && (mk_ == ZR_MAT_LAMBERTIAN || mk_ == ZR_MAT_ISOTROPIC) && b + 1 < depth) {   // a next segment exists: the plain path could still see light there
-            L = L + beta * direct_term(sc, env, lt, rec, out, g, stack, stride, dc, p_b);
+            L = L + beta * direct_term<ENV>(sc, env, lt, el, rec, out, g, stack, stride, dc, p_b);
             took = true;
         }
         cur = out;
@@ -129,15 +138,19 @@ __device__ inline V3 direct_radiance(const DScene& sc, const DCamera& cam, const
             const double p_l = light_pdf_sun(lt, cur.d);
             if (p_l > 0) bg = bg - (p_l / (p_b + p_l)) * sun_term(env, cur.d);   // sky + w sun
         }
+        if (ENV && took && el.on) {
+            const double p_l = env_light_pdf(el, bg);   // read from the colour the lookup returned: no reverse lookup
+            if (p_l > 0) bg = bg * (p_b / (p_b + p_l));
+        }
         L = L + beta * bg;
     }
     return L0 + att0 * L;
 }
 
-template <bool COUNT>
-__global__ __launch_bounds__(ZR_BLOCK) void render_direct_samples(DScene sc, DCamera cam, DEnv env, LightTable lt, uint64_t seed, const uint32_t* __restrict__ pixels,
-                                                                   uint32_t n_pix, uint32_t sample0, uint32_t n, double* __restrict__ samples,
-                                                                   unsigned long long* __restrict__ gctr) {
+template <bool COUNT, bool ENV>
+__global__ __launch_bounds__(ZR_BLOCK) void render_direct_samples(DScene sc, DCamera cam, DEnv env, LightTable lt, EnvLight el, uint64_t seed,
+                                                                   const uint32_t* __restrict__ pixels, uint32_t n_pix, uint32_t sample0, uint32_t n,
+                                                                   double* __restrict__ samples, unsigned long long* __restrict__ gctr) {
     __shared__ uint32_t lds_stack[ZR_STACK_DEPTH * ZR_BLOCK];
     uint32_t* stack = lds_stack + threadIdx.x;
     const unsigned long long k = (unsigned long long)blockIdx.x * ZR_BLOCK + threadIdx.x;
@@ -146,10 +159,10 @@ __global__ __launch_bounds__(ZR_BLOCK) void render_direct_samples(DScene sc, DCa
     const uint32_t pk = pixels[i];
     const int px = (int)(pk & 0xFFFFu), py = (int)(pk >> 16);
     Counters ctr = {0, 0, 0, 0, 0};
-    DirectCtr dc = {0, 0, 0};
+    DirectCtr dc = {0, 0, 0, 0, 0};
     uint32_t segments = 0, hits = 0;
     Rng g; g.key = zr_stream_key(seed, (uint64_t)py * (uint64_t)cam.W + (uint64_t)px, (uint64_t)sample0 + sidx); g.k = 0; g.bounce = 0;
-    const V3 c = direct_radiance<COUNT>(sc, cam, env, lt, px, py, g, stack, ZR_BLOCK, ctr, segments, hits, dc);
+    const V3 c = direct_radiance<COUNT, ENV>(sc, cam, env, lt, el, px, py, g, stack, ZR_BLOCK, ctr, segments, hits, dc);
     double* o = samples + k * 3;
     o[0] = c.x; o[1] = c.y; o[2] = c.z;
     if (COUNT) {
@@ -165,20 +178,28 @@ __global__ __launch_bounds__(ZR_BLOCK) void render_direct_samples(DScene sc, DCa
         atomicAdd(&gctr[CTR_DIRECT_SHADOW], (unsigned long long)dc.shadow);
         atomicAdd(&gctr[CTR_DIRECT_VISIBLE], (unsigned long long)dc.visible);
         atomicAdd(&gctr[CTR_DIRECT_SUN], (unsigned long long)dc.sun);
+        if (ENV) {
+            atomicAdd(&gctr[CTR_DIRECT_ENV], (unsigned long long)dc.env);
+            atomicAdd(&gctr[CTR_DIRECT_ENV_VISIBLE], (unsigned long long)dc.env_visible);
+        }
     }
 }
 
-hipError_t launch_direct_samples(const DScene& sc, const DCamera& cam, const DEnv& env, const LightTable& lt, uint64_t seed, const uint32_t* pixels, uint32_t n_pix,
-                                 uint32_t sample0, uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream) {
+hipError_t launch_direct_samples(const DScene& sc, const DCamera& cam, const DEnv& env, const LightTable& lt, const EnvLight& el, uint64_t seed, const uint32_t* pixels,
+                                 uint32_t n_pix, uint32_t sample0, uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream) {
 #if !ZR_UV
-    if (sc.tri_uv_at) return uvbuild::launch_direct_samples(sc, cam, env, lt, seed, pixels, n_pix, sample0, n, samples, gctr, count, stream);
+    if (sc.tri_uv_at) return uvbuild::launch_direct_samples(sc, cam, env, lt, el, seed, pixels, n_pix, sample0, n, samples, gctr, count, stream);
 #endif
     const unsigned long long blocks = ((unsigned long long)n_pix * n + ZR_BLOCK - 1) / ZR_BLOCK;
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
     dim3 grid((unsigned)blocks), block(ZR_BLOCK);
-    if (count) hipLaunchKernelGGL(render_direct_samples<true>, grid, block, 0, stream, sc, cam, env, lt, seed, pixels, n_pix, sample0, n, samples, gctr);
-    else hipLaunchKernelGGL(render_direct_samples<false>, grid, block, 0, stream, sc, cam, env, lt, seed, pixels, n_pix, sample0, n, samples, gctr);
+    // the environment build runs only when a table is sampled: every other render goes through the kernel without it, whose frames are §20's bit for bit
+    if (el.on) {
+        if (count) hipLaunchKernelGGL((render_direct_samples<true, true>), grid, block, 0, stream, sc, cam, env, lt, el, seed, pixels, n_pix, sample0, n, samples, gctr);
+        else hipLaunchKernelGGL((render_direct_samples<false, true>), grid, block, 0, stream, sc, cam, env, lt, el, seed, pixels, n_pix, sample0, n, samples, gctr);
+    } else if (count) hipLaunchKernelGGL((render_direct_samples<true, false>), grid, block, 0, stream, sc, cam, env, lt, el, seed, pixels, n_pix, sample0, n, samples, gctr);
+    else hipLaunchKernelGGL((render_direct_samples<false, false>), grid, block, 0, stream, sc, cam, env, lt, el, seed, pixels, n_pix, sample0, n, samples, gctr);
     return hipGetLastError();
 }
 

@@ -35,7 +35,7 @@ struct FrameJob {
     double* d_out = nullptr; double* d_out2 = nullptr;   // device frames (d_out2: the refraction frame of the split's replay pass)
     volatile const uint8_t* keep_going = nullptr; volatile int* rows_done = nullptr;
     zr::StreamProgress* progress = nullptr;
-    uint32_t direct = 0;                              // an accumulator bound to the direct-light integrator (zr_accum_set_direct): 0x80000000 | its flags
+    uint32_t direct = 0;                              // an accumulator bound to the direct-light integrator (zr_accum_set_direct): 0x80000000 | its flags (| kDirectEnv)
     const uint32_t* d_list = nullptr; uint32_t n_list = 0;   // a device pixel list of the caller's (an adaptive pass: the active pixels) instead of the plan's cached one
     bool interactive() const { return keep_going || rows_done; }   // the caller polls: the tile-list paths need batch boundaries
 };
@@ -96,6 +96,8 @@ int env_frame(const zr_env& env, const zr_scene* s, zr::DEnv& de);
 // zr_direct.cpp, for zr_accum.cpp (render_batch_samples calls it): a batch of a direct-light accumulator — render_batch_samples' pixel-group branch
 // with the direct kernel; builds the scene's light table on first use
 int check_direct_params(const zr_direct_params* dp);
+// ... and DESIGN §21: kDirectEnv in FrameJob::direct / AccumState::direct asks for the environment map to be sampled too (zr_accum_set_direct_env)
+const uint32_t kDirectEnv = 0x40000000u;
 int render_direct_samples(zr_ctx* c, const zr_scene* s, FrameJob& job, const uint32_t* pixels, uint32_t n_pix, int sample0, int n, HostTimer& timer);
 // zr_temporal.cpp, for zr_accum.cpp (zr_accum_temporal calls them): the parameter check, what a call checks before any device work (its null tests aside),
 // and one frame taken from device memory (d_color / d_variance: W*H*3 doubles, complete on the context's stream)

@@ -8,6 +8,7 @@
 //                  kernel, pixel-group kernel), AOV / split passes, BVH debug view, counters, known-answer entry points
 //   zr_accum.cpp   the accumulator (zr_accum): a frame in batches of samples, adaptive sampling, the queries of what it holds, render_batched
 //   zr_direct.cpp  direct light sampling: the scene's light table, the batch driver of a direct accumulator, zr_render_direct, its known-answer entries
+//   zr_envlight.cpp  ... and of the HDR environment map: the environment table, zr_render_direct_env, its dump and known-answer entries
 //   zr_image.cpp   the image-space entry points, which need no scene: post stack, the two denoisers, sharpening, frame analysis
 //                  (these three share zr_frame.h: Plan, FrameJob, HostTimer and the drivers one of them calls in another)
 // Plain C++ (host compiler, -ffp-contract=off so that the camera frame and the sky constants are computed with exactly the reference's operation order,
@@ -141,6 +142,7 @@ struct zr_ctx {
 
 struct RefitState;   // zr_update.cpp
 namespace zr_host { struct LightCache; }   // zr_direct.cpp
+namespace zr_host { struct EnvLightCache; }   // zr_envlight.cpp
 
 struct zr_scene : SceneInput {   // the world as given (host side), then what the commit made of it
     zr_ctx* ctx = nullptr;
@@ -183,6 +185,7 @@ struct zr_scene : SceneInput {   // the world as given (host side), then what th
     uint64_t epoch = 0;                  // refits applied to this commit
     uint64_t serial = 0;                 // of this commit among all commits of the process (an epoch alone restarts at 0): what a tracking zr_temporal remembers
     mutable std::shared_ptr<zr_host::LightCache> lights;   // the light table of (serial, epoch), built by the first direct-light render that needs it
+    mutable std::shared_ptr<zr_host::EnvLightCache> env_light;   // the environment table of (serial, a texture), built by the first use that needs it; refits keep it
     std::shared_ptr<RefitState> refit;   // reverse indices, leaf boxes, the trees' schedule, device buffers: made by the first update or refit after a commit, dropped by the next
 };
 

@@ -24,6 +24,7 @@ enum { CTR_SAMPLES = 0, CTR_SEGMENTS = 1, CTR_NODES = 2, CTR_SPHERES = 3, CTR_TR
        CTR_HIST = 16, CTR_HIST_WORDS = 24,           // ZR_WAVE_PROFILE build only: EXTEND's per-phase lane histograms, [phase][8 buckets of 8 lanes]
        CTR_FETCH_CHECKED = 40, CTR_FETCH_SKIPPED = 41,   // the counting lean EXTEND: slots it fetched with / without testing their meta word (zr_last_extend_fetches)
        CTR_DIRECT_SHADOW = 42, CTR_DIRECT_VISIBLE = 43, CTR_DIRECT_SUN = 44,   // the counting direct-light kernel (zr_direct.hip): shadow queries, those that saw their sample, sun queries among them (zr_get_direct_stats)
+       CTR_DIRECT_ENV = 45, CTR_DIRECT_ENV_VISIBLE = 46,   // ... queries towards the environment map among them, and those that saw it (zr_get_direct_env_stats)
        CTR_BLOCK = 48 };
 // A -DZR_WAVE_PROFILE build (scripts/wave_profile.sh) runs uninstrumented renders and REUSES words of the block for EXTEND's wave statistics, read back
 // through the zr_counters fields of the words' product meaning (ZR_RAW_COUNTERS=1, scripts/wave_profile.py): phase p = 0 NODE, 1 LEAF, 2 FETCH

@@ -15,15 +15,16 @@ struct LightTable {
     uint32_t n;            // slots that are sampled: 0 when the table is empty or ZR_DIRECT_EMITTERS is off
     uint32_t sun;          // 1: the sun is sampled
     double total;          // sum of the slots' weights
-    double p_choice;       // 1/2 when both emitters and the sun are sampled, else 1
+    double p_choice;       // 1/2 when emitters and the sun (or the environment map) are both sampled, else 1
     double sun_dir[3], sun_t[3], sun_b[3], sun_thr, sun_pdf;   // sun_pdf = 1 / (2 pi (1 - sun_thr))
 };
 
 // zr_direct.hip.  launch_direct_samples: launch_render_samples (zr_launch.h) with light sampling.  launch_light_count: per block of 256 candidates (the
 // world-level spheres, triangles, cubes, placed cubes: n_cand of them) the slots its emitters make, scanned in place into block offsets, *total = their sum;
 // launch_light_emit then writes those slots, in table order, into out[0 .. cap).
-hipError_t launch_direct_samples(const DScene& sc, const DCamera& cam, const DEnv& env, const LightTable& lt, uint64_t seed, const uint32_t* pixels, uint32_t n_pix,
-                                 uint32_t sample0, uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream);
+struct EnvLight;   // zr_envlight.h: the environment table; on = 0 renders without it
+hipError_t launch_direct_samples(const DScene& sc, const DCamera& cam, const DEnv& env, const LightTable& lt, const EnvLight& el, uint64_t seed, const uint32_t* pixels,
+                                 uint32_t n_pix, uint32_t sample0, uint32_t n, double* samples, unsigned long long* gctr, bool count, hipStream_t stream);
 hipError_t launch_light_count(const DScene& sc, uint32_t n_cand, uint32_t* block_count, uint32_t* total, hipStream_t stream);
 hipError_t launch_light_emit(const DScene& sc, uint32_t n_cand, const uint32_t* block_offset, uint32_t cap, zr_light_slot* out, hipStream_t stream);
 hipError_t launch_kat_light_sample(const LightTable& lt, const double* origins, const uint64_t* keys, const uint32_t* bounces, const double* draws8, size_t n,

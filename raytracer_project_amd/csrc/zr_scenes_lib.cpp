@@ -126,6 +126,21 @@ int zrs_render_dropin_direct(void* p, int width, int height, int spp, int device
     return done ? 0 : -1;
 }
 
+// ... and with camera::direct_environment = env beside camera::direct_lighting = on.  info[0] = render_used_direct, info[1] = passes,
+// info[2] = render_used_direct_env.
+int zrs_render_dropin_direct_env(void* p, int width, int height, int spp, int device, int on, int env, int samples_per_pass, double* out, int* info) {
+    const handle& h = *(handle*)p;
+    scene_camera cam(h, width, height, spp, device);
+    cam.reset_accumulator();
+    cam.direct_lighting = on != 0;
+    cam.direct_environment = env != 0;
+    cam.samples_per_pass = samples_per_pass;
+    const bool done = render_world(h, cam, post_processor());
+    if (info) { info[0] = cam.render_used_direct ? 1 : 0; info[1] = cam.passes_rendered; info[2] = cam.render_used_direct_env ? 1 : 0; }
+    copy_out(cam.render_accumulator, out);
+    return done ? 0 : -1;
+}
+
 // camera::render with camera::adaptive_threshold set (min_samples and step <= 0 keep the camera's defaults) and render_flag = flag0 going in.  counts = W*H ints
 // (camera::sample_counts; left alone when the render left it empty), info[0] = current_samples_count after the render (-7 going in), info[1] = passes.  Returns 0,
 // or -1 if the render did not finish; `out`, `counts` and `info` are filled either way.
@@ -487,6 +502,7 @@ extern "C" size_t zrs_sizeof(int which) {
         case 23: return sizeof(zr_direct_stats);
         case 24: return sizeof(zr_light_slot);
         case 25: return sizeof(zr_light_sample);
+        case 26: return sizeof(zr_env_light_info);
         default: return 0;
     }
 }
